@@ -10,14 +10,27 @@ The K timed steps are issued as march calls of --substeps-per-march sub-timestep
 15-minute model timestep at dt = 45 s), as ThermalModel::march runs its dt_subdivisions sub-timesteps
 per call. Inside one call the library keeps zone-connected clusters of surfaces resident on the chip
 (cluster-resident march, include/heat_amd.h) where its planner expects a gain; --no-fusion streams
-every sub-timestep through HBM instead, and a second, shorter leg always measures that streamed kernel
+every sub-timestep through HBM instead. With --full a second, shorter leg measures that streamed kernel
 (`roofline_streaming`) so that the per-sub-timestep HBM roofline stays on record.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-With --config headline (the default) and one GPU the run goes on, after the headline, through the other BASELINE.json
+A plain run does only what its headline figure needs: it builds the workload, settles the chip's clock, marches W
+warmup and K timed sub-timesteps, writes the outputs when --dump-outputs is given, and prints the result line
+(`value`, `ms_per_step` = milliseconds per timed sub-timestep). --full adds everything else, as described below: HIP
+events in the timed region and the `roofline` they feed, the caller-owned and sub-timesteps-per-call measurements, the
+streamed leg, the CPU baseline, the other BASELINE configs and, for N > 1, the exchange leg.
+
+--dump-outputs DIR (one GPU) writes, after the timed steps, what the march left in the state after its last step: the
+arrays a caller of ThermalModel::march receives (node_temperatures, hs_front, hs_back, flow_front, flow_back,
+zone_temperatures) as DIR/<name>.npy in float64; an array longer than its cap in DUMP_CAPS is a fixed, seeded sample
+of its elements. The workload is seeded, and the initial state is uploaded again after the settle phase (whose length
+is set by the clock, not by the arguments), so the same arguments give the same inputs on every run.
+
+With --full, --config headline (the default) and one GPU the run goes on, after the headline, through the other BASELINE.json
 configs as short legs of their own — config 3 (1 M ragged mixed walls), config 5 (glazing + cavities; `5x10`: 1 M + 1 M
 of them), config 2 (10 000 identical walls), `partitions` (buildings of 8 rooms joined by interior walls) and
 `buildings40` (of 40 rooms: clusters larger than a workgroup, marched by teams of workgroups) — and attaches each as
@@ -25,8 +38,8 @@ of them), config 2 (10 000 identical walls), `partitions` (buildings of 8 rooms 
 (--no-configs skips them; `--config 3` etc. runs one of them as the main leg).
 
 N > 1 (BASELINE config 4) shards the SAME model over the ranks ("scaling": "strong"): heat_partition cuts it
-along its zone-connected clusters, so that no zone is shared and no collective is issued (the headline). A second,
-short leg then runs config 3, whose ring of zones is ONE cluster: it is cut by surface ranges and its cut zones are
+along its zone-connected clusters, so that no zone is shared and no collective is issued (the headline). With --full
+a second, short leg then runs config 3, whose ring of zones is ONE cluster: it is cut by surface ranges and its cut zones are
 exchanged with an RCCL all-gather per sub-timestep on the library's own communicator — `"exchange_leg"` reports
 n_shared_zones, collective, comm_ranks (and collective_fallback when the native communicator could not be had on
 every rank). `--scaling weak` gives every rank a model of its own with zones shared across the rank boundaries.
@@ -34,8 +47,10 @@ every rank). `--scaling weak` gives every rank a model of its own with zones sha
 Before the W warmup steps of every leg the batch marches untimed for --settle-ms (60 ms; `settle` in the line): the chip needs
 20-30 ms of load to reach the clock it then holds (tools/settle.py: the headline's sub-timestep goes 69.8 -> 64.4 us over the
 first 25 ms, and is back at 71 after two idle seconds) — a timed region of one march call would otherwise measure that ramp.
+On one GPU the initial state is then uploaded again and RESETTLE_CALLS fixed march calls keep the chip loaded across that
+upload (`settle.sub_timesteps_after_reset`), so the warmup and timed steps start from the same state on every run.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line; with --full it carries these extra objects:
   roofline            the dominant kernel against the resource that bounds it. Streamed march: "hbm" — algorithmic
                       bytes / kernel time (HIP events on the kernel's stream) against 8 TB/s. Cluster-resident march:
                       "valu_f64" — ALGORITHMIC f64 flops (40 per node-update) / kernel time against
@@ -235,6 +250,12 @@ def rocprof_kernel_us(counters_src, kernel_substr):
 SETTLE_NOTE = ("untimed march calls of the same workload before the W warmup steps: the chip takes 20-30 ms of load to reach "
                "the clock it then holds (tools/settle.py: 69.8 -> 64.4 us per sub-timestep of the headline over the first 25 ms; "
                "back to 71 after two idle seconds) — without them a short timed region measures the ramp, not the kernel")
+# single-GPU legs: after the settle the initial state is uploaded again (the settle's length is set by the clock, the
+# timed path's inputs must be set by the arguments), and this many march calls follow it: the upload leaves the chip
+# idle for about 6 ms, after which the headline's first 200 steps ran 1 % slower; a fixed count keeps the inputs fixed
+RESETTLE_CALLS = 20
+RESET_NOTE = ("; then the initial state is uploaded again and sub_timesteps_after_reset untimed sub-timesteps bridge the "
+              "upload, so that the W warmup and K timed steps start from the same state on every run")
 
 
 def settle(march, weather, sync, ms, n_calls=None):
@@ -253,6 +274,34 @@ def march_in_calls(march, weather, per_call):
     """K sub-timesteps as march calls of `per_call` sub-timesteps (ThermalModel::march = one call)."""
     for i in range(0, len(weather), per_call):
         march(weather[i:i + per_call])
+
+
+# --dump-outputs: most elements written per array (float64; 8 * (3 + 4 + 0.25) M = 58 MB at most in all)
+DUMP_CAPS = {"node_temperatures": 3_000_000, "hs_front": 1 << 20, "hs_back": 1 << 20, "flow_front": 1 << 20,
+             "flow_back": 1 << 20, "zone_temperatures": 250_000}
+DUMP_SEED = 20260402
+
+
+def dump_outputs(batch, md, state, out_dir):
+    """Downloads the batch's state and writes the outputs of ThermalModel::march as out_dir/<name>.npy (float64): the
+    whole array, or DUMP_CAPS[name] of its elements at sorted indices drawn with a fixed seed. Returns
+    {name: [written, total]}."""
+    from heat_amd import modeldict as mdl
+    got = state.copy()
+    batch.download_state(got)
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for i, (name, slots) in enumerate((("node_temperatures", mdl.node_slots(md)), ("hs_front", md["hs_front_slot"]),
+                                       ("hs_back", md["hs_back_slot"]), ("flow_front", md["flow_front_slot"]),
+                                       ("flow_back", md["flow_back_slot"]), ("zone_temperatures", md["zone_slot"]))):
+        slots = np.asarray(slots, dtype=np.int64)
+        total = len(slots)
+        if total > DUMP_CAPS[name]:
+            pick = np.random.default_rng(DUMP_SEED + i).choice(total, DUMP_CAPS[name], replace=False)
+            slots = slots[np.sort(pick)]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(got[slots], dtype=np.float64))
+        written[name] = [len(slots), total]
+    return written
 
 
 def issue_view(counters, per_sub, surf_us):
@@ -415,7 +464,14 @@ def single_gpu_leg(config, args, K, W, P, seed, local_rank, main, cpu_seconds):
             if torch_sync:
                 torch_sync()
 
-        settle_calls, settle_s = settle(batch.march_resident, mdl.weather_series(P, dt), barrier, args.settle_ms) if args.settle_ms > 0 else (0, 0.0)
+        weather_settle = mdl.weather_series(P, dt)
+        settle_calls, settle_s = settle(batch.march_resident, weather_settle, barrier, args.settle_ms) if args.settle_ms > 0 else (0, 0.0)
+        if settle_calls:
+            # the settle marched a clock-dependent number of calls: the timed path starts afresh from the initial state,
+            # after a fixed number of calls that bridge the upload's idle gap
+            batch.upload_state(state)
+            for _ in range(RESETTLE_CALLS):
+                batch.march_resident(weather_settle)
         if W > 0:
             march_in_calls(batch.march_resident, mdl.weather_series(W, dt), P)
         barrier()
@@ -432,18 +488,23 @@ def single_gpu_leg(config, args, K, W, P, seed, local_rank, main, cpu_seconds):
         elapsed = time.perf_counter() - t0
         surf_us, substep_us, n_samples = batch.get_timing()
         batch.set_timing(False)
+        dumped = dump_outputs(batch, md, state, args.dump_outputs) if (main and args.dump_outputs) else None
         ab = batch.algorithmic_bytes
         counts = batch.class_counts()
         n_fused = batch.n_fused_surfaces if not args.no_fusion else 0
         res = {"value": n_nodes * K / elapsed, "unit": "node-updates/s", "steps": K, "warmup": W,
                "ms_per_step": elapsed / K * 1e3, "sub_timesteps_per_sec": K / elapsed,
-               "settle": {"sub_timesteps": settle_calls * P, "ms": settle_s * 1e3, "note": SETTLE_NOTE},
+               "settle": {"sub_timesteps": settle_calls * P, "ms": settle_s * 1e3,
+                          "sub_timesteps_after_reset": RESETTLE_CALLS * P if settle_calls else 0,
+                          "note": SETTLE_NOTE + RESET_NOTE},
                "config": {"workload": workload + "; one step = one sub-timestep (iterate_surfaces + zone update)",
                           "config": config, "surfaces": int(md["n_surfaces"]), "nodes": n_nodes,
                           "zones": int(md["n_zones"]), "dt_s": dt, "substeps_per_march": P,
                           "surfaces_on_rank0": n_local, "kernel_classes_rank0[M4,M8,M16,small,general]": counts,
                           "surfaces_in_cluster_resident_march_rank0": n_fused, "n_shared_zones": 0,
                           "parallelism": "single GPU"}}
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if n_samples > 0 and fused:
             counters, src, stale = committed_counters(config, int(md["n_surfaces"]), n_nodes, "fused", P)
             res["roofline"] = fused_roofline(batch.n_nodes, n_nodes, P, surf_us, substep_us, n_samples, ab, counters, src, stale)
@@ -632,7 +693,18 @@ def main():
     ap.add_argument("--collective", choices=("native", "torch"), default="native",
                     help="sharded: library-owned RCCL communicator, all in one stream (default), or "
                          "torch.distributed.all_gather_into_tensor between the split-phase calls")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: HIP events and roofline, caller-owned state, streamed "
+                         "leg, CPU baseline, the other BASELINE configs (one GPU), the exchange leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (one GPU)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # a plain run: set up, warm up, time the K steps, dump, print
+        args.no_timing = args.no_extras = args.no_streaming_leg = args.no_cpu_baseline = True
+        args.no_configs = args.no_exchange_leg = True
 
     # stdout carries exactly one line, the JSON result: anything a library prints meanwhile (RCCL's version
     # banner under NCCL_DEBUG=VERSION goes to stdout) is sent to stderr instead.
@@ -652,6 +724,8 @@ def main():
     weak = args.scaling == "weak" and sharded
     if weak and args.config != "headline":
         raise SystemExit("--scaling weak exists for the headline workload only")
+    if sharded and args.dump_outputs:
+        raise SystemExit("--dump-outputs exists for single-GPU runs only")
 
     result = {"metric": "surface-node-updates/sec", "value": None, "unit": "node-updates/s", "n_gpus": world,
               "steps": K, "warmup": W, "ms_per_step": None, "higher_is_better": True,

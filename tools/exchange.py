@@ -2,7 +2,7 @@
 0 / 16 zones declared shared, library-owned RCCL communicator vs torch.distributed. One rank: the all-gather
 moves one block, so this measures the launch sequence, not xGMI."""
 import json, subprocess, sys
-base = [sys.executable, "bench.py", "--steps", "200", "--warmup", "20", "--no-cpu-baseline"]
+base = [sys.executable, "bench.py", "--steps", "200", "--warmup", "20", "--full", "--no-cpu-baseline"]
 for name, extra in (("fused", []), ("sharded native, nothing shared", ["--force-sharded"]),
                     ("16 shared zones, native", ["--force-shared-zones", "16"]),
                     ("16 shared zones, torch", ["--force-shared-zones", "16", "--collective", "torch"])):

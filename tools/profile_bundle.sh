@@ -13,7 +13,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 stats() {  # name, bench args...
     local name=$1; shift
-    (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$name -- python3 $R/bench.py "$@" --no-cpu-baseline --no-extras > $out/${name}_under_rocprof.json 2> $out/${name}_under_rocprof.err) || true
+    (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$name -- python3 $R/bench.py "$@" --full --no-cpu-baseline --no-extras > $out/${name}_under_rocprof.json 2> $out/${name}_under_rocprof.err) || true
     cp $(ls $out/trace_$name/*/*kernel_stats.csv | head -n 1) $R/profiles/${tag}_${name}_kernel_stats.csv
     cp $out/${name}_under_rocprof.json $R/profiles/${tag}_${name}_under_rocprof.json
     echo "stats $name done"
