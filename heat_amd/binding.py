@@ -85,6 +85,8 @@ _H = C.c_void_p
 SYMBOLS = [
     ("heat_batch_create", C.c_int, [C.POINTER(Desc), C.POINTER(_H)]),
     ("heat_batch_create_ex", C.c_int, [C.POINTER(Desc), C.POINTER(Options), C.POINTER(_H)]),
+    ("heat_batch_create_sites", C.c_int, [C.POINTER(Desc), C.POINTER(Options), C.c_int32, _i32p, C.POINTER(_H)]),
+    ("heat_batch_n_sites", C.c_int32, [_H]),
     ("heat_batch_destroy", None, [_H]),
     ("heat_batch_upload_state", C.c_int, [_H, _dp, C.c_size_t]),
     ("heat_batch_download_state", C.c_int, [_H, _dp, C.c_size_t]),
@@ -124,6 +126,7 @@ SYMBOLS = [
     ("heat_partition", C.c_int, [C.POINTER(Desc), C.c_int32, _i32p, _i64p]),
     ("heat_batch_create_shard", C.c_int, [C.POINTER(Desc), C.POINTER(Options), _i32p, C.POINTER(_H)]),
     ("heat_plan_check", C.c_int, [C.POINTER(Desc), C.POINTER(Options), _i64p]),
+    ("heat_plan_check_sites", C.c_int, [C.POINTER(Desc), C.POINTER(Options), C.c_int32, _i32p, _i64p]),
     ("heat_last_error", C.c_char_p, []),
     ("heat_amd_abi_version", C.c_int, []),
     # include/heat_amd_setup.h
@@ -179,13 +182,20 @@ def _check(rc):
         raise HeatError(rc, load_library().heat_last_error().decode("utf-8", "replace"))
 
 
-def as_weather(weather):
-    """[n,3] array (dry bulb C, wind direction RADIANS, wind speed m/s) -> ctypes array."""
-    w = np.ascontiguousarray(weather, dtype=np.float64).reshape(-1, 3)
+def as_weather(weather, n_sites=1):
+    """[n,3] array (dry bulb C, wind direction RADIANS, wind speed m/s) -> (ctypes array, n). A batch of weather sites
+    takes exactly [n_sub, n_sites, 3] (record [k, s]: site s at sub-timestep k) -> (ctypes array, n_sub); a batch of one
+    site takes [n, 3] or [n, 1, 3]."""
+    w = np.ascontiguousarray(weather, dtype=np.float64)
+    if n_sites > 1 and (w.ndim != 3 or w.shape[1:] != (n_sites, 3)):
+        raise ValueError("a batch of %d weather sites takes weather [n_sub, %d, 3], not %s" % (n_sites, n_sites, w.shape))
+    if n_sites == 1 and w.ndim == 3 and w.shape[1] != 1:
+        raise ValueError("weather of %d sites for a batch of one" % w.shape[1])
+    w = w.reshape(-1, 3)
     arr = (Weather * len(w))()
     if len(w):
         C.memmove(arr, w.ctypes.data, w.nbytes)
-    return arr, len(w)
+    return arr, len(w) // n_sites
 
 
 _F64 = ["mass", "uvalue", "front_alpha", "back_alpha", "front_ambient", "back_ambient", "front_emissivity",
@@ -235,7 +245,7 @@ def make_desc(md):
     return d, keep
 
 
-HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_last_error", "heat_amd_abi_version")
+HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_last_error", "heat_amd_abi_version")
 
 
 def load_host_library(path):
@@ -290,6 +300,20 @@ def plan_check(md, lib=None, **opts):
     return list(summary)
 
 
+def plan_check_sites(md, n_sites, site_of_surface, lib=None, **opts):
+    """heat_plan_check_sites: plan_check for a batch of weather sites (also verifies that every tile, fused workgroup
+    and team holds one site). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    opt = make_options(**opts)
+    sites = np.ascontiguousarray(site_of_surface, dtype=np.int32)
+    summary = (C.c_int64 * 8)()
+    rc = L.heat_plan_check_sites(C.byref(desc), C.byref(opt), int(n_sites), sites.ctypes.data_as(_i32p), summary)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+    return list(summary)
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -306,15 +330,27 @@ class HeatBatch:
     """Device-resident batch of surfaces + zones (≙ ThermalModel, src/model.rs:54-77)."""
 
     def __init__(self, md, device=-1, force_general=False, nodes_per_lane=0, use_graph=False, stream=None,
-                 n_ranks=1, rank=0, no_palette=False, no_fusion=False, fuse_always=False, rank_of_surface=None):
+                 n_ranks=1, rank=0, no_palette=False, no_fusion=False, fuse_always=False, rank_of_surface=None,
+                 sites=None, n_sites=None):
         """rank_of_surface (heat_partition's result): the batch holds the surfaces of `rank` only, picked from the
-        whole model's dict by the library (heat_batch_create_shard)."""
+        whole model's dict by the library (heat_batch_create_shard).
+        sites (modeldict.concat's site_of_surface): a batch of weather sites (heat_batch_create_sites), n_sites of them
+        (default: max(sites) + 1); its marches then take weather [n_sub, n_sites, 3]."""
         self._L = load_library()
         self._h = _H()
         desc, keep = make_desc(md)
         opt = make_options(device, force_general, nodes_per_lane, use_graph, stream, n_ranks, rank, no_palette,
                            no_fusion, fuse_always)
-        if rank_of_surface is None:
+        self.n_sites = 1
+        if sites is not None:
+            assert rank_of_surface is None, "a batch of weather sites cannot be sharded"
+            sos = np.ascontiguousarray(sites, dtype=np.int32)
+            if n_sites is None:
+                n_sites = int(sos.max()) + 1 if len(sos) else 1
+            _check(self._L.heat_batch_create_sites(C.byref(desc), C.byref(opt), int(n_sites), sos.ctypes.data_as(_i32p),
+                                                   C.byref(self._h)))
+            self.n_sites = int(self._L.heat_batch_n_sites(self._h))
+        elif rank_of_surface is None:
             _check(self._L.heat_batch_create_ex(C.byref(desc), C.byref(opt), C.byref(self._h)))
         else:
             ros = np.ascontiguousarray(rank_of_surface, dtype=np.int32)
@@ -368,7 +404,7 @@ class HeatBatch:
     def march(self, state, weather, zone_a0=None, zone_b0=None, outputs=None):
         """≙ ThermalModel::march: len(weather) sub-timesteps, in place on ``state``. ``outputs``: which of this
         path's outputs are written back (OUT_* bits; default all)."""
-        w, n = as_weather(weather)
+        w, n = as_weather(weather, self.n_sites)
         a0, pa = self._opt(zone_a0)
         b0, pb = self._opt(zone_b0)
         if outputs is None:
@@ -380,7 +416,7 @@ class HeatBatch:
         _check(self._L.heat_batch_download_outputs(self._h, self._state_ptr(state), state.size, int(outputs)))
 
     def march_resident(self, weather, zone_a0=None, zone_b0=None):
-        w, n = as_weather(weather)
+        w, n = as_weather(weather, self.n_sites)
         a0, pa = self._opt(zone_a0)
         b0, pb = self._opt(zone_b0)
         _check(self._L.heat_batch_march_resident(self._h, w, n, pa, pb))
@@ -395,7 +431,7 @@ class HeatBatch:
         return int(i.value), int(k.value)
 
     def set_weather(self, weather, zone_a0=None, zone_b0=None):
-        w, n = as_weather(weather)
+        w, n = as_weather(weather, self.n_sites)
         a0, pa = self._opt(zone_a0)
         b0, pb = self._opt(zone_b0)
         _check(self._L.heat_batch_set_weather(self._h, w, n, pa, pb))

@@ -280,8 +280,11 @@ struct heat_batch {
 
     StepWeather *h_weather = nullptr;  // pinned
     double *h_zone_ab = nullptr;       // pinned, [2][n_zones]
-    size_t weather_cap = 0;
+    size_t weather_cap = 0;            // records per site (sa.wstride)
     int n_weather = 0;
+    // weather sites (heat_batch_create_sites): h_weather / d_weather hold n_sites x weather_cap records, site-major
+    int32_t n_sites = 1;
+    DevBuf<int32_t> d_site;            // [S] site of every device surface (layout.hpp, SideArrays::site)
 
     // heat_batch_march on a caller-owned state: compact transfers through pinned staging, host gathers / scatters
     // on a thread pool ("Data at the boundary")
@@ -371,14 +374,17 @@ int flags_to_status(int f) {
 
 int rebuild_unified(heat_batch *b);
 
-int build(heat_batch *b, const heat_batch_desc *d, const heat_batch_options &opt) {
+int build(heat_batch *b, const heat_batch_desc *d, const heat_batch_options &opt, int32_t n_sites = 1,
+          const int32_t *site_of_surface = nullptr) {
     // Classification, clustering, tiling and packing are host-only work (plan.cpp); here the plan is uploaded.
     Plan p;
     {
         std::string err;
-        const int rc = make_plan(d, opt, p, err);
+        const int rc = make_plan(d, opt, p, err, n_sites, site_of_surface);
         if (rc) return fail(rc, "%s", err.c_str());
     }
+    b->n_sites = p.n_sites;
+    if (!p.dev_site.empty()) HIP_TRY(b->d_site.upload(p.dev_site));
     const int64_t S = p.n_surf, Z = p.n_zones;
     b->n_surf = S;
     b->n_zones = Z;
@@ -555,7 +561,8 @@ int build(heat_batch *b, const heat_batch_desc *d, const heat_batch_options &opt
     sa.hs_fix = has_fix ? b->d_hs_fix.p : nullptr;
     sa.zc = b->d_zone_contrib.p;
     sa.S = (int32_t)S;
-    sa.pad = 0;
+    sa.wstride = 0;
+    sa.site = b->n_sites > 1 ? b->d_site.p : nullptr;
     NodeArrays &na = b->na;
     na.T = b->d_T.p; na.V = b->d_V.p; na.U = b->d_U.p;
     na.cls = b->d_cls.p; na.pal = b->d_pal.p;
@@ -1002,7 +1009,8 @@ int heat_batch_create(const heat_batch_desc *desc, heat_batch **out) {
     return heat_batch_create_ex(desc, &opt, out);
 }
 
-int heat_batch_create_ex(const heat_batch_desc *desc, const heat_batch_options *opt_in, heat_batch **out) {
+static int create_impl(const heat_batch_desc *desc, const heat_batch_options *opt_in, int32_t n_sites,
+                       const int32_t *site_of_surface, bool sites, heat_batch **out) {
     if (!out) return fail(HEAT_E_INVALID_ARG, "out is NULL");
     *out = nullptr;
     heat_batch_options opt;
@@ -1010,6 +1018,11 @@ int heat_batch_create_ex(const heat_batch_desc *desc, const heat_batch_options *
     opt.device = -1;
     opt.n_ranks = 1;
     if (opt_in) opt = *opt_in;
+    if (sites) {  // (before any device work)
+        std::string err;
+        const int rc = check_sites(desc, opt, n_sites, site_of_surface, err);
+        if (rc) return fail(rc, "%s", err.c_str());
+    }
     if (opt.n_ranks < 1) opt.n_ranks = 1;
     if (opt.nodes_per_lane != 0 && opt.nodes_per_lane != 4 && opt.nodes_per_lane != 8 && opt.nodes_per_lane != 16)
         return fail(HEAT_E_INVALID_ARG, "nodes_per_lane must be 0, 4, 8 or 16");
@@ -1060,7 +1073,7 @@ int heat_batch_create_ex(const heat_batch_desc *desc, const heat_batch_options *
                     hipEventCreateWithFlags(&b->ev_fused, hipEventDisableTiming) != hipSuccess))
             rc = fail(HEAT_E_DEVICE, "event creation failed");
     }
-    if (!rc) rc = build(b, desc, opt);
+    if (!rc) rc = build(b, desc, opt, n_sites, site_of_surface);
     if (rc) {
         delete b;
         return rc;
@@ -1068,6 +1081,17 @@ int heat_batch_create_ex(const heat_batch_desc *desc, const heat_batch_options *
     *out = b;
     return HEAT_OK;
 }
+
+int heat_batch_create_ex(const heat_batch_desc *desc, const heat_batch_options *opt, heat_batch **out) {
+    return create_impl(desc, opt, 1, nullptr, false, out);
+}
+
+int heat_batch_create_sites(const heat_batch_desc *desc, const heat_batch_options *opt, int32_t n_sites,
+                            const int32_t *site_of_surface, heat_batch **out) {
+    return create_impl(desc, opt, n_sites, site_of_surface, true, out);
+}
+
+int32_t heat_batch_n_sites(const heat_batch *b) { return b ? b->n_sites : 0; }
 
 int heat_batch_create_shard(const heat_batch_desc *desc, const heat_batch_options *opt, const int32_t *rank_of_surface,
                             heat_batch **out) {
@@ -1312,33 +1336,56 @@ int heat_batch_set_weather(heat_batch *b, const heat_weather *weather, int32_t n
     if (rc) return rc;
     // The pinned staging buffers are free again once the previous call's copies have run — they sit at the head of
     // that call's work, so this does not wait for the march itself: consecutive marches queue up back to back.
+    const size_t n_sites = (size_t)b->n_sites;
+    // (weather sites: n_sub * n_sites records in pinned and device memory, 32 bytes each)
+    constexpr int64_t kMaxWeatherRecords = (int64_t)1 << 24;
+    if (n_sites > 1 && (int64_t)n_sub * (int64_t)n_sites > kMaxWeatherRecords)
+        return fail(HEAT_E_INVALID_ARG, "n_sub %d x %d sites = %lld weather records, more than %lld per call", n_sub, (int)n_sites,
+                    (long long)n_sub * (long long)n_sites, (long long)kMaxWeatherRecords);
     if (b->staged) HIP_TRY(hipEventSynchronize(b->ev_staged));
     if ((size_t)n_sub > b->weather_cap) {
         HIP_TRY(hipStreamSynchronize(b->stream));  // kernels in flight read the device array that is about to go
         if (b->h_weather) HIP_TRY(hipHostFree(b->h_weather));
         b->h_weather = nullptr;
-        const size_t cap = std::max<size_t>((size_t)n_sub, 64);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_weather), cap * sizeof(StepWeather)));
-        HIP_TRY(b->d_weather.alloc(cap));
+        // (per site; several sites: exactly the call's length — the head kernel copies every site's records, padding
+        // included, so a batch whose calls keep one length copies nothing it does not use)
+        const size_t cap = n_sites > 1 ? (size_t)n_sub : std::max<size_t>((size_t)n_sub, 64);
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_weather), n_sites * cap * sizeof(StepWeather)));
+        HIP_TRY(b->d_weather.alloc(n_sites * cap));
         b->weather_cap = cap;
-        if (b->graph_exec) {  // the captured graph holds the old pointer
+        b->sa.wstride = (int32_t)cap;
+        if (b->graph_exec) {  // the captured graph holds the old pointer (and the old stride)
             (void)hipGraphExecDestroy(b->graph_exec);
             b->graph_exec = nullptr;
         }
     }
-    for (int i = 0; i < n_sub; i++) {
-        // sin/cos of the wind direction as is_windward takes them (surface.rs:40)
-        b->h_weather[i] = StepWeather{weather[i].dry_bulb, std::sqrt(weather[i].wind_speed),
-                                      std::sin(weather[i].wind_direction), std::cos(weather[i].wind_direction)};
-    }
+    // sin/cos of the wind direction as is_windward takes them (surface.rs:40). The caller's records are sub-timestep-major
+    // ([k * n_sites + s]); the device's are site-major ([s * weather_cap + k], layout.hpp).
+    for (size_t st = 0; st < n_sites; st++)
+        for (int i = 0; i < n_sub; i++) {
+            const heat_weather &w = weather[(size_t)i * n_sites + st];
+            b->h_weather[st * b->weather_cap + i] =
+                StepWeather{w.dry_bulb, std::sqrt(w.wind_speed), std::sin(w.wind_direction), std::cos(w.wind_direction)};
+        }
     b->n_weather = n_sub;
     const int64_t Z = b->n_zones;
     for (int64_t z = 0; z < Z; z++) {
         b->h_zone_ab[z] = zone_a0 ? zone_a0[z] : 0.0;
         b->h_zone_ab[Z + z] = zone_b0 ? zone_b0[z] : 0.0;
     }
-    // weather, a0, b0 and the sub-timestep counter in one launch that reads the pinned buffers itself
-    launch_begin_march(b->h_weather, b->d_weather.p, n_sub, b->h_zone_ab, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p,
+    // weather, a0, b0 and the sub-timestep counter in one launch that reads the pinned buffers itself. Many sites' records
+    // (1 MB and more) go by DMA ahead of it: measured on MI355X (tools/sites.py, copy + head kernel + one round trip), 82 000
+    // records took 73 and 93 us by DMA (two runs) against 84 us read by the kernel, 5 000 records 29 against 22 us.
+    // HEAT_AMD_WEATHER_KERNEL_COPY=1 (measurement) keeps every copy in the kernel.
+    static const bool kernel_copy = getenv("HEAT_AMD_WEATHER_KERNEL_COPY") != nullptr;
+    constexpr int kDmaMinRecords = 32768;
+    int n_records = n_sub > 0 ? (int)((n_sites - 1) * b->weather_cap) + n_sub : 0;
+    if (n_sites > 1 && n_records >= kDmaMinRecords && !kernel_copy) {
+        HIP_TRY(hipMemcpyAsync(b->d_weather.p, b->h_weather, (size_t)n_records * sizeof(StepWeather), hipMemcpyHostToDevice,
+                               b->stream));
+        n_records = 0;
+    }
+    launch_begin_march(b->h_weather, b->d_weather.p, n_sub, n_records, b->h_zone_ab, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p,
                        b->stream);
     if (!b->ev_staged) HIP_TRY(hipEventCreateWithFlags(&b->ev_staged, hipEventDisableTiming));
     HIP_TRY(hipEventRecord(b->ev_staged, b->stream));

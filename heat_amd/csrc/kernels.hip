@@ -46,6 +46,21 @@ __device__ __forceinline__ void eval_side(const SideConst &c, const StepWeather 
     }
 }
 
+// The weather site of a tile (layout.hpp: the site of the tile's first surface stands for all of them). The site table is
+// written once, at batch creation, and never by a kernel: it is read through the constant address space, so that the
+// wave-uniform load is a scalar (SMEM) load — through a plain pointer in a kernel that stores to global memory the
+// compiler emits a per-lane load and waits for it with vmcnt, which counts the wavefront's outstanding stores as well.
+typedef __attribute__((address_space(4))) const int32_t ConstInt32;
+__device__ __forceinline__ int tile_site(const SideArrays &sd, int surf_base) {
+    const ConstInt32 *site = (const ConstInt32 *)sd.site;  // (generic -> constant: the same 64-bit address)
+    return __builtin_amdgcn_readfirstlane(site[__builtin_amdgcn_readfirstlane(surf_base)]);
+}
+// The weather records of that site (site-major), read as scalar loads as in a single-site batch, which reads its own.
+__device__ __forceinline__ const StepWeather *site_weather(const StepWeather *weather, const SideArrays &sd, int surf_base) {
+    if (sd.site == nullptr) return weather;
+    return weather + (int64_t)tile_site(sd, surf_base) * sd.wstride;
+}
+
 __device__ __forceinline__ double boundary_temperature(const SideConst &c, const StepWeather &w,
                                                        const double *__restrict__ zone_T) {
     const int kind = c.kind_n & 3;  // get_boundary_temperature, model.rs:79-96
@@ -419,7 +434,7 @@ k_surfaces_small(const GeneralTile *__restrict__ tiles, int n_tiles, NodeArrays 
     if (wave >= n_tiles) return;
     const GeneralTile tile = tiles[wave];
     const int step = (step_fixed >= 0) ? step_fixed : *step_ptr;
-    const StepWeather w = weather[step];
+    const StepWeather w = site_weather(weather, sd, tile.surf_base)[step];
     const unsigned int iters = small_tile_march<CAV>(tile.node_base, tile.surf_base, tile.G, lane, na, gen_base, sd, w, zone_T, flags);
     if (lane < tile.G) nomass_iters[(int64_t)wave * kWave + lane] += iters;  // one slot per lane of the tile
 }
@@ -667,6 +682,7 @@ __device__ void fused_small_wave(const FusedBlock &blk, const FusedArgs &fa, con
                                  const StepWeather *__restrict__ weather, int *__restrict__ flags) {
     const int tile_index = blk.first_small + (wib - blk.n_tiles);
     const GeneralTile tile = fa.gen_tiles[tile_index];
+    weather = site_weather(weather, sd, tile.surf_base);
     const bool active = lane < tile.G;
     const int d = tile.surf_base + (active ? lane : 0);
     const int S = sd.S;
@@ -1538,8 +1554,11 @@ k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, 
     // what this one reads first, out of the memory-side cache instead of HBM)
     {
     const int tix = (!FUSED && fa.reverse) ? n_tiles - 1 - wave : wave;
-    fast_tile_march<M, NM, PAL, CAV, FUSED, SMALL>(tiles[tix], tix, true, lane, wib, s_pal, s_V, s_pos_static, fl, blk, blk_waves, n_it, step0, na,
-                                                   sd, weather, zone_T, flags, nomass_iters, fa, write_out, team);
+    const FastTile tl = tiles[tix];
+    // (the tile's weather site; a fused workgroup's and a team's tiles are all of one site)
+    fast_tile_march<M, NM, PAL, CAV, FUSED, SMALL>(tl, tix, true, lane, wib, s_pal, s_V, s_pos_static, fl, blk, blk_waves, n_it, step0, na,
+                                                   sd, site_weather(weather, sd, tl.surf_base), zone_T, flags, nomass_iters, fa,
+                                                   write_out, team);
     }
 next_block:
     if constexpr (FUSED) {
@@ -1609,30 +1628,34 @@ k_surfaces_stream(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na
     // last sweep touched last (still in the 256 MB memory-side cache) is what this one reads first
     const int last = n_tiles - 1;
     FastTile tile_next = tiles[__builtin_amdgcn_readfirstlane(reverse ? last - wave0 : wave0)];
+    // weather sites: the next tile's site is fetched at the end of a tile, when its descriptor is long in registers
+    int site_next = sd.site ? tile_site(sd, tile_next.surf_base) : 0;
     for (int wv = wave0; wv < n_tiles; wv += n_waves) {
         const int w = __builtin_amdgcn_readfirstlane(reverse ? last - wv : wv);
         FastTile tile = tile_next;
+        const StepWeather *const wt = weather + (int64_t)site_next * sd.wstride;  // (one site: site 0)
         const int wn = min(wv + n_waves, last);
         tile_next = tiles[__builtin_amdgcn_readfirstlane(reverse ? last - wn : wn)];
         const int kind = (tile.k >> kTileKindShift) & 3;
         const bool nm = (tile.k & kTileNmBit) != 0;
         tile.k = (int16_t)(tile.k & (0x1ff | kTileMixedBit | kTileChunkyBit));
         if constexpr (VARIANT == kStreamWide) {
-            fast_tile_march<16, 0, 1, 0, 0>(tile, w, false, lane, wib, s_pal, nullptr, s_pos, fl, blk, 0, 1, step0, na, sd, weather,
+            fast_tile_march<16, 0, 1, 0, 0>(tile, w, false, lane, wib, s_pal, nullptr, s_pos, fl, blk, 0, 1, step0, na, sd, wt,
                                             zone_T, flags, nomass_iters, fa, write_out);
         } else {
             constexpr int kCav = VARIANT == kStreamCav ? 1 : 0;
             switch (kind) {
             case 1:
-                fast_tile_march<8, kNm, 1, kCav, 0>(tile, w, nm, lane, wib, s_pal, nullptr, s_pos, fl, blk, 0, 1, step0, na, sd, weather,
+                fast_tile_march<8, kNm, 1, kCav, 0>(tile, w, nm, lane, wib, s_pal, nullptr, s_pos, fl, blk, 0, 1, step0, na, sd, wt,
                                                     zone_T, flags, nomass_iters, fa, write_out);
                 break;
             case 0:
-                fast_tile_march<4, kNm, 1, kCav, 0>(tile, w, nm, lane, wib, s_pal, nullptr, s_pos, fl, blk, 0, 1, step0, na, sd, weather,
+                fast_tile_march<4, kNm, 1, kCav, 0>(tile, w, nm, lane, wib, s_pal, nullptr, s_pos, fl, blk, 0, 1, step0, na, sd, wt,
                                                     zone_T, flags, nomass_iters, fa, write_out);
                 break;
             default: {
-                unsigned int tot = small_tile_march<kCav>(tile.node_base, tile.surf_base, tile.G, lane, na, gen_base, sd, weather[step0],
+                unsigned int tot = small_tile_march<kCav>(tile.node_base, tile.surf_base, tile.G, lane, na, gen_base, sd,
+                                                          wt[step0],
                                                           zone_T, flags);
 #pragma unroll
                 for (int o = kWave / 2; o > 0; o >>= 1) tot += __shfl_down(tot, o, kWave);
@@ -1641,6 +1664,7 @@ k_surfaces_stream(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na
             }
             }
         }
+        if (sd.site) site_next = tile_site(sd, tile_next.surf_base);
     }
 }
 
@@ -1668,7 +1692,7 @@ k_surfaces_general(const GeneralTile *__restrict__ tiles, int n_tiles, NodeArray
     const int nn = cf.kind_n >> 16;
     const int bk = cb.kind_n & 3;
     const int step = (step_fixed >= 0) ? step_fixed : *step_ptr;
-    const StepWeather w = weather[step];
+    const StepWeather w = site_weather(weather, sd, tile.surf_base)[step];
 
     double *Tg = na.T + tile.node_base + lane;                       // T(i) = Tg[i*64]
     const double *Vg = na.V + tile.node_base + lane;
@@ -2153,11 +2177,12 @@ __global__ void k_set_step(int *step_ptr, int v, int last) {
 // The head of a march call in one launch: the call's weather and the zones' a0 / b0 terms from the pinned host staging
 // buffers (read over PCIe by the kernel itself: three small copies on the stream cost 30-50 us of idle chip per call
 // between them and the first kernel), and the sub-timestep counter.
-__global__ void k_begin_march(const StepWeather *__restrict__ h_weather, StepWeather *__restrict__ weather, int n_sub,
+// (n_records: the call's sub-timesteps, or with weather sites all sites' records, site-major — layout.hpp)
+__global__ void k_begin_march(const StepWeather *__restrict__ h_weather, StepWeather *__restrict__ weather, int n_records,
                               const double *__restrict__ h_zone_ab, double *__restrict__ a0, double *__restrict__ b0,
                               int n_zones, int *step_ptr, int last) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_sub) weather[i] = h_weather[i];
+    if (i < n_records) weather[i] = h_weather[i];
     if (i < n_zones) {
         a0[i] = h_zone_ab[i];
         b0[i] = h_zone_ab[n_zones + i];
@@ -2423,10 +2448,10 @@ void launch_outputs_compact(int n_surf, int n_zones, const SideOut *out, const i
     hipLaunchKernelGGL(k_outputs_compact, dim3((n + 255) / 256), dim3(256), 0, st, n_surf, n_zones, out, orig_of, zone_T, dst);
 }
 
-void launch_begin_march(const StepWeather *h_weather, StepWeather *weather, int n_sub, const double *h_zone_ab, double *a0,
-                        double *b0, int n_zones, int *step_ptr, hipStream_t st) {
-    const int n = std::max(std::max(n_sub, n_zones), 1);
-    hipLaunchKernelGGL(k_begin_march, dim3((n + 255) / 256), dim3(256), 0, st, h_weather, weather, n_sub, h_zone_ab, a0, b0,
+void launch_begin_march(const StepWeather *h_weather, StepWeather *weather, int n_sub, int n_records, const double *h_zone_ab,
+                        double *a0, double *b0, int n_zones, int *step_ptr, hipStream_t st) {
+    const int n = std::max(std::max(n_records, n_zones), 1);
+    hipLaunchKernelGGL(k_begin_march, dim3((n + 255) / 256), dim3(256), 0, st, h_weather, weather, n_records, h_zone_ab, a0, b0,
                        n_zones, step_ptr, n_sub - 1);
 }
 

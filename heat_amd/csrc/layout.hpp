@@ -111,7 +111,8 @@ struct SideArrays {
     ZoneContrib *zc;       // [zone entries]: what each zone-facing side adds to its zone's heat balance, written by the
                            // surface kernels at the side's position in the zone's list (model.rs:562-585)
     int32_t S;
-    int32_t pad;
+    int32_t wstride;       // weather sites: records per site in the device weather buffer (site-major, below)
+    const int32_t *site;   // [S] weather site of device surface d, the same for every surface of a tile; nullptr: one site
 };
 
 // Unified per-node buffers (all groups).
@@ -163,6 +164,10 @@ struct CavityDev {
 };
 
 // Weather and per-march constants, device-resident. step is advanced by the zone kernel.
+// A batch of several weather sites (heat_batch_create_sites) keeps them site-major: the record of site s at sub-timestep k
+// is weather[s * SideArrays::wstride + k]. The planner gives every tile, fused workgroup and team surfaces of one site, so
+// a wavefront reads its site once — SideArrays::site at the tile's first surface, through the constant address space so
+// that it is a scalar (SMEM) load (kernels.hip, tile_site) — and its weather as scalar loads.
 struct StepWeather {
     double t_out;    // dry bulb
     double sqrt_ws;  // sqrt(wind speed): the forced coefficient is wf * SideConst::forced * sqrt_ws

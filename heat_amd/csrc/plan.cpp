@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <numeric>
 
 namespace heat {
@@ -35,6 +36,7 @@ struct Placed {
     int cls;     // 0..kNumFast-1 fast classes, kGeneral = catch-all
     int k;       // lanes per surface (fast)
     int blk;     // cluster-resident march: workgroup number, -1 = streamed
+    int site;    // weather site (0 in a single-site batch)
 };
 
 // Tiles of a cluster-resident workgroup: its surfaces are packed into wavefronts whatever their lane counts (a
@@ -240,9 +242,29 @@ int check_desc(const heat_batch_desc *d, std::string &err) {
     return HEAT_OK;
 }
 
-int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, std::string &err) {
+int check_sites(const heat_batch_desc *d, const heat_batch_options &opt, int32_t n_sites, const int32_t *site_of_surface,
+                std::string &err) {
+    if (n_sites < 1 || n_sites > kMaxSites)
+        return failp(err, HEAT_E_INVALID_ARG, "n_sites = %d outside [1, %d]", n_sites, kMaxSites);
+    if (opt.n_ranks > 1) return failp(err, HEAT_E_INVALID_ARG, "a batch of weather sites cannot be sharded (n_ranks = %d)", opt.n_ranks);
+    if (!d) return failp(err, HEAT_E_INVALID_ARG, "NULL descriptor");
+    if (d->n_surfaces > 0 && !site_of_surface) return failp(err, HEAT_E_INVALID_ARG, "NULL site_of_surface");
+    for (int64_t s = 0; s < d->n_surfaces; s++)
+        if (site_of_surface[s] < 0 || site_of_surface[s] >= n_sites)
+            return failp(err, HEAT_E_SIZE, "surface %lld: site %d outside [0, %d)", (long long)s, site_of_surface[s], n_sites);
+    return HEAT_OK;
+}
+
+int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, std::string &err, int32_t n_sites,
+              const int32_t *site_of_surface) {
     int rc = check_desc(d, err);
     if (rc) return rc;
+    if (n_sites != 1 || site_of_surface) {
+        rc = check_sites(d, opt, n_sites, site_of_surface, err);
+        if (rc) return rc;
+    }
+    // (one site: the plan of a batch without sites, whatever the array says — it can only say 0)
+    if (n_sites == 1) site_of_surface = nullptr;
     // (heat_batch_create_ex refuses these before it comes here; heat_plan_check comes straight)
     if (opt.nodes_per_lane != 0 && opt.nodes_per_lane != 4 && opt.nodes_per_lane != 8 && opt.nodes_per_lane != 16)
         return failp(err, HEAT_E_INVALID_ARG, "nodes_per_lane must be 0, 4, 8 or 16");
@@ -257,6 +279,8 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
     p.dt = d->dt;
     p.n_nodes = S > 0 ? d->node_offset[S] : 0;
     p.algorithmic_bytes = 32 * p.n_nodes + 152 * S;  // 32 n + 152 bytes per surface per sub-timestep
+    p.n_sites = n_sites;
+    auto site_of = [&](int64_t s) { return site_of_surface ? site_of_surface[s] : 0; };
 
     // ---- classify ----
     std::vector<Placed> placed(S);
@@ -271,7 +295,7 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
             cls = (k > kWave) ? kGeneral : fast_class(M, cat[s]);
             if (k > kWave) { cat[s].kind = kGeneral; k = 1; }
         }
-        placed[s] = Placed{s, n, cls, k, -1};
+        placed[s] = Placed{s, n, cls, k, -1, site_of(s)};
     }
     if (opt.nodes_per_lane == 0) {
         // A class of few surfaces is a launch of its own that cannot fill the chip (1 M ragged walls: the two 4-node
@@ -355,7 +379,8 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
 
         // open workgroup per class: surfaces per k, zones so far
         struct Open { int blk = -1; int cnt[kWave + 1] = {}; int nsmall = 0; int nz = 0; int ne = 0; };
-        Open open[2 * kNumFast];  // [class][mixed]
+        // [site][class][mixed]: clusters of different weather sites never share a workgroup
+        std::map<std::pair<int32_t, int>, Open> open;
         auto new_block = [&](int cls, bool mixed) {
             blocks.push_back(BlockPlan{cls, mixed, {}, -1, 0, {}});
             return (int)blocks.size() - 1;
@@ -384,6 +409,12 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
         auto max_tiles = [&](int m) { return (m == 16 && wide_batch) ? 4 : kFusedMaxWaves; };
         for (int64_t r = 0; r < Z; r++) {
             if (find((int32_t)r) != r || !cok[r] || coff[r + 1] == coff[r]) continue;
+            // a cluster whose surfaces belong to more than one weather site is streamed: a workgroup (and a team) reads
+            // one site's weather
+            const int32_t csite = placed[csurf[coff[r]]].site;
+            bool one_site = true;
+            for (int64_t q = coff[r]; q < coff[r + 1]; q++) one_site = one_site && placed[csurf[q]].site == csite;
+            if (!one_site) continue;
             // one blocking factor for the cluster: the cheapest that keeps every surface at two lanes or more
             // (gas cavities: 4 or 8 nodes per lane only — the 16-node cavity variant does not fit the registers)
             // Small all-no-mass surfaces (glazing, thin walls) of the cluster get wavefronts of their own in the
@@ -555,7 +586,7 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
             }
             Category cc{0, mixed ? 1 : nm, (mixed ? (M < 16) : any_cav) ? 1 : 0, 1, 7};
             const int cls = fast_class(M, cc);
-            Open &o = open[2 * cls + (mixed ? 1 : 0)];
+            Open &o = open[{csite, 2 * cls + (mixed ? 1 : 0)}];
             int merged[kWave + 1];
             for (int k = 0; k <= kWave; k++) merged[k] = o.cnt[k] + cnt[k];
             // Workgroups of four tiles are the target (two of them share a compute unit, so one's zone balance —
@@ -607,16 +638,17 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
         }
         std::stable_sort(lone.begin(), lone.end(), [&](int64_t x, int64_t y) {
             if (placed[x].cls != placed[y].cls) return placed[x].cls < placed[y].cls;
+            if (placed[x].site != placed[y].site) return placed[x].site < placed[y].site;
             return placed[x].k < placed[y].k;
         });
         {
-            int cur_cls = -1, cur_k = -1, cur_blk = -1, in_blk = 0;
+            int cur_cls = -1, cur_k = -1, cur_blk = -1, in_blk = 0, cur_site = -1;
             for (int64_t s : lone) {
                 Placed &pl = placed[s];
                 if (!lone_ok[s] || pl.cls >= kNumFast) continue;
                 const int cap = 4 * (kWave / pl.k);
-                if (pl.cls != cur_cls || pl.k != cur_k || in_blk >= cap) {
-                    cur_cls = pl.cls; cur_k = pl.k; in_blk = 0;
+                if (pl.cls != cur_cls || pl.k != cur_k || pl.site != cur_site || in_blk >= cap) {
+                    cur_cls = pl.cls; cur_k = pl.k; cur_site = pl.site; in_blk = 0;
                     cur_blk = new_block(pl.cls, false);
                 }
                 pl.blk = cur_blk;
@@ -656,7 +688,7 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
         if (placed[s].blk >= 0) p.n_fused_surfaces++;
     }
 
-    // ---- order: class, then streamed surfaces before the fused workgroups, then lanes per surface ----
+    // ---- order: class, then streamed surfaces before the fused workgroups, then weather site, then lanes per surface ----
     // Small surfaces with a gas cavity are grouped by the branch of the Nusselt correlation their tilt selects
     // (gas.rs:197-315: five ranges of the cavity angle): the lanes of a wavefront then take the same branch instead of
     // the wavefront running all of them one after the other.
@@ -680,6 +712,7 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
         const Placed &a = placed[x], &c = placed[y];
         if (a.cls != c.cls) return a.cls < c.cls;
         if (a.blk != c.blk) return a.blk < c.blk;
+        if (a.site != c.site) return a.site < c.site;  // (a workgroup's surfaces share one already)
         if (a.cls < kNumFast && a.k != c.k) return a.k < c.k;
         if (tilt_key[x] != tilt_key[y]) return tilt_key[x] < tilt_key[y];
         if (a.cls < kNumFast) return false;
@@ -711,7 +744,8 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
             // else keeps tiles of one lane count, floor(64 / k) surfaces each.
             bool mixed_block = false;
             if (p0.blk >= 0) {
-                for (size_t q = pos; q < (size_t)S && placed[order[q]].cls == p0.cls && placed[order[q]].blk == p0.blk; q++)
+                for (size_t q = pos; q < (size_t)S && placed[order[q]].cls == p0.cls && placed[order[q]].blk == p0.blk &&
+                                     placed[order[q]].site == p0.site; q++)
                     mixed_block = mixed_block || placed[order[q]].k != k;
             }
             const int Gmax = kWave / k;
@@ -719,13 +753,13 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
             int lanes = 0;
             if (mixed_block) {
                 while (end < (size_t)S && placed[order[end]].cls == p0.cls && placed[order[end]].blk == p0.blk &&
-                       lanes + placed[order[end]].k <= kWave) {
+                       placed[order[end]].site == p0.site && lanes + placed[order[end]].k <= kWave) {
                     lanes += placed[order[end]].k;
                     end++;
                 }
             } else {
                 while (end < (size_t)S && placed[order[end]].cls == p0.cls && placed[order[end]].k == k &&
-                       placed[order[end]].blk == p0.blk && (int)(end - pos) < Gmax)
+                       placed[order[end]].blk == p0.blk && placed[order[end]].site == p0.site && (int)(end - pos) < Gmax)
                     end++;
             }
             const int Lk = mixed_block ? lanes : Gmax * k;
@@ -762,7 +796,7 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
             if (gen_tiles.empty()) p.gen_base = node_cursor;
             size_t end = pos;
             while (end < (size_t)S && end < pos + (size_t)kWave && placed[order[end]].cls == p0.cls &&
-                   placed[order[end]].blk == p0.blk)
+                   placed[order[end]].blk == p0.blk && placed[order[end]].site == p0.site)
                 end++;
             if (p0.cls < kGeneral) p.n_small_tiles++;
             if (p0.cls == kSmall) p.n_small_plain_tiles++;
@@ -1121,6 +1155,10 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
     p.hs_fix = std::move(hFix);
     p.first_slot = std::move(hFirst);
     p.slots = std::move(hSlots);
+    if (site_of_surface) {
+        p.dev_site.resize(S);
+        for (int64_t dd = 0; dd < S; dd++) p.dev_site[dd] = placed[orig_of[dd]].site;
+    }
     p.dev_of = std::move(dev_of);
     p.orig_of = std::move(orig_of);
     p.zone_off = std::move(zoff);
@@ -1189,7 +1227,7 @@ void find_clusters(const heat_batch_desc *d, std::vector<int32_t> &cluster_of_su
 // the cluster-resident march runs surfaces of one lane in the 8-node classes without cavities only (kernels.hip)
 static bool single_lane_class(int c) { return kFastM[c] == 8 && !kFastCAV[c]; }
 
-int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err) {
+int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err, const int32_t *site_of_surface) {
 #define PLAN_REQUIRE(cond, ...) \
     do { if (!(cond)) return failp(err, HEAT_E_SIZE, "plan check failed: " __VA_ARGS__); } while (0)
     const int64_t S = p.n_surf, Z = p.n_zones;
@@ -1405,6 +1443,47 @@ int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err) {
             if (team_sides[z] > 0) PLAN_REQUIRE(team_sides[z] == p.zone_off[z + 1] - p.zone_off[z], "zone %lld: %lld sides in its team, %lld in the model", (long long)z, (long long)team_sides[z], (long long)(p.zone_off[z + 1] - p.zone_off[z]));
     }
     for (int64_t z = 0; z < Z; z++) PLAN_REQUIRE((p.zone_block[z] >= 0) == (zone_seen[z] != 0), "zone %lld: block table and workgroup lists disagree", (long long)z);
+    if (site_of_surface && p.n_sites > 1) {
+        // weather sites: the kernels read the record of the site of a tile's first surface for the whole wavefront, and a
+        // workgroup or team holds one site — so every tile, workgroup and team must be of one site
+        PLAN_REQUIRE((int64_t)p.dev_site.size() == S, "site table size");
+        for (int64_t dd = 0; dd < S; dd++)
+            PLAN_REQUIRE(p.dev_site[dd] == site_of_surface[p.orig_of[dd]], "device surface %lld: site %d, surface %lld has %d",
+                         (long long)dd, p.dev_site[dd], (long long)p.orig_of[dd], site_of_surface[p.orig_of[dd]]);
+        auto run_site = [&](int64_t base, int G) -> int32_t {  // the site of surfaces [base, base + G), -1 when they differ
+            for (int g = 1; g < G; g++) if (p.dev_site[base + g] != p.dev_site[base]) return -1;
+            return G > 0 ? p.dev_site[base] : -2;
+        };
+        for (int c = 0; c < kNumFast; c++)
+            for (size_t t = 0; t < p.fast_tiles[c].size(); t++)
+                PLAN_REQUIRE(run_site(p.fast_tiles[c][t].surf_base, p.fast_tiles[c][t].G) >= 0, "class %d tile %zu holds more than one site", c, t);
+        for (size_t t = 0; t < p.gen_tiles.size(); t++)
+            PLAN_REQUIRE(run_site(p.gen_tiles[t].surf_base, p.gen_tiles[t].G) >= 0, "general tile %zu holds more than one site", t);
+        auto block_site = [&](int c, const FusedBlock &fb, int32_t &site) -> bool {
+            for (int q = 0; q < fb.n_tiles + fb.n_small; q++) {
+                const int32_t ts = q < fb.n_tiles ? p.dev_site[p.fast_tiles[c][fb.first_tile + q].surf_base]
+                                                  : p.dev_site[p.gen_tiles[fb.first_small + q - fb.n_tiles].surf_base];
+                if (site >= 0 && ts != site) return false;
+                site = ts;
+            }
+            return true;
+        };
+        for (int c = 0; c < kNumFast; c++) {
+            for (int g2 = 0; g2 < 4; g2++)
+                for (size_t bi = 0; bi < p.fblocks[c][g2].size(); bi++) {
+                    int32_t site = -1;
+                    PLAN_REQUIRE(block_site(c, p.fblocks[c][g2][bi], site), "class %d list %d: workgroup %zu holds more than one site", c, g2, bi);
+                }
+            for (size_t si = 0; si < p.team_supers[c].size(); si++) {
+                int32_t site = -1;
+                const FusedSuper &su = p.team_supers[c][si];
+                for (int m = 0; m < su.n_members; m++)
+                    PLAN_REQUIRE(block_site(c, p.team_blocks[c][su.first_block + m], site), "class %d: team %zu holds more than one site", c, si);
+            }
+        }
+    } else {
+        PLAN_REQUIRE(p.dev_site.empty() && p.n_sites == 1, "site table of a single-site plan");
+    }
     PLAN_REQUIRE(fused_surfaces == p.n_fused_surfaces, "%lld surfaces in workgroups, %lld counted", (long long)fused_surfaces, (long long)p.n_fused_surfaces);
     if (!p.cavref.empty()) {
         PLAN_REQUIRE((int64_t)p.cavref.size() == 4 * S, "cavref size");
@@ -1561,16 +1640,22 @@ int heat_partition(const heat_batch_desc *desc, int32_t n_ranks, int32_t *rank_o
     return heat::partition_surfaces(desc, n_ranks, rank_of_surface, n_shared_zones, heat::last_error());
 }
 
-int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt_in, int64_t summary[8]) {
+static int plan_check_impl(const heat_batch_desc *desc, const heat_batch_options *opt_in, int32_t n_sites,
+                           const int32_t *site_of_surface, bool sites, int64_t summary[8]) {
     heat_batch_options opt;
     memset(&opt, 0, sizeof opt);
     opt.device = -1;
     opt.n_ranks = 1;
     if (opt_in) opt = *opt_in;
+    int rc;
+    if (sites) {
+        rc = heat::check_sites(desc, opt, n_sites, site_of_surface, heat::last_error());
+        if (rc) return rc;
+    }
     heat::Plan p;
-    int rc = heat::make_plan(desc, opt, p, heat::last_error());
+    rc = heat::make_plan(desc, opt, p, heat::last_error(), n_sites, site_of_surface);
     if (rc) return rc;
-    rc = heat::check_plan(p, desc, heat::last_error());
+    rc = heat::check_plan(p, desc, heat::last_error(), site_of_surface);
     if (rc) return rc;
     if (summary) {
         int64_t n_blocks = 0, n_fast_tiles = 0;
@@ -1589,6 +1674,15 @@ int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt_i
         summary[7] = n_fast_tiles + (int64_t)p.gen_tiles.size();
     }
     return HEAT_OK;
+}
+
+int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt, int64_t summary[8]) {
+    return plan_check_impl(desc, opt, 1, nullptr, false, summary);
+}
+
+int heat_plan_check_sites(const heat_batch_desc *desc, const heat_batch_options *opt, int32_t n_sites,
+                          const int32_t *site_of_surface, int64_t summary[8]) {
+    return plan_check_impl(desc, opt, n_sites, site_of_surface, true, summary);
 }
 
 }  // extern "C"

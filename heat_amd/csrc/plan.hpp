@@ -58,6 +58,11 @@ struct Plan {
     std::vector<int32_t> zone_block;  // zone -> fused workgroup (global number) or -1
     bool any_fused = false;
 
+    // weather sites (heat_batch_create_sites): every tile, fused workgroup and team holds surfaces of one site, so the
+    // kernels read the weather record of device surface surf_base's site for the whole wavefront (layout.hpp, SideArrays)
+    int32_t n_sites = 1;
+    std::vector<int32_t> dev_site;  // [S] site of device surface d; empty for a single-site batch
+
     // per-node constants (device layout)
     std::vector<double> V, U, alpha_f, alpha_b, mass, pal;
     std::vector<uint8_t> cls;
@@ -88,11 +93,19 @@ struct Plan {
 
 // Checks of heat_batch_create (reference: ThermalModel::new's Err / setup-time panics). Returns a heat_status.
 int check_desc(const heat_batch_desc *d, std::string &err);
-// The whole plan. Returns HEAT_OK or a negative heat_status with `err` set.
-int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, std::string &err);
+// The whole plan. Returns HEAT_OK or a negative heat_status with `err` set. site_of_surface (nullable: one site):
+// the weather site of every surface, in [0, n_sites) — checked by check_sites first.
+int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, std::string &err, int32_t n_sites = 1,
+              const int32_t *site_of_surface = nullptr);
 // Internal consistency of a plan against its descriptor (every surface placed once, every index inside its
-// array, every workgroup inside the kernel's limits). Used by the host-only tests; HEAT_OK or HEAT_E_SIZE.
-int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err);
+// array, every workgroup inside the kernel's limits; with sites: every tile, workgroup and team of one site). Used by
+// the host-only tests; HEAT_OK or HEAT_E_SIZE.
+int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err, const int32_t *site_of_surface = nullptr);
+// The arguments of heat_batch_create_sites / heat_plan_check_sites: HEAT_E_INVALID_ARG for a site count outside
+// [1, kMaxSites] or a sharded batch, HEAT_E_SIZE for a surface whose site is out of range.
+constexpr int32_t kMaxSites = 65536;
+int check_sites(const heat_batch_desc *d, const heat_batch_options &opt, int32_t n_sites, const int32_t *site_of_surface,
+                std::string &err);
 
 // Zone-connected clusters (model.rs:556-590: surfaces exchange heat only through the zones they face): cluster id
 // per surface (-1: faces no zone) and per zone, ids dense in [0, n_clusters).

@@ -106,6 +106,110 @@ def subset(md, idx):
     return out
 
 
+def concat(models, interleave=False):
+    """Joins independent model dicts (one per weather site, e.g. a building each) into one batch: zones, cavities and
+    state slots renumbered, each model's SimulationState slots placed after the previous model's, so that the joined
+    state is the models' states back to back (``np.concatenate``). All models share one dt (a batch has one).
+    interleave=True lists the sites' surfaces alternately (surface i of every model in turn) instead of model after
+    model — the planner then has to sort them. Returns (joined dict, site_of_surface); the joined dict's
+    ``site_state_offset[k]`` is where model k's slots start."""
+    models = list(models)
+    assert models, "nothing to join"
+    dt = float(models[0]["dt"])
+    assert all(float(m["dt"]) == dt for m in models), "the models of one batch share one dt"
+    K = len(models)
+    S_k = np.array([int(m["n_surfaces"]) for m in models], dtype=np.int64)
+    Z_k = np.array([int(m["n_zones"]) for m in models], dtype=np.int64)
+    st_k = np.array([int(m["n_state"]) for m in models], dtype=np.int64)
+    C_k = np.array([len(m["cavities"]) if m.get("cavities") is not None and m.get("seg_cavity") is not None else 0
+                    for m in models], dtype=np.int64)
+    z_off = np.concatenate(([0], np.cumsum(Z_k)))
+    st_off = np.concatenate(([0], np.cumsum(st_k)))
+    c_off = np.concatenate(([0], np.cumsum(C_k)))
+    # (site, surface of its model) of every joined surface, in the joined order
+    site = np.repeat(np.arange(K, dtype=np.int32), S_k)
+    local = np.concatenate([np.arange(n, dtype=np.int64) for n in S_k]) if S_k.sum() else np.zeros(0, np.int64)
+    if interleave:
+        order = np.lexsort((site, local))  # surface 0 of every site, then surface 1, ...
+        site, local = site[order], local[order]
+    S = int(S_k.sum())
+    out = empty(S, int(Z_k.sum()), dt)
+    n_of = [np.diff(np.asarray(m["node_offset"], dtype=np.int64)) for m in models]
+    n = np.array([n_of[k][i] for k, i in zip(site, local)], dtype=np.int64)
+    out["node_offset"] = np.concatenate(([0], np.cumsum(n))).astype(np.int64)
+    has_cav = bool(C_k.sum())
+    node_keys = ["mass", "uvalue", "front_alpha", "back_alpha"] + (["seg_cavity"] if has_cav else [])
+    pieces = {k: [] for k in node_keys}
+    for k, i in zip(site, local):
+        m = models[k]
+        o = np.asarray(m["node_offset"], dtype=np.int64)
+        for key in ("mass", "uvalue", "front_alpha", "back_alpha"):
+            pieces[key].append(np.asarray(m[key])[o[i]:o[i + 1]])
+        if has_cav:
+            if C_k[k]:
+                sc = np.asarray(m["seg_cavity"], dtype=np.int32)[o[i]:o[i + 1]]
+                pieces["seg_cavity"].append(np.where(sc >= 0, sc + c_off[k], -1).astype(np.int32))
+            else:
+                pieces["seg_cavity"].append(np.full(o[i + 1] - o[i], -1, dtype=np.int32))
+    for key in node_keys:
+        out[key] = np.concatenate(pieces[key]) if pieces[key] else np.zeros(0)
+    if has_cav:
+        out["seg_cavity"] = out["seg_cavity"].astype(np.int32)
+        out["cavities"] = np.concatenate([np.asarray(m["cavities"], dtype=CAVITY_DTYPE) for m in models if
+                                          m.get("cavities") is not None and m.get("seg_cavity") is not None and
+                                          len(m["cavities"])])
+
+    def per_surface(key, dtype, shift=None, fill=None):
+        vals = []
+        for k in range(K):
+            m = models[k]
+            a = np.asarray(m[key]) if m.get(key) is not None else np.full(S_k[k], fill)
+            vals.append(a + (shift[k] if shift is not None else 0))
+        cat = np.concatenate(vals) if vals else np.zeros(0)
+        start = np.concatenate(([0], np.cumsum(S_k)))[:-1]
+        return cat[start[site] + local].astype(dtype)
+
+    for key in PER_SURFACE_F64:
+        out[key] = per_surface(key, np.float64)
+    for key in ("front_kind", "back_kind"):
+        out[key] = per_surface(key, np.int32)
+    for key, kind in (("front_zone", "front_kind"), ("back_zone", "back_kind")):
+        z = per_surface(key, np.int64, shift=z_off)
+        raw = per_surface(key, np.int64)
+        out[key] = np.where(out[kind] == SPACE, z, raw).astype(np.int32)  # (only a Space side's zone is a zone)
+    for key in SLOT_KEYS + ["first_node_slot"]:
+        out[key] = per_surface(key, np.int64, shift=st_off)
+    if any(m.get("front_hs_fix") is not None for m in models):
+        for key in ("front_hs_fix", "back_hs_fix"):
+            out[key] = per_surface(key, np.float64, fill=np.nan)
+    out["zone_volume"] = np.concatenate([np.asarray(m["zone_volume"], dtype=np.float64) for m in models])
+    out["zone_slot"] = np.concatenate([np.asarray(m["zone_slot"], dtype=np.int64) + st_off[k]
+                                       for k, m in enumerate(models)])
+    out["n_state"] = int(st_off[-1])
+    out["site_state_offset"] = st_off
+    return out, site.astype(np.int32)
+
+
+def weather_sites(n_sub, dt, n_sites, seed=0, t0=0.0):
+    """Weather of n_sites sites over n_sub sub-timesteps: [n_sub, n_sites, 3] (C, radians, m/s), record [k, s] being
+    site s at sub-timestep k. Every site has a dry bulb of its own mean, daily amplitude and phase, a wind speed of
+    its own, and a wind direction of its own: the directions are spread round the compass (with a slow veer), so that
+    the same wall is windward at some sites and leeward at others."""
+    rng = np.random.default_rng(seed)
+    t = t0 + dt * (1 + np.arange(n_sub))[:, None]
+    mean = rng.uniform(-5.0, 25.0, n_sites)
+    amp = rng.uniform(2.0, 12.0, n_sites)
+    phase = rng.uniform(0.0, 2 * np.pi, n_sites)
+    speed = rng.uniform(0.5, 9.0, n_sites)
+    gust = rng.uniform(0.0, 2.0, n_sites)
+    wd0 = 2 * np.pi * (np.arange(n_sites) + rng.uniform(0.0, 0.5, n_sites)) / max(n_sites, 1)
+    w = np.empty((n_sub, n_sites, 3))
+    w[:, :, 0] = mean + amp * np.sin(2 * np.pi * t / 86400.0 + phase)
+    w[:, :, 1] = np.mod(wd0 + 2 * np.pi * t / 43200.0 * rng.uniform(-1, 1, n_sites), 2 * np.pi)
+    w[:, :, 2] = np.maximum(0.0, speed + gust * np.sin(2 * np.pi * t / 3600.0 + phase))
+    return w
+
+
 # ---------------------------------------------------------------------------
 # Synthetic workloads
 def weather_series(n_sub, dt, t0=0.0, wind_speed=3.0, wind_deg=150.0):

@@ -154,6 +154,25 @@ int heat_batch_create(const heat_batch_desc *desc, heat_batch **out);
 int heat_batch_create_ex(const heat_batch_desc *desc, const heat_batch_options *opt, heat_batch **out);
 void heat_batch_destroy(heat_batch *b);
 
+/*
+ * Weather sites: one batch of buildings from several climates, each site with its own weather. A batch of K sites is K
+ * reference models marched in lockstep (model.rs:369-382 reads the weather once per sub-timestep; it reaches only the
+ * Outdoor sides: t_out, model.rs:79-96; wind speed, convection.rs:157-167; wind direction, surface.rs:37-46).
+ *   site_of_surface[n_surfaces]  the site of every surface, in [0, n_sites); 1 <= n_sites <= 65536
+ * A count outside that range is refused with HEAT_E_INVALID_ARG, a site out of range with HEAT_E_SIZE (the message
+ * names the surface), both before any device work; so is a sharded batch (opt->n_ranks > 1: HEAT_E_INVALID_ARG).
+ * n_sites == 1 gives exactly the batch heat_batch_create_ex gives. On a batch of n_sites > 1 the `weather` argument of
+ * heat_batch_march, heat_batch_march_ex, heat_batch_march_resident and heat_batch_set_weather holds n_sub * n_sites
+ * records, sub-timestep-major: record [k * n_sites + s] is site s at sub-timestep k; a call of more than 2^24 records
+ * (n_sub * n_sites) is refused with HEAT_E_INVALID_ARG. A batch has one dt (and each call
+ * one n_sub) for all its sites: buildings whose models chose different time steps go to separate batches.
+ * The planner gives every tile, cluster-resident workgroup and team surfaces of one site; a zone-connected cluster whose
+ * surfaces belong to several sites is legal and is streamed.
+ */
+int heat_batch_create_sites(const heat_batch_desc *desc, const heat_batch_options *opt, int32_t n_sites,
+                            const int32_t *site_of_surface, heat_batch **out);
+int32_t heat_batch_n_sites(const heat_batch *b); /* 1 for a batch made without sites */
+
 /* Copies every slot the path touches (node temperatures, hs, flows, irradiances, zone
  * dry-bulb) from / to the caller's SimulationState. */
 int heat_batch_upload_state(heat_batch *b, const double *state, size_t n_state);
@@ -165,7 +184,8 @@ int heat_batch_download_state(heat_batch *b, double *state, size_t n_state);
 int heat_batch_upload_inputs(heat_batch *b, const double *state, size_t n_state);
 
 /*
- * ≙ ThermalModel::march (model.rs:359-427): n_sub sub-timesteps.
+ * ≙ ThermalModel::march (model.rs:359-427): n_sub sub-timesteps. weather: n_sub records, or n_sub * n_sites records
+ * [k * n_sites + s] on a batch of weather sites (heat_batch_create_sites).
  * zone_a0 / zone_b0 (nullable, [n_zones]) are the terms of calculate_zones_abc that do
  * not come from surfaces (HVAC, luminaires, infiltration, ventilation; model.rs:500-544),
  * evaluated by the caller.
@@ -186,12 +206,13 @@ enum heat_outputs {
     HEAT_OUT_ZONE_TEMPERATURES = 4, /* dry-bulb temperature of the zones this batch owns (model.rs:410-423) */
     HEAT_OUT_ALL = 7
 };
+/* (weather: as heat_batch_march — n_sub * n_sites records [k * n_sites + s] on a batch of weather sites) */
 int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat_weather *weather, int32_t n_sub,
                         const double *zone_a0, const double *zone_b0, int32_t what);
 int heat_batch_download_outputs(heat_batch *b, double *state, size_t n_state, int32_t what);
 
 /* Same, but on the device-resident state only (no host traffic; asynchronous on the batch's
- * stream until heat_batch_synchronize / a download). */
+ * stream until heat_batch_synchronize / a download). weather: as heat_batch_march (n_sub * n_sites records with sites). */
 int heat_batch_march_resident(heat_batch *b, const heat_weather *weather, int32_t n_sub,
                               const double *zone_a0, const double *zone_b0);
 int heat_batch_synchronize(heat_batch *b); /* waits, then reports device-side numerical flags */
@@ -206,6 +227,8 @@ int heat_batch_failed_surface(const heat_batch *b, int64_t *index, int32_t *kind
  * step_surfaces ≙ iterate_surfaces over this rank's surfaces + this rank's partial (a,b) sums.
  * step_zones    ≙ the zone update from `gathered` = n_ranks consecutive partial blocks
  *                 (device pointer, layout [rank][2][n_zones]: a then b), summed in rank order. */
+/* set_weather: the weather of the next n_sub sub-timesteps (n_sub * n_sites records [k * n_sites + s] on a batch of
+ * weather sites) and the zones' a0 / b0 terms. */
 int heat_batch_set_weather(heat_batch *b, const heat_weather *weather, int32_t n_sub,
                            const double *zone_a0, const double *zone_b0);
 int heat_batch_step_surfaces(heat_batch *b, int32_t sub_step);
@@ -324,6 +347,10 @@ int heat_batch_create_shard(const heat_batch_desc *desc, const heat_batch_option
  * cluster-resident march inside the kernel's limits). summary (nullable): surfaces per kernel class [5], surfaces
  * in the cluster-resident march, its workgroups, tiles. */
 int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt, int64_t summary[8]);
+/* Same for a batch of weather sites (heat_batch_create_sites: the same argument checks and codes), and checks that every
+ * tile, cluster-resident workgroup and team holds surfaces of one site. n_sites == 1: what heat_plan_check gives. */
+int heat_plan_check_sites(const heat_batch_desc *desc, const heat_batch_options *opt, int32_t n_sites,
+                          const int32_t *site_of_surface, int64_t summary[8]);
 
 const char *heat_last_error(void);
 int heat_amd_abi_version(void);
