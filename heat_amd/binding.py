@@ -65,6 +65,16 @@ class Options(C.Structure):
                 ("no_palette", C.c_int32), ("no_fusion", C.c_int32)]
 
 
+class Series(C.Structure):
+    """heat_series (include/heat_amd.h): the schedules, driven inputs and probes of a series march"""
+    _fields_ = [("n_steps", C.c_int32), ("n_sub", C.c_int32), ("weather", C.POINTER(Weather)),
+                ("n_zone_term_steps", C.c_int32), ("zone_a0", _dp), ("zone_b0", _dp),
+                ("n_channels", C.c_int32), ("channel", _dp),
+                ("solar_front_chan", _i32p), ("solar_back_chan", _i32p), ("ir_front_chan", _i32p), ("ir_back_chan", _i32p),
+                ("solar_front_gain", _dp), ("solar_back_gain", _dp), ("ir_front_gain", _dp), ("ir_back_gain", _dp),
+                ("ir_own_face", C.POINTER(C.c_uint8)), ("n_probes", C.c_int64), ("probe_slot", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -97,6 +107,8 @@ SYMBOLS = [
     ("heat_batch_march_resident", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_synchronize", C.c_int, [_H]),
     ("heat_batch_failed_surface", C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
+    ("heat_series_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series)]),
+    ("heat_batch_march_series", C.c_int, [_H, C.POINTER(Series), _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -245,7 +257,8 @@ def make_desc(md):
     return d, keep
 
 
-HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_last_error", "heat_amd_abi_version")
+HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_last_error",
+                     "heat_amd_abi_version")
 
 
 def load_host_library(path):
@@ -312,6 +325,102 @@ def plan_check_sites(md, n_sites, site_of_surface, lib=None, **opts):
     if rc != 0:
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
     return list(summary)
+
+
+def make_series(weather, n_sub, n_sites=1, channel=None, solar_front=None, solar_back=None, ir_front=None, ir_back=None,
+                ir_own_face=None, zone_a0=None, zone_b0=None, probes=None, n_steps=None):
+    """Builds a heat_series. Returns (series, keepalive).
+    weather: n_steps * n_sub records of (dry bulb C, wind direction RADIANS, wind speed m/s), step-major — any shape
+    [..., 3] (one site) or [..., n_sites, 3], e.g. [n_steps, n_sub, 3]; n_steps is its length over n_sub (with
+    n_sub == 0: ``n_steps``, or the rows of ``channel``).
+    channel [n_steps, n_channels]; solar_front / solar_back / ir_front / ir_back: a channel number per surface (-1: not
+    driven), or a pair (channel numbers, gains); ir_own_face: bits per surface; zone_a0 / zone_b0: [n_zones] (one row for
+    every step) or [n_steps, n_zones]; probes: state slots."""
+    keep = {}
+    s = Series()
+    n_sub = int(n_sub)
+    w = np.ascontiguousarray(weather if weather is not None else np.zeros((0, 3)), dtype=np.float64)
+    if w.ndim < 2 or w.shape[-1] != 3:
+        raise ValueError("weather records are (dry bulb, wind direction, wind speed), not %s" % (w.shape,))
+    if n_sites > 1 and (w.ndim < 3 or w.shape[-2] != n_sites):
+        raise ValueError("a series of %d weather sites takes weather [..., %d, 3], not %s" % (n_sites, n_sites, w.shape))
+    if n_sites == 1 and w.ndim > 3 and w.shape[-2] != 1:
+        raise ValueError("weather of %d sites for a batch of one" % w.shape[-2])
+    records = w.size // 3
+    ch = None if channel is None else np.ascontiguousarray(channel, dtype=np.float64)
+    if ch is not None and ch.ndim != 2:
+        raise ValueError("channel is [n_steps, n_channels], not %s" % (ch.shape,))
+    if n_sub > 0:
+        if records % (n_sub * n_sites):
+            raise ValueError("%d weather records are no whole number of steps of %d x %d" % (records, n_sub, n_sites))
+        steps = records // (n_sub * n_sites)
+        if n_steps is not None and int(n_steps) != steps:
+            raise ValueError("weather of %d steps, n_steps = %d" % (steps, n_steps))
+    else:
+        steps = int(n_steps) if n_steps is not None else (len(ch) if ch is not None else 0)
+    if ch is not None and len(ch) != steps:
+        raise ValueError("channel of %d rows for %d steps" % (len(ch), steps))
+    s.n_steps, s.n_sub = steps, n_sub
+    keep["weather"] = w
+    s.weather = C.cast(w.ctypes.data, C.POINTER(Weather)) if w.size else None
+    rows = {}
+    for name, a in (("zone_a0", zone_a0), ("zone_b0", zone_b0)):
+        if a is None:
+            continue
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        rows[name] = len(a)
+        keep[name] = a
+        setattr(s, name, a.ctypes.data_as(_dp))
+    if len(set(rows.values())) > 1:
+        raise ValueError("zone_a0 and zone_b0 of different numbers of rows: %s" % rows)
+    s.n_zone_term_steps = next(iter(rows.values())) if rows else 0
+    if ch is not None:
+        keep["channel"] = ch
+        s.n_channels = ch.shape[1]
+        s.channel = ch.ctypes.data_as(_dp)
+    for name, v in (("solar_front", solar_front), ("solar_back", solar_back), ("ir_front", ir_front), ("ir_back", ir_back)):
+        if v is None:
+            continue
+        chan, gain = v if isinstance(v, tuple) else (v, None)
+        chan = np.ascontiguousarray(chan, dtype=np.int32)
+        keep[name + "_chan"] = chan
+        setattr(s, name + "_chan", chan.ctypes.data_as(_i32p))
+        if gain is not None:
+            gain = np.ascontiguousarray(gain, dtype=np.float64)
+            if gain.shape != chan.shape:
+                raise ValueError("%s: %d channel numbers, %d gains" % (name, chan.size, gain.size))
+            keep[name + "_gain"] = gain
+            setattr(s, name + "_gain", gain.ctypes.data_as(_dp))
+    if ir_own_face is not None:
+        own = np.ascontiguousarray(ir_own_face, dtype=np.uint8)
+        keep["ir_own_face"] = own
+        s.ir_own_face = own.ctypes.data_as(C.POINTER(C.c_uint8))
+    pr = np.ascontiguousarray(probes if probes is not None else [], dtype=np.int64).reshape(-1)
+    keep["probe_slot"] = pr
+    s.n_probes = len(pr)
+    s.probe_slot = pr.ctypes.data_as(_i64p) if len(pr) else None
+    return s, keep
+
+
+def _series_arrays_fit(keep, n_surfaces):
+    for k, a in keep.items():
+        if (k.endswith("_chan") or k.endswith("_gain") or k == "ir_own_face") and a.shape != (n_surfaces,):
+            raise ValueError("%s: %s for %d surfaces" % (k, a.shape, n_surfaces))
+
+
+def series_check(md, n_sites=1, lib=None, **series):
+    """heat_series_check: everything about a series that needs no device (arguments as HeatBatch.march_series). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    for k in ("zone_a0", "zone_b0"):
+        if k in skeep and skeep[k].shape[1] != int(md["n_zones"]):
+            raise ValueError("%s: rows of %d for %d zones" % (k, skeep[k].shape[1], int(md["n_zones"])))
+    rc = L.heat_series_check(C.byref(desc), int(n_sites), C.byref(s))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
 def comm_available():
@@ -423,6 +532,25 @@ class HeatBatch:
 
     def synchronize(self):
         _check(self._L.heat_batch_synchronize(self._h))
+
+    def march_series(self, weather, n_sub, **series):
+        """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
+        schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
+        a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far."""
+        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
+        _series_arrays_fit(keep, self.n_surfaces)
+        for k in ("zone_a0", "zone_b0"):
+            if k in keep and keep[k].shape[1] != self.n_zones:
+                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
+        trace = np.zeros((s.n_steps, s.n_probes))
+        failed = C.c_int32(-1)
+        rc = self._L.heat_batch_march_series(self._h, C.byref(s), trace.ctypes.data_as(_dp) if trace.size else None,
+                                             C.byref(failed))
+        if rc != 0:
+            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
+            e.failed_step, e.trace = int(failed.value), trace
+            raise e
+        return trace, int(failed.value)
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

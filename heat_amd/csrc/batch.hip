@@ -262,6 +262,12 @@ struct heat_batch {
     int n_shared = 0, n_touched = 0;
     DevBuf<int32_t> d_zlist, d_slot_of, d_shared_zone;
     std::vector<int64_t> h_orig_of;  // device surface -> surface of the caller's descriptor
+    // series march: where a surface's nodes sit in d_T (plan.hpp, node_slot_index; caller's surface order), and the
+    // caller's slots resolved to what the device keeps there (built with the first series that probes)
+    std::vector<int64_t> h_node_tile_base;
+    std::vector<int32_t> h_node_geom;
+    std::vector<int32_t> h_dev_of;  // surface of the caller's descriptor -> device surface
+    SlotResolver *resolver = nullptr;
     int64_t fail_index = -1;         // where the last reported numerical failure happened first (heat_batch_failed_surface)
     int32_t fail_kind = 0;
     std::vector<uint8_t> h_touched;
@@ -341,6 +347,7 @@ struct heat_batch {
         if (graph) (void)hipGraphDestroy(graph);
         for (auto e : ev_pool) (void)hipEventDestroy(e);
         delete pool;
+        delete resolver;
         if (h_pin) (void)hipHostFree(h_pin);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (auto e : ev_copy) if (e) (void)hipEventDestroy(e);
@@ -488,6 +495,9 @@ int build(heat_batch *b, const heat_batch_desc *d, const heat_batch_options &opt
     HIP_TRY(hipMemset(b->d_flags.p + 2, 0xff, 2 * sizeof(int)));
     HIP_TRY(hipStreamSynchronize(nullptr));
     b->h_orig_of = p.orig_of;
+    b->h_node_tile_base = std::move(p.node_tile_base);
+    b->h_node_geom = std::move(p.node_geom);
+    b->h_dev_of.assign(p.dev_of.begin(), p.dev_of.end());
     HIP_TRY(b->d_nomass_iters.zeros(p.n_nm_counters));
     if (Z > 0) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_zone_ab), 2 * Z * sizeof(double)));
 
@@ -995,6 +1005,22 @@ struct MarchGuard {
     }
 };
 
+// The per-call device buffers of a series go only when the batch's stream has run dry (declared after them: destroyed first).
+struct SeriesDrain {
+    heat_batch *b;
+    ~SeriesDrain() { (void)hipStreamSynchronize(b->stream); }
+};
+
+template <typename T>
+int series_upload(DevBuf<T> &buf, const T *src, size_t count, const char *what) {
+    hipError_t e = buf.alloc(count);
+    if (e == hipSuccess && count > 0) e = hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+        return fail(HEAT_E_DEVICE, "series march: %s (%zu bytes) on the device: %s — nothing has been marched", what, count * sizeof(T),
+                    hipGetErrorString(e));
+    return HEAT_OK;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1328,6 +1354,32 @@ static int download_impl(heat_batch *b, double *state, size_t n_state, int32_t w
     return HEAT_OK;
 }
 
+static inline StepWeather to_step_weather(const heat_weather &w) {
+    return StepWeather{w.dry_bulb, std::sqrt(w.wind_speed), std::sin(w.wind_direction), std::cos(w.wind_direction)};
+}
+
+// Room for the weather of a march call of n_sub sub-timesteps, in pinned and in device memory (heat_batch_set_weather; the
+// series march sizes it once, before its first step).
+static int grow_weather(heat_batch *b, int32_t n_sub) {
+    if ((size_t)n_sub <= b->weather_cap) return HEAT_OK;
+    const size_t n_sites = (size_t)b->n_sites;
+    HIP_TRY(hipStreamSynchronize(b->stream));  // kernels in flight read the device array that is about to go
+    if (b->h_weather) HIP_TRY(hipHostFree(b->h_weather));
+    b->h_weather = nullptr;
+    // (per site; several sites: exactly the call's length — the head kernel copies every site's records, padding
+    // included, so a batch whose calls keep one length copies nothing it does not use)
+    const size_t cap = n_sites > 1 ? (size_t)n_sub : std::max<size_t>((size_t)n_sub, 64);
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_weather), n_sites * cap * sizeof(StepWeather)));
+    HIP_TRY(b->d_weather.alloc(n_sites * cap));
+    b->weather_cap = cap;
+    b->sa.wstride = (int32_t)cap;
+    if (b->graph_exec) {  // the captured graph holds the old pointer (and the old stride)
+        (void)hipGraphExecDestroy(b->graph_exec);
+        b->graph_exec = nullptr;
+    }
+    return HEAT_OK;
+}
+
 int heat_batch_set_weather(heat_batch *b, const heat_weather *weather, int32_t n_sub, const double *zone_a0,
                            const double *zone_b0) {
     if (!b || (!weather && n_sub > 0)) return fail(HEAT_E_INVALID_ARG, "NULL argument");
@@ -1343,29 +1395,16 @@ int heat_batch_set_weather(heat_batch *b, const heat_weather *weather, int32_t n
         return fail(HEAT_E_INVALID_ARG, "n_sub %d x %d sites = %lld weather records, more than %lld per call", n_sub, (int)n_sites,
                     (long long)n_sub * (long long)n_sites, (long long)kMaxWeatherRecords);
     if (b->staged) HIP_TRY(hipEventSynchronize(b->ev_staged));
-    if ((size_t)n_sub > b->weather_cap) {
-        HIP_TRY(hipStreamSynchronize(b->stream));  // kernels in flight read the device array that is about to go
-        if (b->h_weather) HIP_TRY(hipHostFree(b->h_weather));
-        b->h_weather = nullptr;
-        // (per site; several sites: exactly the call's length — the head kernel copies every site's records, padding
-        // included, so a batch whose calls keep one length copies nothing it does not use)
-        const size_t cap = n_sites > 1 ? (size_t)n_sub : std::max<size_t>((size_t)n_sub, 64);
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_weather), n_sites * cap * sizeof(StepWeather)));
-        HIP_TRY(b->d_weather.alloc(n_sites * cap));
-        b->weather_cap = cap;
-        b->sa.wstride = (int32_t)cap;
-        if (b->graph_exec) {  // the captured graph holds the old pointer (and the old stride)
-            (void)hipGraphExecDestroy(b->graph_exec);
-            b->graph_exec = nullptr;
-        }
+    {
+        const int rc2 = grow_weather(b, n_sub);
+        if (rc2) return rc2;
     }
     // sin/cos of the wind direction as is_windward takes them (surface.rs:40). The caller's records are sub-timestep-major
     // ([k * n_sites + s]); the device's are site-major ([s * weather_cap + k], layout.hpp).
     for (size_t st = 0; st < n_sites; st++)
         for (int i = 0; i < n_sub; i++) {
             const heat_weather &w = weather[(size_t)i * n_sites + st];
-            b->h_weather[st * b->weather_cap + i] =
-                StepWeather{w.dry_bulb, std::sqrt(w.wind_speed), std::sin(w.wind_direction), std::cos(w.wind_direction)};
+            b->h_weather[st * b->weather_cap + i] = to_step_weather(w);
         }
     b->n_weather = n_sub;
     const int64_t Z = b->n_zones;
@@ -1693,6 +1732,8 @@ int heat_batch_step_zones(heat_batch *b, const double *gathered_dev, int32_t n_b
     return HEAT_OK;
 }
 
+static int march_body(heat_batch *b, int32_t n_sub);
+
 int heat_batch_march_resident(heat_batch *b, const heat_weather *weather, int32_t n_sub, const double *zone_a0,
                               const double *zone_b0) {
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
@@ -1703,8 +1744,16 @@ int heat_batch_march_resident(heat_batch *b, const heat_weather *weather, int32_
         return fail(HEAT_E_INVALID_ARG, "sharded batch without a communicator: call heat_batch_comm_init, or drive it "
                                         "with heat_batch_step_surfaces / heat_batch_step_zones and your own collective "
                                         "(a batch that shares no zone — heat_batch_set_shared_zones(b, NULL, 0) — needs neither)");
-    int rc = heat_batch_set_weather(b, weather, n_sub, zone_a0, zone_b0);
+    const int rc = heat_batch_set_weather(b, weather, n_sub, zone_a0, zone_b0);
     if (rc) return rc;
+    return march_body(b, n_sub);
+}
+
+// The body of a march call: the n_sub sub-timesteps whose weather, zone terms and counter the head has put on the device
+// (heat_batch_set_weather for heat_batch_march_resident; the head of a series step for heat_batch_march_series).
+static int march_body(heat_batch *b, int32_t n_sub) {
+    const bool exchange = b->shared_set && b->n_shared > 0;
+    int rc = HEAT_OK;
     // A march of no sub-timestep (model.rs:369: the loop body never runs) is the head kernel and nothing else: the
     // graph branch below must never capture or replay an empty graph.
     if (n_sub == 0) return HEAT_OK;
@@ -1916,6 +1965,170 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
     rc = heat_batch_synchronize(b);
     if (rc) return rc;
     return download_impl(b, state, n_state, what, true);
+}
+
+int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, int32_t *failed_step) {
+    if (failed_step) *failed_step = -1;
+    if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
+    // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
+    SeriesModel m;
+    m.n_surfaces = b->n_surf;
+    m.n_zones = b->n_zones;
+    m.first_node_slot = b->h_first_slot.data();
+    m.node_count = b->h_node_count.data();
+    for (int a = 0; a < 4; a++) m.out_slot[a] = b->h_out_slots[a].data();
+    m.zone_slot = b->h_zone_slot_h.data();
+    if (!b->resolver) b->resolver = new SlotResolver(m);
+    int rc = check_series(m, *b->resolver, b->n_sites, s, heat::last_error());
+    if (rc) return rc;
+    if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
+    const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
+    const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
+    if (!trace && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
+    if (n_steps == 0) return HEAT_OK;
+    rc = select_device(b);
+    if (rc) return rc;
+
+    // ---- the schedules and tables, in the device's order ----
+    // weather: a step's records exactly as heat_batch_set_weather lays them out in d_weather (site-major, weather_cap apart)
+    rc = grow_weather(b, n_sub);  // (once, before the first step: the pointers a captured graph holds stay valid)
+    if (rc) return rc;
+    b->n_weather = n_sub;
+    const size_t n_sites = (size_t)b->n_sites, cap = b->weather_cap;
+    const size_t n_rec = n_sub > 0 ? (n_sites - 1) * cap + (size_t)n_sub : 0;
+    std::vector<StepWeather> h_w((size_t)n_steps * n_rec, StepWeather{0.0, 0.0, 0.0, 0.0});
+    for (int k = 0; k < n_steps; k++)
+        for (size_t st = 0; st < n_sites; st++)
+            for (int i = 0; i < n_sub; i++)
+                h_w[(size_t)k * n_rec + st * cap + i] = to_step_weather(s->weather[((size_t)k * n_sub + i) * n_sites + st]);
+    // zone terms: rows of [a0[Z] | b0[Z]] as k_begin_march reads them; no rows given: one of zeros
+    const int zrows = std::max(s->n_zone_term_steps, 1);
+    std::vector<double> h_zab((size_t)zrows * 2 * Z, 0.0);
+    if (s->n_zone_term_steps > 0)
+        for (int r = 0; r < zrows; r++)
+            for (int64_t z = 0; z < Z; z++) {
+                if (s->zone_a0) h_zab[((size_t)r * 2) * Z + z] = s->zone_a0[(size_t)r * Z + z];
+                if (s->zone_b0) h_zab[((size_t)r * 2 + 1) * Z + z] = s->zone_b0[(size_t)r * Z + z];
+            }
+    // driven inputs: channel numbers and gains per DEVICE surface, structure of arrays
+    const int32_t *chan[4] = {s->solar_front_chan, s->solar_back_chan, s->ir_front_chan, s->ir_back_chan};
+    const double *gain[4] = {s->solar_front_gain, s->solar_back_gain, s->ir_front_gain, s->ir_back_gain};
+    bool driven = false, own_any = false;
+    for (int a = 0; a < 4; a++)
+        if (chan[a])
+            for (int64_t q = 0; q < S && !driven; q++) driven = chan[a][q] >= 0;
+    if (s->ir_own_face)
+        for (int64_t q = 0; q < S && !own_any; q++) own_any = (s->ir_own_face[q] & 3) != 0;
+    std::vector<int32_t> h_chan;
+    std::vector<double> h_gain[4];
+    std::vector<uint8_t> h_own;
+    std::vector<uint32_t> h_face;
+    if (driven) {
+        const int64_t *orig_of = b->h_orig_of.data();
+        h_chan.assign(4 * (size_t)S, -1);
+        for (int a = 0; a < 4; a++) {
+            if (!chan[a]) continue;
+            int32_t *dst = h_chan.data() + (size_t)a * S;
+            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) dst[d] = chan[a][orig_of[d]]; });
+            if (!gain[a]) continue;
+            h_gain[a].resize((size_t)S);
+            double *gd = h_gain[a].data();
+            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
+        }
+        if (own_any) {
+            h_own.resize((size_t)S);
+            h_face.resize(2 * (size_t)S);
+            b->pool->run(S, [&](int64_t d0, int64_t d1) {
+                for (int64_t d = d0; d < d1; d++) {
+                    const int64_t q = orig_of[d];
+                    h_own[d] = (uint8_t)(s->ir_own_face[q] & 3);
+                    h_face[d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], 0);
+                    h_face[S + d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], (int)b->h_node_count[q] - 1);
+                }
+            });
+        }
+    }
+    // probes: (buffer, index) of every probed slot
+    std::vector<uint8_t> h_pbuf((size_t)P);
+    std::vector<uint32_t> h_pidx((size_t)P);
+    for (int64_t p = 0; p < P; p++) {
+        int kind = 0, node = 0;
+        int64_t index = 0;
+        if (!b->resolver->resolve(s->probe_slot[p], kind, index, node)) return fail(HEAT_E_SIZE, "probe %lld: slot not resolved", (long long)p);
+        if (kind == PROBE_ZONE) {
+            h_pbuf[p] = (uint8_t)kProbeBufZone;
+            h_pidx[p] = (uint32_t)index;
+        } else if (kind == PROBE_NODE) {
+            h_pbuf[p] = (uint8_t)kProbeBufT;
+            h_pidx[p] = (uint32_t)node_slot_index(b->h_node_tile_base[index], b->h_node_geom[index], node);
+        } else {  // hs front, hs back, flow front, flow back: SideOut record side * S + d, as doubles
+            const int a = kind - PROBE_HS_FRONT;
+            const int64_t rec = (int64_t)(a & 1) * S + b->h_dev_of[index];
+            h_pbuf[p] = (uint8_t)kProbeBufOut;
+            h_pidx[p] = (uint32_t)(2 * rec + (a >> 1));
+        }
+    }
+
+    // ---- on the device for the duration of the call; freed on every return path, after the stream has run dry ----
+    DevBuf<StepWeather> d_w;
+    DevBuf<double> d_zab, d_channel, d_gain[4], d_trace;
+    DevBuf<int32_t> d_chan;
+    DevBuf<uint8_t> d_own, d_pbuf;
+    DevBuf<uint32_t> d_face, d_pidx;
+    DevBuf<int> d_fail;
+    SeriesDrain drain{b};
+    if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
+    if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
+    if ((rc = series_upload(d_channel, s->channel, (size_t)n_steps * NC, "channel table"))) return rc;
+    if ((rc = series_upload(d_chan, h_chan.data(), h_chan.size(), "channel numbers"))) return rc;
+    for (int a = 0; a < 4; a++)
+        if ((rc = series_upload(d_gain[a], h_gain[a].data(), h_gain[a].size(), "gains"))) return rc;
+    if ((rc = series_upload(d_own, h_own.data(), h_own.size(), "own-face bits"))) return rc;
+    if ((rc = series_upload(d_face, h_face.data(), h_face.size(), "face node table"))) return rc;
+    if ((rc = series_upload(d_pbuf, h_pbuf.data(), h_pbuf.size(), "probe table"))) return rc;
+    if ((rc = series_upload(d_pidx, h_pidx.data(), h_pidx.size(), "probe table"))) return rc;
+    const int fail_init[5] = {-1, 0, 0, 0, 0};
+    if ((rc = series_upload(d_fail, fail_init, 5, "failed step"))) return rc;
+    {
+        const hipError_t e = d_trace.alloc((size_t)n_steps * P);
+        if (e != hipSuccess)
+            return fail(HEAT_E_DEVICE, "series march: trace (%zu bytes) on the device: %s — nothing has been marched",
+                        (size_t)n_steps * P * sizeof(double), hipGetErrorString(e));
+    }
+    HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
+
+    SeriesInputs in{};
+    in.chan = d_chan.p;
+    for (int a = 0; a < 4; a++) in.gain[a] = d_gain[a].p;
+    in.own_face = d_own.p;
+    in.face = d_face.p;
+    double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
+    // ---- the steps, enqueued without waiting: head -> driven inputs -> the body of a march call of n_sub -> probes ----
+    for (int k = 0; k < n_steps; k++) {
+        launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
+                           d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
+        if (driven)
+            launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
+                                 b->stream);
+        rc = march_body(b, n_sub);
+        if (rc) return rc;
+        launch_series_probe(P, d_pbuf.p, d_pidx.p, b->d_T.p, b->d_side_out.p, b->d_zone_T.p, d_trace.p + (size_t)k * P, b->d_flags.p,
+                            d_fail.p, k, b->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    // ---- one wait: the trace and the record of the first failure travel at the end of the stream's work ----
+    int first_failed[5] = {-1, 0, 0, 0, 0};
+    if ((int64_t)n_steps * P > 0)
+        HIP_TRY(hipMemcpyAsync(trace, d_trace.p, (size_t)n_steps * P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
+    // A numerical failure: reported as heat_batch_synchronize reports it, from the flags as they were after the step that
+    // set them (the steps enqueued behind it marched on and may have added to them).
+    if (failed_step) *failed_step = first_failed[0];
+    HIP_TRY(hipMemcpy(b->d_flags.p, first_failed + 1, 4 * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return heat_batch_synchronize(b);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

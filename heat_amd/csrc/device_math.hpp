@@ -64,6 +64,11 @@ __device__ __forceinline__ double ir_to_rad_temperature(double ir) {
     return sqrt(sqrt(ir / kSigma)) - 273.15;
 }
 
+// Solar clamps of ThermalSurfaceData::march — reference src/surface.rs:916-923: front NaN or < 0 -> 0; back only
+// NaN -> 0 (its second clause tests solar_front, already clamped).
+__device__ __forceinline__ double clamp_solar_front(double s) { return (s != s || s < 0.0) ? 0.0 : s; }
+__device__ __forceinline__ double clamp_solar_back(double s) { return (s != s) ? 0.0 : s; }
+
 // 4 eps sigma (273.15 + (T_rad + T_surf)/2)^3 — reference src/surface.rs:941-948.
 __device__ __forceinline__ double rad_hs(double emis, double rad_t, double surf_t) {
     const double tm = 273.15 + (rad_t + surf_t) / 2.;

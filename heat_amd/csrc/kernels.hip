@@ -2139,10 +2139,8 @@ k_inputs_compact(int n_surf, int n_zones, const double *__restrict__ in, const d
             mirror[sl.ir_f[i]] = in[2 * (int64_t)S + i];
             mirror[sl.ir_b[i]] = in[3 * (int64_t)S + i];
         }
-        double sf = in[i];
-        if (sf != sf || sf < 0.0) sf = 0.0;  // surface.rs:916-923
-        double sb = in[S + i];
-        if (sb != sb) sb = 0.0;
+        const double sf = clamp_solar_front(in[i]);  // surface.rs:916-923
+        const double sb = clamp_solar_back(in[S + i]);
         SideDyn f, b;
         f.solar = sf * side_alpha[i];
         f.rad_t = ir_to_rad_temperature(in[2 * (int64_t)S + i]);
@@ -2191,6 +2189,80 @@ __global__ void k_begin_march(const StepWeather *__restrict__ h_weather, StepWea
         step_ptr[0] = 0;
         step_ptr[1] = last;
     }
+}
+
+// ---------------------------------------------------------------------------
+// Series march (heat_batch_march_series, batch.hip): what the caller does between two ThermalModel::march calls, done on the
+// device from schedules uploaded once. The head of a step is k_begin_march itself, reading the step's weather records and
+// zone terms from the device-resident schedules instead of the pinned staging buffers.
+//
+// k_series_inputs — the driven inputs of one step, one lane per device surface. `row` is the step's row of the channel
+// table (a few KB: cache resident); the value of an input is gain x channel, for a long-wave input plus
+// sigma (T + 273.15)^4 of the surface's own face node as it is at the start of the step where asked
+// (validate_wall_heat_transfer.rs:689-699). From there on it is k_inputs_compact: the same clamps, the same conversion, the
+// raw value into the state mirror where the batch keeps one. A field whose channel is -1 is NOT written (it keeps what the
+// last upload or series put there): a side with both fields driven is one 16-byte store, with one an 8-byte store, a
+// surface with no driven input leaves after reading its four channel numbers.
+__device__ __forceinline__ void series_side(int side, int d, int S, int c_solar, int c_ir, int own, const double *__restrict__ row,
+                                            const SeriesInputs &in, const double *__restrict__ T,
+                                            const double *__restrict__ side_alpha, SideDyn *__restrict__ dyn, const SlotArrays &sl,
+                                            double *__restrict__ mirror) {
+    if ((c_solar & c_ir) < 0) return;  // both -1
+    const int64_t rec = (int64_t)side * S + d;
+    double solar = 0.0, rad_t = 0.0;
+    if (c_solar >= 0) {
+        double raw = row[c_solar];
+        if (in.gain[side]) raw *= in.gain[side][d];
+        if (mirror != nullptr) mirror[(side ? sl.solar_b : sl.solar_f)[d]] = raw;
+        solar = (side ? clamp_solar_back(raw) : clamp_solar_front(raw)) * side_alpha[rec];
+    }
+    if (c_ir >= 0) {
+        double raw = row[c_ir];
+        if (in.gain[2 + side]) raw *= in.gain[2 + side][d];
+        if ((own >> side) & 1) {
+            const double tk = T[in.face[rec]] + 273.15;
+            const double tk2 = tk * tk;
+            raw += kSigma * (tk2 * tk2);
+        }
+        if (mirror != nullptr) mirror[(side ? sl.ir_b : sl.ir_f)[d]] = raw;
+        rad_t = ir_to_rad_temperature(raw);
+    }
+    if (c_solar >= 0 && c_ir >= 0) reinterpret_cast<double2 *>(dyn)[rec] = make_double2(solar, rad_t);
+    else if (c_solar >= 0) dyn[rec].solar = solar;
+    else dyn[rec].rad_t = rad_t;
+}
+
+__global__ void __launch_bounds__(256)
+k_series_inputs(int n_surf, const double *__restrict__ row, SeriesInputs in, const double *__restrict__ T,
+                const double *__restrict__ side_alpha, SideDyn *__restrict__ dyn, SlotArrays sl, double *__restrict__ mirror) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    const int S = n_surf;
+    if (d >= S) return;
+    const int c_sf = in.chan[d], c_sb = in.chan[(int64_t)S + d], c_if = in.chan[2 * (int64_t)S + d], c_ib = in.chan[3 * (int64_t)S + d];
+    if ((c_sf & c_sb & c_if & c_ib) < 0) return;  // every one of them -1: nothing of this surface is driven
+    const int own = in.own_face ? in.own_face[d] : 0;
+    series_side(0, d, S, c_sf, c_if, own, row, in, T, side_alpha, dyn, sl, mirror);
+    series_side(1, d, S, c_sb, c_ib, own, row, in, T, side_alpha, dyn, sl, mirror);
+}
+
+// k_series_probe — the tail of a step: one lane per probe copies a value of the device state (a node temperature, a
+// coefficient or flow of a SideOut record, a zone temperature: buffer and index resolved by the host) into the step's row
+// of the trace. The first time lane 0 finds the failure flags set it notes the step and the flags as they are then —
+// fail_step[0] = step, [1..4] = flags[0..3] (kinds, first failing surface: report_failure) — so that the host reports what a
+// march call that ended with this step would have reported, whatever the steps after it add.
+__global__ void __launch_bounds__(256)
+k_series_probe(int64_t n_probes, const uint8_t *__restrict__ buf, const uint32_t *__restrict__ idx, const double *__restrict__ T,
+               const SideOut *__restrict__ out, const double *__restrict__ zone_T, double *__restrict__ trace_row,
+               const int *__restrict__ flags, int *__restrict__ fail_step, int step) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p == 0 && fail_step[0] < 0 && flags[0] != 0) {
+        fail_step[0] = step;
+        for (int q = 0; q < 4; q++) fail_step[1 + q] = flags[q];
+    }
+    if (p >= n_probes) return;
+    const int b = buf[p];
+    const double *base = b == kProbeBufT ? T : (b == kProbeBufOut ? reinterpret_cast<const double *>(out) : zone_T);
+    trace_row[p] = base[idx[p]];
 }
 
 // ---------------------------------------------------------------------------
@@ -2453,6 +2525,20 @@ void launch_begin_march(const StepWeather *h_weather, StepWeather *weather, int 
     const int n = std::max(std::max(n_records, n_zones), 1);
     hipLaunchKernelGGL(k_begin_march, dim3((n + 255) / 256), dim3(256), 0, st, h_weather, weather, n_records, h_zone_ab, a0, b0,
                        n_zones, step_ptr, n_sub - 1);
+}
+
+void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in, const double *T, const double *side_alpha,
+                          SideDyn *dyn, const SlotArrays &sl, double *mirror, hipStream_t st) {
+    if (n_surf <= 0) return;
+    hipLaunchKernelGGL(k_series_inputs, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, row, in, T, side_alpha, dyn, sl, mirror);
+}
+
+void launch_series_probe(int64_t n_probes, const uint8_t *buf, const uint32_t *idx, const double *T, const SideOut *out,
+                         const double *zone_T, double *trace_row, const int *flags, int *fail_step, int step, hipStream_t st) {
+    // (at least one lane: lane 0 watches the failure flags also when nothing is probed)
+    const int64_t n = std::max<int64_t>(n_probes, 1);
+    hipLaunchKernelGGL(k_series_probe, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, st, n_probes, buf, idx, T, out, zone_T,
+                       trace_row, flags, fail_step, step);
 }
 
 void launch_set_step(int *step_ptr, int v, int last, hipStream_t st) {

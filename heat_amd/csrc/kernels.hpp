@@ -66,4 +66,23 @@ void launch_begin_march(const StepWeather *h_weather, StepWeather *weather, int 
                         double *a0, double *b0, int n_zones, int *step_ptr, hipStream_t st);
 void launch_set_step(int *step_ptr, int v, int last, hipStream_t st);
 
+// Series march (heat_batch_march_series): the driven inputs of a step and its probes. The head of a step is
+// launch_begin_march with device-resident sources.
+struct SeriesInputs {
+    const int32_t *chan;      // [4][S] in device surface order: solar front, solar back, long-wave front, long-wave back;
+                              // a channel of the step's row, or -1: the input is not driven
+    const double *gain[4];    // [S] each, same order; nullptr: 1
+    const uint8_t *own_face;  // [S]: bit 0 / 1 = add sigma T^4 of the own first / last node to the front / back long-wave
+                              // input; nullptr: nowhere
+    const uint32_t *face;     // [2][S]: index into the T buffer of the first / last node (read only where own_face asks)
+};
+void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in, const double *T, const double *side_alpha,
+                          SideDyn *dyn, const SlotArrays &sl, double *mirror, hipStream_t st);
+// buf / idx: where probe p reads — kProbeBufT: T[idx]; kProbeBufOut: the SideOut records as doubles (2 * record + 0 hs,
+// + 1 flow); kProbeBufZone: zone_T[idx]
+// fail_step: 5 ints, [0] = -1 until lane 0 finds the failure flags set; then the step and flags[0..3] as of that step
+constexpr int kProbeBufT = 0, kProbeBufOut = 1, kProbeBufZone = 2;
+void launch_series_probe(int64_t n_probes, const uint8_t *buf, const uint32_t *idx, const double *T, const SideOut *out,
+                         const double *zone_T, double *trace_row, const int *flags, int *fail_step, int step, hipStream_t st);
+
 }  // namespace heat

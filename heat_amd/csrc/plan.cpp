@@ -890,6 +890,13 @@ int make_plan(const heat_batch_desc *d, const heat_batch_options &opt, Plan &p, 
         node0_index[s] = node_index(dd, 0);
         nodeN_index[s] = node_index(dd, n - 1);
     }
+    p.node_tile_base.resize(S);
+    p.node_geom.resize(S);
+    for (int64_t dd = 0; dd < S; dd++) {  // (node_slot_index, plan.hpp, is node_index for the rest of the library)
+        const NodeMap &m = nmap[dd];
+        p.node_tile_base[orig_of[dd]] = m.base;
+        p.node_geom[orig_of[dd]] = (int32_t)(m.Lk | (m.M << 8) | ((m.M == 0 ? m.g : m.lane0) << 16));
+    }
 
     // ---- no-mass chunk marks: V index 14 / 15 in the class byte of a chunk's first node = one / two nodes (kernels.hip) ----
     if (!hCls.empty())
@@ -1341,6 +1348,27 @@ int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err, const 
         PLAN_REQUIRE((int64_t)p.zone_entries[pos].hs_index == rec, "side record %lld: entry %lld belongs to record %u", (long long)rec, (long long)pos, p.zone_entries[pos].hs_index);
         PLAN_REQUIRE((int64_t)p.zone_entries[pos].t_index < p.node_slots, "entry %lld: face node index", (long long)pos);
     }
+    // where the series march finds a surface's nodes (probes, own-face term): inside the T buffer, no two nodes in one
+    // place
+    PLAN_REQUIRE((int64_t)p.node_tile_base.size() == S && (int64_t)p.node_geom.size() == S, "node placement tables");
+    for (const ZoneEntry &e : p.zone_entries) {  // (the zone lists name the same face nodes)
+        const int64_t s = p.orig_of[e.hs_index % S];
+        const int n = (int)(d->node_offset[s + 1] - d->node_offset[s]);
+        PLAN_REQUIRE((int64_t)e.t_index == node_slot_index(p.node_tile_base[s], p.node_geom[s], (int64_t)e.hs_index >= S ? n - 1 : 0),
+                     "surface %lld: face node of its zone entry is not where its nodes are placed", (long long)s);
+    }
+    {
+        std::vector<uint8_t> taken((size_t)p.node_slots, 0);
+        for (int64_t s = 0; s < S; s++) {
+            const int n = (int)(d->node_offset[s + 1] - d->node_offset[s]);
+            for (int i = 0; i < n; i++) {
+                const int64_t idx = node_slot_index(p.node_tile_base[s], p.node_geom[s], i);
+                PLAN_REQUIRE(idx >= 0 && idx < p.node_slots, "surface %lld node %d: placed outside the T buffer", (long long)s, i);
+                PLAN_REQUIRE(!taken[idx], "surface %lld node %d: shares its place with another node", (long long)s, i);
+                taken[idx] = 1;
+            }
+        }
+    }
     PLAN_REQUIRE(n_space_sides == (int64_t)p.zone_entries.size(), "%lld Space-facing sides, %zu entries", (long long)n_space_sides, p.zone_entries.size());
     // cluster-resident march: workgroups inside the kernel's limits
     PLAN_REQUIRE((int64_t)p.zone_block.size() == Z, "zone_block size");
@@ -1622,6 +1650,97 @@ void ShardDesc::build(const heat_batch_desc *d, const int32_t *rank_of_surface, 
     original_index = std::move(idx);
 }
 
+// ---- series march: the host-only half (include/heat_amd.h, heat_series) ----
+bool SlotResolver::resolve(int64_t slot, int &kind, int64_t &index, int &node) {
+    auto find = [&](const std::vector<std::pair<int64_t, int64_t>> &v, int64_t &what) {
+        auto it = std::lower_bound(v.begin(), v.end(), std::make_pair(slot, (int64_t)INT64_MIN));
+        if (it == v.end() || it->first != slot) return false;
+        what = it->second;
+        return true;
+    };
+    node = 0;
+    if (!zones_built_) {
+        zones_.reserve((size_t)m_.n_zones);
+        for (int64_t z = 0; z < m_.n_zones; z++) zones_.push_back({m_.zone_slot[z], z});
+        std::sort(zones_.begin(), zones_.end());
+        zones_built_ = true;
+    }
+    if (find(zones_, index)) {
+        kind = PROBE_ZONE;
+        return true;
+    }
+    if (!nodes_built_) {
+        nodes_.reserve((size_t)m_.n_surfaces);
+        for (int64_t s = 0; s < m_.n_surfaces; s++) nodes_.push_back({m_.first_node_slot[s], s});
+        std::sort(nodes_.begin(), nodes_.end());
+        nodes_built_ = true;
+    }
+    {   // the surface whose node slots start at or before `slot` (node slots of a surface are contiguous)
+        auto it = std::upper_bound(nodes_.begin(), nodes_.end(), std::make_pair(slot, (int64_t)INT64_MAX));
+        if (it != nodes_.begin()) {
+            --it;
+            if (slot - it->first < m_.node_count[it->second]) {
+                kind = PROBE_NODE;
+                index = it->second;
+                node = (int)(slot - it->first);
+                return true;
+            }
+        }
+    }
+    if (!scalars_built_) {
+        scalars_.reserve(4 * (size_t)m_.n_surfaces);
+        for (int a = 0; a < 4; a++)
+            for (int64_t s = 0; s < m_.n_surfaces; s++) scalars_.push_back({m_.out_slot[a][s], 4 * s + a});
+        std::sort(scalars_.begin(), scalars_.end());
+        scalars_built_ = true;
+    }
+    int64_t code = 0;
+    if (!find(scalars_, code)) return false;
+    kind = PROBE_HS_FRONT + (int)(code & 3);
+    index = code >> 2;
+    return true;
+}
+
+int check_series(const SeriesModel &m, SlotResolver &res, int32_t n_sites, const heat_series *s, std::string &err) {
+    if (!s) return failp(err, HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_steps < 0 || s->n_sub < 0 || s->n_channels < 0 || s->n_probes < 0 || s->n_zone_term_steps < 0)
+        return failp(err, HEAT_E_INVALID_ARG, "negative count in series (n_steps %d, n_sub %d, n_channels %d, n_probes %lld, n_zone_term_steps %d)",
+                     s->n_steps, s->n_sub, s->n_channels, (long long)s->n_probes, s->n_zone_term_steps);
+    if (n_sites < 1 || n_sites > kMaxSites) return failp(err, HEAT_E_INVALID_ARG, "n_sites = %d outside [1, %d]", n_sites, kMaxSites);
+    if (s->n_zone_term_steps != 0 && s->n_zone_term_steps != 1 && s->n_zone_term_steps != s->n_steps)
+        return failp(err, HEAT_E_INVALID_ARG, "n_zone_term_steps = %d: must be 0, 1 or n_steps (%d)", s->n_zone_term_steps, s->n_steps);
+    // (the limit of heat_batch_set_weather, per step)
+    constexpr int64_t kMaxWeatherRecords = (int64_t)1 << 24;
+    if (n_sites > 1 && (int64_t)s->n_sub * n_sites > kMaxWeatherRecords)
+        return failp(err, HEAT_E_INVALID_ARG, "n_sub %d x %d sites = %lld weather records, more than %lld per step", s->n_sub, n_sites,
+                     (long long)s->n_sub * n_sites, (long long)kMaxWeatherRecords);
+    if (!s->weather && (int64_t)s->n_steps * s->n_sub > 0) return failp(err, HEAT_E_INVALID_ARG, "series weather is NULL");
+    if (!s->channel && (int64_t)s->n_steps * s->n_channels > 0) return failp(err, HEAT_E_INVALID_ARG, "series channel table is NULL");
+    if (!s->probe_slot && s->n_probes > 0) return failp(err, HEAT_E_INVALID_ARG, "probe_slot is NULL");
+    const int32_t *chan[4] = {s->solar_front_chan, s->solar_back_chan, s->ir_front_chan, s->ir_back_chan};
+    static const char *const input_name[4] = {"solar front", "solar back", "long-wave front", "long-wave back"};
+    for (int a = 0; a < 4; a++) {
+        if (!chan[a]) continue;
+        for (int64_t q = 0; q < m.n_surfaces; q++)
+            if (chan[a][q] < -1 || chan[a][q] >= s->n_channels)
+                return failp(err, HEAT_E_SIZE, "surface %lld: %s channel %d outside [-1, %d)", (long long)q, input_name[a], chan[a][q], s->n_channels);
+    }
+    if (s->ir_own_face)
+        for (int64_t q = 0; q < m.n_surfaces; q++)
+            for (int side = 0; side < 2; side++)
+                if ((s->ir_own_face[q] >> side & 1) && (!chan[2 + side] || chan[2 + side][q] < 0))
+                    return failp(err, HEAT_E_SIZE, "surface %lld: own-face term on its %s side, whose long-wave input is not driven (channel -1)",
+                                 (long long)q, side ? "back" : "front");
+    for (int64_t q = 0; q < s->n_probes; q++) {
+        int kind, node;
+        int64_t index;
+        if (!res.resolve(s->probe_slot[q], kind, index, node))
+            return failp(err, HEAT_E_SIZE, "probe %lld: slot %lld is not a node-temperature, hs, flow or zone slot of the descriptor", (long long)q,
+                         (long long)s->probe_slot[q]);
+    }
+    return HEAT_OK;
+}
+
 std::string &last_error() {
     thread_local std::string e;
     return e;
@@ -1674,6 +1793,26 @@ static int plan_check_impl(const heat_batch_desc *desc, const heat_batch_options
         summary[7] = n_fast_tiles + (int64_t)p.gen_tiles.size();
     }
     return HEAT_OK;
+}
+
+int heat_series_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    const int64_t S = desc->n_surfaces;
+    std::vector<int64_t> node_count((size_t)S);
+    for (int64_t q = 0; q < S; q++) node_count[q] = desc->node_offset[q + 1] - desc->node_offset[q];
+    heat::SeriesModel m;
+    m.n_surfaces = S;
+    m.n_zones = desc->n_zones;
+    m.first_node_slot = desc->first_node_slot;
+    m.node_count = node_count.data();
+    m.out_slot[0] = desc->hs_front_slot;
+    m.out_slot[1] = desc->hs_back_slot;
+    m.out_slot[2] = desc->flow_front_slot;
+    m.out_slot[3] = desc->flow_back_slot;
+    m.zone_slot = desc->zone_slot;
+    heat::SlotResolver res(m);
+    return heat::check_series(m, res, n_sites, s, heat::last_error());
 }
 
 int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt, int64_t summary[8]) {

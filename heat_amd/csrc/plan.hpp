@@ -71,6 +71,12 @@ struct Plan {
     std::vector<int32_t> cav_idx, cavref;
     std::vector<CavityDev> cavs;
 
+    // where the nodes of a surface sit in the T buffer (ORIGINAL surface order; node_slot_index below): first node slot
+    // of the surface's tile, and lanes the tile uses (Lk) | nodes per lane (M; 0: general layout) << 8 | the surface's
+    // first lane << 16
+    std::vector<int64_t> node_tile_base;
+    std::vector<int32_t> node_geom;
+
     // per-surface records (device order)
     std::vector<int32_t> meta;
     std::vector<SideConst> side;
@@ -106,6 +112,41 @@ int check_plan(const Plan &p, const heat_batch_desc *d, std::string &err, const 
 constexpr int32_t kMaxSites = 65536;
 int check_sites(const heat_batch_desc *d, const heat_batch_options &opt, int32_t n_sites, const int32_t *site_of_surface,
                 std::string &err);
+
+// Index into the T buffer of node i of a surface placed at (tile_base, geom) — Plan::node_tile_base / node_geom; the
+// layouts k_nodes_fast / k_nodes_general walk (layout.hpp).
+inline int64_t node_slot_index(int64_t tile_base, int32_t geom, int i) {
+    const int Lk = geom & 0xff, M = (geom >> 8) & 0xff, lane0 = (geom >> 16) & 0xff;
+    if (M == 0) return tile_base + (int64_t)i * kWave + lane0;
+    const int lane = lane0 + i / M, j = i % M;
+    return tile_base + ((int64_t)(j >> 1) * Lk + lane) * 2 + (j & 1);
+}
+
+// Series march (heat_series, include/heat_amd.h): the host-only half. What a series may probe is described by the
+// slots of the descriptor — or by the host copies a batch keeps of them — in the caller's surface order.
+struct SeriesModel {
+    int64_t n_surfaces = 0, n_zones = 0;
+    const int64_t *first_node_slot = nullptr, *node_count = nullptr;  // [n_surfaces]
+    const int64_t *out_slot[4] = {nullptr, nullptr, nullptr, nullptr};  // hs front, hs back, flow front, flow back
+    const int64_t *zone_slot = nullptr;                                 // [n_zones]
+};
+enum : int { PROBE_NODE = 0, PROBE_HS_FRONT = 1, PROBE_HS_BACK = 2, PROBE_FLOW_FRONT = 3, PROBE_FLOW_BACK = 4, PROBE_ZONE = 5 };
+// Slot of the caller's state -> what this path keeps there. The tables are sorted copies built when first needed, the
+// zones' first (a run that probes its zones only never pays for the 4 S scalar slots); a batch keeps its resolver.
+class SlotResolver {
+  public:
+    explicit SlotResolver(const SeriesModel &m) : m_(m) {}
+    // kind: PROBE_*; index: the surface (or zone) in the caller's numbering; node: the node (PROBE_NODE). false: the slot
+    // is none of this path's outputs.
+    bool resolve(int64_t slot, int &kind, int64_t &index, int &node);
+
+  private:
+    SeriesModel m_;
+    bool zones_built_ = false, nodes_built_ = false, scalars_built_ = false;
+    std::vector<std::pair<int64_t, int64_t>> zones_, nodes_, scalars_;  // (slot, zone) | (first slot, surface) | (slot, 4 s + a)
+};
+// Everything heat_series_check promises (include/heat_amd.h). HEAT_OK or a negative heat_status with `err` set.
+int check_series(const SeriesModel &m, SlotResolver &res, int32_t n_sites, const heat_series *s, std::string &err);
 
 // Zone-connected clusters (model.rs:556-590: surfaces exchange heat only through the zones they face): cluster id
 // per surface (-1: faces no zone) and per zone, ids dense in [0, n_clusters).

@@ -216,6 +216,71 @@ int heat_batch_download_outputs(heat_batch *b, double *state, size_t n_state, in
 int heat_batch_march_resident(heat_batch *b, const heat_weather *weather, int32_t n_sub,
                               const double *zone_a0, const double *zone_b0);
 int heat_batch_synchronize(heat_batch *b); /* waits, then reports device-side numerical flags */
+
+/*
+ * Series march: n_steps caller timesteps of n_sub sub-timesteps each in ONE call (model.rs:359-427 repeated, as the
+ * reference's validation harness repeats it: validate_wall_heat_transfer.rs:615-711). Between two ThermalModel::march calls
+ * only the weather, the irradiance slots and the zones' a0 / b0 terms change; for a free-running building all three are
+ * known before the run starts. They are uploaded once as schedules; before step k the device sets that step's driven
+ * inputs, after step k it records the probed slots into row k of a trace. The host enqueues every step without waiting
+ * and synchronises once at the end.
+ * Contract: the device state after the call and row k of the trace are what n_steps successive heat_batch_march_ex calls
+ * give when the caller writes step k's inputs into its state before call k and reads the probed slots after it (inputs as
+ * validate_wall_heat_transfer.rs:675-705 sets them). Without the own-face term the two are equal bit for bit: a step runs
+ * the kernels of a call of n_sub on the same inputs (one multiplication per driven value).
+ *   weather        n_steps * n_sub * n_sites records: [(k * n_sub + i) * n_sites + s] is site s at sub-timestep i of step k
+ *                  (n_sites = 1 on a batch made without sites). More than 2^24 records PER STEP (n_sub * n_sites, on a
+ *                  batch of several sites) are refused as in heat_batch_march.
+ *   zone terms     n_zone_term_steps = 0: a0 = b0 = 0 in every step; 1: one row [n_zones] for every step; n_steps: row k
+ *                  for step k (model.rs:500-544). With rows, a NULL zone_a0 or zone_b0 stands for zeros.
+ *   driven inputs  surfaces are numbered as in the descriptor. The value of an input of surface s at step k is
+ *                  gain[s] * channel[k * n_channels + chan[s]]; a NULL gain array is all ones. With chan[s] == -1, or a
+ *                  NULL chan array, the input keeps the value the last upload or series put on the device: the matching
+ *                  field of the side's device record (solar, or radiant temperature) is not written, also when the side's
+ *                  other field is. The values pass through the clamps of surface.rs:916-923 and the long-wave conversion of
+ *                  surface.rs:647,692 exactly as an uploaded slot does (the same device functions). Zone temperatures are
+ *                  never driven: they are the path's own output.
+ *   ir_own_face    (nullable) the long-wave feedback of the reference's harness (validate_wall_heat_transfer.rs:689-699):
+ *                  with bit 0 / bit 1 of ir_own_face[s] set, SIGMA * (T + 273.15)^4 of the surface's own first / last node
+ *                  temperature AT THE START OF THE STEP is added to its driven front / back long-wave irradiance. A bit on
+ *                  a side whose long-wave channel is -1 is refused (HEAT_E_SIZE, naming the surface).
+ *   probes         slots of the caller's SimulationState this path owns: node temperatures, hs and convective flow front /
+ *                  back, zone dry-bulb. trace[k * n_probes + p] is slot probe_slot[p] after step k.
+ * heat_series_check validates everything that needs no device, and heat_batch_march_series calls the same checks first,
+ * before any device work: a NULL series, a negative count, a NULL array that a positive count needs ->
+ * HEAT_E_INVALID_ARG; n_zone_term_steps other than 0, 1, n_steps -> HEAT_E_INVALID_ARG; a channel index outside
+ * [-1, n_channels) -> HEAT_E_SIZE naming the surface; a probe slot that is not a node-temperature, hs, flow or zone slot of
+ * the descriptor (an irradiance slot, a slot of another module) -> HEAT_E_SIZE naming the probe. A sharded batch
+ * (n_ranks > 1) is refused with HEAT_E_INVALID_ARG, as heat_batch_create_sites refuses one; weather sites are supported.
+ * n_steps == 0 marches nothing and sets nothing. n_sub == 0 with n_steps > 0 still sets the inputs and records the probes
+ * of every step (model.rs:369: the loop body never runs). n_probes == 0 and n_channels == 0 are legal (trace may be NULL
+ * when it has no element).
+ * A numerical failure is reported as heat_batch_synchronize reports it (same codes; heat_batch_failed_surface works);
+ * *failed_step (nullable) is the first step after which the failure flags were set, -1 when there was none. Trace rows from
+ * that step on are unspecified. The call returns after one synchronisation, with the trace on the host; the device state is
+ * complete (heat_batch_download_state / _outputs fetch anything else) and the caller's zone slots are older than the
+ * device's, as after a resident march without a download (heat_batch_upload_inputs). The schedules live on the device for
+ * the duration of the call; one too large for it fails with HEAT_E_DEVICE before anything is marched — cut the run into
+ * several series: a series of k steps followed by one of n - k gives the same bits as one of n.
+ */
+typedef struct heat_series {
+    int32_t n_steps;            /* caller timesteps (march calls) in this series, >= 0 */
+    int32_t n_sub;              /* sub-timesteps per step (ThermalModel::dt_subdivisions), >= 0 */
+    const heat_weather *weather;/* n_steps * n_sub * n_sites records, [(k * n_sub + i) * n_sites + s] */
+    int32_t n_zone_term_steps;  /* 0 (none), 1 (one row for every step) or n_steps */
+    const double *zone_a0, *zone_b0;      /* [n_zone_term_steps][n_zones] */
+    int32_t n_channels;
+    const double *channel;                /* [n_steps][n_channels] */
+    const int32_t *solar_front_chan, *solar_back_chan, *ir_front_chan, *ir_back_chan;   /* [n_surfaces]; -1 / NULL: not driven */
+    const double *solar_front_gain, *solar_back_gain, *ir_front_gain, *ir_back_gain;    /* [n_surfaces]; NULL = 1 */
+    const uint8_t *ir_own_face;           /* [n_surfaces], nullable */
+    int64_t n_probes;
+    const int64_t *probe_slot;            /* [n_probes] */
+} heat_series;
+
+int heat_series_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s); /* host-only */
+int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace /* [n_steps][n_probes] */,
+                            int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident
