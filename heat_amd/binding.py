@@ -75,6 +75,16 @@ class Series(C.Structure):
                 ("ir_own_face", C.POINTER(C.c_uint8)), ("n_probes", C.c_int64), ("probe_slot", _i64p)]
 
 
+class ZoneLoads(C.Structure):
+    """heat_zone_loads (include/heat_amd.h): gains, air flows and thermostats a series forms on the device at every step"""
+    _fields_ = [("n_gains", C.c_int64), ("gain_zone", _i32p), ("gain_chan", _i32p), ("gain_factor", _dp),
+                ("n_flows", C.c_int64), ("flow_zone", _i32p), ("flow_volume_chan", _i32p), ("flow_temp_chan", _i32p),
+                ("flow_volume_gain", _dp),
+                ("n_thermostats", C.c_int64), ("th_sensor_zone", _i32p), ("th_target_zone", _i32p), ("th_heat_chan", _i32p),
+                ("th_cool_chan", _i32p), ("th_heat_power", _dp), ("th_cool_power", _dp), ("th_band", _dp),
+                ("th_mode", C.POINTER(C.c_uint8))]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -109,6 +119,8 @@ SYMBOLS = [
     ("heat_batch_failed_surface", C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]),
     ("heat_series_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series)]),
     ("heat_batch_march_series", C.c_int, [_H, C.POINTER(Series), _dp, _i32p]),
+    ("heat_zone_loads_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(ZoneLoads)]),
+    ("heat_batch_march_series_loads", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -257,8 +269,8 @@ def make_desc(md):
     return d, keep
 
 
-HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_last_error",
-                     "heat_amd_abi_version")
+HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
+                     "heat_last_error", "heat_amd_abi_version")
 
 
 def load_host_library(path):
@@ -423,6 +435,68 @@ def series_check(md, n_sites=1, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+_GAIN_KEYS = ("zone", "chan", "factor")
+_FLOW_KEYS = ("zone", "volume_chan", "temp_chan", "volume_gain")
+_TH_KEYS = ("sensor_zone", "target_zone", "heat_chan", "cool_chan", "heat_power", "cool_power", "band", "mode")
+
+
+def make_zone_loads(gains=None, flows=None, thermostats=None):
+    """Builds a heat_zone_loads. Returns (loads, keepalive). Each group is a dict of equally long arrays (or a tuple in
+    the order of the keys):
+    gains        zone, chan, factor (optional: 1)
+    flows        zone, volume_chan, temp_chan, volume_gain (optional: 1)
+    thermostats  sensor_zone, target_zone, heat_chan, cool_chan (-1: none), heat_power, cool_power, band,
+                 mode (optional: all off). keepalive["th_mode"] is the array the march updates in place."""
+    keep = {}
+    l = ZoneLoads()
+
+    def group(v, keys, what):
+        if v is None:
+            return {}
+        if not isinstance(v, dict):
+            v = dict(zip(keys, v))
+        unknown = set(v) - set(keys)
+        if unknown:
+            raise ValueError("%s: unknown %s (known: %s)" % (what, sorted(unknown), ", ".join(keys)))
+        return {k: a for k, a in v.items() if a is not None}
+
+    def put(prefix, g, keys, n_optional, what):
+        n = None
+        for i, k in enumerate(keys):
+            if k not in g:
+                if i < len(keys) - n_optional and g:
+                    raise ValueError("%s: %s is missing" % (what, k))
+                continue
+            dtype = np.uint8 if k == "mode" else (np.int32 if k.endswith("zone") or k.endswith("chan") else np.float64)
+            a = np.atleast_1d(np.array(g[k], dtype=dtype))  # (a copy: the mode bytes are written by the march)
+            if a.ndim != 1 or (n is not None and len(a) != n):
+                raise ValueError("%s: %s of shape %s, %s terms" % (what, k, a.shape, n))
+            n = len(a)
+            keep[prefix + k] = a
+            setattr(l, prefix + k, a.ctypes.data_as({np.uint8: C.POINTER(C.c_uint8), np.int32: _i32p, np.float64: _dp}[dtype]))
+        return n or 0
+
+    l.n_gains = put("gain_", group(gains, _GAIN_KEYS, "gains"), _GAIN_KEYS, 1, "gains")
+    l.n_flows = put("flow_", group(flows, _FLOW_KEYS, "flows"), _FLOW_KEYS, 1, "flows")
+    th = group(thermostats, _TH_KEYS, "thermostats")
+    if th and "mode" not in th:
+        th["mode"] = np.zeros(len(np.atleast_1d(th["sensor_zone"])) if "sensor_zone" in th else 0, np.uint8)
+    l.n_thermostats = put("th_", th, _TH_KEYS, 1, "thermostats")
+    return l, keep
+
+
+def zone_loads_check(md, loads=None, lib=None, **series):
+    """heat_zone_loads_check: everything about the zone loads of a series that needs no device (series arguments as
+    HeatBatch.march_series; loads: the arguments of make_zone_loads). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    l, lkeep = make_zone_loads(**(loads or {}))
+    rc = L.heat_zone_loads_check(C.byref(desc), C.byref(s), C.byref(l))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -533,10 +607,13 @@ class HeatBatch:
     def synchronize(self):
         _check(self._L.heat_batch_synchronize(self._h))
 
-    def march_series(self, weather, n_sub, **series):
+    def march_series(self, weather, n_sub, loads=None, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
-        a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far."""
+        a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
+        loads (a dict of make_zone_loads' arguments: gains, flows, thermostats): heat_batch_march_series_loads — the zones'
+        gains, air flows and thermostats formed on the device at every step. Returns (trace, failed_step,
+        applied [n_steps, n_thermostats], modes [n_thermostats]: pass them as thermostats["mode"] to the next series)."""
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
         _series_arrays_fit(keep, self.n_surfaces)
         for k in ("zone_a0", "zone_b0"):
@@ -544,13 +621,22 @@ class HeatBatch:
                 raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
         trace = np.zeros((s.n_steps, s.n_probes))
         failed = C.c_int32(-1)
-        rc = self._L.heat_batch_march_series(self._h, C.byref(s), trace.ctypes.data_as(_dp) if trace.size else None,
-                                             C.byref(failed))
+        if loads is None:
+            rc = self._L.heat_batch_march_series(self._h, C.byref(s), trace.ctypes.data_as(_dp) if trace.size else None,
+                                                 C.byref(failed))
+        else:
+            l, lkeep = make_zone_loads(**loads)
+            applied = np.zeros((s.n_steps, l.n_thermostats))
+            rc = self._L.heat_batch_march_series_loads(self._h, C.byref(s), C.byref(l),
+                                                       trace.ctypes.data_as(_dp) if trace.size else None,
+                                                       applied.ctypes.data_as(_dp) if applied.size else None, C.byref(failed))
         if rc != 0:
             e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
             e.failed_step, e.trace = int(failed.value), trace
             raise e
-        return trace, int(failed.value)
+        if loads is None:
+            return trace, int(failed.value)
+        return trace, int(failed.value), applied, lkeep.get("th_mode", np.zeros(0, np.uint8))
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -1967,7 +1967,9 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
     return download_impl(b, state, n_state, what, true);
 }
 
-int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, int32_t *failed_step) {
+// heat_batch_march_series[_loads]: l == nullptr, or loads without a term, is the series without loads.
+static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, double *trace, double *applied,
+                             int32_t *failed_step) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -1981,7 +1983,11 @@ int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, 
     if (!b->resolver) b->resolver = new SlotResolver(m);
     int rc = check_series(m, *b->resolver, b->n_sites, s, heat::last_error());
     if (rc) return rc;
+    rc = check_zone_loads(b->n_zones, s->n_channels, l, heat::last_error());
+    if (rc) return rc;
     if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
+    const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
+    const int64_t NT = loads ? l->n_thermostats : 0;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!trace && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -2069,7 +2075,19 @@ int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, 
         }
     }
 
+    // zone loads: the term lists sorted by zone with CSR offsets (plan.hpp), the mode bytes in the caller's order
+    ZoneLoadTables zt;
+    std::vector<uint8_t> h_mode;
+    if (loads) {
+        build_zone_load_tables(Z, l, zt);
+        h_mode.assign((size_t)NT, 0);
+        if (l->th_mode) std::copy(l->th_mode, l->th_mode + NT, h_mode.begin());
+    }
+
     // ---- on the device for the duration of the call; freed on every return path, after the stream has run dry ----
+    DevBuf<int32_t> d_zl_i32;
+    DevBuf<double> d_zl_f64, d_applied;
+    DevBuf<uint8_t> d_mode;
     DevBuf<StepWeather> d_w;
     DevBuf<double> d_zab, d_channel, d_gain[4], d_trace;
     DevBuf<int32_t> d_chan;
@@ -2095,6 +2113,41 @@ int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, 
             return fail(HEAT_E_DEVICE, "series march: trace (%zu bytes) on the device: %s — nothing has been marched",
                         (size_t)n_steps * P * sizeof(double), hipGetErrorString(e));
     }
+    ZoneLoadsDev zl{};
+    if (loads) {
+        // (packed into two uploads, not thirteen: each one is an allocation and a pageable copy in the call's set-up)
+        const std::vector<int32_t> *i32[8] = {&zt.off, &zt.gain_chan, &zt.flow_volume_chan, &zt.flow_temp_chan, &zt.th_sensor,
+                                              &zt.th_heat_chan, &zt.th_cool_chan, &zt.th_orig};
+        const std::vector<double> *f64[5] = {&zt.gain_factor, &zt.flow_volume_gain, &zt.th_heat_power, &zt.th_cool_power, &zt.th_half_band};
+        std::vector<int32_t> h_i32;
+        std::vector<double> h_f64;
+        size_t at_i32[8], at_f64[5];
+        for (int a = 0; a < 8; a++) { at_i32[a] = h_i32.size(); h_i32.insert(h_i32.end(), i32[a]->begin(), i32[a]->end()); }
+        for (int a = 0; a < 5; a++) { at_f64[a] = h_f64.size(); h_f64.insert(h_f64.end(), f64[a]->begin(), f64[a]->end()); }
+        if ((rc = series_upload(d_zl_i32, h_i32.data(), h_i32.size(), "zone load tables"))) return rc;
+        if ((rc = series_upload(d_zl_f64, h_f64.data(), h_f64.size(), "zone load tables"))) return rc;
+        if ((rc = series_upload(d_mode, h_mode.data(), h_mode.size(), "thermostat modes"))) return rc;
+        if (applied) {
+            const hipError_t e = d_applied.alloc((size_t)n_steps * NT);
+            if (e != hipSuccess)
+                return fail(HEAT_E_DEVICE, "series march: applied powers (%zu bytes) on the device: %s — nothing has been marched",
+                            (size_t)n_steps * NT * sizeof(double), hipGetErrorString(e));
+        }
+        zl.off = d_zl_i32.p + at_i32[0];
+        zl.gain_chan = d_zl_i32.p + at_i32[1];
+        zl.flow_volume_chan = d_zl_i32.p + at_i32[2];
+        zl.flow_temp_chan = d_zl_i32.p + at_i32[3];
+        zl.th_sensor = d_zl_i32.p + at_i32[4];
+        zl.th_heat_chan = d_zl_i32.p + at_i32[5];
+        zl.th_cool_chan = d_zl_i32.p + at_i32[6];
+        zl.th_orig = d_zl_i32.p + at_i32[7];
+        zl.gain_factor = d_zl_f64.p + at_f64[0];
+        zl.flow_volume_gain = d_zl_f64.p + at_f64[1];
+        zl.th_heat_power = d_zl_f64.p + at_f64[2];
+        zl.th_cool_power = d_zl_f64.p + at_f64[3];
+        zl.th_half_band = d_zl_f64.p + at_f64[4];
+        zl.th_mode = d_mode.p;
+    }
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
 
     SeriesInputs in{};
@@ -2103,10 +2156,13 @@ int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, 
     in.own_face = d_own.p;
     in.face = d_face.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    // ---- the steps, enqueued without waiting: head -> driven inputs -> the body of a march call of n_sub -> probes ----
+    // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> the body of a march call of n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
                            d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
+        if (loads)
+            launch_series_zone_loads((int)Z, zl, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
+                                     d_applied.p ? d_applied.p + (size_t)k * NT : nullptr, b->d_flags.p, b->stream);
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
@@ -2120,6 +2176,10 @@ int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, 
     int first_failed[5] = {-1, 0, 0, 0, 0};
     if ((int64_t)n_steps * P > 0)
         HIP_TRY(hipMemcpyAsync(trace, d_trace.p, (size_t)n_steps * P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (d_applied.p && (int64_t)n_steps * NT > 0)
+        HIP_TRY(hipMemcpyAsync(applied, d_applied.p, (size_t)n_steps * NT * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (loads && l->th_mode && NT > 0)
+        HIP_TRY(hipMemcpyAsync(l->th_mode, d_mode.p, (size_t)NT, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2129,6 +2189,15 @@ int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, 
     HIP_TRY(hipMemcpy(b->d_flags.p, first_failed + 1, 4 * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return heat_batch_synchronize(b);
+}
+
+int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, int32_t *failed_step) {
+    return march_series_impl(b, s, nullptr, trace, nullptr, failed_step);
+}
+
+int heat_batch_march_series_loads(heat_batch *b, const heat_series *s, const heat_zone_loads *l, double *trace, double *applied,
+                                  int32_t *failed_step) {
+    return march_series_impl(b, s, l, trace, applied, failed_step);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

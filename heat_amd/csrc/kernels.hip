@@ -2265,6 +2265,69 @@ k_series_probe(int64_t n_probes, const uint8_t *__restrict__ buf, const uint32_t
     trace_row[p] = base[idx[p]];
 }
 
+// k_series_zone_loads — the zone loads of one step (heat_zone_loads, include/heat_amd.h), between the step's head and its
+// driven inputs: one lane per zone walks the zone's gains, flows and thermostats (CSR ranges of lists sorted by zone, the
+// caller's order kept inside a zone) and adds them to the a0 / b0 the head has just written; a zone without terms leaves
+// after reading its offsets. `row` is the step's row of the channel table (a few KB: cache resident). A thermostat reads its
+// sensor zone's temperature as the step before left it — nothing in this kernel writes zone_T — and belongs to the lane
+// of its target zone alone: its mode byte and its element of `applied` have one writer.
+// Every product and sum is one rounded operation, in the order the header gives: the host applying the same rule between
+// march calls reproduces the bits. Hence no contraction, and the air properties are written out here: device_math.hpp's
+// air_heat_capacity is compiled where a + b * c contracts to a fused multiply-add.
+// A term that turns a zone's a0 or b0 into NaN (a NaN channel value, say) is reported as the zone's failure here: the zone
+// update keeps the temperature of a zone whose b is NaN (model.rs:662-668, |b| > 1e-9 is false) and would hide it.
+#pragma clang fp contract(off)
+__global__ void __launch_bounds__(256)
+k_series_zone_loads(int n_zones, ZoneLoadsDev zl, const double *__restrict__ row, const double *__restrict__ zone_T,
+                    double *__restrict__ a0, double *__restrict__ b0, double *__restrict__ applied_row, int *__restrict__ flags) {
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= n_zones) return;
+    const int32_t *og = zl.off, *of = zl.off + (n_zones + 1), *ot = zl.off + 2 * (n_zones + 1);
+    const int g0 = og[z], g1 = og[z + 1], f0 = of[z], f1 = of[z + 1], t0 = ot[z], t1 = ot[z + 1];
+    if (g0 == g1 && f0 == f1 && t0 == t1) return;
+    double a = a0[z], b = b0[z];
+    const bool clean = a == a && b == b;
+    for (int i = g0; i < g1; i++) {  // model.rs:500-516
+        const double p = zl.gain_factor[i] * row[zl.gain_chan[i]];
+        a = a + p;
+    }
+    for (int i = f0; i < f1; i++) {  // model.rs:522-544
+        const double v = zl.flow_volume_gain[i] * row[zl.flow_volume_chan[i]];
+        const double t_in = row[zl.flow_temp_chan[i]];
+        const double tk = t_in + 273.15;
+        const double rho = 101325. * 28.97 / (8314.46261815324 * tk);  // gas.rs:175-179
+        const double cp = 1002.7370 + 1.2324e-2 * tk;                  // gas.rs:49,165-167
+        const double m = (rho * v) * cp;
+        const double mt = m * t_in;
+        a = a + mt;
+        b = b + m;
+    }
+    for (int i = t0; i < t1; i++) {
+        const int orig = zl.th_orig[i];
+        const int hc = zl.th_heat_chan[i], cc = zl.th_cool_chan[i];
+        const double ts = zone_T[zl.th_sensor[i]], d = zl.th_half_band[i];
+        int mode = zl.th_mode[orig];
+        if (hc >= 0) {
+            const double h = row[hc];
+            if (ts < h - d) mode = 1;
+            else if (mode == 1 && ts > h + d) mode = 0;
+        }
+        if (mode != 1 && cc >= 0) {
+            const double c = row[cc];
+            if (ts > c + d) mode = 2;
+            else if (mode == 2 && ts < c - d) mode = 0;
+        }
+        const double power = mode == 1 ? zl.th_heat_power[i] : (mode == 2 ? -zl.th_cool_power[i] : 0.0);
+        a = a + power;
+        zl.th_mode[orig] = (uint8_t)mode;
+        if (applied_row != nullptr) applied_row[orig] = power;
+    }
+    a0[z] = a;
+    b0[z] = b;
+    if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
+}
+#pragma clang fp contract(fast)
+
 // ---------------------------------------------------------------------------
 // Launch wrappers (host).
 static inline int blocks_for_waves(int n_waves) { return (n_waves + 3) / 4; }
@@ -2531,6 +2594,13 @@ void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in,
                           SideDyn *dyn, const SlotArrays &sl, double *mirror, hipStream_t st) {
     if (n_surf <= 0) return;
     hipLaunchKernelGGL(k_series_inputs, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, row, in, T, side_alpha, dyn, sl, mirror);
+}
+
+void launch_series_zone_loads(int n_zones, const ZoneLoadsDev &zl, const double *row, const double *zone_T, double *a0, double *b0,
+                              double *applied_row, int *flags, hipStream_t st) {
+    if (n_zones <= 0) return;
+    hipLaunchKernelGGL(k_series_zone_loads, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, zl, row, zone_T, a0, b0, applied_row,
+                       flags);
 }
 
 void launch_series_probe(int64_t n_probes, const uint8_t *buf, const uint32_t *idx, const double *T, const SideOut *out,

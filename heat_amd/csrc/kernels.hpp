@@ -78,6 +78,22 @@ struct SeriesInputs {
 };
 void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in, const double *T, const double *side_alpha,
                           SideDyn *dyn, const SlotArrays &sl, double *mirror, hipStream_t st);
+// Zone loads of a series step (heat_zone_loads, include/heat_amd.h; tables: plan.hpp, ZoneLoadTables): launched between the
+// step's head and its driven inputs, one lane per zone.
+struct ZoneLoadsDev {
+    const int32_t *off;  // [3][n_zones + 1]: CSR offsets of the zone's gains, flows, thermostats
+    const int32_t *gain_chan;
+    const double *gain_factor;
+    const int32_t *flow_volume_chan, *flow_temp_chan;
+    const double *flow_volume_gain;
+    const int32_t *th_sensor, *th_heat_chan, *th_cool_chan, *th_orig;
+    const double *th_heat_power, *th_cool_power, *th_half_band;
+    uint8_t *th_mode;  // [n_thermostats], the caller's order
+};
+// row: the step's row of the channel table; applied_row: the step's row of `applied` (caller's order), or nullptr;
+// flags: the batch's failure flags (a term that makes a zone's a0 / b0 NaN is reported as that zone's failure)
+void launch_series_zone_loads(int n_zones, const ZoneLoadsDev &zl, const double *row, const double *zone_T, double *a0, double *b0,
+                              double *applied_row, int *flags, hipStream_t st);
 // buf / idx: where probe p reads — kProbeBufT: T[idx]; kProbeBufOut: the SideOut records as doubles (2 * record + 0 hs,
 // + 1 flow); kProbeBufZone: zone_T[idx]
 // fail_step: 5 ints, [0] = -1 until lane 0 finds the failure flags set; then the step and flags[0..3] as of that step

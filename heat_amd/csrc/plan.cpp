@@ -1741,6 +1741,113 @@ int check_series(const SeriesModel &m, SlotResolver &res, int32_t n_sites, const
     return HEAT_OK;
 }
 
+// ---- zone loads of a series (include/heat_amd.h, heat_zone_loads) ----
+int check_zone_loads(int64_t n_zones, int32_t n_channels, const heat_zone_loads *l, std::string &err) {
+    if (!l) return HEAT_OK;
+    if (l->n_gains < 0 || l->n_flows < 0 || l->n_thermostats < 0)
+        return failp(err, HEAT_E_INVALID_ARG, "negative count in zone loads (n_gains %lld, n_flows %lld, n_thermostats %lld)",
+                     (long long)l->n_gains, (long long)l->n_flows, (long long)l->n_thermostats);
+    // (the tables number their terms with 32 bits)
+    if (l->n_gains > INT32_MAX || l->n_flows > INT32_MAX || l->n_thermostats > INT32_MAX)
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 terms in zone loads (n_gains %lld, n_flows %lld, n_thermostats %lld)",
+                     (long long)l->n_gains, (long long)l->n_flows, (long long)l->n_thermostats);
+    if (l->n_gains > 0 && (!l->gain_zone || !l->gain_chan)) return failp(err, HEAT_E_INVALID_ARG, "gain_zone or gain_chan is NULL");
+    if (l->n_flows > 0 && (!l->flow_zone || !l->flow_volume_chan || !l->flow_temp_chan))
+        return failp(err, HEAT_E_INVALID_ARG, "flow_zone, flow_volume_chan or flow_temp_chan is NULL");
+    if (l->n_thermostats > 0 && (!l->th_sensor_zone || !l->th_target_zone || !l->th_heat_chan || !l->th_cool_chan ||
+                                 !l->th_heat_power || !l->th_cool_power || !l->th_band))
+        return failp(err, HEAT_E_INVALID_ARG, "a thermostat array is NULL (only th_mode may be)");
+    auto zone_ok = [&](int32_t z) { return z >= 0 && z < n_zones; };
+    auto chan_ok = [&](int32_t c) { return c >= 0 && c < n_channels; };
+    for (int64_t i = 0; i < l->n_gains; i++) {
+        if (!zone_ok(l->gain_zone[i]))
+            return failp(err, HEAT_E_SIZE, "gain %lld: zone %d outside [0, %lld)", (long long)i, l->gain_zone[i], (long long)n_zones);
+        if (!chan_ok(l->gain_chan[i]))
+            return failp(err, HEAT_E_SIZE, "gain %lld: channel %d outside [0, %d)", (long long)i, l->gain_chan[i], n_channels);
+    }
+    for (int64_t i = 0; i < l->n_flows; i++) {
+        if (!zone_ok(l->flow_zone[i]))
+            return failp(err, HEAT_E_SIZE, "flow %lld: zone %d outside [0, %lld)", (long long)i, l->flow_zone[i], (long long)n_zones);
+        if (!chan_ok(l->flow_volume_chan[i]))
+            return failp(err, HEAT_E_SIZE, "flow %lld: volume channel %d outside [0, %d)", (long long)i, l->flow_volume_chan[i], n_channels);
+        if (!chan_ok(l->flow_temp_chan[i]))
+            return failp(err, HEAT_E_SIZE, "flow %lld: temperature channel %d outside [0, %d)", (long long)i, l->flow_temp_chan[i], n_channels);
+    }
+    for (int64_t i = 0; i < l->n_thermostats; i++) {
+        if (!zone_ok(l->th_sensor_zone[i]))
+            return failp(err, HEAT_E_SIZE, "thermostat %lld: sensor zone %d outside [0, %lld)", (long long)i, l->th_sensor_zone[i], (long long)n_zones);
+        if (!zone_ok(l->th_target_zone[i]))
+            return failp(err, HEAT_E_SIZE, "thermostat %lld: target zone %d outside [0, %lld)", (long long)i, l->th_target_zone[i], (long long)n_zones);
+        const int32_t hc = l->th_heat_chan[i], cc = l->th_cool_chan[i];
+        if (hc != -1 && !chan_ok(hc))
+            return failp(err, HEAT_E_SIZE, "thermostat %lld: heating setpoint channel %d outside [-1, %d)", (long long)i, hc, n_channels);
+        if (cc != -1 && !chan_ok(cc))
+            return failp(err, HEAT_E_SIZE, "thermostat %lld: cooling setpoint channel %d outside [-1, %d)", (long long)i, cc, n_channels);
+        if (hc == -1 && cc == -1)
+            return failp(err, HEAT_E_SIZE, "thermostat %lld: neither a heating nor a cooling setpoint channel", (long long)i);
+        const double v[3] = {l->th_heat_power[i], l->th_cool_power[i], l->th_band[i]};
+        static const char *const name[3] = {"heating power", "cooling power", "band"};
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(v[a]) || v[a] < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "thermostat %lld: %s %g is negative or not finite", (long long)i, name[a], v[a]);
+        if (l->th_mode && l->th_mode[i] > 2)
+            return failp(err, HEAT_E_INVALID_ARG, "thermostat %lld: mode %d is none of 0 (off), 1 (heating), 2 (cooling)", (long long)i,
+                         (int)l->th_mode[i]);
+    }
+    return HEAT_OK;
+}
+
+void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadTables &t) {
+    const size_t Z = (size_t)n_zones;
+    t = ZoneLoadTables();
+    t.off.assign(3 * (Z + 1), 0);
+    if (!l) return;
+    // a counting sort by zone: stable, so the caller's order survives inside a zone. place[i] = where term i goes.
+    auto csr = [&](int64_t n, const int32_t *zone, int32_t *off, std::vector<int32_t> &place) {
+        place.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) off[zone[i] + 1]++;
+        for (size_t z = 0; z < Z; z++) off[z + 1] += off[z];
+        std::vector<int32_t> next(off, off + Z);
+        for (int64_t i = 0; i < n; i++) place[(size_t)i] = next[(size_t)zone[i]]++;
+    };
+    std::vector<int32_t> place;
+    csr(l->n_gains, l->gain_zone, t.off.data(), place);
+    t.gain_chan.resize(place.size());
+    t.gain_factor.resize(place.size());
+    for (size_t i = 0; i < place.size(); i++) {
+        t.gain_chan[(size_t)place[i]] = l->gain_chan[i];
+        t.gain_factor[(size_t)place[i]] = l->gain_factor ? l->gain_factor[i] : 1.0;
+    }
+    csr(l->n_flows, l->flow_zone, t.off.data() + (Z + 1), place);
+    t.flow_volume_chan.resize(place.size());
+    t.flow_temp_chan.resize(place.size());
+    t.flow_volume_gain.resize(place.size());
+    for (size_t i = 0; i < place.size(); i++) {
+        t.flow_volume_chan[(size_t)place[i]] = l->flow_volume_chan[i];
+        t.flow_temp_chan[(size_t)place[i]] = l->flow_temp_chan[i];
+        t.flow_volume_gain[(size_t)place[i]] = l->flow_volume_gain ? l->flow_volume_gain[i] : 1.0;
+    }
+    csr(l->n_thermostats, l->th_target_zone, t.off.data() + 2 * (Z + 1), place);
+    const size_t n = place.size();
+    t.th_sensor.resize(n);
+    t.th_heat_chan.resize(n);
+    t.th_cool_chan.resize(n);
+    t.th_orig.resize(n);
+    t.th_heat_power.resize(n);
+    t.th_cool_power.resize(n);
+    t.th_half_band.resize(n);
+    for (size_t i = 0; i < n; i++) {
+        const size_t p = (size_t)place[i];
+        t.th_sensor[p] = l->th_sensor_zone[i];
+        t.th_heat_chan[p] = l->th_heat_chan[i];
+        t.th_cool_chan[p] = l->th_cool_chan[i];
+        t.th_orig[p] = (int32_t)i;
+        t.th_heat_power[p] = l->th_heat_power[i];
+        t.th_cool_power[p] = l->th_cool_power[i];
+        t.th_half_band[p] = l->th_band[i] / 2.0;
+    }
+}
+
 std::string &last_error() {
     thread_local std::string e;
     return e;
@@ -1813,6 +1920,25 @@ int heat_series_check(const heat_batch_desc *desc, int32_t n_sites, const heat_s
     m.zone_slot = desc->zone_slot;
     heat::SlotResolver res(m);
     return heat::check_series(m, res, n_sites, s, heat::last_error());
+}
+
+int heat_zone_loads_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    rc = heat::check_zone_loads(desc->n_zones, s->n_channels, l, heat::last_error());
+    if (rc || !l) return rc;
+    // ... and the tables the march would upload, laid out and checked against the counts (this is the build the sanitizers see)
+    heat::ZoneLoadTables t;
+    heat::build_zone_load_tables(desc->n_zones, l, t);
+    const size_t Z1 = (size_t)desc->n_zones + 1;
+    const int64_t n[3] = {l->n_gains, l->n_flows, l->n_thermostats};
+    for (int a = 0; a < 3; a++)
+        for (size_t z = 0; z < Z1; z++)
+            if (t.off[a * Z1 + z] < (z ? t.off[a * Z1 + z - 1] : 0) || t.off[a * Z1 + z] > n[a] || (z + 1 == Z1 && t.off[a * Z1 + z] != n[a]))
+                return heat::failp(heat::last_error(), HEAT_E_SIZE, "zone load tables: offsets of list %d are inconsistent at zone %zu", a, z);
+    return HEAT_OK;
 }
 
 int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt, int64_t summary[8]) {

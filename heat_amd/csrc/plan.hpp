@@ -148,6 +148,24 @@ class SlotResolver {
 // Everything heat_series_check promises (include/heat_amd.h). HEAT_OK or a negative heat_status with `err` set.
 int check_series(const SeriesModel &m, SlotResolver &res, int32_t n_sites, const heat_series *s, std::string &err);
 
+// Zone loads of a series (heat_zone_loads, include/heat_amd.h). Everything heat_zone_loads_check promises about the loads
+// themselves; l == nullptr is no loads. HEAT_OK or a negative heat_status with `err` set.
+int check_zone_loads(int64_t n_zones, int32_t n_channels, const heat_zone_loads *l, std::string &err);
+// The tables of k_series_zone_loads (one lane per zone): the three term lists stably sorted by (target) zone — the caller's
+// order survives inside a zone — each with CSR offsets; gains that are NULL in the ABI are ones here. th_orig keeps the
+// caller's number of a thermostat: `applied` and the mode bytes stay in the caller's order.
+struct ZoneLoadTables {
+    std::vector<int32_t> off;  // [3][n_zones + 1]: gains, flows, thermostats
+    std::vector<int32_t> gain_chan;
+    std::vector<double> gain_factor;
+    std::vector<int32_t> flow_volume_chan, flow_temp_chan;
+    std::vector<double> flow_volume_gain;
+    std::vector<int32_t> th_sensor, th_heat_chan, th_cool_chan, th_orig;
+    std::vector<double> th_heat_power, th_cool_power, th_half_band;
+};
+// (of loads that passed check_zone_loads)
+void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadTables &t);
+
 // Zone-connected clusters (model.rs:556-590: surfaces exchange heat only through the zones they face): cluster id
 // per surface (-1: faces no zone) and per zone, ids dense in [0, n_clusters).
 void find_clusters(const heat_batch_desc *d, std::vector<int32_t> &cluster_of_surface,

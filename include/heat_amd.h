@@ -281,6 +281,70 @@ typedef struct heat_series {
 int heat_series_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s); /* host-only */
 int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace /* [n_steps][n_probes] */,
                             int32_t *failed_step);
+
+/*
+ * Zone loads of a series: the terms of calculate_zones_abc that do not come from surfaces (model.rs:500-544), formed ON THE
+ * DEVICE at every step from the series' channel table and a few constants per term, instead of [n_steps][n_zones] rows of
+ * zone_a0 / zone_b0 the caller computes in advance — and thermostats, which need the zone temperatures the device holds at
+ * the start of the step and so cannot be a schedule at all. The reference forms the heater, luminaire, infiltration and
+ * ventilation terms (model.rs:500-544, air properties gas.rs:49,165-179); it has NO controller (its IdealHeaterCooler is
+ * a todo!(), heating_cooling.rs:66-119): the control law below is this library's own contract, defined — as the series is —
+ * against the per-call loop with the same rule applied by the host between the calls.
+ * Step k, after the step's head (weather, zone-term row) and before its sub-timesteps; T = the zone temperatures the device
+ * holds at that moment (what step k - 1 left; for step 0 the state as it is); row = channel[k]:
+ *   1. a0[z], b0[z] start from the series' own zone-term row (zeros without rows).
+ *   2. gains of zone z, in the caller's order:       a0[z] += gain_factor[i] * row[gain_chan[i]]
+ *   3. air flows of zone z, in the caller's order:   V = flow_volume_gain[i] * row[flow_volume_chan[i]]  (m3/s)
+ *                                                    Tin = row[flow_temp_chan[i]]  (C),  Tk = Tin + 273.15
+ *                                                    rho = 101325 * 28.97 / (8314.46261815324 * Tk)       (gas.rs:175-179)
+ *                                                    cp = 1002.7370 + 1.2324e-2 * Tk                      (gas.rs:49,165-167)
+ *                                                    m = (rho * V) * cp;   a0[z] += m * Tin;   b0[z] += m
+ *   4. thermostats whose TARGET is zone z, in the caller's order, with Ts = T[th_sensor_zone[t]], d = th_band[t] / 2, mode
+ *      the thermostat's mode byte, h / c = row[th_heat_chan[t]] / row[th_cool_chan[t]]:
+ *        heating (only if th_heat_chan[t] >= 0):  Ts < h - d -> mode = 1;  else if mode == 1 and Ts > h + d -> mode = 0
+ *        cooling (only if mode != 1 now and th_cool_chan[t] >= 0):
+ *                                                 Ts > c + d -> mode = 2;  else if mode == 2 and Ts < c - d -> mode = 0
+ *        power = +th_heat_power[t] in mode 1, -th_cool_power[t] in mode 2, 0 otherwise;
+ *        a0[z] += power;  applied[k * n_thermostats + t] = power.
+ *      A NaN setpoint makes every comparison false: the mode stays.
+ *   5. The terms hold for all n_sub sub-timesteps of the step, as the zone_a0 / zone_b0 of a march call do.
+ * Every product and sum above is ONE rounded f64 operation in the order written (no fused multiply-add): a host that applies
+ * the same rule between heat_batch_march_ex calls gets the same bits. A NULL gain_factor / flow_volume_gain is all ones.
+ * th_mode (in / out, nullable) carries the modes over a cut: a series of k steps followed by one of n - k with the returned
+ * modes gives the bits of the series of n. NULL: every thermostat starts off and the modes are not returned.
+ * heat_zone_loads_check (host-only) and heat_batch_march_series_loads run the same checks, all before any device work:
+ * a negative count, a NULL array that a positive count needs (gain_factor, flow_volume_gain and th_mode may be NULL) ->
+ * HEAT_E_INVALID_ARG; a zone outside [0, n_zones) or a channel outside [0, n_channels) (a setpoint channel may be -1, but
+ * not both of a thermostat) -> HEAT_E_SIZE; a power or band that is negative or not finite, a mode byte above 2 ->
+ * HEAT_E_INVALID_ARG. The message names "gain i", "flow i" or "thermostat i". A sharded batch is refused, as by
+ * heat_batch_march_series. Weather sites need nothing: a site's outdoor temperature is a channel the caller fills.
+ * l == NULL, or all three counts 0, is heat_batch_march_series(b, s, trace, failed_step) exactly. applied is nullable;
+ * n_sub == 0 still evaluates the loads of every step. A term that turns a zone's a0 or b0 into NaN (a NaN channel value) is
+ * a numerical failure of that step: HEAT_N_NAN_ZONE, heat_batch_failed_surface names the zone. (Here the series is stricter
+ * than the per-call path: the zone update keeps the temperature of a zone whose b is NaN, model.rs:662-668, and a caller
+ * that passes such terms to heat_batch_march_ex is told nothing.) After a numerical failure applied rows and modes from the
+ * failed step on are unspecified, as the trace's are.
+ */
+typedef struct heat_zone_loads {
+    /* gains (heaters, luminaires, people; model.rs:500-516): a0[zone] += factor * channel[k][chan] */
+    int64_t n_gains;
+    const int32_t *gain_zone, *gain_chan;
+    const double *gain_factor; /* NULL = 1 */
+    /* air flows (infiltration, ventilation; model.rs:522-544) */
+    int64_t n_flows;
+    const int32_t *flow_zone, *flow_volume_chan, *flow_temp_chan;
+    const double *flow_volume_gain; /* NULL = 1 */
+    /* thermostats: one sensor zone, one target zone */
+    int64_t n_thermostats;
+    const int32_t *th_sensor_zone, *th_target_zone, *th_heat_chan, *th_cool_chan; /* setpoint channels, -1: none */
+    const double *th_heat_power, *th_cool_power, *th_band;                        /* W >= 0, W >= 0, K >= 0 */
+    uint8_t *th_mode; /* in/out, nullable: 0 off, 1 heating, 2 cooling */
+} heat_zone_loads;
+
+int heat_zone_loads_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l); /* host-only */
+int heat_batch_march_series_loads(heat_batch *b, const heat_series *s, const heat_zone_loads *l,
+                                  double *trace /* [n_steps][n_probes] */,
+                                  double *applied /* [n_steps][n_thermostats], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

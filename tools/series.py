@@ -6,14 +6,21 @@ in one process, host clock around work that ends in a synchronisation:
   B  march_resident alone, same n_sub, nothing driven, one synchronisation at the end: the floor
   C  march_series: one call for all steps, schedules uploaded inside the clock
 Prints ms per step of each, C / A and C - B (also without the set-up of the call, from a series of one step), and writes profiles/series_march.json.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE]
-  python tools/series.py --one-series [S] [steps]    one warm-up series and one more of n_sub = 2, nothing else (to run
-                                                     under rocprofv3 --kernel-trace --stats)"""
+With --loads two other legs, alternated in the same way, one gain, one infiltration flow and one thermostat per zone
+(heat_batch_march_series_loads):
+  C  march_series carrying [steps][n_zones] rows of zone a0 / b0 the host computed in advance (the gains and flows; a
+     thermostat cannot be a row at all) — what a series offered for these terms before the loads
+  D  march_series with the loads formed on the device at every step
+and writes profiles/series_loads.json: ms per step of each, D / C, and a series of one step of each.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads]
+  python tools/series.py --one-series [S] [steps] [--loads]   one warm-up series and one more of n_sub = 2, nothing else
+                                                     (to run under rocprofv3 --kernel-trace --stats)"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from heat_amd import HeatBatch, modeldict as mdl
 ONE = "--one-series" in sys.argv
+LOADS = "--loads" in sys.argv
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -28,6 +35,22 @@ channel = np.concatenate([rng.uniform(0.0, 600.0, (STEPS, N_CHANNELS // 2)), rng
 drives = {k: ((rng.integers(0, N_CHANNELS // 2, S) + (N_CHANNELS // 2 if i >= 2 else 0)).astype(np.int32), rng.uniform(0.5, 1.5, S))
           for i, k in enumerate(KEYS)}
 probes = md["zone_slot"]
+# --loads: four more channels (gain power W, infiltration m3/s, outdoor C, heating setpoint C) and one term of each kind per zone
+Z = int(md["n_zones"])
+if LOADS:
+    channel = np.concatenate([channel, rng.uniform(0.0, 300.0, (STEPS, 1)), rng.uniform(0.0, 0.05, (STEPS, 1)),
+                              rng.uniform(-5.0, 35.0, (STEPS, 1)), rng.uniform(19.0, 21.0, (STEPS, 1))], axis=1)
+    every, full = np.arange(Z, dtype=np.int32), lambda c: np.full(Z, N_CHANNELS + c, np.int32)
+    loads = dict(gains=dict(zone=every, chan=full(0), factor=rng.uniform(0.5, 1.5, Z)),
+                 flows=dict(zone=every, volume_chan=full(1), temp_chan=full(2), volume_gain=rng.uniform(0.5, 1.5, Z)),
+                 thermostats=dict(sensor_zone=every, target_zone=every, heat_chan=full(3), cool_chan=np.full(Z, -1, np.int32),
+                                  heat_power=rng.uniform(200.0, 2000.0, Z), cool_power=np.zeros(Z), band=np.full(Z, 0.5)))
+    # the rows leg C carries: the gains and flows by the rule of include/heat_amd.h, computed before the clock starts
+    tk = channel[:, N_CHANNELS + 2:N_CHANNELS + 3] + 273.15
+    mcp = (101325. * 28.97 / (8314.46261815324 * tk) * (loads["flows"]["volume_gain"] * channel[:, N_CHANNELS + 1:N_CHANNELS + 2])) * (
+        1002.7370 + 1.2324e-2 * tk)
+    rows_a0 = loads["gains"]["factor"] * channel[:, N_CHANNELS:N_CHANNELS + 1] + mcp * channel[:, N_CHANNELS + 2:N_CHANNELS + 3]
+    rows_b0 = mcp
 
 
 def leg_a(b, state, w, n_sub, steps):
@@ -61,13 +84,51 @@ def leg_c(b, w, n_sub, steps):
     return dt * 1e3 / steps
 
 
-result = dict(model="uniform_massive(%d, 32, Z=%d)" % (S, md["n_zones"]), channels=N_CHANNELS, steps=STEPS, rounds=ROUNDS,
+def leg_rows(b, w, n_sub, steps):
+    b.synchronize()
+    t0 = time.perf_counter()
+    trace, failed = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, zone_a0=rows_a0[:steps],
+                                   zone_b0=rows_b0[:steps], **drives)
+    dt = time.perf_counter() - t0
+    assert failed == -1 and np.all(np.isfinite(trace))
+    return dt * 1e3 / steps
+
+
+def leg_d(b, w, n_sub, steps):
+    b.synchronize()
+    t0 = time.perf_counter()
+    trace, failed, applied, modes = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads, **drives)
+    dt = time.perf_counter() - t0
+    assert failed == -1 and np.all(np.isfinite(trace))
+    return dt * 1e3 / steps
+
+
+result = dict(model="uniform_massive(%d, 32, Z=%d)" % (S, md["n_zones"]), channels=int(channel.shape[1]), steps=STEPS, rounds=ROUNDS,
               probes=int(len(probes)), legs={})
 with HeatBatch(md) as b:
     state = st0.copy()
     b.upload_state(state)
     for n_sub in ((2,) if ONE else (2, 20)):
         w = mdl.weather_series(STEPS * n_sub, 45.0).reshape(STEPS, n_sub, 3)
+        if LOADS:
+            leg_rows(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_d(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with loads: %.3f ms per step" % leg_d(b, w, n_sub, STEPS))
+                continue
+            c, d, c1, d1 = [], [], [], []
+            for r in range(ROUNDS):
+                c.append(leg_rows(b, w, n_sub, STEPS))
+                d.append(leg_d(b, w, n_sub, STEPS))
+                c1.append(leg_rows(b, w, n_sub, 1))
+                d1.append(leg_d(b, w, n_sub, 1))
+            Cc, D, C1, D1 = float(np.median(c)), float(np.median(d)), float(np.median(c1)), float(np.median(d1))
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                C_series_with_rows_ms=Cc, D_series_with_loads_ms=D, D_over_C=D / Cc, C_series_of_one_step_ms=C1,
+                D_series_of_one_step_ms=D1, all_rounds=dict(C=c, D=d, C_one_step=c1, D_one_step=d1))
+            print("n_sub %2d: C series with rows %.3f ms/step, D series with loads %.3f -> D / C = %.3f; a series of one step: "
+                  "C %.2f ms, D %.2f ms (%d steps, median of %d rounds)" % (n_sub, Cc, D, D / Cc, C1, D1, STEPS, ROUNDS), flush=True)
+            continue
         leg_c(b, w, n_sub, min(STEPS, 10))  # warm-up
         if ONE:
             print("one series: %.3f ms per step" % leg_c(b, w, n_sub, STEPS))
@@ -90,7 +151,8 @@ with HeatBatch(md) as b:
               "C - B = %.3f ms (%.3f without the call's set-up: a series of one step takes %.2f ms; %d steps, median of %d rounds)" % (
                   n_sub, A, A_np, B, Cc, Cc / A, Cc - B, steady, C1, STEPS, ROUNDS), flush=True)
 if not ONE:
-    out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_march.json")
+    out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                              "series_loads.json" if LOADS else "series_march.json")
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
     print("wrote", out)
