@@ -85,6 +85,18 @@ class ZoneLoads(C.Structure):
                 ("th_mode", C.POINTER(C.c_uint8))]
 
 
+class Report(C.Structure):
+    """heat_series_report (include/heat_amd.h): statistics and weighted group sums a series maintains on the device"""
+    _fields_ = [("resume", C.c_int32), ("step_base", C.c_int64),
+                ("n_groups", C.c_int64), ("group_offset", _i64p), ("group_slot", _i64p), ("group_weight", _dp),
+                ("group_trace", _dp),
+                ("q_min", _dp), ("q_step_min", _i64p), ("q_max", _dp), ("q_step_max", _i64p), ("q_sum", _dp),
+                ("q_lo", _dp), ("q_n_below", _i64p), ("q_deg_below", _dp),
+                ("q_hi", _dp), ("q_n_above", _i64p), ("q_deg_above", _dp),
+                ("th_steps_heating", _i64p), ("th_steps_cooling", _i64p), ("th_switches", _i64p),
+                ("th_sum_heating", _dp), ("th_sum_cooling", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -121,6 +133,8 @@ SYMBOLS = [
     ("heat_batch_march_series", C.c_int, [_H, C.POINTER(Series), _dp, _i32p]),
     ("heat_zone_loads_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(ZoneLoads)]),
     ("heat_batch_march_series_loads", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), _dp, _dp, _i32p]),
+    ("heat_series_report_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(Report)]),
+    ("heat_batch_march_series_report", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(Report), _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -270,6 +284,7 @@ def make_desc(md):
 
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
+                     "heat_series_report_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -497,6 +512,106 @@ def zone_loads_check(md, loads=None, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+Q_STATS = ("min", "step_min", "max", "step_max", "sum", "n_below", "deg_below", "n_above", "deg_above")
+TH_STATS = ("steps_heating", "steps_cooling", "switches", "sum_heating", "sum_cooling")
+_INT_STATS = ("step_min", "step_max", "n_below", "n_above", "steps_heating", "steps_cooling", "switches")
+
+
+def make_report(n_probes=0, n_thermostats=0, n_steps=0, groups=None, stats=None, limits=None, thermostat_stats=None,
+                group_trace=False, resume=None, step_base=0):
+    """Builds a heat_series_report. Returns (report, keepalive); the march updates the arrays of keepalive in place.
+    groups            a list of groups, each an array of state slots or a pair (slots, weights) — or a dict with offset,
+                      slot and (optional) weight in CSR form
+    stats             names out of Q_STATS: which statistics of the Q = n_probes + n_groups quantities are maintained
+    limits            dict(lo=[Q], hi=[Q]): the limits of n_below / deg_below and n_above / deg_above (NaN: never)
+    thermostat_stats  names out of TH_STATS
+    group_trace       True: keepalive["group_trace"] [n_steps, n_groups] is recorded
+    resume            a dict of arrays a previous report returned (keys as in keepalive): the accumulators start from them
+    step_base         the number the first step of this series has in q_step_min / q_step_max"""
+    keep = {}
+    r = Report()
+    r.step_base = int(step_base)
+    n_groups = 0
+    if groups is not None:
+        if isinstance(groups, dict):
+            off = np.ascontiguousarray(groups["offset"], dtype=np.int64)
+            slot = np.ascontiguousarray(groups["slot"], dtype=np.int64)
+            weight = groups.get("weight")
+            weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.float64)
+        else:
+            parts = [g if isinstance(g, tuple) else (g, None) for g in groups]
+            slots = [np.asarray(g[0], dtype=np.int64).reshape(-1) for g in parts]
+            off = np.concatenate([[0], np.cumsum([len(x) for x in slots])]).astype(np.int64)
+            slot = np.concatenate(slots).astype(np.int64) if slots else np.zeros(0, np.int64)
+            weight = None
+            if any(g[1] is not None for g in parts):
+                weight = np.concatenate([np.ones(len(x)) if g[1] is None else np.asarray(g[1], dtype=np.float64).reshape(-1)
+                                         for x, g in zip(slots, parts)]) if slots else np.zeros(0)
+        if weight is not None and weight.shape != slot.shape:
+            raise ValueError("groups: %d slots, %d weights" % (slot.size, weight.size))
+        n_groups = len(off) - 1
+        if n_groups < 0 or (n_groups > 0 and off[-1] != len(slot)):
+            raise ValueError("groups: offsets end at %s for %d slots" % (off[-1:] if len(off) else "nothing", len(slot)))
+        keep["group_offset"], keep["group_slot"] = off, slot
+        r.n_groups = n_groups
+        r.group_offset = off.ctypes.data_as(_i64p) if n_groups > 0 else None
+        r.group_slot = slot.ctypes.data_as(_i64p) if len(slot) else None
+        if weight is not None:
+            keep["group_weight"] = weight
+            r.group_weight = weight.ctypes.data_as(_dp)
+        if group_trace:
+            keep["group_trace"] = np.zeros((int(n_steps), n_groups))
+            r.group_trace = keep["group_trace"].ctypes.data_as(_dp)
+    elif group_trace:
+        raise ValueError("group_trace without groups")
+    Q = int(n_probes) + n_groups
+    resume = dict(resume) if resume is not None else None
+    r.resume = 0 if resume is None else 1
+
+    def accumulator(prefix, name, n, known):
+        if name not in known:
+            raise ValueError("unknown statistic %r (known: %s)" % (name, ", ".join(known)))
+        dtype = np.int64 if name in _INT_STATS else np.float64
+        key = prefix + name
+        if resume is not None:
+            if key not in resume:
+                raise ValueError("resume: %s is missing" % key)
+            a = np.array(resume[key], dtype=dtype).reshape(-1)      # (a copy: the march writes it)
+            if len(a) != n:
+                raise ValueError("resume: %s of %d values for %d" % (key, len(a), n))
+        else:
+            a = np.zeros(n, dtype)  # (the library initialises on the device)
+        keep[key] = a
+        setattr(r, key, a.ctypes.data_as(_i64p if dtype == np.int64 else _dp))
+
+    for name in (stats or ()):
+        accumulator("q_", name, Q, Q_STATS)
+    for name in (thermostat_stats or ()):
+        accumulator("th_", name, int(n_thermostats), TH_STATS)
+    for name, a in (limits or {}).items():
+        if name not in ("lo", "hi"):
+            raise ValueError("limits are lo and hi, not %r" % name)
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if len(a) != Q:
+            raise ValueError("limits: %s of %d values for %d quantities" % (name, len(a), Q))
+        keep["q_" + name] = a
+        setattr(r, "q_" + name, a.ctypes.data_as(_dp))
+    return r, keep
+
+
+def series_report_check(md, report=None, loads=None, lib=None, **series):
+    """heat_series_report_check: everything about the report of a series that needs no device (series arguments as
+    HeatBatch.march_series; loads / report: the arguments of make_zone_loads / make_report). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    l, lkeep = make_zone_loads(**(loads or {}))
+    r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **(report or {}))
+    rc = L.heat_series_report_check(C.byref(desc), C.byref(s), C.byref(l), C.byref(r))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -607,13 +722,21 @@ class HeatBatch:
     def synchronize(self):
         _check(self._L.heat_batch_synchronize(self._h))
 
-    def march_series(self, weather, n_sub, loads=None, **series):
+    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
         loads (a dict of make_zone_loads' arguments: gains, flows, thermostats): heat_batch_march_series_loads — the zones'
         gains, air flows and thermostats formed on the device at every step. Returns (trace, failed_step,
-        applied [n_steps, n_thermostats], modes [n_thermostats]: pass them as thermostats["mode"] to the next series)."""
+        applied [n_steps, n_thermostats], modes [n_thermostats]: pass them as thermostats["mode"] to the next series).
+        report (a dict of make_report's arguments: groups, stats, limits, thermostat_stats, group_trace, resume, step_base):
+        heat_batch_march_series_report — statistics and group sums maintained on the device. The report's arrays (a dict of
+        numpy arrays: q_min, th_switches, group_trace, ...; pass it as resume to the next series) are returned as one more
+        element. With a report, trace=False / applied=False record no trace / applied powers: an empty array comes back."""
+        if report is not None:
+            return self._march_series_report(weather, n_sub, loads, report, trace, applied, series)
+        if not (trace and applied):
+            raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
         _series_arrays_fit(keep, self.n_surfaces)
         for k in ("zone_a0", "zone_b0"):
@@ -637,6 +760,29 @@ class HeatBatch:
         if loads is None:
             return trace, int(failed.value)
         return trace, int(failed.value), applied, lkeep.get("th_mode", np.zeros(0, np.uint8))
+
+    def _march_series_report(self, weather, n_sub, loads, report, want_trace, want_applied, series):
+        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
+        _series_arrays_fit(keep, self.n_surfaces)
+        for k in ("zone_a0", "zone_b0"):
+            if k in keep and keep[k].shape[1] != self.n_zones:
+                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
+        l, lkeep = make_zone_loads(**(loads or {}))
+        r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **report)
+        trace = np.zeros((s.n_steps if want_trace else 0, s.n_probes))
+        applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
+        failed = C.c_int32(-1)
+        rc = self._L.heat_batch_march_series_report(self._h, C.byref(s), C.byref(l) if loads is not None else None, C.byref(r),
+                                                    trace.ctypes.data_as(_dp) if want_trace and trace.size else None,
+                                                    applied.ctypes.data_as(_dp) if applied.size else None, C.byref(failed))
+        if rc != 0:
+            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
+            e.failed_step, e.trace = int(failed.value), trace
+            raise e
+        out = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
+        if loads is None:
+            return trace, int(failed.value), out
+        return trace, int(failed.value), applied, lkeep.get("th_mode", np.zeros(0, np.uint8)), out
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

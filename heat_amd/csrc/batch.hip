@@ -15,6 +15,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <numeric>
 #include <string>
@@ -1021,6 +1022,33 @@ int series_upload(DevBuf<T> &buf, const T *src, size_t count, const char *what) 
     return HEAT_OK;
 }
 
+// The device copies of a report (heat_series_report): tables, accumulators, the step's group sums. Declared before the
+// SeriesDrain of the call, so freed after the stream has run dry.
+struct ReportDev {
+    DevBuf<uint8_t> gbuf, prev;
+    DevBuf<uint32_t> gidx, seg, part_off;
+    DevBuf<double> gw, part, group_trace, applied_row;
+    DevBuf<double> f64[7];   // q_min, q_max, q_sum, q_deg_below, q_deg_above, q_lo, q_hi
+    DevBuf<int64_t> i64[4];  // q_step_min, q_step_max, q_n_below, q_n_above
+    DevBuf<double> th_f64[2];
+    DevBuf<int64_t> th_i64[3];
+};
+
+template <typename T>
+int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
+    const hipError_t e = buf.alloc(count);
+    if (e != hipSuccess)
+        return fail(HEAT_E_DEVICE, "series march: %s (%zu bytes) on the device: %s — nothing has been marched", what, count * sizeof(T),
+                    hipGetErrorString(e));
+    return HEAT_OK;
+}
+// An in/out array of a report: absent (nullptr: no device copy), uploaded (resume), or allocated for the device to initialise.
+template <typename T>
+int report_array(DevBuf<T> &buf, const T *host, size_t count, bool upload, const char *what) {
+    if (!host) return HEAT_OK;
+    return upload ? series_upload(buf, host, count, what) : series_alloc(buf, count, what);
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1967,9 +1995,10 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
     return download_impl(b, state, n_state, what, true);
 }
 
-// heat_batch_march_series[_loads]: l == nullptr, or loads without a term, is the series without loads.
-static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, double *trace, double *applied,
-                             int32_t *failed_step) {
+// heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
+// is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
+static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
+                             double *trace, double *applied, int32_t *failed_step) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -1985,12 +2014,15 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     if (rc) return rc;
     rc = check_zone_loads(b->n_zones, s->n_channels, l, heat::last_error());
     if (rc) return rc;
+    std::vector<ResolvedSlot> group_entry;
+    rc = check_series_report(*b->resolver, l, r, heat::last_error(), &group_entry);
+    if (rc) return rc;
     if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
-    if (!trace && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
+    if (!trace && !no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
     if (n_steps == 0) return HEAT_OK;
     rc = select_device(b);
     if (rc) return rc;
@@ -2057,21 +2089,47 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     // probes: (buffer, index) of every probed slot
     std::vector<uint8_t> h_pbuf((size_t)P);
     std::vector<uint32_t> h_pidx((size_t)P);
+    auto place = [&](int kind, int64_t index, int node, uint8_t &buf, uint32_t &idx) {
+        if (kind == PROBE_ZONE) {
+            buf = (uint8_t)kProbeBufZone;
+            idx = (uint32_t)index;
+        } else if (kind == PROBE_NODE) {
+            buf = (uint8_t)kProbeBufT;
+            idx = (uint32_t)node_slot_index(b->h_node_tile_base[index], b->h_node_geom[index], node);
+        } else {  // hs front, hs back, flow front, flow back: SideOut record side * S + d, as doubles
+            const int a = kind - PROBE_HS_FRONT;
+            const int64_t rec = (int64_t)(a & 1) * S + b->h_dev_of[index];
+            buf = (uint8_t)kProbeBufOut;
+            idx = (uint32_t)(2 * rec + (a >> 1));
+        }
+    };
     for (int64_t p = 0; p < P; p++) {
         int kind = 0, node = 0;
         int64_t index = 0;
         if (!b->resolver->resolve(s->probe_slot[p], kind, index, node)) return fail(HEAT_E_SIZE, "probe %lld: slot not resolved", (long long)p);
-        if (kind == PROBE_ZONE) {
-            h_pbuf[p] = (uint8_t)kProbeBufZone;
-            h_pidx[p] = (uint32_t)index;
-        } else if (kind == PROBE_NODE) {
-            h_pbuf[p] = (uint8_t)kProbeBufT;
-            h_pidx[p] = (uint32_t)node_slot_index(b->h_node_tile_base[index], b->h_node_geom[index], node);
-        } else {  // hs front, hs back, flow front, flow back: SideOut record side * S + d, as doubles
-            const int a = kind - PROBE_HS_FRONT;
-            const int64_t rec = (int64_t)(a & 1) * S + b->h_dev_of[index];
-            h_pbuf[p] = (uint8_t)kProbeBufOut;
-            h_pidx[p] = (uint32_t)(2 * rec + (a >> 1));
+        place(kind, index, node, h_pbuf[p], h_pidx[p]);
+    }
+    // report: the group entries sorted into device order (buffer, index) and cut into segments (plan.hpp)
+    const int64_t G = r ? r->n_groups : 0, Q = P + G;
+    const bool th_stats = r && (r->th_steps_heating || r->th_steps_cooling || r->th_switches || r->th_sum_heating || r->th_sum_cooling);
+    GroupTables gt;
+    std::vector<uint8_t> h_gbuf;
+    std::vector<uint32_t> h_gidx;
+    if (G > 0) {
+        const int64_t n_entries = r->group_offset[G];
+        std::vector<uint64_t> key((size_t)n_entries);
+        for (int64_t i = 0; i < n_entries; i++) {
+            uint8_t buf = 0;
+            uint32_t idx = 0;
+            place(group_entry[(size_t)i].kind, group_entry[(size_t)i].index, group_entry[(size_t)i].node, buf, idx);
+            key[(size_t)i] = (uint64_t)buf << 32 | idx;
+        }
+        build_group_tables(G, r->group_offset, r->group_weight, key.data(), gt);
+        h_gbuf.resize((size_t)n_entries);
+        h_gidx.resize((size_t)n_entries);
+        for (int64_t i = 0; i < n_entries; i++) {
+            h_gbuf[(size_t)i] = (uint8_t)(gt.key[(size_t)i] >> 32);
+            h_gidx[(size_t)i] = (uint32_t)gt.key[(size_t)i];
         }
     }
 
@@ -2094,6 +2152,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     DevBuf<uint8_t> d_own, d_pbuf;
     DevBuf<uint32_t> d_face, d_pidx;
     DevBuf<int> d_fail;
+    ReportDev rd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2107,7 +2166,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     if ((rc = series_upload(d_pidx, h_pidx.data(), h_pidx.size(), "probe table"))) return rc;
     const int fail_init[5] = {-1, 0, 0, 0, 0};
     if ((rc = series_upload(d_fail, fail_init, 5, "failed step"))) return rc;
-    {
+    if (trace) {
         const hipError_t e = d_trace.alloc((size_t)n_steps * P);
         if (e != hipSuccess)
             return fail(HEAT_E_DEVICE, "series march: trace (%zu bytes) on the device: %s — nothing has been marched",
@@ -2148,6 +2207,58 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         zl.th_half_band = d_zl_f64.p + at_f64[4];
         zl.th_mode = d_mode.p;
     }
+    SeriesGroupsDev gd{};
+    SeriesStatsDev sd{};
+    SeriesThStatsDev td{};
+    bool q_stats = false;
+    if (r) {
+        const bool resume = r->resume != 0;
+        const size_t n_wave = gt.wave_seg.size() / 3, n_row = gt.row_seg.size() / 3;
+        std::vector<uint32_t> h_seg(gt.wave_seg);
+        h_seg.insert(h_seg.end(), gt.row_seg.begin(), gt.row_seg.end());
+        if ((rc = series_upload(rd.gbuf, h_gbuf.data(), h_gbuf.size(), "group tables"))) return rc;
+        if ((rc = series_upload(rd.gidx, h_gidx.data(), h_gidx.size(), "group tables"))) return rc;
+        if ((rc = series_upload(rd.gw, gt.weight.data(), gt.weight.size(), "group tables"))) return rc;
+        if ((rc = series_upload(rd.seg, h_seg.data(), h_seg.size(), "group tables"))) return rc;
+        if ((rc = series_upload(rd.part_off, gt.part_off.data(), G > 0 ? gt.part_off.size() : 0, "group tables"))) return rc;
+        if ((rc = series_alloc(rd.part, n_wave + n_row, "group sums"))) return rc;
+        if ((rc = report_array(rd.group_trace, r->group_trace, (size_t)n_steps * G, false, "group trace"))) return rc;
+        double *const f64[7] = {r->q_min, r->q_max, r->q_sum, r->q_deg_below, r->q_deg_above, const_cast<double *>(r->q_lo),
+                                const_cast<double *>(r->q_hi)};
+        int64_t *const i64[4] = {r->q_step_min, r->q_step_max, r->q_n_below, r->q_n_above};
+        for (int a = 0; a < 7; a++)
+            if ((rc = report_array(rd.f64[a], f64[a], (size_t)Q, resume || a >= 5, "statistics"))) return rc;
+        for (int a = 0; a < 4; a++)
+            if ((rc = report_array(rd.i64[a], i64[a], (size_t)Q, resume, "statistics"))) return rc;
+        gd.buf = rd.gbuf.p, gd.idx = rd.gidx.p, gd.weight = rd.gw.p;
+        gd.wave_seg = rd.seg.p, gd.row_seg = rd.seg.p + 3 * n_wave;
+        gd.n_wave = (int)n_wave, gd.n_row = (int)n_row;
+        gd.part = rd.part.p;
+        sd.n_probes = P, sd.n_groups = G;
+        sd.buf = d_pbuf.p, sd.idx = d_pidx.p;
+        sd.part = rd.part.p, sd.part_off = rd.part_off.p;
+        sd.q_min = rd.f64[0].p, sd.q_max = rd.f64[1].p, sd.q_sum = rd.f64[2].p, sd.q_deg_below = rd.f64[3].p, sd.q_deg_above = rd.f64[4].p;
+        // (a limit nothing is counted against is not read)
+        sd.q_lo = rd.i64[2].p || rd.f64[3].p ? rd.f64[5].p : nullptr;
+        sd.q_hi = rd.i64[3].p || rd.f64[4].p ? rd.f64[6].p : nullptr;
+        sd.q_step_min = rd.i64[0].p, sd.q_step_max = rd.i64[1].p, sd.q_n_below = rd.i64[2].p, sd.q_n_above = rd.i64[3].p;
+        q_stats = Q > 0 && (sd.q_min || sd.q_max || sd.q_sum || sd.q_n_below || sd.q_deg_below || sd.q_n_above || sd.q_deg_above ||
+                            rd.group_trace.p);
+        if (th_stats) {  // (check_series_report: only with thermostats)
+            double *const tf[2] = {r->th_sum_heating, r->th_sum_cooling};
+            int64_t *const ti[3] = {r->th_steps_heating, r->th_steps_cooling, r->th_switches};
+            for (int a = 0; a < 2; a++)
+                if ((rc = report_array(rd.th_f64[a], tf[a], (size_t)NT, resume, "thermostat statistics"))) return rc;
+            for (int a = 0; a < 3; a++)
+                if ((rc = report_array(rd.th_i64[a], ti[a], (size_t)NT, resume, "thermostat statistics"))) return rc;
+            if ((rc = series_upload(rd.prev, h_mode.data(), h_mode.size(), "thermostat modes"))) return rc;
+            // (the powers of the step: a row of the applied buffer, or one row of scratch where the caller takes none)
+            if (!d_applied.p && (tf[0] || tf[1]) && (rc = series_alloc(rd.applied_row, (size_t)NT, "applied powers"))) return rc;
+            td.sum_heating = rd.th_f64[0].p, td.sum_cooling = rd.th_f64[1].p;
+            td.steps_heating = rd.th_i64[0].p, td.steps_cooling = rd.th_i64[1].p, td.switches = rd.th_i64[2].p;
+            td.prev = rd.prev.p;
+        }
+    }
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
 
     SeriesInputs in{};
@@ -2156,30 +2267,65 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     in.own_face = d_own.p;
     in.face = d_face.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
+    if (r && r->resume == 0) {  // the accumulators start on the device: min = +inf, max = -inf, steps = -1, sums and counts 0
+        const double inf = std::numeric_limits<double>::infinity();
+        const double f64_init[5] = {inf, -inf, 0.0, 0.0, 0.0};
+        for (int a = 0; a < 5; a++) launch_fill_f64(rd.f64[a].p, (int64_t)rd.f64[a].n, f64_init[a], b->stream);
+        for (int a = 0; a < 4; a++)
+            if (rd.i64[a].p) HIP_TRY(hipMemsetAsync(rd.i64[a].p, a < 2 ? 0xff : 0, rd.i64[a].n * sizeof(int64_t), b->stream));
+        for (int a = 0; a < 2; a++) launch_fill_f64(rd.th_f64[a].p, (int64_t)rd.th_f64[a].n, 0.0, b->stream);
+        for (int a = 0; a < 3; a++)
+            if (rd.th_i64[a].p) HIP_TRY(hipMemsetAsync(rd.th_i64[a].p, 0, rd.th_i64[a].n * sizeof(int64_t), b->stream));
+    }
+    double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
+    const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
     // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> the body of a march call of n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
                            d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
         if (loads)
             launch_series_zone_loads((int)Z, zl, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
-                                     d_applied.p ? d_applied.p + (size_t)k * NT : nullptr, b->d_flags.p, b->stream);
+                                     applied_dev ? applied_dev + (size_t)k * applied_stride : nullptr, b->d_flags.p, b->stream);
+        if (th_stats) launch_series_th_stats((int)NT, td, d_mode.p, applied_dev ? applied_dev + (size_t)k * applied_stride : nullptr, b->stream);
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
         rc = march_body(b, n_sub);
         if (rc) return rc;
-        launch_series_probe(P, d_pbuf.p, d_pidx.p, b->d_T.p, b->d_side_out.p, b->d_zone_T.p, d_trace.p + (size_t)k * P, b->d_flags.p,
-                            d_fail.p, k, b->stream);
+        // (without a trace: no probe is copied, lane 0 still watches the failure flags)
+        launch_series_probe(d_trace.p ? P : 0, d_pbuf.p, d_pidx.p, b->d_T.p, b->d_side_out.p, b->d_zone_T.p,
+                            d_trace.p ? d_trace.p + (size_t)k * P : nullptr, b->d_flags.p, d_fail.p, k, b->stream);
+        if (q_stats) {  // (a report that asks nothing of its quantities launches nothing here)
+            launch_series_groups(gd, b->d_T.p, b->d_side_out.p, b->d_zone_T.p, b->stream);
+            launch_series_stats(sd, b->d_T.p, b->d_side_out.p, b->d_zone_T.p,
+                                    rd.group_trace.p ? rd.group_trace.p + (size_t)k * G : nullptr, r->step_base + k, b->stream);
+        }
     }
     HIP_TRY(hipGetLastError());
     // ---- one wait: the trace and the record of the first failure travel at the end of the stream's work ----
     int first_failed[5] = {-1, 0, 0, 0, 0};
-    if ((int64_t)n_steps * P > 0)
+    if (trace && (int64_t)n_steps * P > 0)
         HIP_TRY(hipMemcpyAsync(trace, d_trace.p, (size_t)n_steps * P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (d_applied.p && (int64_t)n_steps * NT > 0)
         HIP_TRY(hipMemcpyAsync(applied, d_applied.p, (size_t)n_steps * NT * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (loads && l->th_mode && NT > 0)
         HIP_TRY(hipMemcpyAsync(l->th_mode, d_mode.p, (size_t)NT, hipMemcpyDeviceToHost, b->stream));
+    if (r) {
+        if (rd.group_trace.p && (int64_t)n_steps * G > 0)
+            HIP_TRY(hipMemcpyAsync(r->group_trace, rd.group_trace.p, (size_t)n_steps * G * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        double *const f64[5] = {r->q_min, r->q_max, r->q_sum, r->q_deg_below, r->q_deg_above};
+        int64_t *const i64[4] = {r->q_step_min, r->q_step_max, r->q_n_below, r->q_n_above};
+        double *const tf[2] = {r->th_sum_heating, r->th_sum_cooling};
+        int64_t *const ti[3] = {r->th_steps_heating, r->th_steps_cooling, r->th_switches};
+        for (int a = 0; a < 5; a++)
+            if (rd.f64[a].p && Q > 0) HIP_TRY(hipMemcpyAsync(f64[a], rd.f64[a].p, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        for (int a = 0; a < 4; a++)
+            if (rd.i64[a].p && Q > 0) HIP_TRY(hipMemcpyAsync(i64[a], rd.i64[a].p, (size_t)Q * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+        for (int a = 0; a < 2; a++)
+            if (rd.th_f64[a].p) HIP_TRY(hipMemcpyAsync(tf[a], rd.th_f64[a].p, (size_t)NT * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        for (int a = 0; a < 3; a++)
+            if (rd.th_i64[a].p) HIP_TRY(hipMemcpyAsync(ti[a], rd.th_i64[a].p, (size_t)NT * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2192,12 +2338,17 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
 }
 
 int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, int32_t *failed_step) {
-    return march_series_impl(b, s, nullptr, trace, nullptr, failed_step);
+    return march_series_impl(b, s, nullptr, nullptr, false, trace, nullptr, failed_step);
 }
 
 int heat_batch_march_series_loads(heat_batch *b, const heat_series *s, const heat_zone_loads *l, double *trace, double *applied,
                                   int32_t *failed_step) {
-    return march_series_impl(b, s, l, trace, applied, failed_step);
+    return march_series_impl(b, s, l, nullptr, false, trace, applied, failed_step);
+}
+
+int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, double *trace,
+                                   double *applied, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

@@ -2326,6 +2326,128 @@ k_series_zone_loads(int n_zones, ZoneLoadsDev zl, const double *__restrict__ row
     b0[z] = b;
     if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
 }
+
+// Report of a series (heat_series_report, include/heat_amd.h): on the step's tail, beside k_series_probe. Everything below
+// is written without contraction: the statistics are DEFINED as one rounded operation per rule, and a group's bits are to
+// follow from its tables alone.
+__device__ __forceinline__ double series_value(int b, uint32_t i, const double *__restrict__ T, const SideOut *__restrict__ out,
+                                               const double *__restrict__ zone_T) {
+    const double *base = b == kProbeBufT ? T : (b == kProbeBufOut ? reinterpret_cast<const double *>(out) : zone_T);
+    return base[i];
+}
+
+// One lane's share of a segment: entries first, first + STRIDE, ... below end, added in that order.
+template <int STRIDE>
+__device__ __forceinline__ double series_group_lane(const SeriesGroupsDev &g, uint32_t first, uint32_t end, const double *__restrict__ T,
+                                                    const SideOut *__restrict__ out, const double *__restrict__ zone_T) {
+    double acc = 0.0;
+    if (g.weight != nullptr) {
+#pragma unroll 4
+        for (uint32_t e = first; e < end; e += STRIDE) {
+            const double p = g.weight[e] * series_value(g.buf[e], g.idx[e], T, out, zone_T);
+            acc = acc + p;
+        }
+    } else {
+#pragma unroll 4
+        for (uint32_t e = first; e < end; e += STRIDE) acc = acc + series_value(g.buf[e], g.idx[e], T, out, zone_T);
+    }
+    return acc;
+}
+
+// k_series_groups — the segmented weighted gather-sum: one wavefront per segment of a large group (wavefronts
+// [0, n_wave)), one 16-lane row per small group (four to a wavefront behind them). A lane adds its entries of the segment
+// — lane-strided, so that a wave instruction reads 64 (16) neighbouring table entries and, the entries being sorted into
+// device order, neighbouring records — and the lanes' sums go through the fixed DPP trees of k_zones. Which lane adds
+// which entry, and the tree, follow from the segment's bounds alone: the partial sum does not depend on the grid, on the
+// other segments or on timing. One writer per partial sum; no atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_groups(SeriesGroupsDev g, const double *__restrict__ T, const SideOut *__restrict__ out, const double *__restrict__ zone_T) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int w = blockIdx.x * (256 / kWave) + (threadIdx.x >> 6);  // (wave-uniform)
+    if (w < g.n_wave) {
+        const uint32_t *seg = g.wave_seg + 3 * (size_t)w;
+        const uint32_t e0 = seg[0], e1 = seg[1];
+        const double total = wave_sum_f64(series_group_lane<kWave>(g, e0 + lane, e1, T, out, zone_T));
+        if (lane == 0) g.part[seg[2]] = total;
+        return;
+    }
+    const int r = (w - g.n_wave) * 4 + (lane >> 4);
+    uint32_t e0 = 0, e1 = 0, p = 0;
+    if (r < g.n_row) {
+        const uint32_t *seg = g.row_seg + 3 * (size_t)r;
+        e0 = seg[0], e1 = seg[1], p = seg[2];
+    }
+    const double total = row_sum_f64(series_group_lane<16>(g, e0 + (lane & 15), e1, T, out, zone_T));  // in the row's lane 15
+    if ((lane & 15) == 15 && r < g.n_row) g.part[p] = total;
+}
+
+// k_series_stats — one lane per quantity: a probe's value read as k_series_probe reads it, a group's as its segments'
+// partial sums added in segment order (written to the step's group_trace row where there is one); then the rules of the
+// header on the accumulators the caller asked for. An extremum is stored only when it changes.
+__global__ void __launch_bounds__(256)
+k_series_stats(SeriesStatsDev s, const double *__restrict__ T, const SideOut *__restrict__ out, const double *__restrict__ zone_T,
+               double *__restrict__ group_row, int64_t step) {
+    const int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= s.n_probes + s.n_groups) return;
+    double v;
+    if (q < s.n_probes) {
+        v = series_value(s.buf[q], s.idx[q], T, out, zone_T);
+    } else {
+        const int64_t g = q - s.n_probes;
+        const uint32_t p0 = s.part_off[g], p1 = s.part_off[g + 1];
+        v = p0 < p1 ? s.part[p0] : 0.0;
+        for (uint32_t p = p0 + 1; p < p1; p++) v = v + s.part[p];
+        if (group_row != nullptr) group_row[g] = v;
+    }
+    if (s.q_min != nullptr && v < s.q_min[q]) {
+        s.q_min[q] = v;
+        if (s.q_step_min != nullptr) s.q_step_min[q] = step;
+    }
+    if (s.q_max != nullptr && v > s.q_max[q]) {
+        s.q_max[q] = v;
+        if (s.q_step_max != nullptr) s.q_step_max[q] = step;
+    }
+    if (s.q_sum != nullptr) s.q_sum[q] = s.q_sum[q] + v;
+    if (s.q_lo != nullptr) {
+        const double lo = s.q_lo[q];
+        if (v < lo) {
+            if (s.q_n_below != nullptr) s.q_n_below[q] += 1;
+            if (s.q_deg_below != nullptr) s.q_deg_below[q] = s.q_deg_below[q] + (lo - v);
+        }
+    }
+    if (s.q_hi != nullptr) {
+        const double hi = s.q_hi[q];
+        if (v > hi) {
+            if (s.q_n_above != nullptr) s.q_n_above[q] += 1;
+            if (s.q_deg_above != nullptr) s.q_deg_above[q] = s.q_deg_above[q] + (v - hi);
+        }
+    }
+}
+
+// k_series_th_stats — one lane per thermostat (caller's order), behind k_series_zone_loads: the step's mode and applied
+// power against the mode before the step.
+__global__ void __launch_bounds__(256)
+k_series_th_stats(int n, SeriesThStatsDev t, const uint8_t *__restrict__ mode, const double *__restrict__ applied_row) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int m = mode[i];
+    if (t.steps_heating != nullptr && m == 1) t.steps_heating[i] += 1;
+    if (t.steps_cooling != nullptr && m == 2) t.steps_cooling[i] += 1;
+    if (t.switches != nullptr) {
+        if (m != t.prev[i]) t.switches[i] += 1;
+        t.prev[i] = (uint8_t)m;
+    }
+    if (t.sum_heating != nullptr || t.sum_cooling != nullptr) {
+        const double a = applied_row[i];
+        if (t.sum_heating != nullptr && a > 0.0) t.sum_heating[i] = t.sum_heating[i] + a;
+        if (t.sum_cooling != nullptr && a < 0.0) t.sum_cooling[i] = t.sum_cooling[i] + a;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = value;
+}
 #pragma clang fp contract(fast)
 
 // ---------------------------------------------------------------------------
@@ -2609,6 +2731,29 @@ void launch_series_probe(int64_t n_probes, const uint8_t *buf, const uint32_t *i
     const int64_t n = std::max<int64_t>(n_probes, 1);
     hipLaunchKernelGGL(k_series_probe, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, st, n_probes, buf, idx, T, out, zone_T,
                        trace_row, flags, fail_step, step);
+}
+
+void launch_series_groups(const SeriesGroupsDev &g, const double *T, const SideOut *out, const double *zone_T, hipStream_t st) {
+    const int n_waves = g.n_wave + (g.n_row + 3) / 4;
+    if (n_waves <= 0) return;
+    hipLaunchKernelGGL(k_series_groups, dim3(blocks_for_waves(n_waves)), dim3(256), 0, st, g, T, out, zone_T);
+}
+
+void launch_series_stats(const SeriesStatsDev &s, const double *T, const SideOut *out, const double *zone_T, double *group_row,
+                         int64_t step, hipStream_t st) {
+    const int64_t n = s.n_probes + s.n_groups;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_series_stats, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, st, s, T, out, zone_T, group_row, step);
+}
+
+void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const uint8_t *mode, const double *applied_row, hipStream_t st) {
+    if (n_thermostats <= 0) return;
+    hipLaunchKernelGGL(k_series_th_stats, dim3((n_thermostats + 255) / 256), dim3(256), 0, st, n_thermostats, t, mode, applied_row);
+}
+
+void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_fill_f64, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, st, dst, n, value);
 }
 
 void launch_set_step(int *step_ptr, int v, int last, hipStream_t st) {

@@ -101,4 +101,42 @@ constexpr int kProbeBufT = 0, kProbeBufOut = 1, kProbeBufZone = 2;
 void launch_series_probe(int64_t n_probes, const uint8_t *buf, const uint32_t *idx, const double *T, const SideOut *out,
                          const double *zone_T, double *trace_row, const int *flags, int *fail_step, int step, hipStream_t st);
 
+// Report of a series (heat_series_report, include/heat_amd.h; tables: plan.hpp, GroupTables): on the step's tail, beside
+// launch_series_probe. launch_series_groups reduces every segment of every group to its partial sum (nothing to do without
+// entries); launch_series_stats — one lane per quantity — takes a probe's value as the probe kernel does and a group's as
+// its partial sums added in segment order, writes the group's element of the step's group_trace row and updates the
+// accumulators that exist (a nullptr array costs no load or store).
+struct SeriesGroupsDev {
+    const uint8_t *buf;        // [n_entries]: kProbeBuf* of the entry
+    const uint32_t *idx;       // [n_entries]: index into that buffer
+    const double *weight;      // [n_entries], nullptr: all ones
+    const uint32_t *wave_seg;  // [n_wave][3]: first entry, end entry, partial sum
+    const uint32_t *row_seg;   // [n_row][3]
+    int n_wave, n_row;
+    double *part;              // the segments' partial sums
+};
+void launch_series_groups(const SeriesGroupsDev &g, const double *T, const SideOut *out, const double *zone_T, hipStream_t st);
+struct SeriesStatsDev {
+    int64_t n_probes, n_groups;
+    const uint8_t *buf;        // probes, as launch_series_probe takes them
+    const uint32_t *idx;
+    const double *part;        // groups: partial sums part[part_off[g] .. part_off[g + 1])
+    const uint32_t *part_off;
+    double *q_min, *q_max, *q_sum, *q_deg_below, *q_deg_above;  // [n_probes + n_groups] each, nullptr: not maintained
+    int64_t *q_step_min, *q_step_max, *q_n_below, *q_n_above;
+    const double *q_lo, *q_hi;
+};
+// group_row: the step's row of group_trace, or nullptr; step: K = step_base + k
+void launch_series_stats(const SeriesStatsDev &s, const double *T, const SideOut *out, const double *zone_T, double *group_row,
+                         int64_t step, hipStream_t st);
+// Thermostat statistics, one lane per thermostat, behind launch_series_zone_loads: mode = the bytes it has just written,
+// prev = the modes before this step (kept here), applied_row = the step's applied powers (caller's order).
+struct SeriesThStatsDev {
+    int64_t *steps_heating, *steps_cooling, *switches;  // [n_thermostats] each, nullptr: not maintained
+    double *sum_heating, *sum_cooling;
+    uint8_t *prev;
+};
+void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const uint8_t *mode, const double *applied_row, hipStream_t st);
+void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
+
 }  // namespace heat

@@ -1848,6 +1848,138 @@ void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadT
     }
 }
 
+// ---- report of a series (include/heat_amd.h, heat_series_report) ----
+int check_series_report(SlotResolver &res, const heat_zone_loads *l, const heat_series_report *r, std::string &err,
+                        std::vector<ResolvedSlot> *resolved) {
+    if (!r) return HEAT_OK;
+    if (r->n_groups < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count in series report (n_groups %lld)", (long long)r->n_groups);
+    if (r->n_groups > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 groups in series report");
+    int64_t n_entries = 0;
+    if (r->n_groups > 0) {
+        if (!r->group_offset) return failp(err, HEAT_E_INVALID_ARG, "group_offset is NULL");
+        if (r->group_offset[0] != 0)
+            return failp(err, HEAT_E_INVALID_ARG, "group 0: group_offset starts at %lld, not 0", (long long)r->group_offset[0]);
+        for (int64_t g = 0; g < r->n_groups; g++)
+            if (r->group_offset[g + 1] < r->group_offset[g])
+                return failp(err, HEAT_E_INVALID_ARG, "group %lld: group_offset decreases (%lld after %lld)", (long long)g,
+                             (long long)r->group_offset[g + 1], (long long)r->group_offset[g]);
+        n_entries = r->group_offset[r->n_groups];
+    }
+    // (the tables number their entries with 32 bits)
+    if (n_entries > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 group entries in series report");
+    if (n_entries > 0 && !r->group_slot) return failp(err, HEAT_E_INVALID_ARG, "group_slot is NULL");
+    if ((r->q_step_min && !r->q_min) || (r->q_step_max && !r->q_max))
+        return failp(err, HEAT_E_INVALID_ARG, "q_step_min / q_step_max without q_min / q_max");
+    if ((r->q_n_below || r->q_deg_below) && !r->q_lo) return failp(err, HEAT_E_INVALID_ARG, "q_n_below or q_deg_below without q_lo");
+    if ((r->q_n_above || r->q_deg_above) && !r->q_hi) return failp(err, HEAT_E_INVALID_ARG, "q_n_above or q_deg_above without q_hi");
+    const bool th = r->th_steps_heating || r->th_steps_cooling || r->th_switches || r->th_sum_heating || r->th_sum_cooling;
+    if (th && (!l || l->n_thermostats <= 0)) return failp(err, HEAT_E_INVALID_ARG, "thermostat statistics without thermostats");
+    if (r->group_weight)
+        for (int64_t i = 0; i < n_entries; i++)
+            if (!std::isfinite(r->group_weight[i]))
+                return failp(err, HEAT_E_INVALID_ARG, "group entry %lld: weight %g is not finite", (long long)i, r->group_weight[i]);
+    // every entry resolved once: the march and the host-only check build their tables from `resolved`
+    std::vector<ResolvedSlot> local;
+    std::vector<ResolvedSlot> &out = resolved ? *resolved : local;
+    out.resize((size_t)n_entries);
+    int64_t bad = -1;
+    for (int64_t i = 0; i < n_entries && bad < 0; i++) {
+        int kind = 0, node = 0;
+        int64_t index = 0;
+        if (!res.resolve(r->group_slot[i], kind, index, node)) bad = i;
+        else out[(size_t)i] = ResolvedSlot{kind, node, index};
+    }
+    if (bad >= 0)
+        return failp(err, HEAT_E_SIZE, "group entry %lld: slot %lld is not a node-temperature, hs, flow or zone slot of the descriptor",
+                     (long long)bad, (long long)r->group_slot[bad]);
+    return HEAT_OK;
+}
+
+void build_group_tables(int64_t n_groups, const int64_t *offset, const double *weight, const uint64_t *key, GroupTables &t) {
+    t = GroupTables();
+    t.part_off.assign((size_t)n_groups + 1, 0);
+    if (n_groups <= 0) return;
+    const size_t n_entries = (size_t)offset[n_groups];
+    t.key.resize(n_entries);
+    if (weight) t.weight.resize(n_entries);
+    std::vector<int64_t> order;
+    uint32_t n_part = 0;
+    for (int64_t g = 0; g < n_groups; g++) {
+        const int64_t e0 = offset[g], e1 = offset[g + 1], n = e1 - e0;
+        order.resize((size_t)n);
+        for (int64_t i = 0; i < n; i++) order[(size_t)i] = e0 + i;
+        // (a slot that enters a group several times: by weight, so that the order is a function of the entries, not of how
+        // the caller listed them)
+        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
+            return key[a] != key[b] ? key[a] < key[b] : (weight != nullptr && weight[a] < weight[b]);
+        });
+        for (int64_t i = 0; i < n; i++) {
+            t.key[(size_t)(e0 + i)] = key[order[(size_t)i]];
+            if (weight) t.weight[(size_t)(e0 + i)] = weight[order[(size_t)i]];
+        }
+        t.part_off[(size_t)g] = n_part;
+        if (n == 0) continue;
+        if (n <= kGroupRowEntries) {
+            t.row_seg.insert(t.row_seg.end(), {(uint32_t)e0, (uint32_t)e1, n_part++});
+        } else {
+            for (int64_t a = e0; a < e1; a += kGroupSegment)
+                t.wave_seg.insert(t.wave_seg.end(), {(uint32_t)a, (uint32_t)std::min<int64_t>(a + kGroupSegment, e1), n_part++});
+        }
+    }
+    t.part_off[(size_t)n_groups] = n_part;
+}
+
+int check_group_tables(int64_t n_groups, const int64_t *offset, const GroupTables &t, std::string &err) {
+    if (t.part_off.size() != (size_t)n_groups + 1) return failp(err, HEAT_E_SIZE, "group tables: %zu partial offsets for %lld groups", t.part_off.size(), (long long)n_groups);
+    const size_t n_part = t.part_off[(size_t)n_groups];
+    const size_t n_entries = n_groups > 0 ? (size_t)offset[n_groups] : 0;
+    if (t.key.size() != n_entries || (!t.weight.empty() && t.weight.size() != n_entries))
+        return failp(err, HEAT_E_SIZE, "group tables: %zu keys, %zu weights for %zu entries", t.key.size(), t.weight.size(), n_entries);
+    if (t.wave_seg.size() % 3 || t.row_seg.size() % 3 || t.wave_seg.size() / 3 + t.row_seg.size() / 3 != n_part)
+        return failp(err, HEAT_E_SIZE, "group tables: %zu + %zu segments for %zu partial sums", t.wave_seg.size() / 3, t.row_seg.size() / 3, n_part);
+    // every partial sum has one segment, and a group's segments tile its entries in order
+    std::vector<uint32_t> first(n_part, 0), end(n_part, 0);
+    std::vector<uint8_t> seen(n_part, 0);
+    for (const std::vector<uint32_t> *v : {&t.wave_seg, &t.row_seg})
+        for (size_t i = 0; i < v->size(); i += 3) {
+            const uint32_t e0 = (*v)[i], e1 = (*v)[i + 1], p = (*v)[i + 2];
+            const uint32_t longest = v == &t.row_seg ? kGroupRowEntries : kGroupSegment;
+            if (p >= n_part || seen[p] || e1 <= e0 || e1 - e0 > longest || e1 > n_entries)
+                return failp(err, HEAT_E_SIZE, "group tables: segment %zu [%u, %u) -> partial %u is inconsistent", i / 3, e0, e1, p);
+            seen[p] = 1, first[p] = e0, end[p] = e1;
+        }
+    for (int64_t g = 0; g < n_groups; g++) {
+        int64_t at = offset[g];
+        if (t.part_off[(size_t)g] > t.part_off[(size_t)g + 1]) return failp(err, HEAT_E_SIZE, "group %lld: partial offsets decrease", (long long)g);
+        for (uint32_t p = t.part_off[(size_t)g]; p < t.part_off[(size_t)g + 1]; p++) {
+            if (!seen[p] || first[p] != at) return failp(err, HEAT_E_SIZE, "group %lld: its segments do not tile its entries", (long long)g);
+            at = end[p];
+        }
+        if (at != offset[g + 1]) return failp(err, HEAT_E_SIZE, "group %lld: its segments end at %lld, not %lld", (long long)g, (long long)at, (long long)offset[g + 1]);
+        for (int64_t i = offset[g] + 1; i < offset[g + 1]; i++)
+            if (t.key[(size_t)i] < t.key[(size_t)i - 1]) return failp(err, HEAT_E_SIZE, "group %lld: entries not in device order", (long long)g);
+    }
+    return HEAT_OK;
+}
+
+// What a series may probe, from a descriptor that passed check_desc (node_count: storage the model points into).
+static SeriesModel series_model_of(const heat_batch_desc *desc, std::vector<int64_t> &node_count) {
+    const int64_t S = desc->n_surfaces;
+    node_count.resize((size_t)S);
+    for (int64_t q = 0; q < S; q++) node_count[q] = desc->node_offset[q + 1] - desc->node_offset[q];
+    SeriesModel m;
+    m.n_surfaces = S;
+    m.n_zones = desc->n_zones;
+    m.first_node_slot = desc->first_node_slot;
+    m.node_count = node_count.data();
+    m.out_slot[0] = desc->hs_front_slot;
+    m.out_slot[1] = desc->hs_back_slot;
+    m.out_slot[2] = desc->flow_front_slot;
+    m.out_slot[3] = desc->flow_back_slot;
+    m.zone_slot = desc->zone_slot;
+    return m;
+}
+
 std::string &last_error() {
     thread_local std::string e;
     return e;
@@ -1905,19 +2037,8 @@ static int plan_check_impl(const heat_batch_desc *desc, const heat_batch_options
 int heat_series_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s) {
     int rc = heat::check_desc(desc, heat::last_error());
     if (rc) return rc;
-    const int64_t S = desc->n_surfaces;
-    std::vector<int64_t> node_count((size_t)S);
-    for (int64_t q = 0; q < S; q++) node_count[q] = desc->node_offset[q + 1] - desc->node_offset[q];
-    heat::SeriesModel m;
-    m.n_surfaces = S;
-    m.n_zones = desc->n_zones;
-    m.first_node_slot = desc->first_node_slot;
-    m.node_count = node_count.data();
-    m.out_slot[0] = desc->hs_front_slot;
-    m.out_slot[1] = desc->hs_back_slot;
-    m.out_slot[2] = desc->flow_front_slot;
-    m.out_slot[3] = desc->flow_back_slot;
-    m.zone_slot = desc->zone_slot;
+    std::vector<int64_t> node_count;
+    const heat::SeriesModel m = heat::series_model_of(desc, node_count);
     heat::SlotResolver res(m);
     return heat::check_series(m, res, n_sites, s, heat::last_error());
 }
@@ -1939,6 +2060,28 @@ int heat_zone_loads_check(const heat_batch_desc *desc, const heat_series *s, con
             if (t.off[a * Z1 + z] < (z ? t.off[a * Z1 + z - 1] : 0) || t.off[a * Z1 + z] > n[a] || (z + 1 == Z1 && t.off[a * Z1 + z] != n[a]))
                 return heat::failp(heat::last_error(), HEAT_E_SIZE, "zone load tables: offsets of list %d are inconsistent at zone %zu", a, z);
     return HEAT_OK;
+}
+
+int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,
+                             const heat_series_report *r) {
+    int rc = heat_zone_loads_check(desc, s, l);
+    if (rc) return rc;
+    if (s->n_probes < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_probes %lld)", (long long)s->n_probes);
+    std::vector<int64_t> node_count;
+    const heat::SeriesModel m = heat::series_model_of(desc, node_count);
+    heat::SlotResolver res(m);
+    std::vector<heat::ResolvedSlot> resolved;
+    rc = heat::check_series_report(res, l, r, heat::last_error(), &resolved);
+    if (rc || !r) return rc;
+    // ... and the group tables the march would upload (this is the build the sanitizers see). Without a batch there is no
+    // device layout: the entries are ordered by (kind, surface or zone, node) instead.
+    const int64_t n_entries = r->n_groups > 0 ? r->group_offset[r->n_groups] : 0;
+    std::vector<uint64_t> key((size_t)n_entries);
+    for (int64_t i = 0; i < n_entries; i++)
+        key[(size_t)i] = (uint64_t)resolved[(size_t)i].kind << 56 | (uint64_t)resolved[(size_t)i].index << 16 | (uint64_t)resolved[(size_t)i].node;
+    heat::GroupTables t;
+    heat::build_group_tables(r->n_groups, r->group_offset, r->group_weight, key.data(), t);
+    return heat::check_group_tables(r->n_groups, r->group_offset, t, heat::last_error());
 }
 
 int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt, int64_t summary[8]) {

@@ -166,6 +166,36 @@ struct ZoneLoadTables {
 // (of loads that passed check_zone_loads)
 void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadTables &t);
 
+// Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
+// report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
+// heat_status with `err` set, naming "group g" or "group entry i".
+// resolved (nullable): what every group entry is, in the caller's order.
+struct ResolvedSlot {
+    int32_t kind, node;
+    int64_t index;
+};
+int check_series_report(SlotResolver &res, const heat_zone_loads *l, const heat_series_report *r, std::string &err,
+                        std::vector<ResolvedSlot> *resolved = nullptr);
+// The tables of k_series_groups. A group of at most kGroupRowEntries entries is ONE segment reduced by a 16-lane row; a
+// larger one is cut into segments of kGroupSegment entries (the last one shorter), one wavefront each. Both constants are
+// part of the result's bits — the order of a group's summation follows from its own entry count and keys alone — and so
+// are fixed here, not derived from the device. Inside a group the entries are sorted by `key` (where the entry lives on the
+// device: neighbouring entries are neighbouring records where the layout allows), ties by weight: the caller's order of
+// the entries does not enter the result.
+constexpr int kGroupSegment = 1024;
+constexpr int kGroupRowEntries = 64;
+struct GroupTables {
+    std::vector<uint64_t> key;      // [n_entries], group-major, sorted inside a group
+    std::vector<double> weight;     // [n_entries] in the same order; empty: all ones
+    std::vector<uint32_t> wave_seg; // [n_wave][3]: first entry, end entry, index of the segment's partial sum
+    std::vector<uint32_t> row_seg;  // [n_row][3]: the same, segments a 16-lane row reduces
+    std::vector<uint32_t> part_off; // [n_groups + 1]: a group's partial sums, in segment order (none: an empty group)
+};
+// (of a report that passed check_series_report; key[i]: the device-order key of the caller's entry i)
+void build_group_tables(int64_t n_groups, const int64_t *offset, const double *weight, const uint64_t *key, GroupTables &t);
+// Internal consistency of the tables against the report's offsets (used by the host-only check): HEAT_OK or HEAT_E_SIZE.
+int check_group_tables(int64_t n_groups, const int64_t *offset, const GroupTables &t, std::string &err);
+
 // Zone-connected clusters (model.rs:556-590: surfaces exchange heat only through the zones they face): cluster id
 // per surface (-1: faces no zone) and per zone, ids dense in [0, n_clusters).
 void find_clusters(const heat_batch_desc *d, std::vector<int32_t> &cluster_of_surface,

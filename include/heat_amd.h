@@ -345,6 +345,82 @@ int heat_zone_loads_check(const heat_batch_desc *desc, const heat_series *s, con
 int heat_batch_march_series_loads(heat_batch *b, const heat_series *s, const heat_zone_loads *l,
                                   double *trace /* [n_steps][n_probes] */,
                                   double *applied /* [n_steps][n_thermostats], nullable */, int32_t *failed_step);
+
+/*
+ * Report of a series: statistics and weighted group sums maintained ON THE DEVICE at every step, instead of a
+ * [n_steps][n_probes] trace the caller reduces afterwards. Everything here is O(1) state per quantity, independent of
+ * n_steps in memory and in transfer: a year of quarter-hour steps (35 040) reports on a million quantities without a trace.
+ * heat_batch_march_series_report is the series with loads plus a report; r == NULL is heat_batch_march_series_loads exactly
+ * (and l == NULL then heat_batch_march_series), with ONE difference: trace == NULL means "record no trace" — no
+ * [n_steps][n_probes] buffer exists on the device, the probes still define quantities. Likewise applied == NULL keeps no
+ * [n_steps][n_thermostats] buffer (one row of scratch where thermostat statistics need the powers).
+ * Quantities: Q = n_probes + n_groups. Quantity q < n_probes is probe q of the series; quantity n_probes + g is group g.
+ * Groups: group g is the entries [group_offset[g], group_offset[g + 1]) (CSR) of group_slot / group_weight; a slot is
+ *   anything a probe may be (node temperature, hs, convective flow front / back, zone dry-bulb). The value of group g after
+ *   step k is the sum of weight[i] * slot_i over its entries (group_weight == NULL: all ones); an empty group is 0.0.
+ *   group_trace (nullable): group_trace[k * n_groups + g] is that value. The order of the summation is the library's: it is
+ *   fixed by the group's own entries alone (sorted into device order, cut into segments of a fixed number of entries, a fixed
+ *   tree inside a segment, the segments added in order) — never by launch geometry, timing, or the other groups and probes
+ *   of the report. The same report on the same state gives the same bits, and with n entries
+ *   |value - exact| <= n * 2^-52 * sum |weight[i] * slot_i|.
+ * Statistics: every array is in/out and nullable; a NULL array is not maintained (and costs no traffic). With v the value of
+ *   quantity q after step k and K = step_base + k, applied at every step in step order:
+ *     q_min, q_step_min     if (v < min) { min = v; step_min = K; }      (strict: the first occurrence; a NaN never enters)
+ *     q_max, q_step_max     if (v > max) { max = v; step_max = K; }
+ *     q_sum                 sum = sum + v                                 (one rounded addition per step)
+ *     q_n_below, q_deg_below, limit q_lo (input)   if (v < lo) { n += 1; deg = deg + (lo - v); }
+ *     q_n_above, q_deg_above, limit q_hi (input)   if (v > hi) { n += 1; deg = deg + (v - hi); }
+ *   A NaN limit never counts. q_step_min / q_step_max without q_min / q_max are refused (HEAT_E_INVALID_ARG), as is a count
+ *   or degree array without its limit array. resume == 0: the library initialises on the device (min = +inf, max = -inf,
+ *   steps = -1, sums and counts 0); resume != 0: the accumulators start from the caller's arrays. No fused multiply-add: a
+ *   host applying the rules in a plain loop over the full trace gets the same bits, and a series of k steps followed by one
+ *   of n - k with resume = 1 and step_base + k gives the bits of the series of n.
+ * Thermostat statistics (only with loads and n_thermostats > 0; caller's thermostat order; same resume rule):
+ *     th_steps_heating / th_steps_cooling   steps whose mode after the evaluation of the step is 1 / 2
+ *     th_switches                           steps whose mode after the evaluation differs from the mode before it (before
+ *                                           step 0: the incoming th_mode byte, 0 when th_mode is NULL)
+ *     th_sum_heating / th_sum_cooling       sum = sum + applied over the steps with applied > 0 / applied < 0
+ *   They equal the same loop over the returned applied rows and modes bit for bit.
+ * heat_series_report_check (host-only; it also builds the group tables — ordered by kind, surface or zone and node, since
+ * without a batch there is no device layout to order them by) and the march run the same checks before any device work: a
+ * negative count, a NULL array a positive count needs, group_offset not starting at 0 or decreasing, a non-finite weight,
+ * a count / degree array without its limit, a step array without its extremum, thermostat arrays without thermostats ->
+ * HEAT_E_INVALID_ARG; a group slot that is none of this path's output slots -> HEAT_E_SIZE. The message names
+ * "group g" or "group entry i". Sharded batches are refused as by the series.
+ * n_steps == 0 touches nothing, not even with resume == 0. n_sub == 0 still evaluates every step's report, on the unchanged
+ * state. failed_step, the return code and heat_batch_failed_surface behave as in the series, also with trace == NULL; after
+ * a numerical failure every report output is unspecified from the failed step on, as the trace is.
+ */
+typedef struct heat_series_report {
+    int32_t resume;             /* 0: accumulators initialised by the library; else: they start from the arrays below */
+    int64_t step_base;          /* K = step_base + k is what q_step_min / q_step_max record */
+    int64_t n_groups;
+    const int64_t *group_offset;/* [n_groups + 1], CSR */
+    const int64_t *group_slot;  /* [group_offset[n_groups]] */
+    const double *group_weight; /* same length; NULL = 1 */
+    double *group_trace;        /* [n_steps][n_groups], nullable */
+    /* statistics, [n_probes + n_groups] each, in/out, nullable */
+    double *q_min;
+    int64_t *q_step_min;
+    double *q_max;
+    int64_t *q_step_max;
+    double *q_sum;
+    const double *q_lo;         /* input */
+    int64_t *q_n_below;
+    double *q_deg_below;
+    const double *q_hi;         /* input */
+    int64_t *q_n_above;
+    double *q_deg_above;
+    /* thermostat statistics, [n_thermostats] each, in/out, nullable */
+    int64_t *th_steps_heating, *th_steps_cooling, *th_switches;
+    double *th_sum_heating, *th_sum_cooling;
+} heat_series_report;
+
+int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l /* nullable */,
+                             const heat_series_report *r); /* host-only */
+int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const heat_zone_loads *l /* nullable */,
+                                   heat_series_report *r /* nullable */, double *trace /* [n_steps][n_probes], nullable */,
+                                   double *applied /* [n_steps][n_thermostats], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -12,15 +12,27 @@ With --loads two other legs, alternated in the same way, one gain, one infiltrat
      thermostat cannot be a row at all) — what a series offered for these terms before the loads
   D  march_series with the loads formed on the device at every step
 and writes profiles/series_loads.json: ms per step of each, D / C, and a series of one step of each.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads]
-  python tools/series.py --one-series [S] [steps] [--loads]   one warm-up series and one more of n_sub = 2, nothing else
-                                                     (to run under rocprofv3 --kernel-trace --stats)"""
+With --report (heat_batch_march_series_report; the loads of --loads) four legs, alternated in the same way:
+  D  march_series with the loads, probes = all zones (the leg of --loads, re-measured here)
+  E  the same series tracing all zones and both convective flows of every wall, then numpy on the host: minimum, maximum, sum
+     and steps above 26 C of every zone, one area-weighted envelope-flow sum per zone and step, the thermostats' steps, switches
+     and sums from the applied rows — the only way to these numbers without a report
+  F  the same series with a report and no trace: those statistics of every zone and of one envelope-flow group per zone, and
+     the thermostat statistics
+  G  F with the inside-face node of every wall as further probes (Q = S + 2 Z) and q_min alone; G4: with F's four statistics
+and writes profiles/series_report.json.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes]
+                                                     one warm-up series and one more of n_sub = 2, nothing else (to run under
+                                                     rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
+                                                     over the flows of all sides instead of one per zone; with nodes leg G"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from heat_amd import HeatBatch, modeldict as mdl
 ONE = "--one-series" in sys.argv
-LOADS = "--loads" in sys.argv
+REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
+LOADS = "--loads" in sys.argv or REPORT is not None
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -51,6 +63,55 @@ if LOADS:
         1002.7370 + 1.2324e-2 * tk)
     rows_a0 = loads["gains"]["factor"] * channel[:, N_CHANNELS:N_CHANNELS + 1] + mcp * channel[:, N_CHANNELS + 2:N_CHANNELS + 3]
     rows_b0 = mcp
+if REPORT:
+    # the envelope of zone z: both faces of the walls whose back faces it (uniform_massive: all of a zone's walls, contiguous)
+    assert np.all(np.diff(md["back_zone"]) >= 0) and np.all(md["back_kind"] == mdl.SPACE)
+    walls_of = np.searchsorted(md["back_zone"], np.arange(Z + 1))
+    env_slots = np.concatenate([np.concatenate([md["flow_front_slot"][a:e], md["flow_back_slot"][a:e]]) for a, e in zip(walls_of[:-1], walls_of[1:])])
+    env_weights = np.concatenate([np.tile(md["area"][a:e], 2) for a, e in zip(walls_of[:-1], walls_of[1:])])
+    env_off = 2 * walls_of.astype(np.int64)
+    inside_nodes = md["first_node_slot"] + np.diff(md["node_offset"]) - 1
+    HOT = 26.0
+    TH = ("steps_heating", "steps_cooling", "switches", "sum_heating", "sum_cooling")
+    zone_groups = dict(offset=env_off, slot=env_slots, weight=env_weights)
+    one_group = dict(offset=np.array([0, len(env_slots)]), slot=env_slots, weight=env_weights)
+
+    def report_of(n_probes, groups, stats):
+        Q = n_probes + len(groups["offset"]) - 1
+        hi = np.full(Q, np.nan)
+        hi[:Z] = HOT
+        return dict(groups=groups, stats=stats, limits=dict(hi=hi) if "n_above" in stats else None, thermostat_stats=TH)
+
+    def leg_e(b, w, n_sub, steps):
+        """Trace everything, reduce on the host."""
+        b.synchronize()
+        t0 = time.perf_counter()
+        pr = np.concatenate([probes, env_slots])
+        trace, failed, applied, modes = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=pr, loads=loads, **drives)
+        t1 = time.perf_counter()
+        zt = trace[:, :Z]
+        out = dict(q_min=zt.min(axis=0), q_max=zt.max(axis=0), q_sum=np.add.accumulate(zt, axis=0)[-1], q_n_above=(zt > HOT).sum(axis=0),
+                   envelope=np.add.reduceat(trace[:, Z:] * env_weights, env_off[:-1], axis=1))
+        mode = np.where(applied > 0, 1, np.where(applied < 0, 2, 0))
+        before = np.concatenate([np.zeros((1, Z), mode.dtype), mode[:-1]])
+        out.update(th_steps_heating=(mode == 1).sum(axis=0), th_steps_cooling=(mode == 2).sum(axis=0), th_switches=(mode != before).sum(axis=0),
+                   th_sum_heating=np.add.accumulate(np.where(applied > 0, applied, 0.0), axis=0)[-1],
+                   th_sum_cooling=np.add.accumulate(np.where(applied < 0, applied, 0.0), axis=0)[-1])
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(out["envelope"]))
+        return dt * 1e3 / steps, (t1 - t0) * 1e3 / steps, out
+
+    def leg_f(b, w, n_sub, steps, pr=probes, groups=zone_groups, stats=("min", "max", "sum", "n_above")):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, out = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=pr, loads=loads,
+                                                            report=report_of(len(pr), groups, stats), trace=False, applied=False, **drives)
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(out["q_min"]))
+        return dt * 1e3 / steps, out
+
+    def leg_g(b, w, n_sub, steps, stats=("min",)):
+        return leg_f(b, w, n_sub, steps, pr=np.concatenate([probes, inside_nodes]), stats=stats)
 
 
 def leg_a(b, state, w, n_sub, steps):
@@ -110,6 +171,45 @@ with HeatBatch(md) as b:
     b.upload_state(state)
     for n_sub in ((2,) if ONE else (2, 20)):
         w = mdl.weather_series(STEPS * n_sub, 45.0).reshape(STEPS, n_sub, 3)
+        if REPORT:
+            if ONE:
+                leg = dict(zones=leg_f, nodes=leg_g)
+                run = (lambda n: leg_f(b, w, n_sub, n, groups=one_group)[0]) if REPORT == "one-group" else (lambda n: leg[REPORT](b, w, n_sub, n)[0])
+                run(min(STEPS, 10))  # warm-up
+                print("one series with a report (%s): %.3f ms per step" % (REPORT, run(STEPS)))
+                continue
+            leg_d(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_f(b, w, n_sub, min(STEPS, 10))
+            leg_e(b, w, n_sub, min(STEPS, 10))
+            d, e, e_dev, f, g, g4, f1, d1 = [], [], [], [], [], [], [], []
+            for r in range(ROUNDS):
+                d.append(leg_d(b, w, n_sub, STEPS))
+                x, y, host = leg_e(b, w, n_sub, STEPS)
+                e.append(x), e_dev.append(y)
+                x, dev = leg_f(b, w, n_sub, STEPS)
+                f.append(x)
+                g.append(leg_g(b, w, n_sub, STEPS)[0])
+                g4.append(leg_g(b, w, n_sub, STEPS, stats=("min", "max", "sum", "n_above"))[0])
+                f1.append(leg_f(b, w, n_sub, 1)[0])
+                d1.append(leg_d(b, w, n_sub, 1))
+            # (the legs march on from one another's state, so host and device numbers are of different steps: not compared here;
+            # tests/test_series_report_gpu.py compares them)
+            med = lambda v: float(np.median(v))
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                D_series_with_loads_ms=med(d), E_trace_and_numpy_ms=med(e), E_march_and_trace_alone_ms=med(e_dev), F_report_ms=med(f),
+                G_report_and_node_min_ms=med(g), G4_report_and_four_node_statistics_ms=med(g4), F_series_of_one_step_ms=med(f1),
+                F_without_setup_ms=(med(f) * STEPS - med(f1)) / (STEPS - 1), D_series_of_one_step_ms=med(d1),
+                D_without_setup_ms=(med(d) * STEPS - med(d1)) / (STEPS - 1),
+                F_over_D=med(f) / med(d), E_over_F=med(e) / med(f), G_minus_F_ms=med(g) - med(f), G4_minus_F_ms=med(g4) - med(f),
+                quantities=dict(F=int(2 * Z), G=int(2 * Z + S)), group_entries=int(len(env_slots)),
+                all_rounds=dict(D=d, E=e, E_march_and_trace=e_dev, F=f, G=g, G4=g4, F_one_step=f1, D_one_step=d1))
+            print("n_sub %2d: D loads %.3f ms/step, E trace + numpy %.3f (%.3f before numpy), F report %.3f -> F / D = %.3f, E / F = %.1f; "
+                  "G %.3f, G4 %.3f; a series of one step: F %.2f ms, D %.2f ms -> per step without the set-up F %.3f, D %.3f "
+                  "(%d steps, median of %d rounds)" % (
+                      n_sub, med(d), med(e), med(e_dev), med(f), med(f) / med(d), med(e) / med(f), med(g), med(g4), med(f1), med(d1),
+                      (med(f) * STEPS - med(f1)) / (STEPS - 1), (med(d) * STEPS - med(d1)) / (STEPS - 1), STEPS, ROUNDS),
+                  flush=True)
+            continue
         if LOADS:
             leg_rows(b, w, n_sub, min(STEPS, 10))  # warm-up
             leg_d(b, w, n_sub, min(STEPS, 10))
@@ -152,7 +252,7 @@ with HeatBatch(md) as b:
                   n_sub, A, A_np, B, Cc, Cc / A, Cc - B, steady, C1, STEPS, ROUNDS), flush=True)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_loads.json" if LOADS else "series_march.json")
+                              "series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json"))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
     print("wrote", out)
