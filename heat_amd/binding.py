@@ -97,6 +97,14 @@ class Report(C.Structure):
                 ("th_sum_heating", _dp), ("th_sum_cooling", _dp)]
 
 
+class IdealLoads(C.Structure):
+    """heat_ideal_loads (include/heat_amd.h): zones held at their setpoints in every sub-timestep, the power being the result"""
+    _fields_ = [("n_loads", C.c_int64), ("zone", _i32p), ("heat_chan", _i32p), ("cool_chan", _i32p),
+                ("heat_cap", _dp), ("cool_cap", _dp), ("resume", C.c_int32), ("step_base", C.c_int64),
+                ("sum_heating", _dp), ("sum_cooling", _dp), ("peak_heating", _dp), ("step_peak_heating", _i64p),
+                ("peak_cooling", _dp), ("step_peak_cooling", _i64p), ("n_sat_heating", _i64p), ("n_sat_cooling", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -135,6 +143,9 @@ SYMBOLS = [
     ("heat_batch_march_series_loads", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), _dp, _dp, _i32p]),
     ("heat_series_report_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(Report)]),
     ("heat_batch_march_series_report", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(Report), _dp, _dp, _i32p]),
+    ("heat_ideal_loads_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(IdealLoads)]),
+    ("heat_batch_march_series_ideal", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(IdealLoads), C.POINTER(Report),
+                                                _dp, _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -284,7 +295,7 @@ def make_desc(md):
 
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
-                     "heat_series_report_check",
+                     "heat_series_report_check", "heat_ideal_loads_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -612,6 +623,69 @@ def series_report_check(md, report=None, loads=None, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+IDEAL_STATS = ("sum_heating", "sum_cooling", "peak_heating", "step_peak_heating", "peak_cooling", "step_peak_cooling",
+               "n_sat_heating", "n_sat_cooling")
+_IDEAL_INT = ("step_peak_heating", "step_peak_cooling", "n_sat_heating", "n_sat_cooling")
+
+
+def make_ideal_loads(zone=None, heat_chan=None, cool_chan=None, heat_cap=None, cool_cap=None, stats=IDEAL_STATS, resume=None,
+                     step_base=0):
+    """Builds a heat_ideal_loads. Returns (ideal, keepalive); the march updates the accumulators of keepalive in place.
+    zone, heat_chan, cool_chan   equally long: the zone of every load and its setpoint channels (-1: none; a missing array: all -1)
+    heat_cap, cool_cap           W >= 0, inf = unlimited (optional: all unlimited)
+    stats                        names out of IDEAL_STATS: which accumulators are maintained (default: all)
+    resume                       a dict of arrays a previous series returned: the accumulators start from them
+    step_base                    the number the first step of this series has in step_peak_heating / step_peak_cooling"""
+    keep = {}
+    il = IdealLoads()
+    il.step_base = int(step_base)
+    il.resume = 0 if resume is None else 1
+    z = np.atleast_1d(np.array(zone if zone is not None else [], dtype=np.int32))
+    n = len(z)
+    il.n_loads = n
+    if z.ndim != 1:
+        raise ValueError("ideal loads: zone of shape %s" % (z.shape,))
+    for name, v, dtype in (("zone", z, np.int32), ("heat_chan", heat_chan, np.int32), ("cool_chan", cool_chan, np.int32),
+                           ("heat_cap", heat_cap, np.float64), ("cool_cap", cool_cap, np.float64)):
+        if v is None:
+            if not name.endswith("_chan"):
+                continue
+            v = np.full(n, -1)
+        a = np.atleast_1d(np.array(v, dtype=dtype))
+        if a.shape != (n,):
+            raise ValueError("ideal loads: %s of shape %s for %d loads" % (name, a.shape, n))
+        keep[name] = a
+        if n:
+            setattr(il, name, a.ctypes.data_as(_i32p if dtype == np.int32 else _dp))
+    for name in (stats or ()):
+        if name not in IDEAL_STATS:
+            raise ValueError("unknown ideal-load statistic %r (known: %s)" % (name, ", ".join(IDEAL_STATS)))
+        dtype = np.int64 if name in _IDEAL_INT else np.float64
+        if resume is not None:
+            if name not in resume:
+                raise ValueError("resume: %s is missing" % name)
+            a = np.array(resume[name], dtype=dtype).reshape(-1)  # (a copy: the march writes it)
+            if len(a) != n:
+                raise ValueError("resume: %s of %d values for %d loads" % (name, len(a), n))
+        else:
+            a = np.zeros(n, dtype)  # (the library initialises on the device)
+        keep[name] = a
+        setattr(il, name, a.ctypes.data_as(_i64p if dtype == np.int64 else _dp))
+    return il, keep
+
+
+def ideal_loads_check(md, ideal=None, lib=None, **series):
+    """heat_ideal_loads_check: everything about the ideal loads of a series that needs no device (series arguments as
+    HeatBatch.march_series; ideal: the arguments of make_ideal_loads). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    il, ikeep = make_ideal_loads(**(ideal or {}))
+    rc = L.heat_ideal_loads_check(C.byref(desc), C.byref(s), C.byref(il))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -722,7 +796,7 @@ class HeatBatch:
     def synchronize(self):
         _check(self._L.heat_batch_synchronize(self._h))
 
-    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, **series):
+    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -732,7 +806,14 @@ class HeatBatch:
         report (a dict of make_report's arguments: groups, stats, limits, thermostat_stats, group_trace, resume, step_base):
         heat_batch_march_series_report — statistics and group sums maintained on the device. The report's arrays (a dict of
         numpy arrays: q_min, th_switches, group_trace, ...; pass it as resume to the next series) are returned as one more
-        element. With a report, trace=False / applied=False record no trace / applied powers: an empty array comes back."""
+        element. With a report, trace=False / applied=False record no trace / applied powers: an empty array comes back.
+        ideal (a dict of make_ideal_loads' arguments: zone, heat_chan, cool_chan, heat_cap, cool_cap, stats, resume, step_base):
+        heat_batch_march_series_ideal — zones held at their setpoints in every sub-timestep. Returns a dict: trace, failed_step,
+        ideal_q [n_steps, n_loads] (the step's sum of the power over its sub-timesteps; / n_sub: the mean power in W),
+        ideal (the accumulators: pass it as resume to the next series), and with loads applied and modes, with a report
+        report."""
+        if ideal is not None:
+            return self._march_series_ideal(weather, n_sub, loads, ideal, report, trace, applied, series)
         if report is not None:
             return self._march_series_report(weather, n_sub, loads, report, trace, applied, series)
         if not (trace and applied):
@@ -783,6 +864,35 @@ class HeatBatch:
         if loads is None:
             return trace, int(failed.value), out
         return trace, int(failed.value), applied, lkeep.get("th_mode", np.zeros(0, np.uint8)), out
+
+    def _march_series_ideal(self, weather, n_sub, loads, ideal, report, want_trace, want_applied, series):
+        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
+        _series_arrays_fit(keep, self.n_surfaces)
+        for k in ("zone_a0", "zone_b0"):
+            if k in keep and keep[k].shape[1] != self.n_zones:
+                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
+        l, lkeep = make_zone_loads(**(loads or {}))
+        il, ikeep = make_ideal_loads(**ideal)
+        r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **(report or {}))
+        trace = np.zeros((s.n_steps if want_trace else 0, s.n_probes))
+        applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
+        ideal_q = np.zeros((s.n_steps, il.n_loads))
+        failed = C.c_int32(-1)
+        rc = self._L.heat_batch_march_series_ideal(self._h, C.byref(s), C.byref(l) if loads is not None else None, C.byref(il),
+                                                   C.byref(r) if report is not None else None,
+                                                   trace.ctypes.data_as(_dp) if trace.size else None,
+                                                   applied.ctypes.data_as(_dp) if applied.size else None,
+                                                   ideal_q.ctypes.data_as(_dp) if ideal_q.size else None, C.byref(failed))
+        if rc != 0:
+            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
+            e.failed_step, e.trace = int(failed.value), trace
+            raise e
+        out = dict(trace=trace, failed_step=int(failed.value), ideal_q=ideal_q, ideal={k: ikeep[k] for k in IDEAL_STATS if k in ikeep})
+        if loads is not None:
+            out.update(applied=applied, modes=lkeep.get("th_mode", np.zeros(0, np.uint8)))
+        if report is not None:
+            out["report"] = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
+        return out
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -1034,6 +1034,17 @@ struct ReportDev {
     DevBuf<int64_t> th_i64[3];
 };
 
+// The device copies of the ideal loads of a series (heat_ideal_loads): tables, the step's setpoints and q-sums, accumulators,
+// the ideal_q rows. Declared before the SeriesDrain of the call, as ReportDev is.
+struct IdealDev {
+    DevBuf<int32_t> i32;     // load_of_zone [Z] | heat_chan [N] | cool_chan [N]
+    DevBuf<double> cap;      // heat_cap [N] | cool_cap [N]
+    DevBuf<double> step;     // setpoint [2][N] | qsum [N]
+    DevBuf<double> q;        // ideal_q [n_steps][N]
+    DevBuf<double> f64[4];   // sum_heating, sum_cooling, peak_heating, peak_cooling
+    DevBuf<int64_t> i64[4];  // step_peak_heating, step_peak_cooling, n_sat_heating, n_sat_cooling
+};
+
 template <typename T>
 int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
     const hipError_t e = buf.alloc(count);
@@ -1943,6 +1954,25 @@ static int march_body(heat_batch *b, int32_t n_sub) {
     return HEAT_OK;
 }
 
+// The body of a step of a series with ideal loads (heat_ideal_loads): every sub-timestep streamed — the surface kernels, the
+// zone sums as partials (k_zones, mode 1), the zone update with the rule (k_zone_update_ideal) — in plain launches on the
+// batch's stream. The cluster-resident march balances its zones in LDS and cannot host the rule; the batch's fusion setting
+// and the graph cache of the plain calls are not touched.
+static int march_body_ideal(heat_batch *b, int32_t n_sub, const IdealLoadsDev &ild) {
+    if (n_sub == 0) return HEAT_OK;
+    b->host_zones_stale = true;
+    MarchGuard guard(b);
+    b->partial_ptr = b->d_partial.p;  // (a caller's buffer, heat_batch_use_partials, is left alone; restored by the guard)
+    for (int i = 0; i < n_sub; i++) {
+        enqueue_surfaces(b, -1);
+        enqueue_zones(b, 1);
+        launch_zone_update_ideal(b->d_partial.p, b->d_zone_a0.p, b->d_zone_b0.p, b->d_zone_vol.p, b->d_zone_T.p, (int)b->n_zones, b->dt,
+                                 b->d_step.p, b->d_flags.p, ild, b->stream);
+    }
+    HIP_TRY(hipGetLastError());
+    return HEAT_OK;
+}
+
 int heat_batch_synchronize(heat_batch *b) {
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     int rc = select_device(b);
@@ -1997,8 +2027,10 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 
 // heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
+// il == nullptr, or no ideal load, is the series without them: the same launches.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
-                             double *trace, double *applied, int32_t *failed_step) {
+                             double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
+                             double *ideal_q = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2017,6 +2049,10 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     std::vector<ResolvedSlot> group_entry;
     rc = check_series_report(*b->resolver, l, r, heat::last_error(), &group_entry);
     if (rc) return rc;
+    std::vector<int32_t> load_of_zone;
+    rc = check_ideal_loads(b->n_zones, s->n_channels, il, heat::last_error(), &load_of_zone);
+    if (rc) return rc;
+    const int64_t NI = il ? il->n_loads : 0;
     if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
@@ -2153,6 +2189,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     DevBuf<uint32_t> d_face, d_pidx;
     DevBuf<int> d_fail;
     ReportDev rd;
+    IdealDev idd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2259,6 +2296,34 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             td.prev = rd.prev.p;
         }
     }
+    IdealLoadsDev ild{};
+    if (NI > 0) {
+        const bool resume = il->resume != 0;
+        const double inf = std::numeric_limits<double>::infinity();
+        std::vector<int32_t> h_i32(load_of_zone);
+        h_i32.insert(h_i32.end(), il->heat_chan, il->heat_chan + NI);
+        h_i32.insert(h_i32.end(), il->cool_chan, il->cool_chan + NI);
+        std::vector<double> h_cap(2 * (size_t)NI, inf);
+        if (il->heat_cap) std::copy(il->heat_cap, il->heat_cap + NI, h_cap.begin());
+        if (il->cool_cap) std::copy(il->cool_cap, il->cool_cap + NI, h_cap.begin() + NI);
+        if ((rc = series_upload(idd.i32, h_i32.data(), h_i32.size(), "ideal load tables"))) return rc;
+        if ((rc = series_upload(idd.cap, h_cap.data(), h_cap.size(), "ideal load tables"))) return rc;
+        if ((rc = series_alloc(idd.step, 3 * (size_t)NI, "ideal load setpoints"))) return rc;
+        if (ideal_q && (rc = series_alloc(idd.q, (size_t)n_steps * NI, "ideal powers"))) return rc;
+        double *const f64[4] = {il->sum_heating, il->sum_cooling, il->peak_heating, il->peak_cooling};
+        int64_t *const i64[4] = {il->step_peak_heating, il->step_peak_cooling, il->n_sat_heating, il->n_sat_cooling};
+        for (int a = 0; a < 4; a++)
+            if ((rc = report_array(idd.f64[a], f64[a], (size_t)NI, resume, "ideal load accumulators"))) return rc;
+        for (int a = 0; a < 4; a++)
+            if ((rc = report_array(idd.i64[a], i64[a], (size_t)NI, resume, "ideal load accumulators"))) return rc;
+        ild.n_loads = (int)NI;
+        ild.load_of_zone = idd.i32.p, ild.heat_chan = idd.i32.p + Z, ild.cool_chan = idd.i32.p + Z + NI;
+        ild.heat_cap = idd.cap.p, ild.cool_cap = idd.cap.p + NI;
+        ild.setpoint = idd.step.p, ild.qsum = idd.step.p + 2 * NI;
+        ild.sum_heating = idd.f64[0].p, ild.sum_cooling = idd.f64[1].p, ild.peak_heating = idd.f64[2].p, ild.peak_cooling = idd.f64[3].p;
+        ild.step_peak_heating = idd.i64[0].p, ild.step_peak_cooling = idd.i64[1].p;
+        ild.n_sat_heating = idd.i64[2].p, ild.n_sat_cooling = idd.i64[3].p;
+    }
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
 
     SeriesInputs in{};
@@ -2277,6 +2342,13 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         for (int a = 0; a < 3; a++)
             if (rd.th_i64[a].p) HIP_TRY(hipMemsetAsync(rd.th_i64[a].p, 0, rd.th_i64[a].n * sizeof(int64_t), b->stream));
     }
+    if (NI > 0 && il->resume == 0) {  // sums and counts 0, peak_heating = -inf, peak_cooling = +inf, steps = -1
+        const double inf = std::numeric_limits<double>::infinity();
+        const double f64_init[4] = {0.0, 0.0, -inf, inf};
+        for (int a = 0; a < 4; a++) launch_fill_f64(idd.f64[a].p, (int64_t)idd.f64[a].n, f64_init[a], b->stream);
+        for (int a = 0; a < 4; a++)
+            if (idd.i64[a].p) HIP_TRY(hipMemsetAsync(idd.i64[a].p, a < 2 ? 0xff : 0, idd.i64[a].n * sizeof(int64_t), b->stream));
+    }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
     // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> the body of a march call of n_sub -> probes ----
@@ -2290,8 +2362,14 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
-        rc = march_body(b, n_sub);
+        if (NI > 0) {
+            launch_series_ideal_begin(ild, d_channel.p + (size_t)k * NC, b->stream);
+            rc = march_body_ideal(b, n_sub, ild);
+        } else {
+            rc = march_body(b, n_sub);
+        }
         if (rc) return rc;
+        if (NI > 0) launch_series_ideal_end(ild, idd.q.p ? idd.q.p + (size_t)k * NI : nullptr, il->step_base + k, b->stream);
         // (without a trace: no probe is copied, lane 0 still watches the failure flags)
         launch_series_probe(d_trace.p ? P : 0, d_pbuf.p, d_pidx.p, b->d_T.p, b->d_side_out.p, b->d_zone_T.p,
                             d_trace.p ? d_trace.p + (size_t)k * P : nullptr, b->d_flags.p, d_fail.p, k, b->stream);
@@ -2326,6 +2404,15 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         for (int a = 0; a < 3; a++)
             if (rd.th_i64[a].p) HIP_TRY(hipMemcpyAsync(ti[a], rd.th_i64[a].p, (size_t)NT * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     }
+    if (NI > 0) {
+        if (idd.q.p) HIP_TRY(hipMemcpyAsync(ideal_q, idd.q.p, (size_t)n_steps * NI * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        double *const f64[4] = {il->sum_heating, il->sum_cooling, il->peak_heating, il->peak_cooling};
+        int64_t *const i64[4] = {il->step_peak_heating, il->step_peak_cooling, il->n_sat_heating, il->n_sat_cooling};
+        for (int a = 0; a < 4; a++)
+            if (idd.f64[a].p) HIP_TRY(hipMemcpyAsync(f64[a], idd.f64[a].p, (size_t)NI * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        for (int a = 0; a < 4; a++)
+            if (idd.i64[a].p) HIP_TRY(hipMemcpyAsync(i64[a], idd.i64[a].p, (size_t)NI * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2349,6 +2436,11 @@ int heat_batch_march_series_loads(heat_batch *b, const heat_series *s, const hea
 int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, double *trace,
                                    double *applied, int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step);
+}
+
+int heat_batch_march_series_ideal(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_ideal_loads *il,
+                                  heat_series_report *r, double *trace, double *applied, double *ideal_q, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

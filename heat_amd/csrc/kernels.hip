@@ -2448,6 +2448,108 @@ __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int6
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = value;
 }
+
+// Ideal loads of a series (heat_ideal_loads, include/heat_amd.h): the zone update of a sub-timestep with the power that holds
+// the setpoint. The rule is DEFINED as one rounded operation per line, in the header's order: no contraction here either.
+//
+// k_series_ideal_begin — one lane per load, behind k_series_zone_loads: the step's setpoints out of the channel row (so
+// that the sub-timestep kernel needs no per-step argument) and qsum = 0.
+__global__ void __launch_bounds__(256) k_series_ideal_begin(IdealLoadsDev il, const double *__restrict__ row) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= il.n_loads) return;
+    const int hc = il.heat_chan[i], cc = il.cool_chan[i];
+    il.setpoint[i] = hc >= 0 ? row[hc] : __builtin_nan("");
+    il.setpoint[il.n_loads + i] = cc >= 0 ? row[cc] : __builtin_nan("");
+    il.qsum[i] = 0.0;
+}
+
+// k_zone_update_ideal — one lane per zone, behind k_zones in mode 1: the zone update of k_zone_update from ONE block of
+// partial sums ([2][n_zones], summed by k_zones' lanes and tree), and for a zone with a load the rule of the header. A zone
+// has at most one load and a load one zone: qsum[i] and the saturation counts have one writer — plain stores, no atomics.
+__global__ void __launch_bounds__(256)
+k_zone_update_ideal(const double *__restrict__ partial, const double *__restrict__ a0, const double *__restrict__ b0,
+                    const double *__restrict__ zone_vol, double *__restrict__ zone_T, int n_zones, double dt,
+                    int *__restrict__ step_ptr, int *__restrict__ flags, IdealLoadsDev il) {
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z == 0) *step_ptr += 1;
+    if (z >= n_zones) return;
+    const int i = il.load_of_zone[z];
+    const double a = partial[z] + a0[z];
+    const double b = partial[n_zones + z] + b0[z];
+    const double tc = zone_T[z];
+    const double cz = zone_mcp(zone_vol[z], tc);  // model.rs:549-552
+    double q = 0.0, ft = tc;
+    if (fabs(b) > 1e-9) {  // model.rs:662-668
+        const double r = a / b;
+        const double nbdt = (-b) * dt;
+        const double E = exp(nbdt / cz);
+        const double dE = (tc - r) * E;
+        const double free_t = r + dE;
+        ft = free_t;
+        const double D = 1.0 - E;
+        if (i >= 0 && D > 0.0) {
+            const double h = il.setpoint[i], c = il.setpoint[il.n_loads + i];
+            const double tcE = tc * E;
+            if (il.heat_chan[i] >= 0 && free_t < h) {
+                const double num = b * (h - tcE);
+                const double need = num / D - a;
+                const double cap = il.heat_cap[i];
+                q = need > cap ? cap : need;
+                if (!(q > 0.0)) q = 0.0;
+                if (q > 0.0) {
+                    if (q == need) {
+                        ft = h;
+                    } else {
+                        const double a2 = a + q;
+                        const double r2 = a2 / b;
+                        const double d2 = (tc - r2) * E;
+                        ft = r2 + d2;
+                        if (il.n_sat_heating != nullptr) il.n_sat_heating[i] += 1;
+                    }
+                }
+            } else if (il.cool_chan[i] >= 0 && free_t > c) {
+                const double num = b * (c - tcE);
+                const double need = num / D - a;
+                const double cap = -il.cool_cap[i];
+                q = need < cap ? cap : need;
+                if (!(q < 0.0)) q = 0.0;
+                if (q < 0.0) {
+                    if (q == need) {
+                        ft = c;
+                    } else {
+                        const double a2 = a + q;
+                        const double r2 = a2 / b;
+                        const double d2 = (tc - r2) * E;
+                        ft = r2 + d2;
+                        if (il.n_sat_cooling != nullptr) il.n_sat_cooling[i] += 1;
+                    }
+                }
+            }
+        }
+    }
+    if (ft != ft) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);  // model.rs:417-420
+    zone_T[z] = ft;
+    if (i >= 0) il.qsum[i] = il.qsum[i] + q;
+}
+
+// k_series_ideal_end — one lane per load, on the step's tail: the step's row of ideal_q and the accumulators that exist
+// (the rules of k_series_stats with v = qsum). An extremum is stored only when it changes.
+__global__ void __launch_bounds__(256) k_series_ideal_end(IdealLoadsDev il, double *__restrict__ q_row, int64_t step) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= il.n_loads) return;
+    const double v = il.qsum[i];
+    if (q_row != nullptr) q_row[i] = v;
+    if (il.sum_heating != nullptr && v > 0.0) il.sum_heating[i] = il.sum_heating[i] + v;
+    if (il.sum_cooling != nullptr && v < 0.0) il.sum_cooling[i] = il.sum_cooling[i] + v;
+    if (il.peak_heating != nullptr && v > il.peak_heating[i]) {
+        il.peak_heating[i] = v;
+        if (il.step_peak_heating != nullptr) il.step_peak_heating[i] = step;
+    }
+    if (il.peak_cooling != nullptr && v < il.peak_cooling[i]) {
+        il.peak_cooling[i] = v;
+        if (il.step_peak_cooling != nullptr) il.step_peak_cooling[i] = step;
+    }
+}
 #pragma clang fp contract(fast)
 
 // ---------------------------------------------------------------------------
@@ -2754,6 +2856,23 @@ void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_fill_f64, dim3((unsigned int)((n + 255) / 256)), dim3(256), 0, st, dst, n, value);
+}
+
+void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipStream_t st) {
+    if (il.n_loads <= 0) return;
+    hipLaunchKernelGGL(k_series_ideal_begin, dim3((il.n_loads + 255) / 256), dim3(256), 0, st, il, row);
+}
+
+void launch_zone_update_ideal(const double *partial, const double *a0, const double *b0, const double *zone_vol, double *zone_T,
+                              int n_zones, double dt, int *step_ptr, int *flags, const IdealLoadsDev &il, hipStream_t st) {
+    const int nb = n_zones > 0 ? (n_zones + 255) / 256 : 1;
+    hipLaunchKernelGGL(k_zone_update_ideal, dim3(nb), dim3(256), 0, st, partial, a0, b0, zone_vol, zone_T, n_zones, dt, step_ptr,
+                       flags, il);
+}
+
+void launch_series_ideal_end(const IdealLoadsDev &il, double *q_row, int64_t step, hipStream_t st) {
+    if (il.n_loads <= 0) return;
+    hipLaunchKernelGGL(k_series_ideal_end, dim3((il.n_loads + 255) / 256), dim3(256), 0, st, il, q_row, step);
 }
 
 void launch_set_step(int *step_ptr, int v, int last, hipStream_t st) {

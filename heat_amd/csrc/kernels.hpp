@@ -139,4 +139,25 @@ struct SeriesThStatsDev {
 void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const uint8_t *mode, const double *applied_row, hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 
+// Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Per step: launch_series_ideal_begin (behind the zone loads)
+// copies the step's setpoints out of the channel row and zeroes qsum; per sub-timestep, behind the surface kernels and
+// launch_zones in mode 1 (partial = [2][n_zones]): launch_zone_update_ideal, one lane per zone — it takes no per-step
+// argument, so a captured sub-timestep stays valid over the steps; on the step's tail: launch_series_ideal_end.
+struct IdealLoadsDev {
+    int n_loads;
+    const int32_t *load_of_zone;            // [n_zones]: the zone's load, -1: none
+    const int32_t *heat_chan, *cool_chan;   // [n_loads]: setpoint channels, -1: none
+    const double *heat_cap, *cool_cap;      // [n_loads], +inf: unlimited
+    double *setpoint;                       // [2][n_loads]: the step's heating, then cooling setpoints
+    double *qsum;                           // [n_loads]: the step's sum of q over its sub-timesteps
+    int64_t *n_sat_heating, *n_sat_cooling; // [n_loads] each, nullptr: not maintained
+    double *sum_heating, *sum_cooling, *peak_heating, *peak_cooling;
+    int64_t *step_peak_heating, *step_peak_cooling;
+};
+void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipStream_t st);
+void launch_zone_update_ideal(const double *partial, const double *a0, const double *b0, const double *zone_vol, double *zone_T,
+                              int n_zones, double dt, int *step_ptr, int *flags, const IdealLoadsDev &il, hipStream_t st);
+// q_row: the step's row of ideal_q, or nullptr; step: K = step_base + k
+void launch_series_ideal_end(const IdealLoadsDev &il, double *q_row, int64_t step, hipStream_t st);
+
 }  // namespace heat

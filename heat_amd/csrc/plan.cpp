@@ -1848,6 +1848,43 @@ void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadT
     }
 }
 
+// ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
+int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
+                      std::vector<int32_t> *load_of_zone) {
+    if (load_of_zone) load_of_zone->assign((size_t)std::max<int64_t>(n_zones, 0), -1);
+    if (!il) return HEAT_OK;
+    if (il->n_loads < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count in ideal loads (n_loads %lld)", (long long)il->n_loads);
+    // (the table numbers the loads with 32 bits)
+    if (il->n_loads > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 ideal loads (n_loads %lld)", (long long)il->n_loads);
+    if (il->n_loads > 0 && (!il->zone || !il->heat_chan || !il->cool_chan))
+        return failp(err, HEAT_E_INVALID_ARG, "ideal loads: zone, heat_chan or cool_chan is NULL");
+    if ((il->step_peak_heating && !il->peak_heating) || (il->step_peak_cooling && !il->peak_cooling))
+        return failp(err, HEAT_E_INVALID_ARG, "ideal loads: step_peak_heating / step_peak_cooling without peak_heating / peak_cooling");
+    std::vector<int32_t> local;
+    std::vector<int32_t> &of = load_of_zone ? *load_of_zone : local;
+    if (!load_of_zone) of.assign((size_t)std::max<int64_t>(n_zones, 0), -1);
+    for (int64_t i = 0; i < il->n_loads; i++) {
+        const int32_t z = il->zone[i], hc = il->heat_chan[i], cc = il->cool_chan[i];
+        if (z < 0 || z >= n_zones)
+            return failp(err, HEAT_E_SIZE, "ideal load %lld: zone %d outside [0, %lld)", (long long)i, z, (long long)n_zones);
+        if (hc != -1 && (hc < 0 || hc >= n_channels))
+            return failp(err, HEAT_E_SIZE, "ideal load %lld: heating setpoint channel %d outside [-1, %d)", (long long)i, hc, n_channels);
+        if (cc != -1 && (cc < 0 || cc >= n_channels))
+            return failp(err, HEAT_E_SIZE, "ideal load %lld: cooling setpoint channel %d outside [-1, %d)", (long long)i, cc, n_channels);
+        if (hc == -1 && cc == -1)
+            return failp(err, HEAT_E_SIZE, "ideal load %lld: neither a heating nor a cooling setpoint channel", (long long)i);
+        const double *cap[2] = {il->heat_cap, il->cool_cap};
+        for (int a = 0; a < 2; a++)
+            if (cap[a] && !(cap[a][i] >= 0.0))  // (+inf passes: unlimited)
+                return failp(err, HEAT_E_INVALID_ARG, "ideal load %lld: %s capacity %g is negative or NaN", (long long)i,
+                             a ? "cooling" : "heating", cap[a][i]);
+        if (of[(size_t)z] >= 0)
+            return failp(err, HEAT_E_INVALID_ARG, "ideal load %lld: zone %d already has ideal load %d", (long long)i, z, of[(size_t)z]);
+        of[(size_t)z] = (int32_t)i;
+    }
+    return HEAT_OK;
+}
+
 // ---- report of a series (include/heat_amd.h, heat_series_report) ----
 int check_series_report(SlotResolver &res, const heat_zone_loads *l, const heat_series_report *r, std::string &err,
                         std::vector<ResolvedSlot> *resolved) {
@@ -2059,6 +2096,28 @@ int heat_zone_loads_check(const heat_batch_desc *desc, const heat_series *s, con
         for (size_t z = 0; z < Z1; z++)
             if (t.off[a * Z1 + z] < (z ? t.off[a * Z1 + z - 1] : 0) || t.off[a * Z1 + z] > n[a] || (z + 1 == Z1 && t.off[a * Z1 + z] != n[a]))
                 return heat::failp(heat::last_error(), HEAT_E_SIZE, "zone load tables: offsets of list %d are inconsistent at zone %zu", a, z);
+    return HEAT_OK;
+}
+
+int heat_ideal_loads_check(const heat_batch_desc *desc, const heat_series *s, const heat_ideal_loads *il) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    // ... and the table the march would upload, checked against the loads (this is the build the sanitizers see)
+    std::vector<int32_t> load_of_zone;
+    rc = heat::check_ideal_loads(desc->n_zones, s->n_channels, il, heat::last_error(), &load_of_zone);
+    if (rc || !il) return rc;
+    if (load_of_zone.size() != (size_t)desc->n_zones)
+        return heat::failp(heat::last_error(), HEAT_E_SIZE, "ideal load table: %zu entries for %lld zones", load_of_zone.size(), (long long)desc->n_zones);
+    int64_t n_set = 0;
+    for (int32_t i : load_of_zone) n_set += i >= 0;
+    if (n_set != il->n_loads)
+        return heat::failp(heat::last_error(), HEAT_E_SIZE, "ideal load table: %lld zones with a load for %lld loads", (long long)n_set, (long long)il->n_loads);
+    for (int64_t i = 0; i < il->n_loads; i++)
+        if (load_of_zone[(size_t)il->zone[i]] != (int32_t)i)
+            return heat::failp(heat::last_error(), HEAT_E_SIZE, "ideal load %lld: the table gives its zone %d load %d", (long long)i, il->zone[i],
+                               load_of_zone[(size_t)il->zone[i]]);
     return HEAT_OK;
 }
 

@@ -166,6 +166,12 @@ struct ZoneLoadTables {
 // (of loads that passed check_zone_loads)
 void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadTables &t);
 
+// Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
+// themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".
+// load_of_zone (nullable): [n_zones], the load of every zone or -1 — the table k_zone_update_ideal looks its zone up in.
+int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
+                      std::vector<int32_t> *load_of_zone = nullptr);
+
 // Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
 // report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
 // heat_status with `err` set, naming "group g" or "group entry i".

@@ -421,6 +421,82 @@ int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, 
 int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const heat_zone_loads *l /* nullable */,
                                    heat_series_report *r /* nullable */, double *trace /* [n_steps][n_probes], nullable */,
                                    double *applied /* [n_steps][n_thermostats], nullable */, int32_t *failed_step);
+
+/*
+ * Ideal loads of a series: in EVERY SUB-TIMESTEP a zone with an ideal load receives exactly the power that brings it to its
+ * setpoint, limited by a capacity, and that power is the result of the run — the heating and cooling demand of the zone and
+ * its peak, which the dead-band thermostat of heat_zone_loads (a plant of fixed size switched once per step) cannot give.
+ * The reference leaves this controller as a todo!() (IdealHeaterCooler, heating_cooling.rs:66-119): the rule below is this
+ * library's own contract, defined against a host loop that runs iterate_surfaces, calculate_zones_abc and the rule in every
+ * sub-timestep. It cannot be formed by the caller: it needs the surface sums of the sub-timestep it acts in.
+ * Setpoints: h = channel[k][heat_chan[i]] and c = channel[k][cool_chan[i]] hold for all n_sub sub-timesteps of step k.
+ * In each sub-timestep, after the surfaces, for the zone of load i (every other zone is updated as ever, model.rs:650-674):
+ *   tc        the zone's temperature before the update
+ *   s_a, s_b  the zone's surface sums (sum of h A T_face, sum of h A; model.rs:562-585) exactly as the streamed zone balance
+ *             forms them: same lanes, same tree
+ *   a0, b0    the step's zone terms, INCLUDING the gains, flows and thermostat powers of heat_zone_loads (evaluated first)
+ * Every line is one rounded f64 operation in the order written, no fused multiply-add (zone_mcp: zone.rs:59-65):
+ *   a = s_a + a0;  b = s_b + b0;  cz = zone_mcp(volume, tc);  q = 0;  ft = tc
+ *   if (fabs(b) > 1e-9) {                        (model.rs:662-668: otherwise the zone keeps its temperature)
+ *       r = a / b;  E = exp(((-b) * dt) / cz);  free = r + (tc - r) * E;  ft = free;  D = 1 - E
+ *       if (D > 0) {
+ *           if (heat_chan >= 0 && free < h) {
+ *               need = (b * (h - tc * E)) / D - a
+ *               q = need > heat_cap ? heat_cap : need;  if (!(q > 0)) q = 0
+ *               if (q > 0) { if (q == need) ft = h;      (unsaturated: the zone IS at the setpoint, bit for bit)
+ *                            else { a2 = a + q;  r2 = a2 / b;  ft = r2 + (tc - r2) * E;  n_sat_heating += 1 } }
+ *           } else if (cool_chan >= 0 && free > c) {     (heating is looked at first; the mirror image)
+ *               need = (b * (c - tc * E)) / D - a
+ *               q = need < -cool_cap ? -cool_cap : need;  if (!(q < 0)) q = 0
+ *               if (q < 0) { if (q == need) ft = c;
+ *                            else { a2 = a + q;  r2 = a2 / b;  ft = r2 + (tc - r2) * E;  n_sat_cooling += 1 } }
+ *           }
+ *       }
+ *   }
+ *   zone_T = ft;  qsum[i] = qsum[i] + q          (qsum starts at 0.0 in every step)
+ * A NaN setpoint makes every comparison false: the zone floats. A NaN ft is HEAT_N_NAN_ZONE with the zone's number, as in
+ * the zone balance. After the step's last sub-timestep, with v = qsum[i] and K = step_base + k:
+ *   ideal_q[k * n_loads + i] = v                 (divide by n_sub for the step's mean power in W)
+ *   sum_heating += v where v > 0;  sum_cooling += v where v < 0            (one rounded addition per step)
+ *   if (v > peak_heating) { peak_heating = v; step_peak_heating = K; }     (strict: the first occurrence)
+ *   if (v < peak_cooling) { peak_cooling = v; step_peak_cooling = K; }
+ * Every accumulator is in/out and nullable. resume == 0: the library initialises on the device (sums and counts 0,
+ * peak_heating = -inf, peak_cooling = +inf, steps = -1); resume != 0: they start from the caller's arrays. n_sub == 0 gives
+ * qsum = 0 in every step. The controller has no memory: a series of k steps followed by one of n - k with resume = 1 and
+ * step_base + k gives the bits of the series of n (ideal_q, accumulators, trace and state).
+ * heat_cap / cool_cap: W, >= 0, +inf = unlimited; a NULL array = all unlimited. A capacity of 0 never acts.
+ * The zone of an ideal load may also be a thermostat's target or sensor, a gain or flow zone, a probe or a group entry.
+ * Weather sites are supported. A series with ideal loads marches every sub-timestep streamed (surfaces, zone sums, this
+ * rule): the cluster-resident march is not used for it, and the batch's fusion setting is left as it is for later calls.
+ * heat_ideal_loads_check (host-only) and heat_batch_march_series_ideal run the same checks before any device work; every
+ * message names "ideal load i": a negative count, a NULL array a positive count needs (zone, heat_chan, cool_chan), a step
+ * array without its peak array, a capacity that is negative or NaN, a second load on a zone -> HEAT_E_INVALID_ARG; a zone
+ * outside [0, n_zones), a channel outside [-1, n_channels), a load with neither setpoint channel -> HEAT_E_SIZE. Sharded
+ * batches are refused as by the series.
+ * heat_batch_march_series_ideal with il == NULL or n_loads == 0 is heat_batch_march_series_report exactly (same kernels,
+ * same bits); ideal_q is nullable. After a numerical failure ideal_q rows and accumulators from the failed step on are
+ * unspecified, as the trace is.
+ */
+typedef struct heat_ideal_loads {
+    int64_t n_loads;
+    const int32_t *zone;                   /* [n_loads], at most one load per zone */
+    const int32_t *heat_chan, *cool_chan;  /* setpoint channels of the series, -1: none (not both) */
+    const double *heat_cap, *cool_cap;     /* W, >= 0, +inf = unlimited; NULL = unlimited */
+    int32_t resume;                        /* as heat_series_report::resume, for the arrays below */
+    int64_t step_base;
+    /* accumulators, [n_loads] each, in/out, nullable */
+    double *sum_heating, *sum_cooling;     /* sum over steps of the step's q-sum, by sign */
+    double *peak_heating; int64_t *step_peak_heating;   /* largest step q-sum, first occurrence */
+    double *peak_cooling; int64_t *step_peak_cooling;   /* most negative step q-sum */
+    int64_t *n_sat_heating, *n_sat_cooling;             /* SUB-timesteps that ended at the capacity */
+} heat_ideal_loads;
+
+int heat_ideal_loads_check(const heat_batch_desc *desc, const heat_series *s, const heat_ideal_loads *il); /* host-only */
+int heat_batch_march_series_ideal(heat_batch *b, const heat_series *s, const heat_zone_loads *l /* nullable */,
+                                  heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */,
+                                  double *trace /* [n_steps][n_probes], nullable */,
+                                  double *applied /* [n_steps][n_thermostats], nullable */,
+                                  double *ideal_q /* [n_steps][n_loads], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

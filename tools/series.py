@@ -21,18 +21,26 @@ With --report (heat_batch_march_series_report; the loads of --loads) four legs, 
      the thermostat statistics
   G  F with the inside-face node of every wall as further probes (Q = S + 2 Z) and q_min alone; G4: with F's four statistics
 and writes profiles/series_report.json.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes]
+With --ideal (heat_batch_march_series_ideal; the channels, driven inputs and loads of --loads plus a cooling setpoint channel) three
+legs, alternated in the same way, one ideal load per zone, heating and cooling, unlimited:
+  S  the series with leg D's loads on a batch created with no_fusion: the streamed body the ideal path is built on
+  I  the same plus the ideal loads (same batch)
+  D  leg D itself, on the batch as planned (cluster-resident)
+and writes profiles/series_ideal.json: ms per step of each, I - S per sub-timestep, I / S and I / D.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
-                                                     over the flows of all sides instead of one per zone; with nodes leg G"""
+                                                     over the flows of all sides instead of one per zone; with nodes leg G;
+                                                     with --ideal leg I"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from heat_amd import HeatBatch, modeldict as mdl
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
-LOADS = "--loads" in sys.argv or REPORT is not None
+IDEAL = "--ideal" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -63,6 +71,18 @@ if LOADS:
         1002.7370 + 1.2324e-2 * tk)
     rows_a0 = loads["gains"]["factor"] * channel[:, N_CHANNELS:N_CHANNELS + 1] + mcp * channel[:, N_CHANNELS + 2:N_CHANNELS + 3]
     rows_b0 = mcp
+if IDEAL:
+    # one more channel, the cooling setpoint (C); every zone held between the heating setpoint of leg D's thermostats and it
+    channel = np.concatenate([channel, rng.uniform(24.0, 26.0, (STEPS, 1))], axis=1)
+    ideal = dict(zone=every, heat_chan=full(3), cool_chan=full(4))
+
+    def leg_i(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads, ideal=ideal, **drives)
+        dt = time.perf_counter() - t0
+        assert out["failed_step"] == -1 and np.all(np.isfinite(out["ideal_q"])) and np.all(np.isfinite(out["trace"]))
+        return dt * 1e3 / steps
 if REPORT:
     # the envelope of zone z: both faces of the walls whose back faces it (uniform_massive: all of a zone's walls, contiguous)
     assert np.all(np.diff(md["back_zone"]) >= 0) and np.all(md["back_kind"] == mdl.SPACE)
@@ -169,8 +189,32 @@ result = dict(model="uniform_massive(%d, 32, Z=%d)" % (S, md["n_zones"]), channe
 with HeatBatch(md) as b:
     state = st0.copy()
     b.upload_state(state)
+    if IDEAL:
+        bs = HeatBatch(md, no_fusion=True)
+        bs.upload_state(state)
     for n_sub in ((2,) if ONE else (2, 20)):
         w = mdl.weather_series(STEPS * n_sub, 45.0).reshape(STEPS, n_sub, 3)
+        if IDEAL:
+            leg_i(bs, w, n_sub, min(STEPS, 10))  # warm-up
+            if ONE:
+                print("one series with ideal loads: %.3f ms per step" % leg_i(bs, w, n_sub, STEPS))
+                continue
+            leg_d(bs, w, n_sub, min(STEPS, 10))
+            leg_d(b, w, n_sub, min(STEPS, 10))
+            ss, ii, dd = [], [], []
+            for r in range(ROUNDS):
+                ss.append(leg_d(bs, w, n_sub, STEPS))
+                ii.append(leg_i(bs, w, n_sub, STEPS))
+                dd.append(leg_d(b, w, n_sub, STEPS))
+            Sm, Im, Dm = float(np.median(ss)), float(np.median(ii)), float(np.median(dd))
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                S_streamed_series_with_loads_ms=Sm, I_ideal_series_ms=Im, D_series_with_loads_ms=Dm, I_minus_S_ms=Im - Sm,
+                I_minus_S_per_sub_timestep_us=(Im - Sm) * 1e3 / n_sub, I_over_S=Im / Sm, I_over_D=Im / Dm, ideal_loads=int(Z),
+                all_rounds=dict(S=ss, I=ii, D=dd))
+            print("n_sub %2d: S streamed series with loads %.3f ms/step, I with ideal loads %.3f, D fused %.3f -> I - S = %.3f ms "
+                  "(%.1f us per sub-timestep), I / S = %.3f, I / D = %.3f (%d steps, median of %d rounds)" % (
+                      n_sub, Sm, Im, Dm, Im - Sm, (Im - Sm) * 1e3 / n_sub, Im / Sm, Im / Dm, STEPS, ROUNDS), flush=True)
+            continue
         if REPORT:
             if ONE:
                 leg = dict(zones=leg_f, nodes=leg_g)
@@ -250,9 +294,12 @@ with HeatBatch(md) as b:
         print("n_sub %2d: A per-call %.3f ms/step (%.3f with numpy's writes), B resident %.3f, C series %.3f -> C / A = %.3f, "
               "C - B = %.3f ms (%.3f without the call's set-up: a series of one step takes %.2f ms; %d steps, median of %d rounds)" % (
                   n_sub, A, A_np, B, Cc, Cc / A, Cc - B, steady, C1, STEPS, ROUNDS), flush=True)
+if IDEAL:
+    bs.close()
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json"))
+                              "series_ideal.json" if IDEAL else
+                              ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
     print("wrote", out)
