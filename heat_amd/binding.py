@@ -105,6 +105,18 @@ class IdealLoads(C.Structure):
                 ("peak_cooling", _dp), ("step_peak_cooling", _i64p), ("n_sat_heating", _i64p), ("n_sat_cooling", _i64p)]
 
 
+class SkyRecord(C.Structure):
+    """heat_sky_record (include/heat_amd.h): the sun and sky of one site at one step, 64 bytes"""
+    _fields_ = [("sun_x", _d), ("sun_y", _d), ("sun_z", _d), ("beam", _d), ("diffuse", _d), ("ground", _d), ("ir_sky", _d),
+                ("ir_ground", _d)]
+
+
+class Sky(C.Structure):
+    """heat_sky (include/heat_amd.h): per-site records, per-surface normals and mode bytes of the sky of a series"""
+    _fields_ = [("record", C.POINTER(SkyRecord)), ("normal_x", _dp), ("normal_y", _dp), ("normal_z", _dp),
+                ("mode", C.POINTER(C.c_uint8))]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -146,6 +158,9 @@ SYMBOLS = [
     ("heat_ideal_loads_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(IdealLoads)]),
     ("heat_batch_march_series_ideal", C.c_int, [_H, C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(IdealLoads), C.POINTER(Report),
                                                 _dp, _dp, _dp, _i32p]),
+    ("heat_sky_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky)]),
+    ("heat_batch_march_series_sky", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(ZoneLoads), C.POINTER(IdealLoads),
+                                              C.POINTER(Report), _dp, _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -295,7 +310,7 @@ def make_desc(md):
 
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
-                     "heat_series_report_check", "heat_ideal_loads_check",
+                     "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -686,6 +701,66 @@ def ideal_loads_check(md, ideal=None, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+SKY_SOLAR_FRONT, SKY_SOLAR_BACK, SKY_IR_FRONT, SKY_IR_BACK = 1, 2, 4, 8
+
+
+def make_sky(record, mode, normals=None):
+    """Builds a heat_sky. Returns (sky, keepalive).
+    record   [n_steps, n_sites, 8] (or [n_steps, 8] for one site): sun_x, sun_y, sun_z, beam, diffuse, ground, ir_sky,
+             ir_ground of every site at every step (heat_sky_record)
+    mode     a byte per surface: SKY_SOLAR_FRONT | SKY_SOLAR_BACK | SKY_IR_FRONT | SKY_IR_BACK
+    normals  (x, y, z), each per surface: the outward normal of the front face (HeatBatch.march_series and sky_check take
+             the model's normal_x, normal_y, cos_tilt when it is None)"""
+    keep = {}
+    sky = Sky()
+    if record is not None:
+        rec = np.ascontiguousarray(record, dtype=np.float64)
+        if rec.ndim not in (2, 3) or rec.shape[-1] != 8:
+            raise ValueError("sky records are [n_steps, n_sites, 8], not %s" % (rec.shape,))
+        keep["record"] = rec
+        sky.record = C.cast(rec.ctypes.data, C.POINTER(SkyRecord)) if rec.size else None
+    if mode is not None:
+        m = np.ascontiguousarray(mode, dtype=np.uint8).reshape(-1)
+        keep["mode"] = m
+        sky.mode = m.ctypes.data_as(C.POINTER(C.c_uint8))
+    if normals is not None:
+        for name, a in zip(("normal_x", "normal_y", "normal_z"), normals):
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            keep[name] = a
+            setattr(sky, name, a.ctypes.data_as(_dp))
+    return sky, keep
+
+
+def _sky_fits(skeep, n_steps, n_sites, n_surfaces):
+    rec = skeep.get("record")
+    if rec is not None and rec.size and (rec.size // 8 != n_steps * n_sites or (rec.ndim == 3 and rec.shape[1] != n_sites)):
+        raise ValueError("sky records %s for %d steps of %d sites" % (rec.shape, n_steps, n_sites))
+    for k in ("mode", "normal_x", "normal_y", "normal_z"):
+        if k in skeep and skeep[k].shape != (n_surfaces,):
+            raise ValueError("sky %s: %s for %d surfaces" % (k, skeep[k].shape, n_surfaces))
+
+
+def _model_normals(md):
+    return md["normal_x"], md["normal_y"], md["cos_tilt"]
+
+
+def sky_check(md, sky, n_sites=1, lib=None, **series):
+    """heat_sky_check: everything about the sky of a series that needs no device (series arguments as
+    HeatBatch.march_series; sky: the arguments of make_sky, normals defaulting to the model's). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    sky = dict(sky)
+    if sky.get("normals") is None:
+        sky["normals"] = _model_normals(md)
+    k, kkeep = make_sky(**sky)
+    _sky_fits(kkeep, s.n_steps, int(n_sites), int(md["n_surfaces"]))
+    rc = L.heat_sky_check(C.byref(desc), int(n_sites), C.byref(s), C.byref(k))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -732,6 +807,8 @@ class HeatBatch:
         self.n_state = int(md["n_state"])
         self.n_zones = int(md["n_zones"])
         self.n_surfaces = int(md["n_surfaces"])
+        # (the default normals of a sky: the model's own; of a shard's batch they are the whole model's, like every array)
+        self._normals = tuple(np.array(a, dtype=np.float64) for a in _model_normals(md))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -796,7 +873,7 @@ class HeatBatch:
     def synchronize(self):
         _check(self._L.heat_batch_synchronize(self._h))
 
-    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, **series):
+    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -811,7 +888,12 @@ class HeatBatch:
         heat_batch_march_series_ideal — zones held at their setpoints in every sub-timestep. Returns a dict: trace, failed_step,
         ideal_q [n_steps, n_loads] (the step's sum of the power over its sub-timesteps; / n_sub: the mean power in W),
         ideal (the accumulators: pass it as resume to the next series), and with loads applied and modes, with a report
-        report."""
+        report.
+        sky (a dict of make_sky's arguments: record [n_steps, n_sites, 8], mode, normals — default: the model's normal_x,
+        normal_y, cos_tilt): heat_batch_march_series_sky — the solar and long-wave irradiance of the sides the mode bytes
+        name, formed on the device from one record per site and step. Returns what the same call without sky returns."""
+        if sky is not None:
+            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series)
         if ideal is not None:
             return self._march_series_ideal(weather, n_sub, loads, ideal, report, trace, applied, series)
         if report is not None:
@@ -893,6 +975,48 @@ class HeatBatch:
         if report is not None:
             out["report"] = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
         return out
+
+    def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series):
+        if report is None and ideal is None and not (want_trace and want_applied):
+            raise ValueError("trace=False / applied=False need a report")
+        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
+        _series_arrays_fit(keep, self.n_surfaces)
+        for k in ("zone_a0", "zone_b0"):
+            if k in keep and keep[k].shape[1] != self.n_zones:
+                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
+        sky = dict(sky)
+        if sky.get("normals") is None:
+            sky["normals"] = self._normals
+        k, kkeep = make_sky(**sky)
+        _sky_fits(kkeep, s.n_steps, self.n_sites, self.n_surfaces)
+        l, lkeep = make_zone_loads(**(loads or {}))
+        il, ikeep = make_ideal_loads(**(ideal or {}))
+        r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **(report or {}))
+        trace = np.zeros((s.n_steps if want_trace else 0, s.n_probes))
+        applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
+        ideal_q = np.zeros((s.n_steps, il.n_loads))
+        failed = C.c_int32(-1)
+        rc = self._L.heat_batch_march_series_sky(self._h, C.byref(s), C.byref(k), C.byref(l) if loads is not None else None,
+                                                 C.byref(il) if ideal is not None else None,
+                                                 C.byref(r) if report is not None else None,
+                                                 trace.ctypes.data_as(_dp) if trace.size else None,
+                                                 applied.ctypes.data_as(_dp) if applied.size else None,
+                                                 ideal_q.ctypes.data_as(_dp) if ideal_q.size else None, C.byref(failed))
+        if rc != 0:
+            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
+            e.failed_step, e.trace = int(failed.value), trace
+            raise e
+        modes = lkeep.get("th_mode", np.zeros(0, np.uint8))
+        rep = {k_: v for k_, v in rkeep.items() if not k_.startswith("group_") or k_ == "group_trace"}
+        if ideal is not None:
+            out = dict(trace=trace, failed_step=int(failed.value), ideal_q=ideal_q, ideal={k_: ikeep[k_] for k_ in IDEAL_STATS if k_ in ikeep})
+            if loads is not None:
+                out.update(applied=applied, modes=modes)
+            if report is not None:
+                out["report"] = rep
+            return out
+        out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
+        return out + ((rep,) if report is not None else ())
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -1045,6 +1045,15 @@ struct IdealDev {
     DevBuf<int64_t> i64[4];  // step_peak_heating, step_peak_cooling, n_sat_heating, n_sat_cooling
 };
 
+// The device copies of the sky of a series (heat_sky): the mode bytes and normals in device surface order, the record table
+// as given. Declared before the SeriesDrain of the call, as ReportDev is.
+struct SkyDev {
+    DevBuf<uint8_t> mode;      // [S]
+    DevBuf<double> normal;     // [3][S]
+    DevBuf<SkyRecord> record;  // [n_steps][n_sites]
+};
+static_assert(sizeof(SkyRecord) == sizeof(heat_sky_record) && sizeof(heat_sky_record) == 64, "SkyRecord mirrors heat_sky_record");
+
 template <typename T>
 int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
     const hipError_t e = buf.alloc(count);
@@ -2027,10 +2036,10 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 
 // heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
-// il == nullptr, or no ideal load, is the series without them: the same launches.
+// il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
                              double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
-                             double *ideal_q = nullptr) {
+                             double *ideal_q = nullptr, const heat_sky *sky = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2053,6 +2062,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     rc = check_ideal_loads(b->n_zones, s->n_channels, il, heat::last_error(), &load_of_zone);
     if (rc) return rc;
     const int64_t NI = il ? il->n_loads : 0;
+    unsigned sky_bits = 0;
+    rc = check_sky(b->n_surf, s, sky, heat::last_error(), &sky_bits);
+    if (rc) return rc;
     if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
@@ -2120,6 +2132,31 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
                     h_face[S + d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], (int)b->h_node_count[q] - 1);
                 }
             });
+        }
+    }
+    // sky: mode bytes and normals per DEVICE surface; the gain arrays of the inputs it drives, where the channels have not
+    // brought them along already
+    std::vector<uint8_t> h_sky_mode;
+    std::vector<double> h_sky_normal;
+    if (sky_bits) {
+        const int64_t *orig_of = b->h_orig_of.data();
+        h_sky_mode.resize((size_t)S);
+        h_sky_normal.resize(3 * (size_t)S);
+        b->pool->run(S, [&](int64_t d0, int64_t d1) {
+            for (int64_t d = d0; d < d1; d++) {
+                const int64_t q = orig_of[d];
+                const bool on = sky->mode[q] != 0;  // (the normals of the other surfaces are not read, not even here)
+                h_sky_mode[d] = sky->mode[q];
+                h_sky_normal[d] = on ? sky->normal_x[q] : 0.0;
+                h_sky_normal[S + d] = on ? sky->normal_y[q] : 0.0;
+                h_sky_normal[2 * S + d] = on ? sky->normal_z[q] : 0.0;
+            }
+        });
+        for (int a = 0; a < 4; a++) {
+            if (!(sky_bits >> a & 1) || !gain[a] || !h_gain[a].empty()) continue;
+            h_gain[a].resize((size_t)S);
+            double *gd = h_gain[a].data();
+            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
         }
     }
     // probes: (buffer, index) of every probed slot
@@ -2190,6 +2227,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     DevBuf<int> d_fail;
     ReportDev rd;
     IdealDev idd;
+    SkyDev skd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2324,6 +2362,17 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         ild.step_peak_heating = idd.i64[0].p, ild.step_peak_cooling = idd.i64[1].p;
         ild.n_sat_heating = idd.i64[2].p, ild.n_sat_cooling = idd.i64[3].p;
     }
+    SeriesSky skyd{};
+    if (sky_bits) {
+        if ((rc = series_upload(skd.mode, h_sky_mode.data(), h_sky_mode.size(), "sky modes"))) return rc;
+        if ((rc = series_upload(skd.normal, h_sky_normal.data(), h_sky_normal.size(), "sky normals"))) return rc;
+        if ((rc = series_upload(skd.record, reinterpret_cast<const SkyRecord *>(sky->record), (size_t)n_steps * n_sites, "sky records")))
+            return rc;
+        skyd.mode = skd.mode.p;
+        skyd.normal = skd.normal.p;
+        skyd.site = b->n_sites > 1 ? b->d_site.p : nullptr;
+        for (int a = 0; a < 4; a++) skyd.gain[a] = d_gain[a].p;
+    }
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
 
     SeriesInputs in{};
@@ -2351,7 +2400,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> the body of a march call of n_sub -> probes ----
+    // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> sky -> the body of a march call of n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
                            d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
@@ -2362,6 +2411,8 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
+        if (sky_bits)
+            launch_series_sky((int)S, skd.record.p + (size_t)k * n_sites, skyd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         if (NI > 0) {
             launch_series_ideal_begin(ild, d_channel.p + (size_t)k * NC, b->stream);
             rc = march_body_ideal(b, n_sub, ild);
@@ -2441,6 +2492,11 @@ int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const he
 int heat_batch_march_series_ideal(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_ideal_loads *il,
                                   heat_series_report *r, double *trace, double *applied, double *ideal_q, int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q);
+}
+
+int heat_batch_march_series_sky(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_zone_loads *l, heat_ideal_loads *il,
+                                heat_series_report *r, double *trace, double *applied, double *ideal_q, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

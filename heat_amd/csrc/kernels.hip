@@ -2327,6 +2327,55 @@ k_series_zone_loads(int n_zones, ZoneLoadsDev zl, const double *__restrict__ row
     if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
 }
 
+// k_series_sky — the sky-driven inputs of one step (heat_sky, include/heat_amd.h), behind k_series_inputs and before the
+// body: one lane per device surface. A lane whose mode byte is 0 leaves after reading it; the others read their site's
+// 64-byte record of the step (the planner keeps the surfaces of a site together: a wavefront mostly reads one line) and
+// their normal, and form the incident irradiance of the sides asked for by the header's rule — every product and sum one
+// rounded operation in the order written, hence no contraction: the host applying the same rule (heat_amd/sky.py) between
+// march calls reproduces the bits. From the raw value on it is the tail of series_side, restated: the mirror, the shared
+// clamps and long-wave conversion, one 16-byte store when both fields of a side are sky-driven, else 8 bytes. An input has
+// one source (check_sky): a field k_series_inputs has written is not written here.
+__device__ __forceinline__ void sky_side(int side, int d, int S, bool m_solar, bool m_ir, double nx, double ny, double nz,
+                                         const SkyRecord &r, const SeriesSky &sky, const double *__restrict__ side_alpha,
+                                         SideDyn *__restrict__ dyn, const SlotArrays &sl, double *__restrict__ mirror) {
+#pragma clang fp contract(off)
+    if (!(m_solar || m_ir)) return;
+    const int64_t rec = (int64_t)side * S + d;
+    const double fs = 0.5 + 0.5 * nz, fg = 0.5 - 0.5 * nz;
+    double solar = 0.0, rad_t = 0.0;
+    if (m_solar) {
+        const double c = (nx * r.sun_x + ny * r.sun_y) + nz * r.sun_z;
+        const double bm = c > 0.0 ? r.beam * c : 0.0;
+        double v = (bm + r.diffuse * fs) + r.ground * fg;
+        if (sky.gain[side]) v = v * sky.gain[side][d];
+        if (mirror != nullptr) mirror[(side ? sl.solar_b : sl.solar_f)[d]] = v;
+        solar = (side ? clamp_solar_back(v) : clamp_solar_front(v)) * side_alpha[rec];
+    }
+    if (m_ir) {
+        double v = r.ir_sky * fs + r.ir_ground * fg;
+        if (sky.gain[2 + side]) v = v * sky.gain[2 + side][d];
+        if (mirror != nullptr) mirror[(side ? sl.ir_b : sl.ir_f)[d]] = v;
+        rad_t = ir_to_rad_temperature(v);
+    }
+    if (m_solar && m_ir) reinterpret_cast<double2 *>(dyn)[rec] = make_double2(solar, rad_t);
+    else if (m_solar) dyn[rec].solar = solar;
+    else dyn[rec].rad_t = rad_t;
+}
+
+__global__ void __launch_bounds__(256)
+k_series_sky(int n_surf, const SkyRecord *__restrict__ records, SeriesSky sky, const double *__restrict__ side_alpha,
+             SideDyn *__restrict__ dyn, SlotArrays sl, double *__restrict__ mirror) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    const int S = n_surf;
+    if (d >= S) return;
+    const int m = sky.mode[d];
+    if (m == 0) return;  // nothing of this surface comes from the sky
+    const SkyRecord r = records[sky.site ? sky.site[d] : 0];
+    const double nx = sky.normal[d], ny = sky.normal[(int64_t)S + d], nz = sky.normal[2 * (int64_t)S + d];
+    sky_side(0, d, S, m & 1, m & 4, nx, ny, nz, r, sky, side_alpha, dyn, sl, mirror);
+    sky_side(1, d, S, m & 2, m & 8, -nx, -ny, -nz, r, sky, side_alpha, dyn, sl, mirror);
+}
+
 // Report of a series (heat_series_report, include/heat_amd.h): on the step's tail, beside k_series_probe. Everything below
 // is written without contraction: the statistics are DEFINED as one rounded operation per rule, and a group's bits are to
 // follow from its tables alone.
@@ -2818,6 +2867,12 @@ void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in,
                           SideDyn *dyn, const SlotArrays &sl, double *mirror, hipStream_t st) {
     if (n_surf <= 0) return;
     hipLaunchKernelGGL(k_series_inputs, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, row, in, T, side_alpha, dyn, sl, mirror);
+}
+
+void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
+                       const SlotArrays &sl, double *mirror, hipStream_t st) {
+    if (n_surf <= 0) return;
+    hipLaunchKernelGGL(k_series_sky, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, records, sky, side_alpha, dyn, sl, mirror);
 }
 
 void launch_series_zone_loads(int n_zones, const ZoneLoadsDev &zl, const double *row, const double *zone_T, double *a0, double *b0,

@@ -78,6 +78,20 @@ struct SeriesInputs {
 };
 void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in, const double *T, const double *side_alpha,
                           SideDyn *dyn, const SlotArrays &sl, double *mirror, hipStream_t st);
+// Sky of a series step (heat_sky, include/heat_amd.h): launched behind launch_series_inputs and before the body, one lane per
+// device surface; only when some mode byte is set.
+struct alignas(16) SkyRecord {  // heat_sky_record
+    double sun_x, sun_y, sun_z, beam, diffuse, ground, ir_sky, ir_ground;
+};
+struct SeriesSky {
+    const uint8_t *mode;     // [S] in device surface order: bit 0 solar front, 1 solar back, 2 long-wave front, 3 long-wave back
+    const double *normal;    // [3][S]: x, y, z of the front face's outward normal
+    const int32_t *site;     // [S] (SideArrays::site); nullptr: site 0
+    const double *gain[4];   // the series' gain arrays (SeriesInputs::gain); nullptr: 1
+};
+// records: the step's row of the record table, [n_sites]
+void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
+                       const SlotArrays &sl, double *mirror, hipStream_t st);
 // Zone loads of a series step (heat_zone_loads, include/heat_amd.h; tables: plan.hpp, ZoneLoadTables): launched between the
 // step's head and its driven inputs, one lane per zone.
 struct ZoneLoadsDev {

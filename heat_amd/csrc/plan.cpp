@@ -1885,6 +1885,38 @@ int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_load
     return HEAT_OK;
 }
 
+// ---- sky of a series (include/heat_amd.h, heat_sky) ----
+int check_sky(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, std::string &err, unsigned *any_bits) {
+    if (any_bits) *any_bits = 0;
+    if (!sky) return HEAT_OK;
+    if (!sky->mode) return failp(err, HEAT_E_INVALID_ARG, "sky: mode is NULL (one byte per surface s, 0: the surface takes nothing from the sky)");
+    // (the mode bits number the inputs as the series does)
+    const int32_t *chan_of_bit[4] = {s->solar_front_chan, s->solar_back_chan, s->ir_front_chan, s->ir_back_chan};
+    static const char *const input_name[4] = {"solar front", "solar back", "long-wave front", "long-wave back"};
+    const double *normal[3] = {sky->normal_x, sky->normal_y, sky->normal_z};
+    unsigned any = 0;
+    for (int64_t q = 0; q < n_surfaces; q++) {
+        const unsigned m = sky->mode[q];
+        if (m > 15) return failp(err, HEAT_E_INVALID_ARG, "surface %lld: sky mode %u above 15 (bits 0-3)", (long long)q, m);
+        if (m == 0) continue;
+        any |= m;
+        for (int a = 0; a < 3; a++) {
+            if (!normal[a]) return failp(err, HEAT_E_INVALID_ARG, "surface %lld: sky mode %u, but normal_%c is NULL", (long long)q, m, "xyz"[a]);
+            if (!std::isfinite(normal[a][q]))
+                return failp(err, HEAT_E_INVALID_ARG, "surface %lld: sky mode %u, but normal_%c = %g is not finite", (long long)q, m, "xyz"[a],
+                             normal[a][q]);
+        }
+        if (!sky->record && s->n_steps > 0)
+            return failp(err, HEAT_E_INVALID_ARG, "surface %lld: sky mode %u, but record is NULL (n_steps %d)", (long long)q, m, s->n_steps);
+        for (int a = 0; a < 4; a++)
+            if ((m >> a & 1) && chan_of_bit[a] && chan_of_bit[a][q] >= 0)
+                return failp(err, HEAT_E_SIZE, "surface %lld: its %s input is driven by the sky (mode bit %d) and by channel %d: an input has one source",
+                             (long long)q, input_name[a], a, chan_of_bit[a][q]);
+    }
+    if (any_bits) *any_bits = any;
+    return HEAT_OK;
+}
+
 // ---- report of a series (include/heat_amd.h, heat_series_report) ----
 int check_series_report(SlotResolver &res, const heat_zone_loads *l, const heat_series_report *r, std::string &err,
                         std::vector<ResolvedSlot> *resolved) {
@@ -2119,6 +2151,12 @@ int heat_ideal_loads_check(const heat_batch_desc *desc, const heat_series *s, co
             return heat::failp(heat::last_error(), HEAT_E_SIZE, "ideal load %lld: the table gives its zone %d load %d", (long long)i, il->zone[i],
                                load_of_zone[(size_t)il->zone[i]]);
     return HEAT_OK;
+}
+
+int heat_sky_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky) {
+    int rc = heat_series_check(desc, n_sites, s);
+    if (rc) return rc;
+    return heat::check_sky(desc->n_surfaces, s, sky, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

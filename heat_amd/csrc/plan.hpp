@@ -172,6 +172,11 @@ void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadT
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone = nullptr);
 
+// Sky of a series (heat_sky, include/heat_amd.h). Everything heat_sky_check promises about the sky itself; sky == nullptr is
+// none. s has passed check_series. HEAT_OK or a negative heat_status with `err` set, naming "surface s".
+// any_bits (nullable): the OR of every mode byte — 0: the series launches nothing for the sky.
+int check_sky(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, std::string &err, unsigned *any_bits = nullptr);
+
 // Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
 // report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
 // heat_status with `err` set, naming "group g" or "group entry i".

@@ -497,6 +497,60 @@ int heat_batch_march_series_ideal(heat_batch *b, const heat_series *s, const hea
                                   double *trace /* [n_steps][n_probes], nullable */,
                                   double *applied /* [n_steps][n_thermostats], nullable */,
                                   double *ideal_q /* [n_steps][n_loads], nullable */, int32_t *failed_step);
+
+/*
+ * Sky of a series: the incident solar and long-wave irradiance of sky-facing sides, formed ON THE DEVICE at every step from
+ * one 64-byte record per site and step (the sun's direction, three short-wave and two long-wave irradiances) and the
+ * surface's normal, instead of one channel column per distinct (site, orientation) the caller computes in advance: with a
+ * random azimuth per wall that is one column per wall. The reference has no counterpart — solar geometry lives in another
+ * SIMPLE crate and its harness reads EnergyPlus' incident irradiance from CSV (validate_wall_heat_transfer.rs:675-705): the
+ * rule below is this library's own contract, defined — as the thermostat and the ideal load are — against the per-call loop
+ * with the same rule written on the host (heat_amd/sky.py, incident()).
+ * For a side whose mode bit is set, with n = the front normal (its component-wise negation for the back side) and r = the
+ * record of the surface's site at step k; every line is one rounded f64 operation in the order written, no fused
+ * multiply-add:
+ *   c   = (n.x * r.sun_x + n.y * r.sun_y) + n.z * r.sun_z
+ *   fs  = 0.5 + 0.5 * n.z          fg = 0.5 - 0.5 * n.z
+ *   solar:      bm = c > 0 ? r.beam * c : 0.0
+ *               v  = (bm + r.diffuse * fs) + r.ground * fg
+ *   long-wave:  v  = r.ir_sky * fs + r.ir_ground * fg
+ *   if the series carries the gain array of that input:  v = v * gain[s]
+ * From v on the value is the raw value of a driven input of the series: into the state mirror where the batch keeps one,
+ * through the clamps of surface.rs:916-923 and the side's absorptance factor or the long-wave conversion of
+ * surface.rs:647,692 (the same device functions), into the side's device record. A field that is neither sky-driven nor
+ * channel-driven is not written. The model is an isotropic sky with a ground view of 1 - fs; anisotropic skies, shading and
+ * sun-position formulas are the caller's (it supplies the sun vector, which keeps the rule free of transcendental functions:
+ * the host reproduces the bits). A NaN in a record is treated as a NaN channel value is. The sky has no memory: a series of k
+ * steps followed by one of n - k gives the bits of the series of n. n_sub == 0 still sets the inputs of every step.
+ * heat_sky_check (host-only) and heat_batch_march_series_sky run the same checks before any device work; every message names
+ * "surface s": a NULL mode, NULL normals while some mode byte is not 0, a NULL record while some mode byte is not 0 and
+ * n_steps > 0, a normal component that is not finite on a surface whose mode is not 0, a mode byte above 15 ->
+ * HEAT_E_INVALID_ARG; a mode bit on an input whose channel in the series is >= 0 (an input has one source) -> HEAT_E_SIZE.
+ * An ir_own_face bit on a sky-driven side is refused by the series (it needs a channel). Sharded batches are refused as by
+ * the series; weather sites are supported (n_sites is the batch's).
+ * heat_batch_march_series_sky with sky == NULL, or with every mode byte 0, is heat_batch_march_series_ideal exactly (same
+ * kernels, same bits).
+ */
+typedef struct heat_sky_record {   /* one site at one step; 64 bytes */
+    double sun_x, sun_y, sun_z;    /* vector towards the sun, in the axes of the surfaces' normals (z up) */
+    double beam;                   /* direct normal irradiance, W/m2 */
+    double diffuse;                /* diffuse horizontal irradiance, W/m2 */
+    double ground;                 /* short-wave irradiance leaving the ground (albedo x global horizontal), W/m2 */
+    double ir_sky;                 /* horizontal infrared irradiance from the sky, W/m2 */
+    double ir_ground;              /* long-wave irradiance leaving the ground, W/m2 */
+} heat_sky_record;
+
+typedef struct heat_sky {
+    const heat_sky_record *record;                 /* [n_steps][n_sites]: [k * n_sites + site] */
+    const double *normal_x, *normal_y, *normal_z;  /* [n_surfaces] outward normal of the FRONT face; the back face sees its negation */
+    const uint8_t *mode;                           /* [n_surfaces] bit 0 solar front, 1 solar back, 2 long-wave front, 3 long-wave back */
+} heat_sky;
+
+int heat_sky_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky); /* host-only */
+int heat_batch_march_series_sky(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                const heat_zone_loads *l /* nullable */, heat_ideal_loads *il /* nullable */,
+                                heat_series_report *r /* nullable */, double *trace, double *applied, double *ideal_q,
+                                int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -27,20 +27,27 @@ legs, alternated in the same way, one ideal load per zone, heating and cooling, 
   I  the same plus the ideal loads (same batch)
   D  leg D itself, on the batch as planned (cluster-resident)
 and writes profiles/series_ideal.json: ms per step of each, I - S per sub-timestep, I / S and I / D.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal]
+With --sky (heat_batch_march_series_sky; the model, channels, loads and probes of leg D) two legs, alternated in the same way:
+  C' every wall's front solar and front long-wave input driven from channels (64 columns shared by all walls: what a channel
+     table can hold; with a column per wall — what walls of their own azimuth need — the table is 16 S bytes per step)
+  K  the same two inputs of every wall formed on the device from the sky: every wall its own azimuth, one site, one 64-byte
+     record per step, the sun from heat_amd.sky.sun_direction (day 172, latitude 48 N, the steps spread over the day)
+and writes profiles/series_sky.json: ms per step of each, K / C', K - C'.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
-                                                     with --ideal leg I"""
+                                                     with --ideal leg I; with --sky a series of leg C' and one of leg K"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, modeldict as mdl
+from heat_amd import HeatBatch, modeldict as mdl, sky as skym
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL
+SKY = "--sky" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -82,6 +89,34 @@ if IDEAL:
         out = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads, ideal=ideal, **drives)
         dt = time.perf_counter() - t0
         assert out["failed_step"] == -1 and np.all(np.isfinite(out["ideal_q"])) and np.all(np.isfinite(out["trace"]))
+        return dt * 1e3 / steps
+if SKY:
+    FRONT = ("solar_front", "ir_front")
+    azimuth = rng.uniform(0.0, 2.0 * np.pi, S)
+    sun = skym.sun_direction(172, 24.0 * np.arange(STEPS) / STEPS, np.radians(48.0))
+    up = np.maximum(sun[:, 2], 0.0)
+    beam, diffuse = np.where(sun[:, 2] > 0.0, 800.0, 0.0), 60.0 + 140.0 * up
+    record = np.stack([sun[:, 0], sun[:, 1], sun[:, 2], beam, diffuse, 0.2 * (beam * up + diffuse), np.full(STEPS, 350.0),
+                       np.full(STEPS, 420.0)], axis=1)[:, None, :]
+    sky_args = dict(mode=np.full(S, 1 | 4, np.uint8), normals=(np.cos(azimuth), np.sin(azimuth), np.zeros(S)))
+    not_driven = np.full(S, -1, np.int32)
+
+    def leg_cp(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                       **{k: drives[k] for k in FRONT})
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace))
+        return dt * 1e3 / steps
+
+    def leg_k(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                       sky=dict(sky_args, record=record[:steps]), **{k: (not_driven, drives[k][1]) for k in FRONT})
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace))
         return dt * 1e3 / steps
 if REPORT:
     # the envelope of zone z: both faces of the walls whose back faces it (uniform_massive: all of a zone's walls, contiguous)
@@ -215,6 +250,32 @@ with HeatBatch(md) as b:
                   "(%.1f us per sub-timestep), I / S = %.3f, I / D = %.3f (%d steps, median of %d rounds)" % (
                       n_sub, Sm, Im, Dm, Im - Sm, (Im - Sm) * 1e3 / n_sub, Im / Sm, Im / Dm, STEPS, ROUNDS), flush=True)
             continue
+        if SKY:
+            leg_cp(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_k(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series of each: C' channels %.3f ms per step, K sky %.3f" % (leg_cp(b, w, n_sub, STEPS), leg_k(b, w, n_sub, STEPS)))
+                continue
+            c, k, c1, k1 = [], [], [], []
+            for r in range(ROUNDS):
+                c.append(leg_cp(b, w, n_sub, STEPS))
+                k.append(leg_k(b, w, n_sub, STEPS))
+                c1.append(leg_cp(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                k1.append(leg_k(b, w, n_sub, 1))
+            Cc, K, C1, K1 = float(np.median(c)), float(np.median(k)), float(np.median(c1)), float(np.median(k1))
+            Cs, Ks = (Cc * STEPS - C1) / (STEPS - 1), (K * STEPS - K1) / (STEPS - 1)  # per step once the call is set up
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                C_prime_channels_ms=Cc, K_sky_ms=K, K_over_C_prime=K / Cc, K_minus_C_prime_ms=K - Cc,
+                expectation_K_within_5_percent_of_C_prime=bool(K <= 1.05 * Cc),
+                C_prime_series_of_one_step_ms=C1, K_series_of_one_step_ms=K1, C_prime_without_setup_ms=Cs, K_without_setup_ms=Ks,
+                K_over_C_prime_without_setup=Ks / Cs,
+                table_bytes_per_step=dict(C_prime_as_measured=int(8 * channel.shape[1]), C_prime_with_a_column_per_wall_input=int(8 * 2 * S),
+                                          K_records=64),
+                all_rounds=dict(C_prime=c, K=k, C_prime_one_step=c1, K_one_step=k1))
+            print("n_sub %2d: C' channels %.3f ms/step, K sky %.3f -> K / C' = %.4f, K - C' = %+.3f ms; a series of one step: C' %.2f ms, "
+                  "K %.2f ms -> per step without the set-up C' %.3f, K %.3f, K / C' = %.4f (%d steps, median of %d rounds)" % (
+                      n_sub, Cc, K, K / Cc, K - Cc, C1, K1, Cs, Ks, Ks / Cs, STEPS, ROUNDS), flush=True)
+            continue
         if REPORT:
             if ONE:
                 leg = dict(zones=leg_f, nodes=leg_g)
@@ -298,7 +359,7 @@ if IDEAL:
     bs.close()
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_ideal.json" if IDEAL else
+                              "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
