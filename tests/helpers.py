@@ -119,3 +119,115 @@ def walls_example_model(n_walls=12):
     md["zone_volume"] = np.array([600.0, 250.0])
     state = mdl.layout_state(md)
     return md, state
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Sweeps over the edges of the side physics (tests/physics_ref.py; the host and the GPU tests share them)
+def _signed(vals):
+    out = []
+    for v in vals:
+        out.append(v)
+        if v != 0:
+            out.append(-v)
+    return out
+
+
+_DT_EXACT = [0.0, 1e-9, 4e-4, float(np.nextafter(1e-3, 0.0)), 1e-3, float(np.nextafter(1e-3, 1.0)), 2.2e-3]
+DT_EDGES = _signed(_DT_EXACT + [0.5, 7.0, 40.0])            # air - surface: the 1.31 branch and the MIN_H clamp straddled
+COS_EDGES = _signed([0.0, float(np.nextafter(1e-3, 0.0)), 1e-3, 0.5, 0.707, float(np.nextafter(0.98, 0.0)), 0.98, 1.0])
+GRID = 2.0 ** -26
+
+
+def on_grid(x):
+    """x rounded to the 2^-26 grid: sums and differences of such temperatures are exact in f64."""
+    return np.round(np.asarray(x, dtype=np.float64) / GRID) * GRID
+
+
+def is_exact_dt(dt):
+    """The temperature differences that are given exactly (a face at 0.0 or an air at 0.0)."""
+    return abs(dt) <= 2.2e-3
+
+
+def tarp_sweep():
+    """(air, surface, cos_tilt) triples: DT_EDGES x COS_EDGES; the small differences against a face at 0.0 and against
+    an air at 0.0 (both exact), the others on the grid around three face temperatures."""
+    rows = []
+    for d in DT_EDGES:
+        for c in COS_EDGES:
+            if is_exact_dt(d):
+                rows.append((d, 0.0, c))
+                rows.append((0.0, -d, c))
+            else:
+                for face in (-12.25, 3.0 + 5 * GRID, 31.5 - GRID):
+                    rows.append((face + d, face, c))
+    return np.array(rows)
+
+
+WIND_SWEEP = [(0.0, 0.0), (0.0, 3.5), (-0.0, 0.75), (2.0, 9.0), (4.4, 0.31), (5.9, 2.0)]   # (direction rad, speed m/s)
+NORMALS = [(1.0, 0.0), (-1.0, 0.0), (-0.0, 1.0), (0.0, -1.0), (0.6, 0.8), (-0.6, -0.8), (0.8, -0.6)]
+GEOMETRY = [(4.0, 8.0, 1.0), (37.5, 25.0, 0.45), (0.81, 3.6, 0.62), (120.0, 62.0, 0.0), (11.0, 13.5, 0.3)]  # area, perimeter, wind modifier
+
+CAVITY_THICKNESS = [0.006, 0.0127, 0.02, 0.03, 0.05, 0.1]
+CAVITY_DT = _signed([0.0, 5e-11, 1e-6, 0.3, 3.0, 15.0, 40.0])
+CAVITY_EMIS = [(0.84, 0.84), (0.1, 1.0), (0.3, 0.1), (1.0, 1.0), (0.84, 0.3), (1.0, 0.3), (0.1, 0.1)]   # (ein, eout)
+
+
+def cavity_angles():
+    rad = math.radians
+    a = [0.0, 1e-6, rad(30.0)]
+    for deg in (59.5, 60.5, 89.5, 90.5):
+        a += [rad(deg) - 1e-9, rad(deg) + 1e-9]
+    a += [rad(60.0), rad(73.0), rad(90.0), rad(134.0), rad(179.9)]
+    return a
+
+
+def cavity_exact_angles():
+    """The f64 value of every regime boundary expression of `nusselt` (gas.rs:198-215), and the angles whose flip
+    (180 deg - angle, gas.rs:137-139) lands on one: the branch taken there is part of the claim."""
+    import physics_ref as pr
+    out = []
+    for b in pr.REGIME_BOUNDS:
+        out += [b, pr.PI_RAD_180 - b]
+    return out
+
+
+def cavity_sweep(angles=None):
+    """Records (cavity, t_front, t_back): thickness x temperature difference x gas x angle, height 1, the emissivity
+    pairs taken in turn. The mean temperature wanders between 5 and 30 C on the grid."""
+    angles = cavity_angles() if angles is None else angles
+    cavs, tf, tb = [], [], []
+    i = 0
+    for th in CAVITY_THICKNESS:
+        for d in CAVITY_DT:
+            for gas in range(4):
+                for ang in angles:
+                    ein, eout = CAVITY_EMIS[i % len(CAVITY_EMIS)]
+                    base = float(on_grid(5.0 + 25.0 * ((i * 0.6180339887) % 1.0)))
+                    cavs.append((th, 1.0, ang, eout, ein, gas, 0))
+                    tf.append(base)
+                    tb.append(base - d if abs(d) < 1e-3 else float(on_grid(base - d)))
+                    i += 1
+    return np.array(cavs, dtype=mdl.CAVITY_DTYPE), np.array(tf), np.array(tb)
+
+
+def rel_distance(got, ref):
+    """|got - ref| / |ref| of an f64 against an extended-precision reference, as a float."""
+    ref = np.longdouble(ref)
+    return float(abs(np.longdouble(got) - ref) / abs(ref))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+def ambient_backs(md, state, rng, fraction):
+    """Turns the BACK side of a share of the surfaces to Boundary::AmbientTemperature, in place, across all three kinds
+    of front side; returns the indices of the converted surfaces. The conversion is tools/fuzz.py's `ambient_backs`
+    (the fuzzer draws it too; the suite's own tests import the fuzzer, and it has to load beside any tests/helpers.py
+    those tests come with, so it cannot take a name from here that older ones lack): see there for what it guarantees —
+    emissivities of 0.3 at least, faces more than 0.5 K apart, ambient temperatures from U(5, 30) more than 0.5 K off
+    the front face, the front side's air and the zone."""
+    import os
+    import sys
+    tools = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
+    import fuzz
+    return fuzz.ambient_backs(md, state, rng, fraction)

@@ -16,6 +16,7 @@ from heat_amd import HeatBatch, modeldict as mdl
 from oracle import oracle
 from test_parity_gpu import assert_state_close
 
+AMBIENT_BACKS = 0xa3b1   # (the seeds kept as tests draw no conversion with it: their cases stay what they were)
 
 
 def oracle_march(md, state, w, a0, b0):
@@ -71,6 +72,61 @@ def check(md, ref, got, gpu_iters, iters, oracle_again):
             if jump > 1e-9 * (1.0 + float(np.max(np.abs(ref[slots])))):
                 raise Discontinuity("oracle moves by %.3e K for a relative %.0e on its long-wave inputs (GPU vs oracle: %s)" % (jump, eps, str(e)[:120]))
         raise
+
+
+def ambient_backs(md, state, rng, fraction):
+    """Turns the BACK side of a share of the surfaces to Boundary::AmbientTemperature, in place, across all three kinds
+    of front side (a third of the converted surfaces keep their front, a third get a front facing their zone, a third a
+    front facing an ambient temperature of its own). Such a back side takes t_front for its radiant temperature and the
+    FRONT node for its surface temperature (surface.rs:672-686), so the conversion makes sure both show: emissivities of
+    0.3 at least, front and back faces more than 0.5 K apart, and the ambient temperature (drawn from U(5, 30)) more
+    than 0.5 K off the front face, off the front side's own air, and off the zone's temperature.
+    Returns the indices of the converted surfaces."""
+    S, Z = int(md["n_surfaces"]), int(md["n_zones"])
+    conv = np.flatnonzero(rng.random(S) < fraction)
+    if len(conv) == 0 and S:
+        conv = np.array([int(rng.integers(0, S))])
+    nc = len(conv)
+    for key in ("front_kind", "back_kind", "front_zone", "back_zone"):
+        md[key] = np.array(md[key], dtype=np.int32)
+    for key in ("front_ambient", "back_ambient", "front_emissivity", "back_emissivity"):
+        md[key] = np.array(md[key], dtype=np.float64)
+    front = rng.integers(0, 3, nc)
+    to_space = conv[(front == 1) & (Z > 0)]
+    to_amb = conv[front == 2]
+    md["front_kind"][to_space] = mdl.SPACE
+    md["front_zone"][to_space] = np.clip(md["front_zone"][to_space], 0, max(Z - 1, 0))
+    md["front_kind"][to_amb] = mdl.AMBIENT
+    md["front_ambient"][to_amb] = rng.uniform(5., 30., len(to_amb))
+    md["back_kind"][conv] = mdl.AMBIENT
+    md["front_emissivity"][conv] = np.maximum(md["front_emissivity"][conv], rng.uniform(0.3, 0.5, nc))
+    md["back_emissivity"][conv] = np.maximum(md["back_emissivity"][conv], rng.uniform(0.3, 0.5, nc))
+    first = np.asarray(md["first_node_slot"], dtype=np.int64)[conv]
+    last = first + np.diff(np.asarray(md["node_offset"], dtype=np.int64))[conv] - 1
+    # faces more than 0.5 K apart (a wall of one node has one face)
+    two = last > first
+    gap = rng.uniform(0.6, 3.0, nc) * rng.choice([-1.0, 1.0], nc)
+    close = two & (np.abs(state[last] - state[first]) <= 0.5)
+    state[last[close]] = state[first[close]] + gap[close]
+    # the front side's air (t_front): its zone, its ambient temperature; the outdoor air is the weather's
+    fk = md["front_kind"][conv]
+    zt = state[np.asarray(md["zone_slot"], dtype=np.int64)] if Z else np.zeros(1)
+    t_front = np.where(fk == mdl.SPACE, zt[np.clip(md["front_zone"][conv], 0, max(Z - 1, 0))],
+                       np.where(fk == mdl.AMBIENT, md["front_ambient"][conv], np.nan))
+    amb = rng.uniform(5., 30., nc)
+    for _ in range(50):
+        bad = (np.abs(amb - state[first]) <= 0.5) | (np.abs(amb - t_front) <= 0.5)
+        if not bad.any():
+            break
+        amb[bad] = rng.uniform(5., 30., int(bad.sum()))
+    md["back_ambient"][conv] = amb
+    # a front that faces its zone: the zone's temperature more than 0.5 K off the front face as well
+    sp = fk == mdl.SPACE
+    near = sp & (np.abs(t_front - state[first]) <= 0.5)
+    state[first[near]] = t_front[near] + gap[near]
+    close = two & (np.abs(state[last] - state[first]) <= 0.5)
+    state[last[close]] = state[first[close]] - gap[close]
+    return conv
 
 
 def make_case(seed):
@@ -154,6 +210,11 @@ def make_case(seed):
             md[key] = v
     if rng2.random() < 0.05:
         kw["force_general"] = True
+    # (later still) one case in ten: back sides that face an ambient temperature (surface.rs:672-686), all front kinds
+    rng4 = np.random.default_rng(seed ^ AMBIENT_BACKS)
+    if rng4.random() < 0.10:
+        ambient_backs(md, st, rng4, float(rng4.uniform(0.05, 0.5)))
+        name += " + ambient backs"
     cuts = sorted(set(int(c) for c in rng.integers(1, n_sub + 1, int(rng.integers(0, 4)))) | {n_sub})
     return md, st, name, w, a0, b0, kw, cuts
 
