@@ -117,6 +117,15 @@ class Sky(C.Structure):
                 ("mode", C.POINTER(C.c_uint8))]
 
 
+class SolarGains(C.Structure):
+    """heat_solar_gains (include/heat_amd.h): the apertures (windows seen from the sky) and the entries (shares of an
+    aperture's power that land on a receiving side) of the solar gains of a series"""
+    _fields_ = [("n_apertures", C.c_int64), ("ap_surface", _i64p), ("ap_normal_x", _dp), ("ap_normal_y", _dp), ("ap_normal_z", _dp),
+                ("ap_tau_coef", _dp), ("ap_tau_diffuse", _dp), ("ap_scale", _dp), ("ap_sum", _dp),
+                ("n_entries", C.c_int64), ("en_surface", _i64p), ("en_side", C.POINTER(C.c_uint8)), ("en_aperture", _i32p),
+                ("en_beam", _dp), ("en_diffuse", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -161,6 +170,9 @@ SYMBOLS = [
     ("heat_sky_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky)]),
     ("heat_batch_march_series_sky", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(ZoneLoads), C.POINTER(IdealLoads),
                                               C.POINTER(Report), _dp, _dp, _dp, _i32p]),
+    ("heat_solar_gains_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains)]),
+    ("heat_batch_march_series_gains", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains), C.POINTER(ZoneLoads),
+                                                C.POINTER(IdealLoads), C.POINTER(Report), _dp, _dp, _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -310,7 +322,7 @@ def make_desc(md):
 
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
-                     "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check",
+                     "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -761,6 +773,74 @@ def sky_check(md, sky, n_sites=1, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+_GAIN_ARRAYS = (("ap_surface", np.int64, "n_apertures"), ("ap_normal_x", np.float64, "n_apertures"),
+                ("ap_normal_y", np.float64, "n_apertures"), ("ap_normal_z", np.float64, "n_apertures"),
+                ("ap_tau_diffuse", np.float64, "n_apertures"), ("ap_scale", np.float64, "n_apertures"),
+                ("en_surface", np.int64, "n_entries"), ("en_side", np.uint8, "n_entries"), ("en_aperture", np.int32, "n_entries"),
+                ("en_beam", np.float64, "n_entries"), ("en_diffuse", np.float64, "n_entries"))
+
+
+def make_solar_gains(ap_surface=(), ap_normal=None, ap_tau_coef=None, ap_tau_diffuse=(), ap_scale=(), ap_sum=None,
+                     en_surface=(), en_side=(), en_aperture=(), en_beam=(), en_diffuse=()):
+    """Builds a heat_solar_gains. Returns (gains, keepalive); the march adds onto keepalive["ap_sum"] in place.
+    ap_surface      [n_apertures] the window's surface (its site's sky record is read)
+    ap_normal       (x, y, z), each [n_apertures]: the outward normal of the side that sees the sky
+    ap_tau_coef     [n_apertures, 6] beam transmittance as a polynomial in the cosine of incidence, constant term first
+    ap_tau_diffuse  [n_apertures] hemispherical transmittance;  ap_scale [n_apertures] m2
+    ap_sum          [n_apertures] what a previous series returned (it is copied), None: zeros
+    en_*            [n_entries] the receiver (surface, side 0 front / 1 back), its aperture, its shares in 1/m2"""
+    nx, ny, nz = ap_normal if ap_normal is not None else ((), (), ())
+    given = dict(ap_surface=ap_surface, ap_normal_x=nx, ap_normal_y=ny, ap_normal_z=nz, ap_tau_diffuse=ap_tau_diffuse, ap_scale=ap_scale,
+                 en_surface=en_surface, en_side=en_side, en_aperture=en_aperture, en_beam=en_beam, en_diffuse=en_diffuse)
+    g = SolarGains()
+    g.n_apertures, g.n_entries = len(np.asarray(ap_surface).reshape(-1)), len(np.asarray(en_surface).reshape(-1))
+    keep = {}
+    for name, dtype, count in _GAIN_ARRAYS:
+        a = np.ascontiguousarray(given[name], dtype=dtype).reshape(-1)
+        if a.shape != (getattr(g, count),):
+            raise ValueError("solar gains %s: %s for %s = %d" % (name, a.shape, count, getattr(g, count)))
+        keep[name] = a
+        setattr(g, name, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if a.size else None)
+    coef = np.ascontiguousarray(ap_tau_coef if ap_tau_coef is not None else np.zeros((0, 6)), dtype=np.float64)
+    if coef.shape != (g.n_apertures, 6):
+        raise ValueError("solar gains ap_tau_coef: %s for %d apertures of 6 coefficients" % (coef.shape, g.n_apertures))
+    keep["ap_tau_coef"] = coef
+    g.ap_tau_coef = coef.ctypes.data_as(_dp) if coef.size else None
+    total = np.zeros(g.n_apertures) if ap_sum is None else np.array(ap_sum, dtype=np.float64).reshape(-1)
+    if total.shape != (g.n_apertures,):
+        raise ValueError("solar gains ap_sum: %s for %d apertures" % (total.shape, g.n_apertures))
+    keep["ap_sum"] = total
+    g.ap_sum = total.ctypes.data_as(_dp) if total.size else None
+    return g, keep
+
+
+def _sky_for_gains(sky, normals, n_surfaces):
+    """The sky of a call with gains: the records are the gains' too; without mode bytes no side takes its input from the sky."""
+    sky = dict(sky or {})
+    sky.setdefault("record", None)
+    if sky.get("mode") is None:
+        sky["mode"] = np.zeros(n_surfaces, np.uint8)
+    if sky.get("normals") is None:
+        sky["normals"] = normals
+    return sky
+
+
+def solar_gains_check(md, gains, sky=None, n_sites=1, lib=None, **series):
+    """heat_solar_gains_check: everything about the solar gains of a series that needs no device (series arguments as
+    HeatBatch.march_series; sky: the arguments of make_sky, of which the gains need the records; gains: the arguments of
+    make_solar_gains, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    k, kkeep = make_sky(**_sky_for_gains(sky, _model_normals(md), int(md["n_surfaces"])))
+    _sky_fits(kkeep, s.n_steps, int(n_sites), int(md["n_surfaces"]))
+    g, gkeep = make_solar_gains(**gains) if gains is not None else (None, None)
+    rc = L.heat_solar_gains_check(C.byref(desc), int(n_sites), C.byref(s), C.byref(k), C.byref(g) if g is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -873,7 +953,8 @@ class HeatBatch:
     def synchronize(self):
         _check(self._L.heat_batch_synchronize(self._h))
 
-    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, **series):
+    def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
+                     **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -891,7 +972,14 @@ class HeatBatch:
         report.
         sky (a dict of make_sky's arguments: record [n_steps, n_sites, 8], mode, normals — default: the model's normal_x,
         normal_y, cos_tilt): heat_batch_march_series_sky — the solar and long-wave irradiance of the sides the mode bytes
-        name, formed on the device from one record per site and step. Returns what the same call without sky returns."""
+        name, formed on the device from one record per site and step. Returns what the same call without sky returns.
+        gains (a dict of make_solar_gains' arguments; sky carries the records, its mode may be left out):
+        heat_batch_march_series_gains — the solar radiation the apertures transmit, onto the receiving sides. Returns what the
+        same call without gains returns plus transmitted [n_steps, n_apertures] and ap_sum [n_apertures] (pass it as
+        gains["ap_sum"] to the next series): two more elements of the tuple, or two more keys of the dict."""
+        if gains is not None:
+            return self._march_series_sky(weather, n_sub, loads, ideal, report, _sky_for_gains(sky, self._normals, self.n_surfaces),
+                                          trace, applied, series, gains)
         if sky is not None:
             return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series)
         if ideal is not None:
@@ -976,7 +1064,7 @@ class HeatBatch:
             out["report"] = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
         return out
 
-    def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series):
+    def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None):
         if report is None and ideal is None and not (want_trace and want_applied):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -996,12 +1084,16 @@ class HeatBatch:
         applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
         ideal_q = np.zeros((s.n_steps, il.n_loads))
         failed = C.c_int32(-1)
-        rc = self._L.heat_batch_march_series_sky(self._h, C.byref(s), C.byref(k), C.byref(l) if loads is not None else None,
-                                                 C.byref(il) if ideal is not None else None,
-                                                 C.byref(r) if report is not None else None,
-                                                 trace.ctypes.data_as(_dp) if trace.size else None,
-                                                 applied.ctypes.data_as(_dp) if applied.size else None,
-                                                 ideal_q.ctypes.data_as(_dp) if ideal_q.size else None, C.byref(failed))
+        args = (C.byref(l) if loads is not None else None, C.byref(il) if ideal is not None else None,
+                C.byref(r) if report is not None else None, trace.ctypes.data_as(_dp) if trace.size else None,
+                applied.ctypes.data_as(_dp) if applied.size else None, ideal_q.ctypes.data_as(_dp) if ideal_q.size else None)
+        if gains is not None:
+            g, gkeep = make_solar_gains(**gains)
+            transmitted = np.zeros((s.n_steps, g.n_apertures))
+            rc = self._L.heat_batch_march_series_gains(self._h, C.byref(s), C.byref(k), C.byref(g), *args,
+                                                       transmitted.ctypes.data_as(_dp) if transmitted.size else None, C.byref(failed))
+        else:
+            rc = self._L.heat_batch_march_series_sky(self._h, C.byref(s), C.byref(k), *args, C.byref(failed))
         if rc != 0:
             e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
             e.failed_step, e.trace = int(failed.value), trace
@@ -1014,9 +1106,12 @@ class HeatBatch:
                 out.update(applied=applied, modes=modes)
             if report is not None:
                 out["report"] = rep
+            if gains is not None:
+                out.update(transmitted=transmitted, ap_sum=gkeep["ap_sum"])
             return out
         out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
-        return out + ((rep,) if report is not None else ())
+        out = out + ((rep,) if report is not None else ())
+        return out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -1054,6 +1054,20 @@ struct SkyDev {
 };
 static_assert(sizeof(SkyRecord) == sizeof(heat_sky_record) && sizeof(heat_sky_record) == 64, "SkyRecord mirrors heat_sky_record");
 
+// The device copies of the solar gains of a series (heat_solar_gains): the aperture tables, the sliced-ELL entry tables
+// (plan.hpp, SolarGainTables), the step's (Pb, Pd), ap_sum and the transmitted rows. Declared beside SkyDev.
+struct GainsDev {
+    DevBuf<int32_t> ap_dev;       // [NA]
+    DevBuf<double> ap_f64;        // normal [3][NA] | coef [6][NA] | tau_diffuse [NA] | scale [NA]
+    DevBuf<double2> power;        // [NA]
+    DevBuf<double> sum;           // [NA]
+    DevBuf<double> transmitted;   // [n_steps][NA]
+    DevBuf<uint32_t> rec;
+    DevBuf<int64_t> slice_off;
+    DevBuf<int32_t> ap;
+    DevBuf<double> share;
+};
+
 template <typename T>
 int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
     const hipError_t e = buf.alloc(count);
@@ -2036,10 +2050,12 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 
 // heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
-// il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit.
+// il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit,
+// and gains == nullptr, or neither an aperture nor an entry.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
                              double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
-                             double *ideal_q = nullptr, const heat_sky *sky = nullptr) {
+                             double *ideal_q = nullptr, const heat_sky *sky = nullptr, const heat_solar_gains *gains = nullptr,
+                             double *transmitted = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2066,6 +2082,10 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     rc = check_sky(b->n_surf, s, sky, heat::last_error(), &sky_bits);
     if (rc) return rc;
     if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
+    // (behind the shard's refusal: the gains number the surfaces of the caller's model, a shard holds some of them)
+    rc = check_solar_gains(b->n_surf, s, sky, gains, heat::last_error());
+    if (rc) return rc;
+    const int64_t NA = gains ? gains->n_apertures : 0;  // (entries need an aperture: there are none without)
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
@@ -2159,6 +2179,34 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
         }
     }
+    // solar gains: the apertures as structure of arrays, the entries as sliced ELL over the receivers in device record order;
+    // the solar gain arrays of the sides that receive, where neither the channels nor the sky have brought them along
+    std::vector<int32_t> h_ap_dev;
+    std::vector<double> h_ap_f64;
+    SolarGainTables gnt;
+    if (NA > 0) {
+        h_ap_dev.resize((size_t)NA);
+        h_ap_f64.resize(11 * (size_t)NA);
+        for (int64_t a = 0; a < NA; a++) {
+            h_ap_dev[a] = b->h_dev_of[gains->ap_surface[a]];
+            h_ap_f64[a] = gains->ap_normal_x[a];
+            h_ap_f64[NA + a] = gains->ap_normal_y[a];
+            h_ap_f64[2 * NA + a] = gains->ap_normal_z[a];
+            for (int j = 0; j < 6; j++) h_ap_f64[(3 + j) * NA + a] = gains->ap_tau_coef[6 * a + j];
+            h_ap_f64[9 * NA + a] = gains->ap_tau_diffuse[a];
+            h_ap_f64[10 * NA + a] = gains->ap_scale[a];
+        }
+        build_solar_gain_tables(S, b->h_dev_of.data(), gains, gnt);
+        bool receives[2] = {false, false};
+        for (uint32_t rec : gnt.rec) receives[rec >= (uint64_t)S] = true;
+        const int64_t *orig_of = b->h_orig_of.data();
+        for (int a = 0; a < 2; a++) {
+            if (!receives[a] || !gain[a] || !h_gain[a].empty()) continue;
+            h_gain[a].resize((size_t)S);
+            double *gd = h_gain[a].data();
+            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
+        }
+    }
     // probes: (buffer, index) of every probed slot
     std::vector<uint8_t> h_pbuf((size_t)P);
     std::vector<uint32_t> h_pidx((size_t)P);
@@ -2228,6 +2276,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     ReportDev rd;
     IdealDev idd;
     SkyDev skd;
+    GainsDev gnd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2363,15 +2412,40 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         ild.n_sat_heating = idd.i64[2].p, ild.n_sat_cooling = idd.i64[3].p;
     }
     SeriesSky skyd{};
+    if (sky_bits || NA > 0)
+        if ((rc = series_upload(skd.record, reinterpret_cast<const SkyRecord *>(sky->record), (size_t)n_steps * n_sites, "sky records")))
+            return rc;
     if (sky_bits) {
         if ((rc = series_upload(skd.mode, h_sky_mode.data(), h_sky_mode.size(), "sky modes"))) return rc;
         if ((rc = series_upload(skd.normal, h_sky_normal.data(), h_sky_normal.size(), "sky normals"))) return rc;
-        if ((rc = series_upload(skd.record, reinterpret_cast<const SkyRecord *>(sky->record), (size_t)n_steps * n_sites, "sky records")))
-            return rc;
         skyd.mode = skd.mode.p;
         skyd.normal = skd.normal.p;
         skyd.site = b->n_sites > 1 ? b->d_site.p : nullptr;
         for (int a = 0; a < 4; a++) skyd.gain[a] = d_gain[a].p;
+    }
+    SeriesApertures apd{};
+    SeriesGains gnsd{};
+    if (NA > 0) {
+        if ((rc = series_upload(gnd.ap_dev, h_ap_dev.data(), h_ap_dev.size(), "aperture tables"))) return rc;
+        if ((rc = series_upload(gnd.ap_f64, h_ap_f64.data(), h_ap_f64.size(), "aperture tables"))) return rc;
+        if ((rc = series_alloc(gnd.power, (size_t)NA, "aperture powers"))) return rc;
+        if ((rc = report_array(gnd.sum, gains->ap_sum, (size_t)NA, true, "aperture sums"))) return rc;
+        if (transmitted && (rc = series_alloc(gnd.transmitted, (size_t)n_steps * NA, "transmitted powers"))) return rc;
+        if ((rc = series_upload(gnd.rec, gnt.rec.data(), gnt.rec.size(), "solar gain tables"))) return rc;
+        if ((rc = series_upload(gnd.slice_off, gnt.slice_off.data(), gnt.rec.empty() ? 0 : gnt.slice_off.size(), "solar gain tables"))) return rc;
+        if ((rc = series_upload(gnd.ap, gnt.ap.data(), gnt.ap.size(), "solar gain tables"))) return rc;
+        if ((rc = series_upload(gnd.share, gnt.share.data(), gnt.share.size(), "solar gain tables"))) return rc;
+        apd.n = (int)NA;
+        apd.dev = gnd.ap_dev.p;
+        apd.site = b->n_sites > 1 ? b->d_site.p : nullptr;
+        apd.normal = gnd.ap_f64.p, apd.coef = gnd.ap_f64.p + 3 * NA, apd.tau_scale = gnd.ap_f64.p + 9 * NA;
+        apd.power = gnd.power.p;
+        apd.sum = gnd.sum.p;
+        gnsd.n_receivers = (int)gnt.rec.size();
+        gnsd.rec = gnd.rec.p, gnsd.slice_off = gnd.slice_off.p, gnsd.ap = gnd.ap.p;
+        gnsd.share = reinterpret_cast<const double2 *>(gnd.share.p);
+        gnsd.power = gnd.power.p;
+        gnsd.gain[0] = d_gain[0].p, gnsd.gain[1] = d_gain[1].p;
     }
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
 
@@ -2400,7 +2474,8 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> sky -> the body of a march call of n_sub -> probes ----
+    // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> sky -> solar gains -> the body of a march call of
+    // n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
                            d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
@@ -2413,6 +2488,11 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
                                  b->stream);
         if (sky_bits)
             launch_series_sky((int)S, skd.record.p + (size_t)k * n_sites, skyd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+        if (NA > 0) {
+            launch_series_apertures(skd.record.p + (size_t)k * n_sites, apd, gnd.transmitted.p ? gnd.transmitted.p + (size_t)k * NA : nullptr,
+                                    b->stream);
+            launch_series_solar_gains((int)S, gnsd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+        }
         if (NI > 0) {
             launch_series_ideal_begin(ild, d_channel.p + (size_t)k * NC, b->stream);
             rc = march_body_ideal(b, n_sub, ild);
@@ -2464,6 +2544,11 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         for (int a = 0; a < 4; a++)
             if (idd.i64[a].p) HIP_TRY(hipMemcpyAsync(i64[a], idd.i64[a].p, (size_t)NI * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     }
+    if (NA > 0) {
+        if (gnd.transmitted.p)
+            HIP_TRY(hipMemcpyAsync(transmitted, gnd.transmitted.p, (size_t)n_steps * NA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (gnd.sum.p) HIP_TRY(hipMemcpyAsync(gains->ap_sum, gnd.sum.p, (size_t)NA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2497,6 +2582,12 @@ int heat_batch_march_series_ideal(heat_batch *b, const heat_series *s, const hea
 int heat_batch_march_series_sky(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_zone_loads *l, heat_ideal_loads *il,
                                 heat_series_report *r, double *trace, double *applied, double *ideal_q, int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky);
+}
+
+int heat_batch_march_series_gains(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_solar_gains *gains,
+                                  const heat_zone_loads *l, heat_ideal_loads *il, heat_series_report *r, double *trace, double *applied,
+                                  double *ideal_q, double *transmitted, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

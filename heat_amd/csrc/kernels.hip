@@ -2376,6 +2376,72 @@ k_series_sky(int n_surf, const SkyRecord *__restrict__ records, SeriesSky sky, c
     sky_side(1, d, S, m & 2, m & 8, -nx, -ny, -nz, r, sky, side_alpha, dyn, sl, mirror);
 }
 
+// k_series_apertures — the power every window transmits in one step (heat_solar_gains, include/heat_amd.h), behind
+// k_series_sky: one lane per aperture. A lane reads its site's 64-byte record, its normal, six coefficients, the
+// hemispherical transmittance and the scale (structure of arrays: a wavefront reads lines), and applies the header's rule —
+// every product and sum one rounded operation in the order written, hence no contraction. (Pb, Pd) leave as one 16-byte
+// store for k_series_solar_gains; P goes into the step's row of `transmitted` where the caller takes one, and onto ap_sum.
+__global__ void __launch_bounds__(256)
+k_series_apertures(const SkyRecord *__restrict__ records, SeriesApertures ap, double *__restrict__ transmitted) {
+#pragma clang fp contract(off)
+    const int a = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = ap.n;
+    if (a >= ap.n) return;
+    const int d = ap.dev[a];
+    const SkyRecord r = records[ap.site ? ap.site[d] : 0];
+    const double nx = ap.normal[a], ny = ap.normal[n + a], nz = ap.normal[2 * n + a];
+    const double c = (nx * r.sun_x + ny * r.sun_y) + nz * r.sun_z;
+    const double fs = 0.5 + 0.5 * nz, fg = 0.5 - 0.5 * nz;
+    double t = ap.coef[5 * n + a];
+#pragma unroll
+    for (int j = 4; j >= 0; j--) {
+        t = t * c;
+        t = t + ap.coef[j * n + a];
+    }
+    const double tau_diffuse = ap.tau_scale[a], scale = ap.tau_scale[n + a];
+    const double ib = r.beam * c;
+    const double pb = c > 0.0 ? (ib * t) * scale : 0.0;
+    const double id = r.diffuse * fs + r.ground * fg;
+    const double pd = (id * tau_diffuse) * scale;
+    const double p = pb + pd;
+    ap.power[a] = make_double2(pb, pd);
+    if (transmitted != nullptr) transmitted[a] = p;
+    if (ap.sum != nullptr) ap.sum[a] = ap.sum[a] + p;
+}
+
+// k_series_solar_gains — what the inside faces receive from the windows in one step, behind k_series_apertures and before
+// the body: one lane per receiver (a side that has entries), 64 consecutive receivers a slice of the sliced-ELL tables
+// (plan.hpp, SolarGainTables). In row i of its slice a wavefront reads 64 neighbouring aperture numbers and 64 neighbouring
+// 16-byte share pairs, and gathers (Pb, Pd) of those apertures with 16-byte loads; a lane's sum is its own sequential chain
+// in the caller's order — the layout does not enter the bits. From the raw value on it is the tail of sky_side for the
+// solar field, restated: the gain, the mirror, the shared clamp, the side's absorptance factor, an 8-byte store. The side's
+// long-wave field belongs to whoever drives it and is not touched.
+__global__ void __launch_bounds__(256)
+k_series_solar_gains(int n_surf, SeriesGains g, const double *__restrict__ side_alpha, SideDyn *__restrict__ dyn, SlotArrays sl,
+                     double *__restrict__ mirror) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= g.n_receivers) return;
+    const int lane = r & 63;
+    const int64_t off = g.slice_off[r >> 6], rows = (g.slice_off[(r >> 6) + 1] - off) >> 6;
+    double v = 0.0;
+    for (int64_t i = 0; i < rows; i++) {
+        const int64_t at = off + i * 64 + lane;
+        const int a = g.ap[at];
+        if (a < 0) continue;  // padding
+        const double2 sh = g.share[at], p = g.power[a];
+        v = v + sh.x * p.x;
+        v = v + sh.y * p.y;
+    }
+    const int64_t rec = g.rec[r];
+    const int side = rec >= n_surf;
+    const int d = (int)(rec - (int64_t)side * n_surf);
+    const double *const gain = side ? g.gain[1] : g.gain[0];
+    if (gain != nullptr) v = v * gain[d];
+    if (mirror != nullptr) mirror[(side ? sl.solar_b : sl.solar_f)[d]] = v;
+    dyn[rec].solar = (side ? clamp_solar_back(v) : clamp_solar_front(v)) * side_alpha[rec];
+}
+
 // Report of a series (heat_series_report, include/heat_amd.h): on the step's tail, beside k_series_probe. Everything below
 // is written without contraction: the statistics are DEFINED as one rounded operation per rule, and a group's bits are to
 // follow from its tables alone.
@@ -2873,6 +2939,17 @@ void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sk
                        const SlotArrays &sl, double *mirror, hipStream_t st) {
     if (n_surf <= 0) return;
     hipLaunchKernelGGL(k_series_sky, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, records, sky, side_alpha, dyn, sl, mirror);
+}
+
+void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st) {
+    if (ap.n <= 0) return;
+    hipLaunchKernelGGL(k_series_apertures, dim3((ap.n + 255) / 256), dim3(256), 0, st, records, ap, transmitted);
+}
+
+void launch_series_solar_gains(int n_surf, const SeriesGains &g, const double *side_alpha, SideDyn *dyn, const SlotArrays &sl,
+                               double *mirror, hipStream_t st) {
+    if (g.n_receivers <= 0) return;
+    hipLaunchKernelGGL(k_series_solar_gains, dim3((g.n_receivers + 255) / 256), dim3(256), 0, st, n_surf, g, side_alpha, dyn, sl, mirror);
 }
 
 void launch_series_zone_loads(int n_zones, const ZoneLoadsDev &zl, const double *row, const double *zone_T, double *a0, double *b0,

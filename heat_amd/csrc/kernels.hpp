@@ -92,6 +92,32 @@ struct SeriesSky {
 // records: the step's row of the record table, [n_sites]
 void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
                        const SlotArrays &sl, double *mirror, hipStream_t st);
+// Solar gains of a series step (heat_solar_gains, include/heat_amd.h; tables: plan.hpp, SolarGainTables): two launches
+// behind launch_series_sky and before the body, only when there are apertures — one lane per aperture, then (only when there
+// are entries) one lane per receiver.
+struct SeriesApertures {
+    int n;
+    const int32_t *dev;       // [n] the aperture's device surface (for its site)
+    const int32_t *site;      // [S] (SideArrays::site); nullptr: site 0
+    const double *normal;     // [3][n]
+    const double *coef;       // [6][n]: coefficient j of all apertures contiguous
+    const double *tau_scale;  // [2][n]: tau_diffuse, scale
+    double2 *power;           // [n] (Pb, Pd) of the step, W
+    double *sum;              // [n] ap_sum; nullptr: not kept
+};
+struct SeriesGains {
+    int n_receivers;
+    const uint32_t *rec;       // [n_receivers] side * S + device surface
+    const int64_t *slice_off;  // [n_slices + 1]
+    const int32_t *ap;         // sliced ELL, -1: padding
+    const double2 *share;      // (en_beam, en_diffuse) beside ap
+    const double2 *power;      // SeriesApertures::power
+    const double *gain[2];     // the series' solar gain arrays, front and back (SeriesInputs::gain); nullptr: 1
+};
+// records: the step's row of the record table, [n_sites]; transmitted: the step's row, [n], or nullptr
+void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st);
+void launch_series_solar_gains(int n_surf, const SeriesGains &g, const double *side_alpha, SideDyn *dyn, const SlotArrays &sl,
+                               double *mirror, hipStream_t st);
 // Zone loads of a series step (heat_zone_loads, include/heat_amd.h; tables: plan.hpp, ZoneLoadTables): launched between the
 // step's head and its driven inputs, one lane per zone.
 struct ZoneLoadsDev {

@@ -1917,6 +1917,158 @@ int check_sky(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, std
     return HEAT_OK;
 }
 
+// ---- solar gains of a series (include/heat_amd.h, heat_solar_gains) ----
+int check_solar_gains(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, std::string &err) {
+    if (!g) return HEAT_OK;
+    const int64_t NA = g->n_apertures, NE = g->n_entries;
+    if (NA < 0 || NE < 0)
+        return failp(err, HEAT_E_INVALID_ARG, "negative count in solar gains (n_apertures %lld, n_entries %lld): no aperture a, no entry i",
+                     (long long)NA, (long long)NE);
+    if (NA > INT32_MAX || NE > INT32_MAX)
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 in solar gains (n_apertures %lld, n_entries %lld): aperture a and entry i are 32-bit",
+                     (long long)NA, (long long)NE);
+    if (NA > 0) {
+        const void *need[7] = {g->ap_surface, g->ap_normal_x, g->ap_normal_y, g->ap_normal_z, g->ap_tau_coef, g->ap_tau_diffuse, g->ap_scale};
+        static const char *const name[7] = {"ap_surface", "ap_normal_x", "ap_normal_y", "ap_normal_z", "ap_tau_coef", "ap_tau_diffuse", "ap_scale"};
+        for (int a = 0; a < 7; a++)
+            if (!need[a]) return failp(err, HEAT_E_INVALID_ARG, "aperture 0: %s is NULL (n_apertures %lld)", name[a], (long long)NA);
+        if (s->n_steps > 0 && (!sky || !sky->record))
+            return failp(err, HEAT_E_INVALID_ARG, "aperture 0: its site's record is read, but %s is NULL (n_steps %d)", sky ? "sky->record" : "sky",
+                         s->n_steps);
+    }
+    if (NE > 0) {
+        const void *need[5] = {g->en_surface, g->en_side, g->en_aperture, g->en_beam, g->en_diffuse};
+        static const char *const name[5] = {"en_surface", "en_side", "en_aperture", "en_beam", "en_diffuse"};
+        for (int a = 0; a < 5; a++)
+            if (!need[a]) return failp(err, HEAT_E_INVALID_ARG, "entry 0: %s is NULL (n_entries %lld)", name[a], (long long)NE);
+    }
+    for (int64_t a = 0; a < NA; a++) {
+        if (g->ap_surface[a] < 0 || g->ap_surface[a] >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "aperture %lld: surface %lld outside [0, %lld)", (long long)a, (long long)g->ap_surface[a], (long long)n_surfaces);
+        const double v[5] = {g->ap_normal_x[a], g->ap_normal_y[a], g->ap_normal_z[a], g->ap_tau_diffuse[a], g->ap_scale[a]};
+        static const char *const name[5] = {"normal_x", "normal_y", "normal_z", "tau_diffuse", "scale"};
+        for (int j = 0; j < 5; j++)
+            if (!std::isfinite(v[j])) return failp(err, HEAT_E_INVALID_ARG, "aperture %lld: %s = %g is not finite", (long long)a, name[j], v[j]);
+        for (int j = 0; j < 6; j++)
+            if (!std::isfinite(g->ap_tau_coef[6 * a + j]))
+                return failp(err, HEAT_E_INVALID_ARG, "aperture %lld: tau_coef[%d] = %g is not finite", (long long)a, j, g->ap_tau_coef[6 * a + j]);
+    }
+    const int32_t *chan[2] = {s->solar_front_chan, s->solar_back_chan};
+    for (int64_t i = 0; i < NE; i++) {
+        const int64_t q = g->en_surface[i];
+        const unsigned side = g->en_side[i];
+        if (side > 1) return failp(err, HEAT_E_INVALID_ARG, "entry %lld: side %u above 1 (0 front, 1 back)", (long long)i, side);
+        if (!std::isfinite(g->en_beam[i]) || !std::isfinite(g->en_diffuse[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "entry %lld: shares beam = %g, diffuse = %g are not finite", (long long)i, g->en_beam[i],
+                         g->en_diffuse[i]);
+        if (q < 0 || q >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "entry %lld: surface %lld outside [0, %lld)", (long long)i, (long long)q, (long long)n_surfaces);
+        if (g->en_aperture[i] < 0 || g->en_aperture[i] >= NA)
+            return failp(err, HEAT_E_SIZE, "entry %lld: aperture %d outside [0, %lld)", (long long)i, g->en_aperture[i], (long long)NA);
+        if (chan[side] && chan[side][q] >= 0)
+            return failp(err, HEAT_E_SIZE, "entry %lld: the solar %s input of surface %lld is driven by channel %d already: an input has one source",
+                         (long long)i, side ? "back" : "front", (long long)q, chan[side][q]);
+        if (sky && sky->mode && (sky->mode[q] >> side & 1))
+            return failp(err, HEAT_E_SIZE, "entry %lld: the solar %s input of surface %lld is driven by the sky (mode bit %u) already: an input has one source",
+                         (long long)i, side ? "back" : "front", (long long)q, side);
+    }
+    return HEAT_OK;
+}
+
+static inline int64_t gain_key(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, int64_t i) {
+    const int64_t q = g->en_surface[i];
+    return (int64_t)g->en_side[i] * n_surfaces + (dev_of ? (int64_t)dev_of[q] : q);
+}
+
+void build_solar_gain_tables(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, SolarGainTables &t) {
+    t.rec.clear();
+    t.slice_off.assign(1, 0);
+    t.ap.clear();
+    t.share.clear();
+    const int64_t NE = g ? g->n_entries : 0;
+    if (NE <= 0) return;
+    // a counting sort by receiver: stable by construction — the caller's order survives inside a receiver
+    std::vector<int32_t> count(2 * (size_t)n_surfaces, 0);
+    for (int64_t i = 0; i < NE; i++) count[(size_t)gain_key(n_surfaces, dev_of, g, i)]++;
+    std::vector<int32_t> len;                 // entries of every receiver
+    std::vector<int32_t> &recv_of = count;    // (reused: key -> receiver)
+    for (size_t k = 0; k < 2 * (size_t)n_surfaces; k++) {
+        const int32_t c = count[k];
+        if (c > 0) {
+            recv_of[k] = (int32_t)t.rec.size();
+            t.rec.push_back((uint32_t)k);
+            len.push_back(c);
+        }
+    }
+    const size_t R = t.rec.size(), n_slices = (R + kGainSlice - 1) / kGainSlice;
+    for (size_t q = 0; q < n_slices; q++) {
+        int32_t rows = 0;
+        for (size_t r = q * kGainSlice; r < std::min(R, (q + 1) * kGainSlice); r++) rows = std::max(rows, len[r]);
+        t.slice_off.push_back(t.slice_off.back() + (int64_t)rows * kGainSlice);
+    }
+    t.ap.assign((size_t)t.slice_off.back(), -1);
+    t.share.assign(2 * (size_t)t.slice_off.back(), 0.0);
+    std::vector<int32_t> &cursor = len;  // (reused: the next row of every receiver)
+    std::fill(cursor.begin(), cursor.end(), 0);
+    for (int64_t i = 0; i < NE; i++) {
+        const size_t r = (size_t)recv_of[(size_t)gain_key(n_surfaces, dev_of, g, i)];
+        const size_t at = (size_t)t.slice_off[r / kGainSlice] + (size_t)cursor[r]++ * kGainSlice + r % kGainSlice;
+        t.ap[at] = g->en_aperture[i];
+        t.share[2 * at] = g->en_beam[i];
+        t.share[2 * at + 1] = g->en_diffuse[i];
+    }
+}
+
+int check_solar_gain_tables(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, const SolarGainTables &t,
+                            std::string &err) {
+    const int64_t NE = g ? g->n_entries : 0;
+    const size_t R = t.rec.size(), n_slices = (R + kGainSlice - 1) / kGainSlice;
+    if (t.slice_off.size() != n_slices + 1 || t.slice_off[0] != 0)
+        return failp(err, HEAT_E_SIZE, "solar gain tables: %zu slice offsets for %zu receivers", t.slice_off.size(), R);
+    for (size_t q = 0; q < n_slices; q++)
+        if (t.slice_off[q + 1] < t.slice_off[q] || (t.slice_off[q + 1] - t.slice_off[q]) % kGainSlice != 0)
+            return failp(err, HEAT_E_SIZE, "solar gain tables: slice %zu runs from %lld to %lld", q, (long long)t.slice_off[q], (long long)t.slice_off[q + 1]);
+    if (t.ap.size() != (size_t)t.slice_off.back() || t.share.size() != 2 * t.ap.size())
+        return failp(err, HEAT_E_SIZE, "solar gain tables: %zu apertures and %zu shares for %lld elements", t.ap.size(), t.share.size(),
+                     (long long)t.slice_off.back());
+    for (size_t r = 0; r < R; r++)
+        if (t.rec[r] >= 2 * (uint64_t)n_surfaces || (r > 0 && t.rec[r] <= t.rec[r - 1]))
+            return failp(err, HEAT_E_SIZE, "solar gain tables: receiver %zu is record %u, not above the one before or outside the %lld sides", r,
+                         t.rec[r], (long long)(2 * n_surfaces));
+    // every entry of the caller's, in the caller's order, is the next row of its receiver's lane
+    std::vector<int32_t> cursor(R, 0);
+    for (int64_t i = 0; i < NE; i++) {
+        const uint32_t key = (uint32_t)gain_key(n_surfaces, dev_of, g, i);
+        const auto it = std::lower_bound(t.rec.begin(), t.rec.end(), key);
+        if (it == t.rec.end() || *it != key) return failp(err, HEAT_E_SIZE, "solar gain tables: entry %lld: its receiver is not in the tables", (long long)i);
+        const size_t r = (size_t)(it - t.rec.begin()), q = r / kGainSlice;
+        const int64_t rows = (t.slice_off[q + 1] - t.slice_off[q]) / kGainSlice;
+        if (cursor[r] >= rows) return failp(err, HEAT_E_SIZE, "solar gain tables: entry %lld: receiver %zu has no row %d", (long long)i, r, cursor[r]);
+        const size_t at = (size_t)t.slice_off[q] + (size_t)cursor[r]++ * kGainSlice + r % kGainSlice;
+        if (t.ap[at] != g->en_aperture[i] || std::memcmp(&t.share[2 * at], &g->en_beam[i], sizeof(double)) != 0 ||
+            std::memcmp(&t.share[2 * at + 1], &g->en_diffuse[i], sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "solar gain tables: entry %lld is not row %d of receiver %zu", (long long)i, cursor[r] - 1, r);
+    }
+    // ... and nothing else is: a receiver has an entry, the rest of every column is padding
+    int64_t n_used = 0;
+    for (size_t r = 0; r < R; r++) {
+        const size_t q = r / kGainSlice;
+        const int64_t rows = (t.slice_off[q + 1] - t.slice_off[q]) / kGainSlice;
+        if (cursor[r] < 1) return failp(err, HEAT_E_SIZE, "solar gain tables: receiver %zu has no entry", r);
+        for (int64_t i = cursor[r]; i < rows; i++)
+            if (t.ap[(size_t)t.slice_off[q] + (size_t)i * kGainSlice + r % kGainSlice] != -1)
+                return failp(err, HEAT_E_SIZE, "solar gain tables: receiver %zu: row %lld is neither an entry nor padding", r, (long long)i);
+        n_used += cursor[r];
+    }
+    for (size_t r = R; r < n_slices * kGainSlice; r++) {  // the lanes past the last receiver
+        const size_t q = r / kGainSlice;
+        for (int64_t at = t.slice_off[q] + (int64_t)(r % kGainSlice); at < t.slice_off[q + 1]; at += kGainSlice)
+            if (t.ap[(size_t)at] != -1) return failp(err, HEAT_E_SIZE, "solar gain tables: lane %zu past the last receiver holds an entry", r);
+    }
+    if (n_used != NE) return failp(err, HEAT_E_SIZE, "solar gain tables: %lld entries for %lld", (long long)n_used, (long long)NE);
+    return HEAT_OK;
+}
+
 // ---- report of a series (include/heat_amd.h, heat_series_report) ----
 int check_series_report(SlotResolver &res, const heat_zone_loads *l, const heat_series_report *r, std::string &err,
                         std::vector<ResolvedSlot> *resolved) {
@@ -2157,6 +2309,19 @@ int heat_sky_check(const heat_batch_desc *desc, int32_t n_sites, const heat_seri
     int rc = heat_series_check(desc, n_sites, s);
     if (rc) return rc;
     return heat::check_sky(desc->n_surfaces, s, sky, heat::last_error());
+}
+
+int heat_solar_gains_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                           const heat_solar_gains *gains) {
+    int rc = heat_sky_check(desc, n_sites, s, sky);
+    if (rc) return rc;
+    rc = heat::check_solar_gains(desc->n_surfaces, s, sky, gains, heat::last_error());
+    if (rc || !gains) return rc;
+    // ... and the tables the march would upload (this is the build the sanitizers see). Without a batch there is no device
+    // layout: the receivers stand in the caller's surface order.
+    heat::SolarGainTables t;
+    heat::build_solar_gain_tables(desc->n_surfaces, nullptr, gains, t);
+    return heat::check_solar_gain_tables(desc->n_surfaces, nullptr, gains, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

@@ -177,6 +177,29 @@ int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_load
 // any_bits (nullable): the OR of every mode byte — 0: the series launches nothing for the sky.
 int check_sky(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, std::string &err, unsigned *any_bits = nullptr);
 
+// Solar gains of a series (heat_solar_gains, include/heat_amd.h). Everything heat_solar_gains_check promises about the
+// gains themselves; g == nullptr is none. s has passed check_series and sky check_sky. HEAT_OK or a negative heat_status
+// with `err` set, naming "aperture a" or "entry i".
+int check_solar_gains(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, std::string &err);
+// The tables of k_series_solar_gains (one lane per receiver). The receivers are the sides that have entries, in device
+// record order (side * S + device surface); slice q holds receivers [64 q, 64 q + 64) and as many rows as its longest
+// receiver has entries, row i of all 64 lanes contiguous (sliced ELL): element slice_off[q] + 64 i + lane. A receiver's
+// entries stand in the caller's order; what is left of a lane's column is padding, aperture -1. The layout does not enter
+// the bits: a receiver's sum is one lane's sequential chain, whatever the slice width.
+constexpr int kGainSlice = 64;
+struct SolarGainTables {
+    std::vector<uint32_t> rec;       // [n_receivers] side * S + device surface, ascending
+    std::vector<int64_t> slice_off;  // [n_slices + 1] in elements, multiples of kGainSlice
+    std::vector<int32_t> ap;         // [slice_off.back()] aperture, -1: padding
+    std::vector<double> share;       // [slice_off.back()][2]: en_beam, en_diffuse (0 where padding)
+};
+// (of gains that passed check_solar_gains; dev_of: caller's surface -> device surface, nullptr: the caller's own order)
+void build_solar_gain_tables(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, SolarGainTables &t);
+// The tables against the caller's lists (used by the host-only check): every entry present exactly once, the caller's
+// order kept inside a receiver, every offset inside the buffers. HEAT_OK or HEAT_E_SIZE.
+int check_solar_gain_tables(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, const SolarGainTables &t,
+                            std::string &err);
+
 // Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
 // report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
 // heat_status with `err` set, naming "group g" or "group entry i".

@@ -551,6 +551,71 @@ int heat_batch_march_series_sky(heat_batch *b, const heat_series *s, const heat_
                                 const heat_zone_loads *l /* nullable */, heat_ideal_loads *il /* nullable */,
                                 heat_series_report *r /* nullable */, double *trace, double *applied, double *ideal_q,
                                 int32_t *failed_step);
+
+/*
+ * Solar gains of a series: the solar radiation that enters a room THROUGH ITS WINDOWS and lands on the room's inside faces,
+ * formed on the device at every step from the sky's per-site records — instead of one channel column per inside face the
+ * caller computes in advance. The reference computes this term in another SIMPLE crate; the rule below is this library's own
+ * contract, defined — as the sky is — against the per-call loop with the same rule written on the host
+ * (heat_amd/solar_gains.py, transmitted() and received()).
+ * An APERTURE a is a window seen from the sky: ap_surface (used only for its weather site), the outward normal n of the
+ * side that sees the sky, a beam transmittance as a polynomial of degree 5 in the cosine of incidence
+ * (ap_tau_coef[a][0..5], constant term first), a hemispherical transmittance and a scale in m2 (area x frame or shading
+ * factor). With r = sky->record[k][site of ap_surface[a]]; every line is ONE rounded f64 operation in the order written, no
+ * fused multiply-add:
+ *   c  = (n.x * r.sun_x + n.y * r.sun_y) + n.z * r.sun_z
+ *   fs = 0.5 + 0.5 * n.z          fg = 0.5 - 0.5 * n.z
+ *   t  = coef[5];  for j = 4 .. 0:  t = t * c;  t = t + coef[j]
+ *   ib = r.beam * c
+ *   Pb = c > 0 ? (ib * t) * scale : 0.0                  (W, beam; a NaN cosine is no beam, as in the sky)
+ *   id = r.diffuse * fs + r.ground * fg
+ *   Pd = (id * tau_diffuse) * scale                      (W, diffuse + ground-reflected)
+ *   P  = Pb + Pd;  transmitted[k][a] = P;  ap_sum[a] = ap_sum[a] + P
+ * t is not clamped: the polynomial is the caller's. ap_sum (in/out, nullable) is added onto what the caller passes in: a
+ * series of k steps followed by one of n - k with the returned array gives the bits of the series of n.
+ * An ENTRY i gives a receiver — the side en_side[i] (0 front, 1 back) of surface en_surface[i] — the shares en_beam[i] and
+ * en_diffuse[i] (1/m2: the share of the aperture's beam or diffuse power that lands on the receiver, divided by the
+ * receiver's area) of aperture en_aperture[i]. Entries come in any order; the raw solar value of a receiver is formed over
+ * ITS entries in the caller's order:
+ *   v = 0.0;   per entry:  v = v + en_beam[i] * Pb[a_i];   v = v + en_diffuse[i] * Pd[a_i]
+ *   if the series carries that input's gain array:  v = v * gain[s]
+ * From v on the value is the raw value of a driven solar input of the series: into the state mirror where the batch keeps
+ * one, through the clamps of surface.rs:916-923, times the side's absorptance factor, into the solar field of the side's
+ * device record. The side's long-wave field is never written here, and a side without entries is not written at all.
+ * An input has ONE source: the solar input of a receiver has channel -1 in the series and no solar mode bit in the sky.
+ * The rule has no memory beyond ap_sum; n_sub == 0 still sets the inputs of every step; a NaN in a record or table
+ * propagates as a NaN channel value does.
+ * heat_solar_gains_check (host-only; it also lays out and verifies the tables the march uploads) and
+ * heat_batch_march_series_gains run the same checks before any device work; every message names "aperture a" or "entry i":
+ * a negative count, a NULL array a positive count needs (ap_sum may be NULL), n_apertures > 0 with n_steps > 0 and no sky or
+ * no sky->record, a normal, coefficient, scale, transmittance or share that is not finite, a side byte above 1 ->
+ * HEAT_E_INVALID_ARG; a surface or aperture index out of range, a receiver whose solar input already has a channel or a sky
+ * bit -> HEAT_E_SIZE. Sharded batches are refused as by the series; weather sites are supported.
+ * heat_batch_march_series_gains with gains == NULL, or with n_apertures == 0 and n_entries == 0, is
+ * heat_batch_march_series_sky exactly (same kernels, same bits).
+ */
+typedef struct heat_solar_gains {
+    int64_t n_apertures;
+    const int64_t *ap_surface;                              /* [n_apertures] the window's surface: its site's record is read */
+    const double *ap_normal_x, *ap_normal_y, *ap_normal_z;  /* [n_apertures] outward normal of the side that sees the sky */
+    const double *ap_tau_coef;                              /* [n_apertures][6] beam transmittance, constant term first */
+    const double *ap_tau_diffuse;                           /* [n_apertures] hemispherical transmittance */
+    const double *ap_scale;                                 /* [n_apertures] m2 */
+    double *ap_sum;                                         /* [n_apertures] in/out, nullable: sum of P over the steps, W */
+    int64_t n_entries;
+    const int64_t *en_surface;                              /* [n_entries] the receiver's surface */
+    const uint8_t *en_side;                                 /* [n_entries] 0 front, 1 back */
+    const int32_t *en_aperture;                             /* [n_entries] */
+    const double *en_beam, *en_diffuse;                     /* [n_entries] 1/m2 */
+} heat_solar_gains;
+
+int heat_solar_gains_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                           const heat_solar_gains *gains); /* host-only */
+int heat_batch_march_series_gains(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                  const heat_solar_gains *gains /* nullable */, const heat_zone_loads *l /* nullable */,
+                                  heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
+                                  double *applied, double *ideal_q,
+                                  double *transmitted /* [n_steps][n_apertures], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -29,6 +29,27 @@ pub struct HeatWeather { pub dry_bulb: f64, pub wind_direction: f64, pub wind_sp
     pub stream: *mut c_void, pub n_ranks: i32, pub rank: i32, pub no_palette: i32, pub no_fusion: i32,
 }
 #[repr(C)] pub struct HeatBatch { _private: [u8; 0] }
+// The series structs this file does not spell out (include/heat_amd.h: heat_series, heat_zone_loads, heat_ideal_loads,
+// heat_series_report): passed by pointer only.
+#[repr(C)] pub struct HeatSeries { _private: [u8; 0] }
+#[repr(C)] pub struct HeatZoneLoads { _private: [u8; 0] }
+#[repr(C)] pub struct HeatIdealLoads { _private: [u8; 0] }
+#[repr(C)] pub struct HeatSeriesReport { _private: [u8; 0] }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub beam: f64, pub diffuse: f64, pub ground: f64,
+                           pub ir_sky: f64, pub ir_ground: f64 }
+#[repr(C)] pub struct HeatSky {
+    pub record: *const HeatSkyRecord, pub normal_x: *const f64, pub normal_y: *const f64, pub normal_z: *const f64,
+    pub mode: *const u8,
+}
+// heat_solar_gains: apertures (windows seen from the sky) and entries (the shares of an aperture's power a side receives)
+#[repr(C)] pub struct HeatSolarGains {
+    pub n_apertures: i64, pub ap_surface: *const i64,
+    pub ap_normal_x: *const f64, pub ap_normal_y: *const f64, pub ap_normal_z: *const f64,
+    pub ap_tau_coef: *const f64, pub ap_tau_diffuse: *const f64, pub ap_scale: *const f64, pub ap_sum: *mut f64,
+    pub n_entries: i64, pub en_surface: *const i64, pub en_side: *const u8, pub en_aperture: *const i32,
+    pub en_beam: *const f64, pub en_diffuse: *const f64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -61,6 +82,13 @@ extern "C" {
     pub fn heat_batch_download_outputs(b: *mut HeatBatch, state: *mut f64, n_state: usize, what: i32) -> c_int;
     pub fn heat_batch_failed_surface(b: *const HeatBatch, index: *mut i64, kind: *mut i32) -> c_int;
     pub fn heat_batch_set_fusion(b: *mut HeatBatch, enabled: i32) -> c_int;
+    // solar gains of a series: window-transmitted solar onto the room's faces, formed on the device at every step
+    pub fn heat_solar_gains_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
+                                  gains: *const HeatSolarGains) -> c_int;
+    pub fn heat_batch_march_series_gains(b: *mut HeatBatch, s: *const HeatSeries, sky: *const HeatSky,
+                                         gains: *const HeatSolarGains, l: *const HeatZoneLoads, il: *mut HeatIdealLoads,
+                                         r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64, ideal_q: *mut f64,
+                                         transmitted: *mut f64, failed_step: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

@@ -33,21 +33,33 @@ With --sky (heat_batch_march_series_sky; the model, channels, loads and probes o
   K  the same two inputs of every wall formed on the device from the sky: every wall its own azimuth, one site, one 64-byte
      record per step, the sun from heat_amd.sky.sun_direction (day 172, latitude 48 N, the steps spread over the day)
 and writes profiles/series_sky.json: ms per step of each, K / C', K - C'.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky]
+With --gains (heat_batch_march_series_gains; the model, channels, loads and probes of leg D; every tenth wall of a zone an
+aperture, the zone-facing side of every other wall of the zone a receiver of all the zone's apertures: at 1 M walls 100 k
+apertures, 900 k receivers, 9 M entries) two legs, alternated in the same way:
+  H  what a series offered before: every receiver's back solar input driven from a channel column of its own, the host
+     computing the columns (the rule of heat_amd/solar_gains.py over index arrays prepared once) and widening the table
+     INSIDE the clock
+  J  the same series with gains: one 64-byte sky record per step, the entry list given as it is
+beside leg D (the same series without the receivers: their input from the shared channels like everybody's), and writes
+profiles/series_gains.json: ms per step of each, J / H, a series of ONE step of each, J - D once the calls are set up, the
+bytes a step of k_series_solar_gains and of leg J's k_series_inputs moves.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
-                                                     with --ideal leg I; with --sky a series of leg C' and one of leg K"""
+                                                     with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
+                                                     a series of leg J"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, modeldict as mdl, sky as skym
+from heat_amd import HeatBatch, modeldict as mdl, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
 SKY = "--sky" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY
+GAINS = "--gains" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -117,6 +129,90 @@ if SKY:
                                                        sky=dict(sky_args, record=record[:steps]), **{k: (not_driven, drives[k][1]) for k in FRONT})
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace))
+        return dt * 1e3 / steps
+if GAINS:
+    assert np.all(np.diff(md["back_zone"]) >= 0) and np.all(md["back_kind"] == mdl.SPACE)
+    sun = skym.sun_direction(172, 24.0 * np.arange(STEPS) / STEPS, np.radians(48.0))
+    up = np.maximum(sun[:, 2], 0.0)
+    beam, diffuse = np.where(sun[:, 2] > 0.0, 800.0, 0.0), 60.0 + 140.0 * up
+    record = np.stack([sun[:, 0], sun[:, 1], sun[:, 2], beam, diffuse, 0.2 * (beam * up + diffuse), np.full(STEPS, 350.0),
+                       np.full(STEPS, 420.0)], axis=1)[:, None, :]
+    first_of = np.searchsorted(md["back_zone"], np.arange(Z + 1))
+    rank_in_zone = np.arange(S) - first_of[md["back_zone"]]
+    is_ap = rank_in_zone % 10 == 0
+    windows, receivers = np.flatnonzero(is_ap), np.flatnonzero(~is_ap)
+    NA, NR = len(windows), len(receivers)
+    ap_of_zone = [np.flatnonzero(is_ap[first_of[z]:first_of[z + 1]]) + first_of[z] for z in range(Z)]
+    ap_index = np.cumsum(is_ap) - 1                                        # wall -> its aperture number
+    per_zone = np.array([len(a) for a in ap_of_zone])
+    R_MAX = int(per_zone.max())
+    # rank j of every receiver: the j-th aperture of its zone (-1: the zone has fewer)
+    ap_rank = np.full((R_MAX, NR), -1, np.int64)
+    for j in range(R_MAX):
+        has = per_zone[md["back_zone"][receivers]] > j
+        zr = md["back_zone"][receivers][has]
+        ap_rank[j, has] = ap_index[np.array([a[j] if len(a) > j else -1 for a in ap_of_zone])[zr]]
+    zone_area = np.bincount(md["back_zone"], weights=md["area"], minlength=Z)
+    share_b = rng.uniform(0.5, 1.5, (R_MAX, NR)) / zone_area[md["back_zone"][receivers]]
+    share_d = rng.uniform(0.5, 1.5, (R_MAX, NR)) / zone_area[md["back_zone"][receivers]]
+    on = ap_rank >= 0
+    # the caller's list, aperture-major (as distribute_by_area gives it): the library sorts it by receiver
+    order = np.argsort(ap_rank[on], kind="stable")
+    gains_args = dict(ap_surface=windows, ap_normal=(md["normal_x"][windows], md["normal_y"][windows], md["cos_tilt"][windows]),
+                      ap_tau_coef=np.concatenate([rng.uniform(0.3, 0.8, (NA, 1)), rng.uniform(-0.05, 0.05, (NA, 5))], axis=1),
+                      ap_tau_diffuse=rng.uniform(0.3, 0.7, NA), ap_scale=md["area"][windows],
+                      en_surface=np.broadcast_to(receivers, ap_rank.shape)[on][order], en_side=np.ones(int(on.sum()), np.uint8),
+                      en_aperture=ap_rank[on][order].astype(np.int32), en_beam=share_b[on][order], en_diffuse=share_d[on][order])
+    NE = int(on.sum())
+    back_chan_j = drives["solar_back"][0].copy()
+    back_chan_j[receivers] = -1
+    back_chan_h = drives["solar_back"][0].copy()
+    back_chan_h[receivers] = channel.shape[1] + np.arange(NR)
+    # the bytes a step of k_series_solar_gains moves: per table element the aperture number, the share pair and the gathered
+    # (Pb, Pd); per receiver its record number, gain, absorptance factor, slot number, the mirror and the SideDyn field
+    rows = np.zeros((NR + 63) // 64 * 64, np.int64)
+    rows[:NR] = on.sum(axis=0)[np.argsort(receivers, kind="stable")]
+    padded = int(rows.reshape(-1, 64).max(axis=1).sum() * 64)
+    gains_bytes = dict(entries=NE, table_elements_with_padding=padded, per_element=4 + 16 + 16, receivers=NR, per_receiver=4 + 8 + 8 + 8 + 8 + 8,
+                       total=int(padded * 36 + NR * 44))
+    # the bytes a step of k_series_inputs moves in leg J: 160 per wall with all four inputs driven (16 of channel
+    # numbers, 72 per side), 40 less for a receiver, whose back solar input it leaves alone (gain, absorptance factor, slot
+    # number read; the mirror and the SideDyn field written)
+    inputs_bytes = dict(per_wall_all_four_driven=160, per_receiver=120, total=int(160 * NA + 120 * NR))
+
+    def host_columns(steps):
+        """What the host of leg H computes per series: the rule of solar_gains.transmitted / received over the prepared ranks."""
+        pb, pd = sgm.transmitted(record[:steps, 0][:, None, :], gains_args["ap_normal"], gains_args["ap_tau_coef"],
+                                 gains_args["ap_tau_diffuse"], gains_args["ap_scale"])
+        cols = np.zeros((steps, NR))
+        for k in range(steps):
+            v = np.zeros(NR)
+            for j in range(R_MAX):
+                a = ap_rank[j]
+                v = v + np.where(a >= 0, share_b[j] * pb[k, a], 0.0)
+                v = v + np.where(a >= 0, share_d[j] * pd[k, a], 0.0)
+            cols[k] = v
+        return cols
+
+    def leg_h(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        wide = np.concatenate([channel[:steps], host_columns(steps)], axis=1)
+        t1 = time.perf_counter()
+        trace, failed, applied, modes = b.march_series(w[:steps], n_sub, channel=wide, probes=probes, loads=loads,
+                                                       **dict(drives, solar_back=(back_chan_h, drives["solar_back"][1])))
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace))
+        return dt * 1e3 / steps, (t1 - t0) * 1e3 / steps
+
+    def leg_j(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, transmitted, ap_sum = b.march_series(
+            w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads, sky=dict(record=record[:steps]), gains=gains_args,
+            **dict(drives, solar_back=(back_chan_j, drives["solar_back"][1])))
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace)) and np.all(np.isfinite(transmitted))
         return dt * 1e3 / steps
 if REPORT:
     # the envelope of zone z: both faces of the walls whose back faces it (uniform_massive: all of a zone's walls, contiguous)
@@ -276,6 +372,41 @@ with HeatBatch(md) as b:
                   "K %.2f ms -> per step without the set-up C' %.3f, K %.3f, K / C' = %.4f (%d steps, median of %d rounds)" % (
                       n_sub, Cc, K, K / Cc, K - Cc, C1, K1, Cs, Ks, Ks / Cs, STEPS, ROUNDS), flush=True)
             continue
+        if GAINS:
+            leg_j(b, w, n_sub, min(STEPS, 10))  # warm-up
+            if ONE:
+                print("one series with gains: J %.3f ms per step" % leg_j(b, w, n_sub, STEPS))
+                continue
+            leg_h(b, w, n_sub, min(STEPS, 10))
+            leg_d(b, w, n_sub, min(STEPS, 10))
+            h, hh, j, d, h1, j1, d1 = [], [], [], [], [], [], []
+            for r in range(ROUNDS):
+                x, y = leg_h(b, w, n_sub, STEPS)
+                h.append(x), hh.append(y)
+                j.append(leg_j(b, w, n_sub, STEPS))
+                d.append(leg_d(b, w, n_sub, STEPS))  # the same series without the receivers: their input from the 64 shared channels
+                h1.append(leg_h(b, w, n_sub, 1)[0])  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                j1.append(leg_j(b, w, n_sub, 1))
+                d1.append(leg_d(b, w, n_sub, 1))
+            H, HH, J, D, H1, J1, D1 = (float(np.median(v)) for v in (h, hh, j, d, h1, j1, d1))
+            # per step once the call is set up. A series of one step carries the WHOLE set-up of J and D (tables that do not
+            # grow with the steps) but only one 7.2 MB row of H's [steps] x 7.2 MB table: H_without_setup still holds H's
+            # upload, so J is set against D here, not against H
+            Hs, Js, Ds = ((x * STEPS - x1) / (STEPS - 1) for x, x1 in ((H, H1), (J, J1), (D, D1)))
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                H_channel_columns_ms=H, H_host_columns_alone_ms=HH, J_gains_ms=J, D_no_receivers_ms=D, J_over_H=J / H,
+                J_over_H_without_the_hosts_columns=J / (H - HH),
+                expectation_J_at_most_1_05_H=bool(J <= 1.05 * H), H_series_of_one_step_ms=H1, J_series_of_one_step_ms=J1,
+                D_series_of_one_step_ms=D1, H_without_its_first_row_ms=Hs, J_without_setup_ms=Js, D_without_setup_ms=Ds,
+                J_minus_D_without_setup_ms=Js - Ds, expectation_J_within_5_percent_of_D_plus_230_us=bool(Js <= 1.05 * (Ds + 0.230)),
+                table_bytes_per_step=dict(H_channel_row=int(8 * (channel.shape[1] + NR)), J_records=64),
+                apertures=NA, receivers=NR, k_series_solar_gains_bytes_per_step=gains_bytes, k_series_inputs_bytes_per_step_in_J=inputs_bytes,
+                all_rounds=dict(H=h, H_host_columns=hh, J=j, D=d, H_one_step=h1, J_one_step=j1, D_one_step=d1))
+            print("n_sub %2d: H channel columns %.3f ms/step (%.3f of it the host's columns), J gains %.3f, D without the receivers %.3f "
+                  "-> J / H = %.4f (%.4f of H without the host's columns); a series of one step: H %.2f ms, J %.2f ms, D %.2f ms -> per step "
+                  "without the set-up J %.3f, D %.3f, J - D = %+.3f (H without its first row %.3f) (%d steps, median of %d rounds)" % (
+                      n_sub, H, HH, J, D, J / H, J / (H - HH), H1, J1, D1, Js, Ds, Js - Ds, Hs, STEPS, ROUNDS), flush=True)
+            continue
         if REPORT:
             if ONE:
                 leg = dict(zones=leg_f, nodes=leg_g)
@@ -357,9 +488,26 @@ with HeatBatch(md) as b:
                   n_sub, A, A_np, B, Cc, Cc / A, Cc - B, steady, C1, STEPS, ROUNDS), flush=True)
 if IDEAL:
     bs.close()
+if GAINS and not ONE:
+    # the kernel trace of one J series (--one-series --gains under rocprofv3 --kernel-trace --stats, a run of its own), where
+    # it has been taken: per step and on its own bytes, k_series_solar_gains beside the same trace's k_series_inputs
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_gains_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        kt = {}
+        for name, nbytes in (("k_series_solar_gains", gains_bytes["total"]), ("k_series_inputs", inputs_bytes["total"])):
+            us = float(rows[name]["AverageNs"]) / 1e3
+            kt[name] = dict(calls=int(rows[name]["Calls"]), us_per_step=us, bytes_per_step=nbytes, TB_per_s=nbytes / us / 1e6)
+        kt["k_series_apertures_us_per_step"] = float(rows["k_series_apertures"]["AverageNs"]) / 1e3
+        kt["rate_over_k_series_inputs"] = kt["k_series_solar_gains"]["TB_per_s"] / kt["k_series_inputs"]["TB_per_s"]
+        kt["expectation_rate_at_least_0_95_of_k_series_inputs"] = bool(kt["rate_over_k_series_inputs"] >= 0.95)
+        result["kernel_trace_of_one_J_series"] = kt
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
