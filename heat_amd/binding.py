@@ -126,6 +126,13 @@ class SolarGains(C.Structure):
                 ("en_beam", _dp), ("en_diffuse", _dp)]
 
 
+class AirPaths(C.Structure):
+    """heat_air_paths (include/heat_amd.h): air that moves between zones, and vents controlled on both of their ends"""
+    _fields_ = [("n_paths", C.c_int64), ("target", _i32p), ("source", _i32p), ("temp_chan", _i32p), ("volume_chan", _i32p),
+                ("volume_gain", _dp), ("open_chan", _i32p), ("sense", C.POINTER(C.c_int8)), ("band", _dp), ("min_delta", _dp),
+                ("state", C.POINTER(C.c_uint8)), ("sum_q", _dp), ("steps_open", _i64p), ("switches", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -173,6 +180,10 @@ SYMBOLS = [
     ("heat_solar_gains_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains)]),
     ("heat_batch_march_series_gains", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains), C.POINTER(ZoneLoads),
                                                 C.POINTER(IdealLoads), C.POINTER(Report), _dp, _dp, _dp, _dp, _i32p]),
+    ("heat_air_paths_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(AirPaths)]),
+    ("heat_batch_march_series_air", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains), C.POINTER(ZoneLoads),
+                                              C.POINTER(AirPaths), C.POINTER(IdealLoads), C.POINTER(Report), _dp, _dp, _dp, _dp, _dp,
+                                              _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -323,6 +334,7 @@ def make_desc(md):
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
+                     "heat_air_paths_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -841,6 +853,67 @@ def solar_gains_check(md, gains, sky=None, n_sites=1, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+AIR_STATS = ("sum_q", "steps_open", "switches")
+_AIR_ARRAYS = (("target", np.int32), ("source", np.int32), ("temp_chan", np.int32), ("volume_chan", np.int32),
+               ("volume_gain", np.float64), ("open_chan", np.int32), ("sense", np.int8), ("band", np.float64),
+               ("min_delta", np.float64))
+_AIR_OPTIONAL = ("temp_chan", "volume_gain", "open_chan", "sense", "band", "min_delta")
+_AIR_INOUT = (("state", np.uint8), ("sum_q", np.float64), ("steps_open", np.int64), ("switches", np.int64))
+
+
+def make_air_paths(target=(), source=(), temp_chan=None, volume_chan=(), volume_gain=None, open_chan=None, sense=None, band=None,
+                   min_delta=None, state=None, sum_q=None, steps_open=None, switches=None, stats=AIR_STATS):
+    """Builds a heat_air_paths. Returns (air, keepalive); the march updates keepalive["state"] and the accumulators in place.
+    target, source   [n_paths] zones; source -1: supply air at the temperature of channel temp_chan
+    temp_chan        [n_paths], -1 where the source is a zone; None: no source is -1
+    volume_chan      [n_paths] m3/s;  volume_gain [n_paths], None: 1
+    open_chan        [n_paths] the target's setpoint channel of a controlled path, -1: uncontrolled; None: all uncontrolled
+    sense, band, min_delta   [n_paths] +1 cooling / -1 heating, K, K: read only where controlled
+    state, sum_q, steps_open, switches   [n_paths] what a previous series returned (copied); None: zeros
+    stats            which of sum_q, steps_open, switches the march maintains (the others stay NULL)"""
+    given = dict(target=target, source=source, temp_chan=temp_chan, volume_chan=volume_chan, volume_gain=volume_gain,
+                 open_chan=open_chan, sense=sense, band=band, min_delta=min_delta)
+    unknown = set(stats) - set(AIR_STATS)
+    if unknown:
+        raise ValueError("air paths: unknown stats %s (known: %s)" % (sorted(unknown), ", ".join(AIR_STATS)))
+    a = AirPaths()
+    n = len(np.asarray(target).reshape(-1))
+    a.n_paths = n
+    keep = {}
+    for name, dtype in _AIR_ARRAYS:
+        if given[name] is None and name in _AIR_OPTIONAL:
+            continue
+        v = np.ascontiguousarray(given[name], dtype=dtype).reshape(-1)
+        if v.shape != (n,):
+            raise ValueError("air paths %s: %s for %d paths" % (name, v.shape, n))
+        keep[name] = v
+        setattr(a, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    for (name, dtype), v in zip(_AIR_INOUT, (state, sum_q, steps_open, switches)):
+        if name != "state" and name not in stats:
+            if v is not None:
+                raise ValueError("air paths %s given, but not among stats %s" % (name, tuple(stats)))
+            continue
+        v = np.zeros(n, dtype) if v is None else np.array(v, dtype=dtype).reshape(-1)  # (a copy: the march writes it)
+        if v.shape != (n,):
+            raise ValueError("air paths %s: %s for %d paths" % (name, v.shape, n))
+        keep[name] = v
+        setattr(a, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    return a, keep
+
+
+def air_paths_check(md, air, n_sites=1, lib=None, **series):
+    """heat_air_paths_check: everything about the air paths of a series that needs no device (series arguments as
+    HeatBatch.march_series; air: the arguments of make_air_paths, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    a, akeep = make_air_paths(**air) if air is not None else (None, None)
+    rc = L.heat_air_paths_check(C.byref(desc), int(n_sites), C.byref(s), C.byref(a) if a is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -954,7 +1027,7 @@ class HeatBatch:
         _check(self._L.heat_batch_synchronize(self._h))
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
-                     **series):
+                     air=None, path_q=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -976,7 +1049,17 @@ class HeatBatch:
         gains (a dict of make_solar_gains' arguments; sky carries the records, its mode may be left out):
         heat_batch_march_series_gains — the solar radiation the apertures transmit, onto the receiving sides. Returns what the
         same call without gains returns plus transmitted [n_steps, n_apertures] and ap_sum [n_apertures] (pass it as
-        gains["ap_sum"] to the next series): two more elements of the tuple, or two more keys of the dict."""
+        gains["ap_sum"] to the next series): two more elements of the tuple, or two more keys of the dict.
+        air (a dict of make_air_paths' arguments: target, source, temp_chan, volume_chan, volume_gain, open_chan, sense, band,
+        min_delta, state, sum_q, steps_open, switches, stats): heat_batch_march_series_air — air that moves between zones and
+        controlled vents, formed on the device at every step from the zone temperatures it holds. Returns what the same call
+        without air returns plus one dict: path_q [n_steps, n_paths] (empty with path_q=False), state, and of sum_q,
+        steps_open, switches those in stats (pass state and them on to the next series) — one more element of the tuple, or
+        the key "air" of the dict."""
+        if air is not None:
+            if gains is not None:
+                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
+            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q)
         if gains is not None:
             return self._march_series_sky(weather, n_sub, loads, ideal, report, _sky_for_gains(sky, self._normals, self.n_surfaces),
                                           trace, applied, series, gains)
@@ -1064,7 +1147,8 @@ class HeatBatch:
             out["report"] = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
         return out
 
-    def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None):
+    def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None, air=None,
+                          want_path_q=True):
         if report is None and ideal is None and not (want_trace and want_applied):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1072,11 +1156,13 @@ class HeatBatch:
         for k in ("zone_a0", "zone_b0"):
             if k in keep and keep[k].shape[1] != self.n_zones:
                 raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
-        sky = dict(sky)
-        if sky.get("normals") is None:
-            sky["normals"] = self._normals
-        k, kkeep = make_sky(**sky)
-        _sky_fits(kkeep, s.n_steps, self.n_sites, self.n_surfaces)
+        k = None
+        if sky is not None:  # (only a call with air paths comes here without a sky)
+            sky = dict(sky)
+            if sky.get("normals") is None:
+                sky["normals"] = self._normals
+            k, kkeep = make_sky(**sky)
+            _sky_fits(kkeep, s.n_steps, self.n_sites, self.n_surfaces)
         l, lkeep = make_zone_loads(**(loads or {}))
         il, ikeep = make_ideal_loads(**(ideal or {}))
         r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **(report or {}))
@@ -1090,6 +1176,14 @@ class HeatBatch:
         if gains is not None:
             g, gkeep = make_solar_gains(**gains)
             transmitted = np.zeros((s.n_steps, g.n_apertures))
+        if air is not None:
+            a, akeep = make_air_paths(**air)
+            q = np.zeros((s.n_steps if want_path_q else 0, a.n_paths))
+            rc = self._L.heat_batch_march_series_air(self._h, C.byref(s), C.byref(k) if k is not None else None,
+                                                     C.byref(g) if gains is not None else None, args[0], C.byref(a), *args[1:],
+                                                     transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
+                                                     q.ctypes.data_as(_dp) if q.size else None, C.byref(failed))
+        elif gains is not None:
             rc = self._L.heat_batch_march_series_gains(self._h, C.byref(s), C.byref(k), C.byref(g), *args,
                                                        transmitted.ctypes.data_as(_dp) if transmitted.size else None, C.byref(failed))
         else:
@@ -1108,10 +1202,13 @@ class HeatBatch:
                 out["report"] = rep
             if gains is not None:
                 out.update(transmitted=transmitted, ap_sum=gkeep["ap_sum"])
+            if air is not None:
+                out["air"] = dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep})
             return out
         out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
         out = out + ((rep,) if report is not None else ())
-        return out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
+        out = out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
+        return out + ((dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep}),) if air is not None else ())
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -1068,6 +1068,17 @@ struct GainsDev {
     DevBuf<double> share;
 };
 
+// The device copies of the air paths of a series (heat_air_paths): the tables sorted by target zone (plan.hpp, AirPathTables),
+// the state bytes, the accumulators and the path_q rows in the caller's order. Declared beside GainsDev.
+struct AirDev {
+    DevBuf<int32_t> i32;
+    DevBuf<double> f64;
+    DevBuf<uint8_t> state;     // [NP]
+    DevBuf<double> sum_q;      // [NP]
+    DevBuf<int64_t> i64[2];    // steps_open, switches
+    DevBuf<double> path_q;     // [n_steps][NP]
+};
+
 template <typename T>
 int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
     const hipError_t e = buf.alloc(count);
@@ -2051,11 +2062,11 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 // heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
 // il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit,
-// and gains == nullptr, or neither an aperture nor an entry.
+// and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
                              double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
                              double *ideal_q = nullptr, const heat_sky *sky = nullptr, const heat_solar_gains *gains = nullptr,
-                             double *transmitted = nullptr) {
+                             double *transmitted = nullptr, heat_air_paths *air = nullptr, double *path_q = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2086,6 +2097,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     rc = check_solar_gains(b->n_surf, s, sky, gains, heat::last_error());
     if (rc) return rc;
     const int64_t NA = gains ? gains->n_apertures : 0;  // (entries need an aperture: there are none without)
+    rc = check_air_paths(b->n_zones, s->n_channels, air, heat::last_error());
+    if (rc) return rc;
+    const int64_t NP = air ? air->n_paths : 0;
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
@@ -2263,6 +2277,15 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (l->th_mode) std::copy(l->th_mode, l->th_mode + NT, h_mode.begin());
     }
 
+    // air paths: the list sorted by target zone with CSR offsets (plan.hpp), the state bytes in the caller's order
+    AirPathTables apt;
+    std::vector<uint8_t> h_air_state;
+    if (NP > 0) {
+        build_air_path_tables(Z, air, apt);
+        h_air_state.assign((size_t)NP, 0);
+        if (air->state) std::copy(air->state, air->state + NP, h_air_state.begin());
+    }
+
     // ---- on the device for the duration of the call; freed on every return path, after the stream has run dry ----
     DevBuf<int32_t> d_zl_i32;
     DevBuf<double> d_zl_f64, d_applied;
@@ -2277,6 +2300,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     IdealDev idd;
     SkyDev skd;
     GainsDev gnd;
+    AirDev aird;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2447,6 +2471,24 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         gnsd.power = gnd.power.p;
         gnsd.gain[0] = d_gain[0].p, gnsd.gain[1] = d_gain[1].p;
     }
+    AirPathsDev airp{};
+    if (NP > 0) {
+        if ((rc = series_upload(aird.i32, apt.i32.data(), apt.i32.size(), "air path tables"))) return rc;
+        if ((rc = series_upload(aird.f64, apt.f64.data(), apt.f64.size(), "air path tables"))) return rc;
+        if ((rc = series_upload(aird.state, h_air_state.data(), h_air_state.size(), "air path states"))) return rc;
+        if ((rc = report_array(aird.sum_q, air->sum_q, (size_t)NP, true, "air path accumulators"))) return rc;
+        if ((rc = report_array(aird.i64[0], air->steps_open, (size_t)NP, true, "air path accumulators"))) return rc;
+        if ((rc = report_array(aird.i64[1], air->switches, (size_t)NP, true, "air path accumulators"))) return rc;
+        if (path_q && (rc = series_alloc(aird.path_q, (size_t)n_steps * NP, "air path powers"))) return rc;
+        const int32_t *list = aird.i32.p + (Z + 1);
+        airp.off = aird.i32.p;
+        airp.source = list, airp.temp_chan = list + NP, airp.volume_chan = list + 2 * NP, airp.open_chan = list + 3 * NP;
+        airp.orig = list + 4 * NP;
+        airp.volume_gain = aird.f64.p, airp.sense = aird.f64.p + NP, airp.half_band = aird.f64.p + 2 * NP;
+        airp.min_delta = aird.f64.p + 3 * NP;
+        airp.state = aird.state.p;
+        airp.sum_q = aird.sum_q.p, airp.steps_open = aird.i64[0].p, airp.switches = aird.i64[1].p;
+    }
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
 
     SeriesInputs in{};
@@ -2474,7 +2516,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> driven inputs -> sky -> solar gains -> the body of a march call of
+    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> driven inputs -> sky -> solar gains -> the body of a march call of
     // n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
@@ -2483,6 +2525,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             launch_series_zone_loads((int)Z, zl, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
                                      applied_dev ? applied_dev + (size_t)k * applied_stride : nullptr, b->d_flags.p, b->stream);
         if (th_stats) launch_series_th_stats((int)NT, td, d_mode.p, applied_dev ? applied_dev + (size_t)k * applied_stride : nullptr, b->stream);
+        if (NP > 0)
+            launch_series_air_paths((int)Z, airp, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
+                                    aird.path_q.p ? aird.path_q.p + (size_t)k * NP : nullptr, b->d_flags.p, b->stream);
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
@@ -2549,6 +2594,13 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             HIP_TRY(hipMemcpyAsync(transmitted, gnd.transmitted.p, (size_t)n_steps * NA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
         if (gnd.sum.p) HIP_TRY(hipMemcpyAsync(gains->ap_sum, gnd.sum.p, (size_t)NA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     }
+    if (NP > 0) {
+        if (aird.path_q.p) HIP_TRY(hipMemcpyAsync(path_q, aird.path_q.p, (size_t)n_steps * NP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (air->state) HIP_TRY(hipMemcpyAsync(air->state, aird.state.p, (size_t)NP, hipMemcpyDeviceToHost, b->stream));
+        if (aird.sum_q.p) HIP_TRY(hipMemcpyAsync(air->sum_q, aird.sum_q.p, (size_t)NP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (aird.i64[0].p) HIP_TRY(hipMemcpyAsync(air->steps_open, aird.i64[0].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+        if (aird.i64[1].p) HIP_TRY(hipMemcpyAsync(air->switches, aird.i64[1].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
+    }
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2588,6 +2640,12 @@ int heat_batch_march_series_gains(heat_batch *b, const heat_series *s, const hea
                                   const heat_zone_loads *l, heat_ideal_loads *il, heat_series_report *r, double *trace, double *applied,
                                   double *ideal_q, double *transmitted, int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted);
+}
+
+int heat_batch_march_series_air(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_solar_gains *gains,
+                                const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il, heat_series_report *r, double *trace,
+                                double *applied, double *ideal_q, double *transmitted, double *path_q, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

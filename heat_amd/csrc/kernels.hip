@@ -2559,6 +2559,68 @@ k_series_th_stats(int n, SeriesThStatsDev t, const uint8_t *__restrict__ mode, c
     }
 }
 
+// k_series_air_paths — the air paths of one step (heat_air_paths, include/heat_amd.h), behind k_series_zone_loads /
+// k_series_th_stats and before k_series_inputs: one lane per zone walks the paths whose TARGET it is (a CSR range of the list
+// sorted by target, the caller's order kept inside a zone) and adds the open ones to the a0 / b0 of its own zone alone; a zone
+// nothing flows into leaves after reading its offsets. A path reads the temperature of its source zone — any zone — as the
+// step before left it: nothing on the step's head writes zone_T, so every source is the start of the step's whatever the
+// order of the lanes. A path belongs to the lane of its target: its state byte, its element of the step's path_q row and
+// its accumulators (all in the caller's order, through `orig`) have one writer, and the order of a zone's sum is the
+// caller's — which one lane per path with atomic adds would not give. Which outputs exist is decided by nullable pointers
+// in the kernel argument: wave-uniform branches, an array nobody takes is neither read nor written.
+// Every product and sum is one rounded operation in the header's order, the air properties written out as in
+// k_series_zone_loads (same expressions, same grouping): the host applying the rule between march calls reproduces the bits.
+// A NaN a0 / b0 is reported as the zone's failure, as the zone loads report it.
+__global__ void __launch_bounds__(256)
+k_series_air_paths(int n_zones, AirPathsDev ap, const double *__restrict__ row, const double *__restrict__ zone_T,
+                   double *__restrict__ a0, double *__restrict__ b0, double *__restrict__ q_row, int *__restrict__ flags) {
+#pragma clang fp contract(off)
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= n_zones) return;
+    const int p0 = ap.off[z], p1 = ap.off[z + 1];
+    if (p0 == p1) return;
+    double a = a0[z], b = b0[z];
+    const bool clean = a == a && b == b;
+    const double tt = zone_T[z];
+    for (int i = p0; i < p1; i++) {
+        const int orig = ap.orig[i], src = ap.source[i], oc = ap.open_chan[i];
+        const double ts = src >= 0 ? zone_T[src] : row[ap.temp_chan[i]];
+        bool open = true, switched = false;
+        if (oc >= 0) {
+            const double set = row[oc], d = ap.half_band[i], s = ap.sense[i];
+            const int before = ap.state[orig];
+            const double e = s * (tt - set);
+            const double g = s * (tt - ts);
+            int now = before;
+            if (e > d && g > ap.min_delta[i]) now = 1;
+            else if (before == 1 && (e < -d || g <= 0.0)) now = 0;
+            switched = now != before;
+            if (switched) ap.state[orig] = (uint8_t)now;
+            open = now == 1;
+        }
+        double q = 0.0;
+        if (open) {
+            const double v = ap.volume_gain[i] * row[ap.volume_chan[i]];
+            const double tk = ts + 273.15;
+            const double rho = 101325. * 28.97 / (8314.46261815324 * tk);  // gas.rs:175-179
+            const double cp = 1002.7370 + 1.2324e-2 * tk;                  // gas.rs:49,165-167
+            const double m = (rho * v) * cp;
+            const double mt = m * ts;
+            a = a + mt;
+            b = b + m;
+            const double dt = ts - tt;
+            q = m * dt;
+        }
+        if (q_row != nullptr) q_row[orig] = q;
+        if (ap.sum_q != nullptr) ap.sum_q[orig] = ap.sum_q[orig] + q;
+        if (ap.steps_open != nullptr && open) ap.steps_open[orig] += 1;
+        if (ap.switches != nullptr && switched) ap.switches[orig] += 1;
+    }
+    a0[z] = a;
+    b0[z] = b;
+    if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
+}
+
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = value;
@@ -2983,6 +3045,12 @@ void launch_series_stats(const SeriesStatsDev &s, const double *T, const SideOut
 void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const uint8_t *mode, const double *applied_row, hipStream_t st) {
     if (n_thermostats <= 0) return;
     hipLaunchKernelGGL(k_series_th_stats, dim3((n_thermostats + 255) / 256), dim3(256), 0, st, n_thermostats, t, mode, applied_row);
+}
+
+void launch_series_air_paths(int n_zones, const AirPathsDev &ap, const double *row, const double *zone_T, double *a0, double *b0,
+                             double *q_row, int *flags, hipStream_t st) {
+    if (n_zones <= 0) return;
+    hipLaunchKernelGGL(k_series_air_paths, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, ap, row, zone_T, a0, b0, q_row, flags);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

@@ -177,6 +177,21 @@ struct SeriesThStatsDev {
     uint8_t *prev;
 };
 void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const uint8_t *mode, const double *applied_row, hipStream_t st);
+// Air paths of a series step (heat_air_paths, include/heat_amd.h; tables: plan.hpp, AirPathTables): launched behind
+// launch_series_zone_loads / launch_series_th_stats and before launch_series_inputs, one lane per zone; only when there are
+// paths.
+struct AirPathsDev {
+    const int32_t *off;  // [n_zones + 1]: CSR offsets of the paths whose target the zone is
+    const int32_t *source, *temp_chan, *volume_chan, *open_chan, *orig;
+    const double *volume_gain, *sense, *half_band, *min_delta;
+    uint8_t *state;      // [n_paths], the caller's order (as every array below)
+    double *sum_q;       // nullptr: not maintained
+    int64_t *steps_open, *switches;
+};
+// row: the step's row of the channel table; q_row: the step's row of path_q (caller's order), or nullptr; flags: the batch's
+// failure flags (a path that makes a zone's a0 / b0 NaN is reported as that zone's failure)
+void launch_series_air_paths(int n_zones, const AirPathsDev &ap, const double *row, const double *zone_T, double *a0, double *b0,
+                             double *q_row, int *flags, hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Per step: launch_series_ideal_begin (behind the zone loads)

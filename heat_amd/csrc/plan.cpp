@@ -1848,6 +1848,114 @@ void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadT
     }
 }
 
+// ---- air paths of a series (include/heat_amd.h, heat_air_paths) ----
+int check_air_paths(int64_t n_zones, int32_t n_channels, const heat_air_paths *air, std::string &err) {
+    if (!air) return HEAT_OK;
+    const int64_t n = air->n_paths;
+    if (n < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of air paths (air path count n_paths %lld)", (long long)n);
+    // (the tables number the paths with 32 bits)
+    if (n > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 air paths (air path count n_paths %lld)", (long long)n);
+    if (n == 0) return HEAT_OK;
+    if (!air->target) return failp(err, HEAT_E_INVALID_ARG, "air path 0: target is NULL");
+    if (!air->source) return failp(err, HEAT_E_INVALID_ARG, "air path 0: source is NULL");
+    if (!air->volume_chan) return failp(err, HEAT_E_INVALID_ARG, "air path 0: volume_chan is NULL");
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t zt = air->target[i], zs = air->source[i], vc = air->volume_chan[i];
+        const int32_t tc = air->temp_chan ? air->temp_chan[i] : -1, oc = air->open_chan ? air->open_chan[i] : -1;
+        if (zt < 0 || zt >= n_zones)
+            return failp(err, HEAT_E_SIZE, "air path %lld: target zone %d outside [0, %lld)", (long long)i, zt, (long long)n_zones);
+        if (zs < -1 || zs >= n_zones)
+            return failp(err, HEAT_E_SIZE, "air path %lld: source zone %d outside [-1, %lld)", (long long)i, zs, (long long)n_zones);
+        if (zs == zt) return failp(err, HEAT_E_INVALID_ARG, "air path %lld: source and target are the same zone %d", (long long)i, zt);
+        if (vc < 0 || vc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "air path %lld: volume channel %d outside [0, %d)", (long long)i, vc, n_channels);
+        if (zs == -1 && (tc < 0 || tc >= n_channels))
+            return failp(err, HEAT_E_SIZE, "air path %lld: source -1 (supply air) needs a temperature channel in [0, %d), not %d%s", (long long)i,
+                         n_channels, tc, air->temp_chan ? "" : " (temp_chan is NULL)");
+        if (zs >= 0 && tc != -1)
+            return failp(err, HEAT_E_SIZE, "air path %lld: its air comes from zone %d and from temperature channel %d: an input has one source",
+                         (long long)i, zs, tc);
+        if (oc < -1 || oc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "air path %lld: open channel %d outside [-1, %d)", (long long)i, oc, n_channels);
+        if (air->volume_gain && !std::isfinite(air->volume_gain[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "air path %lld: volume_gain %g is not finite", (long long)i, air->volume_gain[i]);
+        if (air->state && air->state[i] > 1)
+            return failp(err, HEAT_E_INVALID_ARG, "air path %lld: state %d is neither 0 (closed) nor 1 (open)", (long long)i, (int)air->state[i]);
+        if (oc < 0) continue;  // (uncontrolled: sense, band and min_delta are not read)
+        if (!air->sense || !air->band || !air->min_delta)
+            return failp(err, HEAT_E_INVALID_ARG, "air path %lld: controlled (open channel %d), but %s is NULL", (long long)i, oc,
+                         !air->sense ? "sense" : (!air->band ? "band" : "min_delta"));
+        if (air->sense[i] != 1 && air->sense[i] != -1)
+            return failp(err, HEAT_E_INVALID_ARG, "air path %lld: sense %d is neither +1 (cooling) nor -1 (heating)", (long long)i, (int)air->sense[i]);
+        const double v[2] = {air->band[i], air->min_delta[i]};
+        static const char *const name[2] = {"band", "min_delta"};
+        for (int a = 0; a < 2; a++)
+            if (!std::isfinite(v[a]) || v[a] < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "air path %lld: %s %g is negative or not finite", (long long)i, name[a], v[a]);
+    }
+    return HEAT_OK;
+}
+
+void build_air_path_tables(int64_t n_zones, const heat_air_paths *air, AirPathTables &t) {
+    const size_t Z = (size_t)n_zones, n = air ? (size_t)air->n_paths : 0;
+    t = AirPathTables();
+    t.n_zones = n_zones;
+    t.n_paths = (int64_t)n;
+    t.i32.assign(Z + 1 + 5 * n, 0);
+    t.f64.assign(4 * n, 0.0);
+    if (n == 0) return;
+    // a counting sort by target zone: stable, so the caller's order survives inside a zone
+    int32_t *off = t.i32.data();
+    for (size_t i = 0; i < n; i++) off[air->target[i] + 1]++;
+    for (size_t z = 0; z < Z; z++) off[z + 1] += off[z];
+    std::vector<int32_t> next(off, off + Z);
+    int32_t *list = t.i32.data() + Z + 1;
+    double *real = t.f64.data();
+    for (size_t i = 0; i < n; i++) {
+        const size_t p = (size_t)next[(size_t)air->target[i]]++;
+        const int32_t oc = air->open_chan ? air->open_chan[i] : -1;
+        list[p] = air->source[i];
+        list[n + p] = air->temp_chan ? air->temp_chan[i] : -1;
+        list[2 * n + p] = air->volume_chan[i];
+        list[3 * n + p] = oc;
+        list[4 * n + p] = (int32_t)i;
+        real[p] = air->volume_gain ? air->volume_gain[i] : 1.0;
+        real[n + p] = oc >= 0 ? (double)air->sense[i] : 0.0;
+        real[2 * n + p] = oc >= 0 ? air->band[i] / 2.0 : 0.0;
+        real[3 * n + p] = oc >= 0 ? air->min_delta[i] : 0.0;
+    }
+}
+
+int check_air_path_tables(int64_t n_zones, const heat_air_paths *air, const AirPathTables &t, std::string &err) {
+    const size_t Z = (size_t)n_zones, n = air ? (size_t)air->n_paths : 0;
+    if (t.n_zones != n_zones || t.n_paths != (int64_t)n || t.i32.size() != Z + 1 + 5 * n || t.f64.size() != 4 * n)
+        return failp(err, HEAT_E_SIZE, "air path tables: %zu integers and %zu reals for %zu paths into %zu zones", t.i32.size(), t.f64.size(), n, Z);
+    const int32_t *off = t.off();
+    if (off[0] != 0 || off[Z] != (int32_t)n)
+        return failp(err, HEAT_E_SIZE, "air path tables: the offsets run from %d to %d for %zu paths", off[0], off[Z], n);
+    for (size_t z = 0; z < Z; z++)
+        if (off[z + 1] < off[z] || off[z + 1] > (int32_t)n)
+            return failp(err, HEAT_E_SIZE, "air path tables: zone %zu runs from %d to %d", z, off[z], off[z + 1]);
+    // every path of the caller's, in the caller's order, is the next element of its target's range ...
+    std::vector<int32_t> cursor(off, off + Z);
+    for (size_t i = 0; i < n; i++) {
+        const size_t z = (size_t)air->target[i];
+        const int32_t p = cursor[z]++;
+        if (p >= off[z + 1]) return failp(err, HEAT_E_SIZE, "air path tables: air path %zu: zone %zu has no room for it", i, z);
+        const int32_t oc = air->open_chan ? air->open_chan[i] : -1;
+        const double gain = air->volume_gain ? air->volume_gain[i] : 1.0;
+        if (t.list(4)[p] != (int32_t)i || t.list(0)[p] != air->source[i] || t.list(1)[p] != (air->temp_chan ? air->temp_chan[i] : -1) ||
+            t.list(2)[p] != air->volume_chan[i] || t.list(3)[p] != oc || std::memcmp(&t.real(0)[p], &gain, sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "air path tables: air path %zu is not element %d of zone %zu", i, p - off[z], z);
+        if (oc >= 0 && (t.real(1)[p] != (double)air->sense[i] || t.real(2)[p] != air->band[i] / 2.0 || t.real(3)[p] != air->min_delta[i]))
+            return failp(err, HEAT_E_SIZE, "air path tables: air path %zu: its controller is not the caller's", i);
+    }
+    // ... and every range is full: with n elements in all, each path is present exactly once
+    for (size_t z = 0; z < Z; z++)
+        if (cursor[z] != off[z + 1]) return failp(err, HEAT_E_SIZE, "air path tables: zone %zu holds %d paths of %d", z, cursor[z] - off[z], off[z + 1] - off[z]);
+    return HEAT_OK;
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -2322,6 +2430,18 @@ int heat_solar_gains_check(const heat_batch_desc *desc, int32_t n_sites, const h
     heat::SolarGainTables t;
     heat::build_solar_gain_tables(desc->n_surfaces, nullptr, gains, t);
     return heat::check_solar_gain_tables(desc->n_surfaces, nullptr, gains, t, heat::last_error());
+}
+
+int heat_air_paths_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_air_paths *air) {
+    int rc = heat_series_check(desc, n_sites, s);
+    if (rc) return rc;
+    rc = heat::check_air_paths(desc->n_zones, s->n_channels, air, heat::last_error());
+    if (rc || !air) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see)
+    heat::AirPathTables t;
+    heat::build_air_path_tables(desc->n_zones, air, t);
+    return heat::check_air_path_tables(desc->n_zones, air, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

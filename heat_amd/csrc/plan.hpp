@@ -166,6 +166,27 @@ struct ZoneLoadTables {
 // (of loads that passed check_zone_loads)
 void build_zone_load_tables(int64_t n_zones, const heat_zone_loads *l, ZoneLoadTables &t);
 
+// Air paths of a series (heat_air_paths, include/heat_amd.h). Everything heat_air_paths_check promises about the paths
+// themselves; air == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "air path i".
+int check_air_paths(int64_t n_zones, int32_t n_channels, const heat_air_paths *air, std::string &err);
+// The tables of k_series_air_paths (one lane per zone): the paths stably sorted by target zone — the caller's order survives
+// inside a zone — with CSR offsets, packed into one int32 and one f64 buffer (one upload each). A NULL volume_gain is ones
+// here, an uncontrolled path has open_chan -1 and sense, half band and min_delta 0; orig keeps the caller's number of a
+// path: path_q, the state bytes and the accumulators stay in the caller's order.
+struct AirPathTables {
+    int64_t n_zones = 0, n_paths = 0;
+    std::vector<int32_t> i32;  // off [n_zones + 1] | source [n] | temp_chan [n] | volume_chan [n] | open_chan [n] | orig [n]
+    std::vector<double> f64;   // volume_gain [n] | sense [n] (+1.0 / -1.0) | half_band [n] | min_delta [n]
+    const int32_t *off() const { return i32.data(); }
+    const int32_t *list(int a) const { return i32.data() + (n_zones + 1) + a * n_paths; }  // 0 source .. 4 orig
+    const double *real(int a) const { return f64.data() + a * n_paths; }                   // 0 volume_gain .. 3 min_delta
+};
+// (of paths that passed check_air_paths)
+void build_air_path_tables(int64_t n_zones, const heat_air_paths *air, AirPathTables &t);
+// The tables against the caller's lists (used by the host-only check): every path present exactly once, the caller's order
+// kept inside a zone, the offsets monotone and inside the buffers. HEAT_OK or HEAT_E_SIZE.
+int check_air_path_tables(int64_t n_zones, const heat_air_paths *air, const AirPathTables &t, std::string &err);
+
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
 // themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".
 // load_of_zone (nullable): [n_zones], the load of every zone or -1 — the table k_zone_update_ideal looks its zone up in.

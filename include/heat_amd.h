@@ -616,6 +616,80 @@ int heat_batch_march_series_gains(heat_batch *b, const heat_series *s, const hea
                                   heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
                                   double *applied, double *ideal_q,
                                   double *transmitted /* [n_steps][n_apertures], nullable */, int32_t *failed_step);
+
+/*
+ * Air paths of a series: air that moves BETWEEN ZONES — a doorway, a transfer grille, the vent of a Trombe wall — and vents
+ * that open and close on the state of both of their ends: night ventilation, a window that opens when the room is too warm
+ * and the air outside is cooler. It is the one term of calculate_zones_abc the reference marks and leaves empty
+ * ("Mixing with other zones", "AIR MIXTURE WITH OTHER ZONES ... unimplemented()", model.rs:546,592-593): the rule below is
+ * this library's own contract, defined — as the thermostat is — against the per-call loop with the same rule applied by the
+ * host between the calls (heat_amd/air_paths.py, apply()). Like a thermostat it cannot be a schedule: what the target
+ * receives is m * T of the source zone, a temperature the device holds; the flows of heat_zone_loads read volume and
+ * temperature from channels and can express none of it.
+ * A PATH i carries air from source[i] — a zone, or -1: supply air at row[temp_chan[i]] — into target[i]. Balanced exchange
+ * between two zones is TWO paths; that is the caller's business. Step k, after step 4 of the zone loads (thermostats) and
+ * before the driven inputs and the sub-timesteps; T = the zone temperatures the device holds then (what step k - 1 left;
+ * nothing on the step's head writes them), row = channel[k]. Per target zone the paths are taken in the caller's order.
+ * Every line is ONE rounded f64 operation in the order written, no fused multiply-add:
+ *   Tt = T[target];  Ts = source >= 0 ? T[source] : row[temp_chan]
+ *   controlled (open_chan non-NULL and open_chan[i] >= 0):  set = row[open_chan];  d = band / 2;  s = sense (+1.0 / -1.0)
+ *       e = s * (Tt - set)                        how far the target is beyond its setpoint
+ *       g = s * (Tt - Ts)                         how much the source helps
+ *       if      e > d  and g > min_delta           state = 1
+ *       else if state == 1 and (e < -d or g <= 0)  state = 0
+ *     (a NaN makes every comparison false: the state stays)
+ *   uncontrolled: open, whatever the state byte says; the byte is left as it is
+ *   closed:  q = 0.0, nothing is added to a0 / b0
+ *   open:    V = volume_gain * row[volume_chan]  (m3/s);  Tk = Ts + 273.15
+ *            rho = 101325 * 28.97 / (8314.46261815324 * Tk);  cp = 1002.7370 + 1.2324e-2 * Tk;  m = (rho * V) * cp
+ *                                                 (exactly the expressions and grouping of step 3 of heat_zone_loads)
+ *            mt = m * Ts;  a0[target] = a0[target] + mt;  b0[target] = b0[target] + m
+ *            dT = Ts - Tt;  q = m * dT            (W: what the path brings the target at the start of the step)
+ *   path_q[k * n_paths + i] = q;  sum_q[i] = sum_q[i] + q;  steps_open[i] += open;  switches[i] += (state after != before)
+ * sense = +1 is a cooling vent (it wants a source colder than the target, which is above its setpoint), -1 a heating vent.
+ * path_q, the accumulators and state are in the caller's path order. The terms hold for all n_sub sub-timesteps of the step,
+ * as every other a0 / b0 term does: ideal loads see them. EVERY source is read as it was at the START of the step, whatever
+ * the order of the zones: a chain A -> B -> C does not propagate within a step. An uncontrolled path counts as open in
+ * steps_open and never switches. The accumulators add onto what the caller passes in, as ap_sum does, and state carries the
+ * controllers over a cut: a series of k steps followed by one of n - k with the returned arrays gives the bits of the series
+ * of n. state == NULL: every controlled path starts closed and the states are not returned. n_sub == 0 still evaluates the
+ * paths of every step. A term that turns a zone's a0 or b0 into NaN (a NaN volume on an open path) is a numerical failure of
+ * that step: HEAT_N_NAN_ZONE, heat_batch_failed_surface names the zone, as for the zone loads; path_q rows, accumulators and
+ * states from the failed step on are unspecified, as the trace is.
+ * heat_air_paths_check (host-only; it also builds and verifies the tables the march uploads) and
+ * heat_batch_march_series_air run the same checks before any device work; every message names "air path i": a negative
+ * count, a NULL array a positive count needs (target, source, volume_chan; sense, band and min_delta where some path is
+ * controlled), source == target, a band, min_delta or volume_gain that is not finite, a negative band or min_delta, a sense
+ * other than +1 / -1 on a controlled path, a state byte above 1 -> HEAT_E_INVALID_ARG; a zone outside [0, n_zones) (a source
+ * outside [-1, n_zones)), a volume channel outside [0, n_channels), an open channel outside [-1, n_channels), a source of -1
+ * without a temperature channel in [0, n_channels), a temperature channel other than -1 on a path whose source is a zone (an
+ * input has ONE source) -> HEAT_E_SIZE. Sharded batches are refused as by the series; weather sites need nothing.
+ * heat_batch_march_series_air with air == NULL or n_paths == 0 is heat_batch_march_series_gains exactly (same launches, same
+ * bits); path_q is nullable, and an array that is not asked for costs no traffic and changes no bit of the others.
+ */
+typedef struct heat_air_paths {
+    int64_t n_paths;
+    const int32_t *target;        /* [n_paths] zone that receives the air */
+    const int32_t *source;        /* [n_paths] zone the air comes from, or -1: supply air at row[temp_chan] */
+    const int32_t *temp_chan;     /* [n_paths] nullable when no source is -1; must be -1 where source >= 0 */
+    const int32_t *volume_chan;   /* [n_paths] m3/s */
+    const double  *volume_gain;   /* [n_paths] nullable = 1 */
+    const int32_t *open_chan;     /* [n_paths] nullable / -1: uncontrolled, always open; else the target's setpoint, C */
+    const int8_t  *sense;         /* [n_paths] +1 cooling (wants a colder source), -1 heating; read only where controlled */
+    const double  *band;          /* [n_paths] K, >= 0; read only where controlled */
+    const double  *min_delta;     /* [n_paths] K, >= 0; read only where controlled */
+    uint8_t *state;               /* [n_paths] in/out, nullable (= all closed): 0 closed, 1 open */
+    double  *sum_q;               /* [n_paths] in/out, nullable: sum over the steps of q, W */
+    int64_t *steps_open;          /* [n_paths] in/out, nullable */
+    int64_t *switches;            /* [n_paths] in/out, nullable */
+} heat_air_paths;
+
+int heat_air_paths_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_air_paths *air); /* host-only */
+int heat_batch_march_series_air(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                const heat_solar_gains *gains /* nullable */, const heat_zone_loads *l /* nullable */,
+                                heat_air_paths *air /* nullable */, heat_ideal_loads *il /* nullable */,
+                                heat_series_report *r /* nullable */, double *trace, double *applied, double *ideal_q,
+                                double *transmitted, double *path_q /* [n_steps][n_paths], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -50,6 +50,12 @@ pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub b
     pub n_entries: i64, pub en_surface: *const i64, pub en_side: *const u8, pub en_aperture: *const i32,
     pub en_beam: *const f64, pub en_diffuse: *const f64,
 }
+// heat_air_paths: air that moves between zones, and vents controlled on the state of both of their ends
+#[repr(C)] pub struct HeatAirPaths {
+    pub n_paths: i64, pub target: *const i32, pub source: *const i32, pub temp_chan: *const i32, pub volume_chan: *const i32,
+    pub volume_gain: *const f64, pub open_chan: *const i32, pub sense: *const i8, pub band: *const f64, pub min_delta: *const f64,
+    pub state: *mut u8, pub sum_q: *mut f64, pub steps_open: *mut i64, pub switches: *mut i64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -89,6 +95,12 @@ extern "C" {
                                          gains: *const HeatSolarGains, l: *const HeatZoneLoads, il: *mut HeatIdealLoads,
                                          r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64, ideal_q: *mut f64,
                                          transmitted: *mut f64, failed_step: *mut i32) -> c_int;
+    // air paths of a series: zone-to-zone mixing and controlled vents, formed on the device at every step
+    pub fn heat_air_paths_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, air: *const HeatAirPaths) -> c_int;
+    pub fn heat_batch_march_series_air(b: *mut HeatBatch, s: *const HeatSeries, sky: *const HeatSky,
+                                       gains: *const HeatSolarGains, l: *const HeatZoneLoads, air: *mut HeatAirPaths,
+                                       il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
+                                       ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, failed_step: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

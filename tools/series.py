@@ -43,23 +43,32 @@ apertures, 900 k receivers, 9 M entries) two legs, alternated in the same way:
 beside leg D (the same series without the receivers: their input from the shared channels like everybody's), and writes
 profiles/series_gains.json: ms per step of each, J / H, a series of ONE step of each, J - D once the calls are set up, the
 bytes a step of k_series_solar_gains and of leg J's k_series_inputs moves.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains]
+With --air (heat_batch_march_series_air; the model, channels, loads and probes of leg D; the zones taken ten to a building:
+a doorway — two paths — between neighbouring zones of a building, 1.8 paths per zone, and one controlled outdoor vent per
+zone, a cooling vent on the outdoor temperature channel) two legs, alternated in the same way:
+  D  leg D itself: the series with loads and no paths
+  A  the same series with the air paths
+and writes profiles/series_air.json: ms per step of each, A - D, a series of ONE step of each, and — where the kernel trace of
+one A series has been taken (--one-series --air under rocprofv3 --kernel-trace --stats, a run of its own) —
+k_series_air_paths beside the same trace's k_series_zone_loads and whether A <= 1.05 (D + k_series_air_paths).
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
                                                      with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
-                                                     a series of leg J"""
+                                                     a series of leg J; with --air a series of leg A"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, modeldict as mdl, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, air_paths as apm, modeldict as mdl, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
 SKY = "--sky" in sys.argv
 GAINS = "--gains" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS
+AIR = "--air" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -214,6 +223,28 @@ if GAINS:
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace)) and np.all(np.isfinite(transmitted))
         return dt * 1e3 / steps
+if AIR:
+    # three more channels: the volume through a doorway, through a vent (m3/s), the vents' cooling setpoint (C); the supply
+    # air of a vent is leg D's outdoor temperature channel
+    c_air = channel.shape[1]
+    channel = np.concatenate([channel, rng.uniform(0.02, 0.10, (STEPS, 1)), rng.uniform(0.0, 0.05, (STEPS, 1)),
+                              rng.uniform(19.0, 23.0, (STEPS, 1))], axis=1)
+    left = np.flatnonzero((np.arange(Z) % 10 != 9) & (np.arange(Z) + 1 < Z)).astype(np.int32)
+    doors = apm.doorway(left, left + 1, c_air, rng.uniform(0.5, 1.5, len(left)))
+    vents = dict(target=np.arange(Z, dtype=np.int32), source=np.full(Z, -1, np.int32), temp_chan=np.full(Z, N_CHANNELS + 2, np.int32),
+                 volume_chan=np.full(Z, c_air + 1, np.int32), volume_gain=rng.uniform(0.5, 1.5, Z), open_chan=np.full(Z, c_air + 2, np.int32),
+                 sense=np.ones(Z, np.int8), band=np.full(Z, 0.5), min_delta=np.full(Z, 1.0))
+    air_args = apm.concat(doors, vents)
+    NP = len(air_args["target"])
+
+    def leg_air(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, air = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                            air=air_args, **drives)
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace)) and np.all(np.isfinite(air["path_q"]))
+        return dt * 1e3 / steps, air
 if REPORT:
     # the envelope of zone z: both faces of the walls whose back faces it (uniform_massive: all of a zone's walls, contiguous)
     assert np.all(np.diff(md["back_zone"]) >= 0) and np.all(md["back_kind"] == mdl.SPACE)
@@ -407,6 +438,36 @@ with HeatBatch(md) as b:
                   "without the set-up J %.3f, D %.3f, J - D = %+.3f (H without its first row %.3f) (%d steps, median of %d rounds)" % (
                       n_sub, H, HH, J, D, J / H, J / (H - HH), H1, J1, D1, Js, Ds, Js - Ds, Hs, STEPS, ROUNDS), flush=True)
             continue
+        if AIR:
+            leg_air(b, w, n_sub, min(STEPS, 10))  # warm-up
+            if ONE:
+                print("one series with air paths: A %.3f ms per step" % leg_air(b, w, n_sub, STEPS)[0])
+                continue
+            leg_d(b, w, n_sub, min(STEPS, 10))
+            d, a, d1, a1 = [], [], [], []
+            for r in range(ROUNDS):
+                d.append(leg_d(b, w, n_sub, STEPS))
+                x, air = leg_air(b, w, n_sub, STEPS)
+                a.append(x)
+                d1.append(leg_d(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                a1.append(leg_air(b, w, n_sub, 1)[0])
+            D, A, D1, A1 = (float(np.median(v)) for v in (d, a, d1, a1))
+            Ds, As = (D * STEPS - D1) / (STEPS - 1), (A * STEPS - A1) / (STEPS - 1)  # per step once the call is set up
+            vent = air_args["open_chan"] >= 0
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                D_series_with_loads_ms=D, A_series_with_air_paths_ms=A, A_minus_D_ms=A - D, A_over_D=A / D,
+                D_series_of_one_step_ms=D1, A_series_of_one_step_ms=A1, A_minus_D_series_of_one_step_ms=A1 - D1,
+                D_without_setup_ms=Ds, A_without_setup_ms=As, A_minus_D_without_setup_ms=As - Ds,
+                paths=NP, paths_per_zone=NP / Z, controlled=int(vent.sum()),
+                last_series=dict(vent_steps_open_share=float(air["steps_open"][vent].mean() / STEPS),
+                                 vents_that_switched=int((air["switches"][vent] > 0).sum())),
+                all_rounds=dict(D=d, A=a, D_one_step=d1, A_one_step=a1))
+            print("n_sub %2d: D loads %.3f ms/step, A with %d air paths %.3f -> A - D = %+.3f ms, A / D = %.4f; a series of one step: "
+                  "D %.2f ms, A %.2f ms -> per step without the set-up D %.3f, A %.3f, A - D = %+.3f; vents open in %.0f %% of their "
+                  "steps, %d of %d switched (%d steps, median of %d rounds)" % (
+                      n_sub, D, NP, A, A - D, A / D, D1, A1, Ds, As, As - Ds, 100 * air["steps_open"][vent].mean() / STEPS,
+                      int((air["switches"][vent] > 0).sum()), int(vent.sum()), STEPS, ROUNDS), flush=True)
+            continue
         if REPORT:
             if ONE:
                 leg = dict(zones=leg_f, nodes=leg_g)
@@ -505,9 +566,31 @@ if GAINS and not ONE:
         kt["rate_over_k_series_inputs"] = kt["k_series_solar_gains"]["TB_per_s"] / kt["k_series_inputs"]["TB_per_s"]
         kt["expectation_rate_at_least_0_95_of_k_series_inputs"] = bool(kt["rate_over_k_series_inputs"] >= 0.95)
         result["kernel_trace_of_one_J_series"] = kt
+if AIR and not ONE:
+    # the kernel trace of one A series (--one-series --air under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: k_series_air_paths per step beside the same trace's k_series_zone_loads, and the expectation
+    # A <= 1.05 (D + k_series_air_paths)
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_air_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_air_paths", "k_series_zone_loads")}
+        kt = dict(k_series_air_paths_us_per_step=us["k_series_air_paths"], k_series_zone_loads_us_per_step=us["k_series_zone_loads"],
+                  air_paths_over_zone_loads=us["k_series_air_paths"] / us["k_series_zone_loads"], calls=int(rows["k_series_air_paths"]["Calls"]))
+        for leg in result["legs"].values():
+            leg["expectation_A_at_most_1_05_of_D_plus_the_kernel"] = bool(
+                leg["A_series_with_air_paths_ms"] <= 1.05 * (leg["D_series_with_loads_ms"] + us["k_series_air_paths"] * 1e-3))
+        result["kernel_trace_of_one_A_series"] = kt
+        print("kernel trace: k_series_air_paths %.2f us per step, k_series_zone_loads %.2f (ratio %.2f); A <= 1.05 (D + kernel): %s" % (
+            us["k_series_air_paths"], us["k_series_zone_loads"], kt["air_paths_over_zone_loads"],
+            {k: v["expectation_A_at_most_1_05_of_D_plus_the_kernel"] for k, v in result["legs"].items()}))
+    else:
+        print("no kernel trace at %s: the expectation A <= 1.05 (D + k_series_air_paths) is not evaluated" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
