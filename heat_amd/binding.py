@@ -133,6 +133,18 @@ class AirPaths(C.Structure):
                 ("state", C.POINTER(C.c_uint8)), ("sum_q", _dp), ("steps_open", _i64p), ("switches", _i64p)]
 
 
+_SHADE_F64 = ("sh_normal_x", "sh_normal_y", "sh_normal_z", "sh_right_x", "sh_right_y", "sh_right_z", "sh_up_x", "sh_up_y", "sh_up_z",
+              "sh_width", "sh_height", "overhang_depth", "overhang_gap", "fin_pos_depth", "fin_pos_gap", "fin_neg_depth", "fin_neg_gap",
+              "diffuse_factor", "ground_factor")
+
+
+class Shades(C.Structure):
+    """heat_shades (include/heat_amd.h): overhangs, side fins and horizon profiles, and the sides and apertures they shade"""
+    _fields_ = ([("n_shades", C.c_int64), ("sh_surface", _i64p)] + [(name, _dp) for name in _SHADE_F64] +
+                [("sh_horizon", _i32p), ("n_horizons", C.c_int64), ("horizon_tan2", _dp), ("front_shade", _i32p),
+                 ("back_shade", _i32p), ("aperture_shade", _i32p)])
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -184,6 +196,11 @@ SYMBOLS = [
     ("heat_batch_march_series_air", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains), C.POINTER(ZoneLoads),
                                               C.POINTER(AirPaths), C.POINTER(IdealLoads), C.POINTER(Report), _dp, _dp, _dp, _dp, _dp,
                                               _i32p]),
+    ("heat_shades_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains),
+                                    C.POINTER(Shades)]),
+    ("heat_batch_march_series_shaded", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(Shades), C.POINTER(SolarGains),
+                                                 C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads), C.POINTER(Report),
+                                                 _dp, _dp, _dp, _dp, _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -334,7 +351,7 @@ def make_desc(md):
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
-                     "heat_air_paths_check",
+                     "heat_air_paths_check", "heat_shades_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -914,6 +931,88 @@ def air_paths_check(md, air, n_sites=1, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+def make_shades(surface=(), normal=None, right=None, up=None, width=(), height=(), overhang_depth=None, overhang_gap=None,
+                fin_pos_depth=None, fin_pos_gap=None, fin_neg_depth=None, fin_neg_gap=None, diffuse_factor=None, ground_factor=None,
+                horizon=None, horizon_tan2=None, front_shade=None, back_shade=None, aperture_shade=None):
+    """Builds a heat_shades. Returns (shades, keepalive).
+    surface          [n_shades] a surface of the shade's weather site (its site's sky record is read)
+    normal, right, up   (x, y, z) each, [n_shades]: the outward normal n of the shaded plane, its in-plane horizontal axis u
+                     (to the right seen from outside) and its in-plane upward axis v (shading.frame_of builds u and v)
+    width, height    [n_shades] m, > 0
+    overhang_depth, overhang_gap, fin_pos_depth, fin_pos_gap, fin_neg_depth, fin_neg_gap   [n_shades] m, >= 0; None: zeros
+    diffuse_factor, ground_factor   [n_shades]; None: NULL = 1
+    horizon          [n_shades] the shade's horizon profile, -1: none; None: NULL = none
+    horizon_tan2     [n_horizons, 16] (shading.horizon_tan2)
+    front_shade, back_shade   [n_surfaces] the shade of the side's sky-driven solar input, -1: none; None: NULL
+    aperture_shade   [n_apertures] the shade of an aperture of the solar gains, -1: none; None: NULL"""
+    sh = Shades()
+    n = len(np.asarray(surface).reshape(-1))
+    sh.n_shades = n
+    keep = {}
+
+    def put(name, value, dtype, shape, what):
+        a = np.ascontiguousarray(value, dtype=dtype)
+        if shape is not None and a.reshape(-1).shape != shape:
+            raise ValueError("shades %s: %s for %s" % (name, a.shape, what))
+        keep[name] = a
+        setattr(sh, name, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if a.size else None)
+
+    put("sh_surface", surface, np.int64, (n,), "%d shades" % n)
+    for prefix, vec in (("sh_normal", normal), ("sh_right", right), ("sh_up", up)):
+        vec = vec if vec is not None else ((), (), ())
+        for axis, a in zip("xyz", vec):
+            put("%s_%s" % (prefix, axis), a, np.float64, (n,), "%d shades" % n)
+    put("sh_width", width, np.float64, (n,), "%d shades" % n)
+    put("sh_height", height, np.float64, (n,), "%d shades" % n)
+    for name, v in (("overhang_depth", overhang_depth), ("overhang_gap", overhang_gap), ("fin_pos_depth", fin_pos_depth),
+                    ("fin_pos_gap", fin_pos_gap), ("fin_neg_depth", fin_neg_depth), ("fin_neg_gap", fin_neg_gap)):
+        put(name, np.zeros(n) if v is None else v, np.float64, (n,), "%d shades" % n)
+    for name, v in (("diffuse_factor", diffuse_factor), ("ground_factor", ground_factor)):
+        if v is not None:
+            put(name, v, np.float64, (n,), "%d shades" % n)
+    if horizon is not None:
+        put("sh_horizon", horizon, np.int32, (n,), "%d shades" % n)
+    tan2 = np.ascontiguousarray(horizon_tan2 if horizon_tan2 is not None else np.zeros((0, 16)), dtype=np.float64)
+    if tan2.ndim != 2 or tan2.shape[1] != 16:
+        raise ValueError("shades horizon_tan2: %s, not [n_horizons, 16]" % (tan2.shape,))
+    sh.n_horizons = len(tan2)
+    put("horizon_tan2", tan2, np.float64, None, "")
+    for name, v in (("front_shade", front_shade), ("back_shade", back_shade), ("aperture_shade", aperture_shade)):
+        if v is not None:
+            put(name, np.asarray(v).reshape(-1), np.int32, None, "")
+    return sh, keep
+
+
+def _shades_fit(hkeep, n_surfaces, n_apertures):
+    for k in ("front_shade", "back_shade"):
+        if k in hkeep and hkeep[k].shape != (n_surfaces,):
+            raise ValueError("shades %s: %s for %d surfaces" % (k, hkeep[k].shape, n_surfaces))
+    if "aperture_shade" in hkeep and n_apertures is not None and hkeep["aperture_shade"].shape != (n_apertures,):
+        raise ValueError("shades aperture_shade: %s for %d apertures" % (hkeep["aperture_shade"].shape, n_apertures))
+
+
+def shades_check(md, shades, sky=None, gains=None, n_sites=1, lib=None, **series):
+    """heat_shades_check: everything about the shades of a series that needs no device (series arguments as
+    HeatBatch.march_series; sky: the arguments of make_sky, or None; gains: those of make_solar_gains, or None; shades: those
+    of make_shades, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    k = None
+    if sky is not None or gains is not None:
+        k, kkeep = make_sky(**_sky_for_gains(sky, _model_normals(md), int(md["n_surfaces"])))
+        _sky_fits(kkeep, s.n_steps, int(n_sites), int(md["n_surfaces"]))
+    g, gkeep = make_solar_gains(**gains) if gains is not None else (None, None)
+    h, hkeep = make_shades(**shades) if shades is not None else (None, None)
+    if h is not None:
+        _shades_fit(hkeep, int(md["n_surfaces"]), g.n_apertures if g is not None else None)
+    rc = L.heat_shades_check(C.byref(desc), int(n_sites), C.byref(s), C.byref(k) if k is not None else None,
+                             C.byref(g) if g is not None else None, C.byref(h) if h is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1027,7 +1126,7 @@ class HeatBatch:
         _check(self._L.heat_batch_synchronize(self._h))
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
-                     air=None, path_q=True, **series):
+                     air=None, path_q=True, shades=None, sunlit=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1055,7 +1154,16 @@ class HeatBatch:
         controlled vents, formed on the device at every step from the zone temperatures it holds. Returns what the same call
         without air returns plus one dict: path_q [n_steps, n_paths] (empty with path_q=False), state, and of sum_q,
         steps_open, switches those in stats (pass state and them on to the next series) — one more element of the tuple, or
-        the key "air" of the dict."""
+        the key "air" of the dict.
+        shades (a dict of make_shades' arguments; sky carries the records and the mode bits of the shaded sides, gains the
+        shaded apertures): heat_batch_march_series_shaded — the sunlit fraction of overhangs, fins and horizons, formed on the
+        device at every step. Returns what the same call without shades returns plus sunlit [n_steps, n_shades] (empty with
+        sunlit=False): one more element of the tuple, or the key "sunlit" of the dict."""
+        if shades is not None:
+            if gains is not None or sky is None or sky.get("mode") is None:
+                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
+            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q, shades,
+                                          sunlit)
         if air is not None:
             if gains is not None:
                 sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
@@ -1148,7 +1256,7 @@ class HeatBatch:
         return out
 
     def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None, air=None,
-                          want_path_q=True):
+                          want_path_q=True, shades=None, want_sunlit=True):
         if report is None and ideal is None and not (want_trace and want_applied):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1179,6 +1287,17 @@ class HeatBatch:
         if air is not None:
             a, akeep = make_air_paths(**air)
             q = np.zeros((s.n_steps if want_path_q else 0, a.n_paths))
+        if shades is not None:
+            h, hkeep = make_shades(**shades)
+            _shades_fit(hkeep, self.n_surfaces, g.n_apertures if gains is not None else None)
+            lit = np.zeros((s.n_steps if want_sunlit else 0, h.n_shades))
+            rc = self._L.heat_batch_march_series_shaded(self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h),
+                                                        C.byref(g) if gains is not None else None, args[0],
+                                                        C.byref(a) if air is not None else None, *args[1:],
+                                                        transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
+                                                        q.ctypes.data_as(_dp) if air is not None and q.size else None,
+                                                        lit.ctypes.data_as(_dp) if lit.size else None, C.byref(failed))
+        elif air is not None:
             rc = self._L.heat_batch_march_series_air(self._h, C.byref(s), C.byref(k) if k is not None else None,
                                                      C.byref(g) if gains is not None else None, args[0], C.byref(a), *args[1:],
                                                      transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
@@ -1204,11 +1323,14 @@ class HeatBatch:
                 out.update(transmitted=transmitted, ap_sum=gkeep["ap_sum"])
             if air is not None:
                 out["air"] = dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep})
+            if shades is not None:
+                out["sunlit"] = lit
             return out
         out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
         out = out + ((rep,) if report is not None else ())
         out = out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
-        return out + ((dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep}),) if air is not None else ())
+        out = out + ((dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep}),) if air is not None else ())
+        return out + ((lit,) if shades is not None else ())
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -292,6 +292,7 @@ struct heat_batch {
     // weather sites (heat_batch_create_sites): h_weather / d_weather hold n_sites x weather_cap records, site-major
     int32_t n_sites = 1;
     DevBuf<int32_t> d_site;            // [S] site of every device surface (layout.hpp, SideArrays::site)
+    std::vector<int32_t> h_site;       // its host copy (empty for a single-site batch): a shade's site is resolved on the host
 
     // heat_batch_march on a caller-owned state: compact transfers through pinned staging, host gathers / scatters
     // on a thread pool ("Data at the boundary")
@@ -393,6 +394,7 @@ int build(heat_batch *b, const heat_batch_desc *d, const heat_batch_options &opt
     }
     b->n_sites = p.n_sites;
     if (!p.dev_site.empty()) HIP_TRY(b->d_site.upload(p.dev_site));
+    b->h_site = p.dev_site;
     const int64_t S = p.n_surf, Z = p.n_zones;
     b->n_surf = S;
     b->n_zones = Z;
@@ -1077,6 +1079,19 @@ struct AirDev {
     DevBuf<double> sum_q;      // [NP]
     DevBuf<int64_t> i64[2];    // steps_open, switches
     DevBuf<double> path_q;     // [n_steps][NP]
+};
+
+// The device copies of the shades of a series (heat_shades): the shade table (plan.hpp, ShadeTables), the site and horizon
+// numbers, the horizon profiles, the step's sunlit fractions, the shade numbers of the sides in device surface order and of
+// the apertures, the sunlit rows. Declared beside SkyDev.
+struct ShadeDev {
+    DevBuf<double> tab;       // [kShadeRows][NS]
+    DevBuf<int32_t> i32;      // site [NS] | horizon [NS]
+    DevBuf<double> tan2;      // [NH][16]
+    DevBuf<double> f;         // [NS]
+    DevBuf<int32_t> side;     // [2][S]
+    DevBuf<int32_t> aperture; // [NA]
+    DevBuf<double> sunlit;    // [n_steps][NS]
 };
 
 template <typename T>
@@ -2062,11 +2077,12 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 // heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
 // il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit,
-// and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path.
+// and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path, and shades == nullptr, or no shade.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
                              double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
                              double *ideal_q = nullptr, const heat_sky *sky = nullptr, const heat_solar_gains *gains = nullptr,
-                             double *transmitted = nullptr, heat_air_paths *air = nullptr, double *path_q = nullptr) {
+                             double *transmitted = nullptr, heat_air_paths *air = nullptr, double *path_q = nullptr,
+                             const heat_shades *shades = nullptr, double *sunlit = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2097,6 +2113,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     rc = check_solar_gains(b->n_surf, s, sky, gains, heat::last_error());
     if (rc) return rc;
     const int64_t NA = gains ? gains->n_apertures : 0;  // (entries need an aperture: there are none without)
+    rc = check_shades(b->n_surf, s, sky, gains, shades, heat::last_error());
+    if (rc) return rc;
+    const int64_t NS = shades ? shades->n_shades : 0;  // (a side or aperture needs a shade to refer to: none is shaded without)
     rc = check_air_paths(b->n_zones, s->n_channels, air, heat::last_error());
     if (rc) return rc;
     const int64_t NP = air ? air->n_paths : 0;
@@ -2221,6 +2240,27 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
         }
     }
+    // shades: the table as structure of arrays, every shade's site, the shade numbers of the sides per DEVICE surface
+    ShadeTables sht;
+    std::vector<int32_t> h_shade_i32, h_shade_side;
+    if (NS > 0) {
+        build_shade_tables(shades, sht);
+        h_shade_i32.assign(2 * (size_t)NS, 0);
+        for (int64_t j = 0; j < NS; j++) {
+            h_shade_i32[j] = b->h_site.empty() ? 0 : b->h_site[b->h_dev_of[shades->sh_surface[j]]];
+            h_shade_i32[NS + j] = sht.horizon[j];
+        }
+        if ((sky_bits & 3) && (shades->front_shade || shades->back_shade)) {
+            const int64_t *orig_of = b->h_orig_of.data();
+            const int32_t *side_shade[2] = {shades->front_shade, shades->back_shade};
+            h_shade_side.assign(2 * (size_t)S, -1);
+            for (int a = 0; a < 2; a++) {
+                if (!side_shade[a]) continue;
+                int32_t *dst = h_shade_side.data() + (size_t)a * S;
+                b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) dst[d] = side_shade[a][orig_of[d]]; });
+            }
+        }
+    }
     // probes: (buffer, index) of every probed slot
     std::vector<uint8_t> h_pbuf((size_t)P);
     std::vector<uint32_t> h_pidx((size_t)P);
@@ -2301,6 +2341,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     SkyDev skd;
     GainsDev gnd;
     AirDev aird;
+    ShadeDev shd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2436,7 +2477,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         ild.n_sat_heating = idd.i64[2].p, ild.n_sat_cooling = idd.i64[3].p;
     }
     SeriesSky skyd{};
-    if (sky_bits || NA > 0)
+    if (sky_bits || NA > 0 || NS > 0)
         if ((rc = series_upload(skd.record, reinterpret_cast<const SkyRecord *>(sky->record), (size_t)n_steps * n_sites, "sky records")))
             return rc;
     if (sky_bits) {
@@ -2446,6 +2487,25 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         skyd.normal = skd.normal.p;
         skyd.site = b->n_sites > 1 ? b->d_site.p : nullptr;
         for (int a = 0; a < 4; a++) skyd.gain[a] = d_gain[a].p;
+    }
+    SeriesShades shdd{};
+    if (NS > 0) {
+        const int64_t NH = shades->n_horizons;
+        if ((rc = series_upload(shd.tab, sht.f64.data(), sht.f64.size(), "shade table"))) return rc;
+        if ((rc = series_upload(shd.i32, h_shade_i32.data(), h_shade_i32.size(), "shade table"))) return rc;
+        if ((rc = series_upload(shd.tan2, shades->horizon_tan2, 16 * (size_t)NH, "horizon profiles"))) return rc;
+        if ((rc = series_alloc(shd.f, (size_t)NS, "sunlit fractions"))) return rc;
+        if ((rc = series_upload(shd.side, h_shade_side.data(), h_shade_side.size(), "shade numbers"))) return rc;
+        if (NA > 0 && shades->aperture_shade && (rc = series_upload(shd.aperture, shades->aperture_shade, (size_t)NA, "shade numbers"))) return rc;
+        if (sunlit && (rc = series_alloc(shd.sunlit, (size_t)n_steps * NS, "sunlit fractions"))) return rc;
+        shdd.n = (int)NS;
+        shdd.site = shd.i32.p, shdd.horizon = shd.i32.p + NS;
+        shdd.tab = shd.tab.p;
+        shdd.tan2 = shd.tan2.p;
+        shdd.f = shd.f.p;
+        const ShadeFactors sf{shd.f.p, shd.tab.p + (size_t)SH_FD * NS, shd.tab.p + (size_t)SH_FG * NS};
+        skyd.shade = shd.side.p;
+        skyd.sf = sf;
     }
     SeriesApertures apd{};
     SeriesGains gnsd{};
@@ -2465,6 +2525,8 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         apd.normal = gnd.ap_f64.p, apd.coef = gnd.ap_f64.p + 3 * NA, apd.tau_scale = gnd.ap_f64.p + 9 * NA;
         apd.power = gnd.power.p;
         apd.sum = gnd.sum.p;
+        apd.shade = shd.aperture.p;
+        apd.sf = ShadeFactors{shd.f.p, shd.tab.p + (size_t)SH_FD * NS, shd.tab.p + (size_t)SH_FG * NS};
         gnsd.n_receivers = (int)gnt.rec.size();
         gnsd.rec = gnd.rec.p, gnsd.slice_off = gnd.slice_off.p, gnsd.ap = gnd.ap.p;
         gnsd.share = reinterpret_cast<const double2 *>(gnd.share.p);
@@ -2516,7 +2578,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> driven inputs -> sky -> solar gains -> the body of a march call of
+    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> driven inputs -> shades -> sky -> solar gains -> the body of a march call of
     // n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
@@ -2531,6 +2593,8 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
+        if (NS > 0)
+            launch_series_shading(skd.record.p + (size_t)k * n_sites, shdd, shd.sunlit.p ? shd.sunlit.p + (size_t)k * NS : nullptr, b->stream);
         if (sky_bits)
             launch_series_sky((int)S, skd.record.p + (size_t)k * n_sites, skyd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         if (NA > 0) {
@@ -2601,6 +2665,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (aird.i64[0].p) HIP_TRY(hipMemcpyAsync(air->steps_open, aird.i64[0].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
         if (aird.i64[1].p) HIP_TRY(hipMemcpyAsync(air->switches, aird.i64[1].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     }
+    if (shd.sunlit.p) HIP_TRY(hipMemcpyAsync(sunlit, shd.sunlit.p, (size_t)n_steps * NS * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2646,6 +2711,13 @@ int heat_batch_march_series_air(heat_batch *b, const heat_series *s, const heat_
                                 const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il, heat_series_report *r, double *trace,
                                 double *applied, double *ideal_q, double *transmitted, double *path_q, int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q);
+}
+
+int heat_batch_march_series_shaded(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
+                                   const heat_solar_gains *gains, const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il,
+                                   heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
+                                   double *path_q, double *sunlit, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

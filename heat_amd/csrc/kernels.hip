@@ -2327,6 +2327,64 @@ k_series_zone_loads(int n_zones, ZoneLoadsDev zl, const double *__restrict__ row
     if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
 }
 
+// k_series_shading — the sunlit fraction of every shade in one step (heat_shades, include/heat_amd.h), behind k_series_inputs
+// and before k_series_sky: one lane per shade. A lane reads its site's 64-byte record (of which it uses the sun vector), its
+// 19 rows of the shade table (structure of arrays: a wavefront reads lines) and, where it has a horizon profile, one tan2
+// element; it stores f for the shaded sides and apertures of k_series_sky / k_series_apertures to gather, and into the step's
+// row of `sunlit` where the caller takes one. The header's rule, every line one rounded operation in the order written, hence
+// no contraction; min and max are written as the comparisons the header gives, so that a NaN has one outcome. No atomics,
+// no LDS.
+__device__ __forceinline__ double shade_max(double a, double b) { return b > a ? b : a; }  // (the FIRST operand where false)
+__device__ __forceinline__ double shade_min(double a, double b) { return b < a ? b : a; }
+
+__global__ void __launch_bounds__(256)
+k_series_shading(const SkyRecord *__restrict__ records, SeriesShades sh, double *__restrict__ sunlit_row) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = sh.n;
+    if (j >= sh.n) return;
+    const SkyRecord &r = records[sh.site[j]];
+    const double sx = r.sun_x, sy = r.sun_y, sz = r.sun_z;
+    const double *const t = sh.tab + j;
+    const double c = (t[SH_NX * n] * sx + t[SH_NY * n] * sy) + t[SH_NZ * n] * sz;
+    const double us = (t[SH_UX * n] * sx + t[SH_UY * n] * sy) + t[SH_UZ * n] * sz;
+    const double vs = (t[SH_VX * n] * sx + t[SH_VY * n] * sy) + t[SH_VZ * n] * sz;
+    const double W = t[SH_W * n], H = t[SH_H * n];
+    // overhang
+    const double drop = (t[SH_OD * n] * vs) / c;
+    double s = drop - t[SH_OG * n];
+    s = shade_max(s, 0.0);
+    s = shade_min(s, H);
+    const double fv = vs > 0.0 ? (H - s) / H : 1.0;
+    // fins
+    const double ap = (t[SH_PD * n] * us) / c;
+    double wp = ap - t[SH_PG * n];
+    wp = shade_max(wp, 0.0);
+    wp = shade_min(wp, W);
+    const double nu = -us;
+    const double an = (t[SH_ND * n] * nu) / c;
+    double wn = an - t[SH_NG * n];
+    wn = shade_max(wn, 0.0);
+    wn = shade_min(wn, W);
+    const double sw = us > 0.0 ? wp : (us < 0.0 ? wn : 0.0);
+    const double fh = (W - sw) / W;
+    double f = fv * fh;
+    const int p = sh.horizon[j];
+    if (p >= 0) {
+        const double ax = fabs(sx), ay = fabs(sy);
+        const double T = 0.41421356237309503;
+        const int m = (int)(ay > T * ax) + (int)(ay > ax) + (int)(T * ay > ax);
+        const int sector = sx >= 0.0 ? (sy >= 0.0 ? m : 15 - m) : (sy >= 0.0 ? 7 - m : 8 + m);  // in [0, 16) whatever the sun holds
+        const double h2 = sx * sx + sy * sy;
+        const double z2 = sz * sz;
+        const bool lit = sz > 0.0 && z2 > sh.tan2[16 * (int64_t)p + sector] * h2;
+        if (!lit) f = 0.0;
+    }
+    if (!(c > 0.0)) f = 0.0;
+    sh.f[j] = f;
+    if (sunlit_row != nullptr) sunlit_row[j] = f;
+}
+
 // k_series_sky — the sky-driven inputs of one step (heat_sky, include/heat_amd.h), behind k_series_inputs and before the
 // body: one lane per device surface. A lane whose mode byte is 0 leaves after reading it; the others read their site's
 // 64-byte record of the step (the planner keeps the surfaces of a site together: a wavefront mostly reads one line) and
@@ -2345,8 +2403,17 @@ __device__ __forceinline__ void sky_side(int side, int d, int S, bool m_solar, b
     double solar = 0.0, rad_t = 0.0;
     if (m_solar) {
         const double c = (nx * r.sun_x + ny * r.sun_y) + nz * r.sun_z;
-        const double bm = c > 0.0 ? r.beam * c : 0.0;
-        double v = (bm + r.diffuse * fs) + r.ground * fg;
+        double bm = c > 0.0 ? r.beam * c : 0.0;
+        const int j = sky.shade != nullptr ? sky.shade[rec] : -1;  // (a kernel argument: without shades the branch is wave-uniform)
+        double v;
+        if (j >= 0) {  // heat_shades: the beam times the step's sunlit fraction, the other two parts times their constant factors
+            bm = bm * sky.sf.f[j];
+            const double dv = (r.diffuse * fs) * sky.sf.diffuse[j];
+            const double gv = (r.ground * fg) * sky.sf.ground[j];
+            v = (bm + dv) + gv;
+        } else {
+            v = (bm + r.diffuse * fs) + r.ground * fg;
+        }
         if (sky.gain[side]) v = v * sky.gain[side][d];
         if (mirror != nullptr) mirror[(side ? sl.solar_b : sl.solar_f)[d]] = v;
         solar = (side ? clamp_solar_back(v) : clamp_solar_front(v)) * side_alpha[rec];
@@ -2400,8 +2467,15 @@ k_series_apertures(const SkyRecord *__restrict__ records, SeriesApertures ap, do
     }
     const double tau_diffuse = ap.tau_scale[a], scale = ap.tau_scale[n + a];
     const double ib = r.beam * c;
-    const double pb = c > 0.0 ? (ib * t) * scale : 0.0;
-    const double id = r.diffuse * fs + r.ground * fg;
+    double pb = c > 0.0 ? (ib * t) * scale : 0.0;
+    const int j = ap.shade != nullptr ? ap.shade[a] : -1;  // (a kernel argument: without shades the branch is wave-uniform)
+    double id;
+    if (j >= 0) {  // heat_shades
+        pb = c > 0.0 ? pb * ap.sf.f[j] : 0.0;
+        id = (r.diffuse * fs) * ap.sf.diffuse[j] + (r.ground * fg) * ap.sf.ground[j];
+    } else {
+        id = r.diffuse * fs + r.ground * fg;
+    }
     const double pd = (id * tau_diffuse) * scale;
     const double p = pb + pd;
     ap.power[a] = make_double2(pb, pd);
@@ -3001,6 +3075,11 @@ void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sk
                        const SlotArrays &sl, double *mirror, hipStream_t st) {
     if (n_surf <= 0) return;
     hipLaunchKernelGGL(k_series_sky, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, records, sky, side_alpha, dyn, sl, mirror);
+}
+
+void launch_series_shading(const SkyRecord *records, const SeriesShades &sh, double *sunlit_row, hipStream_t st) {
+    if (sh.n <= 0) return;
+    hipLaunchKernelGGL(k_series_shading, dim3((sh.n + 255) / 256), dim3(256), 0, st, records, sh, sunlit_row);
 }
 
 void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st) {

@@ -83,12 +83,33 @@ void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in,
 struct alignas(16) SkyRecord {  // heat_sky_record
     double sun_x, sun_y, sun_z, beam, diffuse, ground, ir_sky, ir_ground;
 };
+// What a shaded consumer gathers (heat_shades): the step's sunlit fraction k_series_shading has just stored and the two
+// constant factors, rows of the shade table.
+struct ShadeFactors {
+    const double *f;        // [n_shades] the step's sunlit fraction of the beam
+    const double *diffuse;  // [n_shades] (ones where the caller gave none)
+    const double *ground;   // [n_shades]
+};
 struct SeriesSky {
     const uint8_t *mode;     // [S] in device surface order: bit 0 solar front, 1 solar back, 2 long-wave front, 3 long-wave back
     const double *normal;    // [3][S]: x, y, z of the front face's outward normal
     const int32_t *site;     // [S] (SideArrays::site); nullptr: site 0
     const double *gain[4];   // the series' gain arrays (SeriesInputs::gain); nullptr: 1
+    const int32_t *shade;    // [2][S] the shade of the front / back solar input, -1: none; nullptr: no side is shaded
+    ShadeFactors sf;
 };
+// Shades of a series step (heat_shades, include/heat_amd.h; table: plan.hpp, ShadeTables): launched behind
+// launch_series_inputs and before launch_series_sky, one lane per shade; only when there are shades.
+struct SeriesShades {
+    int n;
+    const int32_t *site;     // [n] the site whose record the shade reads
+    const int32_t *horizon;  // [n] horizon profile, -1: none
+    const double *tab;       // [kShadeRows][n]
+    const double *tan2;      // [n_horizons][16]
+    double *f;               // [n] out: the step's sunlit fraction
+};
+// records: the step's row of the record table, [n_sites]; sunlit_row: the step's row of sunlit, [n], or nullptr
+void launch_series_shading(const SkyRecord *records, const SeriesShades &sh, double *sunlit_row, hipStream_t st);
 // records: the step's row of the record table, [n_sites]
 void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
                        const SlotArrays &sl, double *mirror, hipStream_t st);
@@ -104,6 +125,8 @@ struct SeriesApertures {
     const double *tau_scale;  // [2][n]: tau_diffuse, scale
     double2 *power;           // [n] (Pb, Pd) of the step, W
     double *sum;              // [n] ap_sum; nullptr: not kept
+    const int32_t *shade;     // [n] the aperture's shade, -1: none; nullptr: no aperture is shaded
+    ShadeFactors sf;
 };
 struct SeriesGains {
     int n_receivers;

@@ -2083,6 +2083,104 @@ int check_solar_gains(int64_t n_surfaces, const heat_series *s, const heat_sky *
     return HEAT_OK;
 }
 
+// ---- shades of a series (include/heat_amd.h, heat_shades) ----
+namespace {
+struct ShadeColumn {
+    const double *v;
+    const char *name;
+    int rule;  // 0: finite, 1: finite and > 0, 2: finite and >= 0
+};
+}  // namespace
+
+int check_shades(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, const heat_shades *sh,
+                 std::string &err) {
+    if (!sh) return HEAT_OK;
+    const int64_t NS = sh->n_shades, NH = sh->n_horizons;
+    if (NS < 0 || NH < 0)
+        return failp(err, HEAT_E_INVALID_ARG, "negative count in shades (n_shades %lld, n_horizons %lld): no shade j, no horizon p", (long long)NS,
+                     (long long)NH);
+    if (NS > INT32_MAX || NH > INT32_MAX)
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 in shades (n_shades %lld, n_horizons %lld): shade j and horizon p are 32-bit",
+                     (long long)NS, (long long)NH);
+    const ShadeColumn col[17] = {{sh->sh_normal_x, "sh_normal_x", 0}, {sh->sh_normal_y, "sh_normal_y", 0}, {sh->sh_normal_z, "sh_normal_z", 0},
+                                 {sh->sh_right_x, "sh_right_x", 0},   {sh->sh_right_y, "sh_right_y", 0},   {sh->sh_right_z, "sh_right_z", 0},
+                                 {sh->sh_up_x, "sh_up_x", 0},         {sh->sh_up_y, "sh_up_y", 0},         {sh->sh_up_z, "sh_up_z", 0},
+                                 {sh->sh_width, "sh_width", 1},       {sh->sh_height, "sh_height", 1},
+                                 {sh->overhang_depth, "overhang_depth", 2}, {sh->overhang_gap, "overhang_gap", 2},
+                                 {sh->fin_pos_depth, "fin_pos_depth", 2},   {sh->fin_pos_gap, "fin_pos_gap", 2},
+                                 {sh->fin_neg_depth, "fin_neg_depth", 2},   {sh->fin_neg_gap, "fin_neg_gap", 2}};
+    const ShadeColumn factor[2] = {{sh->diffuse_factor, "diffuse_factor", 0}, {sh->ground_factor, "ground_factor", 0}};
+    if (NS > 0) {
+        if (!sh->sh_surface) return failp(err, HEAT_E_INVALID_ARG, "shade 0: sh_surface is NULL (n_shades %lld)", (long long)NS);
+        for (const ShadeColumn &c : col)
+            if (!c.v) return failp(err, HEAT_E_INVALID_ARG, "shade 0: %s is NULL (n_shades %lld)", c.name, (long long)NS);
+        if (s->n_steps > 0 && (!sky || !sky->record))
+            return failp(err, HEAT_E_INVALID_ARG, "shade 0: its site's record is read, but %s is NULL (n_steps %d)", sky ? "sky->record" : "sky",
+                         s->n_steps);
+    }
+    if (NH > 0 && !sh->horizon_tan2) return failp(err, HEAT_E_INVALID_ARG, "horizon 0: horizon_tan2 is NULL (n_horizons %lld)", (long long)NH);
+    for (int64_t p = 0; p < NH; p++)
+        for (int q = 0; q < 16; q++) {
+            const double t = sh->horizon_tan2[16 * p + q];
+            if (!std::isfinite(t) || t < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "horizon %lld: tan2[%d] = %g is %s", (long long)p, q, t, std::isfinite(t) ? "negative" : "not finite");
+        }
+    for (int64_t j = 0; j < NS; j++) {
+        for (const ShadeColumn &c : col) {
+            const double v = c.v[j];
+            if (!std::isfinite(v)) return failp(err, HEAT_E_INVALID_ARG, "shade %lld: %s = %g is not finite", (long long)j, c.name, v);
+            if (c.rule == 1 && !(v > 0.0)) return failp(err, HEAT_E_INVALID_ARG, "shade %lld: %s = %g is not positive", (long long)j, c.name, v);
+            if (c.rule == 2 && v < 0.0) return failp(err, HEAT_E_INVALID_ARG, "shade %lld: %s = %g is negative", (long long)j, c.name, v);
+        }
+        for (const ShadeColumn &c : factor)
+            if (c.v && !std::isfinite(c.v[j]))
+                return failp(err, HEAT_E_INVALID_ARG, "shade %lld: %s = %g is not finite", (long long)j, c.name, c.v[j]);
+        if (sh->sh_surface[j] < 0 || sh->sh_surface[j] >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "shade %lld: surface %lld outside [0, %lld)", (long long)j, (long long)sh->sh_surface[j],
+                         (long long)n_surfaces);
+        if (sh->sh_horizon && (sh->sh_horizon[j] < -1 || sh->sh_horizon[j] >= NH))
+            return failp(err, HEAT_E_SIZE, "shade %lld: horizon %d outside [-1, %lld)", (long long)j, sh->sh_horizon[j], (long long)NH);
+    }
+    const int32_t *side_shade[2] = {sh->front_shade, sh->back_shade};
+    for (int side = 0; side < 2; side++) {
+        if (!side_shade[side]) continue;
+        for (int64_t q = 0; q < n_surfaces; q++) {
+            const int32_t j = side_shade[side][q];
+            if (j == -1) continue;
+            if (j < -1 || j >= NS)
+                return failp(err, HEAT_E_SIZE, "surface %lld: %s shade %d outside [-1, %lld)", (long long)q, side ? "back" : "front", j, (long long)NS);
+            if (!sky || !sky->mode || !(sky->mode[q] >> side & 1))
+                return failp(err, HEAT_E_SIZE, "surface %lld: %s shade %d, but the solar %s input is not driven by the sky (mode bit %d is not set)",
+                             (long long)q, side ? "back" : "front", j, side ? "back" : "front", side);
+        }
+    }
+    if (sh->aperture_shade) {
+        if (!g) return failp(err, HEAT_E_INVALID_ARG, "aperture 0: aperture_shade without solar gains (gains is NULL)");
+        for (int64_t a = 0; a < g->n_apertures; a++) {
+            const int32_t j = sh->aperture_shade[a];
+            if (j < -1 || j >= NS)
+                return failp(err, HEAT_E_SIZE, "aperture %lld: shade %d outside [-1, %lld)", (long long)a, j, (long long)NS);
+        }
+    }
+    return HEAT_OK;
+}
+
+void build_shade_tables(const heat_shades *sh, ShadeTables &t) {
+    t.f64.clear();
+    t.horizon.clear();
+    const int64_t NS = sh ? sh->n_shades : 0;
+    if (NS <= 0) return;
+    const double *row[kShadeRows] = {sh->sh_normal_x, sh->sh_normal_y, sh->sh_normal_z, sh->sh_right_x, sh->sh_right_y, sh->sh_right_z,
+                                     sh->sh_up_x, sh->sh_up_y, sh->sh_up_z, sh->sh_width, sh->sh_height, sh->overhang_depth,
+                                     sh->overhang_gap, sh->fin_pos_depth, sh->fin_pos_gap, sh->fin_neg_depth, sh->fin_neg_gap,
+                                     sh->diffuse_factor, sh->ground_factor};
+    t.f64.assign((size_t)kShadeRows * NS, 1.0);
+    for (int a = 0; a < kShadeRows; a++)
+        if (row[a]) std::copy(row[a], row[a] + NS, t.f64.begin() + (size_t)a * NS);
+    t.horizon.assign((size_t)NS, -1);
+    if (sh->sh_horizon) std::copy(sh->sh_horizon, sh->sh_horizon + NS, t.horizon.begin());
+}
+
 static inline int64_t gain_key(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, int64_t i) {
     const int64_t q = g->en_surface[i];
     return (int64_t)g->en_side[i] * n_surfaces + (dev_of ? (int64_t)dev_of[q] : q);
@@ -2430,6 +2528,22 @@ int heat_solar_gains_check(const heat_batch_desc *desc, int32_t n_sites, const h
     heat::SolarGainTables t;
     heat::build_solar_gain_tables(desc->n_surfaces, nullptr, gains, t);
     return heat::check_solar_gain_tables(desc->n_surfaces, nullptr, gains, t, heat::last_error());
+}
+
+int heat_shades_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                      const heat_solar_gains *gains, const heat_shades *shades) {
+    int rc = heat_solar_gains_check(desc, n_sites, s, sky, gains);
+    if (rc) return rc;
+    rc = heat::check_shades(desc->n_surfaces, s, sky, gains, shades, heat::last_error());
+    if (rc || !shades) return rc;
+    // ... and the table the march would upload, laid out and checked against the counts (this is the build the sanitizers see)
+    heat::ShadeTables t;
+    heat::build_shade_tables(shades, t);
+    const size_t NS = shades->n_shades > 0 ? (size_t)shades->n_shades : 0;
+    if (t.f64.size() != heat::kShadeRows * NS || t.horizon.size() != NS)
+        return heat::failp(heat::last_error(), HEAT_E_SIZE, "shade tables: %zu values and %zu horizon numbers for shade j < %zu", t.f64.size(),
+                           t.horizon.size(), NS);
+    return HEAT_OK;
 }
 
 int heat_air_paths_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_air_paths *air) {

@@ -221,6 +221,21 @@ void build_solar_gain_tables(int64_t n_surfaces, const int32_t *dev_of, const he
 int check_solar_gain_tables(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, const SolarGainTables &t,
                             std::string &err);
 
+// Shades of a series (heat_shades, include/heat_amd.h). Everything heat_shades_check promises about the shades themselves;
+// sh == nullptr is none. s has passed check_series, sky check_sky and g check_solar_gains. HEAT_OK or a negative heat_status
+// with `err` set, naming "shade j", "horizon p", "surface s" or "aperture a".
+int check_shades(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, const heat_shades *sh,
+                 std::string &err);
+// The table of k_series_shading (one lane per shade): the shade's geometry as a structure of arrays in one f64 buffer, row a
+// of all shades contiguous — a NULL diffuse_factor / ground_factor is ones here — and the horizon numbers (-1 where
+// sh_horizon is NULL). The rows: layout.hpp, ShadeRow.
+struct ShadeTables {
+    std::vector<double> f64;       // [kShadeRows][n_shades]
+    std::vector<int32_t> horizon;  // [n_shades]
+};
+// (of shades that passed check_shades)
+void build_shade_tables(const heat_shades *sh, ShadeTables &t);
+
 // Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
 // report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
 // heat_status with `err` set, naming "group g" or "group entry i".

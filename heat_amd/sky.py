@@ -12,11 +12,13 @@ FIELDS = ("sun_x", "sun_y", "sun_z", "beam", "diffuse", "ground", "ir_sky", "ir_
 SUN_X, SUN_Y, SUN_Z, BEAM, DIFFUSE, GROUND, IR_SKY, IR_GROUND = range(8)
 
 
-def incident(record, normal, side):
+def incident(record, normal, side, shade=None):
     """The incident irradiance (before the gain) of one kind of input of one side.
     record  [..., 8]: heat_sky_record fields (FIELDS), broadcast against the normals' leading shape
     normal  (x, y, z) of the FRONT face's outward normal, arrays or scalars
     side    "solar_front", "solar_back", "ir_front" or "ir_back" (a back side sees the component-wise negation)
+    shade   None, or (f, fd, fg) of a shaded solar side (heat_shades): the step's sunlit fraction from shading.sunlit and the
+            shade's diffuse and ground factor, broadcast like the normals
     Returns an array of the broadcast shape."""
     if side not in ("solar_front", "solar_back", "ir_front", "ir_back"):
         raise ValueError("side is solar_front, solar_back, ir_front or ir_back, not %r" % (side,))
@@ -30,7 +32,15 @@ def incident(record, normal, side):
         if side.startswith("solar"):
             c = (nx * r[..., SUN_X] + ny * r[..., SUN_Y]) + nz * r[..., SUN_Z]
             bm = np.where(c > 0.0, r[..., BEAM] * c, 0.0)
+            if shade is not None:
+                f, fd, fgr = (np.asarray(a, dtype=np.float64) for a in shade)
+                bm = bm * f
+                dv = (r[..., DIFFUSE] * fs) * fd
+                gv = (r[..., GROUND] * fg) * fgr
+                return (bm + dv) + gv
             return (bm + r[..., DIFFUSE] * fs) + r[..., GROUND] * fg
+        if shade is not None:
+            raise ValueError("a shade acts on a solar input, not on %r" % (side,))
         return r[..., IR_SKY] * fs + r[..., IR_GROUND] * fg
 
 

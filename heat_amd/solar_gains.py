@@ -12,13 +12,15 @@ from . import modeldict as mdl
 from .sky import SUN_X, SUN_Y, SUN_Z, BEAM, DIFFUSE, GROUND
 
 
-def transmitted(record, normal, coef, tau_diffuse, scale):
+def transmitted(record, normal, coef, tau_diffuse, scale, shade=None):
     """The power (W) every aperture transmits: (Pb, Pd), beam and diffuse + ground-reflected.
     record       [..., 8]: heat_sky_record fields (sky.FIELDS) of the aperture's site, broadcast against the apertures
     normal       (x, y, z) of the outward normal of the side that sees the sky, arrays or scalars
     coef         [..., 6]: the beam transmittance as a polynomial in the cosine of incidence, constant term first
     tau_diffuse  the hemispherical transmittance
     scale        area x frame or shading factor, m2
+    shade        None, or (f, fd, fg) of shaded apertures (heat_shades): the step's sunlit fraction from shading.sunlit and
+                 the shade's diffuse and ground factor, broadcast like the apertures
     Returns two arrays of the broadcast shape; P = Pb + Pd is what transmitted[k][a] and ap_sum take."""
     r = np.asarray(record, dtype=np.float64)
     nx, ny, nz = (np.asarray(a, dtype=np.float64) for a in normal)
@@ -35,7 +37,12 @@ def transmitted(record, normal, coef, tau_diffuse, scale):
             t = t + coef[..., j]
         ib = r[..., BEAM] * c
         pb = np.where(c > 0.0, (ib * t) * scale, 0.0)
-        idf = r[..., DIFFUSE] * fs + r[..., GROUND] * fg
+        if shade is not None:
+            f, fd, fgr = (np.asarray(a, dtype=np.float64) for a in shade)
+            pb = np.where(c > 0.0, pb * f, 0.0)
+            idf = (r[..., DIFFUSE] * fs) * fd + (r[..., GROUND] * fg) * fgr
+        else:
+            idf = r[..., DIFFUSE] * fs + r[..., GROUND] * fg
         pd = (idf * tau_diffuse) * scale
     return pb, pd
 

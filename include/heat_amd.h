@@ -690,6 +690,91 @@ int heat_batch_march_series_air(heat_batch *b, const heat_series *s, const heat_
                                 heat_air_paths *air /* nullable */, heat_ideal_loads *il /* nullable */,
                                 heat_series_report *r /* nullable */, double *trace, double *applied, double *ideal_q,
                                 double *transmitted, double *path_q /* [n_steps][n_paths], nullable */, int32_t *failed_step);
+
+/*
+ * Shades of a series: the SUNLIT FRACTION of the beam on a rectangle under an overhang, between side fins and behind a site's
+ * horizon, formed on the device at every step from the sun vector of the sky's per-site record — instead of one channel column
+ * per shaded side the caller computes in advance (an aperture cannot express it at all: its ap_scale is constant over the
+ * series). The reference has no counterpart; the rule below is this library's own contract, defined — as the sky is — against
+ * the per-call loop with the same rule written on the host (heat_amd/shading.py, sunlit()).
+ * A SHADE j is a self-contained geometric device: the plane of a rectangle W wide and H high with outward normal n, the
+ * in-plane horizontal axis u (to the right seen from outside) and the in-plane upward axis v (u = v x n; the caller supplies
+ * all three, heat_amd/shading.py frame_of() builds u and v); a horizontal plate of overhang_depth, overhang_gap above the
+ * rectangle's top edge and unbounded along u; a fin of fin_pos_depth, fin_pos_gap beside the +u edge and one of fin_neg_depth,
+ * fin_neg_gap beside the -u edge, both unbounded along v (a depth of 0: the device is absent); optionally a horizon profile
+ * p = sh_horizon[j]: tan^2 of the obstruction's elevation in 16 sectors of 22.5 degrees, counter-clockwise from east
+ * (horizon_tan2[p][0] covers azimuths [0, 22.5) degrees from the x axis towards y). sh_surface[j] is used only for its
+ * weather site, as ap_surface is. With (sx, sy, sz) = the sun vector of sky->record[k][site of sh_surface[j]]; every line is
+ * ONE rounded f64 operation in the order written, no fused multiply-add, no square root, no transcendental function;
+ * max(a, b) is (b > a ? b : a) and min(a, b) is (b < a ? b : a) — the FIRST operand where the comparison is false, so a NaN
+ * first operand stays:
+ *   c  = (n.x * sx + n.y * sy) + n.z * sz;   us = (u.x * sx + u.y * sy) + u.z * sz;   vs = (v.x * sx + v.y * sy) + v.z * sz
+ *   overhang:  drop = (overhang_depth * vs) / c;  sh = drop - overhang_gap;  sh = max(sh, 0.0);  sh = min(sh, H)
+ *              fv = vs > 0 ? (H - sh) / H : 1.0
+ *   fins:      ap = (fin_pos_depth * us) / c;  wp = ap - fin_pos_gap;  wp = max(wp, 0.0);  wp = min(wp, W)
+ *              nu = -us;  an = (fin_neg_depth * nu) / c;  wn = an - fin_neg_gap;  wn = max(wn, 0.0);  wn = min(wn, W)
+ *              sw = us > 0 ? wp : (us < 0 ? wn : 0.0);  fh = (W - sw) / W
+ *   f = fv * fh
+ *   horizon (p >= 0):
+ *              ax = |sx|;  ay = |sy|;  T = 0.41421356237309503   (tan 22.5 degrees)
+ *              m = (ay > T * ax) + (ay > ax) + (T * ay > ax)
+ *              sector = sx >= 0 ? (sy >= 0 ? m : 15 - m) : (sy >= 0 ? 7 - m : 8 + m)
+ *              h2 = sx * sx + sy * sy;  lit = sz > 0 and sz * sz > horizon_tan2[p][sector] * h2;  if not lit: f = 0.0
+ *   if not (c > 0): f = 0.0                  (the sun behind the plane, or a NaN: no beam, as in the sky)
+ *   sunlit[k * n_shades + j] = f
+ * A sun exactly on a sector boundary belongs to the sector the comparisons give (sy == 0, sx > 0: sector 0; sx == sy > 0:
+ * sector 1; sx == 0, sy > 0: sector 3). Whatever the sun vector holds, the sector is in [0, 16).
+ * The consumers refer to shades by number; one shade may serve several of them, and the cosine of a consumer stays its own,
+ * from its own normal:
+ *   a sky-driven solar side (heat_sky, mode bit 0 / 1) with front_shade[s] / back_shade[s] = j:
+ *       bm = c > 0 ? r.beam * c : 0.0;  bm = bm * f;  dv = (r.diffuse * fs) * diffuse_factor[j]
+ *       gv = (r.ground * fg) * ground_factor[j];  v = (bm + dv) + gv          (then the gain, mirror, clamp, absorptance)
+ *   an aperture (heat_solar_gains) with aperture_shade[a] = j:
+ *       Pb = c > 0 ? ((ib * t) * scale) * f : 0.0
+ *       id = (r.diffuse * fs) * diffuse_factor[j] + (r.ground * fg) * ground_factor[j]      (Pd, P, transmitted, ap_sum as before)
+ *   a side or aperture without a shade (-1, or a NULL array) follows the rule of heat_sky / heat_solar_gains: today's bits.
+ * diffuse_factor / ground_factor are constant factors on the diffuse and the ground-reflected part (the sky and ground view
+ * the devices leave); NULL = 1. A shade has no memory: a series of k steps followed by one of n - k gives the bits of the
+ * series of n. n_sub == 0 still evaluates the shades of every step. A shade reads ITS OWN site's record — that of
+ * sh_surface[j] — whatever the site of the side or aperture that refers to it: a shade shared across sites gives every
+ * consumer the sunlit fraction under the sun of the shade's site.
+ * heat_shades_check (host-only) and heat_batch_march_series_shaded run the same checks before any device work; every message
+ * names "shade j", "horizon p", "surface s" or "aperture a": a negative count, a NULL array a positive count needs
+ * (diffuse_factor, ground_factor, sh_horizon, front_shade, back_shade, aperture_shade may be NULL), n_shades > 0 with
+ * n_steps > 0 and no sky or no sky->record, a vector component, width, height, depth, gap, factor or tan2 that is not
+ * finite, a width or height that is not positive, a negative depth, gap or tan2, an aperture_shade without gains ->
+ * HEAT_E_INVALID_ARG; sh_surface outside [0, n_surfaces), a shade number outside [-1, n_shades), a horizon number outside
+ * [-1, n_horizons), a front_shade / back_shade on a side whose solar mode bit in the sky is not set -> HEAT_E_SIZE. Sharded
+ * batches are refused as by the series; weather sites are supported.
+ * heat_batch_march_series_shaded with shades == NULL or n_shades == 0 is heat_batch_march_series_air exactly (same launches,
+ * same bits); sunlit is nullable.
+ */
+typedef struct heat_shades {
+    int64_t n_shades;
+    const int64_t *sh_surface;        /* [n_shades] used only for its weather site, as ap_surface is */
+    const double *sh_normal_x, *sh_normal_y, *sh_normal_z;   /* outward normal n of the shaded plane */
+    const double *sh_right_x, *sh_right_y, *sh_right_z;      /* u: in-plane horizontal axis, to the right seen from outside (u = v x n) */
+    const double *sh_up_x, *sh_up_y, *sh_up_z;               /* v: in-plane upward axis */
+    const double *sh_width, *sh_height;                      /* W, H of the shaded rectangle, m, > 0 */
+    const double *overhang_depth, *overhang_gap;             /* horizontal plate above the top edge, unbounded along u; depth 0: none */
+    const double *fin_pos_depth, *fin_pos_gap;               /* fin beside the +u edge, unbounded along v */
+    const double *fin_neg_depth, *fin_neg_gap;               /* fin beside the -u edge */
+    const double *diffuse_factor, *ground_factor;            /* nullable = 1: constant factors on the diffuse / ground part */
+    const int32_t *sh_horizon;                               /* nullable / -1: no horizon profile */
+    int64_t n_horizons;
+    const double *horizon_tan2;       /* [n_horizons][16] tan^2 of the obstruction's elevation per 22.5 degree sector */
+    const int32_t *front_shade, *back_shade;   /* [n_surfaces], nullable / -1: the side's sky-driven solar input is unshaded */
+    const int32_t *aperture_shade;             /* [gains->n_apertures], nullable / -1 */
+} heat_shades;
+
+int heat_shades_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                      const heat_solar_gains *gains, const heat_shades *shades); /* host-only */
+int heat_batch_march_series_shaded(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                   const heat_shades *shades /* nullable */, const heat_solar_gains *gains /* nullable */,
+                                   const heat_zone_loads *l /* nullable */, heat_air_paths *air /* nullable */,
+                                   heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
+                                   double *applied, double *ideal_q, double *transmitted, double *path_q,
+                                   double *sunlit /* [n_steps][n_shades], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -56,6 +56,18 @@ pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub b
     pub volume_gain: *const f64, pub open_chan: *const i32, pub sense: *const i8, pub band: *const f64, pub min_delta: *const f64,
     pub state: *mut u8, pub sum_q: *mut f64, pub steps_open: *mut i64, pub switches: *mut i64,
 }
+// heat_shades: overhangs, side fins and horizon profiles, and the sides and apertures they shade
+#[repr(C)] pub struct HeatShades {
+    pub n_shades: i64, pub sh_surface: *const i64,
+    pub sh_normal_x: *const f64, pub sh_normal_y: *const f64, pub sh_normal_z: *const f64,
+    pub sh_right_x: *const f64, pub sh_right_y: *const f64, pub sh_right_z: *const f64,
+    pub sh_up_x: *const f64, pub sh_up_y: *const f64, pub sh_up_z: *const f64,
+    pub sh_width: *const f64, pub sh_height: *const f64, pub overhang_depth: *const f64, pub overhang_gap: *const f64,
+    pub fin_pos_depth: *const f64, pub fin_pos_gap: *const f64, pub fin_neg_depth: *const f64, pub fin_neg_gap: *const f64,
+    pub diffuse_factor: *const f64, pub ground_factor: *const f64, pub sh_horizon: *const i32,
+    pub n_horizons: i64, pub horizon_tan2: *const f64,
+    pub front_shade: *const i32, pub back_shade: *const i32, pub aperture_shade: *const i32,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -101,6 +113,14 @@ extern "C" {
                                        gains: *const HeatSolarGains, l: *const HeatZoneLoads, air: *mut HeatAirPaths,
                                        il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
                                        ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, failed_step: *mut i32) -> c_int;
+    // shades of a series: sunlit fractions of overhangs, fins and horizons, formed on the device at every step
+    pub fn heat_shades_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
+                             gains: *const HeatSolarGains, shades: *const HeatShades) -> c_int;
+    pub fn heat_batch_march_series_shaded(b: *mut HeatBatch, s: *const HeatSeries, sky: *const HeatSky, shades: *const HeatShades,
+                                          gains: *const HeatSolarGains, l: *const HeatZoneLoads, air: *mut HeatAirPaths,
+                                          il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
+                                          ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
+                                          failed_step: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

@@ -51,24 +51,34 @@ zone, a cooling vent on the outdoor temperature channel) two legs, alternated in
 and writes profiles/series_air.json: ms per step of each, A - D, a series of ONE step of each, and — where the kernel trace of
 one A series has been taken (--one-series --air under rocprofv3 --kernel-trace --stats, a run of its own) —
 k_series_air_paths beside the same trace's k_series_zone_loads and whether A <= 1.05 (D + k_series_air_paths).
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air]
+With --shades (heat_batch_march_series_shaded; the model, channels, loads, probes, records and normals of --sky) two legs,
+alternated in the same way:
+  K  the --sky leg K, run again in the same process;
+  S  K with every wall's front solar input shaded by a shade of its own in the wall's plane: an overhang, two fins and the
+     site's horizon profile
+and writes profiles/series_shades.json: ms per step of each, S - K against the expectation
+S - K <= 1.5 x (188 B per shade / 2.0 TB/s) (160 B of k_series_shading's own, 28 B gathered per shaded side in k_series_sky), a
+series of ONE step of each, and — where the kernel trace of one S series has been taken (--one-series --shades under
+rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_shades_kernel_stats.csv) — k_series_shading per step.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
                                                      with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
-                                                     a series of leg J; with --air a series of leg A"""
+                                                     a series of leg J; with --air a series of leg A; with --shades a series of leg S"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, air_paths as apm, modeldict as mdl, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, air_paths as apm, modeldict as mdl, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
 SKY = "--sky" in sys.argv
 GAINS = "--gains" in sys.argv
 AIR = "--air" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR
+SHADES = "--shades" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -111,7 +121,7 @@ if IDEAL:
         dt = time.perf_counter() - t0
         assert out["failed_step"] == -1 and np.all(np.isfinite(out["ideal_q"])) and np.all(np.isfinite(out["trace"]))
         return dt * 1e3 / steps
-if SKY:
+if SKY or SHADES:
     FRONT = ("solar_front", "ir_front")
     azimuth = rng.uniform(0.0, 2.0 * np.pi, S)
     sun = skym.sun_direction(172, 24.0 * np.arange(STEPS) / STEPS, np.radians(48.0))
@@ -136,6 +146,27 @@ if SKY:
         t0 = time.perf_counter()
         trace, failed, applied, modes = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
                                                        sky=dict(sky_args, record=record[:steps]), **{k: (not_driven, drives[k][1]) for k in FRONT})
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace))
+        return dt * 1e3 / steps
+if SHADES:
+    # one shade per wall, in the wall's plane: a window of 1.2 m x 1.5 m under an overhang, between two fins, behind a horizon
+    wall_normal = sky_args["normals"]
+    wall_right, wall_up = shm.frame_of(wall_normal)
+    shade_args = dict(surface=np.arange(S), normal=wall_normal, right=wall_right, up=wall_up, width=rng.uniform(0.8, 2.4, S),
+                      height=rng.uniform(1.0, 2.0, S), overhang_depth=rng.uniform(0.3, 0.9, S), overhang_gap=rng.uniform(0.0, 0.3, S),
+                      fin_pos_depth=rng.uniform(0.1, 0.5, S), fin_pos_gap=rng.uniform(0.0, 0.2, S), fin_neg_depth=rng.uniform(0.1, 0.5, S),
+                      fin_neg_gap=rng.uniform(0.0, 0.2, S), diffuse_factor=rng.uniform(0.6, 0.9, S), ground_factor=rng.uniform(0.8, 1.0, S),
+                      horizon=np.zeros(S, np.int32), horizon_tan2=shm.horizon_tan2(rng.uniform(0.0, 12.0, (1, 16))),
+                      front_shade=np.arange(S, dtype=np.int32))
+    SHADE_BYTES = dict(k_series_shading_per_shade=19 * 8 + 2 * 4, gathered_in_k_series_sky_per_shaded_side=4 + 3 * 8)  # 160 + 28
+
+    def leg_s(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, lit = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                            sky=dict(sky_args, record=record[:steps]), shades=shade_args, sunlit=False,
+                                                            **{k: (not_driven, drives[k][1]) for k in FRONT})
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace))
         return dt * 1e3 / steps
@@ -377,6 +408,32 @@ with HeatBatch(md) as b:
                   "(%.1f us per sub-timestep), I / S = %.3f, I / D = %.3f (%d steps, median of %d rounds)" % (
                       n_sub, Sm, Im, Dm, Im - Sm, (Im - Sm) * 1e3 / n_sub, Im / Sm, Im / Dm, STEPS, ROUNDS), flush=True)
             continue
+        if SHADES:
+            leg_k(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_s(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with shades: S %.3f ms per step" % leg_s(b, w, n_sub, STEPS))
+                continue
+            k, sh, k1, sh1 = [], [], [], []
+            for r in range(ROUNDS):
+                k.append(leg_k(b, w, n_sub, STEPS))
+                sh.append(leg_s(b, w, n_sub, STEPS))
+                k1.append(leg_k(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                sh1.append(leg_s(b, w, n_sub, 1))
+            K, Sh, K1, Sh1 = (float(np.median(v)) for v in (k, sh, k1, sh1))
+            Ks, Ss = (K * STEPS - K1) / (STEPS - 1), (Sh * STEPS - Sh1) / (STEPS - 1)  # per step once the call is set up
+            per_shade = SHADE_BYTES["k_series_shading_per_shade"] + SHADE_BYTES["gathered_in_k_series_sky_per_shaded_side"]
+            bound_ms = 1.5 * per_shade * S / 2.0e12 * 1e3
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                K_sky_ms=K, S_shaded_ms=Sh, S_minus_K_ms=Sh - K, S_over_K=Sh / K, K_series_of_one_step_ms=K1, S_series_of_one_step_ms=Sh1,
+                S_minus_K_series_of_one_step_ms=Sh1 - K1, K_without_setup_ms=Ks, S_without_setup_ms=Ss, S_minus_K_without_setup_ms=Ss - Ks,
+                expectation_bound_ms=bound_ms, expectation_S_minus_K_within_the_bound=bool(Sh - K <= bound_ms),
+                expectation_S_minus_K_without_setup_within_the_bound=bool(Ss - Ks <= bound_ms), shades=int(S), bytes=SHADE_BYTES,
+                all_rounds=dict(K=k, S=sh, K_one_step=k1, S_one_step=sh1))
+            print("n_sub %2d: K sky %.3f ms/step, S shaded %.3f -> S - K = %+.3f ms (bound %.3f), S / K = %.4f; a series of one step: "
+                  "K %.2f ms, S %.2f ms -> per step without the set-up K %.3f, S %.3f, S - K = %+.3f (%d steps, median of %d rounds)" % (
+                      n_sub, K, Sh, Sh - K, bound_ms, Sh / K, K1, Sh1, Ks, Ss, Ss - Ks, STEPS, ROUNDS), flush=True)
+            continue
         if SKY:
             leg_cp(b, w, n_sub, min(STEPS, 10))  # warm-up
             leg_k(b, w, n_sub, min(STEPS, 10))
@@ -588,9 +645,28 @@ if AIR and not ONE:
             {k: v["expectation_A_at_most_1_05_of_D_plus_the_kernel"] for k, v in result["legs"].items()}))
     else:
         print("no kernel trace at %s: the expectation A <= 1.05 (D + k_series_air_paths) is not evaluated" % stats)
+if SHADES and not ONE:
+    # the kernel trace of one S series (--one-series --shades under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: k_series_shading per step and on its own bytes, beside the same trace's k_series_sky
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_shades_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_shading", "k_series_sky")}
+        nbytes = SHADE_BYTES["k_series_shading_per_shade"] * S
+        result["kernel_trace_of_one_S_series"] = dict(
+            k_series_shading_us_per_step=us["k_series_shading"], k_series_sky_us_per_step=us["k_series_sky"],
+            k_series_shading_bytes_per_step=int(nbytes), k_series_shading_TB_per_s=nbytes / us["k_series_shading"] / 1e6,
+            calls=int(rows["k_series_shading"]["Calls"]))
+        print("kernel trace: k_series_shading %.2f us per step (%.2f TB/s on its own bytes), k_series_sky %.2f" % (
+            us["k_series_shading"], nbytes / us["k_series_shading"] / 1e6, us["k_series_sky"]))
+    else:
+        print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
