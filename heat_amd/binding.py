@@ -145,6 +145,13 @@ class Shades(C.Structure):
                  ("back_shade", _i32p), ("aperture_shade", _i32p)])
 
 
+class RoomRadiation(C.Structure):
+    """heat_room_radiation (include/heat_amd.h): long-wave exchange among the faces of a room"""
+    _fields_ = [("n_receivers", C.c_int64), ("rc_surface", _i64p), ("rc_side", C.POINTER(C.c_uint8)), ("sum_irradiance", _dp),
+                ("n_entries", C.c_int64), ("en_receiver", _i64p), ("en_surface", _i64p), ("en_side", C.POINTER(C.c_uint8)),
+                ("en_chan", _i32p), ("en_factor", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -201,6 +208,11 @@ SYMBOLS = [
     ("heat_batch_march_series_shaded", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(Shades), C.POINTER(SolarGains),
                                                  C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads), C.POINTER(Report),
                                                  _dp, _dp, _dp, _dp, _dp, _dp, _i32p]),
+    ("heat_room_radiation_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(RoomRadiation)]),
+    ("heat_batch_march_series_radiation", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(Shades), C.POINTER(SolarGains),
+                                                    C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads),
+                                                    C.POINTER(Report), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(RoomRadiation), _dp,
+                                                    _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -351,7 +363,7 @@ def make_desc(md):
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
-                     "heat_air_paths_check", "heat_shades_check",
+                     "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1013,6 +1025,68 @@ def shades_check(md, shades, sky=None, gains=None, n_sites=1, lib=None, **series
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+_RADIATION_ARRAYS = (("rc_surface", np.int64, "n_receivers"), ("rc_side", np.uint8, "n_receivers"),
+                     ("en_receiver", np.int64, "n_entries"), ("en_surface", np.int64, "n_entries"), ("en_side", np.uint8, "n_entries"),
+                     ("en_factor", np.float64, "n_entries"))
+
+
+def make_room_radiation(rc_surface=(), rc_side=(), en_receiver=(), en_surface=(), en_side=(), en_factor=(), en_chan=None,
+                        sum_irradiance=None):
+    """Builds a heat_room_radiation. Returns (radiation, keepalive); the march adds onto keepalive["sum_irradiance"] in place.
+    rc_surface, rc_side   [n_receivers] the sides whose long-wave input the rule forms (0 front, 1 back)
+    en_receiver      [n_entries] the receiver the entry belongs to
+    en_surface, en_side   [n_entries] the emitter side; en_surface -1: the entry is the value of channel en_chan
+    en_factor        [n_entries] view factor times the caller's emissivity convention
+    en_chan          [n_entries] -1 where the emitter is a surface; None: NULL (no entry is a channel)
+    sum_irradiance   [n_receivers] what a previous series returned (it is copied), None: zeros
+    (room_radiation.exchange_by_area builds the first six for the rooms of a model)"""
+    given = dict(rc_surface=rc_surface, rc_side=rc_side, en_receiver=en_receiver, en_surface=en_surface, en_side=en_side,
+                 en_factor=en_factor)
+    rr = RoomRadiation()
+    rr.n_receivers, rr.n_entries = len(np.asarray(rc_surface).reshape(-1)), len(np.asarray(en_receiver).reshape(-1))
+    keep = {}
+    for name, dtype, count in _RADIATION_ARRAYS:
+        a = np.ascontiguousarray(given[name], dtype=dtype).reshape(-1)
+        if a.shape != (getattr(rr, count),):
+            raise ValueError("room radiation %s: %s for %s = %d" % (name, a.shape, count, getattr(rr, count)))
+        keep[name] = a
+        setattr(rr, name, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if a.size else None)
+    if en_chan is not None:
+        chan = np.ascontiguousarray(en_chan, dtype=np.int32).reshape(-1)
+        if chan.shape != (rr.n_entries,):
+            raise ValueError("room radiation en_chan: %s for n_entries = %d" % (chan.shape, rr.n_entries))
+        keep["en_chan"] = chan
+        rr.en_chan = chan.ctypes.data_as(_i32p) if chan.size else None
+    total = np.zeros(rr.n_receivers) if sum_irradiance is None else np.array(sum_irradiance, dtype=np.float64).reshape(-1)
+    if total.shape != (rr.n_receivers,):
+        raise ValueError("room radiation sum_irradiance: %s for %d receivers" % (total.shape, rr.n_receivers))
+    keep["sum_irradiance"] = total
+    rr.sum_irradiance = total.ctypes.data_as(_dp) if total.size else None
+    return rr, keep
+
+
+def room_radiation_check(md, radiation, sky=None, n_sites=1, lib=None, **series):
+    """heat_room_radiation_check: everything about the room radiation of a series that needs no device (series arguments as
+    HeatBatch.march_series; sky: the arguments of make_sky, or None; radiation: those of make_room_radiation, or None).
+    Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    k = None
+    if sky is not None:
+        sky = dict(sky)
+        if sky.get("normals") is None:
+            sky["normals"] = _model_normals(md)
+        k, kkeep = make_sky(**sky)
+        _sky_fits(kkeep, s.n_steps, int(n_sites), int(md["n_surfaces"]))
+    rr, rkeep = make_room_radiation(**radiation) if radiation is not None else (None, None)
+    rc = L.heat_room_radiation_check(C.byref(desc), int(n_sites), C.byref(s), C.byref(k) if k is not None else None,
+                                     C.byref(rr) if rr is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1126,7 +1200,7 @@ class HeatBatch:
         _check(self._L.heat_batch_synchronize(self._h))
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
-                     air=None, path_q=True, shades=None, sunlit=True, **series):
+                     air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1158,7 +1232,17 @@ class HeatBatch:
         shades (a dict of make_shades' arguments; sky carries the records and the mode bits of the shaded sides, gains the
         shaded apertures): heat_batch_march_series_shaded — the sunlit fraction of overhangs, fins and horizons, formed on the
         device at every step. Returns what the same call without shades returns plus sunlit [n_steps, n_shades] (empty with
-        sunlit=False): one more element of the tuple, or the key "sunlit" of the dict."""
+        sunlit=False): one more element of the tuple, or the key "sunlit" of the dict.
+        radiation (a dict of make_room_radiation's arguments): heat_batch_march_series_radiation — the long-wave irradiance of
+        the faces of a room from the emission of the faces they see, formed on the device at every step from the temperatures
+        it holds. Returns what the same call without radiation returns plus irradiance [n_steps, n_receivers] (empty with
+        irradiance=False) and sum_irradiance [n_receivers] (pass it as radiation["sum_irradiance"] to the next series): two
+        more elements of the tuple, or two more keys of the dict."""
+        if radiation is not None:
+            if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
+                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
+            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q, shades,
+                                          sunlit, radiation, irradiance)
         if shades is not None:
             if gains is not None or sky is None or sky.get("mode") is None:
                 sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
@@ -1256,7 +1340,7 @@ class HeatBatch:
         return out
 
     def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None, air=None,
-                          want_path_q=True, shades=None, want_sunlit=True):
+                          want_path_q=True, shades=None, want_sunlit=True, radiation=None, want_irradiance=True):
         if report is None and ideal is None and not (want_trace and want_applied):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1291,6 +1375,17 @@ class HeatBatch:
             h, hkeep = make_shades(**shades)
             _shades_fit(hkeep, self.n_surfaces, g.n_apertures if gains is not None else None)
             lit = np.zeros((s.n_steps if want_sunlit else 0, h.n_shades))
+        if radiation is not None:
+            rr, rrkeep = make_room_radiation(**radiation)
+            irr = np.zeros((s.n_steps if want_irradiance else 0, rr.n_receivers))
+            rc = self._L.heat_batch_march_series_radiation(
+                self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h) if shades is not None else None,
+                C.byref(g) if gains is not None else None, args[0], C.byref(a) if air is not None else None, *args[1:],
+                transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
+                q.ctypes.data_as(_dp) if air is not None and q.size else None,
+                lit.ctypes.data_as(_dp) if shades is not None and lit.size else None, C.byref(rr),
+                irr.ctypes.data_as(_dp) if irr.size else None, C.byref(failed))
+        elif shades is not None:
             rc = self._L.heat_batch_march_series_shaded(self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h),
                                                         C.byref(g) if gains is not None else None, args[0],
                                                         C.byref(a) if air is not None else None, *args[1:],
@@ -1325,12 +1420,15 @@ class HeatBatch:
                 out["air"] = dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep})
             if shades is not None:
                 out["sunlit"] = lit
+            if radiation is not None:
+                out.update(irradiance=irr, sum_irradiance=rrkeep["sum_irradiance"])
             return out
         out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
         out = out + ((rep,) if report is not None else ())
         out = out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
         out = out + ((dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep}),) if air is not None else ())
-        return out + ((lit,) if shades is not None else ())
+        out = out + ((lit,) if shades is not None else ())
+        return out + ((irr, rrkeep["sum_irradiance"]) if radiation is not None else ())
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

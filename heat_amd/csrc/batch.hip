@@ -1094,6 +1094,19 @@ struct ShadeDev {
     DevBuf<double> sunlit;    // [n_steps][NS]
 };
 
+// The device copies of the room radiation of a series (heat_room_radiation): the emitters' face nodes and the step's
+// emissions, the receivers' records, the CSR entry tables (plan.hpp, RoomRadiationTables), sum_irradiance and the irradiance
+// rows. Declared beside SkyDev.
+struct RadiationDev {
+    DevBuf<uint32_t> face;       // [NM]
+    DevBuf<double> emission;     // [NM]
+    DevBuf<uint32_t> rec;        // [NR]
+    DevBuf<int32_t> off, src;    // [NR + 1], [NE]
+    DevBuf<double> factor;       // [NE]
+    DevBuf<double> sum;          // [NR]
+    DevBuf<double> irradiance;   // [n_steps][NR]
+};
+
 template <typename T>
 int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
     const hipError_t e = buf.alloc(count);
@@ -2077,12 +2090,14 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 // heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
 // il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit,
-// and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path, and shades == nullptr, or no shade.
+// and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path, and shades == nullptr, or no shade,
+// and radiation == nullptr, or no receiver.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
                              double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
                              double *ideal_q = nullptr, const heat_sky *sky = nullptr, const heat_solar_gains *gains = nullptr,
                              double *transmitted = nullptr, heat_air_paths *air = nullptr, double *path_q = nullptr,
-                             const heat_shades *shades = nullptr, double *sunlit = nullptr) {
+                             const heat_shades *shades = nullptr, double *sunlit = nullptr, heat_room_radiation *radiation = nullptr,
+                             double *irradiance = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2119,6 +2134,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     rc = check_air_paths(b->n_zones, s->n_channels, air, heat::last_error());
     if (rc) return rc;
     const int64_t NP = air ? air->n_paths : 0;
+    rc = check_room_radiation(b->n_surf, s, sky, radiation, heat::last_error());
+    if (rc) return rc;
+    const int64_t NR = radiation ? radiation->n_receivers : 0;  // (entries need a receiver: there are none without)
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
@@ -2261,6 +2279,33 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             }
         }
     }
+    // room radiation: the entries as CSR over the receivers, the face node of every distinct emitter side, the receivers'
+    // device records; the long-wave gain arrays of the sides that receive, where neither the channels nor the sky have
+    // brought them along
+    RoomRadiationTables rrt;
+    std::vector<uint32_t> h_rr_face, h_rr_rec;
+    if (NR > 0) {
+        build_room_radiation_tables(S, radiation, rrt);
+        h_rr_face.resize(rrt.emitter.size());
+        for (size_t j = 0; j < rrt.emitter.size(); j++) {
+            const int64_t side = rrt.emitter[j] >= S, q = rrt.emitter[j] - side * S;
+            h_rr_face[j] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], side ? (int)b->h_node_count[q] - 1 : 0);
+        }
+        h_rr_rec.resize((size_t)NR);
+        bool receives[2] = {false, false};
+        for (int64_t r = 0; r < NR; r++) {
+            const int side = radiation->rc_side[r];
+            h_rr_rec[r] = (uint32_t)((int64_t)side * S + b->h_dev_of[radiation->rc_surface[r]]);
+            receives[side] = true;
+        }
+        const int64_t *orig_of = b->h_orig_of.data();
+        for (int a = 2; a < 4; a++) {
+            if (!receives[a - 2] || !gain[a] || !h_gain[a].empty()) continue;
+            h_gain[a].resize((size_t)S);
+            double *gd = h_gain[a].data();
+            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
+        }
+    }
     // probes: (buffer, index) of every probed slot
     std::vector<uint8_t> h_pbuf((size_t)P);
     std::vector<uint32_t> h_pidx((size_t)P);
@@ -2342,6 +2387,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     GainsDev gnd;
     AirDev aird;
     ShadeDev shd;
+    RadiationDev rrd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2533,6 +2579,23 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         gnsd.power = gnd.power.p;
         gnsd.gain[0] = d_gain[0].p, gnsd.gain[1] = d_gain[1].p;
     }
+    SeriesRoomRadiation rrdd{};
+    if (NR > 0) {
+        const size_t NM = rrt.emitter.size();
+        if ((rc = series_upload(rrd.face, h_rr_face.data(), NM, "room radiation tables"))) return rc;
+        if ((rc = series_alloc(rrd.emission, NM, "emissions"))) return rc;
+        if ((rc = series_upload(rrd.rec, h_rr_rec.data(), h_rr_rec.size(), "room radiation tables"))) return rc;
+        if ((rc = series_upload(rrd.off, rrt.off.data(), rrt.off.size(), "room radiation tables"))) return rc;
+        if ((rc = series_upload(rrd.src, rrt.src.data(), rrt.src.size(), "room radiation tables"))) return rc;
+        if ((rc = series_upload(rrd.factor, rrt.factor.data(), rrt.factor.size(), "room radiation tables"))) return rc;
+        if ((rc = report_array(rrd.sum, radiation->sum_irradiance, (size_t)NR, true, "irradiance sums"))) return rc;
+        if (irradiance && (rc = series_alloc(rrd.irradiance, (size_t)n_steps * NR, "irradiances"))) return rc;
+        rrdd.n_emitters = (int)NM, rrdd.n_receivers = (int)NR;
+        rrdd.face = rrd.face.p, rrdd.emission = rrd.emission.p;
+        rrdd.rec = rrd.rec.p, rrdd.off = rrd.off.p, rrdd.src = rrd.src.p, rrdd.factor = rrd.factor.p;
+        rrdd.gain[0] = d_gain[2].p, rrdd.gain[1] = d_gain[3].p;
+        rrdd.sum = rrd.sum.p;
+    }
     AirPathsDev airp{};
     if (NP > 0) {
         if ((rc = series_upload(aird.i32, apt.i32.data(), apt.i32.size(), "air path tables"))) return rc;
@@ -2578,8 +2641,8 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> driven inputs -> shades -> sky -> solar gains -> the body of a march call of
-    // n_sub -> probes ----
+    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> driven inputs -> shades -> sky -> solar gains -> room radiation ->
+    // the body of a march call of n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
                            d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
@@ -2601,6 +2664,11 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             launch_series_apertures(skd.record.p + (size_t)k * n_sites, apd, gnd.transmitted.p ? gnd.transmitted.p + (size_t)k * NA : nullptr,
                                     b->stream);
             launch_series_solar_gains((int)S, gnsd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+        }
+        if (NR > 0) {
+            launch_series_emission(rrdd, b->d_T.p, b->stream);
+            launch_series_room_radiation((int)S, rrdd, d_channel.p + (size_t)k * NC, b->d_side_dyn.p, b->sl, mirror,
+                                         rrd.irradiance.p ? rrd.irradiance.p + (size_t)k * NR : nullptr, b->stream);
         }
         if (NI > 0) {
             launch_series_ideal_begin(ild, d_channel.p + (size_t)k * NC, b->stream);
@@ -2666,6 +2734,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (aird.i64[1].p) HIP_TRY(hipMemcpyAsync(air->switches, aird.i64[1].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
     }
     if (shd.sunlit.p) HIP_TRY(hipMemcpyAsync(sunlit, shd.sunlit.p, (size_t)n_steps * NS * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (rrd.irradiance.p)
+        HIP_TRY(hipMemcpyAsync(irradiance, rrd.irradiance.p, (size_t)n_steps * NR * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (rrd.sum.p) HIP_TRY(hipMemcpyAsync(radiation->sum_irradiance, rrd.sum.p, (size_t)NR * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2718,6 +2789,15 @@ int heat_batch_march_series_shaded(heat_batch *b, const heat_series *s, const he
                                    heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
                                    double *path_q, double *sunlit, int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit);
+}
+
+int heat_batch_march_series_radiation(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
+                                      const heat_solar_gains *gains, const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il,
+                                      heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
+                                      double *path_q, double *sunlit, heat_room_radiation *radiation, double *irradiance,
+                                      int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit,
+                             radiation, irradiance);
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

@@ -2516,6 +2516,53 @@ k_series_solar_gains(int n_surf, SeriesGains g, const double *__restrict__ side_
     dyn[rec].solar = (side ? clamp_solar_back(v) : clamp_solar_front(v)) * side_alpha[rec];
 }
 
+// k_series_emission — sigma T^4 of every distinct emitter side of the room radiation in one step (heat_room_radiation,
+// include/heat_amd.h), behind k_series_solar_gains: one lane per emitter. A lane reads its face node from the T buffer —
+// the one scattered read of the pair of kernels, done once per emitter instead of once per viewer — and stores E into the
+// compact array k_series_room_radiation gathers from. Nothing on the step's head writes T: every emitter is read as it was
+// at the start of the step. The header's rule, one rounded operation per line, hence no contraction.
+__global__ void __launch_bounds__(256)
+k_series_emission(SeriesRoomRadiation rr, const double *__restrict__ T) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= rr.n_emitters) return;
+    const double tk = T[rr.face[j]] + 273.15;
+    const double t2 = tk * tk;
+    const double t4 = t2 * t2;
+    rr.emission[j] = kSigma * t4;
+}
+
+// k_series_room_radiation — the long-wave irradiance of every receiver of the room radiation in one step, behind
+// k_series_emission and before the body: one lane per receiver. A lane walks its CSR range of the entries (plan.hpp,
+// RoomRadiationTables) — the ranges of neighbouring receivers are neighbours — and gathers E of the emitter from the compact
+// array, or the channel's value from the step's row; its sum is its own sequential chain in the caller's order. From the raw
+// value on it is the tail of sky_side for the long-wave field, restated: the gain, the mirror, the shared conversion, one
+// 8-byte store. The side's solar field belongs to whoever drives it and is not touched. Every output has one writer: no
+// atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_room_radiation(int n_surf, SeriesRoomRadiation rr, const double *__restrict__ row, SideDyn *__restrict__ dyn, SlotArrays sl,
+                        double *__restrict__ mirror, double *__restrict__ irradiance_row) {
+#pragma clang fp contract(off)
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rr.n_receivers) return;
+    const int end = rr.off[r + 1];
+    double v = 0.0;
+    for (int at = rr.off[r]; at < end; at++) {
+        const int j = rr.src[at];
+        const double x = rr.factor[at] * (j >= 0 ? rr.emission[j] : row[~j]);
+        v = v + x;
+    }
+    const int64_t rec = rr.rec[r];
+    const int side = rec >= n_surf;
+    const int d = (int)(rec - (int64_t)side * n_surf);
+    const double *const gain = side ? rr.gain[1] : rr.gain[0];
+    if (gain != nullptr) v = v * gain[d];
+    if (irradiance_row != nullptr) irradiance_row[r] = v;
+    if (rr.sum != nullptr) rr.sum[r] = rr.sum[r] + v;
+    if (mirror != nullptr) mirror[(side ? sl.ir_b : sl.ir_f)[d]] = v;
+    dyn[rec].rad_t = ir_to_rad_temperature(v);
+}
+
 // Report of a series (heat_series_report, include/heat_amd.h): on the step's tail, beside k_series_probe. Everything below
 // is written without contraction: the statistics are DEFINED as one rounded operation per rule, and a group's bits are to
 // follow from its tables alone.
@@ -3091,6 +3138,18 @@ void launch_series_solar_gains(int n_surf, const SeriesGains &g, const double *s
                                double *mirror, hipStream_t st) {
     if (g.n_receivers <= 0) return;
     hipLaunchKernelGGL(k_series_solar_gains, dim3((g.n_receivers + 255) / 256), dim3(256), 0, st, n_surf, g, side_alpha, dyn, sl, mirror);
+}
+
+void launch_series_emission(const SeriesRoomRadiation &rr, const double *T, hipStream_t st) {
+    if (rr.n_emitters <= 0) return;
+    hipLaunchKernelGGL(k_series_emission, dim3((rr.n_emitters + 255) / 256), dim3(256), 0, st, rr, T);
+}
+
+void launch_series_room_radiation(int n_surf, const SeriesRoomRadiation &rr, const double *row, SideDyn *dyn, const SlotArrays &sl,
+                                  double *mirror, double *irradiance_row, hipStream_t st) {
+    if (rr.n_receivers <= 0) return;
+    hipLaunchKernelGGL(k_series_room_radiation, dim3((rr.n_receivers + 255) / 256), dim3(256), 0, st, n_surf, rr, row, dyn, sl, mirror,
+                       irradiance_row);
 }
 
 void launch_series_zone_loads(int n_zones, const ZoneLoadsDev &zl, const double *row, const double *zone_T, double *a0, double *b0,

@@ -141,6 +141,24 @@ struct SeriesGains {
 void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st);
 void launch_series_solar_gains(int n_surf, const SeriesGains &g, const double *side_alpha, SideDyn *dyn, const SlotArrays &sl,
                                double *mirror, hipStream_t st);
+// Room radiation of a series step (heat_room_radiation, include/heat_amd.h; tables: plan.hpp, RoomRadiationTables): two
+// launches behind launch_series_solar_gains and before the body, only when there are receivers — one lane per distinct
+// emitter side (only when there are emitters), then one lane per receiver.
+struct SeriesRoomRadiation {
+    int n_emitters, n_receivers;
+    const uint32_t *face;    // [n_emitters] index into the T buffer of the emitter's face node
+    double *emission;        // [n_emitters] E of the step
+    const uint32_t *rec;     // [n_receivers] side * S + device surface
+    const int32_t *off;      // [n_receivers + 1] CSR ranges of the entries
+    const int32_t *src;      // [n_entries] >= 0: emitter number; < 0: ~channel of the step's row
+    const double *factor;    // [n_entries]
+    const double *gain[2];   // the series' long-wave gain arrays, front and back (SeriesInputs::gain[2], [3]); nullptr: 1
+    double *sum;             // [n_receivers] sum_irradiance; nullptr: not kept
+};
+void launch_series_emission(const SeriesRoomRadiation &rr, const double *T, hipStream_t st);
+// row: the step's row of the channel table; irradiance_row: the step's row of irradiance, [n_receivers], or nullptr
+void launch_series_room_radiation(int n_surf, const SeriesRoomRadiation &rr, const double *row, SideDyn *dyn, const SlotArrays &sl,
+                                  double *mirror, double *irradiance_row, hipStream_t st);
 // Zone loads of a series step (heat_zone_loads, include/heat_amd.h; tables: plan.hpp, ZoneLoadTables): launched between the
 // step's head and its driven inputs, one lane per zone.
 struct ZoneLoadsDev {

@@ -2181,6 +2181,149 @@ void build_shade_tables(const heat_shades *sh, ShadeTables &t) {
     if (sh->sh_horizon) std::copy(sh->sh_horizon, sh->sh_horizon + NS, t.horizon.begin());
 }
 
+// ---- room radiation of a series (include/heat_amd.h, heat_room_radiation) ----
+int check_room_radiation(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_room_radiation *rr, std::string &err) {
+    if (!rr) return HEAT_OK;
+    const int64_t NR = rr->n_receivers, NE = rr->n_entries;
+    if (NR < 0 || NE < 0)
+        return failp(err, HEAT_E_INVALID_ARG, "negative count in room radiation (n_receivers %lld, n_entries %lld): no receiver r, no entry i",
+                     (long long)NR, (long long)NE);
+    if (NR > INT32_MAX || NE > INT32_MAX)
+        return failp(err, HEAT_E_INVALID_ARG,
+                     "more than 2^31 - 1 in room radiation (n_receivers %lld, n_entries %lld): receiver r and entry i are 32-bit", (long long)NR,
+                     (long long)NE);
+    if (NR > 0) {
+        if (!rr->rc_surface) return failp(err, HEAT_E_INVALID_ARG, "receiver 0: rc_surface is NULL (n_receivers %lld)", (long long)NR);
+        if (!rr->rc_side) return failp(err, HEAT_E_INVALID_ARG, "receiver 0: rc_side is NULL (n_receivers %lld)", (long long)NR);
+    }
+    if (NE > 0) {
+        const void *need[4] = {rr->en_receiver, rr->en_surface, rr->en_side, rr->en_factor};
+        static const char *const name[4] = {"en_receiver", "en_surface", "en_side", "en_factor"};
+        for (int a = 0; a < 4; a++)
+            if (!need[a]) return failp(err, HEAT_E_INVALID_ARG, "entry 0: %s is NULL (n_entries %lld)", name[a], (long long)NE);
+    }
+    const int32_t *chan[2] = {s->ir_front_chan, s->ir_back_chan};
+    std::vector<int32_t> receiver_of(NR > 0 ? 2 * (size_t)n_surfaces : 0, -1);  // (surface, side) -> its receiver
+    for (int64_t r = 0; r < NR; r++) {
+        const int64_t q = rr->rc_surface[r];
+        const unsigned side = rr->rc_side[r];
+        if (side > 1) return failp(err, HEAT_E_INVALID_ARG, "receiver %lld: side %u above 1 (0 front, 1 back)", (long long)r, side);
+        if (q < 0 || q >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "receiver %lld: surface %lld outside [0, %lld)", (long long)r, (long long)q, (long long)n_surfaces);
+        int32_t &seen = receiver_of[(size_t)side * n_surfaces + q];
+        if (seen >= 0)
+            return failp(err, HEAT_E_SIZE, "receiver %lld: the %s of surface %lld is receiver %d already", (long long)r, side ? "back" : "front",
+                         (long long)q, seen);
+        seen = (int32_t)r;
+        if (chan[side] && chan[side][q] >= 0)
+            return failp(err, HEAT_E_SIZE,
+                         "receiver %lld: the long-wave %s input of surface %lld is driven by channel %d already: an input has one source",
+                         (long long)r, side ? "back" : "front", (long long)q, chan[side][q]);
+        if (sky && sky->mode && (sky->mode[q] >> (2 + side) & 1))
+            return failp(err, HEAT_E_SIZE,
+                         "receiver %lld: the long-wave %s input of surface %lld is driven by the sky (mode bit %u) already: an input has one source",
+                         (long long)r, side ? "back" : "front", (long long)q, 2 + side);
+    }
+    for (int64_t i = 0; i < NE; i++) {
+        const int64_t e = rr->en_surface[i];
+        if (!std::isfinite(rr->en_factor[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "entry %lld: factor = %g is not finite", (long long)i, rr->en_factor[i]);
+        if (e >= 0) {
+            const unsigned side = rr->en_side[i];
+            if (side > 1) return failp(err, HEAT_E_INVALID_ARG, "entry %lld: side %u above 1 (0 front, 1 back)", (long long)i, side);
+            if (rr->en_chan && rr->en_chan[i] != -1)
+                return failp(err, HEAT_E_INVALID_ARG, "entry %lld: channel %d beside emitter surface %lld (-1 where the emitter is a surface)",
+                             (long long)i, rr->en_chan[i], (long long)e);
+        } else if (e == -1 && !rr->en_chan) {
+            return failp(err, HEAT_E_INVALID_ARG, "entry %lld: its emitter is -1 (a channel), but en_chan is NULL", (long long)i);
+        }
+        if (e < -1 || e >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "entry %lld: emitter surface %lld outside [-1, %lld)", (long long)i, (long long)e, (long long)n_surfaces);
+        if (rr->en_receiver[i] < 0 || rr->en_receiver[i] >= NR)
+            return failp(err, HEAT_E_SIZE, "entry %lld: receiver %lld outside [0, %lld)", (long long)i, (long long)rr->en_receiver[i], (long long)NR);
+        if (e == -1 && (rr->en_chan[i] < 0 || rr->en_chan[i] >= s->n_channels))
+            return failp(err, HEAT_E_SIZE, "entry %lld: channel %d outside [0, %d)", (long long)i, rr->en_chan[i], s->n_channels);
+    }
+    return HEAT_OK;
+}
+
+void build_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *rr, RoomRadiationTables &t) {
+    t.off.clear();
+    t.src.clear();
+    t.factor.clear();
+    t.emitter.clear();
+    const int64_t NR = rr ? rr->n_receivers : 0, NE = rr ? rr->n_entries : 0;
+    if (NR <= 0) return;
+    // the distinct emitter sides, ascending by key: a mark per side, then a prefix count (key -> emitter number)
+    std::vector<int32_t> number_of(2 * (size_t)n_surfaces, -1);
+    for (int64_t i = 0; i < NE; i++)
+        if (rr->en_surface[i] >= 0) number_of[(size_t)rr->en_side[i] * n_surfaces + rr->en_surface[i]] = 0;
+    for (size_t k = 0; k < number_of.size(); k++)
+        if (number_of[k] == 0) {
+            number_of[k] = (int32_t)t.emitter.size();
+            t.emitter.push_back((int64_t)k);
+        }
+    // a counting sort by receiver: stable by construction
+    t.off.assign((size_t)NR + 1, 0);
+    for (int64_t i = 0; i < NE; i++) t.off[(size_t)rr->en_receiver[i] + 1]++;
+    for (int64_t r = 0; r < NR; r++) t.off[(size_t)r + 1] += t.off[(size_t)r];
+    t.src.assign((size_t)NE, 0);
+    t.factor.assign((size_t)NE, 0.0);
+    std::vector<int32_t> cursor(t.off.begin(), t.off.end() - 1);
+    for (int64_t i = 0; i < NE; i++) {
+        const size_t at = (size_t)cursor[(size_t)rr->en_receiver[i]]++;
+        const int64_t e = rr->en_surface[i];
+        t.src[at] = e >= 0 ? number_of[(size_t)rr->en_side[i] * n_surfaces + e] : ~rr->en_chan[i];
+        t.factor[at] = rr->en_factor[i];
+    }
+}
+
+int check_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *rr, const RoomRadiationTables &t, std::string &err) {
+    const int64_t NR = rr ? rr->n_receivers : 0, NE = rr ? rr->n_entries : 0;
+    if (NR <= 0) {
+        if (!t.off.empty() || !t.src.empty() || !t.factor.empty() || !t.emitter.empty())
+            return failp(err, HEAT_E_SIZE, "room radiation tables: tables without a receiver r");
+        return HEAT_OK;
+    }
+    if (t.off.size() != (size_t)NR + 1 || t.off[0] != 0 || t.off.back() != NE || t.src.size() != (size_t)NE || t.factor.size() != (size_t)NE)
+        return failp(err, HEAT_E_SIZE, "room radiation tables: %zu offsets, %zu sources and %zu factors for receiver r < %lld, entry i < %lld",
+                     t.off.size(), t.src.size(), t.factor.size(), (long long)NR, (long long)NE);
+    for (int64_t r = 0; r < NR; r++)
+        if (t.off[(size_t)r + 1] < t.off[(size_t)r])
+            return failp(err, HEAT_E_SIZE, "room radiation tables: receiver %lld runs from %d to %d", (long long)r, t.off[(size_t)r], t.off[(size_t)r + 1]);
+    const size_t NM = t.emitter.size();
+    for (size_t j = 0; j < NM; j++)
+        if (t.emitter[j] < 0 || t.emitter[j] >= 2 * n_surfaces || (j > 0 && t.emitter[j] <= t.emitter[j - 1]))
+            return failp(err, HEAT_E_SIZE, "room radiation tables: emitter %zu is side %lld, not above the one before or outside the %lld sides", j,
+                         (long long)t.emitter[j], (long long)(2 * n_surfaces));
+    // every entry of the caller's, in the caller's order, is the next element of its receiver's range
+    std::vector<int32_t> cursor(t.off.begin(), t.off.end() - 1);
+    std::vector<uint8_t> named(NM, 0);
+    for (int64_t i = 0; i < NE; i++) {
+        const size_t r = (size_t)rr->en_receiver[i];
+        if (cursor[r] >= t.off[r + 1]) return failp(err, HEAT_E_SIZE, "room radiation tables: entry %lld: receiver %zu has no room for it", (long long)i, r);
+        const size_t at = (size_t)cursor[r]++;
+        const int64_t e = rr->en_surface[i];
+        bool same = std::memcmp(&t.factor[at], &rr->en_factor[i], sizeof(double)) == 0;
+        if (e >= 0) {
+            const int32_t j = t.src[at];
+            same = same && j >= 0 && (size_t)j < NM && t.emitter[(size_t)j] == (int64_t)rr->en_side[i] * n_surfaces + e;
+            if (same) named[(size_t)j] = 1;
+        } else {
+            same = same && t.src[at] == ~rr->en_chan[i];
+        }
+        if (!same)
+            return failp(err, HEAT_E_SIZE, "room radiation tables: entry %lld is not element %d of receiver %zu", (long long)i, (int)at - t.off[r], r);
+    }
+    for (int64_t r = 0; r < NR; r++)
+        if (cursor[(size_t)r] != t.off[(size_t)r + 1])
+            return failp(err, HEAT_E_SIZE, "room radiation tables: receiver %lld holds %d elements no entry i put there", (long long)r,
+                         t.off[(size_t)r + 1] - cursor[(size_t)r]);
+    for (size_t j = 0; j < NM; j++)
+        if (!named[j]) return failp(err, HEAT_E_SIZE, "room radiation tables: emitter %zu is named by no entry i", j);
+    return HEAT_OK;
+}
+
 static inline int64_t gain_key(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, int64_t i) {
     const int64_t q = g->en_surface[i];
     return (int64_t)g->en_side[i] * n_surfaces + (dev_of ? (int64_t)dev_of[q] : q);
@@ -2544,6 +2687,19 @@ int heat_shades_check(const heat_batch_desc *desc, int32_t n_sites, const heat_s
         return heat::failp(heat::last_error(), HEAT_E_SIZE, "shade tables: %zu values and %zu horizon numbers for shade j < %zu", t.f64.size(),
                            t.horizon.size(), NS);
     return HEAT_OK;
+}
+
+int heat_room_radiation_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                              const heat_room_radiation *radiation) {
+    int rc = heat_sky_check(desc, n_sites, s, sky);
+    if (rc) return rc;
+    rc = heat::check_room_radiation(desc->n_surfaces, s, sky, radiation, heat::last_error());
+    if (rc || !radiation) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see)
+    heat::RoomRadiationTables t;
+    heat::build_room_radiation_tables(desc->n_surfaces, radiation, t);
+    return heat::check_room_radiation_tables(desc->n_surfaces, radiation, t, heat::last_error());
 }
 
 int heat_air_paths_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_air_paths *air) {

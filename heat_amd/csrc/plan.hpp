@@ -236,6 +236,28 @@ struct ShadeTables {
 // (of shades that passed check_shades)
 void build_shade_tables(const heat_shades *sh, ShadeTables &t);
 
+// Room radiation of a series (heat_room_radiation, include/heat_amd.h). Everything heat_room_radiation_check promises about
+// the radiation itself; rr == nullptr is none. s has passed check_series and sky check_sky. HEAT_OK or a negative heat_status
+// with `err` set, naming "receiver r" or "entry i".
+int check_room_radiation(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_room_radiation *rr, std::string &err);
+// The tables of k_series_emission (one lane per distinct emitter side) and k_series_room_radiation (one lane per receiver).
+// The entries are sorted by receiver into CSR ranges — a counting sort, stable: the caller's order survives inside a
+// receiver — and the emitter sides they name are deduplicated into a compact list, ascending by side * n_surfaces + surface
+// in the CALLER's numbering (the batch turns a key into the face node's place in the T buffer). src of an entry: the number
+// of its emitter in that list, or ~channel (negative) for a channel entry.
+struct RoomRadiationTables {
+    std::vector<int32_t> off;      // [n_receivers + 1] entries of receiver r: [off[r], off[r + 1])
+    std::vector<int32_t> src;      // [n_entries] >= 0: emitter number; < 0: ~en_chan
+    std::vector<double> factor;    // [n_entries]
+    std::vector<int64_t> emitter;  // [n_emitters] side * n_surfaces + surface, strictly ascending
+};
+// (of radiation that passed check_room_radiation)
+void build_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *rr, RoomRadiationTables &t);
+// The tables against the caller's lists (used by the host-only check): every entry present exactly once in its receiver's
+// range, the caller's order kept, every emitter in the list once and named by an entry, every index inside its array.
+// HEAT_OK or HEAT_E_SIZE.
+int check_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *rr, const RoomRadiationTables &t, std::string &err);
+
 // Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
 // report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
 // heat_status with `err` set, naming "group g" or "group entry i".

@@ -775,6 +775,74 @@ int heat_batch_march_series_shaded(heat_batch *b, const heat_series *s, const he
                                    heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
                                    double *applied, double *ideal_q, double *transmitted, double *path_q,
                                    double *sunlit /* [n_steps][n_shades], nullable */, int32_t *failed_step);
+
+/*
+ * Room radiation of a series: the LONG-WAVE IRRADIANCE of a side that faces a room, formed on the device at every step from
+ * the emission of the other faces of its room — temperatures only the device holds, at the moment the step starts — instead
+ * of a channel the caller computed in advance, the sky (which is for outside faces) or ir_own_face (where a face sees only
+ * itself). Like a thermostat or an air path it cannot be a schedule at all. The reference has no counterpart (its harness
+ * feeds EnergyPlus' long-wave columns plus the own-face term, validate_wall_heat_transfer.rs:689-699); the rule below is this
+ * library's own contract, defined against the per-call loop with the same rule written on the host
+ * (heat_amd/room_radiation.py, emitted() and irradiance()).
+ * A RECEIVER r is a side whose long-wave input the rule forms: rc_side[r] (0 front, 1 back) of surface rc_surface[r]. An ENTRY
+ * i gives receiver en_receiver[i] one term: the emission of an EMITTER side, en_side[i] of surface en_surface[i] — or, with
+ * en_surface[i] == -1, the value of channel en_chan[i] (a radiant panel, the radiant part of an internal gain; W/m2) — weighted
+ * by en_factor[i]: a view factor times whatever emissivity convention the caller uses, any finite number, the caller's
+ * business. Entries come in any order; a receiver's sum runs over its entries in the caller's order. An emitter may be the
+ * receiver itself, and a side in another zone or at another site.
+ * Step k, behind the solar gains' receivers and before the ideal loads' begin; Tn = the node temperatures the device holds
+ * then (what step k - 1 left; for step 0 the state as it is — nothing on the step's head writes them), row = channel[k];
+ * every line is ONE rounded f64 operation in the order written, no fused multiply-add:
+ *   emitter (surface e, side d):  tk = Tn[first node of e if d == 0, last node if d == 1] + 273.15
+ *                                 t2 = tk * tk;  t4 = t2 * t2;  E = 5.670374419e-8 * t4
+ *   receiver r:                   v = 0.0
+ *     per entry i of r:           x = en_factor[i] * (en_surface[i] >= 0 ? E(en_surface[i], en_side[i]) : row[en_chan[i]])
+ *                                 v = v + x
+ *     if the series carries that input's gain array (ir_front_gain / ir_back_gain):  v = v * gain[s]
+ *   irradiance[k * n_receivers + r] = v;   sum_irradiance[r] = sum_irradiance[r] + v
+ * From v on it is the raw value of a driven long-wave input of the series: into the state mirror where the batch keeps one,
+ * through (v / SIGMA)^0.25 - 273.15 (surface.rs:647,692) into the side's radiant temperature. The side's solar input is never
+ * written here. A receiver without entries gets v = 0.0. Every emitter is read as it was at the START of the step: no
+ * receiver sees a value this step has formed. Unlike the own-face term of heat_series this rule is exempt from nothing: the
+ * host applying it between march calls reproduces every bit.
+ * An input has ONE source: a receiver's long-wave channel in the series is -1 and it has no long-wave sky bit (an ir_own_face
+ * bit on it is therefore refused by the series already). sum_irradiance (in/out, nullable) adds onto what the caller passes;
+ * the rule has no other memory: a series of k steps followed by one of n - k with the returned array gives the bits of the
+ * series of n. irradiance is nullable; an array that is not asked for costs no traffic and changes no bit of the others.
+ * n_sub == 0 still evaluates every step. A NaN temperature or channel value propagates as a NaN channel value does. Weather
+ * sites are supported (nothing here reads a site); sharded batches are refused as by the series.
+ * heat_room_radiation_check (host-only; it also builds and verifies the tables the march uploads) and
+ * heat_batch_march_series_radiation run the same checks before any device work; every message names "receiver r" or
+ * "entry i": a negative count, a NULL array a positive count needs (sum_irradiance may be NULL; en_chan may be NULL when no
+ * en_surface is -1), a side byte above 1, a factor that is not finite, en_chan other than -1 on an entry whose emitter is a
+ * surface -> HEAT_E_INVALID_ARG; rc_surface outside [0, n_surfaces), en_surface outside [-1, n_surfaces), en_receiver
+ * outside [0, n_receivers), a channel outside [0, n_channels) where the emitter is -1, the same (surface, side) twice among
+ * the receivers, a receiver whose long-wave input has a channel or a sky bit already -> HEAT_E_SIZE.
+ * heat_batch_march_series_radiation with radiation == NULL, or n_receivers == 0 and n_entries == 0, is
+ * heat_batch_march_series_shaded exactly (same launches, same bits).
+ */
+typedef struct heat_room_radiation {
+    int64_t n_receivers;
+    const int64_t *rc_surface;        /* [n_receivers] */
+    const uint8_t *rc_side;           /* [n_receivers] 0 front, 1 back */
+    double *sum_irradiance;           /* [n_receivers] in/out, nullable */
+    int64_t n_entries;
+    const int64_t *en_receiver;       /* [n_entries] */
+    const int64_t *en_surface;        /* [n_entries] the emitter's surface; -1: the entry is a channel */
+    const uint8_t *en_side;           /* [n_entries] the emitter's side (not read where en_surface is -1) */
+    const int32_t *en_chan;           /* [n_entries] nullable when no en_surface is -1; -1 where it is >= 0 */
+    const double *en_factor;          /* [n_entries] */
+} heat_room_radiation;
+
+int heat_room_radiation_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky /* nullable */,
+                              const heat_room_radiation *radiation); /* host-only */
+int heat_batch_march_series_radiation(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                      const heat_shades *shades /* nullable */, const heat_solar_gains *gains /* nullable */,
+                                      const heat_zone_loads *l /* nullable */, heat_air_paths *air /* nullable */,
+                                      heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
+                                      double *applied, double *ideal_q, double *transmitted, double *path_q, double *sunlit,
+                                      heat_room_radiation *radiation /* nullable */,
+                                      double *irradiance /* [n_steps][n_receivers], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -68,6 +68,12 @@ pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub b
     pub n_horizons: i64, pub horizon_tan2: *const f64,
     pub front_shade: *const i32, pub back_shade: *const i32, pub aperture_shade: *const i32,
 }
+// heat_room_radiation: long-wave exchange among the faces of a room
+#[repr(C)] pub struct HeatRoomRadiation {
+    pub n_receivers: i64, pub rc_surface: *const i64, pub rc_side: *const u8, pub sum_irradiance: *mut f64,
+    pub n_entries: i64, pub en_receiver: *const i64, pub en_surface: *const i64, pub en_side: *const u8,
+    pub en_chan: *const i32, pub en_factor: *const f64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -121,6 +127,14 @@ extern "C" {
                                           il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
                                           ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
                                           failed_step: *mut i32) -> c_int;
+    // room radiation of a series: the long-wave irradiance of a room's faces from the emission of the faces they see
+    pub fn heat_room_radiation_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
+                                     radiation: *const HeatRoomRadiation) -> c_int;
+    pub fn heat_batch_march_series_radiation(b: *mut HeatBatch, s: *const HeatSeries, sky: *const HeatSky, shades: *const HeatShades,
+                                             gains: *const HeatSolarGains, l: *const HeatZoneLoads, air: *mut HeatAirPaths,
+                                             il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
+                                             ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
+                                             radiation: *mut HeatRoomRadiation, irradiance: *mut f64, failed_step: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

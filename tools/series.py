@@ -60,17 +60,27 @@ and writes profiles/series_shades.json: ms per step of each, S - K against the e
 S - K <= 1.5 x (188 B per shade / 2.0 TB/s) (160 B of k_series_shading's own, 28 B gathered per shaded side in k_series_sky), a
 series of ONE step of each, and — where the kernel trace of one S series has been taken (--one-series --shades under
 rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_shades_kernel_stats.csv) — k_series_shading per step.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades]
+With --radiation (heat_batch_march_series_radiation; NOT the 100-wall zones of the headline: the same walls in rooms of 7
+faces, 6-8 where the count does not divide — Z = S / 7 —, channels, loads and probes as in leg D; the back of every wall a
+receiver that sees the backs of all walls of its room, itself included, by heat_amd.room_radiation.exchange_by_area: at 1 M
+walls 1 M receivers, 1 M distinct emitters, 7 M entries) two legs, alternated in the same way:
+  D  leg D on this model: every receiver's long-wave input driven from the 64 shared channels like everybody's
+  R  the same series with the backs' long-wave input formed by the room radiation instead (irradiance not recorded)
+and writes profiles/series_radiation.json: ms per step of each, R - D, a series of ONE step of each and the per-step times
+once the calls are set up, the bytes a step of k_series_emission and k_series_room_radiation moves. No time is a pass
+criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
                                                      with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
-                                                     a series of leg J; with --air a series of leg A; with --shades a series of leg S"""
+                                                     a series of leg J; with --air a series of leg A; with --shades a series of leg S;
+                                                     with --radiation a series of leg R"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, air_paths as apm, modeldict as mdl, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, air_paths as apm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -78,7 +88,8 @@ SKY = "--sky" in sys.argv
 GAINS = "--gains" in sys.argv
 AIR = "--air" in sys.argv
 SHADES = "--shades" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES
+RADIATION = "--radiation" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -87,7 +98,7 @@ ROUNDS = int(ARGS[2]) if len(ARGS) > 2 else 3
 N_CHANNELS = 64
 KEYS = ("solar_front", "solar_back", "ir_front", "ir_back")
 
-md, st0 = mdl.uniform_massive(S, n=32, Z=max(1, S // 100), dt=45.0)
+md, st0 = mdl.uniform_massive(S, n=32, Z=max(1, S // (7 if RADIATION else 100)), dt=45.0)
 rng = np.random.default_rng(1)
 channel = np.concatenate([rng.uniform(0.0, 600.0, (STEPS, N_CHANNELS // 2)), rng.uniform(300.0, 450.0, (STEPS, N_CHANNELS // 2))], axis=1)
 drives = {k: ((rng.integers(0, N_CHANNELS // 2, S) + (N_CHANNELS // 2 if i >= 2 else 0)).astype(np.int32), rng.uniform(0.5, 1.5, S))
@@ -169,6 +180,23 @@ if SHADES:
                                                             **{k: (not_driven, drives[k][1]) for k in FRONT})
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace))
+        return dt * 1e3 / steps
+if RADIATION:
+    # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
+    exchange = rrm.exchange_by_area(md)
+    assert np.all(exchange["rc_side"] == 1) and len(exchange["rc_surface"]) == S
+    not_driven = np.full(S, -1, np.int32)
+    RADIATION_BYTES = dict(k_series_emission_per_emitter=4 + 8 + 8, k_series_room_radiation_per_entry=4 + 8 + 8,
+                           k_series_room_radiation_per_receiver=4 + 4 + 8 + 8)   # face + T + E; src + factor + E; rec + off + gain + rad_t
+
+    def leg_r(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, irr, total = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                                   radiation=exchange, irradiance=False,
+                                                                   **dict(drives, ir_back=(not_driven, drives["ir_back"][1])))
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace)) and np.all(np.isfinite(total)) and np.all(total > 0)
         return dt * 1e3 / steps
 if GAINS:
     assert np.all(np.diff(md["back_zone"]) >= 0) and np.all(md["back_kind"] == mdl.SPACE)
@@ -407,6 +435,32 @@ with HeatBatch(md) as b:
             print("n_sub %2d: S streamed series with loads %.3f ms/step, I with ideal loads %.3f, D fused %.3f -> I - S = %.3f ms "
                   "(%.1f us per sub-timestep), I / S = %.3f, I / D = %.3f (%d steps, median of %d rounds)" % (
                       n_sub, Sm, Im, Dm, Im - Sm, (Im - Sm) * 1e3 / n_sub, Im / Sm, Im / Dm, STEPS, ROUNDS), flush=True)
+            continue
+        if RADIATION:
+            leg_d(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_r(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with room radiation: R %.3f ms per step" % leg_r(b, w, n_sub, STEPS))
+                continue
+            d, rr, d1, rr1 = [], [], [], []
+            for r in range(ROUNDS):
+                d.append(leg_d(b, w, n_sub, STEPS))
+                rr.append(leg_r(b, w, n_sub, STEPS))
+                d1.append(leg_d(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                rr1.append(leg_r(b, w, n_sub, 1))
+            D, R, D1, R1 = (float(np.median(v)) for v in (d, rr, d1, rr1))
+            Ds, Rs = (D * STEPS - D1) / (STEPS - 1), (R * STEPS - R1) / (STEPS - 1)  # per step once the call is set up
+            NE, NM = len(exchange["en_receiver"]), S
+            nbytes = (RADIATION_BYTES["k_series_emission_per_emitter"] * NM + RADIATION_BYTES["k_series_room_radiation_per_entry"] * NE +
+                      RADIATION_BYTES["k_series_room_radiation_per_receiver"] * S)
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                D_channel_driven_ms=D, R_room_radiation_ms=R, R_minus_D_ms=R - D, R_over_D=R / D, D_series_of_one_step_ms=D1,
+                R_series_of_one_step_ms=R1, R_minus_D_series_of_one_step_ms=R1 - D1, D_without_setup_ms=Ds, R_without_setup_ms=Rs,
+                R_minus_D_without_setup_ms=Rs - Ds, receivers=int(S), emitters=int(NM), entries=int(NE), bytes=RADIATION_BYTES,
+                bytes_per_step_of_the_two_kernels=int(nbytes), all_rounds=dict(D=d, R=rr, D_one_step=d1, R_one_step=rr1))
+            print("n_sub %2d: D channel-driven %.3f ms/step, R room radiation %.3f -> R - D = %+.3f ms, R / D = %.4f; a series of one "
+                  "step: D %.2f ms, R %.2f ms -> per step without the set-up D %.3f, R %.3f, R - D = %+.3f (%d entries, %d steps, median "
+                  "of %d rounds)" % (n_sub, D, R, R - D, R / D, D1, R1, Ds, Rs, Rs - Ds, NE, STEPS, ROUNDS), flush=True)
             continue
         if SHADES:
             leg_k(b, w, n_sub, min(STEPS, 10))  # warm-up
@@ -666,7 +720,7 @@ if SHADES and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
