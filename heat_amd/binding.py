@@ -152,6 +152,12 @@ class RoomRadiation(C.Structure):
                 ("en_chan", _i32p), ("en_factor", _dp)]
 
 
+class AmbientDrive(C.Structure):
+    """heat_ambient_drive (include/heat_amd.h): ambient-side temperatures of a series, per step"""
+    _fields_ = [("n_sides", C.c_int64), ("surface", _i64p), ("side", C.POINTER(C.c_uint8)), ("chan", _i32p), ("gain", _dp),
+                ("offset", _dp), ("mix_zone", _i32p), ("mix", _dp), ("sum_temperature", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -213,6 +219,12 @@ SYMBOLS = [
                                                     C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads),
                                                     C.POINTER(Report), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(RoomRadiation), _dp,
                                                     _i32p]),
+    ("heat_batch_set_ambient", C.c_int, [_H, C.c_int64, _i64p, C.POINTER(C.c_uint8), _dp]),
+    ("heat_ambient_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(AmbientDrive)]),
+    ("heat_batch_march_series_ambient", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(Shades), C.POINTER(SolarGains),
+                                                  C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads),
+                                                  C.POINTER(Report), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(RoomRadiation), _dp,
+                                                  C.POINTER(AmbientDrive), _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -363,7 +375,7 @@ def make_desc(md):
 
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
-                     "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check",
+                     "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1087,6 +1099,55 @@ def room_radiation_check(md, radiation, sky=None, n_sites=1, lib=None, **series)
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+_AMBIENT_ARRAYS = (("surface", np.int64, True), ("side", np.uint8, True), ("chan", np.int32, True), ("gain", np.float64, False),
+                   ("offset", np.float64, False), ("mix_zone", np.int32, False), ("mix", np.float64, False))
+
+
+def make_ambient(surface=(), side=(), chan=(), gain=None, offset=None, mix_zone=None, mix=None, sum_temperature=None):
+    """Builds a heat_ambient_drive. Returns (drive, keepalive); the march adds onto keepalive["sum_temperature"] in place.
+    surface, side    [n_sides] the driven sides (0 front, 1 back), each of kind AMBIENT
+    chan             [n_sides] the channel of the series that carries the temperature, C
+    gain, offset     [n_sides] or None (NULL: 1 / 0)
+    mix_zone         [n_sides] the zone a side's temperature is mixed with, -1: none; None: NULL
+    mix              [n_sides] 1 - b of EN ISO 13789 (ambient.b_factor), read where mix_zone >= 0; None: NULL
+    sum_temperature  [n_sides] what a previous series returned (it is copied), None: zeros, False: NULL (no sums are kept)
+    (ambient.apply is the rule in numpy and takes the same dict)"""
+    given = dict(surface=surface, side=side, chan=chan, gain=gain, offset=offset, mix_zone=mix_zone, mix=mix)
+    a = AmbientDrive()
+    a.n_sides = len(np.asarray(surface).reshape(-1))
+    keep = {}
+    for name, dtype, needed in _AMBIENT_ARRAYS:
+        if given[name] is None and not needed:
+            continue
+        v = np.ascontiguousarray(given[name], dtype=dtype).reshape(-1)
+        if v.shape != (a.n_sides,):
+            raise ValueError("ambient drive %s: %s for n_sides = %d" % (name, v.shape, a.n_sides))
+        keep[name] = v
+        setattr(a, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if v.size else None)
+    if sum_temperature is False:
+        keep["sum_temperature"] = np.zeros(0)
+    else:
+        total = np.zeros(a.n_sides) if sum_temperature is None else np.array(sum_temperature, dtype=np.float64).reshape(-1)
+        if total.shape != (a.n_sides,):
+            raise ValueError("ambient drive sum_temperature: %s for %d sides" % (total.shape, a.n_sides))
+        keep["sum_temperature"] = total
+        a.sum_temperature = total.ctypes.data_as(_dp) if total.size else None
+    return a, keep
+
+
+def ambient_check(md, ambient, n_sites=1, lib=None, **series):
+    """heat_ambient_check: everything about the ambient drive of a series that needs no device (series arguments as
+    HeatBatch.march_series; ambient: the arguments of make_ambient, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    a, akeep = make_ambient(**ambient) if ambient is not None else (None, None)
+    rc = L.heat_ambient_check(C.byref(desc), int(n_sites), C.byref(s), C.byref(a) if a is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1200,7 +1261,8 @@ class HeatBatch:
         _check(self._L.heat_batch_synchronize(self._h))
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
-                     air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, **series):
+                     air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
+                     **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1237,7 +1299,17 @@ class HeatBatch:
         the faces of a room from the emission of the faces they see, formed on the device at every step from the temperatures
         it holds. Returns what the same call without radiation returns plus irradiance [n_steps, n_receivers] (empty with
         irradiance=False) and sum_irradiance [n_receivers] (pass it as radiation["sum_irradiance"] to the next series): two
-        more elements of the tuple, or two more keys of the dict."""
+        more elements of the tuple, or two more keys of the dict.
+        ambient (a dict of make_ambient's arguments; an empty dict: a drive without sides): heat_batch_march_series_ambient —
+        the temperature of Ambient sides from a channel, a gain and an offset, and optionally mixed with a zone temperature
+        the device holds, formed on the device at every step. Returns what the same call without ambient returns plus
+        ambient_t [n_steps, n_sides] (empty with ambient_t=False) and sum_temperature [n_sides] (pass it as
+        ambient["sum_temperature"] to the next series): two more elements of the tuple, or two more keys of the dict."""
+        if ambient is not None:
+            if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
+                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
+            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q, shades,
+                                          sunlit, radiation, irradiance, ambient, ambient_t)
         if radiation is not None:
             if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
                 sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
@@ -1340,7 +1412,8 @@ class HeatBatch:
         return out
 
     def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None, air=None,
-                          want_path_q=True, shades=None, want_sunlit=True, radiation=None, want_irradiance=True):
+                          want_path_q=True, shades=None, want_sunlit=True, radiation=None, want_irradiance=True, ambient=None,
+                          want_ambient_t=True):
         if report is None and ideal is None and not (want_trace and want_applied):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1378,6 +1451,19 @@ class HeatBatch:
         if radiation is not None:
             rr, rrkeep = make_room_radiation(**radiation)
             irr = np.zeros((s.n_steps if want_irradiance else 0, rr.n_receivers))
+        if ambient is not None:
+            ab, abkeep = make_ambient(**ambient)
+            amb_t = np.zeros((s.n_steps if want_ambient_t else 0, ab.n_sides))
+            rc = self._L.heat_batch_march_series_ambient(
+                self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h) if shades is not None else None,
+                C.byref(g) if gains is not None else None, args[0], C.byref(a) if air is not None else None, *args[1:],
+                transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
+                q.ctypes.data_as(_dp) if air is not None and q.size else None,
+                lit.ctypes.data_as(_dp) if shades is not None and lit.size else None,
+                C.byref(rr) if radiation is not None else None,
+                irr.ctypes.data_as(_dp) if radiation is not None and irr.size else None, C.byref(ab),
+                amb_t.ctypes.data_as(_dp) if amb_t.size else None, C.byref(failed))
+        elif radiation is not None:
             rc = self._L.heat_batch_march_series_radiation(
                 self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h) if shades is not None else None,
                 C.byref(g) if gains is not None else None, args[0], C.byref(a) if air is not None else None, *args[1:],
@@ -1422,13 +1508,28 @@ class HeatBatch:
                 out["sunlit"] = lit
             if radiation is not None:
                 out.update(irradiance=irr, sum_irradiance=rrkeep["sum_irradiance"])
+            if ambient is not None:
+                out.update(ambient_t=amb_t, sum_temperature=abkeep["sum_temperature"])
             return out
         out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
         out = out + ((rep,) if report is not None else ())
         out = out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
         out = out + ((dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep}),) if air is not None else ())
         out = out + ((lit,) if shades is not None else ())
-        return out + ((irr, rrkeep["sum_irradiance"]) if radiation is not None else ())
+        out = out + ((irr, rrkeep["sum_irradiance"]) if radiation is not None else ())
+        return out + ((amb_t, abkeep["sum_temperature"]) if ambient is not None else ())
+
+    def set_ambient(self, surfaces, sides, temperatures):
+        """heat_batch_set_ambient: the temperature (C) of the listed Ambient sides (surface of the model, 0 front / 1 back)
+        from the next march on; durable until set again."""
+        q = np.ascontiguousarray(surfaces, dtype=np.int64).reshape(-1)
+        sd = np.ascontiguousarray(sides, dtype=np.uint8).reshape(-1)
+        v = np.ascontiguousarray(temperatures, dtype=np.float64).reshape(-1)
+        if not (q.shape == sd.shape == v.shape):
+            raise ValueError("set_ambient: %d surfaces, %d sides, %d temperatures" % (q.size, sd.size, v.size))
+        _check(self._L.heat_batch_set_ambient(self._h, q.size, q.ctypes.data_as(_i64p) if q.size else None,
+                                              sd.ctypes.data_as(C.POINTER(C.c_uint8)) if q.size else None,
+                                              v.ctypes.data_as(_dp) if q.size else None))
 
     def failed_surface(self):
         """(index, kind) of the first place the last reported numerical failure was seen; (-1, 0) if none."""

@@ -268,6 +268,7 @@ struct heat_batch {
     std::vector<int64_t> h_node_tile_base;
     std::vector<int32_t> h_node_geom;
     std::vector<int32_t> h_dev_of;  // surface of the caller's descriptor -> device surface
+    std::vector<int32_t> h_kind[2];  // the descriptor's front_kind / back_kind, caller's numbering (heat_batch_set_ambient, heat_ambient_drive)
     SlotResolver *resolver = nullptr;
     int64_t fail_index = -1;         // where the last reported numerical failure happened first (heat_batch_failed_surface)
     int32_t fail_kind = 0;
@@ -501,6 +502,8 @@ int build(heat_batch *b, const heat_batch_desc *d, const heat_batch_options &opt
     b->h_node_tile_base = std::move(p.node_tile_base);
     b->h_node_geom = std::move(p.node_geom);
     b->h_dev_of.assign(p.dev_of.begin(), p.dev_of.end());
+    b->h_kind[0].assign(d->front_kind, d->front_kind + S);
+    b->h_kind[1].assign(d->back_kind, d->back_kind + S);
     HIP_TRY(b->d_nomass_iters.zeros(p.n_nm_counters));
     if (Z > 0) HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&b->h_zone_ab), 2 * Z * sizeof(double)));
 
@@ -1105,6 +1108,16 @@ struct RadiationDev {
     DevBuf<double> factor;       // [NE]
     DevBuf<double> sum;          // [NR]
     DevBuf<double> irradiance;   // [n_steps][NR]
+};
+
+// The device copies of the ambient drive of a series (heat_ambient_drive) or of one heat_batch_set_ambient: the record
+// tables (plan.hpp, AmbientTables), the caller's lists as given, sum_temperature and the ambient_t rows. Declared beside SkyDev.
+struct AmbientDev {
+    DevBuf<uint32_t> rec, peer;   // [N]
+    DevBuf<int32_t> chan, zone;   // [N]
+    DevBuf<double> gain, offset, mix;  // [N]
+    DevBuf<double> sum;           // [N]
+    DevBuf<double> t;             // [n_steps][N]; the setter: the temperatures [N]
 };
 
 template <typename T>
@@ -2091,13 +2104,13 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
 // is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
 // il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit,
 // and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path, and shades == nullptr, or no shade,
-// and radiation == nullptr, or no receiver.
+// and radiation == nullptr, or no receiver, and ambient == nullptr, or no driven side.
 static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
                              double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
                              double *ideal_q = nullptr, const heat_sky *sky = nullptr, const heat_solar_gains *gains = nullptr,
                              double *transmitted = nullptr, heat_air_paths *air = nullptr, double *path_q = nullptr,
                              const heat_shades *shades = nullptr, double *sunlit = nullptr, heat_room_radiation *radiation = nullptr,
-                             double *irradiance = nullptr) {
+                             double *irradiance = nullptr, heat_ambient_drive *ambient = nullptr, double *ambient_t = nullptr) {
     if (failed_step) *failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
@@ -2137,6 +2150,10 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     rc = check_room_radiation(b->n_surf, s, sky, radiation, heat::last_error());
     if (rc) return rc;
     const int64_t NR = radiation ? radiation->n_receivers : 0;  // (entries need a receiver: there are none without)
+    const int32_t *const side_kind[2] = {b->h_kind[0].data(), b->h_kind[1].data()};
+    rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, ambient, heat::last_error());
+    if (rc) return rc;
+    const int64_t NB = ambient ? ambient->n_sides : 0;
     const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
     const int64_t NT = loads ? l->n_thermostats : 0;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
@@ -2306,6 +2323,22 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
             b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
         }
     }
+    // ambient drive: the sides' device records and the back records that follow a front; the mixing zones and factors only
+    // where a side mixes (mix is read only there)
+    AmbientTables abt;
+    std::vector<int32_t> h_amb_zone;
+    std::vector<double> h_amb_mix;
+    if (NB > 0) {
+        build_ambient_tables(S, b->h_dev_of.data(), side_kind, NB, ambient->surface, ambient->side, abt);
+        bool mixes = false;
+        for (int64_t i = 0; i < NB && ambient->mix_zone && !mixes; i++) mixes = ambient->mix_zone[i] >= 0;
+        if (mixes) {
+            h_amb_zone.assign(ambient->mix_zone, ambient->mix_zone + NB);
+            h_amb_mix.assign((size_t)NB, 0.0);
+            for (int64_t i = 0; i < NB; i++)
+                if (h_amb_zone[(size_t)i] >= 0) h_amb_mix[(size_t)i] = ambient->mix[i];
+        }
+    }
     // probes: (buffer, index) of every probed slot
     std::vector<uint8_t> h_pbuf((size_t)P);
     std::vector<uint32_t> h_pidx((size_t)P);
@@ -2388,6 +2421,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     AirDev aird;
     ShadeDev shd;
     RadiationDev rrd;
+    AmbientDev abd;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
@@ -2596,6 +2630,25 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         rrdd.gain[0] = d_gain[2].p, rrdd.gain[1] = d_gain[3].p;
         rrdd.sum = rrd.sum.p;
     }
+    SeriesAmbient abdd{};
+    if (NB > 0) {
+        if ((rc = series_upload(abd.rec, abt.rec.data(), abt.rec.size(), "ambient tables"))) return rc;
+        if ((rc = series_upload(abd.peer, abt.peer.data(), abt.peer.size(), "ambient tables"))) return rc;
+        if ((rc = series_upload(abd.chan, ambient->chan, (size_t)NB, "ambient tables"))) return rc;
+        if ((rc = report_array(abd.gain, ambient->gain, (size_t)NB, true, "ambient tables"))) return rc;
+        if ((rc = report_array(abd.offset, ambient->offset, (size_t)NB, true, "ambient tables"))) return rc;
+        if (!h_amb_zone.empty()) {
+            if ((rc = series_upload(abd.zone, h_amb_zone.data(), h_amb_zone.size(), "ambient tables"))) return rc;
+            if ((rc = series_upload(abd.mix, h_amb_mix.data(), h_amb_mix.size(), "ambient tables"))) return rc;
+        }
+        if ((rc = report_array(abd.sum, ambient->sum_temperature, (size_t)NB, true, "ambient temperature sums"))) return rc;
+        if (ambient_t && (rc = series_alloc(abd.t, (size_t)n_steps * NB, "ambient temperatures"))) return rc;
+        abdd.n_sides = (int)NB;
+        abdd.rec = abd.rec.p, abdd.peer = abd.peer.p, abdd.chan = abd.chan.p;
+        abdd.gain = abd.gain.p, abdd.offset = abd.offset.p;
+        abdd.mix_zone = abd.zone.p, abdd.mix = abd.mix.p;
+        abdd.sum = abd.sum.p;
+    }
     AirPathsDev airp{};
     if (NP > 0) {
         if ((rc = series_upload(aird.i32, apt.i32.data(), apt.i32.size(), "air path tables"))) return rc;
@@ -2641,7 +2694,7 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     }
     double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
     const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> driven inputs -> shades -> sky -> solar gains -> room radiation ->
+    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> ambient drive -> driven inputs -> shades -> sky -> solar gains -> room radiation ->
     // the body of a march call of n_sub -> probes ----
     for (int k = 0; k < n_steps; k++) {
         launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
@@ -2653,6 +2706,9 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
         if (NP > 0)
             launch_series_air_paths((int)Z, airp, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
                                     aird.path_q.p ? aird.path_q.p + (size_t)k * NP : nullptr, b->d_flags.p, b->stream);
+        if (NB > 0)
+            launch_series_ambient(abdd, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_side_const.p,
+                                  abd.t.p ? abd.t.p + (size_t)k * NB : nullptr, b->stream);
         if (driven)
             launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
                                  b->stream);
@@ -2737,6 +2793,8 @@ static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zon
     if (rrd.irradiance.p)
         HIP_TRY(hipMemcpyAsync(irradiance, rrd.irradiance.p, (size_t)n_steps * NR * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     if (rrd.sum.p) HIP_TRY(hipMemcpyAsync(radiation->sum_irradiance, rrd.sum.p, (size_t)NR * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (abd.t.p) HIP_TRY(hipMemcpyAsync(ambient_t, abd.t.p, (size_t)n_steps * NB * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+    if (abd.sum.p) HIP_TRY(hipMemcpyAsync(ambient->sum_temperature, abd.sum.p, (size_t)NB * sizeof(double), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -2798,6 +2856,47 @@ int heat_batch_march_series_radiation(heat_batch *b, const heat_series *s, const
                                       int32_t *failed_step) {
     return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit,
                              radiation, irradiance);
+}
+
+int heat_batch_march_series_ambient(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
+                                    const heat_solar_gains *gains, const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il,
+                                    heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
+                                    double *path_q, double *sunlit, heat_room_radiation *radiation, double *irradiance,
+                                    heat_ambient_drive *ambient, double *ambient_t, int32_t *failed_step) {
+    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit,
+                             radiation, irradiance, ambient, ambient_t);
+}
+
+// The ambient temperature of the listed sides from the next march on: k_series_ambient with the temperatures as its row
+// (lane i takes row[i]; no gain, offset or mix), on the batch's stream behind earlier work. The tables and the values are
+// per-call device buffers: the call waits for its own kernel before it frees them, so the caller's arrays are free too.
+int heat_batch_set_ambient(heat_batch *b, int64_t n, const int64_t *surface, const uint8_t *side, const double *temperature) {
+    if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
+    // ---- everything that needs no device ----
+    // (a shard holds some of the caller's surfaces under numbers of its own: out of scope, as for the series)
+    if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot set ambient temperatures", b->n_ranks);
+    if (n > 0 && !temperature) return fail(HEAT_E_INVALID_ARG, "entry 0: temperature is NULL (count %lld)", (long long)n);
+    const int32_t *const side_kind[2] = {b->h_kind[0].data(), b->h_kind[1].data()};
+    int rc = check_ambient_sides(b->n_surf, side_kind, n, surface, side, "entry", heat::last_error());
+    if (rc) return rc;
+    if (n == 0) return HEAT_OK;
+    AmbientTables abt;
+    build_ambient_tables(b->n_surf, b->h_dev_of.data(), side_kind, n, surface, side, abt);
+    rc = select_device(b);
+    if (rc) return rc;
+    AmbientDev abd;
+    SeriesDrain drain{b};
+    if ((rc = series_upload(abd.rec, abt.rec.data(), abt.rec.size(), "ambient tables"))) return rc;
+    if ((rc = series_upload(abd.peer, abt.peer.data(), abt.peer.size(), "ambient tables"))) return rc;
+    if ((rc = series_upload(abd.t, temperature, (size_t)n, "ambient temperatures"))) return rc;
+    HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
+    SeriesAmbient abdd{};
+    abdd.n_sides = (int)n;
+    abdd.rec = abd.rec.p, abdd.peer = abd.peer.p;
+    launch_series_ambient(abdd, abd.t.p, b->d_zone_T.p, b->d_side_const.p, nullptr, b->stream);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return HEAT_OK;
 }
 
 int64_t heat_batch_nomass_iterations(heat_batch *b) {

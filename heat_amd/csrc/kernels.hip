@@ -2563,6 +2563,37 @@ k_series_room_radiation(int n_surf, SeriesRoomRadiation rr, const double *__rest
     dyn[rec].rad_t = ir_to_rad_temperature(v);
 }
 
+// k_series_ambient — the ambient temperature of every driven side in one step (heat_ambient_drive, include/heat_amd.h), and
+// the body of heat_batch_set_ambient (chan == nullptr: lane i takes row[i]; no gain, offset or mix): one lane per side over
+// structure-of-arrays tables in the caller's order (plan.hpp, AmbientTables). The header's rule, one rounded operation per
+// line, hence no contraction. A lane writes the `ambient` field of its side's record and, for a front whose back is Ambient
+// as well, the `forced` field of that back record (its t_front source, layout.hpp) — plain 8-byte stores; the check has made
+// sure that every record is named once, so every field has one writer. Nothing on the step's head writes the zone
+// temperatures: every zone is read as it was at the start of the step. No LDS, no atomics.
+__global__ void __launch_bounds__(256)
+k_series_ambient(SeriesAmbient a, const double *__restrict__ row, const double *__restrict__ zone_T, SideConst *__restrict__ sc,
+                 double *__restrict__ ambient_row) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_sides) return;
+    double v = row[a.chan != nullptr ? a.chan[i] : i];
+    if (a.gain != nullptr) v = a.gain[i] * v;
+    if (a.offset != nullptr) v = v + a.offset[i];
+    if (a.mix_zone != nullptr) {
+        const int z = a.mix_zone[i];
+        if (z >= 0) {
+            const double d = zone_T[z] - v;
+            const double m = a.mix[i] * d;
+            v = v + m;
+        }
+    }
+    sc[a.rec[i]].ambient = v;
+    const uint32_t peer = a.peer[i];
+    if (peer != kNoAmbientPeer) sc[peer].forced = v;
+    if (ambient_row != nullptr) ambient_row[i] = v;
+    if (a.sum != nullptr) a.sum[i] = a.sum[i] + v;
+}
+
 // Report of a series (heat_series_report, include/heat_amd.h): on the step's tail, beside k_series_probe. Everything below
 // is written without contraction: the statistics are DEFINED as one rounded operation per rule, and a group's bits are to
 // follow from its tables alone.
@@ -3150,6 +3181,12 @@ void launch_series_room_radiation(int n_surf, const SeriesRoomRadiation &rr, con
     if (rr.n_receivers <= 0) return;
     hipLaunchKernelGGL(k_series_room_radiation, dim3((rr.n_receivers + 255) / 256), dim3(256), 0, st, n_surf, rr, row, dyn, sl, mirror,
                        irradiance_row);
+}
+
+void launch_series_ambient(const SeriesAmbient &a, const double *row, const double *zone_T, SideConst *sc, double *ambient_row,
+                           hipStream_t st) {
+    if (a.n_sides <= 0) return;
+    hipLaunchKernelGGL(k_series_ambient, dim3((a.n_sides + 255) / 256), dim3(256), 0, st, a, row, zone_T, sc, ambient_row);
 }
 
 void launch_series_zone_loads(int n_zones, const ZoneLoadsDev &zl, const double *row, const double *zone_T, double *a0, double *b0,

@@ -159,6 +159,25 @@ void launch_series_emission(const SeriesRoomRadiation &rr, const double *T, hipS
 // row: the step's row of the channel table; irradiance_row: the step's row of irradiance, [n_receivers], or nullptr
 void launch_series_room_radiation(int n_surf, const SeriesRoomRadiation &rr, const double *row, SideDyn *dyn, const SlotArrays &sl,
                                   double *mirror, double *irradiance_row, hipStream_t st);
+// Ambient temperatures of a series step (heat_ambient_drive, include/heat_amd.h; tables: plan.hpp, AmbientTables) and of
+// heat_batch_set_ambient: one launch between the step's head and its body, only when there are driven sides — one lane per
+// side. It rewrites SideConst::ambient of the side's record, and SideConst::forced of the back record that carries a front's
+// ambient temperature (layout.hpp); every kernel family reads both from global memory at the start of its launch.
+struct SeriesAmbient {
+    int n_sides;
+    const uint32_t *rec;       // [n_sides] side * S + device surface
+    const uint32_t *peer;      // [n_sides] the back record whose `forced` follows, or kNoAmbientPeer
+    const int32_t *chan;       // [n_sides] channel of the step's row; nullptr: lane i reads row[i] (the setter)
+    const double *gain;        // [n_sides]; nullptr: 1
+    const double *offset;      // [n_sides]; nullptr: 0
+    const int32_t *mix_zone;   // [n_sides] -1: none; nullptr: none anywhere
+    const double *mix;         // [n_sides] read where mix_zone >= 0
+    double *sum;               // [n_sides] sum_temperature; nullptr: not kept
+};
+// row: the step's row of the channel table (the setter: the temperatures); ambient_row: the step's row of ambient_t,
+// [n_sides], or nullptr
+void launch_series_ambient(const SeriesAmbient &a, const double *row, const double *zone_T, SideConst *sc, double *ambient_row,
+                           hipStream_t st);
 // Zone loads of a series step (heat_zone_loads, include/heat_amd.h; tables: plan.hpp, ZoneLoadTables): launched between the
 // step's head and its driven inputs, one lane per zone.
 struct ZoneLoadsDev {

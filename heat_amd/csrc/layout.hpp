@@ -88,6 +88,8 @@ struct alignas(16) SideConst {
                       // kind == KIND_SPACE: the surface's area (model.rs:562-585: what the side's coefficient is weighted with)
     double nx, ny;    // surface normal (for is_windward)
 };
+// "No such record" in a table of side record indices (plan.hpp, AmbientTables::peer).
+constexpr uint32_t kNoAmbientPeer = 0xffffffffu;
 // Inputs other modules write between marches, converted once at upload.
 struct alignas(16) SideDyn {
     double solar;     // incident solar irradiance, clamped as src/surface.rs:916-923 does; FAST classes: times the

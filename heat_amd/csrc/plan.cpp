@@ -2324,6 +2324,111 @@ int check_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *r
     return HEAT_OK;
 }
 
+// ---- ambient temperatures after creation (include/heat_amd.h, heat_batch_set_ambient and heat_ambient_drive) ----
+int check_ambient_sides(int64_t n_surfaces, const int32_t *const kind[2], int64_t n, const int64_t *surface, const uint8_t *side,
+                        const char *what, std::string &err) {
+    if (n < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count (%lld): no %s i", (long long)n, what);
+    if (n == 0) return HEAT_OK;
+    if (n > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 sides (%lld): %s i is 32-bit", (long long)n, what);
+    if (!surface) return failp(err, HEAT_E_INVALID_ARG, "%s 0: surface is NULL (count %lld)", what, (long long)n);
+    if (!side) return failp(err, HEAT_E_INVALID_ARG, "%s 0: side is NULL (count %lld)", what, (long long)n);
+    std::vector<int32_t> seen(2 * (size_t)n_surfaces, -1);  // (surface, side) -> the element that names it
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t q = surface[i];
+        const unsigned sd = side[i];
+        if (sd > 1) return failp(err, HEAT_E_INVALID_ARG, "%s %lld: side %u above 1 (0 front, 1 back)", what, (long long)i, sd);
+        if (q < 0 || q >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "%s %lld: surface %lld outside [0, %lld)", what, (long long)i, (long long)q, (long long)n_surfaces);
+        if (kind[sd][q] != HEAT_BOUNDARY_AMBIENT)
+            return failp(err, HEAT_E_SIZE, "%s %lld: the %s of surface %lld is of kind %d, not HEAT_BOUNDARY_AMBIENT (%d)", what, (long long)i,
+                         sd ? "back" : "front", (long long)q, kind[sd][q], (int)HEAT_BOUNDARY_AMBIENT);
+        int32_t &first = seen[(size_t)sd * n_surfaces + q];
+        if (first >= 0)
+            return failp(err, HEAT_E_SIZE, "%s %lld: the %s of surface %lld is %s %d already: an input has one source", what, (long long)i,
+                         sd ? "back" : "front", (long long)q, what, first);
+        first = (int32_t)i;
+    }
+    return HEAT_OK;
+}
+
+int check_ambient(int64_t n_surfaces, const int32_t *const kind[2], int64_t n_zones, const heat_series *s, const heat_ambient_drive *a,
+                  std::string &err) {
+    if (!a) return HEAT_OK;
+    const int64_t N = a->n_sides;
+    int rc = check_ambient_sides(n_surfaces, kind, N, a->surface, a->side, "ambient side", err);
+    if (rc || N == 0) return rc;
+    if (!a->chan) return failp(err, HEAT_E_INVALID_ARG, "ambient side 0: chan is NULL (n_sides %lld)", (long long)N);
+    for (int64_t i = 0; i < N; i++) {
+        if (a->gain && !std::isfinite(a->gain[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "ambient side %lld: gain = %g is not finite", (long long)i, a->gain[i]);
+        if (a->offset && !std::isfinite(a->offset[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "ambient side %lld: offset = %g is not finite", (long long)i, a->offset[i]);
+        const int32_t z = a->mix_zone ? a->mix_zone[i] : -1;
+        if (z >= 0 && !a->mix)
+            return failp(err, HEAT_E_INVALID_ARG, "ambient side %lld: mix_zone %d, but mix is NULL", (long long)i, z);
+        if (z >= 0 && z < n_zones && !std::isfinite(a->mix[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "ambient side %lld: mix = %g is not finite", (long long)i, a->mix[i]);
+        if (a->chan[i] < 0 || a->chan[i] >= s->n_channels)
+            return failp(err, HEAT_E_SIZE, "ambient side %lld: channel %d outside [0, %d)", (long long)i, a->chan[i], s->n_channels);
+        if (z < -1 || z >= n_zones)
+            return failp(err, HEAT_E_SIZE, "ambient side %lld: mix_zone %d outside [-1, %lld)", (long long)i, z, (long long)n_zones);
+    }
+    return HEAT_OK;
+}
+
+void build_ambient_tables(int64_t n_surfaces, const int32_t *dev_of, const int32_t *const kind[2], int64_t n, const int64_t *surface,
+                          const uint8_t *side, AmbientTables &t) {
+    t.rec.clear();
+    t.peer.clear();
+    if (n <= 0) return;
+    t.rec.resize((size_t)n);
+    t.peer.resize((size_t)n);
+    for (int64_t i = 0; i < n; i++) {
+        const int64_t q = surface[i], d = dev_of ? (int64_t)dev_of[q] : q;
+        t.rec[(size_t)i] = (uint32_t)((int64_t)side[i] * n_surfaces + d);
+        // a FRONT whose surface's BACK is Ambient too: that back record's `forced` slot carries this temperature
+        t.peer[(size_t)i] = (side[i] == 0 && kind[1][q] == HEAT_BOUNDARY_AMBIENT) ? (uint32_t)(n_surfaces + d) : kNoAmbientPeer;
+    }
+}
+
+int check_ambient_tables(int64_t n_surfaces, const int32_t *dev_of, const int32_t *const kind[2], int64_t n, const int64_t *surface,
+                         const uint8_t *side, const AmbientTables &t, std::string &err) {
+    if (n <= 0) {
+        if (!t.rec.empty() || !t.peer.empty()) return failp(err, HEAT_E_SIZE, "ambient tables: tables without an ambient side i");
+        return HEAT_OK;
+    }
+    if (t.rec.size() != (size_t)n || t.peer.size() != (size_t)n)
+        return failp(err, HEAT_E_SIZE, "ambient tables: %zu records and %zu peers for ambient side i < %lld", t.rec.size(), t.peer.size(),
+                     (long long)n);
+    // device surface -> the caller's (the inverse of dev_of), to read the kinds of a record
+    std::vector<int64_t> orig_of((size_t)n_surfaces, -1);
+    for (int64_t q = 0; q < n_surfaces; q++) {
+        const int64_t d = dev_of ? (int64_t)dev_of[q] : q;
+        if (d < 0 || d >= n_surfaces || orig_of[(size_t)d] >= 0)
+            return failp(err, HEAT_E_SIZE, "ambient tables: surface %lld has device surface %lld, taken or outside [0, %lld)", (long long)q,
+                         (long long)d, (long long)n_surfaces);
+        orig_of[(size_t)d] = q;
+    }
+    std::vector<uint8_t> named(2 * (size_t)n_surfaces, 0);
+    for (int64_t i = 0; i < n; i++) {
+        const uint64_t rec = t.rec[(size_t)i];
+        if (rec >= 2 * (uint64_t)n_surfaces)
+            return failp(err, HEAT_E_SIZE, "ambient tables: ambient side %lld has record %llu outside [0, %lld)", (long long)i,
+                         (unsigned long long)rec, (long long)(2 * n_surfaces));
+        const int sd = rec >= (uint64_t)n_surfaces;
+        const int64_t d = (int64_t)rec - (int64_t)sd * n_surfaces, q = orig_of[(size_t)d];
+        if (q != surface[i] || sd != (int)side[i] || kind[sd][q] != HEAT_BOUNDARY_AMBIENT)
+            return failp(err, HEAT_E_SIZE, "ambient tables: ambient side %lld has the record of the %s of surface %lld", (long long)i,
+                         sd ? "back" : "front", (long long)q);
+        if (named[(size_t)rec]) return failp(err, HEAT_E_SIZE, "ambient tables: ambient side %lld: record %llu is named twice", (long long)i, (unsigned long long)rec);
+        named[(size_t)rec] = 1;
+        const uint32_t want = (sd == 0 && kind[1][q] == HEAT_BOUNDARY_AMBIENT) ? (uint32_t)(n_surfaces + d) : kNoAmbientPeer;
+        if (t.peer[(size_t)i] != want)
+            return failp(err, HEAT_E_SIZE, "ambient tables: ambient side %lld has peer %u, not %u", (long long)i, t.peer[(size_t)i], want);
+    }
+    return HEAT_OK;
+}
+
 static inline int64_t gain_key(int64_t n_surfaces, const int32_t *dev_of, const heat_solar_gains *g, int64_t i) {
     const int64_t q = g->en_surface[i];
     return (int64_t)g->en_side[i] * n_surfaces + (dev_of ? (int64_t)dev_of[q] : q);
@@ -2700,6 +2805,19 @@ int heat_room_radiation_check(const heat_batch_desc *desc, int32_t n_sites, cons
     heat::RoomRadiationTables t;
     heat::build_room_radiation_tables(desc->n_surfaces, radiation, t);
     return heat::check_room_radiation_tables(desc->n_surfaces, radiation, t, heat::last_error());
+}
+
+int heat_ambient_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_ambient_drive *a) {
+    int rc = heat_series_check(desc, n_sites, s);
+    if (rc) return rc;
+    const int32_t *const kind[2] = {desc->front_kind, desc->back_kind};
+    rc = heat::check_ambient(desc->n_surfaces, kind, desc->n_zones, s, a, heat::last_error());
+    if (rc || !a) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see). Without a batch there is no device layout: the records stand in the caller's surface order.
+    heat::AmbientTables t;
+    heat::build_ambient_tables(desc->n_surfaces, nullptr, kind, a->n_sides, a->surface, a->side, t);
+    return heat::check_ambient_tables(desc->n_surfaces, nullptr, kind, a->n_sides, a->surface, a->side, t, heat::last_error());
 }
 
 int heat_air_paths_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_air_paths *air) {

@@ -258,6 +258,32 @@ void build_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *
 // HEAT_OK or HEAT_E_SIZE.
 int check_room_radiation_tables(int64_t n_surfaces, const heat_room_radiation *rr, const RoomRadiationTables &t, std::string &err);
 
+// Ambient temperatures after creation (heat_batch_set_ambient, heat_ambient_drive; include/heat_amd.h). kind[0] / kind[1]:
+// the descriptor's front_kind / back_kind in the CALLER's numbering (the batch keeps a copy). The sides of a list: n < 0, a
+// NULL array with n > 0, a side byte above 1 -> HEAT_E_INVALID_ARG; a surface out of range, a side that is not Ambient, the
+// same (surface, side) twice -> HEAT_E_SIZE; `what` ("entry", "ambient side") names the element in the message.
+int check_ambient_sides(int64_t n_surfaces, const int32_t *const kind[2], int64_t n, const int64_t *surface, const uint8_t *side,
+                        const char *what, std::string &err);
+// Everything heat_ambient_check promises about the drive itself; a == nullptr is none. s has passed check_series. HEAT_OK or a
+// negative heat_status with `err` set, naming "ambient side i".
+int check_ambient(int64_t n_surfaces, const int32_t *const kind[2], int64_t n_zones, const heat_series *s, const heat_ambient_drive *a,
+                  std::string &err);
+// The tables of k_series_ambient (one lane per listed side), shared by the setter and the drive: the side's device record
+// side * n_surfaces + dev_of[surface] (dev_of == nullptr: the identity), and for a FRONT whose surface's BACK is Ambient as
+// well that back record, n_surfaces + dev_of[surface], whose `forced` slot carries the front's ambient temperature
+// (layout.hpp, SideConst) — kNoAmbientPeer (layout.hpp) otherwise.
+struct AmbientTables {
+    std::vector<uint32_t> rec;   // [n]
+    std::vector<uint32_t> peer;  // [n]
+};
+// (of sides that passed check_ambient_sides)
+void build_ambient_tables(int64_t n_surfaces, const int32_t *dev_of, const int32_t *const kind[2], int64_t n, const int64_t *surface,
+                          const uint8_t *side, AmbientTables &t);
+// The tables against the caller's lists (used by the host-only check): every record inside [0, 2 n_surfaces), of an Ambient
+// side, named once, and the peer exactly where the rule puts one. HEAT_OK or HEAT_E_SIZE.
+int check_ambient_tables(int64_t n_surfaces, const int32_t *dev_of, const int32_t *const kind[2], int64_t n, const int64_t *surface,
+                         const uint8_t *side, const AmbientTables &t, std::string &err);
+
 // Report of a series (heat_series_report, include/heat_amd.h). Everything heat_series_report_check promises about the
 // report itself; r == nullptr is no report. l has passed check_zone_loads. HEAT_OK or a negative
 // heat_status with `err` set, naming "group g" or "group entry i".

@@ -843,6 +843,79 @@ int heat_batch_march_series_radiation(heat_batch *b, const heat_series *s, const
                                       double *applied, double *ideal_q, double *transmitted, double *path_q, double *sunlit,
                                       heat_room_radiation *radiation /* nullable */,
                                       double *irradiance /* [n_steps][n_receivers], nullable */, int32_t *failed_step);
+
+/*
+ * Ambient temperatures after creation: a side of kind HEAT_BOUNDARY_AMBIENT takes Boundary::AmbientTemperature
+ * { temperature } from front_ambient / back_ambient of the descriptor; these two entry points change it afterwards — per call
+ * (heat_batch_set_ambient) and per step of a series (heat_ambient_drive). What it is for: a floor slab or basement wall at
+ * the month's ground temperature (HEAT_BOUNDARY_GROUND is refused, the reference panics there), a party wall to a neighbour
+ * at a scheduled temperature, and an unheated neighbour space (attic, garage, stairwell) by the temperature-reduction
+ * factor b of EN ISO 13789 / EN 12831, T_u = T_out + (1 - b) * (T_zone - T_out), which needs a zone temperature only the
+ * device holds. The reference has no counterpart (its boundaries are fixed at construction); the rule below is this
+ * library's own contract, defined against the per-call loop with the same rule on the host (heat_amd/ambient.py, apply()).
+ *
+ * heat_batch_set_ambient sets the temperature (degrees C) of the n listed sides — side[i] (0 front, 1 back) of surface
+ * surface[i], the descriptor's numbering — from the next march on. The value is durable until set again: it survives
+ * heat_batch_upload_state, heat_batch_upload_inputs, heat_batch_set_fusion, graph replay (use_graph) and a series. It is
+ * ordered on the batch's stream behind earlier work; the caller's arrays are free when the call returns. Where the side is a
+ * FRONT whose surface's BACK is Ambient as well, the back side's radiant temperature (t_front, surface.rs:672-686) follows.
+ * Any double is accepted, a NaN included: it acts as a NaN in the descriptor's field would. Checks, all before any device
+ * work, the message names "entry i": n < 0, a NULL array with n > 0, a side byte above 1 -> HEAT_E_INVALID_ARG; a surface
+ * outside [0, n_surfaces), a side whose kind is not HEAT_BOUNDARY_AMBIENT, the same (surface, side) twice -> HEAT_E_SIZE.
+ * n == 0 does nothing. A sharded batch (n_ranks > 1) is refused with HEAT_E_INVALID_ARG, as the series refuses one.
+ *
+ * heat_ambient_drive: driven side i is side[i] of surface[i], of kind HEAT_BOUNDARY_AMBIENT. Step k, behind the step's head
+ * and before its sub-timesteps (nothing else in a step's preparation reads or writes these temperatures); T = the zone
+ * temperatures the device holds when the step starts (what step k - 1 left), row = channel[k]; every line is ONE rounded f64
+ * operation in the order written, no fused multiply-add:
+ *   v = row[chan[i]]
+ *   if gain:    v = gain[i] * v
+ *   if offset:  v = v + offset[i]
+ *   if mix_zone and mix_zone[i] >= 0:   d = T[mix_zone[i]] - v;   m = mix[i] * d;   v = v + m
+ *   ambient temperature of (surface[i], side[i]) = v      (and the back side's t_front, as in the setter)
+ *   ambient_t[k * n_sides + i] = v;   sum_temperature[i] = sum_temperature[i] + v
+ * mix is 1 - b of EN ISO 13789 (b = 1: the outside channel alone; b = 0: the zone's temperature up to rounding). Every zone
+ * temperature is read as it was at the START of the step, as air paths read it. A side not listed keeps what the descriptor,
+ * the setter or an earlier series left; after the series the listed sides hold the values of step n_steps - 1, as the
+ * per-call loop would leave them. Device state, trace, ambient_t and the sums are bit for bit what n_steps successive
+ * heat_batch_march_ex calls give with heat_batch_set_ambient before call k, the values formed by the rule from the zone
+ * temperatures downloaded before that call. sum_temperature (in/out, nullable) adds onto what the caller passes; the rule
+ * has no other memory: a series of k steps followed by one of n - k with the returned array gives the bits of the series of
+ * n. ambient_t is nullable; an array that is not asked for costs no traffic and changes no bit of the others. n_sub == 0
+ * still sets every step's values. A NaN channel value propagates as a NaN in the descriptor's field would. Weather sites
+ * need nothing; sharded batches are refused as by the series.
+ * heat_ambient_check (host-only; it also builds and verifies the tables the march uploads) and
+ * heat_batch_march_series_ambient run the same checks before any device work; every message names "ambient side i": a
+ * negative count, a NULL array a positive count needs (gain, offset, mix_zone, sum_temperature may be NULL; mix may be NULL
+ * when no mix_zone is >= 0), a side byte above 1, a gain, offset or (where mix_zone is >= 0) mix that is not finite ->
+ * HEAT_E_INVALID_ARG; a surface outside [0, n_surfaces), a side that is not Ambient, a channel outside [0, n_channels), a
+ * mix_zone outside [-1, n_zones), the same (surface, side) twice (an input has ONE source) -> HEAT_E_SIZE.
+ * heat_batch_march_series_ambient with ambient == NULL, or n_sides == 0, is heat_batch_march_series_radiation exactly (same
+ * launches, same bits).
+ */
+int heat_batch_set_ambient(heat_batch *b, int64_t n, const int64_t *surface /* [n] descriptor numbering */,
+                           const uint8_t *side /* [n] 0 front, 1 back */, const double *temperature /* [n] C */);
+
+typedef struct heat_ambient_drive {
+    int64_t n_sides;
+    const int64_t *surface;      /* [n_sides] */
+    const uint8_t *side;         /* [n_sides] 0 front, 1 back; the side's kind is HEAT_BOUNDARY_AMBIENT */
+    const int32_t *chan;         /* [n_sides] channel of the series, C */
+    const double *gain, *offset; /* [n_sides], nullable = 1 / = 0 */
+    const int32_t *mix_zone;     /* [n_sides], nullable / -1: none */
+    const double *mix;           /* [n_sides], read only where mix_zone >= 0 (1 - b of EN ISO 13789) */
+    double *sum_temperature;     /* [n_sides] in/out, nullable */
+} heat_ambient_drive;
+
+int heat_ambient_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_ambient_drive *a); /* host-only */
+int heat_batch_march_series_ambient(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                    const heat_shades *shades /* nullable */, const heat_solar_gains *gains /* nullable */,
+                                    const heat_zone_loads *l /* nullable */, heat_air_paths *air /* nullable */,
+                                    heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
+                                    double *applied, double *ideal_q, double *transmitted, double *path_q, double *sunlit,
+                                    heat_room_radiation *radiation /* nullable */, double *irradiance,
+                                    heat_ambient_drive *ambient /* nullable */,
+                                    double *ambient_t /* [n_steps][n_sides], nullable */, int32_t *failed_step);
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

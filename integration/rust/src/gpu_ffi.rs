@@ -74,6 +74,11 @@ pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub b
     pub n_entries: i64, pub en_receiver: *const i64, pub en_surface: *const i64, pub en_side: *const u8,
     pub en_chan: *const i32, pub en_factor: *const f64,
 }
+// heat_ambient_drive: ambient-side temperatures of a series, per step
+#[repr(C)] pub struct HeatAmbientDrive {
+    pub n_sides: i64, pub surface: *const i64, pub side: *const u8, pub chan: *const i32, pub gain: *const f64,
+    pub offset: *const f64, pub mix_zone: *const i32, pub mix: *const f64, pub sum_temperature: *mut f64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -135,6 +140,15 @@ extern "C" {
                                              il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
                                              ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
                                              radiation: *mut HeatRoomRadiation, irradiance: *mut f64, failed_step: *mut i32) -> c_int;
+    // ambient temperatures after creation: per call, and per step of a series from a channel and a zone temperature
+    pub fn heat_batch_set_ambient(b: *mut HeatBatch, n: i64, surface: *const i64, side: *const u8, temperature: *const f64) -> c_int;
+    pub fn heat_ambient_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, a: *const HeatAmbientDrive) -> c_int;
+    pub fn heat_batch_march_series_ambient(b: *mut HeatBatch, s: *const HeatSeries, sky: *const HeatSky, shades: *const HeatShades,
+                                           gains: *const HeatSolarGains, l: *const HeatZoneLoads, air: *mut HeatAirPaths,
+                                           il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
+                                           ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
+                                           radiation: *mut HeatRoomRadiation, irradiance: *mut f64, ambient: *mut HeatAmbientDrive,
+                                           ambient_t: *mut f64, failed_step: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

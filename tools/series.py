@@ -69,18 +69,28 @@ walls 1 M receivers, 1 M distinct emitters, 7 M entries) two legs, alternated in
 and writes profiles/series_radiation.json: ms per step of each, R - D, a series of ONE step of each and the per-step times
 once the calls are set up, the bytes a step of k_series_emission and k_series_room_radiation moves. No time is a pass
 criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation]
+With --ambient (heat_batch_march_series_ambient; the headline's walls with the back side of one wall in ten turned to
+Boundary::AmbientTemperature — at 1 M walls 100 000 driven sides —, channels, loads and probes as in leg D plus four
+temperature channels) two legs, alternated in the same way:
+  N  the series with loads and the drive NULL: the launches of the parent's path
+  M  the same series with every Ambient back driven from a temperature channel with a gain and an offset, every second one
+     mixed (b = 0.5) with the temperature of the zone next to its wall's own (ambient_t not recorded)
+and writes profiles/series_ambient.json: ms per step of each, M - N, a series of ONE step of each and the per-step times once
+the calls are set up, the bytes a step of k_series_ambient moves, and — where the kernel trace of one M series has been taken
+(--one-series --ambient under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_ambient_kernel_stats.csv) —
+k_series_ambient per step. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
                                                      with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
                                                      a series of leg J; with --air a series of leg A; with --shades a series of leg S;
-                                                     with --radiation a series of leg R"""
+                                                     with --radiation a series of leg R; with --ambient a series of leg M"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, air_paths as apm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, ambient as ambm, air_paths as apm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -89,7 +99,8 @@ GAINS = "--gains" in sys.argv
 AIR = "--air" in sys.argv
 SHADES = "--shades" in sys.argv
 RADIATION = "--radiation" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION
+AMBIENT = "--ambient" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -100,6 +111,11 @@ KEYS = ("solar_front", "solar_back", "ir_front", "ir_back")
 
 md, st0 = mdl.uniform_massive(S, n=32, Z=max(1, S // (7 if RADIATION else 100)), dt=45.0)
 rng = np.random.default_rng(1)
+if AMBIENT:
+    # the back of one wall in ten faces an ambient temperature (a ground slab, a neighbour, an unheated space)
+    ambient_walls = np.arange(0, S, 10, dtype=np.int64)
+    md["back_kind"] = np.where(np.arange(S) % 10 == 0, mdl.AMBIENT, md["back_kind"]).astype(np.int32)
+    md["back_ambient"] = np.where(np.arange(S) % 10 == 0, 12.0, md["back_ambient"])
 channel = np.concatenate([rng.uniform(0.0, 600.0, (STEPS, N_CHANNELS // 2)), rng.uniform(300.0, 450.0, (STEPS, N_CHANNELS // 2))], axis=1)
 drives = {k: ((rng.integers(0, N_CHANNELS // 2, S) + (N_CHANNELS // 2 if i >= 2 else 0)).astype(np.int32), rng.uniform(0.5, 1.5, S))
           for i, k in enumerate(KEYS)}
@@ -197,6 +213,26 @@ if RADIATION:
                                                                    **dict(drives, ir_back=(not_driven, drives["ir_back"][1])))
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace)) and np.all(np.isfinite(total)) and np.all(total > 0)
+        return dt * 1e3 / steps
+if AMBIENT:
+    # four more channels (ground, two neighbours, outdoor air; C); half of the sides mixed with the next zone's temperature
+    c_amb = channel.shape[1]
+    channel = np.concatenate([channel, rng.uniform(8.0, 14.0, (STEPS, 1)), rng.uniform(16.0, 24.0, (STEPS, 2)), rng.uniform(-5.0, 30.0, (STEPS, 1))], axis=1)
+    NB = len(ambient_walls)
+    mixes = np.arange(NB) % 2 == 1
+    ambient_args = dict(surface=ambient_walls, side=np.ones(NB, np.uint8), chan=(c_amb + np.where(mixes, 3, np.arange(NB) % 3)).astype(np.int32),
+                        gain=rng.uniform(0.9, 1.1, NB), offset=rng.uniform(-1.0, 1.0, NB),
+                        mix_zone=np.where(mixes, (md["back_zone"][ambient_walls] + 1) % Z, -1).astype(np.int32),
+                        mix=np.where(mixes, ambm.b_factor(0.5), 0.0))
+    AMBIENT_BYTES = dict(per_side=4 + 4 + 4 + 8 + 8 + 4 + 8 + 8 + 8, per_mixing_side_more=8)   # rec, peer, chan, gain, offset, mix zone, mix, sum (read + write: 16), the record's field; the zone
+
+    def leg_m(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, amb_t, total = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                                     ambient=ambient_args, ambient_t=False, **drives)
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace)) and np.all(np.isfinite(total))
         return dt * 1e3 / steps
 if GAINS:
     assert np.all(np.diff(md["back_zone"]) >= 0) and np.all(md["back_kind"] == mdl.SPACE)
@@ -462,6 +498,30 @@ with HeatBatch(md) as b:
                   "step: D %.2f ms, R %.2f ms -> per step without the set-up D %.3f, R %.3f, R - D = %+.3f (%d entries, %d steps, median "
                   "of %d rounds)" % (n_sub, D, R, R - D, R / D, D1, R1, Ds, Rs, Rs - Ds, NE, STEPS, ROUNDS), flush=True)
             continue
+        if AMBIENT:
+            leg_d(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_m(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with an ambient drive: M %.3f ms per step" % leg_m(b, w, n_sub, STEPS))
+                continue
+            n, m, n1, m1 = [], [], [], []
+            for r in range(ROUNDS):
+                n.append(leg_d(b, w, n_sub, STEPS))
+                m.append(leg_m(b, w, n_sub, STEPS))
+                n1.append(leg_d(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                m1.append(leg_m(b, w, n_sub, 1))
+            N_, M_, N1, M1 = (float(np.median(v)) for v in (n, m, n1, m1))
+            Ns, Ms = (N_ * STEPS - N1) / (STEPS - 1), (M_ * STEPS - M1) / (STEPS - 1)  # per step once the call is set up
+            nbytes = AMBIENT_BYTES["per_side"] * NB + AMBIENT_BYTES["per_mixing_side_more"] * int(mixes.sum())
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                N_drive_null_ms=N_, M_ambient_drive_ms=M_, M_minus_N_ms=M_ - N_, M_over_N=M_ / N_, N_series_of_one_step_ms=N1,
+                M_series_of_one_step_ms=M1, N_without_setup_ms=Ns, M_without_setup_ms=Ms, M_minus_N_without_setup_ms=Ms - Ns,
+                driven_sides=int(NB), mixing_sides=int(mixes.sum()), bytes=AMBIENT_BYTES, bytes_per_step_of_k_series_ambient=int(nbytes),
+                all_rounds=dict(N=n, M=m, N_one_step=n1, M_one_step=m1))
+            print("n_sub %2d: N drive NULL %.3f ms/step, M ambient drive %.3f -> M - N = %+.3f ms, M / N = %.4f; a series of one step: "
+                  "N %.2f ms, M %.2f ms -> per step without the set-up N %.3f, M %.3f, M - N = %+.3f (%d driven sides, %d steps, median of "
+                  "%d rounds)" % (n_sub, N_, M_, M_ - N_, M_ / N_, N1, M1, Ns, Ms, Ms - Ns, NB, STEPS, ROUNDS), flush=True)
+            continue
         if SHADES:
             leg_k(b, w, n_sub, min(STEPS, 10))  # warm-up
             leg_s(b, w, n_sub, min(STEPS, 10))
@@ -718,9 +778,23 @@ if SHADES and not ONE:
             us["k_series_shading"], nbytes / us["k_series_shading"] / 1e6, us["k_series_sky"]))
     else:
         print("no kernel trace at %s" % stats)
+if AMBIENT and not ONE:
+    # the kernel trace of one M series (--one-series --ambient under rocprofv3 --kernel-trace --stats, a run of its own), where
+    # it has been taken: k_series_ambient alone
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_ambient_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = float(rows["k_series_ambient"]["AverageNs"]) / 1e3
+        result["kernel_trace_of_one_M_series"] = dict(k_series_ambient_us_per_step=us, calls=int(rows["k_series_ambient"]["Calls"]))
+        print("kernel trace: k_series_ambient %.2f us per step" % us)
+    else:
+        print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
