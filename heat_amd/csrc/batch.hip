@@ -871,9 +871,42 @@ void enqueue_zones(heat_batch *b, int mode) {
                  b->d_flags.p, mode, zl, nl, b->d_slot_of.p, b->n_shared, b->zone_rows, b->stream);
 }
 
+struct TeamShape {
+    int team_size = 0, room = 0, n_teams = 0;
+};
+
+// The shape of every class's team launch for a call of n_sub sub-timesteps, and the limits of the exchange tags. A call
+// the teams cannot march is refused HERE, before anything of the call is on a stream: a refusal after the plain resident
+// launches (or another class's teams) had started would leave part of the batch n_sub sub-timesteps ahead of the rest.
+static int team_shapes(const heat_batch *b, int n_sub, TeamShape (&shape)[kNumFast]) {
+    for (int c = 0; c < kNumFast; c++) {
+        const int n_super = (int)b->h_team_supers[c].size();
+        if (n_super == 0) continue;
+        if (n_sub > 4095) return fail(HEAT_E_INVALID_ARG, "a march call of %d sub-timesteps: the team exchange tags 4095 at most", n_sub);
+        // what the chip holds of this variant, less a margin (the hardware may admit a workgroup per compute unit fewer than
+        // the occupancy arithmetic says); other kernels in flight only delay a member's start, they end by themselves
+        // (at most two per compute unit whatever the query says: the variants hold 171-256 registers)
+        static const int team_room_env = getenv("HEAT_AMD_TEAM_ROOM") ? atoi(getenv("HEAT_AMD_TEAM_ROOM")) : 0;  // measurement
+        TeamShape &ts = shape[c];
+        ts.room = team_room_env > 0 ? team_room_env : b->n_cu * std::min(2, fused_team_blocks_per_cu(kFastM[c], kFastNM[c], b->na.pal_stride));
+        ts.team_size = 2;
+        for (const FusedSuper &su : b->h_team_supers[c]) ts.team_size = std::max(ts.team_size, (int)su.n_members);
+        ts.n_teams = std::min(n_super, std::max(0, ts.room - ts.room / 8) / ts.team_size);
+        if (ts.n_teams >= 1 && (n_super + ts.n_teams - 1) / ts.n_teams > 1023)
+            return fail(HEAT_E_SIZE, "%d clusters for %d teams: the exchange tags 1023 rounds per launch at most", n_super, ts.n_teams);
+        if (ts.n_teams < 1) return fail(HEAT_E_DEVICE, "the device holds %d workgroups of the team variant: not one team", ts.room);
+    }
+    return HEAT_OK;
+}
+
 // The cluster-resident march: every fused workgroup marches n_sub sub-timesteps in one launch per class.
 // streamed_beside: other surfaces of the batch are streamed on the batch's stream while this launch runs.
 int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside = false) {
+    TeamShape team_shape[kNumFast];
+    {
+        const int rc = team_shapes(b, n_sub, team_shape);
+        if (rc) return rc;
+    }
     FusedArgs fa{};
     {   // zig-zag over march calls (see enqueue_surfaces): what the last call wrote back last is this call's first read
         static const bool zigzag_off = getenv("HEAT_AMD_NO_ZIGZAG") != nullptr;  // measurement
@@ -947,18 +980,7 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
     for (int c = 0; c < kNumFast; c++) {
         const int n_super = (int)b->h_team_supers[c].size();
         if (n_super == 0) continue;
-        if (n_sub > 4095) return fail(HEAT_E_INVALID_ARG, "a march call of %d sub-timesteps: the team exchange tags 4095 at most", n_sub);
-        // what the chip holds of this variant, less a margin (the hardware may admit a workgroup per compute unit fewer than
-        // the occupancy arithmetic says); other kernels in flight only delay a member's start, they end by themselves
-        // (at most two per compute unit whatever the query says: the variants hold 171-256 registers)
-        static const int team_room_env = getenv("HEAT_AMD_TEAM_ROOM") ? atoi(getenv("HEAT_AMD_TEAM_ROOM")) : 0;  // measurement
-        const int room = team_room_env > 0 ? team_room_env : n_cu * std::min(2, fused_team_blocks_per_cu(kFastM[c], kFastNM[c], b->na.pal_stride));
-        int team_size = 2;
-        for (const FusedSuper &su : b->h_team_supers[c]) team_size = std::max(team_size, (int)su.n_members);
-        const int n_teams = std::min(n_super, std::max(0, room - room / 8) / team_size);
-        if (n_teams >= 1 && (n_super + n_teams - 1) / n_teams > 1023)
-            return fail(HEAT_E_SIZE, "%d clusters for %d teams: the exchange tags 1023 rounds per launch at most", n_super, n_teams);
-        if (n_teams < 1) return fail(HEAT_E_DEVICE, "the device holds %d workgroups of the team variant: not one team", room);
+        const int team_size = team_shape[c].team_size, n_teams = team_shape[c].n_teams;  // (checked before the first launch)
         if (b->xbuf_teams < n_teams) {
             HIP_TRY(b->d_xbuf.zeros((size_t)n_teams * 2 * kTeamZones * kTeamMax * 4));
             b->xbuf_teams = n_teams;

@@ -231,3 +231,48 @@ def ambient_backs(md, state, rng, fraction):
         sys.path.insert(0, tools)
     import fuzz
     return fuzz.ambient_backs(md, state, rng, fraction)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Buildings for the team tests (tests/test_team_rounds_gpu.py)
+def faced_buildings(md, state, every=3, seed=0):
+    """No-mass facings on every `every`-th wall of a modeldict.partitioned_buildings model (all-massive walls of one
+    material each, four nodes at least), in place, in the pattern of modeldict.ragged_mixed: node 0 and node n-1 carry no
+    mass, their neighbours half an element's mass, the first and the last segment are a thin insulation layer of
+    U in U[0.5, 3]; both emissivities of those walls are scaled by 0.2 / 0.9, which keeps the reference's no-mass update
+    in its convergent regime (see ragged_mixed). Returns (md, state); the state's layout does not change."""
+    rng = np.random.default_rng(seed)
+    S = int(md["n_surfaces"])
+    off = np.asarray(md["node_offset"], dtype=np.int64)
+    assert np.all(np.diff(off) >= 4)
+    faced = np.arange(S) % every == 0
+    first, last = off[:-1][faced], off[1:][faced] - 1
+    mass = np.array(md["mass"], dtype=np.float64)
+    u = np.array(md["uvalue"], dtype=np.float64)
+    half = mass[first].copy()          # an end node of an all-massive wall holds half an element's mass
+    mass[first] = 0.0
+    mass[last] = 0.0
+    mass[first + 1] = half
+    mass[last - 1] = half
+    u_ins = rng.uniform(0.5, 3.0, S)[faced]
+    u[first] = u_ins
+    u[last - 1] = u_ins
+    md["mass"], md["uvalue"] = mass, u
+    for key in ("front_emissivity", "back_emissivity"):
+        md[key] = np.where(faced, np.asarray(md[key]) * (0.2 / 0.9), md[key])
+    return md, state
+
+
+def uneven_parts(n, rooms_list, seed):
+    """One building of 12 walls a room (n nodes each) per entry of rooms_list: [(md, state), ...]."""
+    return [mdl.partitioned_buildings(rooms * 12, n, rooms=rooms, dt=45.0, seed=seed + 17 * k)
+            for k, rooms in enumerate(rooms_list)]
+
+
+def uneven_buildings(n, rooms_list, seed):
+    """The buildings of uneven_parts joined by modeldict.concat into ONE site: clusters of different sizes in one batch —
+    teams of different member counts, and plain resident workgroups beside them. Returns (md, state); the state is the
+    buildings' states back to back."""
+    parts = uneven_parts(n, rooms_list, seed)
+    md, _ = mdl.concat([m for m, _ in parts])
+    return md, np.concatenate([s for _, s in parts])
