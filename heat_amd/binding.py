@@ -1160,6 +1160,12 @@ def comm_unique_id():
     return bytes(buf)
 
 
+def _zone_rows_fit(keep, n_zones):
+    for k in ("zone_a0", "zone_b0"):
+        if k in keep and keep[k].shape[1] != n_zones:
+            raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], n_zones))
+
+
 class HeatBatch:
     """Device-resident batch of surfaces + zones (≙ ThermalModel, src/model.rs:54-77)."""
 
@@ -1305,219 +1311,111 @@ class HeatBatch:
         the device holds, formed on the device at every step. Returns what the same call without ambient returns plus
         ambient_t [n_steps, n_sides] (empty with ambient_t=False) and sum_temperature [n_sides] (pass it as
         ambient["sum_temperature"] to the next series): two more elements of the tuple, or two more keys of the dict."""
-        if ambient is not None:
-            if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
-                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
-            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q, shades,
-                                          sunlit, radiation, irradiance, ambient, ambient_t)
-        if radiation is not None:
-            if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
-                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
-            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q, shades,
-                                          sunlit, radiation, irradiance)
-        if shades is not None:
-            if gains is not None or sky is None or sky.get("mode") is None:
-                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
-            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q, shades,
-                                          sunlit)
-        if air is not None:
-            if gains is not None:
-                sky = _sky_for_gains(sky, self._normals, self.n_surfaces)
-            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series, gains, air, path_q)
-        if gains is not None:
-            return self._march_series_sky(weather, n_sub, loads, ideal, report, _sky_for_gains(sky, self._normals, self.n_surfaces),
-                                          trace, applied, series, gains)
-        if sky is not None:
-            return self._march_series_sky(weather, n_sub, loads, ideal, report, sky, trace, applied, series)
-        if ideal is not None:
-            return self._march_series_ideal(weather, n_sub, loads, ideal, report, trace, applied, series)
-        if report is not None:
-            return self._march_series_report(weather, n_sub, loads, report, trace, applied, series)
-        if not (trace and applied):
+        given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
+                     ambient=ambient)
+        # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
+        # (One condition for every entry point: without shades it is "gains is not None", and with gains it holds whatever
+        # the shades and the sky are — the spellings this had per entry point all reduce to it.)
+        if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
+            given["sky"] = _sky_for_gains(sky, self._normals, self.n_surfaces)
+        return self._march_series(weather, n_sub, series, given, dict(trace=trace, applied=applied, path_q=path_q, sunlit=sunlit,
+                                                                      irradiance=irradiance, ambient_t=ambient_t))
+
+    # The ten entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
+    # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
+    _SERIES_ENTRY = (("heat_batch_march_series", ()),
+                     ("heat_batch_march_series_loads", ("loads",)),
+                     ("heat_batch_march_series_report", ("loads", "report")),
+                     ("heat_batch_march_series_ideal", ("loads", "report", "ideal")),
+                     ("heat_batch_march_series_sky", ("loads", "report", "ideal", "sky")),
+                     ("heat_batch_march_series_gains", ("loads", "report", "ideal", "sky", "gains")),
+                     ("heat_batch_march_series_air", ("loads", "report", "ideal", "sky", "gains", "air")),
+                     ("heat_batch_march_series_shaded", ("loads", "report", "ideal", "sky", "gains", "air", "shades")),
+                     ("heat_batch_march_series_radiation", ("loads", "report", "ideal", "sky", "gains", "air", "shades", "radiation")),
+                     ("heat_batch_march_series_ambient", ("loads", "report", "ideal", "sky", "gains", "air", "shades", "radiation",
+                                                          "ambient")))
+    _SERIES_ORDER = ("sky", "shades", "gains", "loads", "air", "ideal", "report", "trace", "applied", "ideal_q", "transmitted", "path_q",
+                     "sunlit", "radiation", "irradiance", "ambient", "ambient_t")
+    # term -> (its make_* function, the array of rows it returns, the count of that array's columns)
+    _SERIES_TERMS = dict(loads=(make_zone_loads, "applied", "n_thermostats"), ideal=(make_ideal_loads, "ideal_q", "n_loads"),
+                         gains=(make_solar_gains, "transmitted", "n_apertures"), air=(make_air_paths, "path_q", "n_paths"),
+                         shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
+                         ambient=(make_ambient, "ambient_t", "n_sides"))
+
+    def _march_series(self, weather, n_sub, series, given, want):
+        """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
+        whether they are recorded."""
+        if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
         _series_arrays_fit(keep, self.n_surfaces)
-        for k in ("zone_a0", "zone_b0"):
-            if k in keep and keep[k].shape[1] != self.n_zones:
-                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
-        trace = np.zeros((s.n_steps, s.n_probes))
-        failed = C.c_int32(-1)
-        if loads is None:
-            rc = self._L.heat_batch_march_series(self._h, C.byref(s), trace.ctypes.data_as(_dp) if trace.size else None,
-                                                 C.byref(failed))
-        else:
-            l, lkeep = make_zone_loads(**loads)
-            applied = np.zeros((s.n_steps, l.n_thermostats))
-            rc = self._L.heat_batch_march_series_loads(self._h, C.byref(s), C.byref(l),
-                                                       trace.ctypes.data_as(_dp) if trace.size else None,
-                                                       applied.ctypes.data_as(_dp) if applied.size else None, C.byref(failed))
-        if rc != 0:
-            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
-            e.failed_step, e.trace = int(failed.value), trace
-            raise e
-        if loads is None:
-            return trace, int(failed.value)
-        return trace, int(failed.value), applied, lkeep.get("th_mode", np.zeros(0, np.uint8))
-
-    def _march_series_report(self, weather, n_sub, loads, report, want_trace, want_applied, series):
-        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
-        _series_arrays_fit(keep, self.n_surfaces)
-        for k in ("zone_a0", "zone_b0"):
-            if k in keep and keep[k].shape[1] != self.n_zones:
-                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
-        l, lkeep = make_zone_loads(**(loads or {}))
-        r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **report)
-        trace = np.zeros((s.n_steps if want_trace else 0, s.n_probes))
-        applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
-        failed = C.c_int32(-1)
-        rc = self._L.heat_batch_march_series_report(self._h, C.byref(s), C.byref(l) if loads is not None else None, C.byref(r),
-                                                    trace.ctypes.data_as(_dp) if want_trace and trace.size else None,
-                                                    applied.ctypes.data_as(_dp) if applied.size else None, C.byref(failed))
-        if rc != 0:
-            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
-            e.failed_step, e.trace = int(failed.value), trace
-            raise e
-        out = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
-        if loads is None:
-            return trace, int(failed.value), out
-        return trace, int(failed.value), applied, lkeep.get("th_mode", np.zeros(0, np.uint8)), out
-
-    def _march_series_ideal(self, weather, n_sub, loads, ideal, report, want_trace, want_applied, series):
-        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
-        _series_arrays_fit(keep, self.n_surfaces)
-        for k in ("zone_a0", "zone_b0"):
-            if k in keep and keep[k].shape[1] != self.n_zones:
-                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
-        l, lkeep = make_zone_loads(**(loads or {}))
-        il, ikeep = make_ideal_loads(**ideal)
-        r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **(report or {}))
-        trace = np.zeros((s.n_steps if want_trace else 0, s.n_probes))
-        applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
-        ideal_q = np.zeros((s.n_steps, il.n_loads))
-        failed = C.c_int32(-1)
-        rc = self._L.heat_batch_march_series_ideal(self._h, C.byref(s), C.byref(l) if loads is not None else None, C.byref(il),
-                                                   C.byref(r) if report is not None else None,
-                                                   trace.ctypes.data_as(_dp) if trace.size else None,
-                                                   applied.ctypes.data_as(_dp) if applied.size else None,
-                                                   ideal_q.ctypes.data_as(_dp) if ideal_q.size else None, C.byref(failed))
-        if rc != 0:
-            e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
-            e.failed_step, e.trace = int(failed.value), trace
-            raise e
-        out = dict(trace=trace, failed_step=int(failed.value), ideal_q=ideal_q, ideal={k: ikeep[k] for k in IDEAL_STATS if k in ikeep})
-        if loads is not None:
-            out.update(applied=applied, modes=lkeep.get("th_mode", np.zeros(0, np.uint8)))
-        if report is not None:
-            out["report"] = {k: v for k, v in rkeep.items() if not k.startswith("group_") or k == "group_trace"}
-        return out
-
-    def _march_series_sky(self, weather, n_sub, loads, ideal, report, sky, want_trace, want_applied, series, gains=None, air=None,
-                          want_path_q=True, shades=None, want_sunlit=True, radiation=None, want_irradiance=True, ambient=None,
-                          want_ambient_t=True):
-        if report is None and ideal is None and not (want_trace and want_applied):
-            raise ValueError("trace=False / applied=False need a report")
-        s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
-        _series_arrays_fit(keep, self.n_surfaces)
-        for k in ("zone_a0", "zone_b0"):
-            if k in keep and keep[k].shape[1] != self.n_zones:
-                raise ValueError("%s: rows of %d for %d zones" % (k, keep[k].shape[1], self.n_zones))
-        k = None
-        if sky is not None:  # (only a call with air paths comes here without a sky)
-            sky = dict(sky)
+        _zone_rows_fit(keep, self.n_zones)
+        made, kept = {}, {}
+        if given["sky"] is not None:
+            sky = dict(given["sky"])
             if sky.get("normals") is None:
                 sky["normals"] = self._normals
-            k, kkeep = make_sky(**sky)
-            _sky_fits(kkeep, s.n_steps, self.n_sites, self.n_surfaces)
-        l, lkeep = make_zone_loads(**(loads or {}))
-        il, ikeep = make_ideal_loads(**(ideal or {}))
-        r, rkeep = make_report(n_probes=s.n_probes, n_thermostats=l.n_thermostats, n_steps=s.n_steps, **(report or {}))
-        trace = np.zeros((s.n_steps if want_trace else 0, s.n_probes))
-        applied = np.zeros((s.n_steps if want_applied else 0, l.n_thermostats))
-        ideal_q = np.zeros((s.n_steps, il.n_loads))
+            made["sky"], kept["sky"] = make_sky(**sky)
+            _sky_fits(kept["sky"], s.n_steps, self.n_sites, self.n_surfaces)
+        rows = dict(trace=np.zeros((s.n_steps if want["trace"] else 0, s.n_probes)))
+
+        def build(term):
+            make, key, count = self._SERIES_TERMS[term]
+            if given[term] is not None or term == "loads":
+                made[term], kept[term] = make(**(given[term] or {}))
+                rows[key] = np.zeros((s.n_steps if want.get(key, True) else 0, getattr(made[term], count)))
+
+        # Built in the order the methods this replaces built them, so that input wrong in two places raises what it raised:
+        # sky, loads, ideal loads, report, gains, air paths, shades, room radiation, ambient drive. The loads and the report are
+        # built for every call, also for heat_batch_march_series, which takes neither: not passed they are empty and cannot
+        # raise, and the report is sized by the loads' thermostats.
+        build("loads")
+        build("ideal")
+        made["report"], kept["report"] = make_report(n_probes=s.n_probes, n_thermostats=made["loads"].n_thermostats, n_steps=s.n_steps,
+                                                     **(given["report"] or {}))
+        build("gains")
+        build("air")
+        build("shades")
+        if given["shades"] is not None:
+            _shades_fit(kept["shades"], self.n_surfaces, made["gains"].n_apertures if "gains" in made else None)
+        build("radiation")
+        build("ambient")
+        symbol, carried = next(e for e in self._SERIES_ENTRY if all(v is None or k in e[1] for k, v in given.items()))
+        # The symbol's arguments: of _SERIES_ORDER the names of the terms it carries (a struct, NULL where the term was not
+        # passed), the arrays of rows of those terms and the trace, which every symbol has (an array, NULL where it is empty).
+        term_of = {key: term for term, (_, key, _) in self._SERIES_TERMS.items()}       # the term an array of rows belongs to
+        args = []
+        for name in self._SERIES_ORDER:
+            is_struct = name in given
+            if is_struct and name in carried:
+                args.append(C.byref(made[name]) if given[name] is not None else None)
+            elif not is_struct and (name == "trace" or term_of[name] in carried):
+                args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        args = (C.byref(l) if loads is not None else None, C.byref(il) if ideal is not None else None,
-                C.byref(r) if report is not None else None, trace.ctypes.data_as(_dp) if trace.size else None,
-                applied.ctypes.data_as(_dp) if applied.size else None, ideal_q.ctypes.data_as(_dp) if ideal_q.size else None)
-        if gains is not None:
-            g, gkeep = make_solar_gains(**gains)
-            transmitted = np.zeros((s.n_steps, g.n_apertures))
-        if air is not None:
-            a, akeep = make_air_paths(**air)
-            q = np.zeros((s.n_steps if want_path_q else 0, a.n_paths))
-        if shades is not None:
-            h, hkeep = make_shades(**shades)
-            _shades_fit(hkeep, self.n_surfaces, g.n_apertures if gains is not None else None)
-            lit = np.zeros((s.n_steps if want_sunlit else 0, h.n_shades))
-        if radiation is not None:
-            rr, rrkeep = make_room_radiation(**radiation)
-            irr = np.zeros((s.n_steps if want_irradiance else 0, rr.n_receivers))
-        if ambient is not None:
-            ab, abkeep = make_ambient(**ambient)
-            amb_t = np.zeros((s.n_steps if want_ambient_t else 0, ab.n_sides))
-            rc = self._L.heat_batch_march_series_ambient(
-                self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h) if shades is not None else None,
-                C.byref(g) if gains is not None else None, args[0], C.byref(a) if air is not None else None, *args[1:],
-                transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
-                q.ctypes.data_as(_dp) if air is not None and q.size else None,
-                lit.ctypes.data_as(_dp) if shades is not None and lit.size else None,
-                C.byref(rr) if radiation is not None else None,
-                irr.ctypes.data_as(_dp) if radiation is not None and irr.size else None, C.byref(ab),
-                amb_t.ctypes.data_as(_dp) if amb_t.size else None, C.byref(failed))
-        elif radiation is not None:
-            rc = self._L.heat_batch_march_series_radiation(
-                self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h) if shades is not None else None,
-                C.byref(g) if gains is not None else None, args[0], C.byref(a) if air is not None else None, *args[1:],
-                transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
-                q.ctypes.data_as(_dp) if air is not None and q.size else None,
-                lit.ctypes.data_as(_dp) if shades is not None and lit.size else None, C.byref(rr),
-                irr.ctypes.data_as(_dp) if irr.size else None, C.byref(failed))
-        elif shades is not None:
-            rc = self._L.heat_batch_march_series_shaded(self._h, C.byref(s), C.byref(k) if k is not None else None, C.byref(h),
-                                                        C.byref(g) if gains is not None else None, args[0],
-                                                        C.byref(a) if air is not None else None, *args[1:],
-                                                        transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
-                                                        q.ctypes.data_as(_dp) if air is not None and q.size else None,
-                                                        lit.ctypes.data_as(_dp) if lit.size else None, C.byref(failed))
-        elif air is not None:
-            rc = self._L.heat_batch_march_series_air(self._h, C.byref(s), C.byref(k) if k is not None else None,
-                                                     C.byref(g) if gains is not None else None, args[0], C.byref(a), *args[1:],
-                                                     transmitted.ctypes.data_as(_dp) if gains is not None and transmitted.size else None,
-                                                     q.ctypes.data_as(_dp) if q.size else None, C.byref(failed))
-        elif gains is not None:
-            rc = self._L.heat_batch_march_series_gains(self._h, C.byref(s), C.byref(k), C.byref(g), *args,
-                                                       transmitted.ctypes.data_as(_dp) if transmitted.size else None, C.byref(failed))
-        else:
-            rc = self._L.heat_batch_march_series_sky(self._h, C.byref(s), C.byref(k), *args, C.byref(failed))
+        rc = getattr(self._L, symbol)(self._h, C.byref(s), *args, C.byref(failed))
         if rc != 0:
             e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
-            e.failed_step, e.trace = int(failed.value), trace
+            e.failed_step, e.trace = int(failed.value), rows["trace"]
             raise e
-        modes = lkeep.get("th_mode", np.zeros(0, np.uint8))
-        rep = {k_: v for k_, v in rkeep.items() if not k_.startswith("group_") or k_ == "group_trace"}
-        if ideal is not None:
-            out = dict(trace=trace, failed_step=int(failed.value), ideal_q=ideal_q, ideal={k_: ikeep[k_] for k_ in IDEAL_STATS if k_ in ikeep})
-            if loads is not None:
-                out.update(applied=applied, modes=modes)
-            if report is not None:
-                out["report"] = rep
-            if gains is not None:
-                out.update(transmitted=transmitted, ap_sum=gkeep["ap_sum"])
-            if air is not None:
-                out["air"] = dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep})
-            if shades is not None:
-                out["sunlit"] = lit
-            if radiation is not None:
-                out.update(irradiance=irr, sum_irradiance=rrkeep["sum_irradiance"])
-            if ambient is not None:
-                out.update(ambient_t=amb_t, sum_temperature=abkeep["sum_temperature"])
-            return out
-        out = (trace, int(failed.value)) + ((applied, modes) if loads is not None else ())
-        out = out + ((rep,) if report is not None else ())
-        out = out + ((transmitted, gkeep["ap_sum"]) if gains is not None else ())
-        out = out + ((dict(path_q=q, **{k_: akeep[k_] for k_ in ("state",) + AIR_STATS if k_ in akeep}),) if air is not None else ())
-        out = out + ((lit,) if shades is not None else ())
-        out = out + ((irr, rrkeep["sum_irradiance"]) if radiation is not None else ())
-        return out + ((amb_t, abkeep["sum_temperature"]) if ambient is not None else ())
+        # what is returned, in the order the terms were added to the call: a dict with ideal loads, else a tuple of the values
+        out = [("trace", rows["trace"]), ("failed_step", int(failed.value))]
+        if given["ideal"] is not None:
+            out += [("ideal_q", rows["ideal_q"]), ("ideal", {k: kept["ideal"][k] for k in IDEAL_STATS if k in kept["ideal"]})]
+        if given["loads"] is not None:
+            out += [("applied", rows["applied"]), ("modes", kept["loads"].get("th_mode", np.zeros(0, np.uint8)))]
+        if given["report"] is not None:
+            out += [("report", {k: v for k, v in kept["report"].items() if not k.startswith("group_") or k == "group_trace"})]
+        if given["gains"] is not None:
+            out += [("transmitted", rows["transmitted"]), ("ap_sum", kept["gains"]["ap_sum"])]
+        if given["air"] is not None:
+            out += [("air", dict(path_q=rows["path_q"], **{k: kept["air"][k] for k in ("state",) + AIR_STATS if k in kept["air"]}))]
+        if given["shades"] is not None:
+            out += [("sunlit", rows["sunlit"])]
+        if given["radiation"] is not None:
+            out += [("irradiance", rows["irradiance"]), ("sum_irradiance", kept["radiation"]["sum_irradiance"])]
+        if given["ambient"] is not None:
+            out += [("ambient_t", rows["ambient_t"]), ("sum_temperature", kept["ambient"]["sum_temperature"])]
+        return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):
         """heat_batch_set_ambient: the temperature (C) of the listed Ambient sides (surface of the model, 0 front / 1 back)

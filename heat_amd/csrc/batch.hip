@@ -1038,124 +1038,658 @@ struct SeriesDrain {
     heat_batch *b;
     ~SeriesDrain() { (void)hipStreamSynchronize(b->stream); }
 };
+#define SERIES_TRY(expr) do { if (const int rc_ = (expr)) return rc_; } while (0)
 
 template <typename T>
-int series_upload(DevBuf<T> &buf, const T *src, size_t count, const char *what) {
+int series_alloc(DevBuf<T> &buf, size_t count, const char *what, const T *src = nullptr) {
     hipError_t e = buf.alloc(count);
-    if (e == hipSuccess && count > 0) e = hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice);
+    if (e == hipSuccess && count > 0 && src) e = hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice);
     if (e != hipSuccess)
         return fail(HEAT_E_DEVICE, "series march: %s (%zu bytes) on the device: %s — nothing has been marched", what, count * sizeof(T),
                     hipGetErrorString(e));
     return HEAT_OK;
 }
+template <typename T>
+int series_upload(DevBuf<T> &buf, const T *src, size_t count, const char *what) { return series_alloc(buf, count, what, src); }
+template <typename T>
+int series_upload(DevBuf<T> &buf, const std::vector<T> &src, const char *what) { return series_alloc(buf, src.size(), what, src.data()); }
+// An in/out array of a call: absent (nullptr: no device copy), uploaded (resume), or allocated for the device to initialise.
+template <typename T>
+int report_array(DevBuf<T> &buf, const T *host, size_t count, bool upload, const char *what) {
+    return host ? series_alloc(buf, count, what, upload ? host : nullptr) : HEAT_OK;
+}
+// Back to the host behind the stream's work (and the copy that gave e, if that went well); nothing where either side holds no copy.
+template <typename T>
+hipError_t series_fetch(T *host, const DevBuf<T> &buf, hipStream_t st, hipError_t e = hipSuccess) {
+    return e != hipSuccess || !host || !buf.p ? e : hipMemcpyAsync(host, buf.p, buf.n * sizeof(T), hipMemcpyDeviceToHost, st);
+}
+// Row k of a buffer of rows of n values; nullptr where the buffer is absent.
+template <typename T>
+T *row(const DevBuf<T> &buf, int k, int64_t n) { return buf.p ? buf.p + (size_t)k * (size_t)n : nullptr; }
+// dst[d] = src[orig_of[d]]: an array over the caller's surfaces, in the device's order.
+template <typename T>
+void to_device_order(heat_batch *b, const T *src, T *dst) {
+    const int64_t *orig_of = b->h_orig_of.data();
+    b->pool->run(b->n_surf, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) dst[d] = src[orig_of[d]]; });
+}
+// The start of a fresh run's accumulator on the device (the step numbers start at -1, written as 0xff bytes).
+inline hipError_t series_fill(const DevBuf<double> &d, double v, hipStream_t st) { launch_fill_f64(d.p, (int64_t)d.n, v, st); return hipSuccess; }
+inline hipError_t series_fill(const DevBuf<int64_t> &d, int64_t v, hipStream_t st) {
+    return d.p ? hipMemsetAsync(d.p, v < 0 ? 0xff : 0, d.n * sizeof(int64_t), st) : hipSuccess;
+}
+// An in/out accumulator: the caller's array, its device copy, a fresh run's start value and the device view's field for the copy.
+template <typename T>
+struct Acc {
+    T *host = nullptr, **view = nullptr;
+    T init = 0;
+    DevBuf<T> dev;
+    void bind(T *h, T v, T **field) { host = h, init = v, view = field; }
+    // uploaded on resume, else allocated; nothing where the caller passes no array
+    int stage(size_t n, bool resume, const char *w) { const int rc = report_array(dev, host, n, resume, w); *view = dev.p; return rc; }
+    hipError_t start(hipStream_t st, hipError_t e = hipSuccess) { return e != hipSuccess ? e : series_fill(dev, init, st); }
+    hipError_t fetch(hipStream_t st, hipError_t e = hipSuccess) { return series_fetch(host, dev, st, e); }
+};
+// start() or fetch() of every accumulator of a list, in order, up to the first error
+template <typename A, size_t N>
+hipError_t for_each_acc(A (&acc)[N], hipError_t (A::*what)(hipStream_t, hipError_t), hipStream_t st, hipError_t e = hipSuccess) {
+    for (A &a : acc) e = (a.*what)(st, e);
+    return e;
+}
+inline StepWeather to_step_weather(const heat_weather &w) {
+    return StepWeather{w.dry_bulb, std::sqrt(w.wind_speed), std::sin(w.wind_direction), std::cos(w.wind_direction)};
+}
 
-// The device copies of a report (heat_series_report): tables, accumulators, the step's group sums. Declared before the
-// SeriesDrain of the call, so freed after the stream has run dry.
-struct ReportDev {
+// ---- the terms of a series march: each owns its host tables (prepare: no device call), its device buffers and view (upload:
+// through the null stream) and its way back (fetch: asynchronous). Declared before the call's SeriesDrain: freed after the stream ran dry. ----
+
+// The driven inputs: channel numbers and gains per DEVICE surface, structure of arrays; the own-face bits and face nodes.
+// The gain arrays serve the sky, the solar gains and the room radiation too.
+struct InputsTerm {
+    const double *gain[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool driven = false;
+    std::vector<int32_t> h_chan;
+    std::vector<double> h_gain[4];
+    std::vector<uint8_t> h_own;
+    std::vector<uint32_t> h_face;
+    DevBuf<int32_t> chan;
+    DevBuf<double> d_gain[4];
+    DevBuf<uint8_t> own;
+    DevBuf<uint32_t> face;
+    SeriesInputs view{};
+    // gain[a] in device order, once: for whichever term drives input a first
+    void need_gain(heat_batch *b, int a) {
+        if (!gain[a] || !h_gain[a].empty()) return;
+        h_gain[a].resize((size_t)b->n_surf);
+        to_device_order(b, gain[a], h_gain[a].data());
+    }
+    void prepare(heat_batch *b, const heat_series *s) {
+        const int64_t S = b->n_surf;
+        const int32_t *src[4] = {s->solar_front_chan, s->solar_back_chan, s->ir_front_chan, s->ir_back_chan};
+        const double *g[4] = {s->solar_front_gain, s->solar_back_gain, s->ir_front_gain, s->ir_back_gain};
+        bool own_any = false;
+        for (int a = 0; a < 4; a++) {
+            gain[a] = g[a];
+            for (int64_t q = 0; src[a] && q < S && !driven; q++) driven = src[a][q] >= 0;
+        }
+        for (int64_t q = 0; s->ir_own_face && q < S && !own_any; q++) own_any = (s->ir_own_face[q] & 3) != 0;
+        if (!driven) return;
+        h_chan.assign(4 * (size_t)S, -1);
+        for (int a = 0; a < 4; a++) {
+            if (!src[a]) continue;
+            to_device_order(b, src[a], h_chan.data() + (size_t)a * S);
+            need_gain(b, a);
+        }
+        if (!own_any) return;
+        const int64_t *orig_of = b->h_orig_of.data();
+        h_own.resize((size_t)S);
+        h_face.resize(2 * (size_t)S);
+        b->pool->run(S, [&](int64_t d0, int64_t d1) {
+            for (int64_t d = d0; d < d1; d++) {
+                const int64_t q = orig_of[d];
+                h_own[d] = (uint8_t)(s->ir_own_face[q] & 3);
+                h_face[d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], 0);
+                h_face[S + d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], (int)b->h_node_count[q] - 1);
+            }
+        });
+    }
+    int upload() {
+        SERIES_TRY(series_upload(chan, h_chan, "channel numbers"));
+        for (int a = 0; a < 4; a++) SERIES_TRY(series_upload(d_gain[a], h_gain[a], "gains"));
+        SERIES_TRY(series_upload(own, h_own, "own-face bits"));
+        SERIES_TRY(series_upload(face, h_face, "face node table"));
+        view.chan = chan.p, view.own_face = own.p, view.face = face.p;
+        for (int a = 0; a < 4; a++) view.gain[a] = d_gain[a].p;
+        return HEAT_OK;
+    }
+};
+
+// The probes: (buffer, index) of every probed slot; the trace; the record of the first failed step.
+struct ProbesTerm {
+    int64_t P = 0;
+    std::vector<uint8_t> h_buf;
+    std::vector<uint32_t> h_idx;
+    DevBuf<uint8_t> buf;
+    DevBuf<uint32_t> idx;
+    DevBuf<int> failed;  // the step, then the flags as they were after it
+    DevBuf<double> trace;
+    static void place(const heat_batch *b, int kind, int64_t index, int node, uint8_t &buf, uint32_t &idx) {
+        if (kind == PROBE_ZONE) {
+            buf = (uint8_t)kProbeBufZone, idx = (uint32_t)index;
+        } else if (kind == PROBE_NODE) {
+            buf = (uint8_t)kProbeBufT, idx = (uint32_t)node_slot_index(b->h_node_tile_base[index], b->h_node_geom[index], node);
+        } else {  // hs front, hs back, flow front, flow back: SideOut record side * S + d, as doubles
+            const int a = kind - PROBE_HS_FRONT;
+            const int64_t rec = (int64_t)(a & 1) * b->n_surf + b->h_dev_of[index];
+            buf = (uint8_t)kProbeBufOut, idx = (uint32_t)(2 * rec + (a >> 1));
+        }
+    }
+    int prepare(heat_batch *b, const heat_series *s) {
+        P = s->n_probes;
+        h_buf.resize((size_t)P);
+        h_idx.resize((size_t)P);
+        for (int64_t p = 0; p < P; p++) {
+            int kind = 0, node = 0;
+            int64_t index = 0;
+            if (!b->resolver->resolve(s->probe_slot[p], kind, index, node)) return fail(HEAT_E_SIZE, "probe %lld: slot not resolved", (long long)p);
+            place(b, kind, index, node, h_buf[p], h_idx[p]);
+        }
+        return HEAT_OK;
+    }
+    int upload(const double *host_trace, int n_steps) {
+        const int fail_init[5] = {-1, 0, 0, 0, 0};
+        SERIES_TRY(series_upload(buf, h_buf, "probe table"));
+        SERIES_TRY(series_upload(idx, h_idx, "probe table"));
+        SERIES_TRY(series_upload(failed, fail_init, 5, "failed step"));
+        return host_trace ? series_alloc(trace, (size_t)n_steps * P, "trace") : HEAT_OK;
+    }
+    hipError_t fetch(double *host_trace, hipStream_t st) { return series_fetch(host_trace, trace, st); }
+};
+
+// The zone loads: the term lists sorted by zone with CSR offsets (plan.hpp), the mode bytes in the caller's order, the applied rows.
+struct LoadsTerm {
+    bool on = false;
+    int64_t NT = 0;
+    ZoneLoadTables zt;
+    std::vector<uint8_t> h_mode;
+    DevBuf<int32_t> i32;
+    DevBuf<double> f64, applied;
+    DevBuf<uint8_t> mode;
+    ZoneLoadsDev view{};
+    void prepare(const heat_batch *b, const heat_zone_loads *l) {
+        on = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
+        if (!on) return;
+        NT = l->n_thermostats;
+        build_zone_load_tables(b->n_zones, l, zt);
+        h_mode.assign((size_t)NT, 0);
+        if (l->th_mode) std::copy(l->th_mode, l->th_mode + NT, h_mode.begin());
+    }
+    int upload(const double *host_applied, int n_steps) {
+        if (!on) return HEAT_OK;
+        // (packed into two uploads, not thirteen: each one is an allocation and a pageable copy in the call's set-up)
+        const std::vector<int32_t> *a_i32[8] = {&zt.off, &zt.gain_chan, &zt.flow_volume_chan, &zt.flow_temp_chan, &zt.th_sensor,
+                                                &zt.th_heat_chan, &zt.th_cool_chan, &zt.th_orig};
+        const std::vector<double> *a_f64[5] = {&zt.gain_factor, &zt.flow_volume_gain, &zt.th_heat_power, &zt.th_cool_power, &zt.th_half_band};
+        const int32_t **v_i32[8] = {&view.off, &view.gain_chan, &view.flow_volume_chan, &view.flow_temp_chan, &view.th_sensor,
+                                    &view.th_heat_chan, &view.th_cool_chan, &view.th_orig};
+        const double **v_f64[5] = {&view.gain_factor, &view.flow_volume_gain, &view.th_heat_power, &view.th_cool_power, &view.th_half_band};
+        std::vector<int32_t> h_i32;
+        std::vector<double> h_f64;
+        for (auto *v : a_i32) h_i32.insert(h_i32.end(), v->begin(), v->end());
+        for (auto *v : a_f64) h_f64.insert(h_f64.end(), v->begin(), v->end());
+        SERIES_TRY(series_upload(i32, h_i32, "zone load tables"));
+        SERIES_TRY(series_upload(f64, h_f64, "zone load tables"));
+        SERIES_TRY(series_upload(mode, h_mode, "thermostat modes"));
+        if (host_applied) SERIES_TRY(series_alloc(applied, (size_t)n_steps * NT, "applied powers"));
+        for (size_t a = 0, at = 0; a < 8; at += a_i32[a++]->size()) *v_i32[a] = i32.p + at;
+        for (size_t a = 0, at = 0; a < 5; at += a_f64[a++]->size()) *v_f64[a] = f64.p + at;
+        view.th_mode = mode.p;
+        return HEAT_OK;
+    }
+    hipError_t fetch(const heat_zone_loads *l, double *host_applied, hipStream_t st) {
+        return on ? series_fetch(l->th_mode, mode, st, series_fetch(host_applied, applied, st)) : hipSuccess;
+    }
+};
+
+// The report (heat_series_report): the group entries sorted into device order (buffer, index) and cut into segments
+// (plan.hpp), the step's group sums, the group trace, the limits (always uploaded, never fetched), the accumulators.
+struct ReportTerm {
+    heat_series_report *r = nullptr;
+    int64_t G = 0, Q = 0;
+    bool th_stats = false, q_stats = false;
+    GroupTables gt;
+    std::vector<uint8_t> h_gbuf;
+    std::vector<uint32_t> h_gidx;
     DevBuf<uint8_t> gbuf, prev;
     DevBuf<uint32_t> gidx, seg, part_off;
-    DevBuf<double> gw, part, group_trace, applied_row;
-    DevBuf<double> f64[7];   // q_min, q_max, q_sum, q_deg_below, q_deg_above, q_lo, q_hi
-    DevBuf<int64_t> i64[4];  // q_step_min, q_step_max, q_n_below, q_n_above
-    DevBuf<double> th_f64[2];
-    DevBuf<int64_t> th_i64[3];
+    DevBuf<double> gw, part, group_trace, applied_row, lo, hi;
+    Acc<double> q_f64[5], th_f64[2];   // q_min, q_max, q_sum, q_deg_below, q_deg_above; th_sum_heating, th_sum_cooling
+    Acc<int64_t> q_i64[4], th_i64[3];  // q_step_min, q_step_max, q_n_below, q_n_above; th_steps_heating, th_steps_cooling, th_switches
+    SeriesGroupsDev groups{};
+    SeriesStatsDev stats{};
+    SeriesThStatsDev th{};
+    void prepare(const heat_batch *b, heat_series_report *r_, int64_t P, const std::vector<ResolvedSlot> &entry) {
+        r = r_;
+        Q = P;
+        if (!r) return;
+        const double inf = std::numeric_limits<double>::infinity();
+        q_f64[0].bind(r->q_min, inf, &stats.q_min), q_f64[1].bind(r->q_max, -inf, &stats.q_max), q_f64[2].bind(r->q_sum, 0.0, &stats.q_sum);
+        q_f64[3].bind(r->q_deg_below, 0.0, &stats.q_deg_below), q_f64[4].bind(r->q_deg_above, 0.0, &stats.q_deg_above);
+        q_i64[0].bind(r->q_step_min, -1, &stats.q_step_min), q_i64[1].bind(r->q_step_max, -1, &stats.q_step_max);
+        q_i64[2].bind(r->q_n_below, 0, &stats.q_n_below), q_i64[3].bind(r->q_n_above, 0, &stats.q_n_above);
+        th_f64[0].bind(r->th_sum_heating, 0.0, &th.sum_heating), th_f64[1].bind(r->th_sum_cooling, 0.0, &th.sum_cooling);
+        th_i64[0].bind(r->th_steps_heating, 0, &th.steps_heating), th_i64[1].bind(r->th_steps_cooling, 0, &th.steps_cooling);
+        th_i64[2].bind(r->th_switches, 0, &th.switches);
+        th_stats = th_f64[0].host || th_f64[1].host || th_i64[0].host || th_i64[1].host || th_i64[2].host;
+        G = r->n_groups;
+        Q = P + G;
+        if (G == 0) return;
+        const int64_t n_entries = r->group_offset[G];
+        std::vector<uint64_t> key((size_t)n_entries);
+        for (int64_t i = 0; i < n_entries; i++) {
+            uint8_t buf = 0;
+            uint32_t idx = 0;
+            ProbesTerm::place(b, entry[(size_t)i].kind, entry[(size_t)i].index, entry[(size_t)i].node, buf, idx);
+            key[(size_t)i] = (uint64_t)buf << 32 | idx;
+        }
+        build_group_tables(G, r->group_offset, r->group_weight, key.data(), gt);
+        h_gbuf.resize((size_t)n_entries);
+        h_gidx.resize((size_t)n_entries);
+        for (int64_t i = 0; i < n_entries; i++) h_gbuf[(size_t)i] = (uint8_t)(gt.key[(size_t)i] >> 32), h_gidx[(size_t)i] = (uint32_t)gt.key[(size_t)i];
+    }
+    int upload(int n_steps, const ProbesTerm &probes, const LoadsTerm &loads) {
+        if (!r) return HEAT_OK;
+        const bool resume = r->resume != 0;
+        const size_t n_wave = gt.wave_seg.size() / 3, n_row = gt.row_seg.size() / 3;
+        std::vector<uint32_t> h_seg(gt.wave_seg);
+        h_seg.insert(h_seg.end(), gt.row_seg.begin(), gt.row_seg.end());
+        SERIES_TRY(series_upload(gbuf, h_gbuf, "group tables"));
+        SERIES_TRY(series_upload(gidx, h_gidx, "group tables"));
+        SERIES_TRY(series_upload(gw, gt.weight, "group tables"));
+        SERIES_TRY(series_upload(seg, h_seg, "group tables"));
+        SERIES_TRY(series_upload(part_off, gt.part_off.data(), G > 0 ? gt.part_off.size() : 0, "group tables"));
+        SERIES_TRY(series_alloc(part, n_wave + n_row, "group sums"));
+        SERIES_TRY(report_array(group_trace, r->group_trace, (size_t)n_steps * G, false, "group trace"));
+        for (auto &a : q_f64) SERIES_TRY(a.stage((size_t)Q, resume, "statistics"));
+        SERIES_TRY(report_array(lo, r->q_lo, (size_t)Q, true, "statistics"));
+        SERIES_TRY(report_array(hi, r->q_hi, (size_t)Q, true, "statistics"));
+        for (auto &a : q_i64) SERIES_TRY(a.stage((size_t)Q, resume, "statistics"));
+        groups.buf = gbuf.p, groups.idx = gidx.p, groups.weight = gw.p, groups.part = part.p;
+        groups.wave_seg = seg.p, groups.row_seg = seg.p + 3 * n_wave, groups.n_wave = (int)n_wave, groups.n_row = (int)n_row;
+        stats.n_probes = probes.P, stats.n_groups = G, stats.buf = probes.buf.p, stats.idx = probes.idx.p;
+        stats.part = part.p, stats.part_off = part_off.p;
+        // (a limit nothing is counted against is not read)
+        stats.q_lo = stats.q_n_below || stats.q_deg_below ? lo.p : nullptr;
+        stats.q_hi = stats.q_n_above || stats.q_deg_above ? hi.p : nullptr;
+        q_stats = Q > 0 && (stats.q_min || stats.q_max || stats.q_sum || stats.q_n_below || stats.q_deg_below || stats.q_n_above ||
+                            stats.q_deg_above || group_trace.p);
+        if (!th_stats) return HEAT_OK;  // (check_series_report: only with thermostats)
+        for (auto &a : th_f64) SERIES_TRY(a.stage((size_t)loads.NT, resume, "thermostat statistics"));
+        for (auto &a : th_i64) SERIES_TRY(a.stage((size_t)loads.NT, resume, "thermostat statistics"));
+        SERIES_TRY(series_upload(prev, loads.h_mode, "thermostat modes"));
+        // (the powers of the step: a row of the applied buffer, or one row of scratch where the caller takes none)
+        if (!loads.applied.p && (th_f64[0].host || th_f64[1].host)) SERIES_TRY(series_alloc(applied_row, (size_t)loads.NT, "applied powers"));
+        th.prev = prev.p;
+        return HEAT_OK;
+    }
+    // start (a fresh run: min = +inf, max = -inf, steps = -1, sums and counts 0) or fetch of the accumulators
+    hipError_t each(hipError_t (Acc<double>::*f64)(hipStream_t, hipError_t), hipError_t (Acc<int64_t>::*i64)(hipStream_t, hipError_t), hipStream_t st,
+                    hipError_t e = hipSuccess) {
+        return for_each_acc(th_i64, i64, st, for_each_acc(th_f64, f64, st, for_each_acc(q_i64, i64, st, for_each_acc(q_f64, f64, st, e))));
+    }
+    hipError_t start(hipStream_t st) { return r && r->resume == 0 ? each(&Acc<double>::start, &Acc<int64_t>::start, st) : hipSuccess; }
+    hipError_t fetch(hipStream_t st) {
+        return r ? each(&Acc<double>::fetch, &Acc<int64_t>::fetch, st, series_fetch(r->group_trace, group_trace, st)) : hipSuccess;
+    }
 };
 
-// The device copies of the ideal loads of a series (heat_ideal_loads): tables, the step's setpoints and q-sums, accumulators,
-// the ideal_q rows. Declared before the SeriesDrain of the call, as ReportDev is.
-struct IdealDev {
-    DevBuf<int32_t> i32;     // load_of_zone [Z] | heat_chan [N] | cool_chan [N]
-    DevBuf<double> cap;      // heat_cap [N] | cool_cap [N]
-    DevBuf<double> step;     // setpoint [2][N] | qsum [N]
-    DevBuf<double> q;        // ideal_q [n_steps][N]
-    DevBuf<double> f64[4];   // sum_heating, sum_cooling, peak_heating, peak_cooling
-    DevBuf<int64_t> i64[4];  // step_peak_heating, step_peak_cooling, n_sat_heating, n_sat_cooling
+// The ideal loads (heat_ideal_loads): tables, the step's setpoints and q-sums, the ideal_q rows, the accumulators.
+struct IdealTerm {
+    heat_ideal_loads *il = nullptr;
+    int64_t NI = 0;
+    std::vector<int32_t> h_i32;  // load_of_zone [Z] | heat_chan [N] | cool_chan [N]
+    std::vector<double> h_cap;   // heat_cap [N] | cool_cap [N]
+    DevBuf<int32_t> i32;
+    DevBuf<double> cap, step, q; // step: setpoint [2][N] | qsum [N]; q: ideal_q [n_steps][N]
+    Acc<double> f64[4];          // sum_heating, sum_cooling, peak_heating, peak_cooling
+    Acc<int64_t> i64[4];         // step_peak_heating, step_peak_cooling, n_sat_heating, n_sat_cooling
+    IdealLoadsDev view{};
+    void prepare(heat_ideal_loads *il_, const std::vector<int32_t> &load_of_zone) {
+        il = il_;
+        NI = il ? il->n_loads : 0;
+        if (NI == 0) return;
+        const double inf = std::numeric_limits<double>::infinity();
+        h_i32 = load_of_zone;
+        h_i32.insert(h_i32.end(), il->heat_chan, il->heat_chan + NI);
+        h_i32.insert(h_i32.end(), il->cool_chan, il->cool_chan + NI);
+        h_cap.assign(2 * (size_t)NI, inf);
+        if (il->heat_cap) std::copy(il->heat_cap, il->heat_cap + NI, h_cap.begin());
+        if (il->cool_cap) std::copy(il->cool_cap, il->cool_cap + NI, h_cap.begin() + NI);
+        f64[0].bind(il->sum_heating, 0.0, &view.sum_heating), f64[1].bind(il->sum_cooling, 0.0, &view.sum_cooling);
+        f64[2].bind(il->peak_heating, -inf, &view.peak_heating), f64[3].bind(il->peak_cooling, inf, &view.peak_cooling);
+        i64[0].bind(il->step_peak_heating, -1, &view.step_peak_heating), i64[1].bind(il->step_peak_cooling, -1, &view.step_peak_cooling);
+        i64[2].bind(il->n_sat_heating, 0, &view.n_sat_heating), i64[3].bind(il->n_sat_cooling, 0, &view.n_sat_cooling);
+    }
+    int upload(const heat_batch *b, const double *host_q, int n_steps) {
+        if (NI == 0) return HEAT_OK;
+        const bool resume = il->resume != 0;
+        SERIES_TRY(series_upload(i32, h_i32, "ideal load tables"));
+        SERIES_TRY(series_upload(cap, h_cap, "ideal load tables"));
+        SERIES_TRY(series_alloc(step, 3 * (size_t)NI, "ideal load setpoints"));
+        if (host_q) SERIES_TRY(series_alloc(q, (size_t)n_steps * NI, "ideal powers"));
+        for (auto &a : f64) SERIES_TRY(a.stage((size_t)NI, resume, "ideal load accumulators"));
+        for (auto &a : i64) SERIES_TRY(a.stage((size_t)NI, resume, "ideal load accumulators"));
+        view.n_loads = (int)NI;
+        view.load_of_zone = i32.p, view.heat_chan = i32.p + b->n_zones, view.cool_chan = i32.p + b->n_zones + NI;
+        view.heat_cap = cap.p, view.cool_cap = cap.p + NI, view.setpoint = step.p, view.qsum = step.p + 2 * NI;
+        return HEAT_OK;
+    }
+    hipError_t start(hipStream_t st) {
+        return NI > 0 && il->resume == 0 ? for_each_acc(i64, &Acc<int64_t>::start, st, for_each_acc(f64, &Acc<double>::start, st)) : hipSuccess;
+    }
+    hipError_t fetch(double *host_q, hipStream_t st) {
+        return for_each_acc(i64, &Acc<int64_t>::fetch, st, for_each_acc(f64, &Acc<double>::fetch, st, series_fetch(host_q, q, st)));
+    }
 };
 
-// The device copies of the sky of a series (heat_sky): the mode bytes and normals in device surface order, the record table
-// as given. Declared before the SeriesDrain of the call, as ReportDev is.
-struct SkyDev {
+// The sky (heat_sky): the mode bytes and normals per DEVICE surface, the record table as given (the solar gains and the
+// shades read it too).
+struct SkyTerm {
+    unsigned bits = 0;
+    std::vector<uint8_t> h_mode;
+    std::vector<double> h_normal;
     DevBuf<uint8_t> mode;      // [S]
     DevBuf<double> normal;     // [3][S]
     DevBuf<SkyRecord> record;  // [n_steps][n_sites]
+    SeriesSky view{};
+    void prepare(heat_batch *b, const heat_sky *sky, InputsTerm &in) {
+        if (!bits) return;
+        const int64_t S = b->n_surf;
+        const int64_t *orig_of = b->h_orig_of.data();
+        h_mode.resize((size_t)S);
+        h_normal.resize(3 * (size_t)S);
+        b->pool->run(S, [&](int64_t d0, int64_t d1) {
+            for (int64_t d = d0; d < d1; d++) {
+                const int64_t q = orig_of[d];
+                const bool on = sky->mode[q] != 0;  // (the normals of the other surfaces are not read, not even here)
+                h_mode[d] = sky->mode[q];
+                h_normal[d] = on ? sky->normal_x[q] : 0.0;
+                h_normal[S + d] = on ? sky->normal_y[q] : 0.0;
+                h_normal[2 * S + d] = on ? sky->normal_z[q] : 0.0;
+            }
+        });
+        for (int a = 0; a < 4; a++) if (bits >> a & 1) in.need_gain(b, a);
+    }
+    // records_read: by the sky's own sides, by apertures or by shades
+    int upload(const heat_batch *b, const heat_series *s, const heat_sky *sky, bool records_read, const InputsTerm &in) {
+        if (records_read)
+            SERIES_TRY(series_upload(record, reinterpret_cast<const SkyRecord *>(sky->record), (size_t)s->n_steps * b->n_sites, "sky records"));
+        if (!bits) return HEAT_OK;
+        SERIES_TRY(series_upload(mode, h_mode, "sky modes"));
+        SERIES_TRY(series_upload(normal, h_normal, "sky normals"));
+        view.mode = mode.p, view.normal = normal.p, view.site = b->n_sites > 1 ? b->d_site.p : nullptr;
+        for (int a = 0; a < 4; a++) view.gain[a] = in.d_gain[a].p;
+        return HEAT_OK;
+    }
 };
 static_assert(sizeof(SkyRecord) == sizeof(heat_sky_record) && sizeof(heat_sky_record) == 64, "SkyRecord mirrors heat_sky_record");
 
-// The device copies of the solar gains of a series (heat_solar_gains): the aperture tables, the sliced-ELL entry tables
-// (plan.hpp, SolarGainTables), the step's (Pb, Pd), ap_sum and the transmitted rows. Declared beside SkyDev.
-struct GainsDev {
-    DevBuf<int32_t> ap_dev;       // [NA]
-    DevBuf<double> ap_f64;        // normal [3][NA] | coef [6][NA] | tau_diffuse [NA] | scale [NA]
-    DevBuf<double2> power;        // [NA]
-    DevBuf<double> sum;           // [NA]
-    DevBuf<double> transmitted;   // [n_steps][NA]
+// The shades (heat_shades): the table as structure of arrays (plan.hpp, ShadeTables), every shade's site and horizon, the horizon
+// profiles, the step's sunlit fractions, the shade numbers of the sides per DEVICE surface and of the apertures, the sunlit rows.
+struct ShadesTerm {
+    int64_t NS = 0;
+    ShadeTables sht;
+    std::vector<int32_t> h_i32, h_side;
+    DevBuf<double> tab, tan2, f, sunlit;  // [kShadeRows][NS], [NH][16], [NS], [n_steps][NS]
+    DevBuf<int32_t> i32, side, aperture;  // site [NS] | horizon [NS], [2][S], [NA]
+    SeriesShades view{};
+    // what a shaded consumer reads: the step's fractions, the diffuse and the ground factors (all NULL without shades)
+    ShadeFactors factors() const { return ShadeFactors{f.p, tab.p + (size_t)SH_FD * NS, tab.p + (size_t)SH_FG * NS}; }
+    void prepare(heat_batch *b, const heat_shades *shades, unsigned sky_bits) {
+        NS = shades ? shades->n_shades : 0;  // (a side or aperture needs a shade to refer to: none is shaded without)
+        if (NS == 0) return;
+        build_shade_tables(shades, sht);
+        h_i32.assign(2 * (size_t)NS, 0);
+        for (int64_t j = 0; j < NS; j++) {
+            h_i32[j] = b->h_site.empty() ? 0 : b->h_site[b->h_dev_of[shades->sh_surface[j]]];
+            h_i32[NS + j] = sht.horizon[j];
+        }
+        if (!(sky_bits & 3) || !(shades->front_shade || shades->back_shade)) return;
+        h_side.assign(2 * (size_t)b->n_surf, -1);
+        if (shades->front_shade) to_device_order(b, shades->front_shade, h_side.data());
+        if (shades->back_shade) to_device_order(b, shades->back_shade, h_side.data() + b->n_surf);
+    }
+    int upload(const heat_shades *shades, int64_t NA, const double *host_sunlit, int n_steps, SkyTerm &sky) {
+        if (NS == 0) return HEAT_OK;
+        SERIES_TRY(series_upload(tab, sht.f64, "shade table"));
+        SERIES_TRY(series_upload(i32, h_i32, "shade table"));
+        SERIES_TRY(series_upload(tan2, shades->horizon_tan2, 16 * (size_t)shades->n_horizons, "horizon profiles"));
+        SERIES_TRY(series_alloc(f, (size_t)NS, "sunlit fractions"));
+        SERIES_TRY(series_upload(side, h_side, "shade numbers"));
+        if (NA > 0 && shades->aperture_shade) SERIES_TRY(series_upload(aperture, shades->aperture_shade, (size_t)NA, "shade numbers"));
+        if (host_sunlit) SERIES_TRY(series_alloc(sunlit, (size_t)n_steps * NS, "sunlit fractions"));
+        view.n = (int)NS, view.site = i32.p, view.horizon = i32.p + NS, view.tab = tab.p, view.tan2 = tan2.p, view.f = f.p;
+        sky.view.shade = side.p, sky.view.sf = factors();
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_sunlit, hipStream_t st) { return series_fetch(host_sunlit, sunlit, st); }
+};
+
+// The solar gains (heat_solar_gains): the apertures as structure of arrays, the entries as sliced ELL over the receivers in
+// device record order (plan.hpp, SolarGainTables), the step's (Pb, Pd), ap_sum (always uploaded) and the transmitted rows.
+struct GainsTerm {
+    int64_t NA = 0;
+    std::vector<int32_t> h_ap_dev;
+    std::vector<double> h_ap_f64;
+    SolarGainTables gnt;
+    DevBuf<int32_t> ap_dev, ap;                 // [NA]; the entries' apertures
+    DevBuf<double> ap_f64, transmitted, share;  // normal [3][NA] | coef [6][NA] | tau_diffuse [NA] | scale [NA]; [n_steps][NA]
+    DevBuf<double2> power;                      // [NA]
     DevBuf<uint32_t> rec;
     DevBuf<int64_t> slice_off;
-    DevBuf<int32_t> ap;
-    DevBuf<double> share;
+    Acc<double> sum;
+    SeriesApertures apertures{};
+    SeriesGains view{};
+    void prepare(heat_batch *b, const heat_solar_gains *gains, InputsTerm &in) {
+        NA = gains ? gains->n_apertures : 0;  // (entries need an aperture: there are none without)
+        if (NA == 0) return;
+        const int64_t S = b->n_surf;
+        h_ap_dev.resize((size_t)NA);
+        h_ap_f64.resize(11 * (size_t)NA);
+        for (int64_t a = 0; a < NA; a++) {
+            h_ap_dev[a] = b->h_dev_of[gains->ap_surface[a]];
+            h_ap_f64[a] = gains->ap_normal_x[a];
+            h_ap_f64[NA + a] = gains->ap_normal_y[a];
+            h_ap_f64[2 * NA + a] = gains->ap_normal_z[a];
+            for (int j = 0; j < 6; j++) h_ap_f64[(3 + j) * NA + a] = gains->ap_tau_coef[6 * a + j];
+            h_ap_f64[9 * NA + a] = gains->ap_tau_diffuse[a];
+            h_ap_f64[10 * NA + a] = gains->ap_scale[a];
+        }
+        build_solar_gain_tables(S, b->h_dev_of.data(), gains, gnt);
+        sum.bind(gains->ap_sum, 0.0, &apertures.sum);
+        for (uint32_t r : gnt.rec) in.need_gain(b, r >= (uint64_t)S);  // the solar gain arrays of the sides that receive (once each)
+    }
+    int upload(const heat_batch *b, const double *host_transmitted, int n_steps, const ShadesTerm &shades, const InputsTerm &in) {
+        if (NA == 0) return HEAT_OK;
+        SERIES_TRY(series_upload(ap_dev, h_ap_dev, "aperture tables"));
+        SERIES_TRY(series_upload(ap_f64, h_ap_f64, "aperture tables"));
+        SERIES_TRY(series_alloc(power, (size_t)NA, "aperture powers"));
+        SERIES_TRY(sum.stage((size_t)NA, true, "aperture sums"));
+        if (host_transmitted) SERIES_TRY(series_alloc(transmitted, (size_t)n_steps * NA, "transmitted powers"));
+        SERIES_TRY(series_upload(rec, gnt.rec, "solar gain tables"));
+        SERIES_TRY(series_upload(slice_off, gnt.slice_off.data(), gnt.rec.empty() ? 0 : gnt.slice_off.size(), "solar gain tables"));
+        SERIES_TRY(series_upload(ap, gnt.ap, "solar gain tables"));
+        SERIES_TRY(series_upload(share, gnt.share, "solar gain tables"));
+        apertures.n = (int)NA, apertures.dev = ap_dev.p, apertures.site = b->n_sites > 1 ? b->d_site.p : nullptr;
+        apertures.normal = ap_f64.p, apertures.coef = ap_f64.p + 3 * NA, apertures.tau_scale = ap_f64.p + 9 * NA;
+        apertures.power = power.p, apertures.shade = shades.aperture.p, apertures.sf = shades.factors();
+        view.n_receivers = (int)gnt.rec.size();
+        view.rec = rec.p, view.slice_off = slice_off.p, view.ap = ap.p, view.power = power.p;
+        view.share = reinterpret_cast<const double2 *>(share.p);
+        view.gain[0] = in.d_gain[0].p, view.gain[1] = in.d_gain[1].p;
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_transmitted, hipStream_t st) { return sum.fetch(st, series_fetch(host_transmitted, transmitted, st)); }
 };
 
-// The device copies of the air paths of a series (heat_air_paths): the tables sorted by target zone (plan.hpp, AirPathTables),
-// the state bytes, the accumulators and the path_q rows in the caller's order. Declared beside GainsDev.
-struct AirDev {
+// The room radiation (heat_room_radiation): the entries as CSR over the receivers (plan.hpp, RoomRadiationTables), the face node of
+// every distinct emitter side and the step's emissions, the receivers' records, sum_irradiance (always uploaded), the irradiance rows.
+struct RadiationTerm {
+    int64_t NR = 0;
+    RoomRadiationTables rrt;
+    std::vector<uint32_t> h_face, h_rec;
+    DevBuf<uint32_t> face, rec;                    // [NM], [NR]
+    DevBuf<double> emission, factor, irradiance;   // [NM], [NE], [n_steps][NR]
+    DevBuf<int32_t> off, src;                      // [NR + 1], [NE]
+    Acc<double> sum;
+    SeriesRoomRadiation view{};
+    void prepare(heat_batch *b, heat_room_radiation *radiation, InputsTerm &in) {
+        NR = radiation ? radiation->n_receivers : 0;  // (entries need a receiver: there are none without)
+        if (NR == 0) return;
+        const int64_t S = b->n_surf;
+        build_room_radiation_tables(S, radiation, rrt);
+        h_face.resize(rrt.emitter.size());
+        for (size_t j = 0; j < rrt.emitter.size(); j++) {
+            const int64_t side = rrt.emitter[j] >= S, q = rrt.emitter[j] - side * S;
+            h_face[j] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], side ? (int)b->h_node_count[q] - 1 : 0);
+        }
+        h_rec.resize((size_t)NR);
+        for (int64_t r = 0; r < NR; r++) {
+            const int side = radiation->rc_side[r];
+            h_rec[r] = (uint32_t)((int64_t)side * S + b->h_dev_of[radiation->rc_surface[r]]);
+            in.need_gain(b, 2 + side);  // the long-wave gain arrays of the sides that receive (once each)
+        }
+        sum.bind(radiation->sum_irradiance, 0.0, &view.sum);
+    }
+    int upload(const double *host_irradiance, int n_steps, const InputsTerm &in) {
+        if (NR == 0) return HEAT_OK;
+        SERIES_TRY(series_upload(face, h_face, "room radiation tables"));
+        SERIES_TRY(series_alloc(emission, h_face.size(), "emissions"));
+        SERIES_TRY(series_upload(rec, h_rec, "room radiation tables"));
+        SERIES_TRY(series_upload(off, rrt.off, "room radiation tables"));
+        SERIES_TRY(series_upload(src, rrt.src, "room radiation tables"));
+        SERIES_TRY(series_upload(factor, rrt.factor, "room radiation tables"));
+        SERIES_TRY(sum.stage((size_t)NR, true, "irradiance sums"));
+        if (host_irradiance) SERIES_TRY(series_alloc(irradiance, (size_t)n_steps * NR, "irradiances"));
+        view.n_emitters = (int)h_face.size(), view.n_receivers = (int)NR, view.face = face.p, view.emission = emission.p;
+        view.rec = rec.p, view.off = off.p, view.src = src.p, view.factor = factor.p;
+        view.gain[0] = in.d_gain[2].p, view.gain[1] = in.d_gain[3].p;
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_irradiance, hipStream_t st) { return sum.fetch(st, series_fetch(host_irradiance, irradiance, st)); }
+};
+
+// The ambient drive (heat_ambient_drive), or one heat_batch_set_ambient: the sides' records and the back records that follow a front
+// (plan.hpp, AmbientTables), the caller's lists, the mixing zones and factors only where a side mixes, sum_temperature, the ambient_t rows.
+struct AmbientTerm {
+    int64_t NB = 0;
+    AmbientTables abt;
+    std::vector<int32_t> h_zone;
+    std::vector<double> h_mix;
+    DevBuf<uint32_t> rec, peer;            // [N]
+    DevBuf<int32_t> chan, zone;            // [N]
+    DevBuf<double> gain, offset, mix, t;   // [N]; t: [n_steps][N], the setter: the temperatures [N]
+    Acc<double> sum;
+    SeriesAmbient view{};
+    void prepare(const heat_batch *b, const int32_t *const side_kind[2], heat_ambient_drive *ambient) {
+        NB = ambient ? ambient->n_sides : 0;
+        if (NB == 0) return;
+        build_ambient_tables(b->n_surf, b->h_dev_of.data(), side_kind, NB, ambient->surface, ambient->side, abt);
+        sum.bind(ambient->sum_temperature, 0.0, &view.sum);
+        bool mixes = false;
+        for (int64_t i = 0; i < NB && ambient->mix_zone && !mixes; i++) mixes = ambient->mix_zone[i] >= 0;
+        if (!mixes) return;
+        h_zone.assign(ambient->mix_zone, ambient->mix_zone + NB);
+        h_mix.assign((size_t)NB, 0.0);
+        for (int64_t i = 0; i < NB; i++)
+            if (h_zone[(size_t)i] >= 0) h_mix[(size_t)i] = ambient->mix[i];
+    }
+    int upload_tables() {
+        SERIES_TRY(series_upload(rec, abt.rec, "ambient tables"));
+        SERIES_TRY(series_upload(peer, abt.peer, "ambient tables"));
+        view.rec = rec.p, view.peer = peer.p;
+        return HEAT_OK;
+    }
+    int upload(const heat_ambient_drive *ambient, const double *host_t, int n_steps) {
+        if (NB == 0) return HEAT_OK;
+        SERIES_TRY(upload_tables());
+        SERIES_TRY(series_upload(chan, ambient->chan, (size_t)NB, "ambient tables"));
+        SERIES_TRY(report_array(gain, ambient->gain, (size_t)NB, true, "ambient tables"));
+        SERIES_TRY(report_array(offset, ambient->offset, (size_t)NB, true, "ambient tables"));
+        if (!h_zone.empty()) {
+            SERIES_TRY(series_upload(zone, h_zone, "ambient tables"));
+            SERIES_TRY(series_upload(mix, h_mix, "ambient tables"));
+        }
+        SERIES_TRY(sum.stage((size_t)NB, true, "ambient temperature sums"));
+        if (host_t) SERIES_TRY(series_alloc(t, (size_t)n_steps * NB, "ambient temperatures"));
+        view.n_sides = (int)NB, view.chan = chan.p, view.gain = gain.p, view.offset = offset.p, view.mix_zone = zone.p, view.mix = mix.p;
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_t, hipStream_t st) { return sum.fetch(st, series_fetch(host_t, t, st)); }
+};
+
+// The air paths (heat_air_paths): the list sorted by target zone with CSR offsets (plan.hpp, AirPathTables), the state bytes,
+// the accumulators (always uploaded) and the path_q rows in the caller's order.
+struct AirTerm {
+    heat_air_paths *air = nullptr;
+    int64_t NP = 0;
+    AirPathTables apt;
+    std::vector<uint8_t> h_state;
     DevBuf<int32_t> i32;
-    DevBuf<double> f64;
-    DevBuf<uint8_t> state;     // [NP]
-    DevBuf<double> sum_q;      // [NP]
-    DevBuf<int64_t> i64[2];    // steps_open, switches
-    DevBuf<double> path_q;     // [n_steps][NP]
+    DevBuf<double> f64, path_q;  // path_q: [n_steps][NP]
+    DevBuf<uint8_t> state;       // [NP]
+    Acc<double> sum_q;
+    Acc<int64_t> steps_open, switches;
+    AirPathsDev view{};
+    void prepare(const heat_batch *b, heat_air_paths *air_) {
+        air = air_;
+        NP = air ? air->n_paths : 0;
+        if (NP == 0) return;
+        build_air_path_tables(b->n_zones, air, apt);
+        h_state.assign((size_t)NP, 0);
+        if (air->state) std::copy(air->state, air->state + NP, h_state.begin());
+        sum_q.bind(air->sum_q, 0.0, &view.sum_q), steps_open.bind(air->steps_open, 0, &view.steps_open);
+        switches.bind(air->switches, 0, &view.switches);
+    }
+    int upload(const heat_batch *b, const double *host_q, int n_steps) {
+        if (NP == 0) return HEAT_OK;
+        SERIES_TRY(series_upload(i32, apt.i32, "air path tables"));
+        SERIES_TRY(series_upload(f64, apt.f64, "air path tables"));
+        SERIES_TRY(series_upload(state, h_state, "air path states"));
+        SERIES_TRY(sum_q.stage((size_t)NP, true, "air path accumulators"));
+        SERIES_TRY(steps_open.stage((size_t)NP, true, "air path accumulators"));
+        SERIES_TRY(switches.stage((size_t)NP, true, "air path accumulators"));
+        if (host_q) SERIES_TRY(series_alloc(path_q, (size_t)n_steps * NP, "air path powers"));
+        const int32_t *list = i32.p + (b->n_zones + 1);
+        view.off = i32.p, view.source = list, view.temp_chan = list + NP, view.volume_chan = list + 2 * NP, view.open_chan = list + 3 * NP;
+        view.orig = list + 4 * NP, view.state = state.p;
+        view.volume_gain = f64.p, view.sense = f64.p + NP, view.half_band = f64.p + 2 * NP, view.min_delta = f64.p + 3 * NP;
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_q, hipStream_t st) {
+        if (NP == 0) return hipSuccess;
+        const hipError_t e = series_fetch(air->state, state, st, series_fetch(host_q, path_q, st));
+        return switches.fetch(st, steps_open.fetch(st, sum_q.fetch(st, e)));
+    }
 };
 
-// The device copies of the shades of a series (heat_shades): the shade table (plan.hpp, ShadeTables), the site and horizon
-// numbers, the horizon profiles, the step's sunlit fractions, the shade numbers of the sides in device surface order and of
-// the apertures, the sunlit rows. Declared beside SkyDev.
-struct ShadeDev {
-    DevBuf<double> tab;       // [kShadeRows][NS]
-    DevBuf<int32_t> i32;      // site [NS] | horizon [NS]
-    DevBuf<double> tan2;      // [NH][16]
-    DevBuf<double> f;         // [NS]
-    DevBuf<int32_t> side;     // [2][S]
-    DevBuf<int32_t> aperture; // [NA]
-    DevBuf<double> sunlit;    // [n_steps][NS]
+// What the widest entry point (heat_batch_march_series_ambient) takes; filled by field name. no_trace_ok: a NULL trace records none.
+struct SeriesCall {
+    const heat_series *s = nullptr;
+    const heat_sky *sky = nullptr;
+    const heat_shades *shades = nullptr;
+    const heat_solar_gains *gains = nullptr;
+    const heat_zone_loads *l = nullptr;
+    heat_air_paths *air = nullptr;
+    heat_ideal_loads *il = nullptr;
+    heat_series_report *r = nullptr;
+    double *trace = nullptr, *applied = nullptr, *ideal_q = nullptr, *transmitted = nullptr, *path_q = nullptr, *sunlit = nullptr;
+    heat_room_radiation *radiation = nullptr;
+    double *irradiance = nullptr;
+    heat_ambient_drive *ambient = nullptr;
+    double *ambient_t = nullptr;
+    int32_t *failed_step = nullptr;
+    bool no_trace_ok = false;
 };
-
-// The device copies of the room radiation of a series (heat_room_radiation): the emitters' face nodes and the step's
-// emissions, the receivers' records, the CSR entry tables (plan.hpp, RoomRadiationTables), sum_irradiance and the irradiance
-// rows. Declared beside SkyDev.
-struct RadiationDev {
-    DevBuf<uint32_t> face;       // [NM]
-    DevBuf<double> emission;     // [NM]
-    DevBuf<uint32_t> rec;        // [NR]
-    DevBuf<int32_t> off, src;    // [NR + 1], [NE]
-    DevBuf<double> factor;       // [NE]
-    DevBuf<double> sum;          // [NR]
-    DevBuf<double> irradiance;   // [n_steps][NR]
-};
-
-// The device copies of the ambient drive of a series (heat_ambient_drive) or of one heat_batch_set_ambient: the record
-// tables (plan.hpp, AmbientTables), the caller's lists as given, sum_temperature and the ambient_t rows. Declared beside SkyDev.
-struct AmbientDev {
-    DevBuf<uint32_t> rec, peer;   // [N]
-    DevBuf<int32_t> chan, zone;   // [N]
-    DevBuf<double> gain, offset, mix;  // [N]
-    DevBuf<double> sum;           // [N]
-    DevBuf<double> t;             // [n_steps][N]; the setter: the temperatures [N]
-};
-
-template <typename T>
-int series_alloc(DevBuf<T> &buf, size_t count, const char *what) {
-    const hipError_t e = buf.alloc(count);
-    if (e != hipSuccess)
-        return fail(HEAT_E_DEVICE, "series march: %s (%zu bytes) on the device: %s — nothing has been marched", what, count * sizeof(T),
-                    hipGetErrorString(e));
-    return HEAT_OK;
-}
-// An in/out array of a report: absent (nullptr: no device copy), uploaded (resume), or allocated for the device to initialise.
-template <typename T>
-int report_array(DevBuf<T> &buf, const T *host, size_t count, bool upload, const char *what) {
-    if (!host) return HEAT_OK;
-    return upload ? series_upload(buf, host, count, what) : series_alloc(buf, count, what);
-}
 
 }  // namespace
 
@@ -1488,10 +2022,6 @@ static int download_impl(heat_batch *b, double *state, size_t n_state, int32_t w
     }
     if (delivers_zones) b->host_zones_stale = false;  // (the caller's zone slots are the device's again)
     return HEAT_OK;
-}
-
-static inline StepWeather to_step_weather(const heat_weather &w) {
-    return StepWeather{w.dry_bulb, std::sqrt(w.wind_speed), std::sin(w.wind_direction), std::cos(w.wind_direction)};
 }
 
 // Room for the weather of a march call of n_sub sub-timesteps, in pinned and in device memory (heat_batch_set_weather; the
@@ -2122,753 +2652,217 @@ int heat_batch_march_ex(heat_batch *b, double *state, size_t n_state, const heat
     return download_impl(b, state, n_state, what, true);
 }
 
-// heat_batch_march_series[_loads | _report]: l == nullptr, or loads without a term, is the series without loads; r == nullptr
-// is the series without a report. no_trace_ok: a NULL trace means "record none" (the report's entry point) instead of a refusal.
-// il == nullptr, or no ideal load, is the series without them: the same launches. Likewise sky == nullptr, or no mode bit,
-// and gains == nullptr, or neither an aperture nor an entry, and air == nullptr, or no path, and shades == nullptr, or no shade,
-// and radiation == nullptr, or no receiver, and ambient == nullptr, or no driven side.
-static int march_series_impl(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, bool no_trace_ok,
-                             double *trace, double *applied, int32_t *failed_step, heat_ideal_loads *il = nullptr,
-                             double *ideal_q = nullptr, const heat_sky *sky = nullptr, const heat_solar_gains *gains = nullptr,
-                             double *transmitted = nullptr, heat_air_paths *air = nullptr, double *path_q = nullptr,
-                             const heat_shades *shades = nullptr, double *sunlit = nullptr, heat_room_radiation *radiation = nullptr,
-                             double *irradiance = nullptr, heat_ambient_drive *ambient = nullptr, double *ambient_t = nullptr) {
-    if (failed_step) *failed_step = -1;
+// heat_batch_march_series*: the table of contents of a series march. A term that is absent (its argument NULL, or naming
+// nothing: loads without a term, no ideal load, no mode bit, no aperture, no path, no shade, no receiver, no driven side) is
+// the series without it: the same launches. no_trace_ok: a NULL trace means "record none" instead of a refusal.
+static int march_series_impl(heat_batch *b, const SeriesCall &c) {
+    if (c.failed_step) *c.failed_step = -1;
     if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
+    const heat_series *s = c.s;
     // ---- everything that needs no device (heat_series_check's checks, on the batch's own copies of the slots) ----
     SeriesModel m;
-    m.n_surfaces = b->n_surf;
-    m.n_zones = b->n_zones;
-    m.first_node_slot = b->h_first_slot.data();
-    m.node_count = b->h_node_count.data();
+    m.n_surfaces = b->n_surf, m.n_zones = b->n_zones;
+    m.first_node_slot = b->h_first_slot.data(), m.node_count = b->h_node_count.data();
     for (int a = 0; a < 4; a++) m.out_slot[a] = b->h_out_slots[a].data();
     m.zone_slot = b->h_zone_slot_h.data();
     if (!b->resolver) b->resolver = new SlotResolver(m);
-    int rc = check_series(m, *b->resolver, b->n_sites, s, heat::last_error());
-    if (rc) return rc;
-    rc = check_zone_loads(b->n_zones, s->n_channels, l, heat::last_error());
-    if (rc) return rc;
     std::vector<ResolvedSlot> group_entry;
-    rc = check_series_report(*b->resolver, l, r, heat::last_error(), &group_entry);
-    if (rc) return rc;
     std::vector<int32_t> load_of_zone;
-    rc = check_ideal_loads(b->n_zones, s->n_channels, il, heat::last_error(), &load_of_zone);
-    if (rc) return rc;
-    const int64_t NI = il ? il->n_loads : 0;
-    unsigned sky_bits = 0;
-    rc = check_sky(b->n_surf, s, sky, heat::last_error(), &sky_bits);
-    if (rc) return rc;
+    const int32_t *const side_kind[2] = {b->h_kind[0].data(), b->h_kind[1].data()};
+    SkyTerm sky;
+    int rc;
+    if ((rc = check_series(m, *b->resolver, b->n_sites, s, heat::last_error()))) return rc;
+    if ((rc = check_zone_loads(b->n_zones, s->n_channels, c.l, heat::last_error()))) return rc;
+    if ((rc = check_series_report(*b->resolver, c.l, c.r, heat::last_error(), &group_entry))) return rc;
+    if ((rc = check_ideal_loads(b->n_zones, s->n_channels, c.il, heat::last_error(), &load_of_zone))) return rc;
+    if ((rc = check_sky(b->n_surf, s, c.sky, heat::last_error(), &sky.bits))) return rc;
     if (b->n_ranks > 1) return fail(HEAT_E_INVALID_ARG, "a sharded batch (n_ranks = %d) cannot march a series", b->n_ranks);
     // (behind the shard's refusal: the gains number the surfaces of the caller's model, a shard holds some of them)
-    rc = check_solar_gains(b->n_surf, s, sky, gains, heat::last_error());
-    if (rc) return rc;
-    const int64_t NA = gains ? gains->n_apertures : 0;  // (entries need an aperture: there are none without)
-    rc = check_shades(b->n_surf, s, sky, gains, shades, heat::last_error());
-    if (rc) return rc;
-    const int64_t NS = shades ? shades->n_shades : 0;  // (a side or aperture needs a shade to refer to: none is shaded without)
-    rc = check_air_paths(b->n_zones, s->n_channels, air, heat::last_error());
-    if (rc) return rc;
-    const int64_t NP = air ? air->n_paths : 0;
-    rc = check_room_radiation(b->n_surf, s, sky, radiation, heat::last_error());
-    if (rc) return rc;
-    const int64_t NR = radiation ? radiation->n_receivers : 0;  // (entries need a receiver: there are none without)
-    const int32_t *const side_kind[2] = {b->h_kind[0].data(), b->h_kind[1].data()};
-    rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, ambient, heat::last_error());
-    if (rc) return rc;
-    const int64_t NB = ambient ? ambient->n_sides : 0;
-    const bool loads = l && (l->n_gains > 0 || l->n_flows > 0 || l->n_thermostats > 0);
-    const int64_t NT = loads ? l->n_thermostats : 0;
-    const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes;
+    if ((rc = check_solar_gains(b->n_surf, s, c.sky, c.gains, heat::last_error()))) return rc;
+    if ((rc = check_shades(b->n_surf, s, c.sky, c.gains, c.shades, heat::last_error()))) return rc;
+    if ((rc = check_air_paths(b->n_zones, s->n_channels, c.air, heat::last_error()))) return rc;
+    if ((rc = check_room_radiation(b->n_surf, s, c.sky, c.radiation, heat::last_error()))) return rc;
+    if ((rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, c.ambient, heat::last_error()))) return rc;
+    const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
-    if (!trace && !no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
+    if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
     if (n_steps == 0) return HEAT_OK;
-    rc = select_device(b);
-    if (rc) return rc;
-
-    // ---- the schedules and tables, in the device's order ----
-    // weather: a step's records exactly as heat_batch_set_weather lays them out in d_weather (site-major, weather_cap apart)
-    rc = grow_weather(b, n_sub);  // (once, before the first step: the pointers a captured graph holds stay valid)
-    if (rc) return rc;
+    if ((rc = select_device(b))) return rc;
+    if ((rc = grow_weather(b, n_sub))) return rc;  // (once, before the first step: the pointers a captured graph holds stay valid)
     b->n_weather = n_sub;
-    const size_t n_sites = (size_t)b->n_sites, cap = b->weather_cap;
-    const size_t n_rec = n_sub > 0 ? (n_sites - 1) * cap + (size_t)n_sub : 0;
+    // ---- the terms: host tables first; on the device for the duration of the call, freed on every return path behind the drain ----
+    // The schedules: a step's weather records exactly as heat_batch_set_weather lays them out in d_weather (site-major,
+    // weather_cap apart); the zone terms as rows of [a0[Z] | b0[Z]] as k_begin_march reads them (no rows given: one of zeros)
+    const size_t cap = b->weather_cap, n_rec = n_sub > 0 ? (size_t)(n_sites - 1) * cap + (size_t)n_sub : 0;
+    const int zrows = std::max(s->n_zone_term_steps, 1);
     std::vector<StepWeather> h_w((size_t)n_steps * n_rec, StepWeather{0.0, 0.0, 0.0, 0.0});
+    std::vector<double> h_zab((size_t)zrows * 2 * Z, 0.0);
     for (int k = 0; k < n_steps; k++)
-        for (size_t st = 0; st < n_sites; st++)
+        for (int64_t st = 0; st < n_sites; st++)
             for (int i = 0; i < n_sub; i++)
                 h_w[(size_t)k * n_rec + st * cap + i] = to_step_weather(s->weather[((size_t)k * n_sub + i) * n_sites + st]);
-    // zone terms: rows of [a0[Z] | b0[Z]] as k_begin_march reads them; no rows given: one of zeros
-    const int zrows = std::max(s->n_zone_term_steps, 1);
-    std::vector<double> h_zab((size_t)zrows * 2 * Z, 0.0);
-    if (s->n_zone_term_steps > 0)
-        for (int r = 0; r < zrows; r++)
-            for (int64_t z = 0; z < Z; z++) {
-                if (s->zone_a0) h_zab[((size_t)r * 2) * Z + z] = s->zone_a0[(size_t)r * Z + z];
-                if (s->zone_b0) h_zab[((size_t)r * 2 + 1) * Z + z] = s->zone_b0[(size_t)r * Z + z];
-            }
-    // driven inputs: channel numbers and gains per DEVICE surface, structure of arrays
-    const int32_t *chan[4] = {s->solar_front_chan, s->solar_back_chan, s->ir_front_chan, s->ir_back_chan};
-    const double *gain[4] = {s->solar_front_gain, s->solar_back_gain, s->ir_front_gain, s->ir_back_gain};
-    bool driven = false, own_any = false;
-    for (int a = 0; a < 4; a++)
-        if (chan[a])
-            for (int64_t q = 0; q < S && !driven; q++) driven = chan[a][q] >= 0;
-    if (s->ir_own_face)
-        for (int64_t q = 0; q < S && !own_any; q++) own_any = (s->ir_own_face[q] & 3) != 0;
-    std::vector<int32_t> h_chan;
-    std::vector<double> h_gain[4];
-    std::vector<uint8_t> h_own;
-    std::vector<uint32_t> h_face;
-    if (driven) {
-        const int64_t *orig_of = b->h_orig_of.data();
-        h_chan.assign(4 * (size_t)S, -1);
-        for (int a = 0; a < 4; a++) {
-            if (!chan[a]) continue;
-            int32_t *dst = h_chan.data() + (size_t)a * S;
-            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) dst[d] = chan[a][orig_of[d]]; });
-            if (!gain[a]) continue;
-            h_gain[a].resize((size_t)S);
-            double *gd = h_gain[a].data();
-            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
-        }
-        if (own_any) {
-            h_own.resize((size_t)S);
-            h_face.resize(2 * (size_t)S);
-            b->pool->run(S, [&](int64_t d0, int64_t d1) {
-                for (int64_t d = d0; d < d1; d++) {
-                    const int64_t q = orig_of[d];
-                    h_own[d] = (uint8_t)(s->ir_own_face[q] & 3);
-                    h_face[d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], 0);
-                    h_face[S + d] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], (int)b->h_node_count[q] - 1);
-                }
-            });
-        }
+    for (int64_t i = 0; i < (int64_t)zrows * Z && s->n_zone_term_steps > 0; i++) {
+        if (s->zone_a0) h_zab[(size_t)(i / Z * 2 * Z + i % Z)] = s->zone_a0[i];
+        if (s->zone_b0) h_zab[(size_t)((i / Z * 2 + 1) * Z + i % Z)] = s->zone_b0[i];
     }
-    // sky: mode bytes and normals per DEVICE surface; the gain arrays of the inputs it drives, where the channels have not
-    // brought them along already
-    std::vector<uint8_t> h_sky_mode;
-    std::vector<double> h_sky_normal;
-    if (sky_bits) {
-        const int64_t *orig_of = b->h_orig_of.data();
-        h_sky_mode.resize((size_t)S);
-        h_sky_normal.resize(3 * (size_t)S);
-        b->pool->run(S, [&](int64_t d0, int64_t d1) {
-            for (int64_t d = d0; d < d1; d++) {
-                const int64_t q = orig_of[d];
-                const bool on = sky->mode[q] != 0;  // (the normals of the other surfaces are not read, not even here)
-                h_sky_mode[d] = sky->mode[q];
-                h_sky_normal[d] = on ? sky->normal_x[q] : 0.0;
-                h_sky_normal[S + d] = on ? sky->normal_y[q] : 0.0;
-                h_sky_normal[2 * S + d] = on ? sky->normal_z[q] : 0.0;
-            }
-        });
-        for (int a = 0; a < 4; a++) {
-            if (!(sky_bits >> a & 1) || !gain[a] || !h_gain[a].empty()) continue;
-            h_gain[a].resize((size_t)S);
-            double *gd = h_gain[a].data();
-            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
-        }
-    }
-    // solar gains: the apertures as structure of arrays, the entries as sliced ELL over the receivers in device record order;
-    // the solar gain arrays of the sides that receive, where neither the channels nor the sky have brought them along
-    std::vector<int32_t> h_ap_dev;
-    std::vector<double> h_ap_f64;
-    SolarGainTables gnt;
-    if (NA > 0) {
-        h_ap_dev.resize((size_t)NA);
-        h_ap_f64.resize(11 * (size_t)NA);
-        for (int64_t a = 0; a < NA; a++) {
-            h_ap_dev[a] = b->h_dev_of[gains->ap_surface[a]];
-            h_ap_f64[a] = gains->ap_normal_x[a];
-            h_ap_f64[NA + a] = gains->ap_normal_y[a];
-            h_ap_f64[2 * NA + a] = gains->ap_normal_z[a];
-            for (int j = 0; j < 6; j++) h_ap_f64[(3 + j) * NA + a] = gains->ap_tau_coef[6 * a + j];
-            h_ap_f64[9 * NA + a] = gains->ap_tau_diffuse[a];
-            h_ap_f64[10 * NA + a] = gains->ap_scale[a];
-        }
-        build_solar_gain_tables(S, b->h_dev_of.data(), gains, gnt);
-        bool receives[2] = {false, false};
-        for (uint32_t rec : gnt.rec) receives[rec >= (uint64_t)S] = true;
-        const int64_t *orig_of = b->h_orig_of.data();
-        for (int a = 0; a < 2; a++) {
-            if (!receives[a] || !gain[a] || !h_gain[a].empty()) continue;
-            h_gain[a].resize((size_t)S);
-            double *gd = h_gain[a].data();
-            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
-        }
-    }
-    // shades: the table as structure of arrays, every shade's site, the shade numbers of the sides per DEVICE surface
-    ShadeTables sht;
-    std::vector<int32_t> h_shade_i32, h_shade_side;
-    if (NS > 0) {
-        build_shade_tables(shades, sht);
-        h_shade_i32.assign(2 * (size_t)NS, 0);
-        for (int64_t j = 0; j < NS; j++) {
-            h_shade_i32[j] = b->h_site.empty() ? 0 : b->h_site[b->h_dev_of[shades->sh_surface[j]]];
-            h_shade_i32[NS + j] = sht.horizon[j];
-        }
-        if ((sky_bits & 3) && (shades->front_shade || shades->back_shade)) {
-            const int64_t *orig_of = b->h_orig_of.data();
-            const int32_t *side_shade[2] = {shades->front_shade, shades->back_shade};
-            h_shade_side.assign(2 * (size_t)S, -1);
-            for (int a = 0; a < 2; a++) {
-                if (!side_shade[a]) continue;
-                int32_t *dst = h_shade_side.data() + (size_t)a * S;
-                b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) dst[d] = side_shade[a][orig_of[d]]; });
-            }
-        }
-    }
-    // room radiation: the entries as CSR over the receivers, the face node of every distinct emitter side, the receivers'
-    // device records; the long-wave gain arrays of the sides that receive, where neither the channels nor the sky have
-    // brought them along
-    RoomRadiationTables rrt;
-    std::vector<uint32_t> h_rr_face, h_rr_rec;
-    if (NR > 0) {
-        build_room_radiation_tables(S, radiation, rrt);
-        h_rr_face.resize(rrt.emitter.size());
-        for (size_t j = 0; j < rrt.emitter.size(); j++) {
-            const int64_t side = rrt.emitter[j] >= S, q = rrt.emitter[j] - side * S;
-            h_rr_face[j] = (uint32_t)node_slot_index(b->h_node_tile_base[q], b->h_node_geom[q], side ? (int)b->h_node_count[q] - 1 : 0);
-        }
-        h_rr_rec.resize((size_t)NR);
-        bool receives[2] = {false, false};
-        for (int64_t r = 0; r < NR; r++) {
-            const int side = radiation->rc_side[r];
-            h_rr_rec[r] = (uint32_t)((int64_t)side * S + b->h_dev_of[radiation->rc_surface[r]]);
-            receives[side] = true;
-        }
-        const int64_t *orig_of = b->h_orig_of.data();
-        for (int a = 2; a < 4; a++) {
-            if (!receives[a - 2] || !gain[a] || !h_gain[a].empty()) continue;
-            h_gain[a].resize((size_t)S);
-            double *gd = h_gain[a].data();
-            b->pool->run(S, [&](int64_t d0, int64_t d1) { for (int64_t d = d0; d < d1; d++) gd[d] = gain[a][orig_of[d]]; });
-        }
-    }
-    // ambient drive: the sides' device records and the back records that follow a front; the mixing zones and factors only
-    // where a side mixes (mix is read only there)
-    AmbientTables abt;
-    std::vector<int32_t> h_amb_zone;
-    std::vector<double> h_amb_mix;
-    if (NB > 0) {
-        build_ambient_tables(S, b->h_dev_of.data(), side_kind, NB, ambient->surface, ambient->side, abt);
-        bool mixes = false;
-        for (int64_t i = 0; i < NB && ambient->mix_zone && !mixes; i++) mixes = ambient->mix_zone[i] >= 0;
-        if (mixes) {
-            h_amb_zone.assign(ambient->mix_zone, ambient->mix_zone + NB);
-            h_amb_mix.assign((size_t)NB, 0.0);
-            for (int64_t i = 0; i < NB; i++)
-                if (h_amb_zone[(size_t)i] >= 0) h_amb_mix[(size_t)i] = ambient->mix[i];
-        }
-    }
-    // probes: (buffer, index) of every probed slot
-    std::vector<uint8_t> h_pbuf((size_t)P);
-    std::vector<uint32_t> h_pidx((size_t)P);
-    auto place = [&](int kind, int64_t index, int node, uint8_t &buf, uint32_t &idx) {
-        if (kind == PROBE_ZONE) {
-            buf = (uint8_t)kProbeBufZone;
-            idx = (uint32_t)index;
-        } else if (kind == PROBE_NODE) {
-            buf = (uint8_t)kProbeBufT;
-            idx = (uint32_t)node_slot_index(b->h_node_tile_base[index], b->h_node_geom[index], node);
-        } else {  // hs front, hs back, flow front, flow back: SideOut record side * S + d, as doubles
-            const int a = kind - PROBE_HS_FRONT;
-            const int64_t rec = (int64_t)(a & 1) * S + b->h_dev_of[index];
-            buf = (uint8_t)kProbeBufOut;
-            idx = (uint32_t)(2 * rec + (a >> 1));
-        }
-    };
-    for (int64_t p = 0; p < P; p++) {
-        int kind = 0, node = 0;
-        int64_t index = 0;
-        if (!b->resolver->resolve(s->probe_slot[p], kind, index, node)) return fail(HEAT_E_SIZE, "probe %lld: slot not resolved", (long long)p);
-        place(kind, index, node, h_pbuf[p], h_pidx[p]);
-    }
-    // report: the group entries sorted into device order (buffer, index) and cut into segments (plan.hpp)
-    const int64_t G = r ? r->n_groups : 0, Q = P + G;
-    const bool th_stats = r && (r->th_steps_heating || r->th_steps_cooling || r->th_switches || r->th_sum_heating || r->th_sum_cooling);
-    GroupTables gt;
-    std::vector<uint8_t> h_gbuf;
-    std::vector<uint32_t> h_gidx;
-    if (G > 0) {
-        const int64_t n_entries = r->group_offset[G];
-        std::vector<uint64_t> key((size_t)n_entries);
-        for (int64_t i = 0; i < n_entries; i++) {
-            uint8_t buf = 0;
-            uint32_t idx = 0;
-            place(group_entry[(size_t)i].kind, group_entry[(size_t)i].index, group_entry[(size_t)i].node, buf, idx);
-            key[(size_t)i] = (uint64_t)buf << 32 | idx;
-        }
-        build_group_tables(G, r->group_offset, r->group_weight, key.data(), gt);
-        h_gbuf.resize((size_t)n_entries);
-        h_gidx.resize((size_t)n_entries);
-        for (int64_t i = 0; i < n_entries; i++) {
-            h_gbuf[(size_t)i] = (uint8_t)(gt.key[(size_t)i] >> 32);
-            h_gidx[(size_t)i] = (uint32_t)gt.key[(size_t)i];
-        }
-    }
-
-    // zone loads: the term lists sorted by zone with CSR offsets (plan.hpp), the mode bytes in the caller's order
-    ZoneLoadTables zt;
-    std::vector<uint8_t> h_mode;
-    if (loads) {
-        build_zone_load_tables(Z, l, zt);
-        h_mode.assign((size_t)NT, 0);
-        if (l->th_mode) std::copy(l->th_mode, l->th_mode + NT, h_mode.begin());
-    }
-
-    // air paths: the list sorted by target zone with CSR offsets (plan.hpp), the state bytes in the caller's order
-    AirPathTables apt;
-    std::vector<uint8_t> h_air_state;
-    if (NP > 0) {
-        build_air_path_tables(Z, air, apt);
-        h_air_state.assign((size_t)NP, 0);
-        if (air->state) std::copy(air->state, air->state + NP, h_air_state.begin());
-    }
-
-    // ---- on the device for the duration of the call; freed on every return path, after the stream has run dry ----
-    DevBuf<int32_t> d_zl_i32;
-    DevBuf<double> d_zl_f64, d_applied;
-    DevBuf<uint8_t> d_mode;
     DevBuf<StepWeather> d_w;
-    DevBuf<double> d_zab, d_channel, d_gain[4], d_trace;
-    DevBuf<int32_t> d_chan;
-    DevBuf<uint8_t> d_own, d_pbuf;
-    DevBuf<uint32_t> d_face, d_pidx;
-    DevBuf<int> d_fail;
-    ReportDev rd;
-    IdealDev idd;
-    SkyDev skd;
-    GainsDev gnd;
-    AirDev aird;
-    ShadeDev shd;
-    RadiationDev rrd;
-    AmbientDev abd;
+    DevBuf<double> d_zab, d_channel;
+    InputsTerm in; ProbesTerm probes; LoadsTerm loads; ReportTerm report; IdealTerm ideal;
+    ShadesTerm shades; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air;
+    in.prepare(b, s);
+    sky.prepare(b, c.sky, in);
+    gains.prepare(b, c.gains, in);
+    shades.prepare(b, c.shades, sky.bits);
+    radiation.prepare(b, c.radiation, in);
+    ambient.prepare(b, side_kind, c.ambient);
+    if ((rc = probes.prepare(b, s))) return rc;
+    report.prepare(b, c.r, P, group_entry);
+    loads.prepare(b, c.l);
+    ideal.prepare(c.il, load_of_zone);
+    air.prepare(b, c.air);
+    const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
     SeriesDrain drain{b};
-    if ((rc = series_upload(d_w, h_w.data(), h_w.size(), "weather schedule"))) return rc;
-    if ((rc = series_upload(d_zab, h_zab.data(), h_zab.size(), "zone terms"))) return rc;
+    if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
+    if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
     if ((rc = series_upload(d_channel, s->channel, (size_t)n_steps * NC, "channel table"))) return rc;
-    if ((rc = series_upload(d_chan, h_chan.data(), h_chan.size(), "channel numbers"))) return rc;
-    for (int a = 0; a < 4; a++)
-        if ((rc = series_upload(d_gain[a], h_gain[a].data(), h_gain[a].size(), "gains"))) return rc;
-    if ((rc = series_upload(d_own, h_own.data(), h_own.size(), "own-face bits"))) return rc;
-    if ((rc = series_upload(d_face, h_face.data(), h_face.size(), "face node table"))) return rc;
-    if ((rc = series_upload(d_pbuf, h_pbuf.data(), h_pbuf.size(), "probe table"))) return rc;
-    if ((rc = series_upload(d_pidx, h_pidx.data(), h_pidx.size(), "probe table"))) return rc;
-    const int fail_init[5] = {-1, 0, 0, 0, 0};
-    if ((rc = series_upload(d_fail, fail_init, 5, "failed step"))) return rc;
-    if (trace) {
-        const hipError_t e = d_trace.alloc((size_t)n_steps * P);
-        if (e != hipSuccess)
-            return fail(HEAT_E_DEVICE, "series march: trace (%zu bytes) on the device: %s — nothing has been marched",
-                        (size_t)n_steps * P * sizeof(double), hipGetErrorString(e));
-    }
-    ZoneLoadsDev zl{};
-    if (loads) {
-        // (packed into two uploads, not thirteen: each one is an allocation and a pageable copy in the call's set-up)
-        const std::vector<int32_t> *i32[8] = {&zt.off, &zt.gain_chan, &zt.flow_volume_chan, &zt.flow_temp_chan, &zt.th_sensor,
-                                              &zt.th_heat_chan, &zt.th_cool_chan, &zt.th_orig};
-        const std::vector<double> *f64[5] = {&zt.gain_factor, &zt.flow_volume_gain, &zt.th_heat_power, &zt.th_cool_power, &zt.th_half_band};
-        std::vector<int32_t> h_i32;
-        std::vector<double> h_f64;
-        size_t at_i32[8], at_f64[5];
-        for (int a = 0; a < 8; a++) { at_i32[a] = h_i32.size(); h_i32.insert(h_i32.end(), i32[a]->begin(), i32[a]->end()); }
-        for (int a = 0; a < 5; a++) { at_f64[a] = h_f64.size(); h_f64.insert(h_f64.end(), f64[a]->begin(), f64[a]->end()); }
-        if ((rc = series_upload(d_zl_i32, h_i32.data(), h_i32.size(), "zone load tables"))) return rc;
-        if ((rc = series_upload(d_zl_f64, h_f64.data(), h_f64.size(), "zone load tables"))) return rc;
-        if ((rc = series_upload(d_mode, h_mode.data(), h_mode.size(), "thermostat modes"))) return rc;
-        if (applied) {
-            const hipError_t e = d_applied.alloc((size_t)n_steps * NT);
-            if (e != hipSuccess)
-                return fail(HEAT_E_DEVICE, "series march: applied powers (%zu bytes) on the device: %s — nothing has been marched",
-                            (size_t)n_steps * NT * sizeof(double), hipGetErrorString(e));
-        }
-        zl.off = d_zl_i32.p + at_i32[0];
-        zl.gain_chan = d_zl_i32.p + at_i32[1];
-        zl.flow_volume_chan = d_zl_i32.p + at_i32[2];
-        zl.flow_temp_chan = d_zl_i32.p + at_i32[3];
-        zl.th_sensor = d_zl_i32.p + at_i32[4];
-        zl.th_heat_chan = d_zl_i32.p + at_i32[5];
-        zl.th_cool_chan = d_zl_i32.p + at_i32[6];
-        zl.th_orig = d_zl_i32.p + at_i32[7];
-        zl.gain_factor = d_zl_f64.p + at_f64[0];
-        zl.flow_volume_gain = d_zl_f64.p + at_f64[1];
-        zl.th_heat_power = d_zl_f64.p + at_f64[2];
-        zl.th_cool_power = d_zl_f64.p + at_f64[3];
-        zl.th_half_band = d_zl_f64.p + at_f64[4];
-        zl.th_mode = d_mode.p;
-    }
-    SeriesGroupsDev gd{};
-    SeriesStatsDev sd{};
-    SeriesThStatsDev td{};
-    bool q_stats = false;
-    if (r) {
-        const bool resume = r->resume != 0;
-        const size_t n_wave = gt.wave_seg.size() / 3, n_row = gt.row_seg.size() / 3;
-        std::vector<uint32_t> h_seg(gt.wave_seg);
-        h_seg.insert(h_seg.end(), gt.row_seg.begin(), gt.row_seg.end());
-        if ((rc = series_upload(rd.gbuf, h_gbuf.data(), h_gbuf.size(), "group tables"))) return rc;
-        if ((rc = series_upload(rd.gidx, h_gidx.data(), h_gidx.size(), "group tables"))) return rc;
-        if ((rc = series_upload(rd.gw, gt.weight.data(), gt.weight.size(), "group tables"))) return rc;
-        if ((rc = series_upload(rd.seg, h_seg.data(), h_seg.size(), "group tables"))) return rc;
-        if ((rc = series_upload(rd.part_off, gt.part_off.data(), G > 0 ? gt.part_off.size() : 0, "group tables"))) return rc;
-        if ((rc = series_alloc(rd.part, n_wave + n_row, "group sums"))) return rc;
-        if ((rc = report_array(rd.group_trace, r->group_trace, (size_t)n_steps * G, false, "group trace"))) return rc;
-        double *const f64[7] = {r->q_min, r->q_max, r->q_sum, r->q_deg_below, r->q_deg_above, const_cast<double *>(r->q_lo),
-                                const_cast<double *>(r->q_hi)};
-        int64_t *const i64[4] = {r->q_step_min, r->q_step_max, r->q_n_below, r->q_n_above};
-        for (int a = 0; a < 7; a++)
-            if ((rc = report_array(rd.f64[a], f64[a], (size_t)Q, resume || a >= 5, "statistics"))) return rc;
-        for (int a = 0; a < 4; a++)
-            if ((rc = report_array(rd.i64[a], i64[a], (size_t)Q, resume, "statistics"))) return rc;
-        gd.buf = rd.gbuf.p, gd.idx = rd.gidx.p, gd.weight = rd.gw.p;
-        gd.wave_seg = rd.seg.p, gd.row_seg = rd.seg.p + 3 * n_wave;
-        gd.n_wave = (int)n_wave, gd.n_row = (int)n_row;
-        gd.part = rd.part.p;
-        sd.n_probes = P, sd.n_groups = G;
-        sd.buf = d_pbuf.p, sd.idx = d_pidx.p;
-        sd.part = rd.part.p, sd.part_off = rd.part_off.p;
-        sd.q_min = rd.f64[0].p, sd.q_max = rd.f64[1].p, sd.q_sum = rd.f64[2].p, sd.q_deg_below = rd.f64[3].p, sd.q_deg_above = rd.f64[4].p;
-        // (a limit nothing is counted against is not read)
-        sd.q_lo = rd.i64[2].p || rd.f64[3].p ? rd.f64[5].p : nullptr;
-        sd.q_hi = rd.i64[3].p || rd.f64[4].p ? rd.f64[6].p : nullptr;
-        sd.q_step_min = rd.i64[0].p, sd.q_step_max = rd.i64[1].p, sd.q_n_below = rd.i64[2].p, sd.q_n_above = rd.i64[3].p;
-        q_stats = Q > 0 && (sd.q_min || sd.q_max || sd.q_sum || sd.q_n_below || sd.q_deg_below || sd.q_n_above || sd.q_deg_above ||
-                            rd.group_trace.p);
-        if (th_stats) {  // (check_series_report: only with thermostats)
-            double *const tf[2] = {r->th_sum_heating, r->th_sum_cooling};
-            int64_t *const ti[3] = {r->th_steps_heating, r->th_steps_cooling, r->th_switches};
-            for (int a = 0; a < 2; a++)
-                if ((rc = report_array(rd.th_f64[a], tf[a], (size_t)NT, resume, "thermostat statistics"))) return rc;
-            for (int a = 0; a < 3; a++)
-                if ((rc = report_array(rd.th_i64[a], ti[a], (size_t)NT, resume, "thermostat statistics"))) return rc;
-            if ((rc = series_upload(rd.prev, h_mode.data(), h_mode.size(), "thermostat modes"))) return rc;
-            // (the powers of the step: a row of the applied buffer, or one row of scratch where the caller takes none)
-            if (!d_applied.p && (tf[0] || tf[1]) && (rc = series_alloc(rd.applied_row, (size_t)NT, "applied powers"))) return rc;
-            td.sum_heating = rd.th_f64[0].p, td.sum_cooling = rd.th_f64[1].p;
-            td.steps_heating = rd.th_i64[0].p, td.steps_cooling = rd.th_i64[1].p, td.switches = rd.th_i64[2].p;
-            td.prev = rd.prev.p;
-        }
-    }
-    IdealLoadsDev ild{};
-    if (NI > 0) {
-        const bool resume = il->resume != 0;
-        const double inf = std::numeric_limits<double>::infinity();
-        std::vector<int32_t> h_i32(load_of_zone);
-        h_i32.insert(h_i32.end(), il->heat_chan, il->heat_chan + NI);
-        h_i32.insert(h_i32.end(), il->cool_chan, il->cool_chan + NI);
-        std::vector<double> h_cap(2 * (size_t)NI, inf);
-        if (il->heat_cap) std::copy(il->heat_cap, il->heat_cap + NI, h_cap.begin());
-        if (il->cool_cap) std::copy(il->cool_cap, il->cool_cap + NI, h_cap.begin() + NI);
-        if ((rc = series_upload(idd.i32, h_i32.data(), h_i32.size(), "ideal load tables"))) return rc;
-        if ((rc = series_upload(idd.cap, h_cap.data(), h_cap.size(), "ideal load tables"))) return rc;
-        if ((rc = series_alloc(idd.step, 3 * (size_t)NI, "ideal load setpoints"))) return rc;
-        if (ideal_q && (rc = series_alloc(idd.q, (size_t)n_steps * NI, "ideal powers"))) return rc;
-        double *const f64[4] = {il->sum_heating, il->sum_cooling, il->peak_heating, il->peak_cooling};
-        int64_t *const i64[4] = {il->step_peak_heating, il->step_peak_cooling, il->n_sat_heating, il->n_sat_cooling};
-        for (int a = 0; a < 4; a++)
-            if ((rc = report_array(idd.f64[a], f64[a], (size_t)NI, resume, "ideal load accumulators"))) return rc;
-        for (int a = 0; a < 4; a++)
-            if ((rc = report_array(idd.i64[a], i64[a], (size_t)NI, resume, "ideal load accumulators"))) return rc;
-        ild.n_loads = (int)NI;
-        ild.load_of_zone = idd.i32.p, ild.heat_chan = idd.i32.p + Z, ild.cool_chan = idd.i32.p + Z + NI;
-        ild.heat_cap = idd.cap.p, ild.cool_cap = idd.cap.p + NI;
-        ild.setpoint = idd.step.p, ild.qsum = idd.step.p + 2 * NI;
-        ild.sum_heating = idd.f64[0].p, ild.sum_cooling = idd.f64[1].p, ild.peak_heating = idd.f64[2].p, ild.peak_cooling = idd.f64[3].p;
-        ild.step_peak_heating = idd.i64[0].p, ild.step_peak_cooling = idd.i64[1].p;
-        ild.n_sat_heating = idd.i64[2].p, ild.n_sat_cooling = idd.i64[3].p;
-    }
-    SeriesSky skyd{};
-    if (sky_bits || NA > 0 || NS > 0)
-        if ((rc = series_upload(skd.record, reinterpret_cast<const SkyRecord *>(sky->record), (size_t)n_steps * n_sites, "sky records")))
-            return rc;
-    if (sky_bits) {
-        if ((rc = series_upload(skd.mode, h_sky_mode.data(), h_sky_mode.size(), "sky modes"))) return rc;
-        if ((rc = series_upload(skd.normal, h_sky_normal.data(), h_sky_normal.size(), "sky normals"))) return rc;
-        skyd.mode = skd.mode.p;
-        skyd.normal = skd.normal.p;
-        skyd.site = b->n_sites > 1 ? b->d_site.p : nullptr;
-        for (int a = 0; a < 4; a++) skyd.gain[a] = d_gain[a].p;
-    }
-    SeriesShades shdd{};
-    if (NS > 0) {
-        const int64_t NH = shades->n_horizons;
-        if ((rc = series_upload(shd.tab, sht.f64.data(), sht.f64.size(), "shade table"))) return rc;
-        if ((rc = series_upload(shd.i32, h_shade_i32.data(), h_shade_i32.size(), "shade table"))) return rc;
-        if ((rc = series_upload(shd.tan2, shades->horizon_tan2, 16 * (size_t)NH, "horizon profiles"))) return rc;
-        if ((rc = series_alloc(shd.f, (size_t)NS, "sunlit fractions"))) return rc;
-        if ((rc = series_upload(shd.side, h_shade_side.data(), h_shade_side.size(), "shade numbers"))) return rc;
-        if (NA > 0 && shades->aperture_shade && (rc = series_upload(shd.aperture, shades->aperture_shade, (size_t)NA, "shade numbers"))) return rc;
-        if (sunlit && (rc = series_alloc(shd.sunlit, (size_t)n_steps * NS, "sunlit fractions"))) return rc;
-        shdd.n = (int)NS;
-        shdd.site = shd.i32.p, shdd.horizon = shd.i32.p + NS;
-        shdd.tab = shd.tab.p;
-        shdd.tan2 = shd.tan2.p;
-        shdd.f = shd.f.p;
-        const ShadeFactors sf{shd.f.p, shd.tab.p + (size_t)SH_FD * NS, shd.tab.p + (size_t)SH_FG * NS};
-        skyd.shade = shd.side.p;
-        skyd.sf = sf;
-    }
-    SeriesApertures apd{};
-    SeriesGains gnsd{};
-    if (NA > 0) {
-        if ((rc = series_upload(gnd.ap_dev, h_ap_dev.data(), h_ap_dev.size(), "aperture tables"))) return rc;
-        if ((rc = series_upload(gnd.ap_f64, h_ap_f64.data(), h_ap_f64.size(), "aperture tables"))) return rc;
-        if ((rc = series_alloc(gnd.power, (size_t)NA, "aperture powers"))) return rc;
-        if ((rc = report_array(gnd.sum, gains->ap_sum, (size_t)NA, true, "aperture sums"))) return rc;
-        if (transmitted && (rc = series_alloc(gnd.transmitted, (size_t)n_steps * NA, "transmitted powers"))) return rc;
-        if ((rc = series_upload(gnd.rec, gnt.rec.data(), gnt.rec.size(), "solar gain tables"))) return rc;
-        if ((rc = series_upload(gnd.slice_off, gnt.slice_off.data(), gnt.rec.empty() ? 0 : gnt.slice_off.size(), "solar gain tables"))) return rc;
-        if ((rc = series_upload(gnd.ap, gnt.ap.data(), gnt.ap.size(), "solar gain tables"))) return rc;
-        if ((rc = series_upload(gnd.share, gnt.share.data(), gnt.share.size(), "solar gain tables"))) return rc;
-        apd.n = (int)NA;
-        apd.dev = gnd.ap_dev.p;
-        apd.site = b->n_sites > 1 ? b->d_site.p : nullptr;
-        apd.normal = gnd.ap_f64.p, apd.coef = gnd.ap_f64.p + 3 * NA, apd.tau_scale = gnd.ap_f64.p + 9 * NA;
-        apd.power = gnd.power.p;
-        apd.sum = gnd.sum.p;
-        apd.shade = shd.aperture.p;
-        apd.sf = ShadeFactors{shd.f.p, shd.tab.p + (size_t)SH_FD * NS, shd.tab.p + (size_t)SH_FG * NS};
-        gnsd.n_receivers = (int)gnt.rec.size();
-        gnsd.rec = gnd.rec.p, gnsd.slice_off = gnd.slice_off.p, gnsd.ap = gnd.ap.p;
-        gnsd.share = reinterpret_cast<const double2 *>(gnd.share.p);
-        gnsd.power = gnd.power.p;
-        gnsd.gain[0] = d_gain[0].p, gnsd.gain[1] = d_gain[1].p;
-    }
-    SeriesRoomRadiation rrdd{};
-    if (NR > 0) {
-        const size_t NM = rrt.emitter.size();
-        if ((rc = series_upload(rrd.face, h_rr_face.data(), NM, "room radiation tables"))) return rc;
-        if ((rc = series_alloc(rrd.emission, NM, "emissions"))) return rc;
-        if ((rc = series_upload(rrd.rec, h_rr_rec.data(), h_rr_rec.size(), "room radiation tables"))) return rc;
-        if ((rc = series_upload(rrd.off, rrt.off.data(), rrt.off.size(), "room radiation tables"))) return rc;
-        if ((rc = series_upload(rrd.src, rrt.src.data(), rrt.src.size(), "room radiation tables"))) return rc;
-        if ((rc = series_upload(rrd.factor, rrt.factor.data(), rrt.factor.size(), "room radiation tables"))) return rc;
-        if ((rc = report_array(rrd.sum, radiation->sum_irradiance, (size_t)NR, true, "irradiance sums"))) return rc;
-        if (irradiance && (rc = series_alloc(rrd.irradiance, (size_t)n_steps * NR, "irradiances"))) return rc;
-        rrdd.n_emitters = (int)NM, rrdd.n_receivers = (int)NR;
-        rrdd.face = rrd.face.p, rrdd.emission = rrd.emission.p;
-        rrdd.rec = rrd.rec.p, rrdd.off = rrd.off.p, rrdd.src = rrd.src.p, rrdd.factor = rrd.factor.p;
-        rrdd.gain[0] = d_gain[2].p, rrdd.gain[1] = d_gain[3].p;
-        rrdd.sum = rrd.sum.p;
-    }
-    SeriesAmbient abdd{};
-    if (NB > 0) {
-        if ((rc = series_upload(abd.rec, abt.rec.data(), abt.rec.size(), "ambient tables"))) return rc;
-        if ((rc = series_upload(abd.peer, abt.peer.data(), abt.peer.size(), "ambient tables"))) return rc;
-        if ((rc = series_upload(abd.chan, ambient->chan, (size_t)NB, "ambient tables"))) return rc;
-        if ((rc = report_array(abd.gain, ambient->gain, (size_t)NB, true, "ambient tables"))) return rc;
-        if ((rc = report_array(abd.offset, ambient->offset, (size_t)NB, true, "ambient tables"))) return rc;
-        if (!h_amb_zone.empty()) {
-            if ((rc = series_upload(abd.zone, h_amb_zone.data(), h_amb_zone.size(), "ambient tables"))) return rc;
-            if ((rc = series_upload(abd.mix, h_amb_mix.data(), h_amb_mix.size(), "ambient tables"))) return rc;
-        }
-        if ((rc = report_array(abd.sum, ambient->sum_temperature, (size_t)NB, true, "ambient temperature sums"))) return rc;
-        if (ambient_t && (rc = series_alloc(abd.t, (size_t)n_steps * NB, "ambient temperatures"))) return rc;
-        abdd.n_sides = (int)NB;
-        abdd.rec = abd.rec.p, abdd.peer = abd.peer.p, abdd.chan = abd.chan.p;
-        abdd.gain = abd.gain.p, abdd.offset = abd.offset.p;
-        abdd.mix_zone = abd.zone.p, abdd.mix = abd.mix.p;
-        abdd.sum = abd.sum.p;
-    }
-    AirPathsDev airp{};
-    if (NP > 0) {
-        if ((rc = series_upload(aird.i32, apt.i32.data(), apt.i32.size(), "air path tables"))) return rc;
-        if ((rc = series_upload(aird.f64, apt.f64.data(), apt.f64.size(), "air path tables"))) return rc;
-        if ((rc = series_upload(aird.state, h_air_state.data(), h_air_state.size(), "air path states"))) return rc;
-        if ((rc = report_array(aird.sum_q, air->sum_q, (size_t)NP, true, "air path accumulators"))) return rc;
-        if ((rc = report_array(aird.i64[0], air->steps_open, (size_t)NP, true, "air path accumulators"))) return rc;
-        if ((rc = report_array(aird.i64[1], air->switches, (size_t)NP, true, "air path accumulators"))) return rc;
-        if (path_q && (rc = series_alloc(aird.path_q, (size_t)n_steps * NP, "air path powers"))) return rc;
-        const int32_t *list = aird.i32.p + (Z + 1);
-        airp.off = aird.i32.p;
-        airp.source = list, airp.temp_chan = list + NP, airp.volume_chan = list + 2 * NP, airp.open_chan = list + 3 * NP;
-        airp.orig = list + 4 * NP;
-        airp.volume_gain = aird.f64.p, airp.sense = aird.f64.p + NP, airp.half_band = aird.f64.p + 2 * NP;
-        airp.min_delta = aird.f64.p + 3 * NP;
-        airp.state = aird.state.p;
-        airp.sum_q = aird.sum_q.p, airp.steps_open = aird.i64[0].p, airp.switches = aird.i64[1].p;
-    }
+    if ((rc = in.upload())) return rc;
+    if ((rc = probes.upload(c.trace, n_steps))) return rc;
+    if ((rc = loads.upload(c.applied, n_steps))) return rc;
+    if ((rc = report.upload(n_steps, probes, loads))) return rc;
+    if ((rc = ideal.upload(b, c.ideal_q, n_steps))) return rc;
+    if ((rc = sky.upload(b, s, c.sky, sky.bits || NA > 0 || NS > 0, in))) return rc;
+    if ((rc = shades.upload(c.shades, NA, c.sunlit, n_steps, sky))) return rc;
+    if ((rc = gains.upload(b, c.transmitted, n_steps, shades, in))) return rc;
+    if ((rc = radiation.upload(c.irradiance, n_steps, in))) return rc;
+    if ((rc = ambient.upload(c.ambient, c.ambient_t, n_steps))) return rc;
+    if ((rc = air.upload(b, c.path_q, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
-
-    SeriesInputs in{};
-    in.chan = d_chan.p;
-    for (int a = 0; a < 4; a++) in.gain[a] = d_gain[a].p;
-    in.own_face = d_own.p;
-    in.face = d_face.p;
+    HIP_TRY(report.start(b->stream));
+    HIP_TRY(ideal.start(b->stream));
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    if (r && r->resume == 0) {  // the accumulators start on the device: min = +inf, max = -inf, steps = -1, sums and counts 0
-        const double inf = std::numeric_limits<double>::infinity();
-        const double f64_init[5] = {inf, -inf, 0.0, 0.0, 0.0};
-        for (int a = 0; a < 5; a++) launch_fill_f64(rd.f64[a].p, (int64_t)rd.f64[a].n, f64_init[a], b->stream);
-        for (int a = 0; a < 4; a++)
-            if (rd.i64[a].p) HIP_TRY(hipMemsetAsync(rd.i64[a].p, a < 2 ? 0xff : 0, rd.i64[a].n * sizeof(int64_t), b->stream));
-        for (int a = 0; a < 2; a++) launch_fill_f64(rd.th_f64[a].p, (int64_t)rd.th_f64[a].n, 0.0, b->stream);
-        for (int a = 0; a < 3; a++)
-            if (rd.th_i64[a].p) HIP_TRY(hipMemsetAsync(rd.th_i64[a].p, 0, rd.th_i64[a].n * sizeof(int64_t), b->stream));
-    }
-    if (NI > 0 && il->resume == 0) {  // sums and counts 0, peak_heating = -inf, peak_cooling = +inf, steps = -1
-        const double inf = std::numeric_limits<double>::infinity();
-        const double f64_init[4] = {0.0, 0.0, -inf, inf};
-        for (int a = 0; a < 4; a++) launch_fill_f64(idd.f64[a].p, (int64_t)idd.f64[a].n, f64_init[a], b->stream);
-        for (int a = 0; a < 4; a++)
-            if (idd.i64[a].p) HIP_TRY(hipMemsetAsync(idd.i64[a].p, a < 2 ? 0xff : 0, idd.i64[a].n * sizeof(int64_t), b->stream));
-    }
-    double *const applied_dev = d_applied.p ? d_applied.p : rd.applied_row.p;  // (one row of scratch without the buffer)
-    const size_t applied_stride = d_applied.p ? (size_t)NT : 0;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> air paths -> ambient drive -> driven inputs -> shades -> sky -> solar gains -> room radiation ->
-    // the body of a march call of n_sub -> probes ----
+    // ---- the steps, enqueued without waiting: head -> zone loads -> thermostat statistics -> air paths -> ambient drive ->
+    // driven inputs -> shades -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
-        launch_begin_march(d_w.p + (size_t)k * n_rec, b->d_weather.p, n_sub, (int)n_rec,
-                           d_zab.p + (size_t)std::min(k, zrows - 1) * 2 * Z, b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
-        if (loads)
-            launch_series_zone_loads((int)Z, zl, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
-                                     applied_dev ? applied_dev + (size_t)k * applied_stride : nullptr, b->d_flags.p, b->stream);
-        if (th_stats) launch_series_th_stats((int)NT, td, d_mode.p, applied_dev ? applied_dev + (size_t)k * applied_stride : nullptr, b->stream);
+        const double *channel = row(d_channel, k, NC);
+        const SkyRecord *record = row(sky.record, k, n_sites);
+        // (the powers of the step: a row of the applied buffer, or one row of scratch where the caller takes none)
+        double *applied = loads.applied.p ? row(loads.applied, k, NT) : report.applied_row.p;
+        launch_begin_march(row(d_w, k, (int64_t)n_rec), b->d_weather.p, n_sub, (int)n_rec, row(d_zab, std::min(k, zrows - 1), 2 * Z), b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
+        if (loads.on)
+            launch_series_zone_loads((int)Z, loads.view, channel, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p, applied, b->d_flags.p, b->stream);
+        if (report.th_stats) launch_series_th_stats((int)NT, report.th, loads.mode.p, applied, b->stream);
         if (NP > 0)
-            launch_series_air_paths((int)Z, airp, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p,
-                                    aird.path_q.p ? aird.path_q.p + (size_t)k * NP : nullptr, b->d_flags.p, b->stream);
-        if (NB > 0)
-            launch_series_ambient(abdd, d_channel.p + (size_t)k * NC, b->d_zone_T.p, b->d_side_const.p,
-                                  abd.t.p ? abd.t.p + (size_t)k * NB : nullptr, b->stream);
-        if (driven)
-            launch_series_inputs((int)S, d_channel.p + (size_t)k * NC, in, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror,
-                                 b->stream);
-        if (NS > 0)
-            launch_series_shading(skd.record.p + (size_t)k * n_sites, shdd, shd.sunlit.p ? shd.sunlit.p + (size_t)k * NS : nullptr, b->stream);
-        if (sky_bits)
-            launch_series_sky((int)S, skd.record.p + (size_t)k * n_sites, skyd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
-        if (NA > 0) {
-            launch_series_apertures(skd.record.p + (size_t)k * n_sites, apd, gnd.transmitted.p ? gnd.transmitted.p + (size_t)k * NA : nullptr,
+            launch_series_air_paths((int)Z, air.view, channel, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p, row(air.path_q, k, NP), b->d_flags.p,
                                     b->stream);
-            launch_series_solar_gains((int)S, gnsd, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+        if (NB > 0) launch_series_ambient(ambient.view, channel, b->d_zone_T.p, b->d_side_const.p, row(ambient.t, k, NB), b->stream);
+        if (in.driven)
+            launch_series_inputs((int)S, channel, in.view, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+        if (NS > 0) launch_series_shading(record, shades.view, row(shades.sunlit, k, NS), b->stream);
+        if (sky.bits) launch_series_sky((int)S, record, sky.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+        if (NA > 0) {
+            launch_series_apertures(record, gains.apertures, row(gains.transmitted, k, NA), b->stream);
+            launch_series_solar_gains((int)S, gains.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         }
         if (NR > 0) {
-            launch_series_emission(rrdd, b->d_T.p, b->stream);
-            launch_series_room_radiation((int)S, rrdd, d_channel.p + (size_t)k * NC, b->d_side_dyn.p, b->sl, mirror,
-                                         rrd.irradiance.p ? rrd.irradiance.p + (size_t)k * NR : nullptr, b->stream);
+            launch_series_emission(radiation.view, b->d_T.p, b->stream);
+            launch_series_room_radiation((int)S, radiation.view, channel, b->d_side_dyn.p, b->sl, mirror, row(radiation.irradiance, k, NR),
+                                         b->stream);
         }
         if (NI > 0) {
-            launch_series_ideal_begin(ild, d_channel.p + (size_t)k * NC, b->stream);
-            rc = march_body_ideal(b, n_sub, ild);
+            launch_series_ideal_begin(ideal.view, channel, b->stream);
+            rc = march_body_ideal(b, n_sub, ideal.view);
         } else {
             rc = march_body(b, n_sub);
         }
         if (rc) return rc;
-        if (NI > 0) launch_series_ideal_end(ild, idd.q.p ? idd.q.p + (size_t)k * NI : nullptr, il->step_base + k, b->stream);
+        if (NI > 0) launch_series_ideal_end(ideal.view, row(ideal.q, k, NI), c.il->step_base + k, b->stream);
         // (without a trace: no probe is copied, lane 0 still watches the failure flags)
-        launch_series_probe(d_trace.p ? P : 0, d_pbuf.p, d_pidx.p, b->d_T.p, b->d_side_out.p, b->d_zone_T.p,
-                            d_trace.p ? d_trace.p + (size_t)k * P : nullptr, b->d_flags.p, d_fail.p, k, b->stream);
-        if (q_stats) {  // (a report that asks nothing of its quantities launches nothing here)
-            launch_series_groups(gd, b->d_T.p, b->d_side_out.p, b->d_zone_T.p, b->stream);
-            launch_series_stats(sd, b->d_T.p, b->d_side_out.p, b->d_zone_T.p,
-                                    rd.group_trace.p ? rd.group_trace.p + (size_t)k * G : nullptr, r->step_base + k, b->stream);
+        launch_series_probe(probes.trace.p ? P : 0, probes.buf.p, probes.idx.p, b->d_T.p, b->d_side_out.p, b->d_zone_T.p,
+                            row(probes.trace, k, P), b->d_flags.p, probes.failed.p, k, b->stream);
+        if (report.q_stats) {  // (a report that asks nothing of its quantities launches nothing here)
+            launch_series_groups(report.groups, b->d_T.p, b->d_side_out.p, b->d_zone_T.p, b->stream);
+            launch_series_stats(report.stats, b->d_T.p, b->d_side_out.p, b->d_zone_T.p, row(report.group_trace, k, G), c.r->step_base + k,
+                                b->stream);
         }
     }
     HIP_TRY(hipGetLastError());
-    // ---- one wait: the trace and the record of the first failure travel at the end of the stream's work ----
+    // ---- one wait: the rows, the accumulators and the record of the first failure travel at the end of the stream's work ----
     int first_failed[5] = {-1, 0, 0, 0, 0};
-    if (trace && (int64_t)n_steps * P > 0)
-        HIP_TRY(hipMemcpyAsync(trace, d_trace.p, (size_t)n_steps * P * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (d_applied.p && (int64_t)n_steps * NT > 0)
-        HIP_TRY(hipMemcpyAsync(applied, d_applied.p, (size_t)n_steps * NT * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (loads && l->th_mode && NT > 0)
-        HIP_TRY(hipMemcpyAsync(l->th_mode, d_mode.p, (size_t)NT, hipMemcpyDeviceToHost, b->stream));
-    if (r) {
-        if (rd.group_trace.p && (int64_t)n_steps * G > 0)
-            HIP_TRY(hipMemcpyAsync(r->group_trace, rd.group_trace.p, (size_t)n_steps * G * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        double *const f64[5] = {r->q_min, r->q_max, r->q_sum, r->q_deg_below, r->q_deg_above};
-        int64_t *const i64[4] = {r->q_step_min, r->q_step_max, r->q_n_below, r->q_n_above};
-        double *const tf[2] = {r->th_sum_heating, r->th_sum_cooling};
-        int64_t *const ti[3] = {r->th_steps_heating, r->th_steps_cooling, r->th_switches};
-        for (int a = 0; a < 5; a++)
-            if (rd.f64[a].p && Q > 0) HIP_TRY(hipMemcpyAsync(f64[a], rd.f64[a].p, (size_t)Q * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        for (int a = 0; a < 4; a++)
-            if (rd.i64[a].p && Q > 0) HIP_TRY(hipMemcpyAsync(i64[a], rd.i64[a].p, (size_t)Q * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-        for (int a = 0; a < 2; a++)
-            if (rd.th_f64[a].p) HIP_TRY(hipMemcpyAsync(tf[a], rd.th_f64[a].p, (size_t)NT * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        for (int a = 0; a < 3; a++)
-            if (rd.th_i64[a].p) HIP_TRY(hipMemcpyAsync(ti[a], rd.th_i64[a].p, (size_t)NT * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    }
-    if (NI > 0) {
-        if (idd.q.p) HIP_TRY(hipMemcpyAsync(ideal_q, idd.q.p, (size_t)n_steps * NI * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        double *const f64[4] = {il->sum_heating, il->sum_cooling, il->peak_heating, il->peak_cooling};
-        int64_t *const i64[4] = {il->step_peak_heating, il->step_peak_cooling, il->n_sat_heating, il->n_sat_cooling};
-        for (int a = 0; a < 4; a++)
-            if (idd.f64[a].p) HIP_TRY(hipMemcpyAsync(f64[a], idd.f64[a].p, (size_t)NI * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        for (int a = 0; a < 4; a++)
-            if (idd.i64[a].p) HIP_TRY(hipMemcpyAsync(i64[a], idd.i64[a].p, (size_t)NI * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    }
-    if (NA > 0) {
-        if (gnd.transmitted.p)
-            HIP_TRY(hipMemcpyAsync(transmitted, gnd.transmitted.p, (size_t)n_steps * NA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (gnd.sum.p) HIP_TRY(hipMemcpyAsync(gains->ap_sum, gnd.sum.p, (size_t)NA * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    }
-    if (NP > 0) {
-        if (aird.path_q.p) HIP_TRY(hipMemcpyAsync(path_q, aird.path_q.p, (size_t)n_steps * NP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (air->state) HIP_TRY(hipMemcpyAsync(air->state, aird.state.p, (size_t)NP, hipMemcpyDeviceToHost, b->stream));
-        if (aird.sum_q.p) HIP_TRY(hipMemcpyAsync(air->sum_q, aird.sum_q.p, (size_t)NP * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-        if (aird.i64[0].p) HIP_TRY(hipMemcpyAsync(air->steps_open, aird.i64[0].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-        if (aird.i64[1].p) HIP_TRY(hipMemcpyAsync(air->switches, aird.i64[1].p, (size_t)NP * sizeof(int64_t), hipMemcpyDeviceToHost, b->stream));
-    }
-    if (shd.sunlit.p) HIP_TRY(hipMemcpyAsync(sunlit, shd.sunlit.p, (size_t)n_steps * NS * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (rrd.irradiance.p)
-        HIP_TRY(hipMemcpyAsync(irradiance, rrd.irradiance.p, (size_t)n_steps * NR * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (rrd.sum.p) HIP_TRY(hipMemcpyAsync(radiation->sum_irradiance, rrd.sum.p, (size_t)NR * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (abd.t.p) HIP_TRY(hipMemcpyAsync(ambient_t, abd.t.p, (size_t)n_steps * NB * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    if (abd.sum.p) HIP_TRY(hipMemcpyAsync(ambient->sum_temperature, abd.sum.p, (size_t)NB * sizeof(double), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipMemcpyAsync(first_failed, d_fail.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(probes.fetch(c.trace, b->stream));
+    HIP_TRY(loads.fetch(c.l, c.applied, b->stream));
+    HIP_TRY(report.fetch(b->stream));
+    HIP_TRY(ideal.fetch(c.ideal_q, b->stream));
+    HIP_TRY(gains.fetch(c.transmitted, b->stream));
+    HIP_TRY(air.fetch(c.path_q, b->stream));
+    HIP_TRY(shades.fetch(c.sunlit, b->stream));
+    HIP_TRY(radiation.fetch(c.irradiance, b->stream));
+    HIP_TRY(ambient.fetch(c.ambient_t, b->stream));
+    HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
     // A numerical failure: reported as heat_batch_synchronize reports it, from the flags as they were after the step that
     // set them (the steps enqueued behind it marched on and may have added to them).
-    if (failed_step) *failed_step = first_failed[0];
+    if (c.failed_step) *c.failed_step = first_failed[0];
     HIP_TRY(hipMemcpy(b->d_flags.p, first_failed + 1, 4 * sizeof(int), hipMemcpyHostToDevice));
     HIP_TRY(hipStreamSynchronize(nullptr));
     return heat_batch_synchronize(b);
 }
 
 int heat_batch_march_series(heat_batch *b, const heat_series *s, double *trace, int32_t *failed_step) {
-    return march_series_impl(b, s, nullptr, nullptr, false, trace, nullptr, failed_step);
+    SeriesCall c; c.s = s, c.trace = trace, c.failed_step = failed_step;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_loads(heat_batch *b, const heat_series *s, const heat_zone_loads *l, double *trace, double *applied,
                                   int32_t *failed_step) {
-    return march_series_impl(b, s, l, nullptr, false, trace, applied, failed_step);
+    SeriesCall c; c.s = s, c.l = l, c.trace = trace, c.applied = applied, c.failed_step = failed_step;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_series_report *r, double *trace,
                                    double *applied, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step);
+    SeriesCall c; c.s = s, c.l = l, c.r = r, c.trace = trace, c.applied = applied, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_ideal(heat_batch *b, const heat_series *s, const heat_zone_loads *l, heat_ideal_loads *il,
                                   heat_series_report *r, double *trace, double *applied, double *ideal_q, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q);
+    SeriesCall c; c.s = s, c.l = l, c.il = il, c.r = r, c.trace = trace, c.applied = applied, c.ideal_q = ideal_q;
+    c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_sky(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_zone_loads *l, heat_ideal_loads *il,
                                 heat_series_report *r, double *trace, double *applied, double *ideal_q, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky);
+    SeriesCall c; c.s = s, c.sky = sky, c.l = l, c.il = il, c.r = r, c.trace = trace, c.applied = applied, c.ideal_q = ideal_q;
+    c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_gains(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_solar_gains *gains,
                                   const heat_zone_loads *l, heat_ideal_loads *il, heat_series_report *r, double *trace, double *applied,
                                   double *ideal_q, double *transmitted, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted);
+    SeriesCall c; c.s = s, c.sky = sky, c.gains = gains, c.l = l, c.il = il, c.r = r, c.trace = trace, c.applied = applied;
+    c.ideal_q = ideal_q, c.transmitted = transmitted, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_air(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_solar_gains *gains,
                                 const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il, heat_series_report *r, double *trace,
                                 double *applied, double *ideal_q, double *transmitted, double *path_q, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q);
+    SeriesCall c; c.s = s, c.sky = sky, c.gains = gains, c.l = l, c.air = air, c.il = il, c.r = r, c.trace = trace, c.applied = applied;
+    c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_shaded(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
                                    const heat_solar_gains *gains, const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il,
                                    heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
                                    double *path_q, double *sunlit, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit);
+    SeriesCall c; c.s = s, c.sky = sky, c.shades = shades, c.gains = gains, c.l = l, c.air = air, c.il = il, c.r = r, c.trace = trace;
+    c.applied = applied, c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.sunlit = sunlit;
+    c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_radiation(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
@@ -2876,8 +2870,10 @@ int heat_batch_march_series_radiation(heat_batch *b, const heat_series *s, const
                                       heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
                                       double *path_q, double *sunlit, heat_room_radiation *radiation, double *irradiance,
                                       int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit,
-                             radiation, irradiance);
+    SeriesCall c; c.s = s, c.sky = sky, c.shades = shades, c.gains = gains, c.l = l, c.air = air, c.il = il, c.r = r, c.trace = trace;
+    c.applied = applied, c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.sunlit = sunlit, c.radiation = radiation;
+    c.irradiance = irradiance, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 int heat_batch_march_series_ambient(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
@@ -2885,8 +2881,10 @@ int heat_batch_march_series_ambient(heat_batch *b, const heat_series *s, const h
                                     heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
                                     double *path_q, double *sunlit, heat_room_radiation *radiation, double *irradiance,
                                     heat_ambient_drive *ambient, double *ambient_t, int32_t *failed_step) {
-    return march_series_impl(b, s, l, r, true, trace, applied, failed_step, il, ideal_q, sky, gains, transmitted, air, path_q, shades, sunlit,
-                             radiation, irradiance, ambient, ambient_t);
+    SeriesCall c; c.s = s, c.sky = sky, c.shades = shades, c.gains = gains, c.l = l, c.air = air, c.il = il, c.r = r, c.trace = trace;
+    c.applied = applied, c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.sunlit = sunlit, c.radiation = radiation;
+    c.irradiance = irradiance, c.ambient = ambient, c.ambient_t = ambient_t, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
 }
 
 // The ambient temperature of the listed sides from the next march on: k_series_ambient with the temperatures as its row
@@ -2902,20 +2900,16 @@ int heat_batch_set_ambient(heat_batch *b, int64_t n, const int64_t *surface, con
     int rc = check_ambient_sides(b->n_surf, side_kind, n, surface, side, "entry", heat::last_error());
     if (rc) return rc;
     if (n == 0) return HEAT_OK;
-    AmbientTables abt;
-    build_ambient_tables(b->n_surf, b->h_dev_of.data(), side_kind, n, surface, side, abt);
+    AmbientTerm abd;
+    build_ambient_tables(b->n_surf, b->h_dev_of.data(), side_kind, n, surface, side, abd.abt);
     rc = select_device(b);
     if (rc) return rc;
-    AmbientDev abd;
     SeriesDrain drain{b};
-    if ((rc = series_upload(abd.rec, abt.rec.data(), abt.rec.size(), "ambient tables"))) return rc;
-    if ((rc = series_upload(abd.peer, abt.peer.data(), abt.peer.size(), "ambient tables"))) return rc;
+    if ((rc = abd.upload_tables())) return rc;
     if ((rc = series_upload(abd.t, temperature, (size_t)n, "ambient temperatures"))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
-    SeriesAmbient abdd{};
-    abdd.n_sides = (int)n;
-    abdd.rec = abd.rec.p, abdd.peer = abd.peer.p;
-    launch_series_ambient(abdd, abd.t.p, b->d_zone_T.p, b->d_side_const.p, nullptr, b->stream);
+    abd.view.n_sides = (int)n;
+    launch_series_ambient(abd.view, abd.t.p, b->d_zone_T.p, b->d_side_const.p, nullptr, b->stream);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(b->stream));
     return HEAT_OK;
