@@ -158,6 +158,14 @@ class AmbientDrive(C.Structure):
                 ("offset", _dp), ("mix_zone", _i32p), ("mix", _dp), ("sum_temperature", _dp)]
 
 
+class Blinds(C.Structure):
+    """heat_blinds (include/heat_amd.h): movable solar protection that rides on shades, controlled or scheduled"""
+    _fields_ = [("n_blinds", C.c_int64), ("shade", _i32p), ("beam_closed", _dp), ("diffuse_closed", _dp), ("ground_closed", _dp),
+                ("pos_chan", _i32p), ("irr_close", _dp), ("irr_open", _dp), ("zone", _i32p), ("set_chan", _i32p), ("band", _dp),
+                ("enable_chan", _i32p), ("state", C.POINTER(C.c_uint8)), ("steps_closed", _i64p), ("switches", _i64p),
+                ("sum_position", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -225,6 +233,12 @@ SYMBOLS = [
                                                   C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads),
                                                   C.POINTER(Report), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(RoomRadiation), _dp,
                                                   C.POINTER(AmbientDrive), _dp, _i32p]),
+    ("heat_blinds_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains),
+                                    C.POINTER(Shades), C.POINTER(Blinds)]),
+    ("heat_batch_march_series_blinds", C.c_int, [_H, C.POINTER(Series), C.POINTER(Sky), C.POINTER(Shades), C.POINTER(SolarGains),
+                                                 C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads),
+                                                 C.POINTER(Report), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(RoomRadiation), _dp,
+                                                 C.POINTER(AmbientDrive), _dp, C.POINTER(Blinds), _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -376,6 +390,7 @@ def make_desc(md):
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
+                     "heat_blinds_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1148,6 +1163,81 @@ def ambient_check(md, ambient, n_sites=1, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+BLIND_STATS = ("steps_closed", "switches", "sum_position")
+_BLIND_ARRAYS = (("shade", np.int32, True), ("beam_closed", np.float64, True), ("diffuse_closed", np.float64, True),
+                 ("ground_closed", np.float64, True), ("pos_chan", np.int32, False), ("irr_close", np.float64, False),
+                 ("irr_open", np.float64, False), ("zone", np.int32, False), ("set_chan", np.int32, False), ("band", np.float64, False),
+                 ("enable_chan", np.int32, False))
+_BLIND_INOUT = (("state", np.uint8), ("steps_closed", np.int64), ("switches", np.int64), ("sum_position", np.float64))
+
+
+def make_blinds(shade=(), beam_closed=(), diffuse_closed=(), ground_closed=(), pos_chan=None, irr_close=None, irr_open=None, zone=None,
+                set_chan=None, band=None, enable_chan=None, state=None, steps_closed=None, switches=None, sum_position=None,
+                stats=BLIND_STATS):
+    """Builds a heat_blinds. Returns (blinds, keepalive); the march updates keepalive["state"] and the accumulators in place.
+    shade            [n_blinds] the shade of the call's shades the blind rides on (at most one blind per shade)
+    beam_closed, diffuse_closed, ground_closed   [n_blinds] the factors of the fully closed blind, >= 0
+    pos_chan         [n_blinds] the position channel of a SCHEDULED blind, -1: controlled; None: all controlled
+    irr_close, irr_open   [n_blinds] W/m2 on the shade's plane, irr_open <= irr_close: read only where controlled
+    zone             [n_blinds] the zone whose temperature gates the blind, -1: none; None: no room condition anywhere
+    set_chan, band   [n_blinds] the zone's setpoint channel (C) and the band (K): read only where zone >= 0
+    enable_chan      [n_blinds] enabled where row[chan] > 0, -1: always; None: always enabled
+    state, steps_closed, switches, sum_position   [n_blinds] what a previous series returned (copied); None: zeros
+    stats            which of steps_closed, switches, sum_position the march maintains (the others stay NULL)
+    (blinds.apply is the rule in numpy and takes the same dict)"""
+    given = dict(shade=shade, beam_closed=beam_closed, diffuse_closed=diffuse_closed, ground_closed=ground_closed, pos_chan=pos_chan,
+                 irr_close=irr_close, irr_open=irr_open, zone=zone, set_chan=set_chan, band=band, enable_chan=enable_chan)
+    unknown = set(stats) - set(BLIND_STATS)
+    if unknown:
+        raise ValueError("blinds: unknown stats %s (known: %s)" % (sorted(unknown), ", ".join(BLIND_STATS)))
+    bl = Blinds()
+    n = len(np.asarray(shade).reshape(-1))
+    bl.n_blinds = n
+    keep = {}
+    for name, dtype, needed in _BLIND_ARRAYS:
+        if given[name] is None and not needed:
+            continue
+        v = np.ascontiguousarray(given[name], dtype=dtype).reshape(-1)
+        if v.shape != (n,):
+            raise ValueError("blinds %s: %s for %d blinds" % (name, v.shape, n))
+        keep[name] = v
+        setattr(bl, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    for (name, dtype), v in zip(_BLIND_INOUT, (state, steps_closed, switches, sum_position)):
+        if name != "state" and name not in stats:
+            if v is not None:
+                raise ValueError("blinds %s given, but not among stats %s" % (name, tuple(stats)))
+            continue
+        v = np.zeros(n, dtype) if v is None else np.array(v, dtype=dtype).reshape(-1)  # (a copy: the march writes it)
+        if v.shape != (n,):
+            raise ValueError("blinds %s: %s for %d blinds" % (name, v.shape, n))
+        keep[name] = v
+        setattr(bl, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    return bl, keep
+
+
+def blinds_check(md, blinds, shades=None, sky=None, gains=None, n_sites=1, lib=None, **series):
+    """heat_blinds_check: everything about the blinds of a series that needs no device (series arguments as
+    HeatBatch.march_series; sky, gains, shades as shades_check takes them; blinds: the arguments of make_blinds, or None).
+    Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    k = None
+    if sky is not None or gains is not None:
+        k, kkeep = make_sky(**_sky_for_gains(sky, _model_normals(md), int(md["n_surfaces"])))
+        _sky_fits(kkeep, s.n_steps, int(n_sites), int(md["n_surfaces"]))
+    g, gkeep = make_solar_gains(**gains) if gains is not None else (None, None)
+    h, hkeep = make_shades(**shades) if shades is not None else (None, None)
+    if h is not None:
+        _shades_fit(hkeep, int(md["n_surfaces"]), g.n_apertures if g is not None else None)
+    bl, bkeep = make_blinds(**blinds) if blinds is not None else (None, None)
+    ref = lambda x: C.byref(x) if x is not None else None
+    rc = L.heat_blinds_check(C.byref(desc), int(n_sites), C.byref(s), ref(k), ref(g), ref(h), ref(bl))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1268,7 +1358,7 @@ class HeatBatch:
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
-                     **series):
+                     blinds=None, position=True, blind_incident=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1310,18 +1400,25 @@ class HeatBatch:
         the temperature of Ambient sides from a channel, a gain and an offset, and optionally mixed with a zone temperature
         the device holds, formed on the device at every step. Returns what the same call without ambient returns plus
         ambient_t [n_steps, n_sides] (empty with ambient_t=False) and sum_temperature [n_sides] (pass it as
-        ambient["sum_temperature"] to the next series): two more elements of the tuple, or two more keys of the dict."""
+        ambient["sum_temperature"] to the next series): two more elements of the tuple, or two more keys of the dict.
+        blinds (a dict of make_blinds' arguments; an empty dict: no blind; shades carries the shades they ride on):
+        heat_batch_march_series_blinds — movable solar protection, closed by the irradiance on the shade's plane and a zone
+        temperature the device holds, or following a position channel, formed on the device at every step. Returns what the
+        same call without blinds returns plus one dict: position and incident [n_steps, n_blinds] (empty with position=False /
+        blind_incident=False), state, and of steps_closed, switches, sum_position those in stats (pass state and them on to the
+        next series) — one more element of the tuple, or the key "blinds" of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
-                     ambient=ambient)
+                     ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
         # (One condition for every entry point: without shades it is "gains is not None", and with gains it holds whatever
         # the shades and the sky are — the spellings this had per entry point all reduce to it.)
         if gains is not None or (shades is not None and (sky is None or sky.get("mode") is None)):
             given["sky"] = _sky_for_gains(sky, self._normals, self.n_surfaces)
         return self._march_series(weather, n_sub, series, given, dict(trace=trace, applied=applied, path_q=path_q, sunlit=sunlit,
-                                                                      irradiance=irradiance, ambient_t=ambient_t))
+                                                                      irradiance=irradiance, ambient_t=ambient_t, position=position,
+                                                                      blind_incident=blind_incident))
 
-    # The ten entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
+    # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
     _SERIES_ENTRY = (("heat_batch_march_series", ()),
                      ("heat_batch_march_series_loads", ("loads",)),
@@ -1333,14 +1430,17 @@ class HeatBatch:
                      ("heat_batch_march_series_shaded", ("loads", "report", "ideal", "sky", "gains", "air", "shades")),
                      ("heat_batch_march_series_radiation", ("loads", "report", "ideal", "sky", "gains", "air", "shades", "radiation")),
                      ("heat_batch_march_series_ambient", ("loads", "report", "ideal", "sky", "gains", "air", "shades", "radiation",
-                                                          "ambient")))
+                                                          "ambient")),
+                     ("heat_batch_march_series_blinds", ("loads", "report", "ideal", "sky", "gains", "air", "shades", "radiation",
+                                                         "ambient", "blinds")))
     _SERIES_ORDER = ("sky", "shades", "gains", "loads", "air", "ideal", "report", "trace", "applied", "ideal_q", "transmitted", "path_q",
-                     "sunlit", "radiation", "irradiance", "ambient", "ambient_t")
-    # term -> (its make_* function, the array of rows it returns, the count of that array's columns)
+                     "sunlit", "radiation", "irradiance", "ambient", "ambient_t", "blinds", "position", "blind_incident")
+    # term -> (its make_* function, the array of rows it returns, the count of that array's columns); the blinds return a
+    # second array of rows of the same width, blind_incident
     _SERIES_TERMS = dict(loads=(make_zone_loads, "applied", "n_thermostats"), ideal=(make_ideal_loads, "ideal_q", "n_loads"),
                          gains=(make_solar_gains, "transmitted", "n_apertures"), air=(make_air_paths, "path_q", "n_paths"),
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
-                         ambient=(make_ambient, "ambient_t", "n_sides"))
+                         ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
     def _march_series(self, weather, n_sub, series, given, want):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
@@ -1380,10 +1480,14 @@ class HeatBatch:
             _shades_fit(kept["shades"], self.n_surfaces, made["gains"].n_apertures if "gains" in made else None)
         build("radiation")
         build("ambient")
+        build("blinds")
+        if "position" in rows:
+            rows["blind_incident"] = np.zeros((s.n_steps if want["blind_incident"] else 0, made["blinds"].n_blinds))
         symbol, carried = next(e for e in self._SERIES_ENTRY if all(v is None or k in e[1] for k, v in given.items()))
         # The symbol's arguments: of _SERIES_ORDER the names of the terms it carries (a struct, NULL where the term was not
         # passed), the arrays of rows of those terms and the trace, which every symbol has (an array, NULL where it is empty).
         term_of = {key: term for term, (_, key, _) in self._SERIES_TERMS.items()}       # the term an array of rows belongs to
+        term_of["blind_incident"] = "blinds"
         args = []
         for name in self._SERIES_ORDER:
             is_struct = name in given
@@ -1415,6 +1519,9 @@ class HeatBatch:
             out += [("irradiance", rows["irradiance"]), ("sum_irradiance", kept["radiation"]["sum_irradiance"])]
         if given["ambient"] is not None:
             out += [("ambient_t", rows["ambient_t"]), ("sum_temperature", kept["ambient"]["sum_temperature"])]
+        if given["blinds"] is not None:
+            out += [("blinds", dict(position=rows["position"], incident=rows["blind_incident"],
+                                    **{k: kept["blinds"][k] for k in ("state",) + BLIND_STATS if k in kept["blinds"]}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

@@ -1440,10 +1440,15 @@ struct ShadesTerm {
     ShadeTables sht;
     std::vector<int32_t> h_i32, h_side;
     DevBuf<double> tab, tan2, f, sunlit;  // [kShadeRows][NS], [NH][16], [NS], [n_steps][NS]
+    DevBuf<double> eff;                   // [3][NS] the effective factors k_series_blinds writes; absent without blinds
     DevBuf<int32_t> i32, side, aperture;  // site [NS] | horizon [NS], [2][S], [NA]
     SeriesShades view{};
-    // what a shaded consumer reads: the step's fractions, the diffuse and the ground factors (all NULL without shades)
-    ShadeFactors factors() const { return ShadeFactors{f.p, tab.p + (size_t)SH_FD * NS, tab.p + (size_t)SH_FG * NS}; }
+    // what a shaded consumer reads: the step's fractions, the diffuse and the ground factors (all NULL without shades) — with
+    // blinds (heat_blinds) the effective ones of the step
+    ShadeFactors factors() const {
+        if (eff.p) return ShadeFactors{eff.p, eff.p + (size_t)NS, eff.p + 2 * (size_t)NS};
+        return ShadeFactors{f.p, tab.p + (size_t)SH_FD * NS, tab.p + (size_t)SH_FG * NS};
+    }
     void prepare(heat_batch *b, const heat_shades *shades, unsigned sky_bits) {
         NS = shades ? shades->n_shades : 0;  // (a side or aperture needs a shade to refer to: none is shaded without)
         if (NS == 0) return;
@@ -1458,8 +1463,9 @@ struct ShadesTerm {
         if (shades->front_shade) to_device_order(b, shades->front_shade, h_side.data());
         if (shades->back_shade) to_device_order(b, shades->back_shade, h_side.data() + b->n_surf);
     }
-    int upload(const heat_shades *shades, int64_t NA, const double *host_sunlit, int n_steps, SkyTerm &sky) {
+    int upload(const heat_shades *shades, int64_t NA, const double *host_sunlit, int n_steps, bool blinds, SkyTerm &sky) {
         if (NS == 0) return HEAT_OK;
+        if (blinds) SERIES_TRY(series_alloc(eff, 3 * (size_t)NS, "effective shade factors"));
         SERIES_TRY(series_upload(tab, sht.f64, "shade table"));
         SERIES_TRY(series_upload(i32, h_i32, "shade table"));
         SERIES_TRY(series_upload(tan2, shades->horizon_tan2, 16 * (size_t)shades->n_horizons, "horizon profiles"));
@@ -1472,6 +1478,58 @@ struct ShadesTerm {
         return HEAT_OK;
     }
     hipError_t fetch(double *host_sunlit, hipStream_t st) { return series_fetch(host_sunlit, sunlit, st); }
+};
+
+// The blinds (heat_blinds): the blind of every shade and the blinds as structures of arrays (plan.hpp, BlindTables), the state
+// bytes, the accumulators (uploaded where the caller passes them), the position and blind_incident rows in the caller's order.
+// It reads the shades' site numbers, table and fractions and writes the shades' effective factors: uploaded behind them.
+struct BlindsTerm {
+    heat_blinds *blinds = nullptr;
+    int64_t NL = 0;
+    BlindTables blt;
+    std::vector<uint8_t> h_state;
+    DevBuf<int32_t> of_shade, i32;       // [NS], [kBlindI32Rows][NL]
+    DevBuf<double> f64, position, incident;  // [kBlindF64Rows][NL], [n_steps][NL], [n_steps][NL]
+    DevBuf<uint8_t> state;               // [NL]
+    Acc<double> sum_position;
+    Acc<int64_t> steps_closed, switches;
+    SeriesBlinds view{};
+    void prepare(heat_blinds *blinds_, int64_t NS) {
+        blinds = blinds_;
+        NL = blinds ? blinds->n_blinds : 0;
+        if (NL == 0) return;
+        build_blind_tables(NS, blinds, blt);
+        h_state.assign((size_t)NL, 0);
+        if (blinds->state) std::copy(blinds->state, blinds->state + NL, h_state.begin());
+        sum_position.bind(blinds->sum_position, 0.0, &view.sum_position), steps_closed.bind(blinds->steps_closed, 0, &view.steps_closed);
+        switches.bind(blinds->switches, 0, &view.switches);
+    }
+    int upload(const ShadesTerm &shades, const double *host_position, const double *host_incident, int n_steps) {
+        if (NL == 0) return HEAT_OK;
+        SERIES_TRY(series_upload(of_shade, blt.blind_of_shade, "blind tables"));
+        SERIES_TRY(series_upload(i32, blt.i32, "blind tables"));
+        SERIES_TRY(series_upload(f64, blt.f64, "blind tables"));
+        SERIES_TRY(series_upload(state, h_state, "blind states"));
+        SERIES_TRY(sum_position.stage((size_t)NL, true, "blind accumulators"));
+        SERIES_TRY(steps_closed.stage((size_t)NL, true, "blind accumulators"));
+        SERIES_TRY(switches.stage((size_t)NL, true, "blind accumulators"));
+        if (host_position) SERIES_TRY(series_alloc(position, (size_t)n_steps * NL, "blind positions"));
+        if (host_incident) SERIES_TRY(series_alloc(incident, (size_t)n_steps * NL, "blind irradiances"));
+        view.n_shades = (int)shades.NS, view.n_blinds = (int)NL, view.blind_of_shade = of_shade.p;
+        view.site = shades.view.site, view.tab = shades.tab.p, view.f = shades.f.p;
+        view.pos_chan = i32.p + BL_POS_CHAN * NL, view.zone = i32.p + BL_ZONE * NL, view.set_chan = i32.p + BL_SET_CHAN * NL;
+        view.enable_chan = i32.p + BL_ENABLE_CHAN * NL;
+        view.beam_closed = f64.p + BL_BEAM * NL, view.diffuse_closed = f64.p + BL_DIFFUSE * NL, view.ground_closed = f64.p + BL_GROUND * NL;
+        view.irr_close = f64.p + BL_IRR_CLOSE * NL, view.irr_open = f64.p + BL_IRR_OPEN * NL, view.half_band = f64.p + BL_HALF_BAND * NL;
+        view.state = state.p;
+        view.eff_f = shades.eff.p, view.eff_diffuse = shades.eff.p + shades.NS, view.eff_ground = shades.eff.p + 2 * shades.NS;
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_position, double *host_incident, hipStream_t st) {
+        if (NL == 0) return hipSuccess;
+        const hipError_t e = series_fetch(blinds->state, state, st, series_fetch(host_incident, incident, st, series_fetch(host_position, position, st)));
+        return switches.fetch(st, steps_closed.fetch(st, sum_position.fetch(st, e)));
+    }
 };
 
 // The solar gains (heat_solar_gains): the apertures as structure of arrays, the entries as sliced ELL over the receivers in
@@ -1672,7 +1730,7 @@ struct AirTerm {
     }
 };
 
-// What the widest entry point (heat_batch_march_series_ambient) takes; filled by field name. no_trace_ok: a NULL trace records none.
+// What the widest entry point (heat_batch_march_series_blinds) takes; filled by field name. no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
@@ -1687,6 +1745,8 @@ struct SeriesCall {
     double *irradiance = nullptr;
     heat_ambient_drive *ambient = nullptr;
     double *ambient_t = nullptr;
+    heat_blinds *blinds = nullptr;
+    double *position = nullptr, *blind_incident = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -2680,6 +2740,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     // (behind the shard's refusal: the gains number the surfaces of the caller's model, a shard holds some of them)
     if ((rc = check_solar_gains(b->n_surf, s, c.sky, c.gains, heat::last_error()))) return rc;
     if ((rc = check_shades(b->n_surf, s, c.sky, c.gains, c.shades, heat::last_error()))) return rc;
+    if ((rc = check_blinds(b->n_zones, s, c.shades, c.blinds, heat::last_error()))) return rc;
     if ((rc = check_air_paths(b->n_zones, s->n_channels, c.air, heat::last_error()))) return rc;
     if ((rc = check_room_radiation(b->n_surf, s, c.sky, c.radiation, heat::last_error()))) return rc;
     if ((rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, c.ambient, heat::last_error()))) return rc;
@@ -2708,11 +2769,12 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     DevBuf<StepWeather> d_w;
     DevBuf<double> d_zab, d_channel;
     InputsTerm in; ProbesTerm probes; LoadsTerm loads; ReportTerm report; IdealTerm ideal;
-    ShadesTerm shades; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air;
+    ShadesTerm shades; BlindsTerm blinds; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
     shades.prepare(b, c.shades, sky.bits);
+    blinds.prepare(c.blinds, shades.NS);
     radiation.prepare(b, c.radiation, in);
     ambient.prepare(b, side_kind, c.ambient);
     if ((rc = probes.prepare(b, s))) return rc;
@@ -2721,6 +2783,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     ideal.prepare(c.il, load_of_zone);
     air.prepare(b, c.air);
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
+    const int64_t NL = blinds.NL;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -2731,7 +2794,8 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = report.upload(n_steps, probes, loads))) return rc;
     if ((rc = ideal.upload(b, c.ideal_q, n_steps))) return rc;
     if ((rc = sky.upload(b, s, c.sky, sky.bits || NA > 0 || NS > 0, in))) return rc;
-    if ((rc = shades.upload(c.shades, NA, c.sunlit, n_steps, sky))) return rc;
+    if ((rc = shades.upload(c.shades, NA, c.sunlit, n_steps, NL > 0, sky))) return rc;
+    if ((rc = blinds.upload(shades, c.position, c.blind_incident, n_steps))) return rc;
     if ((rc = gains.upload(b, c.transmitted, n_steps, shades, in))) return rc;
     if ((rc = radiation.upload(c.irradiance, n_steps, in))) return rc;
     if ((rc = ambient.upload(c.ambient, c.ambient_t, n_steps))) return rc;
@@ -2741,7 +2805,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(ideal.start(b->stream));
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
     // ---- the steps, enqueued without waiting: head -> zone loads -> thermostat statistics -> air paths -> ambient drive ->
-    // driven inputs -> shades -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
+    // driven inputs -> shades -> blinds -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
         const double *channel = row(d_channel, k, NC);
         const SkyRecord *record = row(sky.record, k, n_sites);
@@ -2758,6 +2822,8 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
         if (in.driven)
             launch_series_inputs((int)S, channel, in.view, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         if (NS > 0) launch_series_shading(record, shades.view, row(shades.sunlit, k, NS), b->stream);
+        if (NL > 0)
+            launch_series_blinds(record, blinds.view, channel, b->d_zone_T.p, row(blinds.position, k, NL), row(blinds.incident, k, NL), b->stream);
         if (sky.bits) launch_series_sky((int)S, record, sky.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         if (NA > 0) {
             launch_series_apertures(record, gains.apertures, row(gains.transmitted, k, NA), b->stream);
@@ -2795,6 +2861,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(gains.fetch(c.transmitted, b->stream));
     HIP_TRY(air.fetch(c.path_q, b->stream));
     HIP_TRY(shades.fetch(c.sunlit, b->stream));
+    HIP_TRY(blinds.fetch(c.position, c.blind_incident, b->stream));
     HIP_TRY(radiation.fetch(c.irradiance, b->stream));
     HIP_TRY(ambient.fetch(c.ambient_t, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
@@ -2884,6 +2951,19 @@ int heat_batch_march_series_ambient(heat_batch *b, const heat_series *s, const h
     SeriesCall c; c.s = s, c.sky = sky, c.shades = shades, c.gains = gains, c.l = l, c.air = air, c.il = il, c.r = r, c.trace = trace;
     c.applied = applied, c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.sunlit = sunlit, c.radiation = radiation;
     c.irradiance = irradiance, c.ambient = ambient, c.ambient_t = ambient_t, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
+}
+
+int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const heat_sky *sky, const heat_shades *shades,
+                                   const heat_solar_gains *gains, const heat_zone_loads *l, heat_air_paths *air, heat_ideal_loads *il,
+                                   heat_series_report *r, double *trace, double *applied, double *ideal_q, double *transmitted,
+                                   double *path_q, double *sunlit, heat_room_radiation *radiation, double *irradiance,
+                                   heat_ambient_drive *ambient, double *ambient_t, heat_blinds *blinds, double *position,
+                                   double *blind_incident, int32_t *failed_step) {
+    SeriesCall c; c.s = s, c.sky = sky, c.shades = shades, c.gains = gains, c.l = l, c.air = air, c.il = il, c.r = r, c.trace = trace;
+    c.applied = applied, c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.sunlit = sunlit, c.radiation = radiation;
+    c.irradiance = irradiance, c.ambient = ambient, c.ambient_t = ambient_t, c.blinds = blinds, c.position = position;
+    c.blind_incident = blind_incident, c.failed_step = failed_step, c.no_trace_ok = true;
     return march_series_impl(b, c);
 }
 

@@ -2385,6 +2385,84 @@ k_series_shading(const SkyRecord *__restrict__ records, SeriesShades sh, double 
     if (sunlit_row != nullptr) sunlit_row[j] = f;
 }
 
+// k_series_blinds — the effective factors of every shade in one step (heat_blinds, include/heat_amd.h), behind
+// k_series_shading and before k_series_sky: one lane per SHADE. Neighbouring lanes read neighbouring elements of
+// blind_of_shade, of f and of five rows of the shade table (the normal and the two constant factors), and store neighbouring
+// elements of the three effective arrays k_series_sky / k_series_apertures gather from. A lane whose shade carries no blind
+// stores plain copies. The others gather their blind's rows of the blind table (structure of arrays in the caller's blind
+// order: where the shades are not in that order the gather is scattered, over a table of 64 bytes a blind), form the
+// irradiance on the shade's plane from the record of the shade's site and apply the header's rule, every line one rounded
+// operation in the order written, hence no contraction; min and max are shade_max / shade_min. A blind rides on one shade:
+// its state byte, accumulators and output elements have one writer. Nothing on the step's head writes the zone temperatures:
+// every zone is read as it was at the start of the step. No atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_blinds(const SkyRecord *__restrict__ records, SeriesBlinds bl, const double *__restrict__ row, const double *__restrict__ zone_T,
+                double *__restrict__ position_row, double *__restrict__ incident_row) {
+#pragma clang fp contract(off)
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t n = bl.n_shades;
+    if (j >= bl.n_shades) return;
+    const double f = bl.f[j], fd = bl.tab[SH_FD * n + j], fg = bl.tab[SH_FG * n + j];
+    const int i = bl.blind_of_shade[j];
+    if (i < 0) {  // no blind: the consumers read what they read without blinds
+        bl.eff_f[j] = f;
+        bl.eff_diffuse[j] = fd;
+        bl.eff_ground[j] = fg;
+        return;
+    }
+    const SkyRecord &r = records[bl.site[j]];
+    const double nx = bl.tab[SH_NX * n + j], ny = bl.tab[SH_NY * n + j], nz = bl.tab[SH_NZ * n + j];
+    const double c = (nx * r.sun_x + ny * r.sun_y) + nz * r.sun_z;
+    const double fs = 0.5 + 0.5 * nz, fgv = 0.5 - 0.5 * nz;
+    double bm = c > 0.0 ? r.beam * c : 0.0;
+    bm = bm * f;
+    const double dv = (r.diffuse * fs) * fd;
+    const double gv = (r.ground * fgv) * fg;
+    const double I = (bm + dv) + gv;
+    const int pc = bl.pos_chan[i];
+    double p;
+    bool switched = false;
+    if (pc >= 0) {  // scheduled
+        p = row[pc];
+        p = shade_max(p, 0.0);
+        p = shade_min(p, 1.0);
+    } else {        // controlled
+        const int ec = bl.enable_chan[i], z = bl.zone[i];
+        const bool enabled = ec < 0 || row[ec] > 0.0;
+        bool hot = true, cool = false;
+        if (z >= 0) {
+            const double set = row[bl.set_chan[i]], d = bl.half_band[i], T = zone_T[z];
+            const double hi = set + d;
+            const double lo = set - d;
+            hot = T > hi;
+            cool = T < lo;
+        }
+        const int before = bl.state[i];
+        int state = before;
+        if (!enabled) state = 0;
+        else if (I > bl.irr_close[i] && hot) state = 1;
+        else if (state == 1 && (I < bl.irr_open[i] || cool)) state = 0;
+        switched = state != before;
+        if (switched) bl.state[i] = (uint8_t)state;
+        p = (double)state;
+    }
+    const double q = 1.0 - p;
+    const double pb = p * bl.beam_closed[i];
+    const double kb = q + pb;
+    const double pd = p * bl.diffuse_closed[i];
+    const double kd = q + pd;
+    const double pg = p * bl.ground_closed[i];
+    const double kg = q + pg;
+    bl.eff_f[j] = f * kb;
+    bl.eff_diffuse[j] = fd * kd;
+    bl.eff_ground[j] = fg * kg;
+    if (position_row != nullptr) position_row[i] = p;
+    if (incident_row != nullptr) incident_row[i] = I;
+    if (bl.sum_position != nullptr) bl.sum_position[i] = bl.sum_position[i] + p;
+    if (bl.steps_closed != nullptr && p > 0.0) bl.steps_closed[i] = bl.steps_closed[i] + 1;
+    if (bl.switches != nullptr && switched) bl.switches[i] = bl.switches[i] + 1;
+}
+
 // k_series_sky — the sky-driven inputs of one step (heat_sky, include/heat_amd.h), behind k_series_inputs and before the
 // body: one lane per device surface. A lane whose mode byte is 0 leaves after reading it; the others read their site's
 // 64-byte record of the step (the planner keeps the surfaces of a site together: a wavefront mostly reads one line) and
@@ -3158,6 +3236,13 @@ void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sk
 void launch_series_shading(const SkyRecord *records, const SeriesShades &sh, double *sunlit_row, hipStream_t st) {
     if (sh.n <= 0) return;
     hipLaunchKernelGGL(k_series_shading, dim3((sh.n + 255) / 256), dim3(256), 0, st, records, sh, sunlit_row);
+}
+
+void launch_series_blinds(const SkyRecord *records, const SeriesBlinds &bl, const double *row, const double *zone_T,
+                          double *position_row, double *incident_row, hipStream_t st) {
+    if (bl.n_blinds <= 0 || bl.n_shades <= 0) return;
+    hipLaunchKernelGGL(k_series_blinds, dim3((bl.n_shades + 255) / 256), dim3(256), 0, st, records, bl, row, zone_T, position_row,
+                       incident_row);
 }
 
 void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st) {

@@ -110,6 +110,29 @@ struct SeriesShades {
 };
 // records: the step's row of the record table, [n_sites]; sunlit_row: the step's row of sunlit, [n], or nullptr
 void launch_series_shading(const SkyRecord *records, const SeriesShades &sh, double *sunlit_row, hipStream_t st);
+// Blinds of a series step (heat_blinds, include/heat_amd.h; tables: plan.hpp, BlindTables): one launch behind
+// launch_series_shading and before launch_series_sky, only when there are blinds — one lane per SHADE. A lane reads its
+// shade's normal and constant factors from the shade table's rows and the f launch_series_shading has just stored, and writes
+// the three EFFECTIVE factors the shaded consumers gather (ShadeFactors) in place of (f, the table's rows): plain copies where
+// the shade carries no blind. The blind table is a structure of arrays in the caller's blind order; a blind has one shade, so
+// its state byte, accumulators and output elements have one writer.
+struct SeriesBlinds {
+    int n_shades, n_blinds;
+    const int32_t *blind_of_shade;  // [n_shades] -1: the shade carries no blind
+    const int32_t *site;            // [n_shades] (SeriesShades::site)
+    const double *tab;              // [kShadeRows][n_shades] (SeriesShades::tab)
+    const double *f;                // [n_shades] (SeriesShades::f)
+    const int32_t *pos_chan, *zone, *set_chan, *enable_chan;  // [n_blinds] each, -1: none
+    const double *beam_closed, *diffuse_closed, *ground_closed, *irr_close, *irr_open, *half_band;  // [n_blinds] each
+    uint8_t *state;                 // [n_blinds]
+    double *sum_position;           // [n_blinds] each; nullptr: not maintained
+    int64_t *steps_closed, *switches;
+    double *eff_f, *eff_diffuse, *eff_ground;  // [n_shades] each, out: what ShadeFactors hands the consumers
+};
+// records: the step's row of the record table, [n_sites]; row: the step's row of the channel table; position_row /
+// incident_row: the step's rows of position / blind_incident, [n_blinds] (caller's order), or nullptr
+void launch_series_blinds(const SkyRecord *records, const SeriesBlinds &bl, const double *row, const double *zone_T,
+                          double *position_row, double *incident_row, hipStream_t st);
 // records: the step's row of the record table, [n_sites]
 void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
                        const SlotArrays &sl, double *mirror, hipStream_t st);

@@ -2181,6 +2181,109 @@ void build_shade_tables(const heat_shades *sh, ShadeTables &t) {
     if (sh->sh_horizon) std::copy(sh->sh_horizon, sh->sh_horizon + NS, t.horizon.begin());
 }
 
+// ---- blinds of a series (include/heat_amd.h, heat_blinds) ----
+int check_blinds(int64_t n_zones, const heat_series *s, const heat_shades *sh, const heat_blinds *bl, std::string &err) {
+    if (!bl) return HEAT_OK;
+    const int64_t N = bl->n_blinds, NS = sh ? sh->n_shades : 0;
+    if (N < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of blinds (n_blinds %lld): no blind i", (long long)N);
+    if (N == 0) return HEAT_OK;
+    if (NS <= 0)
+        return failp(err, HEAT_E_INVALID_ARG, "blind 0: a blind rides on a shade, but there are no shades (%s, n_blinds %lld)",
+                     sh ? "n_shades is 0" : "shades is NULL", (long long)N);
+    if (!bl->shade) return failp(err, HEAT_E_INVALID_ARG, "blind 0: shade is NULL (n_blinds %lld)", (long long)N);
+    const double *const closed[3] = {bl->beam_closed, bl->diffuse_closed, bl->ground_closed};
+    static const char *const closed_name[3] = {"beam_closed", "diffuse_closed", "ground_closed"};
+    for (int a = 0; a < 3; a++)
+        if (!closed[a]) return failp(err, HEAT_E_INVALID_ARG, "blind 0: %s is NULL (n_blinds %lld)", closed_name[a], (long long)N);
+    const int32_t NC = s->n_channels;
+    std::vector<uint8_t> taken((size_t)NS, 0);
+    for (int64_t i = 0; i < N; i++) {
+        const int32_t j = bl->shade[i], pc = bl->pos_chan ? bl->pos_chan[i] : -1, z = bl->zone ? bl->zone[i] : -1;
+        const int32_t ec = bl->enable_chan ? bl->enable_chan[i] : -1;
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(closed[a][i]) || closed[a][i] < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "blind %lld: %s = %g is negative or not finite", (long long)i, closed_name[a], closed[a][i]);
+        if (bl->state && bl->state[i] > 1)
+            return failp(err, HEAT_E_INVALID_ARG, "blind %lld: state %d is neither 0 (open) nor 1 (closed)", (long long)i, (int)bl->state[i]);
+        if (j < 0 || j >= NS) return failp(err, HEAT_E_SIZE, "blind %lld: shade %d outside [0, %lld)", (long long)i, j, (long long)NS);
+        if (taken[(size_t)j]) return failp(err, HEAT_E_SIZE, "blind %lld: shade %d carries a blind already (at most one blind per shade)", (long long)i, j);
+        taken[(size_t)j] = 1;
+        if (pc < -1 || pc >= NC) return failp(err, HEAT_E_SIZE, "blind %lld: position channel %d outside [-1, %d)", (long long)i, pc, NC);
+        if (ec < -1 || ec >= NC) return failp(err, HEAT_E_SIZE, "blind %lld: enable channel %d outside [-1, %d)", (long long)i, ec, NC);
+        if (z < -1 || z >= n_zones) return failp(err, HEAT_E_SIZE, "blind %lld: zone %d outside [-1, %lld)", (long long)i, z, (long long)n_zones);
+        if (pc < 0) {  // (controlled; the thresholds of a scheduled blind are not read)
+            if (!bl->irr_close || !bl->irr_open)
+                return failp(err, HEAT_E_INVALID_ARG, "blind %lld: controlled (no position channel), but %s is NULL", (long long)i,
+                             !bl->irr_close ? "irr_close" : "irr_open");
+            if (!std::isfinite(bl->irr_close[i]) || !std::isfinite(bl->irr_open[i]))
+                return failp(err, HEAT_E_INVALID_ARG, "blind %lld: irr_close = %g / irr_open = %g is not finite", (long long)i, bl->irr_close[i],
+                             bl->irr_open[i]);
+            if (bl->irr_open[i] > bl->irr_close[i])
+                return failp(err, HEAT_E_INVALID_ARG, "blind %lld: irr_open = %g is above irr_close = %g", (long long)i, bl->irr_open[i],
+                             bl->irr_close[i]);
+        }
+        if (z < 0) continue;  // (no room condition: setpoint channel and band are not read)
+        if (!bl->set_chan || !bl->band)
+            return failp(err, HEAT_E_INVALID_ARG, "blind %lld: gated by zone %d, but %s is NULL", (long long)i, z, !bl->set_chan ? "set_chan" : "band");
+        if (!std::isfinite(bl->band[i]) || bl->band[i] < 0.0)
+            return failp(err, HEAT_E_INVALID_ARG, "blind %lld: band = %g is negative or not finite", (long long)i, bl->band[i]);
+        if (bl->set_chan[i] < 0 || bl->set_chan[i] >= NC)
+            return failp(err, HEAT_E_SIZE, "blind %lld: setpoint channel %d outside [0, %d)", (long long)i, bl->set_chan[i], NC);
+    }
+    return HEAT_OK;
+}
+
+void build_blind_tables(int64_t n_shades, const heat_blinds *bl, BlindTables &t) {
+    t = BlindTables();
+    const size_t N = bl && bl->n_blinds > 0 ? (size_t)bl->n_blinds : 0;
+    if (N == 0) return;
+    t.blind_of_shade.assign((size_t)n_shades, -1);
+    t.i32.assign(kBlindI32Rows * N, -1);
+    t.f64.assign(kBlindF64Rows * N, 0.0);
+    for (size_t i = 0; i < N; i++) {
+        t.blind_of_shade[(size_t)bl->shade[i]] = (int32_t)i;
+        const int32_t pc = bl->pos_chan ? bl->pos_chan[i] : -1;
+        const int32_t z = pc < 0 && bl->zone ? bl->zone[i] : -1;
+        t.i32[BL_POS_CHAN * N + i] = pc;
+        t.i32[BL_ZONE * N + i] = z;
+        t.i32[BL_SET_CHAN * N + i] = z >= 0 ? bl->set_chan[i] : -1;
+        t.i32[BL_ENABLE_CHAN * N + i] = pc < 0 && bl->enable_chan ? bl->enable_chan[i] : -1;
+        t.f64[BL_BEAM * N + i] = bl->beam_closed[i];
+        t.f64[BL_DIFFUSE * N + i] = bl->diffuse_closed[i];
+        t.f64[BL_GROUND * N + i] = bl->ground_closed[i];
+        t.f64[BL_IRR_CLOSE * N + i] = pc < 0 ? bl->irr_close[i] : 0.0;
+        t.f64[BL_IRR_OPEN * N + i] = pc < 0 ? bl->irr_open[i] : 0.0;
+        t.f64[BL_HALF_BAND * N + i] = z >= 0 ? bl->band[i] / 2.0 : 0.0;
+    }
+}
+
+int check_blind_tables(int64_t n_shades, const heat_blinds *bl, const BlindTables &t, std::string &err) {
+    const size_t N = bl && bl->n_blinds > 0 ? (size_t)bl->n_blinds : 0, NS = N ? (size_t)n_shades : 0;
+    if (t.blind_of_shade.size() != NS || t.i32.size() != kBlindI32Rows * N || t.f64.size() != kBlindF64Rows * N)
+        return failp(err, HEAT_E_SIZE, "blind tables: %zu shades, %zu integers and %zu reals for blind i < %zu on %zu shades",
+                     t.blind_of_shade.size(), t.i32.size(), t.f64.size(), N, NS);
+    size_t carried = 0;
+    for (size_t j = 0; j < NS; j++) {
+        const int32_t i = t.blind_of_shade[j];
+        if (i == -1) continue;
+        if (i < 0 || (size_t)i >= N || bl->shade[i] != (int32_t)j)
+            return failp(err, HEAT_E_SIZE, "blind tables: shade %zu carries blind %d, which is not on it", j, i);
+        carried++;
+    }
+    if (carried != N) return failp(err, HEAT_E_SIZE, "blind tables: %zu shades carry a blind i, of %zu blinds", carried, N);
+    for (size_t i = 0; i < N; i++) {
+        const int32_t pc = t.i32[BL_POS_CHAN * N + i], z = t.i32[BL_ZONE * N + i];
+        const bool same = pc == (bl->pos_chan ? bl->pos_chan[i] : -1) && t.f64[BL_BEAM * N + i] == bl->beam_closed[i] &&
+                          t.f64[BL_DIFFUSE * N + i] == bl->diffuse_closed[i] && t.f64[BL_GROUND * N + i] == bl->ground_closed[i] &&
+                          (pc >= 0 || (z == (bl->zone ? bl->zone[i] : -1) && t.f64[BL_IRR_CLOSE * N + i] == bl->irr_close[i] &&
+                                       t.f64[BL_IRR_OPEN * N + i] == bl->irr_open[i] &&
+                                       t.i32[BL_ENABLE_CHAN * N + i] == (bl->enable_chan ? bl->enable_chan[i] : -1))) &&
+                          (z < 0 || (t.i32[BL_SET_CHAN * N + i] == bl->set_chan[i] && t.f64[BL_HALF_BAND * N + i] == bl->band[i] / 2.0));
+        if (!same) return failp(err, HEAT_E_SIZE, "blind tables: blind %zu is not the caller's", i);
+    }
+    return HEAT_OK;
+}
+
 // ---- room radiation of a series (include/heat_amd.h, heat_room_radiation) ----
 int check_room_radiation(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_room_radiation *rr, std::string &err) {
     if (!rr) return HEAT_OK;
@@ -2792,6 +2895,20 @@ int heat_shades_check(const heat_batch_desc *desc, int32_t n_sites, const heat_s
         return heat::failp(heat::last_error(), HEAT_E_SIZE, "shade tables: %zu values and %zu horizon numbers for shade j < %zu", t.f64.size(),
                            t.horizon.size(), NS);
     return HEAT_OK;
+}
+
+int heat_blinds_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                      const heat_solar_gains *gains, const heat_shades *shades, const heat_blinds *blinds) {
+    int rc = heat_shades_check(desc, n_sites, s, sky, gains, shades);
+    if (rc) return rc;
+    rc = heat::check_blinds(desc->n_zones, s, shades, blinds, heat::last_error());
+    if (rc || !blinds) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see)
+    const int64_t NS = shades ? shades->n_shades : 0;
+    heat::BlindTables t;
+    heat::build_blind_tables(NS, blinds, t);
+    return heat::check_blind_tables(NS, blinds, t, heat::last_error());
 }
 
 int heat_room_radiation_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,

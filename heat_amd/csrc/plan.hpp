@@ -236,6 +236,27 @@ struct ShadeTables {
 // (of shades that passed check_shades)
 void build_shade_tables(const heat_shades *sh, ShadeTables &t);
 
+// Blinds of a series (heat_blinds, include/heat_amd.h). Everything heat_blinds_check promises about the blinds themselves;
+// bl == nullptr is none. s has passed check_series and sh check_shades. HEAT_OK or a negative heat_status with `err` set,
+// naming "blind i".
+int check_blinds(int64_t n_zones, const heat_series *s, const heat_shades *sh, const heat_blinds *bl, std::string &err);
+// The tables of k_series_blinds (one lane per SHADE): the blind of every shade (-1: none) and the blinds as structures of
+// arrays in the caller's blind order, row a of all blinds contiguous. What the rule does not read is neutral here: a NULL
+// pos_chan / zone / enable_chan is -1, set_chan is -1 and the half band 0 where the blind has no zone, the thresholds are 0
+// where the blind is scheduled. The half band is band / 2, the one operation the header gives it.
+enum BlindI32 : int { BL_POS_CHAN, BL_ZONE, BL_SET_CHAN, BL_ENABLE_CHAN, kBlindI32Rows };
+enum BlindF64 : int { BL_BEAM, BL_DIFFUSE, BL_GROUND, BL_IRR_CLOSE, BL_IRR_OPEN, BL_HALF_BAND, kBlindF64Rows };
+struct BlindTables {
+    std::vector<int32_t> blind_of_shade;  // [n_shades]
+    std::vector<int32_t> i32;             // [kBlindI32Rows][n_blinds]
+    std::vector<double> f64;              // [kBlindF64Rows][n_blinds]
+};
+// (of blinds that passed check_blinds)
+void build_blind_tables(int64_t n_shades, const heat_blinds *bl, BlindTables &t);
+// The tables against the caller's lists (used by the host-only check): every blind on its shade and no other shade taken,
+// every row of the caller's values. HEAT_OK or HEAT_E_SIZE.
+int check_blind_tables(int64_t n_shades, const heat_blinds *bl, const BlindTables &t, std::string &err);
+
 // Room radiation of a series (heat_room_radiation, include/heat_amd.h). Everything heat_room_radiation_check promises about
 // the radiation itself; rr == nullptr is none. s has passed check_series and sky check_sky. HEAT_OK or a negative heat_status
 // with `err` set, naming "receiver r" or "entry i".

@@ -916,6 +916,92 @@ int heat_batch_march_series_ambient(heat_batch *b, const heat_series *s, const h
                                     heat_room_radiation *radiation /* nullable */, double *irradiance,
                                     heat_ambient_drive *ambient /* nullable */,
                                     double *ambient_t /* [n_steps][n_sides], nullable */, int32_t *failed_step);
+
+/*
+ * Blinds of a series: MOVABLE solar protection — a blind, roller shade or shutter that closes when the sun is on the window and
+ * the room is warm, or that follows a position schedule. Nothing else that acts on the sun can move: an aperture's ap_scale and
+ * a shade's diffuse_factor / ground_factor are constant over a series and the sunlit fraction is pure geometry. A blind cannot
+ * be a channel (what an aperture transmits is formed on the device from the sky record) and, where it is controlled, not a
+ * schedule either: the decision needs a zone temperature only the device holds, as a thermostat, an air path and a b-factor mix
+ * do. The reference has no counterpart; the rule below is this library's own contract, defined against the per-call loop with
+ * the same rule written on the host (heat_amd/blinds.py, incident_on() and apply()).
+ * A BLIND i rides on shade j = shade[i] of the call's heat_shades (at most one blind per shade; a window without overhang or
+ * fins uses a shade of zero depths). It turns the shade's three factors (f, diffuse_factor, ground_factor) into EFFECTIVE
+ * factors (f', fd', fg'), and every consumer of that shade — sky-driven solar sides and apertures — reads those where it reads
+ * (f, fd, fg) without blinds. A shade without a blind gets plain copies. sunlit[k][j] keeps the geometric f.
+ * Step k, behind the shades and before the sky; r = the record of the shade's own site, f = the sunlit fraction the shades have
+ * just stored for shade j, fd, fg = the shade's constant factors (1 where NULL), n = the shade's normal, T = the zone
+ * temperatures the device holds when the step starts (as air paths and the ambient drive read them), row = channel[k]. Every
+ * line is ONE rounded f64 operation in the order written, no fused multiply-add; max and min are those of heat_shades (the
+ * FIRST operand where the comparison is false):
+ *   c  = (n.x * r.sun_x + n.y * r.sun_y) + n.z * r.sun_z;   fs = 0.5 + 0.5 * n.z;   fg_ = 0.5 - 0.5 * n.z
+ *   bm = c > 0 ? r.beam * c : 0.0;  bm = bm * f;  dv = (r.diffuse * fs) * fd;  gv = (r.ground * fg_) * fg
+ *   I  = (bm + dv) + gv                       (W/m2: what an unblinded sky-driven side in the shade's plane receives)
+ *   scheduled (pos_chan[i] >= 0):   p = row[pos_chan[i]];  p = max(p, 0.0);  p = min(p, 1.0)
+ *                                             (a NaN position stays NaN and propagates; the state byte is left as it is)
+ *   controlled (pos_chan NULL or -1):
+ *       enabled = enable_chan[i] < 0 or row[enable_chan[i]] > 0
+ *       d = band[i] / 2;  hi = set + d;  lo = set - d          (set = row[set_chan[i]]; only where zone[i] >= 0)
+ *       hot  = zone[i] < 0 or T[zone[i]] > hi
+ *       cool = zone[i] >= 0 and T[zone[i]] < lo
+ *       if not enabled:                                   state = 0
+ *       else if I > irr_close[i] and hot:                 state = 1
+ *       else if state == 1 and (I < irr_open[i] or cool): state = 0
+ *       p = state            (a NaN makes every comparison false: the state stays; a NaN enable value disables)
+ *   q = 1.0 - p
+ *   kb = q + p * beam_closed[i];   kd = q + p * diffuse_closed[i];   kg = q + p * ground_closed[i]      (two operations each)
+ *   f' = f * kb;   fd' = fd * kd;   fg' = fg * kg
+ *   position[k * n_blinds + i] = p;   blind_incident[k * n_blinds + i] = I;   sum_position[i] = sum_position[i] + p
+ *   steps_closed[i] += (p > 0);   switches[i] += (state after != before)
+ * With p == 0 every factor is multiplied by exactly 1.0: an open blind gives the bits of the call without blinds. With p == 1
+ * the factors are exactly f * beam_closed and so on. Between irr_open and irr_close, and inside the band, a blind keeps its
+ * state (hysteresis). A scheduled blind never switches. position, blind_incident, state and the accumulators are in the
+ * caller's blind order. State and the accumulators carry a cut: a series of k steps followed by one of n - k with the
+ * returned arrays gives the bits of the series of n; state == NULL: every controlled blind starts open and the states are not
+ * returned. n_sub == 0 still evaluates the blinds of every step. A blind reads the record of ITS SHADE's site: weather sites
+ * are supported. Sharded batches are refused, as by the series.
+ * Out of scope: a blind that redirects beam into diffuse radiation (venetian slats), and a blind's effect on the window's
+ * long-wave exchange or convection — the blind acts on the three solar factors alone.
+ * heat_blinds_check (host-only; it also builds and verifies the table the march uploads) and heat_batch_march_series_blinds
+ * run the same checks before any device work; every message names "blind i": a negative count, a NULL array a positive count
+ * needs (pos_chan, zone, enable_chan, state and the accumulators may be NULL; irr_close and irr_open may be NULL when every
+ * blind is scheduled; set_chan and band when no zone is >= 0), n_blinds > 0 without shades, a closed factor that is not finite
+ * or negative, irr_open > irr_close or either not finite on a controlled blind, a band that is negative or not finite where
+ * zone >= 0, a state byte above 1 -> HEAT_E_INVALID_ARG; a shade outside [0, n_shades), a shade named twice, a zone outside
+ * [-1, n_zones), set_chan outside [0, n_channels) where zone >= 0, pos_chan or enable_chan outside [-1, n_channels) ->
+ * HEAT_E_SIZE.
+ * heat_batch_march_series_blinds with blinds == NULL or n_blinds == 0 is heat_batch_march_series_ambient exactly (same
+ * launches, same bits); position and blind_incident are nullable, and an array that is not asked for costs no traffic and
+ * changes no bit of the others.
+ */
+typedef struct heat_blinds {
+    int64_t n_blinds;
+    const int32_t *shade;          /* [n_blinds] the shade the blind rides on */
+    const double *beam_closed, *diffuse_closed, *ground_closed;   /* [n_blinds] factors of the fully closed blind, finite, >= 0 */
+    const int32_t *pos_chan;       /* [n_blinds] nullable / -1: controlled; else SCHEDULED: the position is a channel */
+    const double *irr_close, *irr_open;   /* [n_blinds] W/m2 on the shade's plane, irr_open <= irr_close; read only where controlled */
+    const int32_t *zone;           /* [n_blinds] nullable / -1: no room condition; else the zone whose temperature gates the blind */
+    const int32_t *set_chan;       /* [n_blinds] the zone's setpoint channel, C; read only where zone >= 0 */
+    const double *band;            /* [n_blinds] K, >= 0; read only where zone >= 0 */
+    const int32_t *enable_chan;    /* [n_blinds] nullable / -1: always enabled; else enabled where row[chan] > 0 */
+    uint8_t *state;                /* [n_blinds] in/out, nullable (= all open): 0 open, 1 closed; controlled blinds only */
+    int64_t *steps_closed;         /* [n_blinds] in/out, nullable */
+    int64_t *switches;             /* [n_blinds] in/out, nullable */
+    double *sum_position;          /* [n_blinds] in/out, nullable */
+} heat_blinds;
+
+int heat_blinds_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                      const heat_solar_gains *gains, const heat_shades *shades, const heat_blinds *blinds); /* host-only */
+int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const heat_sky *sky /* nullable */,
+                                   const heat_shades *shades /* nullable */, const heat_solar_gains *gains /* nullable */,
+                                   const heat_zone_loads *l /* nullable */, heat_air_paths *air /* nullable */,
+                                   heat_ideal_loads *il /* nullable */, heat_series_report *r /* nullable */, double *trace,
+                                   double *applied, double *ideal_q, double *transmitted, double *path_q, double *sunlit,
+                                   heat_room_radiation *radiation /* nullable */, double *irradiance,
+                                   heat_ambient_drive *ambient /* nullable */, double *ambient_t,
+                                   heat_blinds *blinds /* nullable */, double *position /* [n_steps][n_blinds], nullable */,
+                                   double *blind_incident /* [n_steps][n_blinds], nullable */, int32_t *failed_step);
+
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -79,6 +79,14 @@ pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub b
     pub n_sides: i64, pub surface: *const i64, pub side: *const u8, pub chan: *const i32, pub gain: *const f64,
     pub offset: *const f64, pub mix_zone: *const i32, pub mix: *const f64, pub sum_temperature: *mut f64,
 }
+// heat_blinds: movable solar protection that rides on shades, controlled or scheduled
+#[repr(C)] pub struct HeatBlinds {
+    pub n_blinds: i64, pub shade: *const i32,
+    pub beam_closed: *const f64, pub diffuse_closed: *const f64, pub ground_closed: *const f64,
+    pub pos_chan: *const i32, pub irr_close: *const f64, pub irr_open: *const f64,
+    pub zone: *const i32, pub set_chan: *const i32, pub band: *const f64, pub enable_chan: *const i32,
+    pub state: *mut u8, pub steps_closed: *mut i64, pub switches: *mut i64, pub sum_position: *mut f64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -149,6 +157,16 @@ extern "C" {
                                            ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
                                            radiation: *mut HeatRoomRadiation, irradiance: *mut f64, ambient: *mut HeatAmbientDrive,
                                            ambient_t: *mut f64, failed_step: *mut i32) -> c_int;
+    // blinds of a series: movable shades driven by the sun on the window, a zone temperature and schedules, at every step
+    pub fn heat_blinds_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
+                             gains: *const HeatSolarGains, shades: *const HeatShades, blinds: *const HeatBlinds) -> c_int;
+    pub fn heat_batch_march_series_blinds(b: *mut HeatBatch, s: *const HeatSeries, sky: *const HeatSky, shades: *const HeatShades,
+                                          gains: *const HeatSolarGains, l: *const HeatZoneLoads, air: *mut HeatAirPaths,
+                                          il: *mut HeatIdealLoads, r: *mut HeatSeriesReport, trace: *mut f64, applied: *mut f64,
+                                          ideal_q: *mut f64, transmitted: *mut f64, path_q: *mut f64, sunlit: *mut f64,
+                                          radiation: *mut HeatRoomRadiation, irradiance: *mut f64, ambient: *mut HeatAmbientDrive,
+                                          ambient_t: *mut f64, blinds: *mut HeatBlinds, position: *mut f64,
+                                          blind_incident: *mut f64, failed_step: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

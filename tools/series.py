@@ -79,14 +79,24 @@ and writes profiles/series_ambient.json: ms per step of each, M - N, a series of
 the calls are set up, the bytes a step of k_series_ambient moves, and — where the kernel trace of one M series has been taken
 (--one-series --ambient under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_ambient_kernel_stats.csv) —
 k_series_ambient per step. No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient]
+With --blinds (heat_batch_march_series_blinds; the model, channels, loads, probes, records, normals and shades of --shades plus
+three channels: a position schedule, an enable schedule and a cooling setpoint) two legs, alternated in the same way:
+  S  the --shades leg S, run again in the same process with blinds = None: the launches of the parent's path
+  B  S with a blind on every shade — in turn scheduled; controlled by the irradiance alone; gated by the temperature of the
+     wall's zone; gated and with an enable schedule — (position and blind_incident not recorded)
+and writes profiles/series_blinds.json: ms per step of each, B - S, a series of ONE step of each and the per-step times once
+the calls are set up, the bytes a step of k_series_blinds moves, and — where the kernel trace of one B series has been taken
+(--one-series --blinds under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_blinds_kernel_stats.csv) —
+k_series_blinds per step beside the same trace's k_series_shading. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
                                                      with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
                                                      a series of leg J; with --air a series of leg A; with --shades a series of leg S;
-                                                     with --radiation a series of leg R; with --ambient a series of leg M"""
+                                                     with --radiation a series of leg R; with --ambient a series of leg M; with --blinds a series
+                                                     of leg B"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -97,7 +107,8 @@ IDEAL = "--ideal" in sys.argv
 SKY = "--sky" in sys.argv
 GAINS = "--gains" in sys.argv
 AIR = "--air" in sys.argv
-SHADES = "--shades" in sys.argv
+BLINDS = "--blinds" in sys.argv
+SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
 LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT
@@ -196,6 +207,36 @@ if SHADES:
                                                             **{k: (not_driven, drives[k][1]) for k in FRONT})
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace))
+        return dt * 1e3 / steps
+if BLINDS:
+    # three more channels (a position schedule, an enable schedule, a cooling setpoint C) and a blind on every shade, of four
+    # kinds in turn: scheduled; controlled by the irradiance; gated by the wall's zone; gated and with an enable schedule
+    c_bl = channel.shape[1]
+    channel = np.concatenate([channel, rng.uniform(-0.2, 1.2, (STEPS, 1)), np.where(np.arange(STEPS) % 8 < 6, 1.0, 0.0)[:, None],
+                              rng.uniform(19.5, 20.5, (STEPS, 1))], axis=1)
+    kind = np.arange(S) % 4
+    wall_zone = np.where(md["back_kind"] == mdl.SPACE, md["back_zone"], md["front_zone"]).astype(np.int32)
+    blind_args = dict(shade=np.arange(S, dtype=np.int32), beam_closed=rng.uniform(0.05, 0.3, S), diffuse_closed=rng.uniform(0.1, 0.4, S),
+                      ground_closed=rng.uniform(0.1, 0.4, S), pos_chan=np.where(kind == 0, c_bl, -1).astype(np.int32),
+                      irr_close=rng.uniform(150.0, 400.0, S), irr_open=rng.uniform(50.0, 150.0, S),
+                      zone=np.where(kind >= 2, np.clip(wall_zone, 0, Z - 1), -1).astype(np.int32),
+                      set_chan=np.where(kind >= 2, c_bl + 2, -1).astype(np.int32), band=np.full(S, 0.5),
+                      enable_chan=np.where(kind == 3, c_bl + 1, -1).astype(np.int32))
+    # per shade: blind_of_shade, site, f, five table rows, three effective factors; per blind: four integers, six reals, the
+    # state byte, three accumulators read and written; the record, the channels and the zone temperature are shared
+    BLIND_BYTES = dict(k_series_blinds_per_shade=4 + 4 + 8 + 5 * 8 + 3 * 8, k_series_blinds_per_blind=4 * 4 + 6 * 8 + 1 + 3 * 16)
+
+    def leg_bl(b, w, n_sub, steps):
+        b.synchronize()
+        t0 = time.perf_counter()
+        trace, failed, applied, modes, lit, bl = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                                                                sky=dict(sky_args, record=record[:steps]), shades=shade_args, sunlit=False,
+                                                                blinds=blind_args, position=False, blind_incident=False,
+                                                                **{k: (not_driven, drives[k][1]) for k in FRONT})
+        dt = time.perf_counter() - t0
+        assert failed == -1 and np.all(np.isfinite(trace)) and bl["steps_closed"].any()
+        # (a whole day: the sun comes and goes, controlled blinds switch; a short series may lie in the night)
+        assert steps < STEPS or bl["switches"].any()
         return dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
@@ -522,6 +563,30 @@ with HeatBatch(md) as b:
                   "N %.2f ms, M %.2f ms -> per step without the set-up N %.3f, M %.3f, M - N = %+.3f (%d driven sides, %d steps, median of "
                   "%d rounds)" % (n_sub, N_, M_, M_ - N_, M_ / N_, N1, M1, Ns, Ms, Ms - Ns, NB, STEPS, ROUNDS), flush=True)
             continue
+        if BLINDS:
+            leg_s(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_bl(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with blinds: B %.3f ms per step" % leg_bl(b, w, n_sub, STEPS))
+                continue
+            sh, bl, sh1, bl1 = [], [], [], []
+            for r in range(ROUNDS):
+                sh.append(leg_s(b, w, n_sub, STEPS))
+                bl.append(leg_bl(b, w, n_sub, STEPS))
+                sh1.append(leg_s(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                bl1.append(leg_bl(b, w, n_sub, 1))
+            Sh, B, Sh1, B1 = (float(np.median(v)) for v in (sh, bl, sh1, bl1))
+            Ss, Bs = (Sh * STEPS - Sh1) / (STEPS - 1), (B * STEPS - B1) / (STEPS - 1)  # per step once the call is set up
+            nbytes = (BLIND_BYTES["k_series_blinds_per_shade"] + BLIND_BYTES["k_series_blinds_per_blind"]) * S
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                S_blinds_null_ms=Sh, B_blinds_ms=B, B_minus_S_ms=B - Sh, B_over_S=B / Sh, S_series_of_one_step_ms=Sh1,
+                B_series_of_one_step_ms=B1, S_without_setup_ms=Ss, B_without_setup_ms=Bs, B_minus_S_without_setup_ms=Bs - Ss,
+                shades=int(S), blinds=int(S), bytes=BLIND_BYTES, bytes_per_step_of_k_series_blinds=int(nbytes),
+                all_rounds=dict(S=sh, B=bl, S_one_step=sh1, B_one_step=bl1))
+            print("n_sub %2d: S blinds NULL %.3f ms/step, B blinds %.3f -> B - S = %+.3f ms, B / S = %.4f; a series of one step: "
+                  "S %.2f ms, B %.2f ms -> per step without the set-up S %.3f, B %.3f, B - S = %+.3f (%d blinds, %d steps, median of "
+                  "%d rounds)" % (n_sub, Sh, B, B - Sh, B / Sh, Sh1, B1, Ss, Bs, Bs - Ss, S, STEPS, ROUNDS), flush=True)
+            continue
         if SHADES:
             leg_k(b, w, n_sub, min(STEPS, 10))  # warm-up
             leg_s(b, w, n_sub, min(STEPS, 10))
@@ -759,7 +824,26 @@ if AIR and not ONE:
             {k: v["expectation_A_at_most_1_05_of_D_plus_the_kernel"] for k, v in result["legs"].items()}))
     else:
         print("no kernel trace at %s: the expectation A <= 1.05 (D + k_series_air_paths) is not evaluated" % stats)
-if SHADES and not ONE:
+if BLINDS and not ONE:
+    # the kernel trace of one B series (--one-series --blinds under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: k_series_blinds per step and on its own bytes, beside the same trace's k_series_shading
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_blinds_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_blinds", "k_series_shading", "k_series_sky")}
+        nbytes = (BLIND_BYTES["k_series_blinds_per_shade"] + BLIND_BYTES["k_series_blinds_per_blind"]) * S
+        result["kernel_trace_of_one_B_series"] = dict(
+            k_series_blinds_us_per_step=us["k_series_blinds"], k_series_shading_us_per_step=us["k_series_shading"],
+            k_series_sky_us_per_step=us["k_series_sky"], k_series_blinds_bytes_per_step=int(nbytes),
+            k_series_blinds_TB_per_s=nbytes / us["k_series_blinds"] / 1e6, calls=int(rows["k_series_blinds"]["Calls"]))
+        print("kernel trace: k_series_blinds %.2f us per step (%.2f TB/s on its own bytes), k_series_shading %.2f, k_series_sky %.2f" % (
+            us["k_series_blinds"], nbytes / us["k_series_blinds"] / 1e6, us["k_series_shading"], us["k_series_sky"]))
+    else:
+        print("no kernel trace at %s" % stats)
+if SHADES and not BLINDS and not ONE:
     # the kernel trace of one S series (--one-series --shades under rocprofv3 --kernel-trace --stats, a run of its own), where it
     # has been taken: k_series_shading per step and on its own bytes, beside the same trace's k_series_sky
     stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
@@ -794,7 +878,7 @@ if AMBIENT and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
