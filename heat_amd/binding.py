@@ -166,6 +166,26 @@ class Blinds(C.Structure):
                 ("sum_position", _dp)]
 
 
+class SkyCoef(C.Structure):
+    """heat_sky_coef (include/heat_amd.h): the circumsolar fraction and the horizon coefficient of one site at one step, 16 bytes"""
+    _fields_ = [("circ", _d), ("horiz", _d)]
+
+
+class SkyAniso(C.Structure):
+    """heat_sky_aniso (include/heat_amd.h): per-site coefficient pairs beside the sky records, and the consumers' bands"""
+    _fields_ = [("coef", C.POINTER(SkyCoef)), ("front_band", _dp), ("back_band", _dp), ("aperture_band", _dp), ("shade_band", _dp)]
+
+
+class SeriesCall(C.Structure):
+    """heat_series_call (include/heat_amd.h): every term of a series march by name, for heat_batch_march_series_call"""
+    _fields_ = [("size", C.c_size_t), ("s", C.POINTER(Series)), ("sky", C.POINTER(Sky)), ("aniso", C.POINTER(SkyAniso)),
+                ("shades", C.POINTER(Shades)), ("gains", C.POINTER(SolarGains)), ("l", C.POINTER(ZoneLoads)),
+                ("air", C.POINTER(AirPaths)), ("il", C.POINTER(IdealLoads)), ("r", C.POINTER(Report)),
+                ("radiation", C.POINTER(RoomRadiation)), ("ambient", C.POINTER(AmbientDrive)), ("blinds", C.POINTER(Blinds)),
+                ("trace", _dp), ("applied", _dp), ("ideal_q", _dp), ("transmitted", _dp), ("path_q", _dp), ("sunlit", _dp),
+                ("irradiance", _dp), ("ambient_t", _dp), ("position", _dp), ("blind_incident", _dp), ("failed_step", _i32p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -239,6 +259,9 @@ SYMBOLS = [
                                                  C.POINTER(ZoneLoads), C.POINTER(AirPaths), C.POINTER(IdealLoads),
                                                  C.POINTER(Report), _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(RoomRadiation), _dp,
                                                  C.POINTER(AmbientDrive), _dp, C.POINTER(Blinds), _dp, _dp, _i32p]),
+    ("heat_sky_aniso_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains),
+                                       C.POINTER(Shades), C.POINTER(SkyAniso)]),
+    ("heat_batch_march_series_call", C.c_int, [_H, C.POINTER(SeriesCall)]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -390,7 +413,7 @@ def make_desc(md):
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
-                     "heat_blinds_check",
+                     "heat_blinds_check", "heat_sky_aniso_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1238,6 +1261,70 @@ def blinds_check(md, blinds, shades=None, sky=None, gains=None, n_sites=1, lib=N
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+_ANISO_BANDS = ("front_band", "back_band", "aperture_band", "shade_band")
+
+
+def make_sky_aniso(coef=None, front_band=None, back_band=None, aperture_band=None, shade_band=None):
+    """Builds a heat_sky_aniso. Returns (aniso, keepalive).
+    coef            [n_steps, n_sites, 2] (or [n_steps, 2] for one site): (circ, horiz) = (F1, F2) of every site at every step,
+                    beside the sky's records (sky.hay_davies and sky.reindl give pairs: np.stack them on the last axis)
+    front_band, back_band   a value per surface: the band of the front / back solar input (sky.band_reindl, sky.band_perez);
+                    None: zeros
+    aperture_band   a value per aperture of the call's gains; None: zeros
+    shade_band      a value per shade of the call's shades, read by the blinds for the irradiance they decide on; None: zeros"""
+    keep = {}
+    an = SkyAniso()
+    if coef is not None:
+        q = np.ascontiguousarray(coef, dtype=np.float64)
+        if q.ndim not in (2, 3) or q.shape[-1] != 2:
+            raise ValueError("sky coefficients are [n_steps, n_sites, 2], not %s" % (q.shape,))
+        keep["coef"] = q
+        an.coef = C.cast(q.ctypes.data, C.POINTER(SkyCoef)) if q.size else None
+    for name, v in zip(_ANISO_BANDS, (front_band, back_band, aperture_band, shade_band)):
+        if v is None:
+            continue
+        v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+        keep[name] = v
+        setattr(an, name, v.ctypes.data_as(_dp))   # (also of no length: a band that was given is not NULL)
+    return an, keep
+
+
+def _aniso_fits(akeep, n_steps, n_sites, n_surfaces, n_apertures, n_shades):
+    q = akeep.get("coef")
+    if q is not None and q.size and (q.size // 2 != n_steps * n_sites or (q.ndim == 3 and q.shape[1] != n_sites)):
+        raise ValueError("sky coefficients %s for %d steps of %d sites" % (q.shape, n_steps, n_sites))
+    for name, n, what in (("front_band", n_surfaces, "surfaces"), ("back_band", n_surfaces, "surfaces"),
+                          ("aperture_band", n_apertures, "apertures"), ("shade_band", n_shades, "shades")):
+        if name in akeep and n is not None and akeep[name].shape != (n,):
+            raise ValueError("sky aniso %s: %s for %d %s" % (name, akeep[name].shape, n, what))
+
+
+def sky_aniso_check(md, aniso, sky=None, gains=None, shades=None, n_sites=1, lib=None, **series):
+    """heat_sky_aniso_check: everything about the anisotropic sky of a series that needs no device (series arguments as
+    HeatBatch.march_series; sky, gains, shades as shades_check takes them, or None; aniso: the arguments of make_sky_aniso, or
+    None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(n_sites=n_sites, **series)
+    _series_arrays_fit(skeep, int(md["n_surfaces"]))
+    k = None
+    if sky is not None or gains is not None:
+        k, kkeep = make_sky(**_sky_for_gains(sky, _model_normals(md), int(md["n_surfaces"])))
+        _sky_fits(kkeep, s.n_steps, int(n_sites), int(md["n_surfaces"]))
+    g, gkeep = make_solar_gains(**gains) if gains is not None else (None, None)
+    h, hkeep = make_shades(**shades) if shades is not None else (None, None)
+    if h is not None:
+        _shades_fit(hkeep, int(md["n_surfaces"]), g.n_apertures if g is not None else None)
+    an, akeep = make_sky_aniso(**aniso) if aniso is not None else (None, None)
+    if an is not None:
+        _aniso_fits(akeep, s.n_steps, int(n_sites), int(md["n_surfaces"]), g.n_apertures if g is not None else None,
+                    h.n_shades if h is not None else None)
+    ref = lambda x: C.byref(x) if x is not None else None
+    rc = L.heat_sky_aniso_check(C.byref(desc), int(n_sites), C.byref(s), ref(k), ref(g), ref(h), ref(an))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1358,7 +1445,7 @@ class HeatBatch:
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
-                     blinds=None, position=True, blind_incident=True, **series):
+                     blinds=None, position=True, blind_incident=True, aniso=None, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1406,7 +1493,12 @@ class HeatBatch:
         temperature the device holds, or following a position channel, formed on the device at every step. Returns what the
         same call without blinds returns plus one dict: position and incident [n_steps, n_blinds] (empty with position=False /
         blind_incident=False), state, and of steps_closed, switches, sum_position those in stats (pass state and them on to the
-        next series) — one more element of the tuple, or the key "blinds" of the dict."""
+        next series) — one more element of the tuple, or the key "blinds" of the dict.
+        aniso (a dict of make_sky_aniso's arguments: coef [n_steps, n_sites, 2], front_band, back_band, aperture_band,
+        shade_band): an anisotropic sky — every sky-driven solar side, aperture and blind takes the diffuse radiation by the
+        caller's circumsolar and horizon coefficients (heat_sky_aniso). The call then goes through
+        heat_batch_march_series_call, the entry point that takes every term in one struct (an empty dict: that entry point
+        without an anisotropic sky). Returns what the same call without aniso returns: anisotropy has no output of its own."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -1416,7 +1508,7 @@ class HeatBatch:
             given["sky"] = _sky_for_gains(sky, self._normals, self.n_surfaces)
         return self._march_series(weather, n_sub, series, given, dict(trace=trace, applied=applied, path_q=path_q, sunlit=sunlit,
                                                                       irradiance=irradiance, ambient_t=ambient_t, position=position,
-                                                                      blind_incident=blind_incident))
+                                                                      blind_incident=blind_incident), aniso=aniso)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -1442,9 +1534,9 @@ class HeatBatch:
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
-    def _march_series(self, weather, n_sub, series, given, want):
+    def _march_series(self, weather, n_sub, series, given, want, aniso=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
-        whether they are recorded."""
+        whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1496,7 +1588,25 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        rc = getattr(self._L, symbol)(self._h, C.byref(s), *args, C.byref(failed))
+        if aniso is not None:
+            # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
+            # that are recorded, and the anisotropic sky.
+            call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
+            if aniso:
+                an, akeep = make_sky_aniso(**aniso)
+                _aniso_fits(akeep, s.n_steps, self.n_sites, self.n_surfaces, made["gains"].n_apertures if "gains" in made else None,
+                            made["shades"].n_shades if "shades" in made else None)
+                call.aniso = C.pointer(an)
+            field = dict(loads="l", ideal="il", report="r")
+            for term, v in given.items():
+                if v is not None:
+                    setattr(call, field.get(term, term), C.pointer(made[term]))
+            for name, a in rows.items():
+                if a.size:
+                    setattr(call, name, a.ctypes.data_as(_dp))
+            rc = self._L.heat_batch_march_series_call(self._h, C.byref(call))
+        else:
+            rc = getattr(self._L, symbol)(self._h, C.byref(s), *args, C.byref(failed))
         if rc != 0:
             e = HeatError(rc, self._L.heat_last_error().decode("utf-8", "replace"))
             e.failed_step, e.trace = int(failed.value), rows["trace"]

@@ -9,7 +9,7 @@ heat_batch_march_series_blinds.
 The reference has no counterpart: it has no solar geometry at all, let alone one that moves."""
 import numpy as np
 
-from .sky import SUN_X, SUN_Y, SUN_Z, BEAM, DIFFUSE, GROUND
+from .sky import SUN_X, SUN_Y, SUN_Z, BEAM, DIFFUSE, GROUND, circumsolar_ratio
 
 KEYS = ("shade", "beam_closed", "diffuse_closed", "ground_closed", "pos_chan", "irr_close", "irr_open", "zone", "set_chan", "band",
         "enable_chan")
@@ -35,12 +35,14 @@ def shade_factors(shades):
     return fd, fg
 
 
-def incident_on(shades, record, sunlit, site=None):
+def incident_on(shades, record, sunlit, site=None, aniso=None):
     """I: what an unblinded sky-driven side in every shade's plane receives, W/m2.
     shades  a dict of binding.make_shades' arguments (surface, normal, diffuse_factor, ground_factor are read)
     record  [n_sites, 8] the step's records, or [n_steps, n_sites, 8]
     sunlit  [n_shades] the step's geometric sunlit fractions (shading.sunlit), or [n_steps, n_shades]
     site    [n_surfaces] the site of every surface; None: one site
+    aniso   None, or (circ, horiz, band) of heat_sky_aniso: circ and horiz [n_sites] the step's pairs, or [n_steps, n_sites],
+            as the records; band [n_shades] (shade_band)
     Returns [n_shades], or [n_steps, n_shades]. A shade reads the record of ITS surface's site."""
     r = np.asarray(record, dtype=np.float64)
     f = np.asarray(sunlit, dtype=np.float64)
@@ -54,6 +56,22 @@ def incident_on(shades, record, sunlit, site=None):
         fs = 0.5 + 0.5 * nz
         fg_ = 0.5 - 0.5 * nz
         bm = np.where(c > 0.0, r[..., BEAM] * c, 0.0)
+        if aniso is not None:
+            circ = np.asarray(aniso[0], dtype=np.float64)[..., at]
+            horiz = np.asarray(aniso[1], dtype=np.float64)[..., at]
+            band = np.asarray(aniso[2], dtype=np.float64)
+            rb = circumsolar_ratio(c, r[..., SUN_Z])
+            iso = 1.0 - circ
+            cs = (r[..., DIFFUSE] * circ) * rb
+            sun = bm + cs
+            dv = (r[..., DIFFUSE] * fs) * iso
+            hv = (r[..., DIFFUSE] * horiz) * band
+            dv = dv + hv
+            gv = r[..., GROUND] * fg_
+            sun = sun * f
+            dv = dv * fd
+            gv = gv * fg
+            return (sun + dv) + gv
         bm = bm * f
         dv = (r[..., DIFFUSE] * fs) * fd
         gv = (r[..., GROUND] * fg_) * fg

@@ -1730,10 +1730,43 @@ struct AirTerm {
     }
 };
 
-// What the widest entry point (heat_batch_march_series_blinds) takes; filled by field name. no_trace_ok: a NULL trace records none.
+// The anisotropic sky (heat_sky_aniso): the coefficient table as given, beside the record table, and the bands of the three
+// consumers — the sides' per DEVICE surface, the apertures' and the shades' in the caller's order as their tables are; zeros
+// where the caller gave none. Absent (every pointer NULL) without aniso: the isotropic kernels are launched.
+struct AnisoTerm {
+    const heat_sky_aniso *an = nullptr;
+    std::vector<double> h_side;
+    DevBuf<SkyCoef> coef;                  // [n_steps][n_sites]
+    DevBuf<double> side, aperture, shade;  // [2][S], [NA], [NS]
+    void prepare(heat_batch *b, const heat_sky_aniso *an_, unsigned sky_bits) {
+        an = an_;
+        if (!an || !(sky_bits & 3)) return;
+        h_side.assign(2 * (size_t)b->n_surf, 0.0);
+        if (an->front_band) to_device_order(b, an->front_band, h_side.data());
+        if (an->back_band) to_device_order(b, an->back_band, h_side.data() + b->n_surf);
+    }
+    static int band(DevBuf<double> &buf, const double *src, int64_t n, const char *what) {
+        if (n <= 0) return HEAT_OK;
+        if (src) return series_upload(buf, src, (size_t)n, what);
+        return series_upload(buf, std::vector<double>((size_t)n, 0.0), what);
+    }
+    int upload(const heat_batch *b, const heat_series *s, int64_t NA, int64_t NS) {
+        if (!an) return HEAT_OK;
+        SERIES_TRY(series_upload(coef, reinterpret_cast<const SkyCoef *>(an->coef), (size_t)s->n_steps * b->n_sites, "sky coefficients"));
+        SERIES_TRY(series_upload(side, h_side, "side bands"));
+        SERIES_TRY(band(aperture, an->aperture_band, NA, "aperture bands"));
+        SERIES_TRY(band(shade, an->shade_band, NS, "shade bands"));
+        return HEAT_OK;
+    }
+};
+static_assert(sizeof(SkyCoef) == sizeof(heat_sky_coef) && sizeof(heat_sky_coef) == 16, "SkyCoef mirrors heat_sky_coef");
+
+// What heat_batch_march_series_call takes (the eleven positional entry points fill what they have); filled by field name.
+// no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
+    const heat_sky_aniso *aniso = nullptr;
     const heat_shades *shades = nullptr;
     const heat_solar_gains *gains = nullptr;
     const heat_zone_loads *l = nullptr;
@@ -2740,6 +2773,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     // (behind the shard's refusal: the gains number the surfaces of the caller's model, a shard holds some of them)
     if ((rc = check_solar_gains(b->n_surf, s, c.sky, c.gains, heat::last_error()))) return rc;
     if ((rc = check_shades(b->n_surf, s, c.sky, c.gains, c.shades, heat::last_error()))) return rc;
+    if ((rc = check_sky_aniso(b->n_surf, s, c.sky, c.gains, c.shades, c.aniso, heat::last_error()))) return rc;
     if ((rc = check_blinds(b->n_zones, s, c.shades, c.blinds, heat::last_error()))) return rc;
     if ((rc = check_air_paths(b->n_zones, s->n_channels, c.air, heat::last_error()))) return rc;
     if ((rc = check_room_radiation(b->n_surf, s, c.sky, c.radiation, heat::last_error()))) return rc;
@@ -2769,12 +2803,13 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     DevBuf<StepWeather> d_w;
     DevBuf<double> d_zab, d_channel;
     InputsTerm in; ProbesTerm probes; LoadsTerm loads; ReportTerm report; IdealTerm ideal;
-    ShadesTerm shades; BlindsTerm blinds; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air;
+    ShadesTerm shades; BlindsTerm blinds; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air; AnisoTerm aniso;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
     shades.prepare(b, c.shades, sky.bits);
     blinds.prepare(c.blinds, shades.NS);
+    aniso.prepare(b, c.aniso, sky.bits);
     radiation.prepare(b, c.radiation, in);
     ambient.prepare(b, side_kind, c.ambient);
     if ((rc = probes.prepare(b, s))) return rc;
@@ -2797,6 +2832,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = shades.upload(c.shades, NA, c.sunlit, n_steps, NL > 0, sky))) return rc;
     if ((rc = blinds.upload(shades, c.position, c.blind_incident, n_steps))) return rc;
     if ((rc = gains.upload(b, c.transmitted, n_steps, shades, in))) return rc;
+    if ((rc = aniso.upload(b, s, NA, NS))) return rc;
     if ((rc = radiation.upload(c.irradiance, n_steps, in))) return rc;
     if ((rc = ambient.upload(c.ambient, c.ambient_t, n_steps))) return rc;
     if ((rc = air.upload(b, c.path_q, n_steps))) return rc;
@@ -2809,6 +2845,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     for (int k = 0; k < n_steps; k++) {
         const double *channel = row(d_channel, k, NC);
         const SkyRecord *record = row(sky.record, k, n_sites);
+        const SkyCoef *coef = row(aniso.coef, k, n_sites);  // (nullptr without aniso: the isotropic kernels)
         // (the powers of the step: a row of the applied buffer, or one row of scratch where the caller takes none)
         double *applied = loads.applied.p ? row(loads.applied, k, NT) : report.applied_row.p;
         launch_begin_march(row(d_w, k, (int64_t)n_rec), b->d_weather.p, n_sub, (int)n_rec, row(d_zab, std::min(k, zrows - 1), 2 * Z), b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
@@ -2823,10 +2860,11 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
             launch_series_inputs((int)S, channel, in.view, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         if (NS > 0) launch_series_shading(record, shades.view, row(shades.sunlit, k, NS), b->stream);
         if (NL > 0)
-            launch_series_blinds(record, blinds.view, channel, b->d_zone_T.p, row(blinds.position, k, NL), row(blinds.incident, k, NL), b->stream);
-        if (sky.bits) launch_series_sky((int)S, record, sky.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
+            launch_series_blinds(record, blinds.view, channel, b->d_zone_T.p, row(blinds.position, k, NL), row(blinds.incident, k, NL), coef,
+                                 aniso.shade.p, b->stream);
+        if (sky.bits) launch_series_sky((int)S, record, sky.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, coef, aniso.side.p, b->stream);
         if (NA > 0) {
-            launch_series_apertures(record, gains.apertures, row(gains.transmitted, k, NA), b->stream);
+            launch_series_apertures(record, gains.apertures, row(gains.transmitted, k, NA), coef, aniso.aperture.p, b->stream);
             launch_series_solar_gains((int)S, gains.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         }
         if (NR > 0) {
@@ -2964,6 +3002,16 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
     c.applied = applied, c.ideal_q = ideal_q, c.transmitted = transmitted, c.path_q = path_q, c.sunlit = sunlit, c.radiation = radiation;
     c.irradiance = irradiance, c.ambient = ambient, c.ambient_t = ambient_t, c.blinds = blinds, c.position = position;
     c.blind_incident = blind_incident, c.failed_step = failed_step, c.no_trace_ok = true;
+    return march_series_impl(b, c);
+}
+
+int heat_batch_march_series_call(heat_batch *b, const heat_series_call *call) {
+    if (const int rc = check_series_call(call, heat::last_error())) return rc;  // (a struct of another size is not read further)
+    SeriesCall c; c.s = call->s, c.sky = call->sky, c.aniso = call->aniso, c.shades = call->shades, c.gains = call->gains, c.l = call->l;
+    c.air = call->air, c.il = call->il, c.r = call->r, c.radiation = call->radiation, c.ambient = call->ambient, c.blinds = call->blinds;
+    c.trace = call->trace, c.applied = call->applied, c.ideal_q = call->ideal_q, c.transmitted = call->transmitted, c.path_q = call->path_q;
+    c.sunlit = call->sunlit, c.irradiance = call->irradiance, c.ambient_t = call->ambient_t, c.position = call->position;
+    c.blind_incident = call->blind_incident, c.failed_step = call->failed_step, c.no_trace_ok = true;
     return march_series_impl(b, c);
 }
 

@@ -2385,6 +2385,16 @@ k_series_shading(const SkyRecord *__restrict__ records, SeriesShades sh, double 
     if (sunlit_row != nullptr) sunlit_row[j] = f;
 }
 
+// The circumsolar ratio of heat_sky_aniso: cos(incidence) over the zenith cosine held at cos 85 deg, one division; 0 on a
+// plane the sun is behind and with the sun at or below the horizon. A NaN makes every comparison false.
+__device__ __forceinline__ double aniso_rb(double c, double sun_z) {
+#pragma clang fp contract(off)
+    const double Z0 = 0.08715574274765817;
+    const bool up = sun_z > 0.0;
+    const double zb = sun_z > Z0 ? sun_z : Z0;
+    return (c > 0.0 && up) ? c / zb : 0.0;
+}
+
 // k_series_blinds — the effective factors of every shade in one step (heat_blinds, include/heat_amd.h), behind
 // k_series_shading and before k_series_sky: one lane per SHADE. Neighbouring lanes read neighbouring elements of
 // blind_of_shade, of f and of five rows of the shade table (the normal and the two constant factors), and store neighbouring
@@ -2395,9 +2405,13 @@ k_series_shading(const SkyRecord *__restrict__ records, SeriesShades sh, double 
 // operation in the order written, hence no contraction; min and max are shade_max / shade_min. A blind rides on one shade:
 // its state byte, accumulators and output elements have one writer. Nothing on the step's head writes the zone temperatures:
 // every zone is read as it was at the start of the step. No atomics, no LDS.
+// ANISO (heat_sky_aniso): the lane also loads the 16-byte coefficient pair of the shade's site and the shade's band, and I
+// is the anisotropic rule of a shaded side; the instantiation without it is the kernel as it was.
+template <bool ANISO>
 __global__ void __launch_bounds__(256)
 k_series_blinds(const SkyRecord *__restrict__ records, SeriesBlinds bl, const double *__restrict__ row, const double *__restrict__ zone_T,
-                double *__restrict__ position_row, double *__restrict__ incident_row) {
+                double *__restrict__ position_row, double *__restrict__ incident_row, const SkyCoef *__restrict__ coef,
+                const double *__restrict__ band) {
 #pragma clang fp contract(off)
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n = bl.n_shades;
@@ -2415,10 +2429,27 @@ k_series_blinds(const SkyRecord *__restrict__ records, SeriesBlinds bl, const do
     const double c = (nx * r.sun_x + ny * r.sun_y) + nz * r.sun_z;
     const double fs = 0.5 + 0.5 * nz, fgv = 0.5 - 0.5 * nz;
     double bm = c > 0.0 ? r.beam * c : 0.0;
-    bm = bm * f;
-    const double dv = (r.diffuse * fs) * fd;
-    const double gv = (r.ground * fgv) * fg;
-    const double I = (bm + dv) + gv;
+    double I;
+    if (ANISO) {
+        const SkyCoef q = coef[bl.site[j]];
+        const double rb = aniso_rb(c, r.sun_z);
+        const double iso = 1.0 - q.circ;
+        const double cs = (r.diffuse * q.circ) * rb;
+        double sun = bm + cs;
+        double dv = (r.diffuse * fs) * iso;
+        const double hv = (r.diffuse * q.horiz) * band[j];
+        dv = dv + hv;
+        double gv = r.ground * fgv;
+        sun = sun * f;
+        dv = dv * fd;
+        gv = gv * fg;
+        I = (sun + dv) + gv;
+    } else {
+        bm = bm * f;
+        const double dv = (r.diffuse * fs) * fd;
+        const double gv = (r.ground * fgv) * fg;
+        I = (bm + dv) + gv;
+    }
     const int pc = bl.pos_chan[i];
     double p;
     bool switched = false;
@@ -2471,9 +2502,13 @@ k_series_blinds(const SkyRecord *__restrict__ records, SeriesBlinds bl, const do
 // march calls reproduces the bits. From the raw value on it is the tail of series_side, restated: the mirror, the shared
 // clamps and long-wave conversion, one 16-byte store when both fields of a side are sky-driven, else 8 bytes. An input has
 // one source (check_sky): a field k_series_inputs has written is not written here.
+// ANISO (heat_sky_aniso): a lane also loads its site's 16-byte coefficient pair, and a solar side its band; the solar value
+// is the anisotropic rule, shaded or not. The instantiation without it is the kernel as it was.
+template <bool ANISO>
 __device__ __forceinline__ void sky_side(int side, int d, int S, bool m_solar, bool m_ir, double nx, double ny, double nz,
                                          const SkyRecord &r, const SeriesSky &sky, const double *__restrict__ side_alpha,
-                                         SideDyn *__restrict__ dyn, const SlotArrays &sl, double *__restrict__ mirror) {
+                                         SideDyn *__restrict__ dyn, const SlotArrays &sl, double *__restrict__ mirror,
+                                         const SkyCoef &q, const double *__restrict__ band) {
 #pragma clang fp contract(off)
     if (!(m_solar || m_ir)) return;
     const int64_t rec = (int64_t)side * S + d;
@@ -2484,7 +2519,22 @@ __device__ __forceinline__ void sky_side(int side, int d, int S, bool m_solar, b
         double bm = c > 0.0 ? r.beam * c : 0.0;
         const int j = sky.shade != nullptr ? sky.shade[rec] : -1;  // (a kernel argument: without shades the branch is wave-uniform)
         double v;
-        if (j >= 0) {  // heat_shades: the beam times the step's sunlit fraction, the other two parts times their constant factors
+        if (ANISO) {
+            const double rb = aniso_rb(c, r.sun_z);
+            const double iso = 1.0 - q.circ;
+            const double cs = (r.diffuse * q.circ) * rb;
+            double sun = bm + cs;
+            double dv = (r.diffuse * fs) * iso;
+            const double hv = (r.diffuse * q.horiz) * band[rec];
+            dv = dv + hv;
+            double gv = r.ground * fg;
+            if (j >= 0) {  // heat_shades: the sun's part times the step's sunlit fraction, the other two times their factors
+                sun = sun * sky.sf.f[j];
+                dv = dv * sky.sf.diffuse[j];
+                gv = gv * sky.sf.ground[j];
+            }
+            v = (sun + dv) + gv;
+        } else if (j >= 0) {  // heat_shades: the beam times the step's sunlit fraction, the other two parts times their constant factors
             bm = bm * sky.sf.f[j];
             const double dv = (r.diffuse * fs) * sky.sf.diffuse[j];
             const double gv = (r.ground * fg) * sky.sf.ground[j];
@@ -2507,18 +2557,23 @@ __device__ __forceinline__ void sky_side(int side, int d, int S, bool m_solar, b
     else dyn[rec].rad_t = rad_t;
 }
 
+template <bool ANISO>
 __global__ void __launch_bounds__(256)
 k_series_sky(int n_surf, const SkyRecord *__restrict__ records, SeriesSky sky, const double *__restrict__ side_alpha,
-             SideDyn *__restrict__ dyn, SlotArrays sl, double *__restrict__ mirror) {
+             SideDyn *__restrict__ dyn, SlotArrays sl, double *__restrict__ mirror, const SkyCoef *__restrict__ coef,
+             const double *__restrict__ band) {
     const int d = blockIdx.x * blockDim.x + threadIdx.x;
     const int S = n_surf;
     if (d >= S) return;
     const int m = sky.mode[d];
     if (m == 0) return;  // nothing of this surface comes from the sky
-    const SkyRecord r = records[sky.site ? sky.site[d] : 0];
+    const int site = sky.site ? sky.site[d] : 0;
+    const SkyRecord r = records[site];
+    SkyCoef q{0.0, 0.0};
+    if (ANISO && (m & 3)) q = coef[site];  // (read by the solar sides alone)
     const double nx = sky.normal[d], ny = sky.normal[(int64_t)S + d], nz = sky.normal[2 * (int64_t)S + d];
-    sky_side(0, d, S, m & 1, m & 4, nx, ny, nz, r, sky, side_alpha, dyn, sl, mirror);
-    sky_side(1, d, S, m & 2, m & 8, -nx, -ny, -nz, r, sky, side_alpha, dyn, sl, mirror);
+    sky_side<ANISO>(0, d, S, m & 1, m & 4, nx, ny, nz, r, sky, side_alpha, dyn, sl, mirror, q, band);
+    sky_side<ANISO>(1, d, S, m & 2, m & 8, -nx, -ny, -nz, r, sky, side_alpha, dyn, sl, mirror, q, band);
 }
 
 // k_series_apertures — the power every window transmits in one step (heat_solar_gains, include/heat_amd.h), behind
@@ -2526,14 +2581,19 @@ k_series_sky(int n_surf, const SkyRecord *__restrict__ records, SeriesSky sky, c
 // hemispherical transmittance and the scale (structure of arrays: a wavefront reads lines), and applies the header's rule —
 // every product and sum one rounded operation in the order written, hence no contraction. (Pb, Pd) leave as one 16-byte
 // store for k_series_solar_gains; P goes into the step's row of `transmitted` where the caller takes one, and onto ap_sum.
+// ANISO (heat_sky_aniso): the lane also loads its site's 16-byte coefficient pair and its band; the circumsolar part passes
+// with the beam transmittance and the sunlit fraction. The instantiation without it is the kernel as it was.
+template <bool ANISO>
 __global__ void __launch_bounds__(256)
-k_series_apertures(const SkyRecord *__restrict__ records, SeriesApertures ap, double *__restrict__ transmitted) {
+k_series_apertures(const SkyRecord *__restrict__ records, SeriesApertures ap, double *__restrict__ transmitted,
+                   const SkyCoef *__restrict__ coef, const double *__restrict__ band) {
 #pragma clang fp contract(off)
     const int a = blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t n = ap.n;
     if (a >= ap.n) return;
     const int d = ap.dev[a];
-    const SkyRecord r = records[ap.site ? ap.site[d] : 0];
+    const int site = ap.site ? ap.site[d] : 0;
+    const SkyRecord r = records[site];
     const double nx = ap.normal[a], ny = ap.normal[n + a], nz = ap.normal[2 * n + a];
     const double c = (nx * r.sun_x + ny * r.sun_y) + nz * r.sun_z;
     const double fs = 0.5 + 0.5 * nz, fg = 0.5 - 0.5 * nz;
@@ -2548,7 +2608,26 @@ k_series_apertures(const SkyRecord *__restrict__ records, SeriesApertures ap, do
     double pb = c > 0.0 ? (ib * t) * scale : 0.0;
     const int j = ap.shade != nullptr ? ap.shade[a] : -1;  // (a kernel argument: without shades the branch is wave-uniform)
     double id;
-    if (j >= 0) {  // heat_shades
+    if (ANISO) {
+        const SkyCoef q = coef[site];
+        const double rb = aniso_rb(c, r.sun_z);
+        const double iso = 1.0 - q.circ;
+        const double pbm = (ib * t) * scale;
+        const double ics = (r.diffuse * q.circ) * rb;
+        const double pcs = (ics * t) * scale;
+        double ps = pbm + pcs;
+        double dd = (r.diffuse * fs) * iso;
+        const double hv = (r.diffuse * q.horiz) * band[a];
+        dd = dd + hv;
+        double gg = r.ground * fg;
+        if (j >= 0) {  // heat_shades
+            ps = ps * ap.sf.f[j];
+            dd = dd * ap.sf.diffuse[j];
+            gg = gg * ap.sf.ground[j];
+        }
+        pb = c > 0.0 ? ps : 0.0;
+        id = dd + gg;
+    } else if (j >= 0) {  // heat_shades
         pb = c > 0.0 ? pb * ap.sf.f[j] : 0.0;
         id = (r.diffuse * fs) * ap.sf.diffuse[j] + (r.ground * fg) * ap.sf.ground[j];
     } else {
@@ -3228,9 +3307,12 @@ void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in,
 }
 
 void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
-                       const SlotArrays &sl, double *mirror, hipStream_t st) {
+                       const SlotArrays &sl, double *mirror, const SkyCoef *coef, const double *band, hipStream_t st) {
     if (n_surf <= 0) return;
-    hipLaunchKernelGGL(k_series_sky, dim3((n_surf + 255) / 256), dim3(256), 0, st, n_surf, records, sky, side_alpha, dyn, sl, mirror);
+    const dim3 grid((n_surf + 255) / 256);
+    const double *no_band = nullptr;
+    if (coef) hipLaunchKernelGGL(k_series_sky<true>, grid, dim3(256), 0, st, n_surf, records, sky, side_alpha, dyn, sl, mirror, coef, band);
+    else hipLaunchKernelGGL(k_series_sky<false>, grid, dim3(256), 0, st, n_surf, records, sky, side_alpha, dyn, sl, mirror, coef, no_band);
 }
 
 void launch_series_shading(const SkyRecord *records, const SeriesShades &sh, double *sunlit_row, hipStream_t st) {
@@ -3239,15 +3321,21 @@ void launch_series_shading(const SkyRecord *records, const SeriesShades &sh, dou
 }
 
 void launch_series_blinds(const SkyRecord *records, const SeriesBlinds &bl, const double *row, const double *zone_T,
-                          double *position_row, double *incident_row, hipStream_t st) {
+                          double *position_row, double *incident_row, const SkyCoef *coef, const double *band, hipStream_t st) {
     if (bl.n_blinds <= 0 || bl.n_shades <= 0) return;
-    hipLaunchKernelGGL(k_series_blinds, dim3((bl.n_shades + 255) / 256), dim3(256), 0, st, records, bl, row, zone_T, position_row,
-                       incident_row);
+    const dim3 grid((bl.n_shades + 255) / 256);
+    const double *no_band = nullptr;
+    if (coef) hipLaunchKernelGGL(k_series_blinds<true>, grid, dim3(256), 0, st, records, bl, row, zone_T, position_row, incident_row, coef, band);
+    else hipLaunchKernelGGL(k_series_blinds<false>, grid, dim3(256), 0, st, records, bl, row, zone_T, position_row, incident_row, coef, no_band);
 }
 
-void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st) {
+void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, const SkyCoef *coef,
+                             const double *band, hipStream_t st) {
     if (ap.n <= 0) return;
-    hipLaunchKernelGGL(k_series_apertures, dim3((ap.n + 255) / 256), dim3(256), 0, st, records, ap, transmitted);
+    const dim3 grid((ap.n + 255) / 256);
+    const double *no_band = nullptr;
+    if (coef) hipLaunchKernelGGL(k_series_apertures<true>, grid, dim3(256), 0, st, records, ap, transmitted, coef, band);
+    else hipLaunchKernelGGL(k_series_apertures<false>, grid, dim3(256), 0, st, records, ap, transmitted, coef, no_band);
 }
 
 void launch_series_solar_gains(int n_surf, const SeriesGains &g, const double *side_alpha, SideDyn *dyn, const SlotArrays &sl,

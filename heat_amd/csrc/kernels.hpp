@@ -83,6 +83,12 @@ void launch_series_inputs(int n_surf, const double *row, const SeriesInputs &in,
 struct alignas(16) SkyRecord {  // heat_sky_record
     double sun_x, sun_y, sun_z, beam, diffuse, ground, ir_sky, ir_ground;
 };
+// Anisotropic sky (heat_sky_aniso, include/heat_amd.h): one pair per site and step beside the record. The three consumers of
+// the record — launch_series_blinds, launch_series_sky, launch_series_apertures — take the step's row of pairs, [n_sites], and
+// their bands (sides [2][S] in device order, shades [n_shades], apertures [n]); coef == nullptr launches the isotropic kernels.
+struct alignas(16) SkyCoef {  // heat_sky_coef
+    double circ, horiz;
+};
 // What a shaded consumer gathers (heat_shades): the step's sunlit fraction k_series_shading has just stored and the two
 // constant factors, rows of the shade table.
 struct ShadeFactors {
@@ -132,10 +138,10 @@ struct SeriesBlinds {
 // records: the step's row of the record table, [n_sites]; row: the step's row of the channel table; position_row /
 // incident_row: the step's rows of position / blind_incident, [n_blinds] (caller's order), or nullptr
 void launch_series_blinds(const SkyRecord *records, const SeriesBlinds &bl, const double *row, const double *zone_T,
-                          double *position_row, double *incident_row, hipStream_t st);
+                          double *position_row, double *incident_row, const SkyCoef *coef, const double *band, hipStream_t st);
 // records: the step's row of the record table, [n_sites]
 void launch_series_sky(int n_surf, const SkyRecord *records, const SeriesSky &sky, const double *side_alpha, SideDyn *dyn,
-                       const SlotArrays &sl, double *mirror, hipStream_t st);
+                       const SlotArrays &sl, double *mirror, const SkyCoef *coef, const double *band, hipStream_t st);
 // Solar gains of a series step (heat_solar_gains, include/heat_amd.h; tables: plan.hpp, SolarGainTables): two launches
 // behind launch_series_sky and before the body, only when there are apertures — one lane per aperture, then (only when there
 // are entries) one lane per receiver.
@@ -161,7 +167,8 @@ struct SeriesGains {
     const double *gain[2];     // the series' solar gain arrays, front and back (SeriesInputs::gain); nullptr: 1
 };
 // records: the step's row of the record table, [n_sites]; transmitted: the step's row, [n], or nullptr
-void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, hipStream_t st);
+void launch_series_apertures(const SkyRecord *records, const SeriesApertures &ap, double *transmitted, const SkyCoef *coef,
+                             const double *band, hipStream_t st);
 void launch_series_solar_gains(int n_surf, const SeriesGains &g, const double *side_alpha, SideDyn *dyn, const SlotArrays &sl,
                                double *mirror, hipStream_t st);
 // Room radiation of a series step (heat_room_radiation, include/heat_amd.h; tables: plan.hpp, RoomRadiationTables): two

@@ -2025,6 +2025,40 @@ int check_sky(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, std
     return HEAT_OK;
 }
 
+// ---- the one-struct call of a series (include/heat_amd.h, heat_series_call) ----
+int check_series_call(const heat_series_call *call, std::string &err) {
+    if (!call) return failp(err, HEAT_E_INVALID_ARG, "series call is NULL");
+    if (call->size != sizeof(heat_series_call))
+        return failp(err, HEAT_E_INVALID_ARG, "series call: size %zu is not sizeof(heat_series_call) = %zu of this library", call->size,
+                     sizeof(heat_series_call));
+    if (!call->s) return failp(err, HEAT_E_INVALID_ARG, "series call: s is NULL");
+    return HEAT_OK;
+}
+
+// ---- anisotropic sky of a series (include/heat_amd.h, heat_sky_aniso) ----
+int check_sky_aniso(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, const heat_shades *sh,
+                    const heat_sky_aniso *an, std::string &err) {
+    if (!an) return HEAT_OK;
+    if (!sky || !sky->record)
+        return failp(err, HEAT_E_INVALID_ARG, "sky aniso: the coefficients stand beside the sky records, but %s is NULL", sky ? "sky->record" : "sky");
+    if (!an->coef && s->n_steps > 0) return failp(err, HEAT_E_INVALID_ARG, "sky aniso: coef is NULL (n_steps %d)", s->n_steps);
+    if (an->aperture_band && !g) return failp(err, HEAT_E_INVALID_ARG, "sky aniso: aperture_band without solar gains: no aperture a reads it");
+    if (an->shade_band && !sh) return failp(err, HEAT_E_INVALID_ARG, "sky aniso: shade_band without shades: no shade j reads it");
+    const double *side_band[2] = {an->front_band, an->back_band};
+    for (int side = 0; side < 2; side++)
+        for (int64_t q = 0; q < n_surfaces && side_band[side] && sky->mode; q++)
+            if ((sky->mode[q] >> side & 1) && !(side_band[side][q] >= 0.0 && std::isfinite(side_band[side][q])))
+                return failp(err, HEAT_E_INVALID_ARG, "surface %lld: %s_band = %g is negative or not finite", (long long)q, side ? "back" : "front",
+                             side_band[side][q]);
+    for (int64_t a = 0; an->aperture_band && a < g->n_apertures; a++)
+        if (!(an->aperture_band[a] >= 0.0 && std::isfinite(an->aperture_band[a])))
+            return failp(err, HEAT_E_INVALID_ARG, "aperture %lld: aperture_band = %g is negative or not finite", (long long)a, an->aperture_band[a]);
+    for (int64_t j = 0; an->shade_band && j < sh->n_shades; j++)
+        if (!(an->shade_band[j] >= 0.0 && std::isfinite(an->shade_band[j])))
+            return failp(err, HEAT_E_INVALID_ARG, "shade %lld: shade_band = %g is negative or not finite", (long long)j, an->shade_band[j]);
+    return HEAT_OK;
+}
+
 // ---- solar gains of a series (include/heat_amd.h, heat_solar_gains) ----
 int check_solar_gains(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, std::string &err) {
     if (!g) return HEAT_OK;
@@ -2909,6 +2943,13 @@ int heat_blinds_check(const heat_batch_desc *desc, int32_t n_sites, const heat_s
     heat::BlindTables t;
     heat::build_blind_tables(NS, blinds, t);
     return heat::check_blind_tables(NS, blinds, t, heat::last_error());
+}
+
+int heat_sky_aniso_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                         const heat_solar_gains *gains, const heat_shades *shades, const heat_sky_aniso *aniso) {
+    int rc = heat_shades_check(desc, n_sites, s, sky, gains, shades);
+    if (rc) return rc;
+    return heat::check_sky_aniso(desc->n_surfaces, s, sky, gains, shades, aniso, heat::last_error());
 }
 
 int heat_room_radiation_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,

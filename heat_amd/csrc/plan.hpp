@@ -197,6 +197,12 @@ int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_load
 // none. s has passed check_series. HEAT_OK or a negative heat_status with `err` set, naming "surface s".
 // any_bits (nullable): the OR of every mode byte — 0: the series launches nothing for the sky.
 int check_sky(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, std::string &err, unsigned *any_bits = nullptr);
+// The struct heat_batch_march_series_call takes: it is there, of this library's size, and names a series.
+int check_series_call(const heat_series_call *call, std::string &err);
+// The anisotropic sky of a series (heat_sky_aniso), behind check_sky, check_solar_gains and check_shades: what the bands and
+// the coefficient table need of the other terms, and every band a consumer reads.
+int check_sky_aniso(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_solar_gains *g, const heat_shades *sh,
+                    const heat_sky_aniso *an, std::string &err);
 
 // Solar gains of a series (heat_solar_gains, include/heat_amd.h). Everything heat_solar_gains_check promises about the
 // gains themselves; g == nullptr is none. s has passed check_series and sky check_sky. HEAT_OK or a negative heat_status

@@ -9,10 +9,10 @@ The reference has no counterpart: window-transmitted solar is computed in anothe
 import numpy as np
 
 from . import modeldict as mdl
-from .sky import SUN_X, SUN_Y, SUN_Z, BEAM, DIFFUSE, GROUND
+from .sky import SUN_X, SUN_Y, SUN_Z, BEAM, DIFFUSE, GROUND, circumsolar_ratio
 
 
-def transmitted(record, normal, coef, tau_diffuse, scale, shade=None):
+def transmitted(record, normal, coef, tau_diffuse, scale, shade=None, aniso=None):
     """The power (W) every aperture transmits: (Pb, Pd), beam and diffuse + ground-reflected.
     record       [..., 8]: heat_sky_record fields (sky.FIELDS) of the aperture's site, broadcast against the apertures
     normal       (x, y, z) of the outward normal of the side that sees the sky, arrays or scalars
@@ -21,6 +21,8 @@ def transmitted(record, normal, coef, tau_diffuse, scale, shade=None):
     scale        area x frame or shading factor, m2
     shade        None, or (f, fd, fg) of shaded apertures (heat_shades): the step's sunlit fraction from shading.sunlit and
                  the shade's diffuse and ground factor, broadcast like the apertures
+    aniso        None, or (circ, horiz, band) of heat_sky_aniso: the coefficient pair of the record's site at the step and the
+                 band of the aperture, broadcast like the apertures
     Returns two arrays of the broadcast shape; P = Pb + Pd is what transmitted[k][a] and ap_sum take."""
     r = np.asarray(record, dtype=np.float64)
     nx, ny, nz = (np.asarray(a, dtype=np.float64) for a in normal)
@@ -36,6 +38,26 @@ def transmitted(record, normal, coef, tau_diffuse, scale, shade=None):
             t = t * c
             t = t + coef[..., j]
         ib = r[..., BEAM] * c
+        if aniso is not None:
+            circ, horiz, band = (np.asarray(a, dtype=np.float64) for a in aniso)
+            rb = circumsolar_ratio(c, r[..., SUN_Z])
+            iso = 1.0 - circ
+            pbm = (ib * t) * scale
+            ics = (r[..., DIFFUSE] * circ) * rb
+            pcs = (ics * t) * scale
+            ps = pbm + pcs
+            dd = (r[..., DIFFUSE] * fs) * iso
+            hv = (r[..., DIFFUSE] * horiz) * band
+            dd = dd + hv
+            gg = r[..., GROUND] * fg
+            if shade is not None:
+                f, fd, fgr = (np.asarray(a, dtype=np.float64) for a in shade)
+                ps = ps * f
+                dd = dd * fd
+                gg = gg * fgr
+            pb = np.where(c > 0.0, ps, 0.0)
+            idf = dd + gg
+            return pb, (idf * tau_diffuse) * scale
         pb = np.where(c > 0.0, (ib * t) * scale, 0.0)
         if shade is not None:
             f, fd, fgr = (np.asarray(a, dtype=np.float64) for a in shade)

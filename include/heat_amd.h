@@ -1002,6 +1002,91 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
                                    heat_blinds *blinds /* nullable */, double *position /* [n_steps][n_blinds], nullable */,
                                    double *blind_incident /* [n_steps][n_blinds], nullable */, int32_t *failed_step);
 
+/*
+ * Anisotropic sky of a series: every solar term above takes the sky's diffuse radiation as isotropic, diffuse * (0.5 + 0.5 * n.z)
+ * on every plane. Hay-Davies, Reindl and Perez share one form,
+ *   D_tilt = D * [ (1 - F1) * sky_view + F1 * cos(incidence) / max(cos 85 deg, cos(zenith)) + F2 * band(plane) ],
+ * with F1 the circumsolar fraction and F2 the horizon coefficient, functions of site and step alone (clearness, brightness and
+ * zenith: transcendental work of the caller, as the sun's direction is), and band a function of the plane alone. The caller
+ * passes ONE PAIR (circ, horiz) = (F1, F2) per site and step beside the record, and one band per consumer; the device does a
+ * handful of multiplications and one division. The circumsolar part comes from the sun's direction: it is shaded by the sunlit
+ * fraction, passes a window with the beam transmittance at the sun's incidence, lands through en_beam and counts in the
+ * irradiance a blind decides on — which is why it cannot be pre-mixed into `diffuse`. The reference has no counterpart; the rule
+ * below is this library's own contract, defined against the per-call loop with the same rule written on the host
+ * (heat_amd/sky.py incident(), solar_gains.py transmitted(), blinds.py incident_on(), each with aniso=).
+ * q = coef[k * n_sites + site], the site being the one whose record the consumer reads; Z0 = 0.08715574274765817 (cos 85 deg:
+ * the literal is the contract); c, fs, fg, t, ib, scale, f, fd, fgr as the consumer has them above. Every line is ONE rounded
+ * f64 operation in the order written, no fused multiply-add; a NaN makes every comparison false:
+ *   up  = r.sun_z > 0.0
+ *   zb  = r.sun_z > Z0 ? r.sun_z : Z0
+ *   rb  = (c > 0 and up) ? c / zb : 0.0
+ *   iso = 1.0 - q.circ
+ * A sky-driven solar side (mode bit 0 / 1), band = front_band[s] / back_band[s]:
+ *   bm = c > 0 ? r.beam * c : 0.0
+ *   cs = (r.diffuse * q.circ) * rb;      sun = bm + cs
+ *   dv = (r.diffuse * fs) * iso;         hv = (r.diffuse * q.horiz) * band;    dv = dv + hv
+ *   gv = r.ground * fg
+ *   with a shade j (the effective factors where blinds act):  sun = sun * f;  dv = dv * fd;  gv = gv * fgr
+ *   v  = (sun + dv) + gv                 (then the gain, the mirror, the clamp, the absorptance: unchanged)
+ * An aperture, band = aperture_band[a]:
+ *   pbm = (ib * t) * scale
+ *   ics = (r.diffuse * q.circ) * rb;     pcs = (ics * t) * scale;              ps = pbm + pcs
+ *   with a shade:  ps = ps * f
+ *   Pb  = c > 0 ? ps : 0.0
+ *   dd  = (r.diffuse * fs) * iso;        hv = (r.diffuse * q.horiz) * band;    dd = dd + hv
+ *   gg  = r.ground * fg
+ *   with a shade:  dd = dd * fd;  gg = gg * fgr
+ *   id  = dd + gg;   Pd = (id * tau_diffuse) * scale;   P = Pb + Pd            (transmitted, ap_sum, the entries: unchanged)
+ * A blind's I is the rule of a shaded side with the shade's normal, the shade's own geometric f and constant fd, fg (as
+ * heat_blinds has them), band = shade_band[j] and q of the shade's own site.
+ * Long-wave inputs, channel-driven inputs and everything behind the raw value are untouched. With q.circ == 0 and q.horiz == 0
+ * every consumer gives the bits of the isotropic rule (the sign of a zero aside), shaded or not. The rule has no memory: a
+ * series of k steps followed by one of n - k gives the bits of the series of n; n_sub == 0 still sets every input. Weather
+ * sites are supported; sharded batches are refused, as by the series.
+ * heat_sky_aniso_check (host-only) and heat_batch_march_series_call run the same checks before any device work: aniso without
+ * sky or without sky->record, coef NULL with n_steps > 0, aperture_band without gains, shade_band without shades, a band that
+ * is negative or not finite on a consumer that reads it — "surface s" where the side's solar mode bit is set, every "aperture
+ * a", every "shade j" -> HEAT_E_INVALID_ARG. The coefficients are not checked: they are the caller's, as the transmittance
+ * polynomial is, and a NaN propagates as a NaN record field does.
+ */
+typedef struct heat_sky_coef { double circ, horiz; } heat_sky_coef;   /* F1, F2 of one site at one step; 16 bytes */
+
+typedef struct heat_sky_aniso {
+    const heat_sky_coef *coef;                 /* [n_steps][n_sites]: [k * n_sites + site] */
+    const double *front_band, *back_band;      /* [n_surfaces], nullable = 0: band of the front / back solar input */
+    const double *aperture_band;               /* [gains->n_apertures], nullable = 0 */
+    const double *shade_band;                  /* [shades->n_shades], nullable = 0: read by blinds for I */
+} heat_sky_aniso;
+
+/*
+ * One call for every term of a series: heat_batch_march_series_call takes what heat_batch_march_series_blinds takes, by name,
+ * plus aniso. Zero-initialise the struct, set size = sizeof(heat_series_call) and fill the fields the call has; every pointer
+ * but s may be NULL, and a NULL trace records none. call or call->s NULL, or a size that is not this library's
+ * sizeof(heat_series_call) -> HEAT_E_INVALID_ARG. With aniso == NULL it is heat_batch_march_series_blinds on the same arguments
+ * exactly: same launches, same bits. A refused call leaves the device state untouched.
+ */
+typedef struct heat_series_call {
+    size_t size;                               /* sizeof(heat_series_call) as the caller compiled it */
+    const heat_series *s;
+    const heat_sky *sky;
+    const heat_sky_aniso *aniso;
+    const heat_shades *shades;
+    const heat_solar_gains *gains;
+    const heat_zone_loads *l;
+    heat_air_paths *air;
+    heat_ideal_loads *il;
+    heat_series_report *r;
+    heat_room_radiation *radiation;
+    heat_ambient_drive *ambient;
+    heat_blinds *blinds;
+    double *trace, *applied, *ideal_q, *transmitted, *path_q, *sunlit, *irradiance, *ambient_t, *position, *blind_incident;
+    int32_t *failed_step;
+} heat_series_call;
+
+int heat_sky_aniso_check(const heat_batch_desc *desc, int32_t n_sites, const heat_series *s, const heat_sky *sky,
+                         const heat_solar_gains *gains, const heat_shades *shades, const heat_sky_aniso *aniso); /* host-only */
+int heat_batch_march_series_call(heat_batch *b, const heat_series_call *call);
+
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -87,6 +87,23 @@ pub struct HeatSkyRecord { pub sun_x: f64, pub sun_y: f64, pub sun_z: f64, pub b
     pub zone: *const i32, pub set_chan: *const i32, pub band: *const f64, pub enable_chan: *const i32,
     pub state: *mut u8, pub steps_closed: *mut i64, pub switches: *mut i64, pub sum_position: *mut f64,
 }
+// heat_sky_coef / heat_sky_aniso: an anisotropic sky — (F1, F2) per site and step beside the records, a band per consumer
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
+#[repr(C)] pub struct HeatSkyAniso {
+    pub coef: *const HeatSkyCoef, pub front_band: *const f64, pub back_band: *const f64,
+    pub aperture_band: *const f64, pub shade_band: *const f64,
+}
+// heat_series_call: every term of a series by name; zero it (std::mem::zeroed), set size = size_of::<HeatSeriesCall>(), fill
+#[repr(C)] pub struct HeatSeriesCall {
+    pub size: usize, pub s: *const HeatSeries, pub sky: *const HeatSky, pub aniso: *const HeatSkyAniso,
+    pub shades: *const HeatShades, pub gains: *const HeatSolarGains, pub l: *const HeatZoneLoads, pub air: *mut HeatAirPaths,
+    pub il: *mut HeatIdealLoads, pub r: *mut HeatSeriesReport, pub radiation: *mut HeatRoomRadiation,
+    pub ambient: *mut HeatAmbientDrive, pub blinds: *mut HeatBlinds,
+    pub trace: *mut f64, pub applied: *mut f64, pub ideal_q: *mut f64, pub transmitted: *mut f64, pub path_q: *mut f64,
+    pub sunlit: *mut f64, pub irradiance: *mut f64, pub ambient_t: *mut f64, pub position: *mut f64,
+    pub blind_incident: *mut f64, pub failed_step: *mut i32,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -167,6 +184,10 @@ extern "C" {
                                           radiation: *mut HeatRoomRadiation, irradiance: *mut f64, ambient: *mut HeatAmbientDrive,
                                           ambient_t: *mut f64, blinds: *mut HeatBlinds, position: *mut f64,
                                           blind_incident: *mut f64, failed_step: *mut i32) -> c_int;
+    // anisotropic sky of a series, and the entry point that takes every term of a series in one struct
+    pub fn heat_sky_aniso_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
+                                gains: *const HeatSolarGains, shades: *const HeatShades, aniso: *const HeatSkyAniso) -> c_int;
+    pub fn heat_batch_march_series_call(b: *mut HeatBatch, call: *const HeatSeriesCall) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

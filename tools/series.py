@@ -88,7 +88,15 @@ and writes profiles/series_blinds.json: ms per step of each, B - S, a series of 
 the calls are set up, the bytes a step of k_series_blinds moves, and — where the kernel trace of one B series has been taken
 (--one-series --blinds under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_blinds_kernel_stats.csv) —
 k_series_blinds per step beside the same trace's k_series_shading. No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds]
+With --aniso (heat_batch_march_series_call with an anisotropic sky, heat_sky_aniso; everything of --blinds plus Reindl's
+coefficients of the day's records and Reindl's band of every wall and shade) it alternates
+  B  the --blinds leg B through the positional entry point, aniso = None: the isotropic kernels
+  A  the same call with aniso given: the anisotropic instantiations of k_series_blinds and k_series_sky
+and writes profiles/series_aniso.json: ms per step of each, A - B, a series of ONE step of each and the per-step times once the
+calls are set up, and — where the kernel trace of one A series has been taken (--one-series --aniso under rocprofv3
+--kernel-trace --stats, a run of its own; profiles/series_aniso_kernel_stats.csv) — the kernels' own times. No time is a pass
+criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso]
   python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
@@ -107,7 +115,8 @@ IDEAL = "--ideal" in sys.argv
 SKY = "--sky" in sys.argv
 GAINS = "--gains" in sys.argv
 AIR = "--air" in sys.argv
-BLINDS = "--blinds" in sys.argv
+ANISO = "--aniso" in sys.argv
+BLINDS = "--blinds" in sys.argv or ANISO
 SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
@@ -226,18 +235,29 @@ if BLINDS:
     # state byte, three accumulators read and written; the record, the channels and the zone temperature are shared
     BLIND_BYTES = dict(k_series_blinds_per_shade=4 + 4 + 8 + 5 * 8 + 3 * 8, k_series_blinds_per_blind=4 * 4 + 6 * 8 + 1 + 3 * 16)
 
-    def leg_bl(b, w, n_sub, steps):
+    def leg_bl(b, w, n_sub, steps, aniso=None):
         b.synchronize()
         t0 = time.perf_counter()
         trace, failed, applied, modes, lit, bl = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
                                                                 sky=dict(sky_args, record=record[:steps]), shades=shade_args, sunlit=False,
                                                                 blinds=blind_args, position=False, blind_incident=False,
+                                                                aniso=None if aniso is None else dict(aniso, coef=aniso["coef"][:steps]),
                                                                 **{k: (not_driven, drives[k][1]) for k in FRONT})
         dt = time.perf_counter() - t0
         assert failed == -1 and np.all(np.isfinite(trace)) and bl["steps_closed"].any()
         # (a whole day: the sun comes and goes, controlled blinds switch; a short series may lie in the night)
         assert steps < STEPS or bl["switches"].any()
         return dt * 1e3 / steps
+if ANISO:
+    # Reindl's coefficients of the day's records and Reindl's band of every wall and shade (vertical planes); per consumer lane one
+    # 16-byte pair beside the record and one band
+    circ, horiz = skym.reindl(record[:, 0, :], 172)
+    wall_band = skym.band_reindl(sky_args["normals"])
+    aniso_args = dict(coef=np.stack([circ, horiz], axis=1)[:, None, :], front_band=wall_band, shade_band=wall_band)
+    ANISO_BYTES = dict(per_sky_driven_side=8, per_shade_with_a_blind=8, per_site_and_step=16)
+
+    def leg_an(b, w, n_sub, steps):
+        return leg_bl(b, w, n_sub, steps, aniso_args)
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
     exchange = rrm.exchange_by_area(md)
@@ -563,6 +583,29 @@ with HeatBatch(md) as b:
                   "N %.2f ms, M %.2f ms -> per step without the set-up N %.3f, M %.3f, M - N = %+.3f (%d driven sides, %d steps, median of "
                   "%d rounds)" % (n_sub, N_, M_, M_ - N_, M_ / N_, N1, M1, Ns, Ms, Ms - Ns, NB, STEPS, ROUNDS), flush=True)
             continue
+        if ANISO:
+            leg_bl(b, w, n_sub, min(STEPS, 10))  # warm-up
+            leg_an(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with blinds under an anisotropic sky: A %.3f ms per step" % leg_an(b, w, n_sub, STEPS))
+                continue
+            bl, an, bl1, an1 = [], [], [], []
+            for r in range(ROUNDS):
+                bl.append(leg_bl(b, w, n_sub, STEPS))
+                an.append(leg_an(b, w, n_sub, STEPS))
+                bl1.append(leg_bl(b, w, n_sub, 1))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                an1.append(leg_an(b, w, n_sub, 1))
+            B, A, B1, A1 = (float(np.median(v)) for v in (bl, an, bl1, an1))
+            Bs, As = (B * STEPS - B1) / (STEPS - 1), (A * STEPS - A1) / (STEPS - 1)  # per step once the call is set up
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                B_aniso_null_ms=B, A_aniso_ms=A, A_minus_B_ms=A - B, A_over_B=A / B, B_series_of_one_step_ms=B1,
+                A_series_of_one_step_ms=A1, A_minus_B_series_of_one_step_ms=A1 - B1, B_without_setup_ms=Bs, A_without_setup_ms=As,
+                A_minus_B_without_setup_ms=As - Bs, sky_driven_sides=int(S), shades=int(S), blinds=int(S), bytes=ANISO_BYTES,
+                all_rounds=dict(B=bl, A=an, B_one_step=bl1, A_one_step=an1))
+            print("n_sub %2d: B aniso NULL %.3f ms/step, A aniso %.3f -> A - B = %+.3f ms, A / B = %.4f; a series of one step: "
+                  "B %.2f ms, A %.2f ms -> per step without the set-up B %.3f, A %.3f, A - B = %+.3f (%d sides and blinds, %d steps, "
+                  "median of %d rounds)" % (n_sub, B, A, A - B, A / B, B1, A1, Bs, As, As - Bs, S, STEPS, ROUNDS), flush=True)
+            continue
         if BLINDS:
             leg_s(b, w, n_sub, min(STEPS, 10))  # warm-up
             leg_bl(b, w, n_sub, min(STEPS, 10))
@@ -824,7 +867,26 @@ if AIR and not ONE:
             {k: v["expectation_A_at_most_1_05_of_D_plus_the_kernel"] for k, v in result["legs"].items()}))
     else:
         print("no kernel trace at %s: the expectation A <= 1.05 (D + k_series_air_paths) is not evaluated" % stats)
-if BLINDS and not ONE:
+if ANISO and not ONE:
+    # the kernel trace of one A series (--one-series --aniso under rocprofv3 --kernel-trace --stats, a run of its own), where it has
+    # been taken: the anisotropic instantiations of the record's consumers, and the isotropic ones of the warm-up series beside them
+    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles")
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")), os.path.join(here, "series_aniso_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+
+        def per_step(path):
+            with open(path) as f:
+                rows = {r["Name"].split("(")[0].split("::")[-1].replace("void ", ""): r for r in csv.DictReader(f)}
+            # (the warm-up's isotropic series is in the same trace: both instantiations, each under its own name)
+            return {name: dict(us_per_step=float(r["AverageNs"]) / 1e3, calls=int(r["Calls"])) for name, r in sorted(rows.items())
+                    if name.split("<")[0] in ("k_series_blinds", "k_series_sky", "k_series_apertures", "k_series_shading")}
+        kt = per_step(stats)
+        result["kernel_trace_of_one_A_series"] = kt
+        print("kernel trace:", kt)
+    else:
+        print("no kernel trace at %s" % stats)
+if BLINDS and not ANISO and not ONE:
     # the kernel trace of one B series (--one-series --blinds under rocprofv3 --kernel-trace --stats, a run of its own), where it
     # has been taken: k_series_blinds per step and on its own bytes, beside the same trace's k_series_shading
     stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
@@ -878,7 +940,7 @@ if AMBIENT and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
