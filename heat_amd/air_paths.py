@@ -14,7 +14,7 @@ def n_paths(air):
     return 0 if not air or air.get("target") is None else len(np.atleast_1d(air["target"]))
 
 
-def apply(T, row, a0, b0, air, state):
+def apply(T, row, a0, b0, air, state, control_T=None):
     """One step of the rule. Returns (a0, b0, q); `state` ([n_paths] uint8, 0 closed / 1 open) is updated in place.
     T      the zone temperatures at the start of the step
     row    the step's channel row
@@ -22,6 +22,9 @@ def apply(T, row, a0, b0, air, state):
     air    a dict of arrays, [n_paths] each: target, source (-1: supply air at row[temp_chan]), temp_chan (optional without
            a source of -1), volume_chan, volume_gain (optional: 1), open_chan (optional / -1: uncontrolled, always open),
            sense (+1 cooling / -1 heating), band, min_delta (the three read only where controlled)
+    control_T  what a controlled path senses for e = s * (control_T[target] - set): None is T itself (today's rule); with a
+           comfort term the step's control temperatures (comfort.control_temperatures). g, dT and q keep T: the air that
+           moves is air.
     np.add.at adds unbuffered, in the order of its index array: per target zone the caller's order; closed paths add nothing.
     open = state == 1 for a controlled path after the call; an uncontrolled path is open and its state byte is left alone."""
     T = np.asarray(T, dtype=np.float64)
@@ -41,6 +44,7 @@ def apply(T, row, a0, b0, air, state):
     temp_chan, open_chan = given("temp_chan", -1, np.int64), given("open_chan", -1, np.int64)
     with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
         tt = T[target]
+        tc = tt if control_T is None else np.asarray(control_T, dtype=np.float64)[target]
         ts = np.where(source >= 0, T[np.maximum(source, 0)], row[np.maximum(temp_chan, 0)] if len(row) else np.nan)
         ctl = open_chan >= 0
         if ctl.any():
@@ -48,7 +52,7 @@ def apply(T, row, a0, b0, air, state):
             d = given("band", 0.0, np.float64) / 2.0
             min_delta = given("min_delta", 0.0, np.float64)
             setpoint = row[np.maximum(open_chan, 0)]
-            e = s * (tt - setpoint)
+            e = s * (tc - setpoint)
             g = s * (tt - ts)
             opens = ctl & (e > d) & (g > min_delta)
             closes = ctl & ~opens & (state == 1) & ((e < -d) | (g <= 0.0))

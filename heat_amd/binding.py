@@ -186,6 +186,16 @@ class SeriesCall(C.Structure):
                 ("irradiance", _dp), ("ambient_t", _dp), ("position", _dp), ("blind_incident", _dp), ("failed_step", _i32p)]
 
 
+class Comfort(C.Structure):
+    """heat_comfort (include/heat_amd.h): operative-temperature sensors of a series, their limits and accumulators"""
+    _fields_ = [("n_sensors", C.c_int64), ("zone", _i32p), ("air_weight", _dp), ("control", C.POINTER(C.c_uint8)),
+                ("n_entries", C.c_int64), ("en_sensor", _i32p), ("en_surface", _i64p), ("en_side", C.POINTER(C.c_uint8)),
+                ("en_weight", _dp), ("occ_chan", _i32p), ("lo_chan", _i32p), ("hi_chan", _i32p), ("resume", C.c_int32),
+                ("step_base", C.c_int64), ("n_occupied", _i64p), ("sum_operative", _dp), ("min_operative", _dp), ("step_min", _i64p),
+                ("max_operative", _dp), ("step_max", _i64p), ("n_below", _i64p), ("deg_below", _dp), ("n_above", _i64p),
+                ("deg_above", _dp), ("max_above", _dp), ("step_max_above", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -262,6 +272,8 @@ SYMBOLS = [
     ("heat_sky_aniso_check", C.c_int, [C.POINTER(Desc), C.c_int32, C.POINTER(Series), C.POINTER(Sky), C.POINTER(SolarGains),
                                        C.POINTER(Shades), C.POINTER(SkyAniso)]),
     ("heat_batch_march_series_call", C.c_int, [_H, C.POINTER(SeriesCall)]),
+    ("heat_comfort_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(Comfort)]),
+    ("heat_batch_march_series_comfort", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -413,7 +425,7 @@ def make_desc(md):
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
-                     "heat_blinds_check", "heat_sky_aniso_check",
+                     "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1325,6 +1337,78 @@ def sky_aniso_check(md, aniso, sky=None, gains=None, shades=None, n_sites=1, lib
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+COMFORT_STATS = ("n_occupied", "sum_operative", "min_operative", "step_min", "max_operative", "step_max", "n_below", "deg_below",
+                 "n_above", "deg_above", "max_above", "step_max_above")
+_COMFORT_INT = ("n_occupied", "step_min", "step_max", "n_below", "n_above", "step_max_above")
+_COMFORT_SENSOR = (("zone", np.int32, True), ("air_weight", np.float64, False), ("control", np.uint8, False), ("occ_chan", np.int32, False),
+                   ("lo_chan", np.int32, False), ("hi_chan", np.int32, False))
+_COMFORT_ENTRY = (("en_sensor", np.int32), ("en_surface", np.int64), ("en_side", np.uint8), ("en_weight", np.float64))
+
+
+def make_comfort(zone=(), air_weight=None, control=None, en_sensor=(), en_surface=(), en_side=(), en_weight=(), occ_chan=None,
+                 lo_chan=None, hi_chan=None, stats=COMFORT_STATS, resume=None, step_base=0):
+    """Builds a heat_comfort. Returns (comfort, keepalive); the march updates the accumulators of keepalive in place.
+    zone             [n_sensors] the zone whose air the sensor stands in
+    air_weight       [n_sensors] the share of the air temperature in the operative temperature, in [0, 1]; None: 0.5
+    control          [n_sensors] 1: the sensor is the control temperature of its zone (at most one per zone); None: none
+    en_sensor, en_surface, en_side, en_weight   [n_entries] the faces a sensor sees: its number, the surface, 0 first / 1 last
+                     node, the weight (comfort.by_area makes them sum to 1 per sensor); in any order
+    occ_chan, lo_chan, hi_chan   [n_sensors] occupied where row[chan] > 0 / the band's limits, -1 or None: always / no limit
+    stats            names out of COMFORT_STATS: which accumulators are maintained (default: all)
+    resume           a dict of arrays a previous series returned: the accumulators start from them
+    step_base        the number the first step of this series has in step_min, step_max, step_max_above
+    (comfort.operative, control_temperatures and accumulate are the rule in numpy and take the same dict)"""
+    given = dict(zone=zone, air_weight=air_weight, control=control, occ_chan=occ_chan, lo_chan=lo_chan, hi_chan=hi_chan,
+                 en_sensor=en_sensor, en_surface=en_surface, en_side=en_side, en_weight=en_weight)
+    unknown = set(stats or ()) - set(COMFORT_STATS)
+    if unknown:
+        raise ValueError("comfort: unknown stats %s (known: %s)" % (sorted(unknown), ", ".join(COMFORT_STATS)))
+    cf = Comfort()
+    keep = {}
+    n = len(np.asarray(zone if zone is not None else ()).reshape(-1))
+    ne = len(np.asarray(en_sensor if en_sensor is not None else ()).reshape(-1))
+    cf.n_sensors, cf.n_entries, cf.resume, cf.step_base = n, ne, 0 if resume is None else 1, int(step_base)
+    for name, dtype, needed in _COMFORT_SENSOR:
+        if given[name] is None and not needed:
+            continue
+        v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+        if v.shape != (n,):
+            raise ValueError("comfort %s: %s for %d sensors" % (name, v.shape, n))
+        keep[name] = v
+        setattr(cf, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    for name, dtype in _COMFORT_ENTRY:
+        v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+        if v.shape != (ne,):
+            raise ValueError("comfort %s: %s for %d entries" % (name, v.shape, ne))
+        keep[name] = v
+        setattr(cf, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if ne else None)
+    for name in (stats or ()):
+        dtype = np.int64 if name in _COMFORT_INT else np.float64
+        if resume is not None:
+            if name not in resume:
+                raise ValueError("comfort resume: %s is missing" % name)
+            a = np.array(resume[name], dtype=dtype).reshape(-1)  # (a copy: the march writes it)
+            if len(a) != n:
+                raise ValueError("comfort resume: %s of %d values for %d sensors" % (name, len(a), n))
+        else:
+            a = np.zeros(n, dtype)  # (the library initialises on the device)
+        keep[name] = a
+        setattr(cf, name, a.ctypes.data_as(_i64p if dtype == np.int64 else _dp))
+    return cf, keep
+
+
+def comfort_check(md, comfort, lib=None, **series):
+    """heat_comfort_check: everything about the comfort term of a series that needs no device (series arguments as
+    HeatBatch.march_series; comfort: the arguments of make_comfort, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    cf, ckeep = make_comfort(**comfort) if comfort is not None else (None, None)
+    rc = L.heat_comfort_check(C.byref(desc), C.byref(s), C.byref(cf) if cf is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1445,7 +1529,7 @@ class HeatBatch:
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
-                     blinds=None, position=True, blind_incident=True, aniso=None, **series):
+                     blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1498,7 +1582,13 @@ class HeatBatch:
         shade_band): an anisotropic sky — every sky-driven solar side, aperture and blind takes the diffuse radiation by the
         caller's circumsolar and horizon coefficients (heat_sky_aniso). The call then goes through
         heat_batch_march_series_call, the entry point that takes every term in one struct (an empty dict: that entry point
-        without an anisotropic sky). Returns what the same call without aniso returns: anisotropy has no output of its own."""
+        without an anisotropic sky). Returns what the same call without aniso returns: anisotropy has no output of its own.
+        comfort (a dict of make_comfort's arguments; an empty dict: no sensor): heat_batch_march_series_comfort — operative
+        temperatures of rooms from the face and zone temperatures the device holds at the start of every step, accumulated
+        against limits that are channels and, where a sensor has its control bit, sensed by thermostats, air paths and blinds in
+        place of the zone temperature. Returns what the same call without comfort returns plus one dict: operative and mrt
+        [n_steps, n_sensors] (empty with operative=False / mrt=False) and of COMFORT_STATS those in stats (pass them as
+        comfort["resume"] to the next series) — one more element of the tuple, or the key "comfort" of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -1508,7 +1598,8 @@ class HeatBatch:
             given["sky"] = _sky_for_gains(sky, self._normals, self.n_surfaces)
         return self._march_series(weather, n_sub, series, given, dict(trace=trace, applied=applied, path_q=path_q, sunlit=sunlit,
                                                                       irradiance=irradiance, ambient_t=ambient_t, position=position,
-                                                                      blind_incident=blind_incident), aniso=aniso)
+                                                                      blind_incident=blind_incident, operative=operative, mrt=mrt),
+                                  aniso=aniso, comfort=comfort)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -1534,9 +1625,10 @@ class HeatBatch:
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
-    def _march_series(self, weather, n_sub, series, given, want, aniso=None):
+    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
-        whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None."""
+        whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None; comfort: the dict of make_comfort's
+        arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1588,7 +1680,7 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        if aniso is not None:
+        if aniso is not None or comfort is not None:
             # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
             # that are recorded, and the anisotropic sky.
             call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
@@ -1604,7 +1696,14 @@ class HeatBatch:
             for name, a in rows.items():
                 if a.size:
                     setattr(call, name, a.ctypes.data_as(_dp))
-            rc = self._L.heat_batch_march_series_call(self._h, C.byref(call))
+            if comfort is not None:
+                cf, ckeep = make_comfort(**comfort)
+                top_rows = np.zeros((s.n_steps if want["operative"] else 0, cf.n_sensors))
+                mrt_rows = np.zeros((s.n_steps if want["mrt"] else 0, cf.n_sensors))
+                rc = self._L.heat_batch_march_series_comfort(self._h, C.byref(call), C.byref(cf), top_rows.ctypes.data_as(_dp) if top_rows.size else None,
+                                                             mrt_rows.ctypes.data_as(_dp) if mrt_rows.size else None)
+            else:
+                rc = self._L.heat_batch_march_series_call(self._h, C.byref(call))
         else:
             rc = getattr(self._L, symbol)(self._h, C.byref(s), *args, C.byref(failed))
         if rc != 0:
@@ -1632,6 +1731,8 @@ class HeatBatch:
         if given["blinds"] is not None:
             out += [("blinds", dict(position=rows["position"], incident=rows["blind_incident"],
                                     **{k: kept["blinds"][k] for k in ("state",) + BLIND_STATS if k in kept["blinds"]}))]
+        if comfort is not None:
+            out += [("comfort", dict(operative=top_rows, mrt=mrt_rows, **{k: ckeep[k] for k in COMFORT_STATS if k in ckeep}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

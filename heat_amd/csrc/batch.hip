@@ -1761,8 +1761,67 @@ struct AnisoTerm {
 };
 static_assert(sizeof(SkyCoef) == sizeof(heat_sky_coef) && sizeof(heat_sky_coef) == 16, "SkyCoef mirrors heat_sky_coef");
 
-// What heat_batch_march_series_call takes (the eleven positional entry points fill what they have); filled by field name.
-// no_trace_ok: a NULL trace records none.
+// Comfort (heat_comfort): the entries as CSR over the sensors with their face nodes and weights (plan.hpp, ComfortTables), the
+// sensors' rows, the step's operative temperatures, the accumulators (uploaded on resume, else started on the device) and the
+// operative / mrt rows; with a control sensor the control sensor of every zone and the step's control temperatures. Nothing of
+// it exists on the device without sensors.
+struct ComfortTerm {
+    heat_comfort *cf = nullptr;
+    int64_t NF = 0;
+    ComfortTables cft;
+    DevBuf<int32_t> off, i32, ctl;                    // [NF + 1], [kComfortI32Rows][NF], [Z]
+    DevBuf<uint32_t> face;                            // [NE]
+    DevBuf<double> weight, air_weight, top, control_T, operative, mrt;  // [NE], [NF], [NF], [Z], [n_steps][NF] twice
+    Acc<double> f64[6];   // sum_operative, min_operative, max_operative, deg_below, deg_above, max_above
+    Acc<int64_t> i64[6];  // n_occupied, step_min, step_max, n_below, n_above, step_max_above
+    SeriesComfort view{};
+    void prepare(const heat_batch *b, heat_comfort *cf_) {
+        cf = cf_;
+        NF = cf ? cf->n_sensors : 0;
+        if (NF == 0) return;
+        const double inf = std::numeric_limits<double>::infinity();
+        build_comfort_tables(b->n_zones, cf, b->h_node_tile_base.data(), b->h_node_geom.data(), b->h_first_slot.data(), b->h_node_count.data(), cft);
+        f64[0].bind(cf->sum_operative, 0.0, &view.sum_operative), f64[1].bind(cf->min_operative, inf, &view.min_operative);
+        f64[2].bind(cf->max_operative, -inf, &view.max_operative), f64[3].bind(cf->deg_below, 0.0, &view.deg_below);
+        f64[4].bind(cf->deg_above, 0.0, &view.deg_above), f64[5].bind(cf->max_above, -inf, &view.max_above);
+        i64[0].bind(cf->n_occupied, 0, &view.n_occupied), i64[1].bind(cf->step_min, -1, &view.step_min);
+        i64[2].bind(cf->step_max, -1, &view.step_max), i64[3].bind(cf->n_below, 0, &view.n_below);
+        i64[4].bind(cf->n_above, 0, &view.n_above), i64[5].bind(cf->step_max_above, -1, &view.step_max_above);
+    }
+    int upload(const heat_batch *b, const double *host_operative, const double *host_mrt, int n_steps) {
+        if (NF == 0) return HEAT_OK;
+        const bool resume = cf->resume != 0;
+        SERIES_TRY(series_upload(off, cft.off, "comfort tables"));
+        SERIES_TRY(series_upload(face, cft.face, "comfort tables"));
+        SERIES_TRY(series_upload(weight, cft.weight, "comfort tables"));
+        SERIES_TRY(series_upload(i32, cft.i32, "comfort tables"));
+        SERIES_TRY(series_upload(air_weight, cft.air_weight, "comfort tables"));
+        SERIES_TRY(series_alloc(top, (size_t)NF, "operative temperatures"));
+        if (cft.any_control) {
+            SERIES_TRY(series_upload(ctl, cft.ctl_sensor, "comfort tables"));
+            SERIES_TRY(series_alloc(control_T, (size_t)b->n_zones, "control temperatures"));
+        }
+        if (host_operative) SERIES_TRY(series_alloc(operative, (size_t)n_steps * NF, "operative temperatures"));
+        if (host_mrt) SERIES_TRY(series_alloc(mrt, (size_t)n_steps * NF, "mean radiant temperatures"));
+        for (auto &a : f64) SERIES_TRY(a.stage((size_t)NF, resume, "comfort accumulators"));
+        for (auto &a : i64) SERIES_TRY(a.stage((size_t)NF, resume, "comfort accumulators"));
+        view.n_sensors = (int)NF, view.off = off.p, view.face = face.p, view.weight = weight.p;
+        view.zone = i32.p + CF_ZONE * NF, view.occ_chan = i32.p + CF_OCC_CHAN * NF, view.lo_chan = i32.p + CF_LO_CHAN * NF;
+        view.hi_chan = i32.p + CF_HI_CHAN * NF, view.air_weight = air_weight.p, view.top = top.p;
+        return HEAT_OK;
+    }
+    hipError_t start(hipStream_t st) {
+        return NF > 0 && cf->resume == 0 ? for_each_acc(i64, &Acc<int64_t>::start, st, for_each_acc(f64, &Acc<double>::start, st)) : hipSuccess;
+    }
+    hipError_t fetch(double *host_operative, double *host_mrt, hipStream_t st) {
+        if (NF == 0) return hipSuccess;
+        const hipError_t e = series_fetch(host_mrt, mrt, st, series_fetch(host_operative, operative, st));
+        return for_each_acc(i64, &Acc<int64_t>::fetch, st, for_each_acc(f64, &Acc<double>::fetch, st, e));
+    }
+};
+
+// What heat_batch_march_series_call takes (the eleven positional entry points fill what they have) and, beside it, the comfort
+// term and its two arrays of rows (heat_batch_march_series_comfort); filled by field name. no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
@@ -1780,6 +1839,8 @@ struct SeriesCall {
     double *ambient_t = nullptr;
     heat_blinds *blinds = nullptr;
     double *position = nullptr, *blind_incident = nullptr;
+    heat_comfort *comfort = nullptr;
+    double *operative = nullptr, *mrt = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -2778,6 +2839,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = check_air_paths(b->n_zones, s->n_channels, c.air, heat::last_error()))) return rc;
     if ((rc = check_room_radiation(b->n_surf, s, c.sky, c.radiation, heat::last_error()))) return rc;
     if ((rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, c.ambient, heat::last_error()))) return rc;
+    if ((rc = check_comfort(b->n_surf, b->n_zones, s, c.comfort, heat::last_error()))) return rc;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -2804,6 +2866,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     DevBuf<double> d_zab, d_channel;
     InputsTerm in; ProbesTerm probes; LoadsTerm loads; ReportTerm report; IdealTerm ideal;
     ShadesTerm shades; BlindsTerm blinds; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air; AnisoTerm aniso;
+    ComfortTerm comfort;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
@@ -2817,8 +2880,9 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     loads.prepare(b, c.l);
     ideal.prepare(c.il, load_of_zone);
     air.prepare(b, c.air);
+    comfort.prepare(b, c.comfort);
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
-    const int64_t NL = blinds.NL;
+    const int64_t NL = blinds.NL, NF = comfort.NF;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -2836,11 +2900,15 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = radiation.upload(c.irradiance, n_steps, in))) return rc;
     if ((rc = ambient.upload(c.ambient, c.ambient_t, n_steps))) return rc;
     if ((rc = air.upload(b, c.path_q, n_steps))) return rc;
+    if ((rc = comfort.upload(b, c.operative, c.mrt, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
     HIP_TRY(report.start(b->stream));
     HIP_TRY(ideal.start(b->stream));
+    HIP_TRY(comfort.start(b->stream));
+    // what the thermostats, the air paths' e and the blinds sense: the zone temperatures, or with a control sensor the step's Tc
+    const double *control_T = comfort.control_T.p ? comfort.control_T.p : b->d_zone_T.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    // ---- the steps, enqueued without waiting: head -> zone loads -> thermostat statistics -> air paths -> ambient drive ->
+    // ---- the steps, enqueued without waiting: head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> ambient drive ->
     // driven inputs -> shades -> blinds -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
         const double *channel = row(d_channel, k, NC);
@@ -2849,18 +2917,23 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
         // (the powers of the step: a row of the applied buffer, or one row of scratch where the caller takes none)
         double *applied = loads.applied.p ? row(loads.applied, k, NT) : report.applied_row.p;
         launch_begin_march(row(d_w, k, (int64_t)n_rec), b->d_weather.p, n_sub, (int)n_rec, row(d_zab, std::min(k, zrows - 1), 2 * Z), b->d_zone_a0.p, b->d_zone_b0.p, (int)Z, b->d_step.p, b->stream);
+        if (NF > 0) {
+            launch_series_comfort(comfort.view, channel, b->d_T.p, b->d_zone_T.p, row(comfort.operative, k, NF), row(comfort.mrt, k, NF),
+                                  c.comfort->step_base + k, b->stream);
+            if (comfort.control_T.p) launch_series_control_T((int)Z, comfort.ctl.p, comfort.top.p, b->d_zone_T.p, comfort.control_T.p, b->stream);
+        }
         if (loads.on)
-            launch_series_zone_loads((int)Z, loads.view, channel, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p, applied, b->d_flags.p, b->stream);
+            launch_series_zone_loads((int)Z, loads.view, channel, control_T, b->d_zone_a0.p, b->d_zone_b0.p, applied, b->d_flags.p, b->stream);
         if (report.th_stats) launch_series_th_stats((int)NT, report.th, loads.mode.p, applied, b->stream);
         if (NP > 0)
-            launch_series_air_paths((int)Z, air.view, channel, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p, row(air.path_q, k, NP), b->d_flags.p,
+            launch_series_air_paths((int)Z, air.view, channel, b->d_zone_T.p, control_T, b->d_zone_a0.p, b->d_zone_b0.p, row(air.path_q, k, NP), b->d_flags.p,
                                     b->stream);
         if (NB > 0) launch_series_ambient(ambient.view, channel, b->d_zone_T.p, b->d_side_const.p, row(ambient.t, k, NB), b->stream);
         if (in.driven)
             launch_series_inputs((int)S, channel, in.view, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
         if (NS > 0) launch_series_shading(record, shades.view, row(shades.sunlit, k, NS), b->stream);
         if (NL > 0)
-            launch_series_blinds(record, blinds.view, channel, b->d_zone_T.p, row(blinds.position, k, NL), row(blinds.incident, k, NL), coef,
+            launch_series_blinds(record, blinds.view, channel, control_T, row(blinds.position, k, NL), row(blinds.incident, k, NL), coef,
                                  aniso.shade.p, b->stream);
         if (sky.bits) launch_series_sky((int)S, record, sky.view, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, coef, aniso.side.p, b->stream);
         if (NA > 0) {
@@ -2902,6 +2975,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(blinds.fetch(c.position, c.blind_incident, b->stream));
     HIP_TRY(radiation.fetch(c.irradiance, b->stream));
     HIP_TRY(ambient.fetch(c.ambient_t, b->stream));
+    HIP_TRY(comfort.fetch(c.operative, c.mrt, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -3005,14 +3079,21 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
     return march_series_impl(b, c);
 }
 
-int heat_batch_march_series_call(heat_batch *b, const heat_series_call *call) {
+// heat_batch_march_series_call and heat_batch_march_series_comfort: the struct's fields by name, then the comfort term.
+static int march_series_call(heat_batch *b, const heat_series_call *call, heat_comfort *comfort, double *operative, double *mrt) {
     if (const int rc = check_series_call(call, heat::last_error())) return rc;  // (a struct of another size is not read further)
-    SeriesCall c; c.s = call->s, c.sky = call->sky, c.aniso = call->aniso, c.shades = call->shades, c.gains = call->gains, c.l = call->l;
+    SeriesCall c; c.comfort = comfort, c.operative = operative, c.mrt = mrt; c.s = call->s, c.sky = call->sky, c.aniso = call->aniso, c.shades = call->shades, c.gains = call->gains, c.l = call->l;
     c.air = call->air, c.il = call->il, c.r = call->r, c.radiation = call->radiation, c.ambient = call->ambient, c.blinds = call->blinds;
     c.trace = call->trace, c.applied = call->applied, c.ideal_q = call->ideal_q, c.transmitted = call->transmitted, c.path_q = call->path_q;
     c.sunlit = call->sunlit, c.irradiance = call->irradiance, c.ambient_t = call->ambient_t, c.position = call->position;
     c.blind_incident = call->blind_incident, c.failed_step = call->failed_step, c.no_trace_ok = true;
     return march_series_impl(b, c);
+}
+
+int heat_batch_march_series_call(heat_batch *b, const heat_series_call *call) { return march_series_call(b, call, nullptr, nullptr, nullptr); }
+
+int heat_batch_march_series_comfort(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt) {
+    return march_series_call(b, call, c, operative, mrt);
 }
 
 // The ambient temperature of the listed sides from the next march on: k_series_ambient with the temperatures as its row

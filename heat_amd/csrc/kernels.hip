@@ -2880,9 +2880,13 @@ k_series_th_stats(int n, SeriesThStatsDev t, const uint8_t *__restrict__ mode, c
 // Every product and sum is one rounded operation in the header's order, the air properties written out as in
 // k_series_zone_loads (same expressions, same grouping): the host applying the rule between march calls reproduces the bits.
 // A NaN a0 / b0 is reported as the zone's failure, as the zone loads report it.
+// control_T is what a controlled path senses for e alone: zone_T itself (the same pointer: the same bits as ever), or the
+// step's control temperatures where a comfort sensor controls a zone (heat_comfort). The air that moves is air: g, dT and q
+// keep zone_T.
 __global__ void __launch_bounds__(256)
 k_series_air_paths(int n_zones, AirPathsDev ap, const double *__restrict__ row, const double *__restrict__ zone_T,
-                   double *__restrict__ a0, double *__restrict__ b0, double *__restrict__ q_row, int *__restrict__ flags) {
+                   const double *__restrict__ control_T, double *__restrict__ a0, double *__restrict__ b0, double *__restrict__ q_row,
+                   int *__restrict__ flags) {
 #pragma clang fp contract(off)
     const int z = blockIdx.x * blockDim.x + threadIdx.x;
     if (z >= n_zones) return;
@@ -2898,7 +2902,7 @@ k_series_air_paths(int n_zones, AirPathsDev ap, const double *__restrict__ row, 
         if (oc >= 0) {
             const double set = row[oc], d = ap.half_band[i], s = ap.sense[i];
             const int before = ap.state[orig];
-            const double e = s * (tt - set);
+            const double e = s * (control_T[z] - set);
             const double g = s * (tt - ts);
             int now = before;
             if (e > d && g > ap.min_delta[i]) now = 1;
@@ -2928,6 +2932,95 @@ k_series_air_paths(int n_zones, AirPathsDev ap, const double *__restrict__ row, 
     a0[z] = a;
     b0[z] = b;
     if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
+}
+
+// k_series_comfort — the operative temperature of every sensor in one step (heat_comfort, include/heat_amd.h), behind the
+// step's head and before k_series_zone_loads: one lane per SENSOR. A lane walks its CSR range of entries (sorted by sensor,
+// the caller's order kept inside a sensor) and gathers each face node straight from T: a scattered 8-byte load per entry,
+// over entries whose (face, weight) pairs neighbouring lanes read from neighbouring ranges. A face usually belongs to one
+// sensor, so a compact emitter list as in k_series_emission would buy nothing. The sum is the lane's own sequential chain in
+// the caller's order — which a reduction over lanes would not give. Nothing on the step's head writes T or zone_T: every
+// temperature is what the step before left. The header's rule, every line one rounded operation in the order written, hence
+// no contraction; a NaN makes every comparison false. A sensor is one lane: its element of `top`, of the two rows and of
+// every accumulator has one writer. Which outputs exist is decided by nullable pointers in the kernel argument:
+// wave-uniform branches, an array nobody takes is neither read nor written. No atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_comfort(SeriesComfort cf, const double *__restrict__ row, const double *__restrict__ T, const double *__restrict__ zone_T,
+                 double *__restrict__ operative_row, double *__restrict__ mrt_row, int64_t step) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cf.n_sensors) return;
+    const int j0 = cf.off[i], j1 = cf.off[i + 1];
+    double r = 0.0;
+    int j = j0;
+    // eight entries at a time: the gathers of a batch are in flight together (a long sensor would otherwise wait out one
+    // memory latency per entry); the products are the same rounded operations and the sum keeps the caller's order
+    for (; j + 8 <= j1; j += 8) {
+        double x[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) x[u] = cf.weight[j + u] * T[cf.face[j + u]];
+#pragma unroll
+        for (int u = 0; u < 8; u++) r = r + x[u];
+    }
+    for (; j < j1; j++) {
+        const double x = cf.weight[j] * T[cf.face[j]];
+        r = r + x;
+    }
+    const double a = cf.air_weight[i];
+    const double xa = a * zone_T[cf.zone[i]];
+    const double b = 1.0 - a;
+    const double xr = b * r;
+    const double top = xa + xr;
+    cf.top[i] = top;
+    if (mrt_row != nullptr) mrt_row[i] = r;
+    if (operative_row != nullptr) operative_row[i] = top;
+    const int oc = cf.occ_chan[i];
+    if (!(oc < 0 || row[oc] > 0.0)) return;
+    if (cf.n_occupied != nullptr) cf.n_occupied[i] = cf.n_occupied[i] + 1;
+    if (cf.sum_operative != nullptr) cf.sum_operative[i] = cf.sum_operative[i] + top;
+    if (cf.min_operative != nullptr && top < cf.min_operative[i]) {
+        cf.min_operative[i] = top;
+        if (cf.step_min != nullptr) cf.step_min[i] = step;
+    }
+    if (cf.max_operative != nullptr && top > cf.max_operative[i]) {
+        cf.max_operative[i] = top;
+        if (cf.step_max != nullptr) cf.step_max[i] = step;
+    }
+    const int lc = cf.lo_chan[i], hc = cf.hi_chan[i];
+    if (lc >= 0) {
+        const double lo = row[lc];
+        if (top < lo) {
+            if (cf.n_below != nullptr) cf.n_below[i] = cf.n_below[i] + 1;
+            const double d = lo - top;
+            if (cf.deg_below != nullptr) cf.deg_below[i] = cf.deg_below[i] + d;
+        }
+    }
+    if (hc >= 0) {
+        const double hi = row[hc];
+        if (top > hi) {
+            if (cf.n_above != nullptr) cf.n_above[i] = cf.n_above[i] + 1;
+            const double d = top - hi;
+            if (cf.deg_above != nullptr) cf.deg_above[i] = cf.deg_above[i] + d;
+            if (cf.max_above != nullptr && d > cf.max_above[i]) {
+                cf.max_above[i] = d;
+                if (cf.step_max_above != nullptr) cf.step_max_above[i] = step;
+            }
+        }
+    }
+}
+
+// k_series_control_T — the control temperature of every zone in one step (heat_comfort), behind k_series_comfort and only
+// when a sensor controls a zone: one lane per zone copies the operative temperature of the zone's control sensor (a gather
+// from the step's `top`), or the zone's own temperature where it has none. The thermostats, the air paths' e and the blinds
+// of the step read this array in place of zone_T.
+__global__ void __launch_bounds__(256)
+k_series_control_T(int n_zones, const int32_t *__restrict__ ctl_sensor, const double *__restrict__ top, const double *__restrict__ zone_T,
+                   double *__restrict__ control_T) {
+#pragma clang fp contract(off)
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= n_zones) return;
+    const int i = ctl_sensor[z];
+    control_T[z] = i >= 0 ? top[i] : zone_T[z];
 }
 
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
@@ -3395,10 +3488,23 @@ void launch_series_th_stats(int n_thermostats, const SeriesThStatsDev &t, const 
     hipLaunchKernelGGL(k_series_th_stats, dim3((n_thermostats + 255) / 256), dim3(256), 0, st, n_thermostats, t, mode, applied_row);
 }
 
-void launch_series_air_paths(int n_zones, const AirPathsDev &ap, const double *row, const double *zone_T, double *a0, double *b0,
-                             double *q_row, int *flags, hipStream_t st) {
+void launch_series_air_paths(int n_zones, const AirPathsDev &ap, const double *row, const double *zone_T, const double *control_T,
+                             double *a0, double *b0, double *q_row, int *flags, hipStream_t st) {
     if (n_zones <= 0) return;
-    hipLaunchKernelGGL(k_series_air_paths, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, ap, row, zone_T, a0, b0, q_row, flags);
+    hipLaunchKernelGGL(k_series_air_paths, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, ap, row, zone_T, control_T, a0, b0, q_row,
+                       flags);
+}
+
+void launch_series_comfort(const SeriesComfort &cf, const double *row, const double *T, const double *zone_T, double *operative_row,
+                           double *mrt_row, int64_t step, hipStream_t st) {
+    if (cf.n_sensors <= 0) return;
+    hipLaunchKernelGGL(k_series_comfort, dim3((cf.n_sensors + 255) / 256), dim3(256), 0, st, cf, row, T, zone_T, operative_row, mrt_row, step);
+}
+
+void launch_series_control_T(int n_zones, const int32_t *ctl_sensor, const double *top, const double *zone_T, double *control_T,
+                             hipStream_t st) {
+    if (n_zones <= 0) return;
+    hipLaunchKernelGGL(k_series_control_T, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, ctl_sensor, top, zone_T, control_T);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

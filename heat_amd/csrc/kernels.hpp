@@ -279,9 +279,32 @@ struct AirPathsDev {
     int64_t *steps_open, *switches;
 };
 // row: the step's row of the channel table; q_row: the step's row of path_q (caller's order), or nullptr; flags: the batch's
-// failure flags (a path that makes a zone's a0 / b0 NaN is reported as that zone's failure)
-void launch_series_air_paths(int n_zones, const AirPathsDev &ap, const double *row, const double *zone_T, double *a0, double *b0,
-                             double *q_row, int *flags, hipStream_t st);
+// failure flags (a path that makes a zone's a0 / b0 NaN is reported as that zone's failure); control_T: what a controlled
+// path senses for e — zone_T itself, or the step's control temperatures (heat_comfort); the air that moves stays zone_T
+void launch_series_air_paths(int n_zones, const AirPathsDev &ap, const double *row, const double *zone_T, const double *control_T,
+                             double *a0, double *b0, double *q_row, int *flags, hipStream_t st);
+// Comfort of a series step (heat_comfort, include/heat_amd.h; tables: plan.hpp, ComfortTables): launched behind the step's
+// head and before launch_series_zone_loads, only when there are sensors. launch_series_comfort — one lane per sensor — walks
+// the sensor's CSR range of entries, gathers each face node from T, forms the mean radiant and the operative temperature,
+// stores them into `top` (always) and the step's rows (where asked) and updates the accumulators that exist.
+// launch_series_control_T — one lane per zone, only with a control sensor — writes control_T[z] = top[ctl_sensor[z]], or
+// zone_T[z] where the zone has none: what the thermostats, the air paths' e and the blinds then read in place of zone_T.
+struct SeriesComfort {
+    int n_sensors;
+    const int32_t *off;        // [n_sensors + 1]
+    const uint32_t *face;      // [n_entries]: index into T
+    const double *weight;      // [n_entries]
+    const int32_t *zone, *occ_chan, *lo_chan, *hi_chan;  // [n_sensors] each; channels -1: none
+    const double *air_weight;  // [n_sensors]
+    double *top;               // [n_sensors]: the step's operative temperatures
+    int64_t *n_occupied, *step_min, *step_max, *n_below, *n_above, *step_max_above;  // [n_sensors] each, nullptr: not maintained
+    double *sum_operative, *min_operative, *max_operative, *deg_below, *deg_above, *max_above;
+};
+// row: the step's row of the channel table; operative_row / mrt_row: the step's rows, [n_sensors], or nullptr; step: K
+void launch_series_comfort(const SeriesComfort &cf, const double *row, const double *T, const double *zone_T, double *operative_row,
+                           double *mrt_row, int64_t step, hipStream_t st);
+void launch_series_control_T(int n_zones, const int32_t *ctl_sensor, const double *top, const double *zone_T, double *control_T,
+                             hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Per step: launch_series_ideal_begin (behind the zone loads)

@@ -2318,6 +2318,133 @@ int check_blind_tables(int64_t n_shades, const heat_blinds *bl, const BlindTable
     return HEAT_OK;
 }
 
+// ---- comfort of a series (include/heat_amd.h, heat_comfort) ----
+int check_comfort(int64_t n_surfaces, int64_t n_zones, const heat_series *s, const heat_comfort *c, std::string &err) {
+    if (!c) return HEAT_OK;
+    const int64_t N = c->n_sensors, E = c->n_entries;
+    if (N < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of comfort sensors (n_sensors %lld): no comfort sensor i", (long long)N);
+    if (E < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of comfort entries (n_entries %lld): no comfort entry j", (long long)E);
+    // (the tables number sensors and entries with 32 bits)
+    if (N > INT32_MAX || E > INT32_MAX)
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 comfort sensors i or comfort entries j (n_sensors %lld, n_entries %lld)",
+                     (long long)N, (long long)E);
+    if (N == 0) return HEAT_OK;  // (no sensor: the term is absent, whatever its entry list holds)
+    if (!c->zone) return failp(err, HEAT_E_INVALID_ARG, "comfort sensor 0: zone is NULL (n_sensors %lld)", (long long)N);
+    if ((c->step_min && !c->min_operative) || (c->step_max && !c->max_operative) || (c->step_max_above && !c->max_above))
+        return failp(err, HEAT_E_INVALID_ARG, "comfort sensor 0: %s without %s: a step array records where its extremum was taken",
+                     c->step_min && !c->min_operative ? "step_min" : (c->step_max && !c->max_operative ? "step_max" : "step_max_above"),
+                     c->step_min && !c->min_operative ? "min_operative" : (c->step_max && !c->max_operative ? "max_operative" : "max_above"));
+    const int32_t NC = s->n_channels;
+    std::vector<uint8_t> controlled((size_t)std::max<int64_t>(n_zones, 0), 0);
+    const int32_t *const chans[3] = {c->occ_chan, c->lo_chan, c->hi_chan};
+    static const char *const chan_name[3] = {"occupancy", "lower limit", "upper limit"};
+    for (int64_t i = 0; i < N; i++) {
+        const int32_t z = c->zone[i];
+        if (c->air_weight && !(std::isfinite(c->air_weight[i]) && c->air_weight[i] >= 0.0 && c->air_weight[i] <= 1.0))
+            return failp(err, HEAT_E_INVALID_ARG, "comfort sensor %lld: air_weight = %g is not finite or outside [0, 1]", (long long)i, c->air_weight[i]);
+        if (c->control && c->control[i] > 1)
+            return failp(err, HEAT_E_INVALID_ARG, "comfort sensor %lld: control %d is neither 0 nor 1", (long long)i, (int)c->control[i]);
+        if (z < 0 || z >= n_zones) return failp(err, HEAT_E_SIZE, "comfort sensor %lld: zone %d outside [0, %lld)", (long long)i, z, (long long)n_zones);
+        for (int a = 0; a < 3; a++) {
+            const int32_t ch = chans[a] ? chans[a][i] : -1;
+            if (ch < -1 || ch >= NC)
+                return failp(err, HEAT_E_SIZE, "comfort sensor %lld: %s channel %d outside [-1, %d)", (long long)i, chan_name[a], ch, NC);
+        }
+        if (c->control && c->control[i]) {
+            if (controlled[(size_t)z])
+                return failp(err, HEAT_E_SIZE, "comfort sensor %lld: zone %d has a control sensor already (at most one per zone)", (long long)i, z);
+            controlled[(size_t)z] = 1;
+        }
+    }
+    if (E == 0) return HEAT_OK;
+    if (!c->en_sensor || !c->en_surface || !c->en_side || !c->en_weight)
+        return failp(err, HEAT_E_INVALID_ARG, "comfort entry 0: %s is NULL (n_entries %lld)",
+                     !c->en_sensor ? "en_sensor" : (!c->en_surface ? "en_surface" : (!c->en_side ? "en_side" : "en_weight")), (long long)E);
+    for (int64_t j = 0; j < E; j++) {
+        if (!std::isfinite(c->en_weight[j])) return failp(err, HEAT_E_INVALID_ARG, "comfort entry %lld: en_weight = %g is not finite", (long long)j, c->en_weight[j]);
+        if (c->en_sensor[j] < 0 || c->en_sensor[j] >= N)
+            return failp(err, HEAT_E_SIZE, "comfort entry %lld: sensor %d outside [0, %lld)", (long long)j, c->en_sensor[j], (long long)N);
+        if (c->en_surface[j] < 0 || c->en_surface[j] >= n_surfaces)
+            return failp(err, HEAT_E_SIZE, "comfort entry %lld: surface %lld outside [0, %lld)", (long long)j, (long long)c->en_surface[j], (long long)n_surfaces);
+        if (c->en_side[j] > 1) return failp(err, HEAT_E_SIZE, "comfort entry %lld: side %d is neither 0 (first node) nor 1 (last node)", (long long)j, (int)c->en_side[j]);
+    }
+    return HEAT_OK;
+}
+
+void build_comfort_tables(int64_t n_zones, const heat_comfort *c, const int64_t *node_tile_base, const int32_t *node_geom,
+                          const int64_t *first_node_slot, const int64_t *node_count, ComfortTables &t) {
+    t = ComfortTables();
+    const size_t N = c && c->n_sensors > 0 ? (size_t)c->n_sensors : 0, E = N ? (size_t)c->n_entries : 0;
+    if (N == 0) return;
+    t.off.assign(N + 1, 0);
+    t.face.assign(E, 0);
+    t.weight.assign(E, 0.0);
+    t.orig.assign(E, -1);
+    t.i32.assign(kComfortI32Rows * N, -1);
+    t.air_weight.assign(N, 0.5);
+    t.ctl_sensor.assign((size_t)n_zones, -1);
+    // a counting sort by sensor: stable, so the caller's order survives inside a sensor
+    for (size_t j = 0; j < E; j++) t.off[(size_t)c->en_sensor[j] + 1]++;
+    for (size_t i = 0; i < N; i++) t.off[i + 1] += t.off[i];
+    std::vector<int32_t> next(t.off.begin(), t.off.begin() + N);
+    for (size_t j = 0; j < E; j++) {
+        const size_t p = (size_t)next[(size_t)c->en_sensor[j]]++;
+        const int64_t q = c->en_surface[j];
+        const int node = c->en_side[j] ? (int)node_count[q] - 1 : 0;
+        t.face[p] = (uint32_t)(node_tile_base ? node_slot_index(node_tile_base[q], node_geom[q], node) : first_node_slot[q] + node);
+        t.weight[p] = c->en_weight[j];
+        t.orig[p] = (int32_t)j;
+    }
+    for (size_t i = 0; i < N; i++) {
+        t.i32[CF_ZONE * N + i] = c->zone[i];
+        if (c->occ_chan) t.i32[CF_OCC_CHAN * N + i] = c->occ_chan[i];
+        if (c->lo_chan) t.i32[CF_LO_CHAN * N + i] = c->lo_chan[i];
+        if (c->hi_chan) t.i32[CF_HI_CHAN * N + i] = c->hi_chan[i];
+        if (c->air_weight) t.air_weight[i] = c->air_weight[i];
+        if (c->control && c->control[i]) t.ctl_sensor[(size_t)c->zone[i]] = (int32_t)i, t.any_control = true;
+    }
+}
+
+int check_comfort_tables(int64_t n_zones, const heat_comfort *c, const ComfortTables &t, std::string &err) {
+    const size_t N = c && c->n_sensors > 0 ? (size_t)c->n_sensors : 0, E = N ? (size_t)c->n_entries : 0, Z = N ? (size_t)n_zones : 0;
+    if (t.off.size() != (N ? N + 1 : 0) || t.face.size() != E || t.weight.size() != E || t.orig.size() != E || t.i32.size() != kComfortI32Rows * N ||
+        t.air_weight.size() != N || t.ctl_sensor.size() != Z)
+        return failp(err, HEAT_E_SIZE, "comfort tables: %zu offsets, %zu faces, %zu weights, %zu rows and %zu zones for comfort sensor i < %zu, comfort entry j < %zu",
+                     t.off.size(), t.face.size(), t.weight.size(), t.air_weight.size(), t.ctl_sensor.size(), N, E);
+    if (N == 0) return HEAT_OK;
+    if (t.off[0] != 0 || t.off[N] != (int32_t)E) return failp(err, HEAT_E_SIZE, "comfort tables: the offsets run from %d to %d for %zu entries", t.off[0], t.off[N], E);
+    for (size_t i = 0; i < N; i++)
+        if (t.off[i + 1] < t.off[i] || t.off[i + 1] > (int32_t)E)
+            return failp(err, HEAT_E_SIZE, "comfort tables: comfort sensor %zu runs from %d to %d", i, t.off[i], t.off[i + 1]);
+    // every entry of the caller's, in the caller's order, is the next element of its sensor's range ...
+    std::vector<int32_t> cursor(t.off.begin(), t.off.begin() + N);
+    for (size_t j = 0; j < E; j++) {
+        const size_t i = (size_t)c->en_sensor[j];
+        const int32_t p = cursor[i]++;
+        if (p >= t.off[i + 1]) return failp(err, HEAT_E_SIZE, "comfort tables: comfort entry %zu: comfort sensor %zu has no room for it", j, i);
+        if (t.orig[(size_t)p] != (int32_t)j || std::memcmp(&t.weight[(size_t)p], &c->en_weight[j], sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "comfort tables: comfort entry %zu is not element %d of comfort sensor %zu", j, p - t.off[i], i);
+    }
+    // ... and every range is full: with n_entries elements in all, each entry is present exactly once
+    std::vector<int32_t> ctl(Z, -1);
+    for (size_t i = 0; i < N; i++) {
+        if (cursor[i] != t.off[i + 1]) return failp(err, HEAT_E_SIZE, "comfort tables: comfort sensor %zu holds %d entries of %d", i, cursor[i] - t.off[i], t.off[i + 1] - t.off[i]);
+        const double a = c->air_weight ? c->air_weight[i] : 0.5;
+        const bool same = t.i32[CF_ZONE * N + i] == c->zone[i] && t.i32[CF_OCC_CHAN * N + i] == (c->occ_chan ? c->occ_chan[i] : -1) &&
+                          t.i32[CF_LO_CHAN * N + i] == (c->lo_chan ? c->lo_chan[i] : -1) && t.i32[CF_HI_CHAN * N + i] == (c->hi_chan ? c->hi_chan[i] : -1) &&
+                          t.air_weight[i] == a;
+        if (!same) return failp(err, HEAT_E_SIZE, "comfort tables: comfort sensor %zu is not the caller's", i);
+        if (c->control && c->control[i]) ctl[(size_t)c->zone[i]] = (int32_t)i;
+    }
+    bool any = false;
+    for (size_t z = 0; z < Z; z++) {
+        if (ctl[z] != t.ctl_sensor[z]) return failp(err, HEAT_E_SIZE, "comfort tables: zone %zu is controlled by comfort sensor %d, not %d", z, t.ctl_sensor[z], ctl[z]);
+        any = any || ctl[z] >= 0;
+    }
+    if (any != t.any_control) return failp(err, HEAT_E_SIZE, "comfort tables: any_control is %d with%s a control comfort sensor i", (int)t.any_control, any ? "" : "out");
+    return HEAT_OK;
+}
+
 // ---- room radiation of a series (include/heat_amd.h, heat_room_radiation) ----
 int check_room_radiation(int64_t n_surfaces, const heat_series *s, const heat_sky *sky, const heat_room_radiation *rr, std::string &err) {
     if (!rr) return HEAT_OK;
@@ -2988,6 +3115,22 @@ int heat_air_paths_check(const heat_batch_desc *desc, int32_t n_sites, const hea
     heat::AirPathTables t;
     heat::build_air_path_tables(desc->n_zones, air, t);
     return heat::check_air_path_tables(desc->n_zones, air, t, heat::last_error());
+}
+
+int heat_comfort_check(const heat_batch_desc *desc, const heat_series *s, const heat_comfort *c) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    rc = heat::check_comfort(desc->n_surfaces, desc->n_zones, s, c, heat::last_error());
+    if (rc || !c) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see). Without a batch there is no device layout: a face stands as the caller's state slot.
+    std::vector<int64_t> node_count;
+    const heat::SeriesModel m = heat::series_model_of(desc, node_count);
+    heat::ComfortTables t;
+    heat::build_comfort_tables(desc->n_zones, c, nullptr, nullptr, m.first_node_slot, m.node_count, t);
+    return heat::check_comfort_tables(desc->n_zones, c, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

@@ -263,6 +263,34 @@ void build_blind_tables(int64_t n_shades, const heat_blinds *bl, BlindTables &t)
 // every row of the caller's values. HEAT_OK or HEAT_E_SIZE.
 int check_blind_tables(int64_t n_shades, const heat_blinds *bl, const BlindTables &t, std::string &err);
 
+// Comfort of a series (heat_comfort, include/heat_amd.h). Everything heat_comfort_check promises about the term itself;
+// c == nullptr is none. s has passed check_series. HEAT_OK or a negative heat_status with `err` set, naming
+// "comfort sensor i" or "comfort entry j".
+int check_comfort(int64_t n_surfaces, int64_t n_zones, const heat_series *s, const heat_comfort *c, std::string &err);
+// The tables of k_series_comfort (one lane per sensor) and k_series_control_T (one lane per zone): the entries stably sorted
+// by sensor (a counting sort: the caller's order survives inside a sensor) with CSR offsets, each entry's face as an index
+// into the node buffer and its weight; the sensors' rows in the caller's order (a NULL air_weight is 0.5 here, a NULL channel
+// list -1); the control sensor of every zone, -1 for none.
+enum ComfortI32 : int { CF_ZONE, CF_OCC_CHAN, CF_LO_CHAN, CF_HI_CHAN, kComfortI32Rows };
+struct ComfortTables {
+    std::vector<int32_t> off;         // [n_sensors + 1]
+    std::vector<uint32_t> face;       // [n_entries]
+    std::vector<double> weight;       // [n_entries]
+    std::vector<int32_t> orig;        // [n_entries] the caller's number of the entry (host side only: the check reads it)
+    std::vector<int32_t> i32;         // [kComfortI32Rows][n_sensors]
+    std::vector<double> air_weight;   // [n_sensors]
+    std::vector<int32_t> ctl_sensor;  // [n_zones]
+    bool any_control = false;
+};
+// (of a term that passed check_comfort) The node buffer's layout is a batch's: node_tile_base / node_geom in the caller's
+// surface order (Plan). Without one (node_tile_base == nullptr: the host-only check) a face stands as the caller's state
+// slot, first_node_slot[surface] (+ node_count[surface] - 1 for the last node).
+void build_comfort_tables(int64_t n_zones, const heat_comfort *c, const int64_t *node_tile_base, const int32_t *node_geom,
+                          const int64_t *first_node_slot, const int64_t *node_count, ComfortTables &t);
+// The tables against the caller's lists (used by the host-only check): every entry present exactly once in its sensor's
+// range and in the caller's order, the offsets monotone, every row the caller's, every zone's control sensor the caller's.
+int check_comfort_tables(int64_t n_zones, const heat_comfort *c, const ComfortTables &t, std::string &err);
+
 // Room radiation of a series (heat_room_radiation, include/heat_amd.h). Everything heat_room_radiation_check promises about
 // the radiation itself; rr == nullptr is none. s has passed check_series and sky check_sky. HEAT_OK or a negative heat_status
 // with `err` set, naming "receiver r" or "entry i".

@@ -1087,6 +1087,82 @@ int heat_sky_aniso_check(const heat_batch_desc *desc, int32_t n_sites, const hea
                          const heat_solar_gains *gains, const heat_shades *shades, const heat_sky_aniso *aniso); /* host-only */
 int heat_batch_march_series_call(heat_batch *b, const heat_series_call *call);
 
+/*
+ * Comfort of a series: the operative temperature of rooms, reported per step, accumulated against limits that are channels,
+ * and — where a sensor says so — sensed by the controls in place of the zone's air temperature. A sensor stands in a zone and
+ * sees a list of faces: entry j gives sensor en_sensor[j] the first (en_side 0) or last (en_side 1) node of surface
+ * en_surface[j] with weight en_weight[j]; the weighted sum is the mean radiant temperature, mixed with the zone's air by
+ * air_weight. The faces are temperatures only the device holds at the start of a step: neither the rows nor the controls'
+ * reaction can be formed by the caller ahead of time. The reference has no comfort model; the rule below is this library's
+ * own contract, defined against the per-call loop with the same rule written on the host (heat_amd/comfort.py operative(),
+ * control_temperatures(), accumulate()).
+ * The rule of step k, evaluated behind the step's head and before the zone loads: T the node temperatures and Tz the zone
+ * temperatures the device holds at that moment — what step k - 1 left; nothing on the head writes either —, row = channel[k],
+ * K = step_base + k. Every line is ONE rounded f64 operation in the order written, no fused multiply-add; a NaN makes every
+ * comparison false:
+ *   per sensor i:
+ *     r = 0.0;  per entry j of i, in the caller's order:  x = en_weight[j] * T[face(en_surface[j], en_side[j])];  r = r + x
+ *     a = air_weight[i];  xa = a * Tz[zone[i]];  b = 1.0 - a;  xr = b * r;  top = xa + xr
+ *     mrt[k][i] = r;  operative[k][i] = top
+ *     occ = occ_chan[i] < 0 or row[occ_chan[i]] > 0
+ *     if occ:  n_occupied += 1;  sum_operative = sum_operative + top
+ *              if top < min_operative { min_operative = top; step_min = K }      (strict: the first occurrence stays)
+ *              if top > max_operative { max_operative = top; step_max = K }
+ *              if lo_chan[i] >= 0 and top < row[lo]:  n_below += 1;  d = row[lo] - top;  deg_below = deg_below + d
+ *              if hi_chan[i] >= 0 and top > row[hi]:  n_above += 1;  d = top - row[hi];  deg_above = deg_above + d
+ *                                                     if d > max_above { max_above = d; step_max_above = K }
+ *   the control temperature of the step:  Tc[z] = top of the sensor with control == 1 and zone == z, else Tz[z]
+ * Who reads Tc: the thermostats of heat_zone_loads (Ts = Tc[sensor]); the air paths for e = s * (Tc[target] - set) alone — Tt
+ * in g, dT and q stays the air temperature: the air that moves is air —; the blinds for their room condition (Tc[zone]).
+ * The ideal loads and the ambient drive's mix keep the air temperature: they act on, or stand for, the zone's air.
+ * A sensor without entries has r = 0.0. Row k describes the state at the START of step k, as path_q and irradiance do.
+ * n_sub == 0 still evaluates every step, on the unchanged state. Every accumulator is in/out and nullable; resume == 0: the
+ * library initialises on the device (sums and counts 0, min = +inf, max = -inf, max_above = -inf, steps = -1); resume != 0:
+ * they start from the caller's arrays. The term has no other memory: a series of k steps followed by one of n - k with
+ * resume = 1 and step_base + k gives the bits of the series of n.
+ * heat_comfort_check (host-only) and heat_batch_march_series_comfort run the same checks before any device work; every
+ * message names "comfort sensor i" or "comfort entry j". HEAT_E_INVALID_ARG: a negative count; a NULL array that a positive
+ * count needs (zone; en_sensor, en_surface, en_side, en_weight); an en_weight or air_weight that is not finite; an air_weight
+ * outside [0, 1]; a control byte above 1; a step array without its extremum (step_min / step_max / step_max_above without
+ * min_operative / max_operative / max_above). HEAT_E_SIZE: a zone, surface, sensor or channel out of range; a side above 1; a
+ * second control sensor on a zone. Sharded batches are refused, as by the series. A refused call leaves the device state
+ * untouched.
+ * With c == NULL or n_sensors == 0 heat_batch_march_series_comfort is heat_batch_march_series_call on `call` exactly: same
+ * launches, same bits. Sensors without a control bit change no bit of any other output.
+ */
+typedef struct heat_comfort {
+    int64_t n_sensors;
+    const int32_t *zone;          /* [n_sensors] the zone whose air the sensor stands in */
+    const double  *air_weight;    /* [n_sensors] nullable = 0.5; finite, in [0, 1] */
+    const uint8_t *control;       /* [n_sensors] nullable = 0; 1: this sensor is the control temperature of its zone */
+    int64_t n_entries;
+    const int32_t *en_sensor;     /* entries in any order; summed per sensor in the caller's order */
+    const int64_t *en_surface;
+    const uint8_t *en_side;       /* 0: first node, 1: last node of the surface */
+    const double  *en_weight;     /* finite; the caller makes them sum to 1 per sensor (comfort.by_area does) */
+    const int32_t *occ_chan, *lo_chan, *hi_chan;   /* [n_sensors] each nullable / -1: always occupied / no limit */
+    int32_t resume;               /* as heat_series_report::resume, for the arrays below */
+    int64_t step_base;            /* K = step_base + k is what the step arrays record */
+    /* accumulators, [n_sensors] each, in/out, nullable */
+    int64_t *n_occupied;
+    double *sum_operative;
+    double *min_operative;
+    int64_t *step_min;
+    double *max_operative;
+    int64_t *step_max;
+    int64_t *n_below;
+    double *deg_below;
+    int64_t *n_above;
+    double *deg_above;
+    double *max_above;
+    int64_t *step_max_above;
+} heat_comfort;
+
+int heat_comfort_check(const heat_batch_desc *desc, const heat_series *s, const heat_comfort *c); /* host-only */
+int heat_batch_march_series_comfort(heat_batch *b, const heat_series_call *call, heat_comfort *c /* nullable */,
+                                    double *operative /* [n_steps][n_sensors], nullable */,
+                                    double *mrt /* [n_steps][n_sensors], nullable */);
+
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -104,6 +104,16 @@ pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
     pub sunlit: *mut f64, pub irradiance: *mut f64, pub ambient_t: *mut f64, pub position: *mut f64,
     pub blind_incident: *mut f64, pub failed_step: *mut i32,
 }
+// heat_comfort: operative-temperature sensors of a series — faces and weights, limits as channels, in/out accumulators
+#[repr(C)] pub struct HeatComfort {
+    pub n_sensors: i64, pub zone: *const i32, pub air_weight: *const f64, pub control: *const u8,
+    pub n_entries: i64, pub en_sensor: *const i32, pub en_surface: *const i64, pub en_side: *const u8, pub en_weight: *const f64,
+    pub occ_chan: *const i32, pub lo_chan: *const i32, pub hi_chan: *const i32,
+    pub resume: i32, pub step_base: i64,
+    pub n_occupied: *mut i64, pub sum_operative: *mut f64, pub min_operative: *mut f64, pub step_min: *mut i64,
+    pub max_operative: *mut f64, pub step_max: *mut i64, pub n_below: *mut i64, pub deg_below: *mut f64,
+    pub n_above: *mut i64, pub deg_above: *mut f64, pub max_above: *mut f64, pub step_max_above: *mut i64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -188,6 +198,10 @@ extern "C" {
     pub fn heat_sky_aniso_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
                                 gains: *const HeatSolarGains, shades: *const HeatShades, aniso: *const HeatSkyAniso) -> c_int;
     pub fn heat_batch_march_series_call(b: *mut HeatBatch, call: *const HeatSeriesCall) -> c_int;
+    // comfort of a series: operative temperatures per room, reported, accumulated and sensed by the controls
+    pub fn heat_comfort_check(desc: *const HeatBatchDesc, s: *const HeatSeries, c: *const HeatComfort) -> c_int;
+    pub fn heat_batch_march_series_comfort(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
+                                           operative: *mut f64, mrt: *mut f64) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

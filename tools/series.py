@@ -96,19 +96,27 @@ and writes profiles/series_aniso.json: ms per step of each, A - B, a series of O
 calls are set up, and — where the kernel trace of one A series has been taken (--one-series --aniso under rocprofv3
 --kernel-trace --stats, a run of its own; profiles/series_aniso_kernel_stats.csv) — the kernels' own times. No time is a pass
 criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds]
+With --comfort (heat_batch_march_series_comfort, heat_comfort; the loads of --loads, whose thermostats then sense) it alternates
+  N  the series with loads through heat_batch_march_series_call, comfort = NULL
+  C  the same call with one sensor per zone by comfort.by_area, every sensor the control temperature of its zone, occupancy
+     and an adaptive band in three channels, every accumulator kept (operative and mrt not recorded)
+and writes profiles/series_comfort.json: ms per step of each, C - N, a series of ONE step of each and the per-step times once
+the calls are set up, the bytes a step of the two kernels moves, and — where the kernel trace of one C series has been taken
+(--one-series --comfort under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_comfort_kernel_stats.csv) —
+k_series_comfort and k_series_control_T per step. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
                                                      with --ideal leg I; with --sky a series of leg C' and one of leg K; with --gains
                                                      a series of leg J; with --air a series of leg A; with --shades a series of leg S;
                                                      with --radiation a series of leg R; with --ambient a series of leg M; with --blinds a series
-                                                     of leg B"""
+                                                     of leg B; with --comfort a series of leg C"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, ambient as ambm, air_paths as apm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -120,7 +128,8 @@ BLINDS = "--blinds" in sys.argv or ANISO
 SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT
+COMFORT = "--comfort" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT or COMFORT
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -258,6 +267,27 @@ if ANISO:
 
     def leg_an(b, w, n_sub, steps):
         return leg_bl(b, w, n_sub, steps, aniso_args)
+if COMFORT:
+    # three more channels (occupancy: nine steps in twenty-four; an adaptive band that drifts with the steps) and one sensor per
+    # zone over the sides that face it, area-weighted, every one the control temperature of its zone: the thermostats sense it
+    c_cf = channel.shape[1]
+    drift = 0.5 * np.sin(2.0 * np.pi * np.arange(STEPS) / 24.0)
+    channel = np.concatenate([channel, np.where(np.arange(STEPS) % 24 < 9, 1.0, 0.0)[:, None], (20.0 + drift)[:, None], (24.0 + drift)[:, None]], axis=1)
+    comfort_args = dict(cfm.by_area(md, air_weight=0.5, control=True), occ_chan=np.full(Z, c_cf, np.int32), lo_chan=np.full(Z, c_cf + 1, np.int32),
+                        hi_chan=np.full(Z, c_cf + 2, np.int32))
+    # per entry: face index, weight and the gathered node; per sensor: two offsets, four integers, the air weight, the zone
+    # temperature, `top`, twelve accumulators read and written; per zone: the control sensor, a gather and a store
+    COMFORT_BYTES = dict(k_series_comfort_per_entry=4 + 8 + 8, k_series_comfort_per_sensor=8 + 4 * 4 + 8 + 8 + 8 + 12 * 16, k_series_control_T_per_zone=4 + 8 + 8)
+
+    def leg_cf(b, w, n_sub, steps, comfort="given"):
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads, aniso={},
+                             comfort=comfort_args if comfort == "given" else comfort, operative=False, mrt=False, **drives)
+        dt = time.perf_counter() - t0
+        assert out[1] == -1 and np.all(np.isfinite(out[0]))
+        assert comfort is None or (out[4]["n_occupied"] > 0).all()
+        return dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
     exchange = rrm.exchange_by_area(md)
@@ -512,6 +542,31 @@ with HeatBatch(md) as b:
         bs.upload_state(state)
     for n_sub in ((2,) if ONE else (2, 20)):
         w = mdl.weather_series(STEPS * n_sub, 45.0).reshape(STEPS, n_sub, 3)
+        if COMFORT:
+            leg_cf(b, w, n_sub, min(STEPS, 10), None)  # warm-up
+            leg_cf(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with comfort: C %.3f ms per step" % leg_cf(b, w, n_sub, STEPS))
+                continue
+            nn, cc, nn1, cc1 = [], [], [], []
+            for r in range(ROUNDS):
+                nn.append(leg_cf(b, w, n_sub, STEPS, None))
+                cc.append(leg_cf(b, w, n_sub, STEPS))
+                nn1.append(leg_cf(b, w, n_sub, 1, None))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                cc1.append(leg_cf(b, w, n_sub, 1))
+            N_, C_, N1, C1 = (float(np.median(v)) for v in (nn, cc, nn1, cc1))
+            Ns, Cs = (N_ * STEPS - N1) / (STEPS - 1), (C_ * STEPS - C1) / (STEPS - 1)  # per step once the call is set up
+            NE = len(comfort_args["en_sensor"])
+            nbytes = COMFORT_BYTES["k_series_comfort_per_entry"] * NE + COMFORT_BYTES["k_series_comfort_per_sensor"] * Z + COMFORT_BYTES["k_series_control_T_per_zone"] * Z
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                N_comfort_null_ms=N_, C_comfort_ms=C_, C_minus_N_ms=C_ - N_, C_over_N=C_ / N_, N_series_of_one_step_ms=N1,
+                C_series_of_one_step_ms=C1, C_minus_N_series_of_one_step_ms=C1 - N1, N_without_setup_ms=Ns, C_without_setup_ms=Cs,
+                C_minus_N_without_setup_ms=Cs - Ns, sensors=int(Z), entries=int(NE), bytes=COMFORT_BYTES,
+                bytes_per_step_of_the_two_kernels=int(nbytes), all_rounds=dict(N=nn, C=cc, N_one_step=nn1, C_one_step=cc1))
+            print("n_sub %2d: N comfort NULL %.3f ms/step, C comfort %.3f -> C - N = %+.3f ms, C / N = %.4f; a series of one step: "
+                  "N %.2f ms, C %.2f ms -> per step without the set-up N %.3f, C %.3f, C - N = %+.3f (%d sensors, %d entries, %d steps, "
+                  "median of %d rounds)" % (n_sub, N_, C_, C_ - N_, C_ / N_, N1, C1, Ns, Cs, Cs - Ns, Z, NE, STEPS, ROUNDS), flush=True)
+            continue
         if IDEAL:
             leg_i(bs, w, n_sub, min(STEPS, 10))  # warm-up
             if ONE:
@@ -924,6 +979,25 @@ if SHADES and not BLINDS and not ONE:
             us["k_series_shading"], nbytes / us["k_series_shading"] / 1e6, us["k_series_sky"]))
     else:
         print("no kernel trace at %s" % stats)
+if COMFORT and not ONE:
+    # the kernel trace of one C series (--one-series --comfort under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: the two kernels per step, k_series_comfort on its own bytes, beside the same trace's k_series_zone_loads
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_comfort_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_comfort", "k_series_control_T", "k_series_zone_loads")}
+        nbytes = COMFORT_BYTES["k_series_comfort_per_entry"] * len(comfort_args["en_sensor"]) + COMFORT_BYTES["k_series_comfort_per_sensor"] * Z
+        result["kernel_trace_of_one_C_series"] = dict(
+            k_series_comfort_us_per_step=us["k_series_comfort"], k_series_control_T_us_per_step=us["k_series_control_T"],
+            k_series_zone_loads_us_per_step=us["k_series_zone_loads"], k_series_comfort_bytes_per_step=int(nbytes),
+            k_series_comfort_TB_per_s=nbytes / us["k_series_comfort"] / 1e6, calls=int(rows["k_series_comfort"]["Calls"]))
+        print("kernel trace: k_series_comfort %.2f us per step (%.2f TB/s on its own bytes), k_series_control_T %.2f, k_series_zone_loads %.2f" % (
+            us["k_series_comfort"], nbytes / us["k_series_comfort"] / 1e6, us["k_series_control_T"], us["k_series_zone_loads"]))
+    else:
+        print("no kernel trace at %s" % stats)
 if AMBIENT and not ONE:
     # the kernel trace of one M series (--one-series --ambient under rocprofv3 --kernel-trace --stats, a run of its own), where
     # it has been taken: k_series_ambient alone
@@ -940,7 +1014,7 @@ if AMBIENT and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
