@@ -442,7 +442,8 @@ k_surfaces_small(const GeneralTile *__restrict__ tiles, int n_tiles, NodeArrays 
 
 // ---------------------------------------------------------------------------
 // Cluster-resident march, pieces shared by the fast-path wavefronts and the small-surface wavefronts of a
-// workgroup (layout.hpp, FusedBlock). LDS after the palettes (and V): see k_surfaces_fast.
+// workgroup (layout.hpp, FusedBlock). LDS after the palettes (and, in two instantiations, V: fused_v_in_lds): see
+// k_surfaces_fast.
 struct FusedLds {
     double2 *hT;            // (hs * area, face temperature) of the zone-facing sides, in the order of the zones' lists
     double *zT, *za0, *zb0, *zvol;
@@ -450,6 +451,14 @@ struct FusedLds {
     int *zoff;
     unsigned short *slots;  // place in hT of side [2][lanes] (front sides, then back sides, by lane of the workgroup)
 };
+
+// V = dt/C of a lane's nodes lives in registers over the march. Two instantiations keep it in an LDS array [16][lanes]
+// behind the palettes instead, read where it is used: 16-node walls with no-mass facings in teams and, with four
+// wavefronts, beside small surfaces — the two whose scratch grows with V in registers (12 -> 20 and 336 -> 352 bytes;
+// DESIGN.md 4a). FW: the workgroup's wavefronts (the kernel's FUSED), SMALL as there.
+constexpr bool fused_v_in_lds(int M, int NM, int FW, int SMALL) {
+    return M == 16 && NM == 1 && (SMALL == 2 || (SMALL == 1 && FW == 4));
+}
 
 // Barriers a wavefront of a fused workgroup passes: one at the end of fused_block_init, two per sub-timestep in
 // fused_zone_phase. A wavefront without a tile that stays for the work queue keeps step with exactly these counts
@@ -789,7 +798,7 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
                                                 unsigned long long *__restrict__ nomass_iters, const FusedArgs &fa,
                                                 bool write_out = true, const TeamCtx team = TeamCtx{0, 0, 0, 0, nullptr}) {
     constexpr int kLanes = (FUSED ? FUSED : 4) * kWave;
-    constexpr bool kVinLds = FUSED && M == 16;
+    constexpr bool kVinLds = FUSED && fused_v_in_lds(M, NM, FUSED, SMALL);
     HEAT_STAMP(4, true);
     HEAT_STAMP(0, false);
     HEAT_SSTAMP(0, false);
@@ -989,7 +998,7 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
         if constexpr (kSingleLane) zt_b2 = zone_T[cb2.zone];
     }
 
-    // V = dt/C of local node j: registers, or the workgroup's LDS array (FUSED with 16 nodes per lane)
+    // V = dt/C of local node j: registers, or the workgroup's LDS array (fused_v_in_lds)
     auto Vat = [&](int j) -> double {
         if constexpr (kVinLds) return s_V[j * kLanes + threadIdx.x];
         else return V[j];
@@ -1320,9 +1329,21 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
         asm volatile("" : "+v"(T[0]), "+v"(T[M - 1]));
         HEAT_SSTAMP(6, false);
 #endif
+        // V in registers over the march: each of the two copies below gets a V of its own (an empty asm: no instruction,
+        // the registers stay where they are). Sharing one V, the copies' last product V (f - f_prev) and the addition
+        // behind it are merged after the branch and contracted there into one FMA — one rounding fewer than inside a
+        // copy, which is what the march did while each copy read V from LDS itself: its outputs keep their bits.
+        auto own_V = [&]() {
+            if constexpr (FUSED && M == 16 && !kVinLds) {  // (the variants that had V in LDS: the others are as they were)
+#pragma unroll
+                for (int j = 0; j < M; j++) asm volatile("" : "+v"(V[j]));
+            }
+        };
         if (full) {
+            own_V();
             rk4_horner<M>(T, Vat, U, ULe, is_first, is_last, qFe, [&](int j) -> double { return (j == M - 1) ? qBe : 0.0; });
         } else {
+            own_V();
             rk4_horner<M>(T, Vat, U, ULe, is_first, is_last, qFe, [&](int j) -> double { return (j == jl) ? qBe : 0.0; });
         }
 #ifdef HEAT_STREAM_STAMPS
@@ -1470,11 +1491,13 @@ k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, 
     extern __shared__ double s_dyn[];
     __shared__ double s_pos_static[FUSED ? 2 : kLanes];
     double *const s_pal = s_dyn;  // (dynamic: kLanes * na.pal_stride doubles)
-    // FUSED, after the palettes: with 16 nodes per lane V = dt/C of every node, [M][kLanes] (read where it is used:
-    // held in registers over the march it would push that variant out of the register file); (hs * area, face temperature)
-    // per side [2][kLanes] double2; zone temperatures, a0, b0, volume [kFusedMaxZones] each; first slot of every
-    // zone [kFusedMaxZones + 1]; the slot lists.
-    constexpr bool kVinLds = FUSED && M == 16;
+    // FUSED, after the palettes: (hs * area, face temperature) per side [2][kLanes] double2; zone temperatures, a0, b0,
+    // volume, a team member's own sums (two arrays) [kFusedMaxZones] each; first slot of every zone [kFusedMaxZones + 2];
+    // the slot lists. V = dt/C stays in registers over the march — the compiler read all of a lane's V in the first RK
+    // stage and kept them anyway, behind eight serialised LDS round trips per sub-timestep; only where fused_v_in_lds
+    // says so (the registers' last bytes) an array [M][kLanes] of V sits between the palettes and the pairs, read where
+    // it is used. Host side: fused_lds_bytes.
+    constexpr bool kVinLds = FUSED && fused_v_in_lds(M, NM, FUSED, SMALL);
     double *const s_V = s_dyn + kLanes * na.pal_stride;
     FusedLds fl;
     fl.hT = reinterpret_cast<double2 *>(s_V + (kVinLds ? M : 0) * kLanes);
@@ -3193,8 +3216,10 @@ void launch_surfaces_stream(int variant, const FastTile *tiles, int n_tiles, con
 
 // Cluster-resident march of one class: one workgroup of `max_waves` (4 or 8) wavefronts per FusedBlock, fa.n_sub
 // sub-timesteps in one launch. Palette classes without cavities only.
-size_t fused_lds_bytes(int max_waves, int M, int pal_stride) {
-    return (size_t)max_waves * kWave * ((pal_stride + (M == 16 ? M : 0)) * sizeof(double) + 2 * sizeof(double2)) +
+// (what k_surfaces_fast carves up: palettes, V rows where fused_v_in_lds, pairs [2][lanes], six zone arrays, offsets, slots)
+size_t fused_lds_bytes(int max_waves, int M, int pal_stride, bool v_in_lds) {
+    const int v_rows = v_in_lds ? M : 0;
+    return (size_t)max_waves * kWave * ((pal_stride + v_rows) * sizeof(double) + 2 * sizeof(double2)) +
            6 * kFusedMaxZones * sizeof(double) + (kFusedMaxZones + 2) * sizeof(int) + kFusedMaxEntries * sizeof(uint16_t);
 }
 
@@ -3202,7 +3227,7 @@ template <int MM, int NN, int CC, int FW, int SM>
 static hipError_t launch_fused_one(int grid_blocks, const FastTile *tiles, int n_tiles, const NodeArrays &na,
                                    const SideArrays &sa, const StepWeather *weather, int *flags,
                                    unsigned long long *nomass_iters, const FusedArgs &fa, hipStream_t st) {
-    const size_t lds = fused_lds_bytes(FW, MM, na.pal_stride);
+    const size_t lds = fused_lds_bytes(FW, MM, na.pal_stride, fused_v_in_lds(MM, NN, FW, SM));
     // (per instantiation and device) dynamic LDS above the 64 KB default needs the attribute; it grows with the palette width
     constexpr int kMaxDevices = 64;
     static std::atomic<size_t> attr_bytes[kMaxDevices];  // 0: never set
@@ -3228,7 +3253,9 @@ static hipError_t launch_fused_one(int grid_blocks, const FastTile *tiles, int n
 int fused_blocks_per_cu(int M, int cav, int mixed, int max_waves, int pal_stride) {
     const int waves_per_simd = (M == 4 && !cav && !mixed) ? 3 : 2;
     const int by_regs = std::max(1, waves_per_simd * 4 / max_waves);
-    const int by_lds = std::max<int>(1, (int)(160 * 1024 / fused_lds_bytes(max_waves, M, pal_stride)));
+    // (mixed is 0 or 1 here — teams: fused_team_blocks_per_cu; workgroups with small surfaces run the NM = 1 variants)
+    const bool v_in_lds = fused_v_in_lds(M, mixed ? 1 : 0, max_waves <= 4 ? 4 : 8, mixed);
+    const int by_lds = std::max<int>(1, (int)(160 * 1024 / fused_lds_bytes(max_waves, M, pal_stride, v_in_lds)));
     return std::min(by_regs, by_lds);
 }
 
@@ -3243,7 +3270,7 @@ static int team_occupancy(size_t lds) {
     return n;
 }
 int fused_team_blocks_per_cu(int M, int nm, int pal_stride) {
-    const size_t lds = fused_lds_bytes(4, M, pal_stride);
+    const size_t lds = fused_lds_bytes(4, M, pal_stride, fused_v_in_lds(M, nm ? 1 : 0, 4, 2));
     if (M == 4) return nm ? team_occupancy<4, 1>(lds) : team_occupancy<4, 0>(lds);
     if (M == 8) return nm ? team_occupancy<8, 1>(lds) : team_occupancy<8, 0>(lds);
     return nm ? team_occupancy<16, 1>(lds) : team_occupancy<16, 0>(lds);
