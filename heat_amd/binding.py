@@ -196,6 +196,17 @@ class Comfort(C.Structure):
                 ("deg_above", _dp), ("max_above", _dp), ("step_max_above", _i64p)]
 
 
+class AirHandlers(C.Structure):
+    """heat_air_handlers (include/heat_amd.h): ventilation units with heat recovery, a bypass and supply-air coils, and their
+    branches into the zones"""
+    _fields_ = [("n_units", C.c_int64), ("outdoor_chan", _i32p), ("eff_chan", _i32p), ("eff_gain", _dp), ("bypass_chan", _i32p),
+                ("bypass_band", _dp), ("bypass_min_delta", _dp), ("heat_chan", _i32p), ("cool_chan", _i32p), ("heat_cap", _dp),
+                ("cool_cap", _dp), ("n_branches", C.c_int64), ("br_unit", _i32p), ("br_zone", _i32p), ("br_volume_chan", _i32p),
+                ("br_volume_gain", _dp), ("br_kind", C.POINTER(C.c_uint8)), ("bypass", C.POINTER(C.c_uint8)), ("sum_recovered", _dp),
+                ("sum_heating", _dp), ("sum_cooling", _dp), ("steps_bypass", _i64p), ("switches", _i64p),
+                ("steps_heat_saturated", _i64p), ("steps_cool_saturated", _i64p), ("sum_branch_q", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -274,6 +285,9 @@ SYMBOLS = [
     ("heat_batch_march_series_call", C.c_int, [_H, C.POINTER(SeriesCall)]),
     ("heat_comfort_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(Comfort)]),
     ("heat_batch_march_series_comfort", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp]),
+    ("heat_air_handlers_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(AirHandlers)]),
+    ("heat_batch_march_series_handlers", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
+                                                   _dp, _dp, _dp, _dp]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -425,7 +439,7 @@ def make_desc(md):
 HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
-                     "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check",
+                     "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check", "heat_air_handlers_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1409,6 +1423,80 @@ def comfort_check(md, comfort, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+HANDLER_STATS = ("sum_recovered", "sum_heating", "sum_cooling", "steps_bypass", "switches", "steps_heat_saturated",
+                 "steps_cool_saturated", "sum_branch_q")
+_HANDLER_UNIT = (("outdoor_chan", np.int32, True), ("eff_chan", np.int32, False), ("eff_gain", np.float64, False),
+                 ("bypass_chan", np.int32, False), ("bypass_band", np.float64, False), ("bypass_min_delta", np.float64, False),
+                 ("heat_chan", np.int32, False), ("cool_chan", np.int32, False), ("heat_cap", np.float64, False),
+                 ("cool_cap", np.float64, False))
+_HANDLER_BRANCH = (("br_unit", np.int32, True), ("br_zone", np.int32, True), ("br_volume_chan", np.int32, True),
+                   ("br_volume_gain", np.float64, False), ("br_kind", np.uint8, False))
+_HANDLER_INT = ("steps_bypass", "switches", "steps_heat_saturated", "steps_cool_saturated")
+
+
+def make_air_handlers(outdoor_chan=(), eff_chan=None, eff_gain=None, bypass_chan=None, bypass_band=None, bypass_min_delta=None,
+                      heat_chan=None, cool_chan=None, heat_cap=None, cool_cap=None, br_unit=(), br_zone=(), br_volume_chan=(),
+                      br_volume_gain=None, br_kind=None, bypass=None, stats=HANDLER_STATS, **acc):
+    """Builds a heat_air_handlers. Returns (handlers, keepalive); the march updates keepalive["bypass"] and the accumulators in
+    place.
+    outdoor_chan     [n_units] the channel of the outdoor-air temperature, C
+    eff_gain, eff_chan   [n_units] the effectiveness: the gain (None: 1) times the channel's value (None / -1: none)
+    bypass_chan, bypass_band, bypass_min_delta   [n_units] the setpoint channel of the extract air (None / -1: no bypass), K, K
+    heat_chan, cool_chan   [n_units] the channel of the minimum / maximum supply temperature (None / -1: no coil)
+    heat_cap, cool_cap     [n_units] W, inf allowed; None: inf
+    br_unit, br_zone, br_volume_chan   [n_branches] the unit, the zone, the channel of the volume flow in m3/s
+    br_volume_gain, br_kind   [n_branches] None: 1 / None: 3 (1 supplies, 2 extracts, 3 both)
+    bypass and the names of HANDLER_STATS   what a previous series returned (copied); None: zeros
+    stats            which of HANDLER_STATS the march maintains (the others stay NULL)
+    (air_handlers.apply and accumulate are the rule in numpy and take the same dict)"""
+    given = dict(outdoor_chan=outdoor_chan, eff_chan=eff_chan, eff_gain=eff_gain, bypass_chan=bypass_chan, bypass_band=bypass_band,
+                 bypass_min_delta=bypass_min_delta, heat_chan=heat_chan, cool_chan=cool_chan, heat_cap=heat_cap, cool_cap=cool_cap,
+                 br_unit=br_unit, br_zone=br_zone, br_volume_chan=br_volume_chan, br_volume_gain=br_volume_gain, br_kind=br_kind)
+    unknown = (set(stats or ()) | set(acc)) - set(HANDLER_STATS)
+    if unknown:
+        raise ValueError("air handlers: unknown stats %s (known: %s)" % (sorted(unknown), ", ".join(HANDLER_STATS)))
+    h = AirHandlers()
+    keep = {}
+    n = len(np.asarray(outdoor_chan if outdoor_chan is not None else ()).reshape(-1))
+    nb = len(np.asarray(br_unit if br_unit is not None else ()).reshape(-1))
+    h.n_units, h.n_branches = n, nb
+    for rows, count, what in ((_HANDLER_UNIT, n, "units"), (_HANDLER_BRANCH, nb, "branches")):
+        for name, dtype, needed in rows:
+            if given[name] is None and not needed:
+                continue
+            v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+            if v.shape != (count,):
+                raise ValueError("air handlers %s: %s for %d %s" % (name, v.shape, count, what))
+            keep[name] = v
+            setattr(h, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if count else None)
+    inout = [("bypass", np.uint8, n, bypass)]
+    for name in HANDLER_STATS:
+        if name not in (stats or ()):
+            if acc.get(name) is not None:
+                raise ValueError("air handlers %s given, but not among stats %s" % (name, tuple(stats or ())))
+            continue
+        inout.append((name, np.int64 if name in _HANDLER_INT else np.float64, nb if name == "sum_branch_q" else n, acc.get(name)))
+    for name, dtype, count, v in inout:
+        v = np.zeros(count, dtype) if v is None else np.array(v, dtype=dtype).reshape(-1)  # (a copy: the march writes it)
+        if v.shape != (count,):
+            raise ValueError("air handlers %s: %s for %d" % (name, v.shape, count))
+        keep[name] = v
+        setattr(h, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if count else None)
+    return h, keep
+
+
+def air_handlers_check(md, handlers, lib=None, **series):
+    """heat_air_handlers_check: everything about the air handlers of a series that needs no device (series arguments as
+    HeatBatch.march_series; handlers: the arguments of make_air_handlers, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    h, hkeep = make_air_handlers(**handlers) if handlers is not None else (None, None)
+    rc = L.heat_air_handlers_check(C.byref(desc), C.byref(s), C.byref(h) if h is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1529,7 +1617,8 @@ class HeatBatch:
 
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
-                     blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True, **series):
+                     blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True,
+                     handlers=None, supply_t=True, recovered=True, coil_q=True, branch_q=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1588,7 +1677,13 @@ class HeatBatch:
         against limits that are channels and, where a sensor has its control bit, sensed by thermostats, air paths and blinds in
         place of the zone temperature. Returns what the same call without comfort returns plus one dict: operative and mrt
         [n_steps, n_sensors] (empty with operative=False / mrt=False) and of COMFORT_STATS those in stats (pass them as
-        comfort["resume"] to the next series) — one more element of the tuple, or the key "comfort" of the dict."""
+        comfort["resume"] to the next series) — one more element of the tuple, or the key "comfort" of the dict.
+        handlers (a dict of make_air_handlers' arguments; an empty dict: no unit): heat_batch_march_series_handlers —
+        ventilation units with heat recovery, a bypass and supply-air coils, formed on the device at every step from the zone
+        air temperatures it holds. Returns what the same call without handlers returns plus one dict: supply_t, recovered,
+        coil_q [n_steps, n_units] and branch_q [n_steps, n_branches] (each empty with its flag False), bypass, and of
+        HANDLER_STATS those in stats (pass bypass and them on to the next series) — one more element of the tuple, or the key
+        "handlers" of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -1598,8 +1693,10 @@ class HeatBatch:
             given["sky"] = _sky_for_gains(sky, self._normals, self.n_surfaces)
         return self._march_series(weather, n_sub, series, given, dict(trace=trace, applied=applied, path_q=path_q, sunlit=sunlit,
                                                                       irradiance=irradiance, ambient_t=ambient_t, position=position,
-                                                                      blind_incident=blind_incident, operative=operative, mrt=mrt),
-                                  aniso=aniso, comfort=comfort)
+                                                                      blind_incident=blind_incident, operative=operative, mrt=mrt,
+                                                                      supply_t=supply_t, recovered=recovered, coil_q=coil_q,
+                                                                      branch_q=branch_q),
+                                  aniso=aniso, comfort=comfort, handlers=handlers)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -1625,10 +1722,10 @@ class HeatBatch:
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
-    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None):
+    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
         whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None; comfort: the dict of make_comfort's
-        arguments or None."""
+        arguments or None; handlers: the dict of make_air_handlers' arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1680,7 +1777,7 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        if aniso is not None or comfort is not None:
+        if aniso is not None or comfort is not None or handlers is not None:
             # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
             # that are recorded, and the anisotropic sky.
             call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
@@ -1696,10 +1793,21 @@ class HeatBatch:
             for name, a in rows.items():
                 if a.size:
                     setattr(call, name, a.ctypes.data_as(_dp))
+            ptr = lambda a: a.ctypes.data_as(_dp) if a.size else None  # noqa: E731
+            cf = None
             if comfort is not None:
                 cf, ckeep = make_comfort(**comfort)
                 top_rows = np.zeros((s.n_steps if want["operative"] else 0, cf.n_sensors))
                 mrt_rows = np.zeros((s.n_steps if want["mrt"] else 0, cf.n_sensors))
+            if handlers is not None:
+                ah, hkeep = make_air_handlers(**handlers)
+                hrows = {k: np.zeros((s.n_steps if want[k] else 0, ah.n_branches if k == "branch_q" else ah.n_units))
+                         for k in ("supply_t", "recovered", "coil_q", "branch_q")}
+                rc = self._L.heat_batch_march_series_handlers(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
+                                                              ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
+                                                              C.byref(ah), ptr(hrows["supply_t"]), ptr(hrows["recovered"]), ptr(hrows["coil_q"]),
+                                                              ptr(hrows["branch_q"]))
+            elif comfort is not None:
                 rc = self._L.heat_batch_march_series_comfort(self._h, C.byref(call), C.byref(cf), top_rows.ctypes.data_as(_dp) if top_rows.size else None,
                                                              mrt_rows.ctypes.data_as(_dp) if mrt_rows.size else None)
             else:
@@ -1733,6 +1841,8 @@ class HeatBatch:
                                     **{k: kept["blinds"][k] for k in ("state",) + BLIND_STATS if k in kept["blinds"]}))]
         if comfort is not None:
             out += [("comfort", dict(operative=top_rows, mrt=mrt_rows, **{k: ckeep[k] for k in COMFORT_STATS if k in ckeep}))]
+        if handlers is not None:
+            out += [("handlers", dict(hrows, **{k: hkeep[k] for k in ("bypass",) + HANDLER_STATS if k in hkeep}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

@@ -1730,6 +1730,78 @@ struct AirTerm {
     }
 };
 
+// The air handlers (heat_air_handlers): the branches as CSR over the units and the supply branches as CSR over the zones
+// (plan.hpp, HandlerTables), the units' rows, the step's scratch (Ts per unit, m per branch), the bypass bytes, the
+// accumulators (always uploaded) and the four arrays of rows in the caller's order. Nothing of it exists on the device
+// without units.
+struct HandlersTerm {
+    heat_air_handlers *ah = nullptr;
+    int64_t NU = 0, NBR = 0;
+    HandlerTables aht;
+    std::vector<uint8_t> h_bypass;
+    DevBuf<int32_t> unit_off, u_zone, u_chan, u_orig, zone_off, z_unit, z_orig, i32;
+    DevBuf<uint8_t> u_kind, bypass;
+    DevBuf<double> u_gain, f64, ts, m, supply_t, recovered, coil_q, branch_q;  // the last four: [n_steps][NU] thrice, [n_steps][NBR]
+    Acc<double> unit_f64[3];   // sum_recovered, sum_heating, sum_cooling
+    Acc<int64_t> unit_i64[4];  // steps_bypass, switches, steps_heat_saturated, steps_cool_saturated
+    Acc<double> sum_branch_q;
+    HandlersDev view{};
+    void prepare(const heat_batch *b, heat_air_handlers *ah_) {
+        ah = ah_;
+        NU = ah ? ah->n_units : 0;
+        if (NU == 0) return;
+        NBR = ah->n_branches;
+        build_air_handler_tables(b->n_zones, ah, aht);
+        h_bypass.assign((size_t)NU, 0);
+        if (ah->bypass) std::copy(ah->bypass, ah->bypass + NU, h_bypass.begin());
+        unit_f64[0].bind(ah->sum_recovered, 0.0, &view.sum_recovered), unit_f64[1].bind(ah->sum_heating, 0.0, &view.sum_heating);
+        unit_f64[2].bind(ah->sum_cooling, 0.0, &view.sum_cooling);
+        unit_i64[0].bind(ah->steps_bypass, 0, &view.steps_bypass), unit_i64[1].bind(ah->switches, 0, &view.switches);
+        unit_i64[2].bind(ah->steps_heat_saturated, 0, &view.steps_heat_saturated);
+        unit_i64[3].bind(ah->steps_cool_saturated, 0, &view.steps_cool_saturated);
+        sum_branch_q.bind(ah->sum_branch_q, 0.0, &view.sum_branch_q);
+    }
+    bool supplies() const { return !aht.z_orig.empty(); }
+    int upload(const double *host_supply, const double *host_recovered, const double *host_coil, const double *host_branch, int n_steps) {
+        if (NU == 0) return HEAT_OK;
+        SERIES_TRY(series_upload(unit_off, aht.unit_off, "air handler tables"));
+        SERIES_TRY(series_upload(u_zone, aht.u_zone, "air handler tables"));
+        SERIES_TRY(series_upload(u_chan, aht.u_chan, "air handler tables"));
+        SERIES_TRY(series_upload(u_orig, aht.u_orig, "air handler tables"));
+        SERIES_TRY(series_upload(u_kind, aht.u_kind, "air handler tables"));
+        SERIES_TRY(series_upload(u_gain, aht.u_gain, "air handler tables"));
+        SERIES_TRY(series_upload(zone_off, aht.zone_off, "air handler tables"));
+        SERIES_TRY(series_upload(z_unit, aht.z_unit, "air handler tables"));
+        SERIES_TRY(series_upload(z_orig, aht.z_orig, "air handler tables"));
+        SERIES_TRY(series_upload(i32, aht.i32, "air handler tables"));
+        SERIES_TRY(series_upload(f64, aht.f64, "air handler tables"));
+        SERIES_TRY(series_upload(bypass, h_bypass, "air handler bypass states"));
+        SERIES_TRY(series_alloc(ts, (size_t)NU, "supply temperatures"));
+        SERIES_TRY(series_alloc(m, (size_t)NBR, "branch mass flows"));
+        for (auto &a : unit_f64) SERIES_TRY(a.stage((size_t)NU, true, "air handler accumulators"));
+        for (auto &a : unit_i64) SERIES_TRY(a.stage((size_t)NU, true, "air handler accumulators"));
+        SERIES_TRY(sum_branch_q.stage((size_t)NBR, true, "air handler accumulators"));
+        if (host_supply) SERIES_TRY(series_alloc(supply_t, (size_t)n_steps * NU, "supply temperatures"));
+        if (host_recovered) SERIES_TRY(series_alloc(recovered, (size_t)n_steps * NU, "recovered powers"));
+        if (host_coil) SERIES_TRY(series_alloc(coil_q, (size_t)n_steps * NU, "coil powers"));
+        if (host_branch) SERIES_TRY(series_alloc(branch_q, (size_t)n_steps * NBR, "branch powers"));
+        view.n_units = (int)NU, view.unit_off = unit_off.p, view.u_zone = u_zone.p, view.u_chan = u_chan.p, view.u_orig = u_orig.p;
+        view.u_kind = u_kind.p, view.u_gain = u_gain.p, view.zone_off = zone_off.p, view.z_unit = z_unit.p, view.z_orig = z_orig.p;
+        view.outdoor_chan = i32.p + AH_OUTDOOR_CHAN * NU, view.eff_chan = i32.p + AH_EFF_CHAN * NU, view.bypass_chan = i32.p + AH_BYPASS_CHAN * NU;
+        view.heat_chan = i32.p + AH_HEAT_CHAN * NU, view.cool_chan = i32.p + AH_COOL_CHAN * NU;
+        view.eff_gain = f64.p + AH_EFF_GAIN * NU, view.half_band = f64.p + AH_HALF_BAND * NU, view.min_delta = f64.p + AH_MIN_DELTA * NU;
+        view.heat_cap = f64.p + AH_HEAT_CAP * NU, view.cool_cap = f64.p + AH_COOL_CAP * NU;
+        view.ts = ts.p, view.m = m.p, view.bypass = bypass.p;
+        return HEAT_OK;
+    }
+    hipError_t fetch(double *host_supply, double *host_recovered, double *host_coil, double *host_branch, hipStream_t st) {
+        if (NU == 0) return hipSuccess;
+        hipError_t e = series_fetch(host_recovered, recovered, st, series_fetch(host_supply, supply_t, st));
+        e = series_fetch(ah->bypass, bypass, st, series_fetch(host_branch, branch_q, st, series_fetch(host_coil, coil_q, st, e)));
+        return sum_branch_q.fetch(st, for_each_acc(unit_i64, &Acc<int64_t>::fetch, st, for_each_acc(unit_f64, &Acc<double>::fetch, st, e)));
+    }
+};
+
 // The anisotropic sky (heat_sky_aniso): the coefficient table as given, beside the record table, and the bands of the three
 // consumers — the sides' per DEVICE surface, the apertures' and the shades' in the caller's order as their tables are; zeros
 // where the caller gave none. Absent (every pointer NULL) without aniso: the isotropic kernels are launched.
@@ -1821,7 +1893,8 @@ struct ComfortTerm {
 };
 
 // What heat_batch_march_series_call takes (the eleven positional entry points fill what they have) and, beside it, the comfort
-// term and its two arrays of rows (heat_batch_march_series_comfort); filled by field name. no_trace_ok: a NULL trace records none.
+// term and its two arrays of rows (heat_batch_march_series_comfort) and the air handlers with their four
+// (heat_batch_march_series_handlers); filled by field name. no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
@@ -1841,6 +1914,8 @@ struct SeriesCall {
     double *position = nullptr, *blind_incident = nullptr;
     heat_comfort *comfort = nullptr;
     double *operative = nullptr, *mrt = nullptr;
+    heat_air_handlers *handlers = nullptr;
+    double *supply_t = nullptr, *recovered = nullptr, *coil_q = nullptr, *branch_q = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -2840,6 +2915,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = check_room_radiation(b->n_surf, s, c.sky, c.radiation, heat::last_error()))) return rc;
     if ((rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, c.ambient, heat::last_error()))) return rc;
     if ((rc = check_comfort(b->n_surf, b->n_zones, s, c.comfort, heat::last_error()))) return rc;
+    if ((rc = check_air_handlers(b->n_zones, s->n_channels, c.handlers, heat::last_error()))) return rc;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -2867,6 +2943,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     InputsTerm in; ProbesTerm probes; LoadsTerm loads; ReportTerm report; IdealTerm ideal;
     ShadesTerm shades; BlindsTerm blinds; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air; AnisoTerm aniso;
     ComfortTerm comfort;
+    HandlersTerm handlers;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
@@ -2881,8 +2958,9 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     ideal.prepare(c.il, load_of_zone);
     air.prepare(b, c.air);
     comfort.prepare(b, c.comfort);
+    handlers.prepare(b, c.handlers);
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
-    const int64_t NL = blinds.NL, NF = comfort.NF;
+    const int64_t NL = blinds.NL, NF = comfort.NF, NU = handlers.NU, NBR = handlers.NBR;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -2901,6 +2979,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = ambient.upload(c.ambient, c.ambient_t, n_steps))) return rc;
     if ((rc = air.upload(b, c.path_q, n_steps))) return rc;
     if ((rc = comfort.upload(b, c.operative, c.mrt, n_steps))) return rc;
+    if ((rc = handlers.upload(c.supply_t, c.recovered, c.coil_q, c.branch_q, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
     HIP_TRY(report.start(b->stream));
     HIP_TRY(ideal.start(b->stream));
@@ -2908,7 +2987,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     // what the thermostats, the air paths' e and the blinds sense: the zone temperatures, or with a control sensor the step's Tc
     const double *control_T = comfort.control_T.p ? comfort.control_T.p : b->d_zone_T.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    // ---- the steps, enqueued without waiting: head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> ambient drive ->
+    // ---- the steps, enqueued without waiting: head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> ambient drive ->
     // driven inputs -> shades -> blinds -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
         const double *channel = row(d_channel, k, NC);
@@ -2928,6 +3007,13 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
         if (NP > 0)
             launch_series_air_paths((int)Z, air.view, channel, b->d_zone_T.p, control_T, b->d_zone_a0.p, b->d_zone_b0.p, row(air.path_q, k, NP), b->d_flags.p,
                                     b->stream);
+        if (NU > 0) {
+            double *branch_row = row(handlers.branch_q, k, NBR);
+            launch_series_handler_units(handlers.view, channel, b->d_zone_T.p, row(handlers.supply_t, k, NU), row(handlers.recovered, k, NU),
+                                        row(handlers.coil_q, k, NU), branch_row, b->stream);
+            if (handlers.supplies())
+                launch_series_handler_supply((int)Z, handlers.view, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p, branch_row, b->d_flags.p, b->stream);
+        }
         if (NB > 0) launch_series_ambient(ambient.view, channel, b->d_zone_T.p, b->d_side_const.p, row(ambient.t, k, NB), b->stream);
         if (in.driven)
             launch_series_inputs((int)S, channel, in.view, b->d_T.p, b->d_side_alpha.p, b->d_side_dyn.p, b->sl, mirror, b->stream);
@@ -2976,6 +3062,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(radiation.fetch(c.irradiance, b->stream));
     HIP_TRY(ambient.fetch(c.ambient_t, b->stream));
     HIP_TRY(comfort.fetch(c.operative, c.mrt, b->stream));
+    HIP_TRY(handlers.fetch(c.supply_t, c.recovered, c.coil_q, c.branch_q, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -3079,10 +3166,14 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
     return march_series_impl(b, c);
 }
 
-// heat_batch_march_series_call and heat_batch_march_series_comfort: the struct's fields by name, then the comfort term.
-static int march_series_call(heat_batch *b, const heat_series_call *call, heat_comfort *comfort, double *operative, double *mrt) {
+// heat_batch_march_series_call, heat_batch_march_series_comfort and heat_batch_march_series_handlers: the struct's fields by
+// name, then the comfort term, then the air handlers (`more`: what the last of them adds, or nullptr).
+static int march_series_call(heat_batch *b, const heat_series_call *call, heat_comfort *comfort, double *operative, double *mrt,
+                             const SeriesCall *more = nullptr) {
     if (const int rc = check_series_call(call, heat::last_error())) return rc;  // (a struct of another size is not read further)
-    SeriesCall c; c.comfort = comfort, c.operative = operative, c.mrt = mrt; c.s = call->s, c.sky = call->sky, c.aniso = call->aniso, c.shades = call->shades, c.gains = call->gains, c.l = call->l;
+    SeriesCall c;
+    if (more) c = *more;
+    c.comfort = comfort, c.operative = operative, c.mrt = mrt; c.s = call->s, c.sky = call->sky, c.aniso = call->aniso, c.shades = call->shades, c.gains = call->gains, c.l = call->l;
     c.air = call->air, c.il = call->il, c.r = call->r, c.radiation = call->radiation, c.ambient = call->ambient, c.blinds = call->blinds;
     c.trace = call->trace, c.applied = call->applied, c.ideal_q = call->ideal_q, c.transmitted = call->transmitted, c.path_q = call->path_q;
     c.sunlit = call->sunlit, c.irradiance = call->irradiance, c.ambient_t = call->ambient_t, c.position = call->position;
@@ -3094,6 +3185,12 @@ int heat_batch_march_series_call(heat_batch *b, const heat_series_call *call) { 
 
 int heat_batch_march_series_comfort(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt) {
     return march_series_call(b, call, c, operative, mrt);
+}
+
+int heat_batch_march_series_handlers(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt,
+                                     heat_air_handlers *h, double *supply_t, double *recovered, double *coil_q, double *branch_q) {
+    SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
+    return march_series_call(b, call, c, operative, mrt, &more);
 }
 
 // The ambient temperature of the listed sides from the next march on: k_series_ambient with the temperatures as its row

@@ -3046,6 +3046,146 @@ k_series_control_T(int n_zones, const int32_t *__restrict__ ctl_sensor, const do
     control_T[z] = i >= 0 ? top[i] : zone_T[z];
 }
 
+// k_series_handler_units — the air handlers of one step (heat_air_handlers, include/heat_amd.h), behind k_series_air_paths and
+// before k_series_handler_supply: one lane per UNIT. A lane walks its CSR range of branches (sorted by unit, the caller's
+// order kept inside a unit) twice, each a sequential chain of its own: the extract branches for the flow-weighted mix Te — a
+// gather of zone temperatures nothing on the step's head writes: every one is the start of the step's —, then, with the
+// bypass decided and the air properties taken behind the exchanger, the supply branches for their m[j] and the sum M. A
+// reduction over lanes would not give the caller's order. The header's rule, every line one rounded operation in the order
+// written, hence no contraction; a NaN makes every comparison false. Ts[u] and m[j] go to the call's scratch for
+// k_series_handler_supply (m in the caller's branch order, through `orig`). A unit is one lane: its element of the three
+// rows, its state byte and every accumulator have one writer; so has the branch_q of an extract-only branch, 0.0, which no
+// zone's lane visits. Which outputs exist is decided by nullable pointers in the kernel argument: wave-uniform branches, an
+// array nobody takes is neither read nor written. No atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_handler_units(HandlersDev h, const double *__restrict__ row, const double *__restrict__ zone_T, double *__restrict__ supply_row,
+                       double *__restrict__ recovered_row, double *__restrict__ coil_row, double *__restrict__ branch_row) {
+#pragma clang fp contract(off)
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= h.n_units) return;
+    const int j0 = h.unit_off[u], j1 = h.unit_off[u + 1];
+    const double to = row[h.outdoor_chan[u]];
+    double st = 0.0, sv = 0.0;
+    for (int j = j0; j < j1; j++) {
+        if (!(h.u_kind[j] & 2)) continue;
+        const double v = h.u_gain[j] * row[h.u_chan[j]];
+        const double x = v * zone_T[h.u_zone[j]];
+        st = st + x;
+        sv = sv + v;
+    }
+    const double te = sv > 0.0 ? st / sv : to;
+    double eta = h.eff_gain[u];
+    const int ec = h.eff_chan[u], bc = h.bypass_chan[u], hc = h.heat_chan[u], cc = h.cool_chan[u];
+    if (ec >= 0) eta = eta * row[ec];
+    if (eta < 0.0) eta = 0.0;
+    if (eta > 1.0) eta = 1.0;
+    const int before = h.bypass[u];
+    int now = before;
+    if (bc >= 0) {
+        const double set = row[bc], d = h.half_band[u];
+        const double e = te - set;
+        const double g = te - to;
+        if (e > d && g > h.min_delta[u]) now = 1;
+        else if (before == 1 && (e < -d || g <= 0.0)) now = 0;
+        if (now != before) h.bypass[u] = (uint8_t)now;
+        if (now == 1) eta = 0.0;
+    }
+    const double dt = te - to;
+    const double r = eta * dt;
+    const double tr = to + r;
+    const double tk = tr + 273.15;
+    const double rho = 101325. * 28.97 / (8314.46261815324 * tk);  // gas.rs:175-179
+    const double cp = 1002.7370 + 1.2324e-2 * tk;                  // gas.rs:49,165-167
+    double M = 0.0;
+    for (int j = j0; j < j1; j++) {
+        const int orig = h.u_orig[j];
+        if (h.u_kind[j] & 1) {
+            const double v = h.u_gain[j] * row[h.u_chan[j]];
+            const double m = (rho * v) * cp;
+            h.m[orig] = m;
+            M = M + m;
+        } else {  // (extracts only: nothing flows into its zone)
+            if (branch_row != nullptr) branch_row[orig] = 0.0;
+            if (h.sum_branch_q != nullptr) h.sum_branch_q[orig] = h.sum_branch_q[orig] + 0.0;
+        }
+    }
+    const double recovered = M * r;
+    double ts = tr, q = 0.0;
+    bool heat_sat = false, cool_sat = false;
+    const double heat_set = hc >= 0 ? row[hc] : 0.0, cool_set = cc >= 0 ? row[cc] : 0.0;
+    if (hc >= 0 && tr < heat_set) {
+        const double lift = heat_set - tr;
+        const double need = M * lift;
+        const double cap = h.heat_cap[u];
+        if (need <= cap) {
+            ts = heat_set;
+            q = need;
+        } else {
+            q = cap;
+            const double x = cap / M;
+            ts = tr + x;
+            heat_sat = true;
+        }
+    } else if (cc >= 0 && tr > cool_set) {
+        const double drop = tr - cool_set;
+        const double need = M * drop;
+        const double cap = h.cool_cap[u];
+        if (need <= cap) {
+            ts = cool_set;
+            q = 0.0 - need;
+        } else {
+            q = 0.0 - cap;
+            const double x = cap / M;
+            ts = tr - x;
+            cool_sat = true;
+        }
+    }
+    h.ts[u] = ts;
+    if (supply_row != nullptr) supply_row[u] = ts;
+    if (recovered_row != nullptr) recovered_row[u] = recovered;
+    if (coil_row != nullptr) coil_row[u] = q;
+    if (h.sum_recovered != nullptr) h.sum_recovered[u] = h.sum_recovered[u] + recovered;
+    if (h.sum_heating != nullptr && q > 0.0) h.sum_heating[u] = h.sum_heating[u] + q;
+    if (h.sum_cooling != nullptr && q < 0.0) h.sum_cooling[u] = h.sum_cooling[u] + q;
+    if (h.steps_bypass != nullptr) h.steps_bypass[u] += now;
+    if (h.switches != nullptr && now != before) h.switches[u] += 1;
+    if (h.steps_heat_saturated != nullptr && heat_sat) h.steps_heat_saturated[u] += 1;
+    if (h.steps_cool_saturated != nullptr && cool_sat) h.steps_cool_saturated[u] += 1;
+}
+
+// k_series_handler_supply — what the air handlers supply in one step, behind k_series_handler_units: one lane per ZONE walks
+// the supply branches into it (a CSR range of the supply branches sorted by zone, the caller's order kept inside a zone) and
+// adds m[j] * Ts[unit] and m[j] to the a0 / b0 of its own zone alone, behind what the zone loads and the air paths added; a
+// zone without a branch leaves after reading its offsets. Ts and m are the scratch the units' kernel wrote in this step. A
+// supply branch belongs to the lane of its zone: its element of the step's branch_q row and of sum_branch_q (the caller's
+// order, through `orig`) has one writer. A NaN a0 / b0 is reported as the zone's failure, as the air paths report it.
+__global__ void __launch_bounds__(256)
+k_series_handler_supply(int n_zones, HandlersDev h, const double *__restrict__ zone_T, double *__restrict__ a0, double *__restrict__ b0,
+                        double *__restrict__ branch_row, int *__restrict__ flags) {
+#pragma clang fp contract(off)
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= n_zones) return;
+    const int p0 = h.zone_off[z], p1 = h.zone_off[z + 1];
+    if (p0 == p1) return;
+    double a = a0[z], b = b0[z];
+    const bool clean = a == a && b == b;
+    const double tz = zone_T[z];
+    for (int i = p0; i < p1; i++) {
+        const int orig = h.z_orig[i];
+        const double m = h.m[orig], ts = h.ts[h.z_unit[i]];
+        const double mt = m * ts;
+        a = a + mt;
+        b = b + m;
+        const double dz = ts - tz;
+        const double bq = m * dz;
+        if (branch_row != nullptr) branch_row[orig] = bq;
+        if (h.sum_branch_q != nullptr) h.sum_branch_q[orig] = h.sum_branch_q[orig] + bq;
+    }
+    a0[z] = a;
+    b0[z] = b;
+    if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
+}
+
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = value;
@@ -3532,6 +3672,19 @@ void launch_series_control_T(int n_zones, const int32_t *ctl_sensor, const doubl
                              hipStream_t st) {
     if (n_zones <= 0) return;
     hipLaunchKernelGGL(k_series_control_T, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, ctl_sensor, top, zone_T, control_T);
+}
+
+void launch_series_handler_units(const HandlersDev &h, const double *row, const double *zone_T, double *supply_row, double *recovered_row,
+                                 double *coil_row, double *branch_row, hipStream_t st) {
+    if (h.n_units <= 0) return;
+    hipLaunchKernelGGL(k_series_handler_units, dim3((h.n_units + 255) / 256), dim3(256), 0, st, h, row, zone_T, supply_row, recovered_row,
+                       coil_row, branch_row);
+}
+
+void launch_series_handler_supply(int n_zones, const HandlersDev &h, const double *zone_T, double *a0, double *b0, double *branch_row,
+                                  int *flags, hipStream_t st) {
+    if (n_zones <= 0 || h.n_units <= 0) return;
+    hipLaunchKernelGGL(k_series_handler_supply, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, h, zone_T, a0, b0, branch_row, flags);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

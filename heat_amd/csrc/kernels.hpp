@@ -305,6 +305,34 @@ void launch_series_comfort(const SeriesComfort &cf, const double *row, const dou
                            double *mrt_row, int64_t step, hipStream_t st);
 void launch_series_control_T(int n_zones, const int32_t *ctl_sensor, const double *top, const double *zone_T, double *control_T,
                              hipStream_t st);
+// Air handlers of a series step (heat_air_handlers, include/heat_amd.h; tables: plan.hpp, HandlerTables): launched behind
+// launch_series_air_paths and before launch_series_ambient, only when there are units. launch_series_handler_units — one lane
+// per unit — walks the unit's CSR range of branches twice (extract, then supply), forms Te, the bypass, Tr, the mass flows and
+// the coil, stores Ts[u] and m[j] into the call's scratch and updates the unit's rows, state byte and accumulators.
+// launch_series_handler_supply — one lane per zone, behind it — adds the zone's supply branches to its a0 / b0 and writes
+// their branch_q.
+struct HandlersDev {
+    int n_units;
+    const int32_t *unit_off;                       // [n_units + 1]: CSR offsets of all branches of the unit
+    const int32_t *u_zone, *u_chan, *u_orig;       // [n_branches], sorted by unit
+    const uint8_t *u_kind;
+    const double *u_gain;
+    const int32_t *zone_off;                       // [n_zones + 1]: CSR offsets of the supply branches into the zone
+    const int32_t *z_unit, *z_orig;                // [n_supply], sorted by zone
+    const int32_t *outdoor_chan, *eff_chan, *bypass_chan, *heat_chan, *cool_chan;   // [n_units] each; -1: none
+    const double *eff_gain, *half_band, *min_delta, *heat_cap, *cool_cap;           // [n_units] each
+    double *ts, *m;                                // [n_units], [n_branches] (caller's order): the step's scratch
+    uint8_t *bypass;                               // [n_units]
+    double *sum_recovered, *sum_heating, *sum_cooling;   // [n_units] each, nullptr: not maintained
+    int64_t *steps_bypass, *switches, *steps_heat_saturated, *steps_cool_saturated;
+    double *sum_branch_q;                          // [n_branches], the caller's order; nullptr: not maintained
+};
+// row: the step's row of the channel table; the four rows of the step's outputs (caller's order), or nullptr each
+void launch_series_handler_units(const HandlersDev &h, const double *row, const double *zone_T, double *supply_row, double *recovered_row,
+                                 double *coil_row, double *branch_row, hipStream_t st);
+// flags: the batch's failure flags (a branch that makes a zone's a0 / b0 NaN is reported as that zone's failure)
+void launch_series_handler_supply(int n_zones, const HandlersDev &h, const double *zone_T, double *a0, double *b0, double *branch_row,
+                                  int *flags, hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Per step: launch_series_ideal_begin (behind the zone loads)

@@ -1956,6 +1956,178 @@ int check_air_path_tables(int64_t n_zones, const heat_air_paths *air, const AirP
     return HEAT_OK;
 }
 
+// ---- air handlers of a series (include/heat_amd.h, heat_air_handlers) ----
+int check_air_handlers(int64_t n_zones, int32_t n_channels, const heat_air_handlers *h, std::string &err) {
+    if (!h) return HEAT_OK;
+    const int64_t U = h->n_units, B = h->n_branches;
+    const int NC = n_channels;
+    if (U < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of air handlers (n_units %lld): no air handler u", (long long)U);
+    if (B < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of air handler branches (n_branches %lld): no air handler branch j", (long long)B);
+    // (the tables number units and branches with 32 bits)
+    if (U > INT32_MAX || B > INT32_MAX)
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 air handlers u or air handler branches j (n_units %lld, n_branches %lld)",
+                     (long long)U, (long long)B);
+    if (U == 0 && B > 0)
+        return failp(err, HEAT_E_INVALID_ARG, "air handler branch 0: %lld branches, but no air handler u (n_units 0)", (long long)B);
+    if (U == 0) return HEAT_OK;
+    if (!h->outdoor_chan) return failp(err, HEAT_E_INVALID_ARG, "air handler 0: outdoor_chan is NULL (n_units %lld)", (long long)U);
+    for (int64_t u = 0; u < U; u++) {
+        const int32_t oc = h->outdoor_chan[u];
+        if (oc < 0 || oc >= NC) return failp(err, HEAT_E_SIZE, "air handler %lld: outdoor channel %d outside [0, %d)", (long long)u, oc, NC);
+        const int32_t *const opt[4] = {h->eff_chan, h->bypass_chan, h->heat_chan, h->cool_chan};
+        static const char *const opt_name[4] = {"effectiveness", "bypass", "heating", "cooling"};
+        for (int a = 0; a < 4; a++) {
+            const int32_t ch = opt[a] ? opt[a][u] : -1;
+            if (ch < -1 || ch >= NC)
+                return failp(err, HEAT_E_SIZE, "air handler %lld: %s channel %d outside [-1, %d)", (long long)u, opt_name[a], ch, NC);
+        }
+        if (h->eff_gain && !std::isfinite(h->eff_gain[u]))
+            return failp(err, HEAT_E_INVALID_ARG, "air handler %lld: eff_gain %g is not finite", (long long)u, h->eff_gain[u]);
+        const double *const cap[2] = {h->heat_cap, h->cool_cap};
+        static const char *const cap_name[2] = {"heat_cap", "cool_cap"};
+        for (int a = 0; a < 2; a++)
+            if (cap[a] && !(cap[a][u] >= 0.0))
+                return failp(err, HEAT_E_INVALID_ARG, "air handler %lld: %s %g is negative or NaN", (long long)u, cap_name[a], cap[a][u]);
+        if (h->bypass && h->bypass[u] > 1)
+            return failp(err, HEAT_E_INVALID_ARG, "air handler %lld: bypass %d is neither 0 (recovering) nor 1 (bypassed)", (long long)u, (int)h->bypass[u]);
+        if (!h->bypass_chan || h->bypass_chan[u] < 0) continue;  // (no bypass: band and min_delta are not read)
+        if (!h->bypass_band || !h->bypass_min_delta)
+            return failp(err, HEAT_E_INVALID_ARG, "air handler %lld: it bypasses (bypass channel %d), but %s is NULL", (long long)u, h->bypass_chan[u],
+                         !h->bypass_band ? "bypass_band" : "bypass_min_delta");
+        const double v[2] = {h->bypass_band[u], h->bypass_min_delta[u]};
+        static const char *const name[2] = {"bypass_band", "bypass_min_delta"};
+        for (int a = 0; a < 2; a++)
+            if (!std::isfinite(v[a]) || v[a] < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "air handler %lld: %s %g is negative or not finite", (long long)u, name[a], v[a]);
+    }
+    if (B == 0) return HEAT_OK;
+    if (!h->br_unit || !h->br_zone || !h->br_volume_chan)
+        return failp(err, HEAT_E_INVALID_ARG, "air handler branch 0: %s is NULL (n_branches %lld)",
+                     !h->br_unit ? "br_unit" : (!h->br_zone ? "br_zone" : "br_volume_chan"), (long long)B);
+    for (int64_t j = 0; j < B; j++) {
+        const int32_t u = h->br_unit[j], z = h->br_zone[j], vc = h->br_volume_chan[j];
+        if (u < 0 || u >= U) return failp(err, HEAT_E_SIZE, "air handler branch %lld: unit %d outside [0, %lld)", (long long)j, u, (long long)U);
+        if (z < 0 || z >= n_zones) return failp(err, HEAT_E_SIZE, "air handler branch %lld: zone %d outside [0, %lld)", (long long)j, z, (long long)n_zones);
+        if (vc < 0 || vc >= NC) return failp(err, HEAT_E_SIZE, "air handler branch %lld: volume channel %d outside [0, %d)", (long long)j, vc, NC);
+        if (h->br_volume_gain && !std::isfinite(h->br_volume_gain[j]))
+            return failp(err, HEAT_E_INVALID_ARG, "air handler branch %lld: br_volume_gain %g is not finite", (long long)j, h->br_volume_gain[j]);
+        if (h->br_kind && (h->br_kind[j] < 1 || h->br_kind[j] > 3))
+            return failp(err, HEAT_E_INVALID_ARG, "air handler branch %lld: br_kind %d is none of 1 (supplies), 2 (extracts), 3 (both)", (long long)j,
+                         (int)h->br_kind[j]);
+    }
+    return HEAT_OK;
+}
+
+void build_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, HandlerTables &t) {
+    t = HandlerTables();
+    const size_t U = h ? (size_t)h->n_units : 0, B = h ? (size_t)h->n_branches : 0, Z = (size_t)n_zones;
+    if (U == 0) return;
+    const double inf = std::numeric_limits<double>::infinity();
+    t.i32.assign(kHandlerI32Rows * U, -1);
+    t.f64.assign(kHandlerF64Rows * U, 0.0);
+    for (size_t u = 0; u < U; u++) {
+        const int32_t bc = h->bypass_chan ? h->bypass_chan[u] : -1;
+        t.i32[AH_OUTDOOR_CHAN * U + u] = h->outdoor_chan[u];
+        t.i32[AH_EFF_CHAN * U + u] = h->eff_chan ? h->eff_chan[u] : -1;
+        t.i32[AH_BYPASS_CHAN * U + u] = bc;
+        t.i32[AH_HEAT_CHAN * U + u] = h->heat_chan ? h->heat_chan[u] : -1;
+        t.i32[AH_COOL_CHAN * U + u] = h->cool_chan ? h->cool_chan[u] : -1;
+        t.f64[AH_EFF_GAIN * U + u] = h->eff_gain ? h->eff_gain[u] : 1.0;
+        t.f64[AH_HALF_BAND * U + u] = bc >= 0 ? h->bypass_band[u] / 2.0 : 0.0;
+        t.f64[AH_MIN_DELTA * U + u] = bc >= 0 ? h->bypass_min_delta[u] : 0.0;
+        t.f64[AH_HEAT_CAP * U + u] = h->heat_cap ? h->heat_cap[u] : inf;
+        t.f64[AH_COOL_CAP * U + u] = h->cool_cap ? h->cool_cap[u] : inf;
+    }
+    // two counting sorts, stable: the caller's order survives inside a unit and inside a zone
+    t.unit_off.assign(U + 1, 0);
+    t.zone_off.assign(Z + 1, 0);
+    size_t n_supply = 0;
+    for (size_t j = 0; j < B; j++) {
+        const unsigned kind = h->br_kind ? h->br_kind[j] : 3u;
+        t.unit_off[(size_t)h->br_unit[j] + 1]++;
+        if (kind & 1u) t.zone_off[(size_t)h->br_zone[j] + 1]++, n_supply++;
+    }
+    for (size_t u = 0; u < U; u++) t.unit_off[u + 1] += t.unit_off[u];
+    for (size_t z = 0; z < Z; z++) t.zone_off[z + 1] += t.zone_off[z];
+    t.u_zone.resize(B), t.u_chan.resize(B), t.u_orig.resize(B), t.u_kind.resize(B), t.u_gain.resize(B);
+    t.z_unit.resize(n_supply), t.z_orig.resize(n_supply);
+    std::vector<int32_t> next_u(t.unit_off.begin(), t.unit_off.end() - 1), next_z(t.zone_off.begin(), t.zone_off.end() - 1);
+    for (size_t j = 0; j < B; j++) {
+        const unsigned kind = h->br_kind ? h->br_kind[j] : 3u;
+        const size_t p = (size_t)next_u[(size_t)h->br_unit[j]]++;
+        t.u_zone[p] = h->br_zone[j];
+        t.u_chan[p] = h->br_volume_chan[j];
+        t.u_orig[p] = (int32_t)j;
+        t.u_kind[p] = (uint8_t)kind;
+        t.u_gain[p] = h->br_volume_gain ? h->br_volume_gain[j] : 1.0;
+        if (!(kind & 1u)) continue;
+        const size_t q = (size_t)next_z[(size_t)h->br_zone[j]]++;
+        t.z_unit[q] = h->br_unit[j];
+        t.z_orig[q] = (int32_t)j;
+    }
+}
+
+int check_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, const HandlerTables &t, std::string &err) {
+    const size_t U = h ? (size_t)h->n_units : 0, B = h ? (size_t)h->n_branches : 0, Z = (size_t)n_zones;
+    if (U == 0) return HEAT_OK;
+    const size_t NS = t.z_unit.size();
+    if (t.unit_off.size() != U + 1 || t.zone_off.size() != Z + 1 || t.u_zone.size() != B || t.u_chan.size() != B || t.u_orig.size() != B ||
+        t.u_kind.size() != B || t.u_gain.size() != B || t.z_orig.size() != NS || NS > B || t.i32.size() != kHandlerI32Rows * U ||
+        t.f64.size() != kHandlerF64Rows * U)
+        return failp(err, HEAT_E_SIZE, "air handler tables: %zu unit offsets, %zu zone offsets, %zu and %zu elements for air handler u < %zu, air handler branch j < %zu",
+                     t.unit_off.size(), t.zone_off.size(), t.u_zone.size(), NS, U, B);
+    if (t.unit_off[0] != 0 || t.unit_off[U] != (int32_t)B || t.zone_off[0] != 0 || t.zone_off[Z] != (int32_t)NS)
+        return failp(err, HEAT_E_SIZE, "air handler tables: the offsets run from %d to %d for %zu branches and from %d to %d for %zu supply branches",
+                     t.unit_off[0], t.unit_off[U], B, t.zone_off[0], t.zone_off[Z], NS);
+    for (size_t u = 0; u < U; u++)
+        if (t.unit_off[u + 1] < t.unit_off[u] || t.unit_off[u + 1] > (int32_t)B)
+            return failp(err, HEAT_E_SIZE, "air handler tables: air handler %zu runs from %d to %d", u, t.unit_off[u], t.unit_off[u + 1]);
+    for (size_t z = 0; z < Z; z++)
+        if (t.zone_off[z + 1] < t.zone_off[z] || t.zone_off[z + 1] > (int32_t)NS)
+            return failp(err, HEAT_E_SIZE, "air handler tables: zone %zu runs from %d to %d", z, t.zone_off[z], t.zone_off[z + 1]);
+    // every branch of the caller's, in the caller's order, is the next element of its unit's range and, where it supplies, of
+    // its zone's ...
+    std::vector<int32_t> cu(t.unit_off.begin(), t.unit_off.end() - 1), cz(t.zone_off.begin(), t.zone_off.end() - 1);
+    for (size_t j = 0; j < B; j++) {
+        const size_t u = (size_t)h->br_unit[j], z = (size_t)h->br_zone[j];
+        const unsigned kind = h->br_kind ? h->br_kind[j] : 3u;
+        const double gain = h->br_volume_gain ? h->br_volume_gain[j] : 1.0;
+        const int32_t p = cu[u]++;
+        if (p >= t.unit_off[u + 1]) return failp(err, HEAT_E_SIZE, "air handler tables: air handler branch %zu: air handler %zu has no room for it", j, u);
+        if (t.u_orig[p] != (int32_t)j || t.u_zone[p] != h->br_zone[j] || t.u_chan[p] != h->br_volume_chan[j] || (unsigned)t.u_kind[p] != kind ||
+            std::memcmp(&t.u_gain[p], &gain, sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "air handler tables: air handler branch %zu is not element %d of air handler %zu", j, p - t.unit_off[u], u);
+        if (!(kind & 1u)) continue;
+        const int32_t q = cz[z]++;
+        if (q >= t.zone_off[z + 1]) return failp(err, HEAT_E_SIZE, "air handler tables: air handler branch %zu: zone %zu has no room for it", j, z);
+        if (t.z_orig[q] != (int32_t)j || t.z_unit[q] != h->br_unit[j])
+            return failp(err, HEAT_E_SIZE, "air handler tables: air handler branch %zu is not element %d of zone %zu", j, q - t.zone_off[z], z);
+    }
+    // ... and every range is full: each branch is present exactly once
+    for (size_t u = 0; u < U; u++)
+        if (cu[u] != t.unit_off[u + 1])
+            return failp(err, HEAT_E_SIZE, "air handler tables: air handler %zu holds %d branches of %d", u, cu[u] - t.unit_off[u], t.unit_off[u + 1] - t.unit_off[u]);
+    for (size_t z = 0; z < Z; z++)
+        if (cz[z] != t.zone_off[z + 1])
+            return failp(err, HEAT_E_SIZE, "air handler tables: zone %zu holds %d supply branches of %d", z, cz[z] - t.zone_off[z], t.zone_off[z + 1] - t.zone_off[z]);
+    // the units' rows
+    const double inf = std::numeric_limits<double>::infinity();
+    for (size_t u = 0; u < U; u++) {
+        const int32_t bc = h->bypass_chan ? h->bypass_chan[u] : -1;
+        const int32_t i32[kHandlerI32Rows] = {h->outdoor_chan[u], h->eff_chan ? h->eff_chan[u] : -1, bc, h->heat_chan ? h->heat_chan[u] : -1,
+                                              h->cool_chan ? h->cool_chan[u] : -1};
+        const double f64[kHandlerF64Rows] = {h->eff_gain ? h->eff_gain[u] : 1.0, bc >= 0 ? h->bypass_band[u] / 2.0 : 0.0,
+                                             bc >= 0 ? h->bypass_min_delta[u] : 0.0, h->heat_cap ? h->heat_cap[u] : inf,
+                                             h->cool_cap ? h->cool_cap[u] : inf};
+        for (int a = 0; a < kHandlerI32Rows; a++)
+            if (t.i32[a * U + u] != i32[a]) return failp(err, HEAT_E_SIZE, "air handler tables: air handler %zu: row %d is not the caller's", u, a);
+        for (int a = 0; a < kHandlerF64Rows; a++)
+            if (std::memcmp(&t.f64[a * U + u], &f64[a], sizeof(double)) != 0)
+                return failp(err, HEAT_E_SIZE, "air handler tables: air handler %zu: real row %d is not the caller's", u, a);
+    }
+    return HEAT_OK;
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -3131,6 +3303,20 @@ int heat_comfort_check(const heat_batch_desc *desc, const heat_series *s, const 
     heat::ComfortTables t;
     heat::build_comfort_tables(desc->n_zones, c, nullptr, nullptr, m.first_node_slot, m.node_count, t);
     return heat::check_comfort_tables(desc->n_zones, c, t, heat::last_error());
+}
+
+int heat_air_handlers_check(const heat_batch_desc *desc, const heat_series *s, const heat_air_handlers *h) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    rc = heat::check_air_handlers(desc->n_zones, s->n_channels, h, heat::last_error());
+    if (rc || !h) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see)
+    heat::HandlerTables t;
+    heat::build_air_handler_tables(desc->n_zones, h, t);
+    return heat::check_air_handler_tables(desc->n_zones, h, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

@@ -187,6 +187,34 @@ void build_air_path_tables(int64_t n_zones, const heat_air_paths *air, AirPathTa
 // kept inside a zone, the offsets monotone and inside the buffers. HEAT_OK or HEAT_E_SIZE.
 int check_air_path_tables(int64_t n_zones, const heat_air_paths *air, const AirPathTables &t, std::string &err);
 
+// Air handlers of a series (heat_air_handlers, include/heat_amd.h). Everything heat_air_handlers_check promises about the
+// term itself; h == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "air handler u" or "air handler
+// branch j".
+int check_air_handlers(int64_t n_zones, int32_t n_channels, const heat_air_handlers *h, std::string &err);
+// The tables of k_series_handler_units (one lane per unit) and k_series_handler_supply (one lane per zone): ALL branches stably
+// sorted by unit and the SUPPLY branches (kind bit 0) stably sorted by zone — two counting sorts, the caller's order survives
+// inside a range — each with CSR offsets; orig keeps the caller's number of a branch: m, branch_q and sum_branch_q stay in
+// the caller's order. The units' rows in the caller's order: a NULL eff_gain is ones here, a NULL channel list -1, a NULL
+// capacity +inf; half band (band / 2, the one operation the header gives it) and min_delta 0 where the unit has no bypass.
+enum HandlerI32 : int { AH_OUTDOOR_CHAN, AH_EFF_CHAN, AH_BYPASS_CHAN, AH_HEAT_CHAN, AH_COOL_CHAN, kHandlerI32Rows };
+enum HandlerF64 : int { AH_EFF_GAIN, AH_HALF_BAND, AH_MIN_DELTA, AH_HEAT_CAP, AH_COOL_CAP, kHandlerF64Rows };
+struct HandlerTables {
+    std::vector<int32_t> unit_off;                  // [n_units + 1]
+    std::vector<int32_t> u_zone, u_chan, u_orig;    // [n_branches] by unit
+    std::vector<uint8_t> u_kind;                    // [n_branches]
+    std::vector<double> u_gain;                     // [n_branches]
+    std::vector<int32_t> zone_off;                  // [n_zones + 1]
+    std::vector<int32_t> z_unit, z_orig;            // [n_supply] by zone
+    std::vector<int32_t> i32;                       // [kHandlerI32Rows][n_units]
+    std::vector<double> f64;                        // [kHandlerF64Rows][n_units]
+};
+// (of a term that passed check_air_handlers)
+void build_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, HandlerTables &t);
+// The tables against the caller's lists (used by the host-only check): every branch present exactly once in its unit's
+// range, every supply branch exactly once in its zone's, both in the caller's order, the offsets monotone and inside the
+// buffers, every row the caller's. HEAT_OK or HEAT_E_SIZE.
+int check_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, const HandlerTables &t, std::string &err);
+
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
 // themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".
 // load_of_zone (nullable): [n_zones], the load of every zone or -1 — the table k_zone_update_ideal looks its zone up in.

@@ -1163,6 +1163,108 @@ int heat_batch_march_series_comfort(heat_batch *b, const heat_series_call *call,
                                     double *operative /* [n_steps][n_sensors], nullable */,
                                     double *mrt /* [n_steps][n_sensors], nullable */);
 
+/*
+ * Air handlers of a series: mechanical ventilation with HEAT RECOVERY — a unit that extracts air from zones, passes it through
+ * an exchanger against the outdoor air it takes in, and supplies that air to zones, past a summer bypass and a supply-air coil.
+ * A flow of heat_zone_loads and a supply path of heat_air_paths (source == -1) take their inlet temperature from a channel; a
+ * recovery unit supplies at T_out + eta * (T_extract - T_out), and T_extract is the flow-weighted mix of zone temperatures only
+ * the device holds when the step starts. The bypass and the coil's power depend on the same temperatures: none of it can be a
+ * schedule. The reference has no counterpart (heating_cooling.rs is a todo!(), model.rs:522-544 knows scheduled flows only);
+ * the rule below is this library's own contract, defined against the per-call loop with the same rule written on the host
+ * (heat_amd/air_handlers.py, apply()). The air properties are the reference's (gas.rs:49,165-179), written exactly as the
+ * zone loads and the air paths write them.
+ * A UNIT u has an outdoor-air temperature channel, a recovery effectiveness (a constant gain times an optional channel), an
+ * optional bypass controller with hysteresis, an optional heating coil (a minimum supply temperature channel and a capacity in
+ * W) and an optional cooling coil (a maximum supply temperature channel and a capacity in W). A BRANCH j joins a unit to a
+ * zone: a volume channel times a gain, m3/s, and a kind byte — it supplies (bit 0), extracts (bit 1) or both (3).
+ * The rule of step k, behind the air paths and before the ambient drive — a zone's sum is ((row + loads) + paths) + branches.
+ * T = the zone AIR temperatures the device holds then (what step k - 1 left; no control temperature: a unit senses air),
+ * row = channel[k]. Every line is ONE rounded f64 operation in the order written, no fused multiply-add; a NaN makes every
+ * comparison false:
+ *   per unit u:
+ *     To = row[outdoor_chan]
+ *     st = 0.0;  sv = 0.0
+ *     per EXTRACT branch j of u, in the caller's order:
+ *         V = br_volume_gain[j] * row[br_volume_chan[j]];  x = V * T[br_zone[j]];  st = st + x;  sv = sv + V
+ *     Te = sv > 0.0 ? st / sv : To                      (no extraction: nothing to recover from)
+ *     eta = eff_gain[u]
+ *     eff_chan >= 0:  eta = eta * row[eff_chan]
+ *     if eta < 0.0: eta = 0.0
+ *     if eta > 1.0: eta = 1.0
+ *     bypass (bypass_chan >= 0):
+ *         set = row[bypass_chan];  d = bypass_band / 2;  e = Te - set;  g = Te - To
+ *         if      e > d and g > bypass_min_delta             state = 1
+ *         else if state == 1 and (e < -d or g <= 0.0)        state = 0
+ *         state == 1: eta = 0.0
+ *     dT = Te - To;  r = eta * dT;  Tr = To + r         (behind the exchanger; the fan stands here)
+ *     Tk = Tr + 273.15;  rho = 101325 * 28.97 / (8314.46261815324 * Tk);  cp = 1002.7370 + 1.2324e-2 * Tk
+ *     M = 0.0
+ *     per SUPPLY branch j of u, in the caller's order:
+ *         V = gain * row[chan];  m[j] = (rho * V) * cp;  M = M + m[j]
+ *     recovered = M * r                                 (W, positive when the exchanger warms the supply)
+ *     Ts = Tr;  q = 0.0
+ *     if heat_chan >= 0 and Tr < row[heat_chan]:
+ *         lift = row[heat_chan] - Tr;  need = M * lift
+ *         if need <= heat_cap:  Ts = row[heat_chan];  q = need
+ *         else:                 q = heat_cap;  x = heat_cap / M;  Ts = Tr + x;  heat-saturated
+ *     else if cool_chan >= 0 and Tr > row[cool_chan]:
+ *         drop = Tr - row[cool_chan];  need = M * drop
+ *         if need <= cool_cap:  Ts = row[cool_chan];  q = 0.0 - need
+ *         else:                 q = 0.0 - cool_cap;  x = cool_cap / M;  Ts = Tr - x;  cool-saturated
+ *     supply_t[k][u] = Ts;  recovered[k][u] = recovered;  coil_q[k][u] = q
+ *     sum_recovered += recovered;  sum_heating += q where q > 0;  sum_cooling += q where q < 0
+ *     steps_bypass += state;  switches += (state after != before);  steps_*_saturated += 1 where saturated
+ *   per zone z, its SUPPLY branches in the caller's order:
+ *     mt = m[j] * Ts[unit];  a0[z] = a0[z] + mt;  b0[z] = b0[z] + m[j]
+ *     dz = Ts[unit] - T[z];  bq = m[j] * dz
+ *     branch_q[k][j] = bq;  sum_branch_q[j] = sum_branch_q[j] + bq
+ * An extract-only branch adds nothing to its zone — only inflows appear in the balance — and its branch_q is 0.0. Every T is
+ * the start of the step's value, whatever the order of units and zones. The terms hold for all n_sub sub-timesteps of the
+ * step: ideal loads see them. n_sub == 0 still evaluates every step. bypass and every accumulator carry a cut: a series of k
+ * steps followed by one of n - k with the returned arrays gives the bits of the series of n. bypass == NULL: every unit starts
+ * recovering and nothing is returned. A unit without a bypass controller recovers whatever its byte says and leaves the byte
+ * as it is (steps_bypass still adds the byte: pass 0). A supply branch that turns a clean a0 or b0 into NaN is HEAT_N_NAN_ZONE for that zone at that step, as for the
+ * air paths; a NaN in a unit without supply branches reaches its rows only. An array that is not asked for costs no traffic
+ * and changes no bit of the others. With h == NULL or n_units == 0 heat_batch_march_series_handlers is
+ * heat_batch_march_series_comfort exactly: same launches, same bits. A refused call leaves the device state untouched. Sharded
+ * batches are refused as by the series; weather sites need nothing.
+ * heat_air_handlers_check (host-only; it also builds and verifies the tables the march uploads) and
+ * heat_batch_march_series_handlers run the same checks before any device work; every message names "air handler u" or "air
+ * handler branch j". HEAT_E_INVALID_ARG: a negative count; a NULL array that a positive count needs (outdoor_chan; br_unit,
+ * br_zone, br_volume_chan); NULL bypass_band or bypass_min_delta where some unit bypasses; an eff_gain, br_volume_gain, band or
+ * min_delta that is not finite; a negative band or min_delta; a negative or NaN capacity; a br_kind outside 1..3; a bypass
+ * byte above 1; branches with n_units == 0. HEAT_E_SIZE: a unit, zone or channel out of range (eff_chan, bypass_chan,
+ * heat_chan and cool_chan may be -1).
+ * Out of scope: frost protection of the exchanger, fan heat, latent recovery, variable-volume control by a zone, and a unit
+ * whose mass flow follows the coil outlet (every m[j] is taken at the exchanger's outlet, Tr).
+ */
+typedef struct heat_air_handlers {
+    int64_t n_units;
+    const int32_t *outdoor_chan;        /* [n_units] outdoor-air temperature, C */
+    const int32_t *eff_chan;            /* nullable / -1: eta = eff_gain */
+    const double  *eff_gain;            /* nullable = 1 */
+    const int32_t *bypass_chan;         /* nullable / -1: no bypass; else the setpoint of the extract air, C */
+    const double  *bypass_band, *bypass_min_delta;   /* K >= 0; read only where bypass_chan >= 0 */
+    const int32_t *heat_chan, *cool_chan;            /* nullable / -1: no coil; minimum / maximum supply temperature, C */
+    const double  *heat_cap, *cool_cap;              /* W >= 0, +inf allowed; nullable = +inf */
+    int64_t n_branches;
+    const int32_t *br_unit, *br_zone, *br_volume_chan;
+    const double  *br_volume_gain;      /* nullable = 1 */
+    const uint8_t *br_kind;             /* nullable = 3; 1 supplies, 2 extracts, 3 both */
+    uint8_t *bypass;                    /* [n_units] in/out, nullable (= all recovering): 0 / 1 */
+    double  *sum_recovered, *sum_heating, *sum_cooling;            /* [n_units] in/out, nullable */
+    int64_t *steps_bypass, *switches, *steps_heat_saturated, *steps_cool_saturated;
+    double  *sum_branch_q;              /* [n_branches] in/out, nullable */
+} heat_air_handlers;
+
+int heat_air_handlers_check(const heat_batch_desc *desc, const heat_series *s, const heat_air_handlers *h); /* host-only */
+int heat_batch_march_series_handlers(heat_batch *b, const heat_series_call *call, heat_comfort *c /* nullable */,
+                                     double *operative, double *mrt, heat_air_handlers *h /* nullable */,
+                                     double *supply_t  /* [n_steps][n_units], nullable */,
+                                     double *recovered /* [n_steps][n_units], nullable */,
+                                     double *coil_q    /* [n_steps][n_units], nullable */,
+                                     double *branch_q  /* [n_steps][n_branches], nullable */);
+
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -114,6 +114,17 @@ pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
     pub max_operative: *mut f64, pub step_max: *mut i64, pub n_below: *mut i64, pub deg_below: *mut f64,
     pub n_above: *mut i64, pub deg_above: *mut f64, pub max_above: *mut f64, pub step_max_above: *mut i64,
 }
+// heat_air_handlers: ventilation units with heat recovery, a bypass and supply-air coils, and their branches into the zones
+#[repr(C)] pub struct HeatAirHandlers {
+    pub n_units: i64, pub outdoor_chan: *const i32, pub eff_chan: *const i32, pub eff_gain: *const f64,
+    pub bypass_chan: *const i32, pub bypass_band: *const f64, pub bypass_min_delta: *const f64,
+    pub heat_chan: *const i32, pub cool_chan: *const i32, pub heat_cap: *const f64, pub cool_cap: *const f64,
+    pub n_branches: i64, pub br_unit: *const i32, pub br_zone: *const i32, pub br_volume_chan: *const i32,
+    pub br_volume_gain: *const f64, pub br_kind: *const u8,
+    pub bypass: *mut u8, pub sum_recovered: *mut f64, pub sum_heating: *mut f64, pub sum_cooling: *mut f64,
+    pub steps_bypass: *mut i64, pub switches: *mut i64, pub steps_heat_saturated: *mut i64, pub steps_cool_saturated: *mut i64,
+    pub sum_branch_q: *mut f64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -202,6 +213,11 @@ extern "C" {
     pub fn heat_comfort_check(desc: *const HeatBatchDesc, s: *const HeatSeries, c: *const HeatComfort) -> c_int;
     pub fn heat_batch_march_series_comfort(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
                                            operative: *mut f64, mrt: *mut f64) -> c_int;
+    // air handlers of a series: heat recovery, bypass and supply coils from the zone temperatures the device holds
+    pub fn heat_air_handlers_check(desc: *const HeatBatchDesc, s: *const HeatSeries, h: *const HeatAirHandlers) -> c_int;
+    pub fn heat_batch_march_series_handlers(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
+                                            operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
+                                            recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

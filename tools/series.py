@@ -104,8 +104,15 @@ and writes profiles/series_comfort.json: ms per step of each, C - N, a series of
 the calls are set up, the bytes a step of the two kernels moves, and — where the kernel trace of one C series has been taken
 (--one-series --comfort under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_comfort_kernel_stats.csv) —
 k_series_comfort and k_series_control_T per step. No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort]
+With --handlers (heat_batch_march_series_handlers, heat_air_handlers; the loads of --loads) it alternates
+  N  the series with loads through heat_batch_march_series_handlers, handlers = NULL
+  H  the same call with one unit for every five zones: five balanced branches, a bypass, a heating and a cooling coil each
+and writes profiles/series_handlers.json: ms per step of each, H - N, a series of ONE step of each (the call's set-up) and the
+per-step times once the set-up is taken off — and, where a kernel trace of one H series has been taken (--one-series --handlers
+under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_handlers_kernel_stats.csv), k_series_handler_units
+and k_series_handler_supply per step. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
@@ -116,7 +123,7 @@ k_series_comfort and k_series_control_T per step. No time is a pass criterion.
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, air_handlers as ahm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -129,7 +136,8 @@ SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
 COMFORT = "--comfort" in sys.argv
-LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT or COMFORT
+HANDLERS = "--handlers" in sys.argv
+LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT or COMFORT or HANDLERS
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 S = int(ARGS[0]) if len(ARGS) > 0 else 1_000_000
@@ -287,6 +295,27 @@ if COMFORT:
         dt = time.perf_counter() - t0
         assert out[1] == -1 and np.all(np.isfinite(out[0]))
         assert comfort is None or (out[4]["n_occupied"] > 0).all()
+        return dt * 1e3 / steps
+if HANDLERS:
+    # five more channels (outdoor air, the bypass setpoint of the extract air, the minimum and the maximum supply temperature,
+    # the volume flow of a branch) and one unit for every five zones: five balanced branches, a bypass and both coils
+    c_ah = channel.shape[1]
+    channel = np.concatenate([channel, rng.uniform(-5.0, 30.0, (STEPS, 1)), rng.uniform(21.0, 25.0, (STEPS, 1)), rng.uniform(16.0, 18.0, (STEPS, 1)),
+                              rng.uniform(22.0, 26.0, (STEPS, 1)), rng.uniform(0.01, 0.05, (STEPS, 1))], axis=1)
+    NU = max(1, Z // 5)
+    handler_args = ahm.concat(*[ahm.balanced(np.arange(5 * u, min(5 * u + 5, Z)), c_ah + 4, c_ah, eff_gain=0.8, bypass_chan=c_ah + 1, bypass_band=0.5,
+                                             bypass_min_delta=0.5, heat_chan=c_ah + 2, cool_chan=c_ah + 3, heat_cap=2000.0, cool_cap=1500.0)
+                                for u in range(NU)])
+
+    def leg_ah(b, w, n_sub, steps, handlers="given"):
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads,
+                             handlers=handler_args if handlers == "given" else handlers, supply_t=False, recovered=False, coil_q=False,
+                             branch_q=False, **drives)
+        dt = time.perf_counter() - t0
+        assert out[1] == -1 and np.all(np.isfinite(out[0]))
+        assert handlers is None or np.all(np.isfinite(out[4]["sum_branch_q"]))
         return dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
@@ -566,6 +595,30 @@ with HeatBatch(md) as b:
             print("n_sub %2d: N comfort NULL %.3f ms/step, C comfort %.3f -> C - N = %+.3f ms, C / N = %.4f; a series of one step: "
                   "N %.2f ms, C %.2f ms -> per step without the set-up N %.3f, C %.3f, C - N = %+.3f (%d sensors, %d entries, %d steps, "
                   "median of %d rounds)" % (n_sub, N_, C_, C_ - N_, C_ / N_, N1, C1, Ns, Cs, Cs - Ns, Z, NE, STEPS, ROUNDS), flush=True)
+            continue
+        if HANDLERS:
+            leg_ah(b, w, n_sub, min(STEPS, 10), {})  # warm-up
+            leg_ah(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with air handlers: H %.3f ms per step" % leg_ah(b, w, n_sub, STEPS))
+                continue
+            nn, hh, nn1, hh1 = [], [], [], []
+            for r in range(ROUNDS):
+                nn.append(leg_ah(b, w, n_sub, STEPS, {}))
+                hh.append(leg_ah(b, w, n_sub, STEPS))
+                nn1.append(leg_ah(b, w, n_sub, 1, {}))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                hh1.append(leg_ah(b, w, n_sub, 1))
+            N_, H_, N1, H1 = (float(np.median(v)) for v in (nn, hh, nn1, hh1))
+            Ns, Hs = (N_ * STEPS - N1) / (STEPS - 1), (H_ * STEPS - H1) / (STEPS - 1)  # per step once the call is set up
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                N_handlers_null_ms=N_, H_handlers_ms=H_, H_minus_N_ms=H_ - N_, H_over_N=H_ / N_, N_series_of_one_step_ms=N1,
+                H_series_of_one_step_ms=H1, H_minus_N_series_of_one_step_ms=H1 - N1, N_without_setup_ms=Ns, H_without_setup_ms=Hs,
+                H_minus_N_without_setup_ms=Hs - Ns, units=int(NU), branches=int(len(handler_args["br_unit"])),
+                all_rounds=dict(N=nn, H=hh, N_one_step=nn1, H_one_step=hh1))
+            print("n_sub %2d: N handlers NULL %.3f ms/step, H handlers %.3f -> H - N = %+.3f ms, H / N = %.4f; a series of one step: "
+                  "N %.2f ms, H %.2f ms -> per step without the set-up N %.3f, H %.3f, H - N = %+.3f (%d units, %d branches, %d steps, "
+                  "median of %d rounds)" % (n_sub, N_, H_, H_ - N_, H_ / N_, N1, H1, Ns, Hs, Hs - Ns, NU, len(handler_args["br_unit"]), STEPS, ROUNDS),
+                  flush=True)
             continue
         if IDEAL:
             leg_i(bs, w, n_sub, min(STEPS, 10))  # warm-up
@@ -1012,9 +1065,25 @@ if AMBIENT and not ONE:
         print("kernel trace: k_series_ambient %.2f us per step" % us)
     else:
         print("no kernel trace at %s" % stats)
+if HANDLERS and not ONE:
+    # the kernel trace of one H series (--one-series --handlers under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: the two kernels per step, beside the same trace's k_series_zone_loads
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_handlers_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_handler_units", "k_series_handler_supply", "k_series_zone_loads")}
+        result["kernel_trace_of_one_H_series"] = dict({"%s_us_per_step" % k: v for k, v in us.items()}, calls=int(rows["k_series_handler_units"]["Calls"]))
+        print("kernel trace: k_series_handler_units %.2f us per step, k_series_handler_supply %.2f, k_series_zone_loads %.2f" % (
+            us["k_series_handler_units"], us["k_series_handler_supply"], us["k_series_zone_loads"]))
+    else:
+        result["kernel_trace_of_one_H_series"] = "not measured"
+        print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
