@@ -145,6 +145,8 @@ struct DevBuf {
 // cluster-resident call costs 155 us + 59 us per sub-timestep, the same batch streamed 198-212 us per sub-timestep (its layout
 // pads every cluster to whole wavefronts; laid out for streaming alone it takes 166-188) -> resident from two sub-timesteps on.
 static const int kFusedMinSubsteps = getenv("HEAT_AMD_FUSED_MIN") ? atoi(getenv("HEAT_AMD_FUSED_MIN")) : 2;
+// ... and from which a list of more blocks than the chip holds is marched by persistent workgroups (enqueue_fused)
+constexpr int kFusedQueueMinSubsteps = 12;
 
 }  // namespace
 
@@ -185,7 +187,8 @@ struct heat_batch {
     int xbuf_teams = 0;                 // teams the exchange areas are sized for
     uint32_t team_epoch = 0;            // launches so far: names the granules of a launch (tag_base)
     bool any_teams = false;
-    DevBuf<unsigned int> d_fqueue;      // work-queue counters of the fused launches (sharded batches): one per list
+    DevBuf<unsigned int> d_fqueue;      // work-queue counters of the fused launches: one per list, never reset ...
+    unsigned int fqueue_base[kNumFast * 4] = {};  // ... the tickets the list's launches so far have drawn (FusedArgs::queue_base)
     DevBuf<int32_t> d_fzones, d_fzone_eoff;
     DevBuf<uint16_t> d_fslots;
     DevBuf<double> d_side_area;
@@ -942,8 +945,17 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
         }
         streamed_share = ns / std::max(ns + nf, 1.0);
     }
+    // A list of more blocks than the chip holds at once is marched by exactly that many workgroups, which take their
+    // blocks from the same queue — in calls of kFusedQueueMinSubsteps sub-timesteps or more: a workgroup that follows
+    // another into its slot costs the write-back's acknowledgement, a dispatch and the kernel arguments before its first
+    // load, a workgroup that stays two barriers and the ticket's round trip; the first is the dearer one only where the
+    // blocks live long (0.5 us per sub-timestep won at 20 per call, 2 lost at 2).
+    // HEAT_AMD_FUSED_PERSIST (measurement, tests): the call length from which on; 0: never.
+    static const int persist_env = getenv("HEAT_AMD_FUSED_PERSIST") ? atoi(getenv("HEAT_AMD_FUSED_PERSIST")) : -1;
+    const int persist_min = persist_env >= 0 ? persist_env : kFusedQueueMinSubsteps;
+    const bool persist = persist_min > 0 && n_sub >= persist_min;
     const int n_cu = b->n_cu;
-    if (beside_exchange && b->d_fqueue.n == 0) HIP_TRY(b->d_fqueue.zeros(kNumFast * 4));
+    if (b->d_fqueue.n == 0) HIP_TRY(b->d_fqueue.zeros(kNumFast * 4));
     for (int c = 0; c < kNumFast; c++)
         for (int g2 = 0; g2 < 4; g2++) {
             const int nb = (int)b->h_fblocks[c][g2].size();
@@ -952,16 +964,16 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
             fa.n_blocks = nb;
             fa.queue = nullptr;
             int grid = nb;
-            if (beside_exchange) {
+            if (beside_exchange || persist) {
                 const int fw = (g2 & 1) ? 8 : 4;
                 static const int room_env = getenv("HEAT_AMD_FUSED_ROOM") ? atoi(getenv("HEAT_AMD_FUSED_ROOM")) : 0;  // tests
                 const int room = room_env > 0 ? room_env : n_cu * fused_blocks_per_cu(kFastM[c], kFastCAV[c], g2 >> 1, fw, b->na.pal_stride);
-                const int reserve = reserve_env >= 0 ? reserve_env
+                const int reserve = !beside_exchange ? 0 : reserve_env >= 0 ? reserve_env
                                                      : std::min(room / 2, std::max(fw == 4 ? 16 : 8, (int)(room * streamed_share)));
                 if (nb > room - reserve) {
                     grid = std::max(1, room - reserve);
                     fa.queue = b->d_fqueue.p + c * 4 + g2;
-                    HIP_TRY(hipMemsetAsync(fa.queue, 0, sizeof(unsigned int), st));
+                    fa.queue_base = b->fqueue_base[c * 4 + g2];
                 }
             }
             static const bool trace = getenv("HEAT_AMD_TRACE") != nullptr;
@@ -974,6 +986,7 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
             HIP_TRY(launch_surfaces_fused(kFastM[c], nm_variant, kFastCAV[c], g2 >> 1, (g2 & 1) ? 8 : 4, grid, b->d_fast_tiles[c].p, b->n_fast_tiles[c],
                                           b->na, b->sa, b->d_weather.p, b->d_flags.p,
                                           b->d_nomass_iters.p + b->nm_count_base[c], fa, st));
+            if (fa.queue) b->fqueue_base[c * 4 + g2] += (unsigned int)nb;  // one ticket per block marched (layout.hpp)
         }
     // Teams (clusters larger than a workgroup): n_teams x kTeamMax workgroups, ALL of them on the chip at once — a member
     // waits for the others' zone sums, so no workgroup of the launch may have to wait for a slot a waiting one holds.

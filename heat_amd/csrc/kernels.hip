@@ -542,10 +542,33 @@ struct TeamCtx {
 __device__ __forceinline__ unsigned long long team_granule(unsigned int data, unsigned int tag) {
     return ((unsigned long long)tag << 32) | data;
 }
+// Priority: the zone work is the one serial segment a whole workgroup waits for, and the SIMD it runs on is shared with
+// a wavefront of the compute unit's other workgroup, which is in its RK4 meanwhile. VALU issue between the two goes by
+// priority, then age: at equal priority the younger workgroup's zone work gets the slots the older one's RK4 leaves
+// (DESIGN.md 4a). A wavefront with zone work runs it at priority kZonePrio; every wavefront is back at 0 before the
+// closing barrier. s_setprio ignores EXEC, so every raise sits behind a branch on a wave-uniform (readfirstlane)
+// condition. Teams stay at 0 throughout: a member polls for the others' sums (gather), which nothing may do at raised
+// priority, and the raise around the rest of its zone work did not pay.
+// clk (diagnostic build, HEAT_STAMPS): ticks waited at the opening barrier and ticks between the two barriers, added up.
+constexpr int kZonePrio = 2;
+__device__ __forceinline__ void zone_prio_raise(bool lead) {
+    // (the flag itself through readfirstlane: where the compiler keeps a loop counter in a vector register the branch
+    // would otherwise become an EXEC mask around an unconditional s_setprio)
+    if (__builtin_amdgcn_readfirstlane((int)lead)) __builtin_amdgcn_s_setprio(kZonePrio);
+}
+__device__ __forceinline__ void zone_prio_drop() { __builtin_amdgcn_s_setprio(0); }
 template <int TEAM>
 __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const FusedArgs &fa, const FusedLds &l, int wib,
-                                                 int n_waves, int lane, int &bad_all, const TeamCtx &tc_) {
+                                                 int n_waves, int lane, int &bad_all, const TeamCtx &tc_,
+                                                 unsigned long long *clk = nullptr) {
+#ifdef HEAT_STAMPS
+    const unsigned long long t_in = __builtin_amdgcn_s_memtime();
+#endif
     __syncthreads();
+#ifdef HEAT_STAMPS
+    const unsigned long long t_open = __builtin_amdgcn_s_memtime();
+#endif
+    const int wib_u = __builtin_amdgcn_readfirstlane(wib), nz_u = __builtin_amdgcn_readfirstlane(blk.n_zones);
     // TEAM: a zone faced from several members is balanced from all their sums. Every member PUBLISHES its sums of ALL its
     // zones before it waits for anybody's (two passes below): a member that waited zone by zone could wait for a sum its
     // partner publishes only after a zone it is itself still to reach — two members that share two zones and meet them in
@@ -605,6 +628,7 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
         l.zT[j] = ft;
     };
     if (blk.n_zones <= n_waves) {
+        if constexpr (!TEAM) zone_prio_raise(wib_u < nz_u);  // this wavefront has a zone
         if (wib < blk.n_zones) {
             const int j = wib;
             const int e0 = l.zoff[j], e1 = l.zoff[j + 1];
@@ -627,6 +651,7 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
                 finish(j, a, b, tc, cz);
             }
         }
+        if constexpr (!TEAM) zone_prio_drop();
     } else {
         const int row = lane >> 4, rl = lane & 15;
         const bool one_pass = blk.n_zones <= 4 * n_waves;  // (workgroup-uniform) the loop below runs once
@@ -635,6 +660,7 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
         for (int j0 = 0; j0 < blk.n_zones; j0 += 4 * n_waves) {  // (workgroup-uniform trip count)
             const int j = j0 + 4 * wib + row;
             const bool on = j < blk.n_zones;
+            if constexpr (!TEAM) zone_prio_raise(j0 + 4 * wib_u < nz_u);  // a row of this wavefront has a zone in this pass
             const int jj = on ? j : 0;
             const int e0 = l.zoff[jj], e1 = on ? l.zoff[jj + 1] : e0;
             const double tc = l.zT[jj];
@@ -662,6 +688,7 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
                 }
             } else {
                 if (on && rl == 15) finish(j, a, b, tc, cz);
+                zone_prio_drop();
             }
         }
         if constexpr (TEAM) {
@@ -680,6 +707,12 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
             }
         }
     }
+#ifdef HEAT_STAMPS
+    if (clk) {
+        clk[0] += t_open - t_in;
+        clk[1] += __builtin_amdgcn_s_memtime() - t_open;
+    }
+#endif
     __syncthreads();
 }
 
@@ -748,8 +781,15 @@ __device__ void fused_small_wave(const FusedBlock &blk, const FusedArgs &fa, con
 // wavefront 0 of every cluster-resident workgroup stamps the shader clock at its phases and the 100 MHz real-time
 // clock at both ends into a buffer nothing else reads. In the product build no stamp exists.
 #ifdef HEAT_STAMPS
-constexpr int kStampsPerBlock = 8;
+constexpr int kStampsPerBlock = 16;
 __device__ unsigned long long g_stamps[65536 * kStampsPerBlock];
+#define HEAT_STAMP_VALUE(k, v)                                                                                \
+    do {                                                                                                      \
+        if constexpr (FUSED) {                                                                                \
+            if (threadIdx.x == 0 && (counter_index >> 2) < 65536)                                             \
+                g_stamps[(counter_index >> 2) * kStampsPerBlock + (k)] = (v);                                 \
+        }                                                                                                     \
+    } while (0)
 #define HEAT_STAMP(k, real)                                                                                   \
     do {                                                                                                      \
         if constexpr (FUSED) {                                                                                \
@@ -760,6 +800,7 @@ __device__ unsigned long long g_stamps[65536 * kStampsPerBlock];
     } while (0)
 #else
 #define HEAT_STAMP(k, real) do { } while (0)
+#define HEAT_STAMP_VALUE(k, v) do { } while (0)
 #endif
 // Diagnostic build only (-DHEAT_STREAM_STAMPS -> lib/libheat_amd_sstamps.so; tools/stream_phases.py): lane 0 of every
 // STREAMED fast tile stamps the shader clock at the tile's phases — 0 start, 1 loads arrived, 6 boundary terms / no-mass
@@ -1019,6 +1060,8 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
 
     HEAT_STAMP(1, false);
     HEAT_SSTAMP(1, true);
+    unsigned long long chain_clk[2] = {0ull, 0ull};  // (diagnostic build only: fused_zone_phase, clk)
+    (void)chain_clk;
     // The side record: FUSED fetches it again for every sub-timestep (an L1/L2 hit) instead of holding its 20 registers
     // across the RK stages — at the END of the sub-timestep before, so that it travels while the zone balance is summed.
     SideConst c_cur = c_load;
@@ -1416,13 +1459,15 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
         if constexpr (SMALL == 2) {
             TeamCtx tcx = team;
             tcx.it = it;
-            fused_zone_phase<1>(blk, fa, fl, wib, blk_waves, lane, bad_all, tcx);
+            fused_zone_phase<1>(blk, fa, fl, wib, blk_waves, lane, bad_all, tcx, chain_clk);
         } else {
-            fused_zone_phase<0>(blk, fa, fl, wib, blk_waves, lane, bad_all, team);
+            fused_zone_phase<0>(blk, fa, fl, wib, blk_waves, lane, bad_all, team, chain_clk);
         }
     }
     }  // sub-timesteps
     HEAT_STAMP(2, false);
+    HEAT_STAMP_VALUE(8, chain_clk[0]);  // wavefront 0: ticks waited at the zone phase's opening barrier, over the march
+    HEAT_STAMP_VALUE(9, chain_clk[1]);  // ... and between its two barriers: the serial zone chain
     HEAT_SSTAMP(2, false);
 
     if constexpr (FUSED) {
@@ -1523,7 +1568,8 @@ k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, 
     const bool write_out = FUSED || step_fixed >= 0 || step0 == step_ptr[1];
     // Streaming (FUSED = 0), persistent waves: each walks the tile list with a grid stride, so the write-back of
     // one tile (a wave cannot retire before its stores are acknowledged) overlaps the loads of the next.
-    // FUSED: one pass per FusedBlock; with a work queue (sharded batches, fa.queue) the workgroup takes further ones.
+    // FUSED: one pass per FusedBlock; with a work queue (lists of more blocks than the chip holds, sharded batches:
+    // fa.queue) the workgroup takes further ones.
     // TEAM (SMALL == 2): the workgroup is member blockIdx.x % team_size of team blockIdx.x / team_size; the team walks the
     // clusters (FusedSuper) team, team + n_teams, ... — every member in the same order, so that the members of a cluster
     // are always at work on it together (layout.hpp).
@@ -1592,7 +1638,7 @@ next_block:
         } else {
             if (fa.queue == nullptr) break;
             __syncthreads();  // every wavefront is done with this block's LDS
-            if (threadIdx.x == 0) s_next_block = (int)(gridDim.x + atomicAdd(fa.queue, 1u));
+            if (threadIdx.x == 0) s_next_block = (int)(gridDim.x + (atomicAdd(fa.queue, 1u) - fa.queue_base));
             __syncthreads();
             bi = s_next_block;
         }
