@@ -7,8 +7,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libheat_amd.so")
-SOURCES = ["kernels.hip", "batch.hip", "plan.cpp", "setup.cpp"]
-HEADERS = ["layout.hpp", "kernels.hpp", "device_math.hpp", "plan.hpp", os.path.join("..", "..", "include", "heat_amd.h"),
+SOURCES = ["kernels.hip", "batch.hip", "series.hip", "plan.cpp", "setup.cpp"]
+HOST_SOURCES = ["plan.cpp"]  # host-only: g++ compiles them too (build_plan_host, the tests' sanitizer programs)
+HEADERS = ["layout.hpp", "kernels.hpp", "device_math.hpp", "plan.hpp", "batch.hpp", os.path.join("..", "..", "include", "heat_amd.h"),
            os.path.join("..", "..", "include", "heat_amd_setup.h")]
 
 
@@ -88,17 +89,17 @@ PLAN_HOST_LIB = os.path.join(LIB_DIR, "libheat_plan_host.so")
 
 
 def build_plan_host(force=False):
-    """The planner on its own (csrc/plan.cpp, host-only), compiled by g++ with AddressSanitizer + UBSan: the library
+    """The planner on its own (HOST_SOURCES, host-only), compiled by g++ with AddressSanitizer + UBSan: the library
     tests/test_planner_host.py loads in a child process (LD_PRELOAD of libasan). Not part of the product."""
-    src = os.path.join(CSRC, "plan.cpp")
-    deps = [src, os.path.join(CSRC, "plan.hpp"), os.path.join(CSRC, "layout.hpp"),
-            os.path.join(HERE, "..", "include", "heat_amd.h")]
+    srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES]
+    deps = srcs + [os.path.join(CSRC, "plan.hpp"), os.path.join(CSRC, "layout.hpp"),
+                   os.path.join(HERE, "..", "include", "heat_amd.h")]
     if not force and os.path.exists(PLAN_HOST_LIB) and os.path.getmtime(PLAN_HOST_LIB) >= max(map(os.path.getmtime, deps)):
         return PLAN_HOST_LIB
     os.makedirs(LIB_DIR, exist_ok=True)
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared", src,
-                           "-o", PLAN_HOST_LIB])
+                           "-fno-sanitize-recover=undefined", "-Wall", "-Wextra", "-Werror", "-fPIC", "-shared"] + srcs +
+                          ["-o", PLAN_HOST_LIB])
     return PLAN_HOST_LIB
 
 

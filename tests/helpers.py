@@ -1,9 +1,24 @@
 """Shared builders for tests: single-surface model dicts in the shape of the reference's unit tests."""
 import math
+import os
+import subprocess
 
 import numpy as np
 
-from heat_amd import modeldict as mdl
+from heat_amd import build as heat_build, modeldict as mdl
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def build_host_main(tmp_path, stem):
+    """tests/<stem>.cpp — a stand-alone program with its own main — compiled together with the library's host-only sources
+    (heat_amd.build.HOST_SOURCES) under AddressSanitizer / UBSan, the sanitizers' runtimes linked in. Returns the executable."""
+    exe = tmp_path / stem
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", stem + ".cpp")] + [os.path.join(heat_build.CSRC, s) for s in heat_build.HOST_SOURCES] +
+                          ["-o", str(exe)])
+    return exe
 
 BRICKWORK = dict(k=0.816, rho=1700., cp=800., front_thermal_abs=0., back_thermal_abs=0.)   # surface.rs:1061-1075
 POLYURETHANE = dict(k=0.0252, rho=17.5, cp=2400., front_thermal_abs=0., back_thermal_abs=0.)  # surface.rs:1048-1059

@@ -19,6 +19,7 @@ import pytest
 import heat_amd
 from heat_amd import air_handlers as ah, binding, modeldict as mdl
 import air_handlers_cases as ahc
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("heat_air_handlers_check", "heat_batch_march_series_handlers")
@@ -484,11 +485,7 @@ def test_the_generators_cases_are_accepted_and_their_controllers_move(oracle, mo
 
 def test_air_handlers_check_under_address_and_ub_sanitizers(tmp_path):
     """A stand-alone program with its own main, compiled together with the planner: nothing is preloaded."""
-    exe = tmp_path / "air_handlers_host_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "air_handlers_host_main.cpp"), os.path.join(ROOT, "heat_amd", "csrc", "plan.cpp"),
-                           "-o", str(exe)])
+    exe = helpers.build_host_main(tmp_path, "air_handlers_host_main")
     env = dict(os.environ)   # (the sanitizers' runtimes are linked into the program)
     env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=1"
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"

@@ -18,6 +18,7 @@ from heat_amd import binding, blinds as bl, modeldict as mdl, sky, solar_gains
 import blinds_cases as bc
 import shades_cases as sc
 from test_shades_host import good_gains, good_shades, good_sky, series
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("heat_blinds_check", "heat_batch_march_series_blinds")
@@ -434,11 +435,7 @@ def test_the_case_builder_takes_every_branch_of_the_rule(seed):
 
 def test_blinds_check_under_address_and_ub_sanitizers(tmp_path):
     """A stand-alone program with its own main, compiled together with the planner: nothing is preloaded."""
-    exe = tmp_path / "blinds_host_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "blinds_host_main.cpp"), os.path.join(ROOT, "heat_amd", "csrc", "plan.cpp"),
-                           "-o", str(exe)])
+    exe = helpers.build_host_main(tmp_path, "blinds_host_main")
     env = dict(os.environ)   # (the sanitizers' runtimes are linked into the program)
     env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=1"
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"

@@ -18,6 +18,7 @@ import pytest
 
 from heat_amd import air_paths, binding, comfort as cf, modeldict as mdl
 import comfort_cases as cc
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("heat_comfort_check", "heat_batch_march_series_comfort")
@@ -452,11 +453,7 @@ def test_every_decision_of_the_oracle_case_is_away_from_a_tie(oracle):
 
 def test_comfort_check_under_address_and_ub_sanitizers(tmp_path):
     """A stand-alone program with its own main, compiled together with the planner: nothing is preloaded."""
-    exe = tmp_path / "comfort_host_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "comfort_host_main.cpp"), os.path.join(ROOT, "heat_amd", "csrc", "plan.cpp"),
-                           "-o", str(exe)])
+    exe = helpers.build_host_main(tmp_path, "comfort_host_main")
     env = dict(os.environ)   # (the sanitizers' runtimes are linked into the program)
     env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=1"
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"

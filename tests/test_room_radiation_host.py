@@ -17,6 +17,7 @@ import pytest
 
 from heat_amd import binding, modeldict as mdl, room_radiation as rrm
 import room_radiation_cases as rc
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("heat_room_radiation_check", "heat_batch_march_series_radiation")
@@ -390,11 +391,7 @@ def test_the_case_builder_covers_what_it_promises(seed):
 
 def test_room_radiation_check_under_address_and_ub_sanitizers(tmp_path):
     """A stand-alone program with its own main, compiled together with the planner: nothing is preloaded."""
-    exe = tmp_path / "room_radiation_host_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "room_radiation_host_main.cpp"), os.path.join(ROOT, "heat_amd", "csrc", "plan.cpp"),
-                           "-o", str(exe)])
+    exe = helpers.build_host_main(tmp_path, "room_radiation_host_main")
     env = dict(os.environ)   # (the sanitizers' runtimes are linked into the program)
     env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=1"
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"

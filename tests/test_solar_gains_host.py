@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from heat_amd import binding, modeldict as mdl, sky, solar_gains
+import helpers
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("heat_solar_gains_check", "heat_batch_march_series_gains")
@@ -358,11 +359,7 @@ def test_the_wrapper_reads_the_shapes(model):
 
 def test_solar_gains_check_under_address_and_ub_sanitizers(tmp_path):
     """A stand-alone program with its own main, compiled together with the planner: nothing is preloaded."""
-    exe = tmp_path / "solar_gains_host_main"
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
-                           "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "solar_gains_host_main.cpp"), os.path.join(ROOT, "heat_amd", "csrc", "plan.cpp"),
-                           "-o", str(exe)])
+    exe = helpers.build_host_main(tmp_path, "solar_gains_host_main")
     env = dict(os.environ)   # (the sanitizers' runtimes are linked into the program)
     env["ASAN_OPTIONS"] = "detect_leaks=1:abort_on_error=1"
     env["UBSAN_OPTIONS"] = "halt_on_error=1:print_stacktrace=1"
