@@ -130,6 +130,29 @@ __device__ __forceinline__ double row_sum_f64(double v) {
     v = dpp_add_f64<0x118, 0xf>(v);
     return v;
 }
+// Two sums side by side: each level for both before the next level, so that the two trees' dependent DPP steps
+// overlap (one after the other they are twelve dependent levels). Each tree is wave_sum_f64's / row_sum_f64's.
+__device__ __forceinline__ void row_sum2_f64(double &a, double &b) {
+    a = dpp_add_f64<0x111, 0xf>(a);
+    b = dpp_add_f64<0x111, 0xf>(b);
+    a = dpp_add_f64<0x112, 0xf>(a);
+    b = dpp_add_f64<0x112, 0xf>(b);
+    a = dpp_add_f64<0x114, 0xf>(a);
+    b = dpp_add_f64<0x114, 0xf>(b);
+    a = dpp_add_f64<0x118, 0xf>(a);
+    b = dpp_add_f64<0x118, 0xf>(b);
+}
+__device__ __forceinline__ void wave_sum2_f64(double &a, double &b) {
+    row_sum2_f64(a, b);
+    a = dpp_add_f64<0x142, 0xa>(a);
+    b = dpp_add_f64<0x142, 0xa>(b);
+    a = dpp_add_f64<0x143, 0xc>(a);
+    b = dpp_add_f64<0x143, 0xc>(b);
+    const int alo = __builtin_amdgcn_readlane(__double2loint(a), 63), ahi = __builtin_amdgcn_readlane(__double2hiint(a), 63);
+    const int blo = __builtin_amdgcn_readlane(__double2loint(b), 63), bhi = __builtin_amdgcn_readlane(__double2hiint(b), 63);
+    a = __hiloint2double(ahi, alo);
+    b = __hiloint2double(bhi, blo);
+}
 
 __device__ __forceinline__ double from_prev_lane(double v) { return dpp_rotate_f64<0x13C>(v); }  // wave_ror:1
 __device__ __forceinline__ double from_next_lane(double v) { return dpp_rotate_f64<0x134>(v); }  // wave_rol:1
@@ -619,20 +642,88 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
         a = sa;
         b = sb;
     };
-    auto finish = [&](int j, double a, double b, double tc, double cz) {
-        a += l.za0[j];
-        b += l.zb0[j];
+    auto finish_with = [&](int j, double a, double b, double tc, double cz, double a0, double b0) {
+        a += a0;
+        b += b0;
         double ft = tc;
         if (fabs(b) > 1e-9) ft = a / b + (tc - a / b) * exp(-b * fa.dt / cz);  // model.rs:662-666
         if (ft != ft) bad_all |= FLAG_NAN_ZONE;                                // model.rs:417-420
         l.zT[j] = ft;
     };
-    if (blk.n_zones <= n_waves) {
-        if constexpr (!TEAM) zone_prio_raise(wib_u < nz_u);  // this wavefront has a zone
+    auto finish = [&](int j, double a, double b, double tc, double cz) { finish_with(j, a, b, tc, cz, l.za0[j], l.zb0[j]); };
+    if constexpr (!TEAM) {
+        // The wavefront (the row) that owns a zone is the one the workgroup waits for, so its LDS reads go out together:
+        // the list's bounds first (the gather's addresses need them, nothing else does), zT, the volume, a0 and b0 behind
+        // them, then the gather's first pairs (a wavefront's first two passes, a row's first): one wait per value, in
+        // the order issued, instead of one round trip after the other. The capacitance is formed while the pairs travel
+        // (pinned: left alone its division sinks to its only use, behind the sums, into the lane that finishes), the two
+        // sums run level by level side by side, and a0 / b0 are in registers when the sums arrive. A wavefront without
+        // a zone reads nothing. The arithmetic is the team path's below, operation for operation.
+        if (blk.n_zones <= n_waves) {
+            zone_prio_raise(wib_u < nz_u);  // this wavefront has a zone
+            if (wib < blk.n_zones) {
+                const int j = wib;
+                const int e0 = l.zoff[j], e1 = l.zoff[j + 1];
+                const double tc = l.zT[j], vol = l.zvol[j], a0 = l.za0[j], b0 = l.zb0[j];
+                const int ea = e0 + lane, eb = ea + kWave, last = max(e1 - 1, 0);
+                const double2 h0 = l.hT[min(ea, last)], h1 = l.hT[min(eb, last)];  // (a lane past the list reads a pair it drops)
+                double cz = zone_mcp(vol, tc);  // model.rs:549-552
+                asm volatile("" : "+v"(cz));
+                double a = 0.0, b = 0.0;
+                if (ea < e1) {
+                    a += h0.x * h0.y;
+                    b += h0.x;
+                }
+                if (eb < e1) {
+                    a += h1.x * h1.y;
+                    b += h1.x;
+                }
+                for (int e = eb + kWave; e < e1; e += kWave) {  // lists of more than 128 entries
+                    const double2 ht = l.hT[e];
+                    a += ht.x * ht.y;
+                    b += ht.x;
+                }
+                wave_sum2_f64(a, b);
+                if (lane == 0) finish_with(j, a, b, tc, cz, a0, b0);
+            }
+            zone_prio_drop();
+        } else {
+            const int row = lane >> 4, rl = lane & 15;
+#pragma clang loop unroll(disable)
+            for (int j0 = 0; j0 < blk.n_zones; j0 += 4 * n_waves) {  // (workgroup-uniform trip count)
+                if (__builtin_amdgcn_readfirstlane((int)(j0 + 4 * wib_u < nz_u))) {  // a row of this wavefront has a zone in this pass
+                    __builtin_amdgcn_s_setprio(kZonePrio);
+                    const int j = j0 + 4 * wib + row;
+                    const bool on = j < blk.n_zones;
+                    const int jj = on ? j : 0;
+                    const int e0 = l.zoff[jj], e_next = l.zoff[jj + 1], e1 = on ? e_next : e0;  // (both read: a read under `on` waits for the first)
+                    const double tc = l.zT[jj], vol = l.zvol[jj], a0 = l.za0[jj], b0 = l.zb0[jj];
+                    const int ea = e0 + rl;
+                    const double2 h0 = l.hT[min(ea, max(e1 - 1, 0))];  // (one pass ahead: a second one lost on rooms of 14 sides)
+                    double cz = zone_mcp(vol, tc);
+                    asm volatile("" : "+v"(cz));
+                    double a = 0.0, b = 0.0;
+                    if (ea < e1) {
+                        a += h0.x * h0.y;
+                        b += h0.x;
+                    }
+                    for (int e = ea + 16; __any(e < e1); e += 16) {  // (wave-uniform trip count: DPP below must not sit in divergent code)
+                        if (e < e1) {
+                            const double2 ht = l.hT[e];
+                            a += ht.x * ht.y;
+                            b += ht.x;
+                        }
+                    }
+                    row_sum2_f64(a, b);
+                    if (on && rl == 15) finish_with(j, a, b, tc, cz, a0, b0);
+                }
+                zone_prio_drop();
+            }
+        }
+    } else if (blk.n_zones <= n_waves) {
         if (wib < blk.n_zones) {
             const int j = wib;
             const int e0 = l.zoff[j], e1 = l.zoff[j + 1];
-            // (the capacitance does not wait for the sums: its division overlaps their LDS round trips)
             const double tc = l.zT[j];
             const double cz = zone_mcp(l.zvol[j], tc);  // model.rs:549-552
             double a = 0.0, b = 0.0;
@@ -643,24 +734,19 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
             }
             a = wave_sum_f64(a);
             b = wave_sum_f64(b);
-            if (lane == 0) {
-                if constexpr (TEAM) {  // (one zone per wavefront: nothing of this member's is published behind this wait)
-                    publish(j, a, b);
-                    gather(j, a, b);
-                }
+            if (lane == 0) {  // (one zone per wavefront: nothing of this member's is published behind this wait)
+                publish(j, a, b);
+                gather(j, a, b);
                 finish(j, a, b, tc, cz);
             }
         }
-        if constexpr (!TEAM) zone_prio_drop();
     } else {
         const int row = lane >> 4, rl = lane & 15;
         const bool one_pass = blk.n_zones <= 4 * n_waves;  // (workgroup-uniform) the loop below runs once
-        (void)one_pass;
 #pragma clang loop unroll(disable)
         for (int j0 = 0; j0 < blk.n_zones; j0 += 4 * n_waves) {  // (workgroup-uniform trip count)
             const int j = j0 + 4 * wib + row;
             const bool on = j < blk.n_zones;
-            if constexpr (!TEAM) zone_prio_raise(j0 + 4 * wib_u < nz_u);  // a row of this wavefront has a zone in this pass
             const int jj = on ? j : 0;
             const int e0 = l.zoff[jj], e1 = on ? l.zoff[jj + 1] : e0;
             const double tc = l.zT[jj];
@@ -675,34 +761,27 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
             }
             a = row_sum_f64(a);
             b = row_sum_f64(b);
-            if constexpr (TEAM) {
-                if (on && rl == 15) {
-                    publish(j, a, b);
-                    if (one_pass) {  // (a row meets one zone only: everything of this member is published before any wait)
-                        gather(j, a, b);
-                        finish(j, a, b, tc, cz);
-                    } else {  // pass 1: keep the own sums for pass 2 (same lane: no barrier needed)
-                        l.zsa[j] = a;
-                        l.zsb[j] = b;
-                    }
+            if (on && rl == 15) {
+                publish(j, a, b);
+                if (one_pass) {  // (a row meets one zone only: everything of this member is published before any wait)
+                    gather(j, a, b);
+                    finish(j, a, b, tc, cz);
+                } else {  // pass 1: keep the own sums for pass 2 (same lane: no barrier needed)
+                    l.zsa[j] = a;
+                    l.zsb[j] = b;
                 }
-            } else {
-                if (on && rl == 15) finish(j, a, b, tc, cz);
-                zone_prio_drop();
             }
         }
-        if constexpr (TEAM) {
-            if (!one_pass) {
+        if (!one_pass) {
 #pragma clang loop unroll(disable)
-                for (int j0 = 0; j0 < blk.n_zones; j0 += 4 * n_waves) {  // pass 2: everything of this member is published
-                    const int j = j0 + 4 * wib + row;
-                    if (j < blk.n_zones && rl == 15) {
-                        const double tc = l.zT[j];
-                        const double cz = zone_mcp(l.zvol[j], tc);
-                        double a = l.zsa[j], b = l.zsb[j];
-                        gather(j, a, b);
-                        finish(j, a, b, tc, cz);
-                    }
+            for (int j0 = 0; j0 < blk.n_zones; j0 += 4 * n_waves) {  // pass 2: everything of this member is published
+                const int j = j0 + 4 * wib + row;
+                if (j < blk.n_zones && rl == 15) {
+                    const double tc = l.zT[j];
+                    const double cz = zone_mcp(l.zvol[j], tc);
+                    double a = l.zsa[j], b = l.zsb[j];
+                    gather(j, a, b);
+                    finish(j, a, b, tc, cz);
                 }
             }
         }
