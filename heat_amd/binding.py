@@ -306,6 +306,8 @@ SYMBOLS = [
     ("heat_batch_set_fusion", C.c_int, [_H, C.c_int32]),
     ("heat_batch_n_fused_surfaces", C.c_int64, [_H]),
     ("heat_batch_n_fused_launches", C.c_int64, [_H]),
+    ("heat_batch_set_ideal_resident", C.c_int, [_H, C.c_int32]),
+    ("heat_batch_ideal_resident", C.c_int32, [_H]),
     ("heat_batch_n_surfaces", C.c_int64, [_H]),
     ("heat_batch_n_nodes", C.c_int64, [_H]),
     ("heat_batch_n_zones", C.c_int64, [_H]),
@@ -318,6 +320,7 @@ SYMBOLS = [
     ("heat_batch_create_shard", C.c_int, [C.POINTER(Desc), C.POINTER(Options), _i32p, C.POINTER(_H)]),
     ("heat_plan_check", C.c_int, [C.POINTER(Desc), C.POINTER(Options), _i64p]),
     ("heat_plan_check_sites", C.c_int, [C.POINTER(Desc), C.POINTER(Options), C.c_int32, _i32p, _i64p]),
+    ("heat_plan_ideal_resident", C.c_int, [C.POINTER(Desc), C.POINTER(Options), C.c_int32, _i32p, _i32p]),
     ("heat_last_error", C.c_char_p, []),
     ("heat_amd_abi_version", C.c_int, []),
     # include/heat_amd_setup.h
@@ -436,7 +439,8 @@ def make_desc(md):
     return d, keep
 
 
-HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_series_check", "heat_zone_loads_check",
+HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites", "heat_plan_ideal_resident", "heat_series_check",
+                     "heat_zone_loads_check",
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
                      "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check", "heat_air_handlers_check",
@@ -507,6 +511,26 @@ def plan_check_sites(md, n_sites, site_of_surface, lib=None, **opts):
     if rc != 0:
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
     return list(summary)
+
+
+# heat_ideal_resident_reason (include/heat_amd.h): why a batch's ideal series cannot keep its resident clusters resident
+IDEAL_RESIDENT_OK, IDEAL_RESIDENT_NONE_PLANNED, IDEAL_RESIDENT_TEAMS, IDEAL_RESIDENT_CAVITY_CLASS, IDEAL_RESIDENT_CHUNK_LOOP_CLASS = range(5)
+
+
+def plan_ideal_resident(md, n_sites=1, site_of_surface=None, lib=None, **opts):
+    """heat_plan_ideal_resident: (eligible, reason) — whether an ideal series of a batch made from this model and these
+    options could keep its resident clusters resident (HeatBatch.set_ideal_resident), and if not why (IDEAL_RESIDENT_*).
+    Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    opt = make_options(**opts)
+    sites = None if site_of_surface is None else np.ascontiguousarray(site_of_surface, dtype=np.int32)
+    reason = C.c_int32(-1)
+    rc = L.heat_plan_ideal_resident(C.byref(desc), C.byref(opt), int(n_sites),
+                                    sites.ctypes.data_as(_i32p) if sites is not None else None, C.byref(reason))
+    if rc < 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+    return bool(rc), int(reason.value)
 
 
 def make_series(weather, n_sub, n_sites=1, channel=None, solar_front=None, solar_back=None, ir_front=None, ir_back=None,
@@ -1520,11 +1544,12 @@ class HeatBatch:
 
     def __init__(self, md, device=-1, force_general=False, nodes_per_lane=0, use_graph=False, stream=None,
                  n_ranks=1, rank=0, no_palette=False, no_fusion=False, fuse_always=False, rank_of_surface=None,
-                 sites=None, n_sites=None):
+                 sites=None, n_sites=None, ideal_resident=False):
         """rank_of_surface (heat_partition's result): the batch holds the surfaces of `rank` only, picked from the
         whole model's dict by the library (heat_batch_create_shard).
         sites (modeldict.concat's site_of_surface): a batch of weather sites (heat_batch_create_sites), n_sites of them
-        (default: max(sites) + 1); its marches then take weather [n_sub, n_sites, 3]."""
+        (default: max(sites) + 1); its marches then take weather [n_sub, n_sites, 3].
+        ideal_resident: set_ideal_resident(True) on the new batch (no option of the descriptor: a setting of the batch)."""
         self._L = load_library()
         self._h = _H()
         desc, keep = make_desc(md)
@@ -1551,6 +1576,8 @@ class HeatBatch:
         self.n_surfaces = int(md["n_surfaces"])
         # (the default normals of a sky: the model's own; of a shard's batch they are the whole model's, like every array)
         self._normals = tuple(np.array(a, dtype=np.float64) for a in _model_normals(md))
+        if ideal_resident:
+            self.set_ideal_resident(True)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1921,6 +1948,16 @@ class HeatBatch:
     def set_fusion(self, enabled):
         """Cluster-resident march on/off (off: every surface is streamed one sub-timestep per launch)."""
         _check(self._L.heat_batch_set_fusion(self._h, 1 if enabled else 0))
+
+    def set_ideal_resident(self, enabled):
+        """Opt-in, durable: ideal series of this batch keep its resident clusters resident (heat_ideal_loads, RESIDENT
+        FORM) where the batch is eligible; otherwise, and by default, they march streamed."""
+        _check(self._L.heat_batch_set_ideal_resident(self._h, 1 if enabled else 0))
+
+    @property
+    def ideal_resident(self):
+        """1 when the next ideal series would march the resident clusters resident: the opt-in, fusion on, an eligible batch."""
+        return int(self._L.heat_batch_ideal_resident(self._h))
 
     @property
     def n_fused_surfaces(self):

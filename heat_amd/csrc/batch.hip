@@ -617,10 +617,11 @@ void enqueue_surfaces(heat_batch *b, int step_fixed, bool streamed_only = false)
 
 // mode 0 / 1 / 2 as k_zones; mode 3: as mode 0 (full update, advances the step counter) but only the zones no
 // fused workgroup owns (the cluster-resident march balances its own zones in LDS).
+// mode 6: the partials of those zones only (an ideal series beside a resident march: march_body_ideal finishes them).
 void enqueue_zones(heat_batch *b, int mode) {
     const int32_t *zl = b->d_zlist.p;
     int nl = b->n_touched;
-    if (mode == 3) { zl = b->d_stream_zones.p; nl = b->n_stream_zones; }
+    if (mode == 3 || mode == 6) { zl = b->d_stream_zones.p; nl = b->n_stream_zones; }  // (6: their partials only, k_zones)
     if (mode == 5) { mode = 3; }  // sharded batch, nothing fused in this call: every zone it owns (d_zlist), full update
     if (mode == 4) { zl = b->d_zlist_stream.p; nl = b->n_touched_stream; mode = 2; }  // sharded, beside a fused march
     launch_zones(b->d_zone_off.p, b->d_zone_entries.p, b->d_zone_contrib.p, b->d_zone_a0.p, b->d_zone_b0.p,
@@ -658,7 +659,9 @@ static int team_shapes(const heat_batch *b, int n_sub, TeamShape (&shape)[kNumFa
 
 // The cluster-resident march: every fused workgroup marches n_sub sub-timesteps in one launch per class.
 // streamed_beside: other surfaces of the batch are streamed on the batch's stream while this launch runs.
-int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside = false) {
+// ild (an ideal series on an eligible batch, march_body_ideal): the IDEAL instantiations, which host the rule of the loads.
+int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside = false, const IdealLoadsDev *ild = nullptr) {
+    if (ild != nullptr && b->any_teams) return fail(HEAT_E_INVALID_ARG, "ideal loads in the cluster-resident march: the batch marches teams");
     TeamShape team_shape[kNumFast];
     {
         const int rc = team_shapes(b, n_sub, team_shape);
@@ -683,6 +686,16 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
     fa.gen_tiles = b->d_gen_tiles.p;
     fa.gen_base = b->gen_base;
     fa.small_iters = b->d_nomass_iters.p + b->nm_count_base[kNumFast];
+    const int ideal = ild != nullptr ? 1 : 0;
+    if (ideal) {
+        fa.il_load_of_zone = ild->load_of_zone;
+        fa.il_setpoint = ild->setpoint;
+        fa.il_heat_cap = ild->heat_cap, fa.il_cool_cap = ild->cool_cap;
+        fa.il_heat_chan = ild->heat_chan, fa.il_cool_chan = ild->cool_chan;
+        fa.il_qsum = ild->qsum;
+        fa.il_n_sat_heating = ild->n_sat_heating, fa.il_n_sat_cooling = ild->n_sat_cooling;
+        fa.il_n_loads = ild->n_loads;
+    }
     // Beside an exchange loop (sharded batch with shared zones) the fused launch must not take every wavefront slot
     // of the chip: the loop's small kernels and the collective would each wait tens of microseconds for a slot
     // (measured: 27-74 us instead of 5) and become the critical path. So the launch holds a few workgroups fewer
@@ -721,7 +734,7 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
             if (beside_exchange || persist) {
                 const int fw = (g2 & 1) ? 8 : 4;
                 static const int room_env = getenv("HEAT_AMD_FUSED_ROOM") ? atoi(getenv("HEAT_AMD_FUSED_ROOM")) : 0;  // tests
-                const int room = room_env > 0 ? room_env : n_cu * fused_blocks_per_cu(kFastM[c], kFastCAV[c], g2 >> 1, fw, b->na.pal_stride);
+                const int room = room_env > 0 ? room_env : n_cu * fused_blocks_per_cu(kFastM[c], kFastCAV[c], g2 >> 1, fw, b->na.pal_stride, ideal);
                 const int reserve = !beside_exchange ? 0 : reserve_env >= 0 ? reserve_env
                                                      : std::min(room / 2, std::max(fw == 4 ? 16 : 8, (int)(room * streamed_share)));
                 if (nb > room - reserve) {
@@ -732,14 +745,14 @@ int enqueue_fused(heat_batch *b, int n_sub, hipStream_t st, bool streamed_beside
             }
             static const bool trace = getenv("HEAT_AMD_TRACE") != nullptr;
             if (trace)
-                fprintf(stderr, "heat_amd: fused launch%s: %d workgroups for %d blocks (class %d, list %d, %d sub-timesteps)\n",
-                        fa.queue ? " on the work queue" : "", grid, nb, c, g2, n_sub);
+                fprintf(stderr, "heat_amd: fused launch%s%s: %d workgroups for %d blocks (class %d, list %d, %d sub-timesteps)\n",
+                        fa.queue ? " on the work queue" : "", ideal ? " with ideal loads" : "", grid, nb, c, g2, n_sub);
             b->n_fused_launches++;
             // (a class whose walls hold no-mass chunks other than facings marches with the variant that carries the chunk loop)
             const int nm_variant = kFastNM[c] ? ((b->class_has_chunks[c] && !(g2 >> 1) && !kFastCAV[c] && kFastM[c] <= 8) ? 2 : 1) : 0;
             HIP_TRY(launch_surfaces_fused(kFastM[c], nm_variant, kFastCAV[c], g2 >> 1, (g2 & 1) ? 8 : 4, grid, b->d_fast_tiles[c].p, b->n_fast_tiles[c],
                                           b->na, b->sa, b->d_weather.p, b->d_flags.p,
-                                          b->d_nomass_iters.p + b->nm_count_base[c], fa, st));
+                                          b->d_nomass_iters.p + b->nm_count_base[c], fa, st, ideal));
             if (fa.queue) b->fqueue_base[c * 4 + g2] += (unsigned int)nb;  // one ticket per block marched (layout.hpp)
         }
     // Teams (clusters larger than a workgroup): n_teams x kTeamMax workgroups, ALL of them on the chip at once — a member
@@ -1694,20 +1707,78 @@ int heat::march_body(heat_batch *b, int32_t n_sub) {
     return HEAT_OK;
 }
 
-// The body of a step of a series with ideal loads (heat_ideal_loads): every sub-timestep streamed — the surface kernels, the
-// zone sums as partials (k_zones, mode 1), the zone update with the rule (k_zone_update_ideal) — in plain launches on the
-// batch's stream. The cluster-resident march balances its zones in LDS and cannot host the rule; the batch's fusion setting
-// and the graph cache of the plain calls are not touched.
+// Whether an ideal series may keep this batch's resident clusters resident: every resident launch it would make has an
+// ideal instantiation (plan.hpp, ideal_resident_reason — the function heat_plan_ideal_resident asks of a plan).
+static int ideal_reason_of(const heat_batch *b) {
+    size_t n_blocks[kNumFast][4], n_supers[kNumFast];
+    bool has_chunks[kNumFast];
+    for (int c = 0; c < kNumFast; c++) {
+        for (int g2 = 0; g2 < 4; g2++) n_blocks[c][g2] = b->h_fblocks[c][g2].size();
+        n_supers[c] = b->h_team_supers[c].size();
+        has_chunks[c] = b->class_has_chunks[c];
+    }
+    return ideal_resident_reason(n_blocks, n_supers, has_chunks);
+}
+static bool ideal_resident_now(const heat_batch *b) {
+    return b->ideal_resident_on && b->fusion_on && b->any_fused && b->n_ranks == 1 && !b->comm &&
+           ideal_reason_of(b) == HEAT_IDEAL_RESIDENT_OK;
+}
+
+// The body of a step of a series with ideal loads (heat_ideal_loads), in plain launches; the batch's fusion setting and
+// the graph cache of the plain calls are not touched.
+// Streamed form (the default): every sub-timestep streamed — the surface kernels, the zone sums as partials (k_zones, mode
+// 1), the zone update with the rule (k_zone_update_ideal) — on the batch's stream.
+// Resident form (heat_batch_set_ideal_resident on an eligible batch, fusion on, a call as long as march_body asks for): the
+// resident clusters march in the IDEAL instantiations, whose zone balance hosts the rule; what is not resident is streamed
+// beside them (a small batch, on two streams) or behind them, as in march_body, and the zones no workgroup owns get the rule
+// from k_zones' partials of that list (mode 6) and k_zone_update_ideal restricted to it — it never writes a zone a
+// workgroup has in LDS. Fork and join, the guard, the zig-zag parity, the work queue's tickets and n_fused_launches: as there.
 int heat::march_body_ideal(heat_batch *b, int32_t n_sub, const IdealLoadsDev &ild) {
     if (n_sub == 0) return HEAT_OK;
     b->host_zones_stale = true;
     MarchGuard guard(b);
     b->partial_ptr = b->d_partial.p;  // (a caller's buffer, heat_batch_use_partials, is left alone; restored by the guard)
-    for (int i = 0; i < n_sub; i++) {
-        enqueue_surfaces(b, -1);
-        enqueue_zones(b, 1);
-        launch_zone_update_ideal(b->d_partial.p, b->d_zone_a0.p, b->d_zone_b0.p, b->d_zone_vol.p, b->d_zone_T.p, (int)b->n_zones, b->dt,
-                                 b->d_step.p, b->d_flags.p, ild, b->stream);
+    static const bool trace = getenv("HEAT_AMD_TRACE") != nullptr;
+    if (trace && b->ideal_resident_on && !b->ideal_reason_traced) {
+        b->ideal_reason_traced = true;
+        const int why = ideal_reason_of(b);
+        if (why != HEAT_IDEAL_RESIDENT_OK)
+            fprintf(stderr, "heat_amd: ideal series streamed despite heat_batch_set_ideal_resident: %s\n", ideal_resident_reason_text(why));
+    }
+    const bool fused = ideal_resident_now(b) && n_sub >= (b->n_surf <= 8192 ? 1 : kFusedMinSubsteps);
+    if (!fused) {
+        for (int i = 0; i < n_sub; i++) {
+            enqueue_surfaces(b, -1);
+            enqueue_zones(b, 1);
+            launch_zone_update_ideal(b->d_partial.p, b->d_zone_a0.p, b->d_zone_b0.p, b->d_zone_vol.p, b->d_zone_T.p, (int)b->n_zones, b->dt,
+                                     b->d_step.p, b->d_flags.p, ild, b->stream);
+        }
+        HIP_TRY(hipGetLastError());
+        return HEAT_OK;
+    }
+    bool streamed = b->n_gen_tiles > 0 || b->n_stream_zones > 0;
+    for (int c = 0; c < kNumFast; c++) streamed = streamed || b->n_stream_tiles[c] > 0;
+    hipStream_t fs = b->stream;
+    if (streamed && b->fused_stream != nullptr && b->n_surf <= 8192) {  // (side by side on a small batch: march_body)
+        fs = b->fused_stream;
+        HIP_TRY(hipEventRecord(b->ev_fork, b->stream));
+        HIP_TRY(hipStreamWaitEvent(fs, b->ev_fork, 0));
+        guard.forked = true;
+    }
+    int rc = enqueue_fused(b, n_sub, fs, streamed && fs != b->stream, &ild);
+    if (rc) return rc;
+    if (streamed) {
+        for (int i = 0; i < n_sub; i++) {
+            enqueue_surfaces(b, -1, true);
+            enqueue_zones(b, 6);
+            launch_zone_update_ideal(b->d_partial.p, b->d_zone_a0.p, b->d_zone_b0.p, b->d_zone_vol.p, b->d_zone_T.p, (int)b->n_zones, b->dt,
+                                     b->d_step.p, b->d_flags.p, ild, b->stream, b->d_stream_zones.p, b->n_stream_zones);
+        }
+    }
+    if (fs != b->stream) {
+        HIP_TRY(hipEventRecord(b->ev_fused, fs));
+        HIP_TRY(hipStreamWaitEvent(b->stream, b->ev_fused, 0));
+        guard.joined = true;
     }
     HIP_TRY(hipGetLastError());
     return HEAT_OK;
@@ -1838,6 +1909,15 @@ int heat_batch_set_fusion(heat_batch *b, int32_t enabled) {
     b->fusion_on = enabled != 0;
     return HEAT_OK;
 }
+
+int heat_batch_set_ideal_resident(heat_batch *b, int32_t enabled) {
+    if (!b) return fail(HEAT_E_INVALID_ARG, "NULL batch");
+    b->ideal_resident_on = enabled != 0;
+    b->ideal_reason_traced = false;
+    return HEAT_OK;
+}
+
+int32_t heat_batch_ideal_resident(const heat_batch *b) { return b && ideal_resident_now(b) ? 1 : 0; }
 
 int64_t heat_batch_n_fused_surfaces(const heat_batch *b) { return b ? b->n_fused_surfaces : 0; }
 int64_t heat_batch_n_fused_launches(const heat_batch *b) { return b ? b->n_fused_launches : 0; }

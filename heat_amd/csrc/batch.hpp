@@ -277,6 +277,8 @@ struct heat_batch {
     std::vector<EvPair> ev_fused_pairs;
     bool fusion_on = true;     // heat_batch_options::no_fusion / heat_batch_set_fusion
     int64_t n_fused_launches = 0;  // cluster-resident launches issued since creation (introspection)
+    bool ideal_resident_on = false;   // heat_batch_set_ideal_resident: an ideal series keeps its resident clusters resident
+    bool ideal_reason_traced = false; // (HEAT_AMD_TRACE: why the opt-in has no effect on this batch, said once)
     bool graph_fused = false;  // what the captured sub-timestep graph leaves out
     int graph_subs = 0;        // sub-timesteps one replay of the captured graph runs
     int graph_recaptures = 0;  // captures forced by a change of the calls' length
@@ -292,7 +294,9 @@ int select_device(heat_batch *b);
 int grow_weather(heat_batch *b, int32_t n_sub);
 // The body of a march call: n_sub sub-timesteps from the weather, zone terms and counter already on the device.
 int march_body(heat_batch *b, int32_t n_sub);
-// The same with every sub-timestep streamed and the zone update under the ideal-loads rule.
+// The same with the zone update under the ideal-loads rule: every sub-timestep streamed, or — heat_batch_set_ideal_resident
+// on an eligible batch, fusion on, a call long enough — the resident clusters resident (the IDEAL instantiations host the
+// rule) and the rest streamed beside or behind them. The engine decides; the caller hands the loads' view over.
 int march_body_ideal(heat_batch *b, int32_t n_sub, const IdealLoadsDev &ild);
 
 }  // namespace heat

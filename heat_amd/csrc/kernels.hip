@@ -463,6 +463,72 @@ k_surfaces_small(const GeneralTile *__restrict__ tiles, int n_tiles, NodeArrays 
 }
 #pragma clang fp contract(fast)
 
+// The ideal-loads rule of one zone in one sub-timestep (heat_ideal_loads, include/heat_amd.h), line by line: every line is
+// ONE rounded f64 operation in the header's order, no contraction. The streamed zone update (k_zone_update_ideal) and the
+// finishing lane of the cluster-resident march (fused_zone_phase, IDEAL) both run it; they differ in the sums they hand in.
+//   has_load  the zone has an ideal load (otherwise h, c and the capacities are not looked at: the zone floats)
+//   h, c      the step's setpoints, NaN where the load has no channel of that kind (a NaN makes every comparison false)
+//   sat       out: 0, or 1 / 2 where the sub-timestep ended at the heating / cooling capacity
+#pragma clang fp contract(off)
+__device__ __forceinline__ void ideal_zone_rule(bool has_load, double s_a, double s_b, double a0, double b0, double tc, double cz,
+                                                double dt, double h, double c, double heat_cap, double cool_cap, double &ft_out,
+                                                double &q_out, int &sat) {
+    const double a = s_a + a0;
+    const double b = s_b + b0;
+    double q = 0.0, ft = tc;
+    sat = 0;
+    if (fabs(b) > 1e-9) {  // model.rs:662-668
+        const double r = a / b;
+        const double nbdt = (-b) * dt;
+        const double E = exp(nbdt / cz);
+        const double dE = (tc - r) * E;
+        const double free_t = r + dE;
+        ft = free_t;
+        const double D = 1.0 - E;
+        if (has_load && D > 0.0) {
+            const double tcE = tc * E;
+            if (free_t < h) {
+                const double num = b * (h - tcE);
+                const double need = num / D - a;
+                const double cap = heat_cap;
+                q = need > cap ? cap : need;
+                if (!(q > 0.0)) q = 0.0;
+                if (q > 0.0) {
+                    if (q == need) {
+                        ft = h;
+                    } else {
+                        const double a2 = a + q;
+                        const double r2 = a2 / b;
+                        const double d2 = (tc - r2) * E;
+                        ft = r2 + d2;
+                        sat = 1;
+                    }
+                }
+            } else if (free_t > c) {
+                const double num = b * (c - tcE);
+                const double need = num / D - a;
+                const double cap = -cool_cap;
+                q = need < cap ? cap : need;
+                if (!(q < 0.0)) q = 0.0;
+                if (q < 0.0) {
+                    if (q == need) {
+                        ft = c;
+                    } else {
+                        const double a2 = a + q;
+                        const double r2 = a2 / b;
+                        const double d2 = (tc - r2) * E;
+                        ft = r2 + d2;
+                        sat = 2;
+                    }
+                }
+            }
+        }
+    }
+    ft_out = ft;
+    q_out = q;
+}
+#pragma clang fp contract(fast)
+
 // ---------------------------------------------------------------------------
 // Cluster-resident march, pieces shared by the fast-path wavefronts and the small-surface wavefronts of a
 // workgroup (layout.hpp, FusedBlock). LDS after the palettes (and, in two instantiations, V: fused_v_in_lds): see
@@ -489,7 +555,58 @@ constexpr bool fused_v_in_lds(int M, int NM, int FW, int SMALL) {
 constexpr int kFusedBarriersAtInit = 1;
 constexpr int kFusedBarriersPerSubstep = 2;
 
+// IDEAL (a series with ideal loads marched resident): the per-zone arrays behind the slot lists (layout.hpp,
+// kFusedIdealLdsBytes) — a view, so that FusedLds and everything that carries it stay as they are.
+struct FusedIdealLds {
+    double *sp_h, *sp_c;    // the step's setpoints, NaN: the load has no channel of that kind
+    double *cap_h, *cap_c;
+    double *q;              // the zone's q-sum over the sub-timesteps of this launch, from 0.0
+    int *nsat_h, *nsat_c;   // sub-timesteps of this launch that ended at a capacity
+    int *load;              // the zone's load, -1: none
+};
+__device__ __forceinline__ FusedIdealLds fused_ideal_lds(const FusedLds &l) {
+    FusedIdealLds il;
+    il.sp_h = reinterpret_cast<double *>(l.slots + kFusedMaxEntries);
+    il.sp_c = il.sp_h + kFusedMaxZones;
+    il.cap_h = il.sp_c + kFusedMaxZones;
+    il.cap_c = il.cap_h + kFusedMaxZones;
+    il.q = il.cap_c + kFusedMaxZones;
+    il.nsat_h = reinterpret_cast<int *>(il.q + kFusedMaxZones);
+    il.nsat_c = il.nsat_h + kFusedMaxZones;
+    il.load = il.nsat_c + kFusedMaxZones;
+    return il;
+}
+// ... filled for block-local zone threadIdx.x = global zone z by that thread (fused_block_init, both forms; with the work
+// queue again for every block a persistent workgroup takes: the accumulators start at nought for each)
+__device__ __forceinline__ void fused_ideal_init(const FusedArgs &fa, const FusedLds &l, int z) {
+    const FusedIdealLds il = fused_ideal_lds(l);
+    const int t = threadIdx.x;
+    const int i = fa.il_load_of_zone[z];
+    const int ii = i >= 0 ? i : 0;
+    const double nan = __builtin_nan("");
+    il.load[t] = i;
+    il.sp_h[t] = (i >= 0 && fa.il_heat_chan[ii] >= 0) ? fa.il_setpoint[ii] : nan;
+    il.sp_c[t] = (i >= 0 && fa.il_cool_chan[ii] >= 0) ? fa.il_setpoint[fa.il_n_loads + ii] : nan;
+    il.cap_h[t] = i >= 0 ? fa.il_heat_cap[ii] : 0.0;
+    il.cap_c[t] = i >= 0 ? fa.il_cool_cap[ii] : 0.0;
+    il.q[t] = 0.0;
+    il.nsat_h[t] = 0;
+    il.nsat_c[t] = 0;
+}
+// ... and handed back when the block's march ends, by the thread that writes the zone's temperature back: the step's q-sum
+// starts at 0.0, so qsum is a plain store; a zone has one load and one owning workgroup, so nothing here is atomic.
+__device__ __forceinline__ void fused_ideal_write_back(const FusedArgs &fa, const FusedLds &l) {
+    const FusedIdealLds il = fused_ideal_lds(l);
+    const int t = threadIdx.x;
+    const int i = il.load[t];
+    if (i < 0) return;
+    fa.il_qsum[i] = il.q[t];
+    if (fa.il_n_sat_heating != nullptr && il.nsat_h[t] != 0) fa.il_n_sat_heating[i] += il.nsat_h[t];
+    if (fa.il_n_sat_cooling != nullptr && il.nsat_c[t] != 0) fa.il_n_sat_cooling[i] += il.nsat_c[t];
+}
+
 // The block's zone data -> LDS (every wavefront of the block takes part; ends with kFusedBarriersAtInit barrier).
+template <int IDEAL = 0>
 __device__ __forceinline__ void fused_block_init(const FusedBlock &blk, const FusedArgs &fa, const FusedLds &l, int n_threads) {
     const int e_first = fa.zone_eoff[blk.first_zone];
     if ((int)threadIdx.x <= blk.n_zones) l.zoff[threadIdx.x] = fa.zone_eoff[blk.first_zone + threadIdx.x] - e_first;
@@ -499,6 +616,7 @@ __device__ __forceinline__ void fused_block_init(const FusedBlock &blk, const Fu
         l.za0[threadIdx.x] = fa.a0[z];
         l.zb0[threadIdx.x] = fa.b0[z];
         l.zvol[threadIdx.x] = fa.vol[z];
+        if constexpr (IDEAL) fused_ideal_init(fa, l, z);
     }
     const int n_e = fa.zone_eoff[blk.first_zone + blk.n_zones] - e_first;
     // where every zone-facing side puts its (hs A, T) pair: at its entry's place in its zone's list, so that the sums
@@ -536,6 +654,7 @@ __device__ __forceinline__ void fused_pre_b(const FusedBlock &blk, const FusedAr
         if (p.n_e > 0) p.slot0 = fa.slots[p.e_first + min((int)threadIdx.x, p.n_e - 1)];
     }
 }
+template <int IDEAL = 0>
 __device__ __forceinline__ void fused_block_init(const FusedBlock &blk, const FusedArgs &fa, const FusedLds &l, int n_threads,
                                                  const FusedPre &p) {
     if ((int)threadIdx.x <= blk.n_zones) l.zoff[threadIdx.x] = p.zoff;
@@ -544,6 +663,7 @@ __device__ __forceinline__ void fused_block_init(const FusedBlock &blk, const Fu
         l.za0[threadIdx.x] = p.za0;
         l.zb0[threadIdx.x] = p.zb0;
         l.zvol[threadIdx.x] = p.zvol;
+        if constexpr (IDEAL) fused_ideal_init(fa, l, p.z);  // (p.z: this thread's zone, fused_pre_a)
     }
     if ((int)threadIdx.x < p.n_e) l.slots[p.slot0] = (unsigned short)threadIdx.x;
     for (int e = threadIdx.x + n_threads; e < p.n_e; e += n_threads) l.slots[fa.slots[p.e_first + e]] = (unsigned short)e;
@@ -580,7 +700,10 @@ __device__ __forceinline__ void zone_prio_raise(bool lead) {
     if (__builtin_amdgcn_readfirstlane((int)lead)) __builtin_amdgcn_s_setprio(kZonePrio);
 }
 __device__ __forceinline__ void zone_prio_drop() { __builtin_amdgcn_s_setprio(0); }
-template <int TEAM>
+// IDEAL (never with TEAM): a zone with an ideal load is finished by ideal_zone_rule instead — same lane, the sums the
+// resident march forms, a0 / b0 and the load's setpoints and capacities from LDS, read with the owner's other reads; the
+// lane then adds q to the zone's accumulator and counts a saturation. A zone without a load takes finish_with unchanged.
+template <int TEAM, int IDEAL = 0>
 __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const FusedArgs &fa, const FusedLds &l, int wib,
                                                  int n_waves, int lane, int &bad_all, const TeamCtx &tc_,
                                                  unsigned long long *clk = nullptr) {
@@ -651,6 +774,32 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
         l.zT[j] = ft;
     };
     auto finish = [&](int j, double a, double b, double tc, double cz) { finish_with(j, a, b, tc, cz, l.za0[j], l.zb0[j]); };
+    static_assert(!(TEAM && IDEAL), "teams have no ideal instantiation");
+    // IDEAL: what the finishing lane needs of the zone's load, read where the owner reads everything else
+    struct IdealZone {
+        int load;
+        double h, c, cap_h, cap_c, q;
+    };
+    auto ideal_read = [&](int j) {
+        const FusedIdealLds il = fused_ideal_lds(l);
+        return IdealZone{il.load[j], il.sp_h[j], il.sp_c[j], il.cap_h[j], il.cap_c[j], il.q[j]};
+    };
+    auto finish_ideal = [&](int j, double a, double b, double tc, double cz, double a0, double b0, const IdealZone &iz) {
+        if (iz.load < 0) {
+            finish_with(j, a, b, tc, cz, a0, b0);
+            return;
+        }
+        const FusedIdealLds il = fused_ideal_lds(l);
+        double ft, q;
+        int sat;
+        ideal_zone_rule(true, a, b, a0, b0, tc, cz, fa.dt, iz.h, iz.c, iz.cap_h, iz.cap_c, ft, q, sat);
+        if (ft != ft) bad_all |= FLAG_NAN_ZONE;
+        l.zT[j] = ft;
+        il.q[j] = iz.q + q;  // (one rounded addition per sub-timestep, in order: the sequential sum of the step)
+        if (sat == 1) il.nsat_h[j] += 1;
+        if (sat == 2) il.nsat_c[j] += 1;
+    };
+    (void)ideal_read; (void)finish_ideal;
     if constexpr (!TEAM) {
         // The wavefront (the row) that owns a zone is the one the workgroup waits for, so its LDS reads go out together:
         // the list's bounds first (the gather's addresses need them, nothing else does), zT, the volume, a0 and b0 behind
@@ -665,6 +814,9 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
                 const int j = wib;
                 const int e0 = l.zoff[j], e1 = l.zoff[j + 1];
                 const double tc = l.zT[j], vol = l.zvol[j], a0 = l.za0[j], b0 = l.zb0[j];
+                IdealZone iz{-1, 0.0, 0.0, 0.0, 0.0, 0.0};
+                if constexpr (IDEAL) iz = ideal_read(j);
+                (void)iz;
                 const int ea = e0 + lane, eb = ea + kWave, last = max(e1 - 1, 0);
                 const double2 h0 = l.hT[min(ea, last)], h1 = l.hT[min(eb, last)];  // (a lane past the list reads a pair it drops)
                 double cz = zone_mcp(vol, tc);  // model.rs:549-552
@@ -684,7 +836,11 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
                     b += ht.x;
                 }
                 wave_sum2_f64(a, b);
-                if (lane == 0) finish_with(j, a, b, tc, cz, a0, b0);
+                if constexpr (IDEAL) {
+                    if (lane == 0) finish_ideal(j, a, b, tc, cz, a0, b0, iz);
+                } else {
+                    if (lane == 0) finish_with(j, a, b, tc, cz, a0, b0);
+                }
             }
             zone_prio_drop();
         } else {
@@ -698,6 +854,9 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
                     const int jj = on ? j : 0;
                     const int e0 = l.zoff[jj], e_next = l.zoff[jj + 1], e1 = on ? e_next : e0;  // (both read: a read under `on` waits for the first)
                     const double tc = l.zT[jj], vol = l.zvol[jj], a0 = l.za0[jj], b0 = l.zb0[jj];
+                    IdealZone iz{-1, 0.0, 0.0, 0.0, 0.0, 0.0};
+                    if constexpr (IDEAL) iz = ideal_read(jj);
+                    (void)iz;
                     const int ea = e0 + rl;
                     const double2 h0 = l.hT[min(ea, max(e1 - 1, 0))];  // (one pass ahead: a second one lost on rooms of 14 sides)
                     double cz = zone_mcp(vol, tc);
@@ -715,7 +874,11 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
                         }
                     }
                     row_sum2_f64(a, b);
-                    if (on && rl == 15) finish_with(j, a, b, tc, cz, a0, b0);
+                    if constexpr (IDEAL) {
+                        if (on && rl == 15) finish_ideal(j, a, b, tc, cz, a0, b0, iz);
+                    } else {
+                        if (on && rl == 15) finish_with(j, a, b, tc, cz, a0, b0);
+                    }
                 }
                 zone_prio_drop();
             }
@@ -798,6 +961,7 @@ __device__ __forceinline__ void fused_zone_phase(const FusedBlock &blk, const Fu
 // A wavefront of small surfaces inside a fused workgroup: one lane per surface, everything in registers over
 // the march; same arithmetic as k_surfaces_small (small_step), zone temperatures from LDS.
 #pragma clang fp contract(off)
+template <int IDEAL = 0>
 __device__ void fused_small_wave(const FusedBlock &blk, const FusedArgs &fa, const FusedLds &l, int lanes_per_side,
                                  int wib, int n_waves, int lane, const NodeArrays &na, const SideArrays &sd,
                                  const StepWeather *__restrict__ weather, int *__restrict__ flags) {
@@ -819,7 +983,7 @@ __device__ void fused_small_wave(const FusedBlock &blk, const FusedArgs &fa, con
     int cav[kSmallNodes];
     CavityDev cv[kSmallNodes - 1];
     small_load<1>(tile, active ? lane : 0, na, fa.gen_base, df, db, nn, T, Us, sol, cav, cv);
-    fused_block_init(blk, fa, l, n_waves * kWave);
+    fused_block_init<IDEAL>(blk, fa, l, n_waves * kWave);
     int bad_all = 0;
     unsigned int iters = 0;
     SideOut of{0.0, 0.0}, ob{0.0, 0.0};
@@ -841,9 +1005,12 @@ __device__ void fused_small_wave(const FusedBlock &blk, const FusedArgs &fa, con
             if ((cf.kind_n & 3) == KIND_SPACE) l.hT[l.slots[wib * kWave + lane]] = make_double2(of.hs * area, T.a);
             if ((cb.kind_n & 3) == KIND_SPACE) l.hT[l.slots[lanes_per_side + wib * kWave + lane]] = make_double2(ob.hs * area, Tl);
         }
-        fused_zone_phase<0>(blk, fa, l, wib, n_waves, lane, bad_all, TeamCtx{0, 0, 0, 0, nullptr});
+        fused_zone_phase<0, IDEAL>(blk, fa, l, wib, n_waves, lane, bad_all, TeamCtx{0, 0, 0, 0, nullptr});
     }
-    if ((int)threadIdx.x < blk.n_zones) fa.zone_T[fa.zones[blk.first_zone + threadIdx.x]] = l.zT[threadIdx.x];
+    if ((int)threadIdx.x < blk.n_zones) {
+        fa.zone_T[fa.zones[blk.first_zone + threadIdx.x]] = l.zT[threadIdx.x];
+        if constexpr (IDEAL) fused_ideal_write_back(fa, l);
+    }
     if (active) {
         double *Tg = na.T + tile.node_base + lane;
 #pragma unroll
@@ -909,7 +1076,7 @@ __device__ unsigned long long g_stamps[65536 * kStampsPerBlock];
 //   counter_index  slot of the tile in `nomass_iters` (NM)
 //   nm_on          NM variants: whether this tile holds walls with no-mass facings at all (wave-uniform; the unified
 //                  streamed kernel runs all-massive and faced tiles through one variant)
-template <int M, int NM, int PAL, int CAV, int FUSED, int SMALL = 0>
+template <int M, int NM, int PAL, int CAV, int FUSED, int SMALL = 0, int IDEAL = 0>
 __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter_index, bool nm_on, int lane, int wib,
                                                 double *s_pal, double *s_V, double *s_pos, const FusedLds &fl, const FusedBlock &blk,
                                                 int blk_waves, int n_it, int step0, const NodeArrays &na,
@@ -1089,7 +1256,7 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
         }
     }
     HEAT_STAMP(7, false);
-    if constexpr (FUSED) fused_block_init(blk, fa, fl, blk_waves * kWave, pre);  // the block's zone data -> LDS
+    if constexpr (FUSED) fused_block_init<IDEAL>(blk, fa, fl, blk_waves * kWave, pre);  // the block's zone data -> LDS
 
     const int first_lane = lane - seg;
     const int nn = kind_n_mine >> 16;
@@ -1540,7 +1707,7 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
             tcx.it = it;
             fused_zone_phase<1>(blk, fa, fl, wib, blk_waves, lane, bad_all, tcx, chain_clk);
         } else {
-            fused_zone_phase<0>(blk, fa, fl, wib, blk_waves, lane, bad_all, team, chain_clk);
+            fused_zone_phase<0, IDEAL>(blk, fa, fl, wib, blk_waves, lane, bad_all, team, chain_clk);
         }
     }
     }  // sub-timesteps
@@ -1555,7 +1722,10 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
 #pragma unroll
             for (int jp = 0; jp < M / 2; jp++) pT[jp * Lk + lane] = make_double2(T[2 * jp], T[2 * jp + 1]);
         }
-        if (threadIdx.x < blk.n_zones) fa.zone_T[fa.zones[blk.first_zone + threadIdx.x]] = s_zT[threadIdx.x];
+        if (threadIdx.x < blk.n_zones) {
+            fa.zone_T[fa.zones[blk.first_zone + threadIdx.x]] = s_zT[threadIdx.x];
+            if constexpr (IDEAL) fused_ideal_write_back(fa, fl);
+        }
     }
     if (write_out && active && (is_first || is_last)) {
         SideOut o;
@@ -1600,7 +1770,10 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
 // only the final temperatures, coefficients and flows are written back.
 // (FUSED is the most wavefronts a workgroup may hold: 4 or 8; it needs PAL = 1; with cavities, M <= 8.)
 // SMALL = 1: the workgroup may also hold wavefronts of small all-no-mass surfaces (fused_small_wave).
-template <int M, int NM, int PAL, int CAV, int FUSED, int SMALL = 0>
+// IDEAL = 1 (FUSED, no teams, no cavity class, no chunk loop): the zone balance hosts the ideal-loads rule of a series
+// (fused_zone_phase); the LDS grows by kFusedIdealLdsBytes behind the slot lists. Everything of it sits behind
+// `if constexpr (IDEAL)`: the other instantiations compile from the source they always had.
+template <int M, int NM, int PAL, int CAV, int FUSED, int SMALL = 0, int IDEAL = 0>
 __global__ void __launch_bounds__(FUSED ? 64 * FUSED : 256, (FUSED || (M == 16 && !CAV)) ? 2 : 1)
 k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, SideArrays sd,
                 const StepWeather *__restrict__ weather, const int *__restrict__ step_ptr, int step_fixed,
@@ -1608,6 +1781,8 @@ k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, 
                 unsigned long long *__restrict__ nomass_iters, FusedArgs fa) {
     static_assert(!FUSED || (PAL && !(CAV && M == 16)),
                   "the cluster-resident march exists for palette classes; with gas cavities for 4 or 8 nodes per lane");
+    static_assert(!IDEAL || (FUSED && SMALL != 2 && NM != 2 && (SMALL == 1 || !CAV)),
+                  "ideal loads ride on the plain and the mixed workgroups only: no teams, no cavity class, no chunk loop");
     constexpr int kMaxW = FUSED ? FUSED : 4;
     constexpr int kLanes = kMaxW * kWave;
     // LDS: the palettes of the block's tiles; FUSED adds the per-side (hs, face temperature) pairs the zone
@@ -1691,7 +1866,7 @@ k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, 
         }
         if constexpr (SMALL == 1) {
             if (wib >= blk.n_tiles) {
-                fused_small_wave(blk, fa, fl, kLanes, wib, blk_waves, lane, na, sd, weather, flags);
+                fused_small_wave<IDEAL>(blk, fa, fl, kLanes, wib, blk_waves, lane, na, sd, weather, flags);
                 if (!looping) return;
                 goto next_block;
             }
@@ -1704,9 +1879,9 @@ k_surfaces_fast(const FastTile *__restrict__ tiles, int n_tiles, NodeArrays na, 
     const int tix = (!FUSED && fa.reverse) ? n_tiles - 1 - wave : wave;
     const FastTile tl = tiles[tix];
     // (the tile's weather site; a fused workgroup's and a team's tiles are all of one site)
-    fast_tile_march<M, NM, PAL, CAV, FUSED, SMALL>(tl, tix, true, lane, wib, s_pal, s_V, s_pos_static, fl, blk, blk_waves, n_it, step0, na,
-                                                   sd, site_weather(weather, sd, tl.surf_base), zone_T, flags, nomass_iters, fa,
-                                                   write_out, team);
+    fast_tile_march<M, NM, PAL, CAV, FUSED, SMALL, IDEAL>(tl, tix, true, lane, wib, s_pal, s_V, s_pos_static, fl, blk, blk_waves, n_it, step0,
+                                                          na, sd, site_weather(weather, sd, tl.surf_base), zone_T, flags, nomass_iters,
+                                                          fa, write_out, team);
     }
 next_block:
     if constexpr (FUSED) {
@@ -2042,6 +2217,8 @@ k_surfaces_general(const GeneralTile *__restrict__ tiles, int n_tiles, NodeArray
 //   mode 0: every zone, full update (single GPU).
 //   mode 1: every zone, write the partial (a, b) into partial[2][n_zones] only.
 //   mode 3: as mode 0, but only the zones in zlist[n_list] (the others are owned by fused workgroups).
+//   mode 6: as mode 1, but only the zones in zlist[n_list] (an ideal series beside a resident march: k_zone_update_ideal
+//           finishes that list).
 //   mode 2: sharded: only the zones in zlist[n_list] (those this rank's surfaces touch); a zone no other rank
 //           touches (slot_of[z] < 0) is updated here and now, a shared one writes its partial (a, b) into the
 //           compact partial[2][n_shared] at its slot for the exchange.
@@ -2058,7 +2235,7 @@ k_zones(const int64_t *__restrict__ zone_off, const ZoneEntry *__restrict__ entr
     const int wv = (blockIdx.x * blockDim.x + threadIdx.x) / kW;
     if (blockIdx.x == 0 && threadIdx.x == 0 && (mode == 0 || mode == 3)) *step_ptr += 1;
     int z = wv;
-    if (mode == 2 || mode == 3) {
+    if (mode == 2 || mode == 3 || mode == 6) {
         if (wv >= n_list) return;  // (whole rows leave: the row sums below stay inside a row)
         z = zlist[wv];
     }
@@ -2091,7 +2268,7 @@ k_zones(const int64_t *__restrict__ zone_off, const ZoneEntry *__restrict__ entr
         b = wave_sum_f64(b);
         if (lane != 0) return;
     }
-    if (mode == 1) {
+    if (mode == 1 || mode == 6) {
         partial[z] = a;
         partial[n_zones + z] = b;
         return;
@@ -3333,67 +3510,36 @@ __global__ void __launch_bounds__(256) k_series_ideal_begin(IdealLoadsDev il, co
 // k_zone_update_ideal — one lane per zone, behind k_zones in mode 1: the zone update of k_zone_update from ONE block of
 // partial sums ([2][n_zones], summed by k_zones' lanes and tree), and for a zone with a load the rule of the header. A zone
 // has at most one load and a load one zone: qsum[i] and the saturation counts have one writer — plain stores, no atomics.
+// n_list >= 0: only the zones zlist[0 .. n_list) — an ideal series whose clusters march resident streams the zones no
+// workgroup owns (k_zones in mode 6 before it) and must never write a zone a workgroup has in LDS; an empty list only
+// advances the step counter. n_list < 0 (zlist is not read): every zone.
 __global__ void __launch_bounds__(256)
 k_zone_update_ideal(const double *__restrict__ partial, const double *__restrict__ a0, const double *__restrict__ b0,
                     const double *__restrict__ zone_vol, double *__restrict__ zone_T, int n_zones, double dt,
-                    int *__restrict__ step_ptr, int *__restrict__ flags, IdealLoadsDev il) {
-    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+                    int *__restrict__ step_ptr, int *__restrict__ flags, IdealLoadsDev il, const int32_t *__restrict__ zlist,
+                    int n_list) {
+    int z = blockIdx.x * blockDim.x + threadIdx.x;
     if (z == 0) *step_ptr += 1;
+    if (n_list >= 0) {
+        if (z >= n_list) return;
+        z = zlist[z];
+    }
     if (z >= n_zones) return;
     const int i = il.load_of_zone[z];
-    const double a = partial[z] + a0[z];
-    const double b = partial[n_zones + z] + b0[z];
     const double tc = zone_T[z];
     const double cz = zone_mcp(zone_vol[z], tc);  // model.rs:549-552
-    double q = 0.0, ft = tc;
-    if (fabs(b) > 1e-9) {  // model.rs:662-668
-        const double r = a / b;
-        const double nbdt = (-b) * dt;
-        const double E = exp(nbdt / cz);
-        const double dE = (tc - r) * E;
-        const double free_t = r + dE;
-        ft = free_t;
-        const double D = 1.0 - E;
-        if (i >= 0 && D > 0.0) {
-            const double h = il.setpoint[i], c = il.setpoint[il.n_loads + i];
-            const double tcE = tc * E;
-            if (il.heat_chan[i] >= 0 && free_t < h) {
-                const double num = b * (h - tcE);
-                const double need = num / D - a;
-                const double cap = il.heat_cap[i];
-                q = need > cap ? cap : need;
-                if (!(q > 0.0)) q = 0.0;
-                if (q > 0.0) {
-                    if (q == need) {
-                        ft = h;
-                    } else {
-                        const double a2 = a + q;
-                        const double r2 = a2 / b;
-                        const double d2 = (tc - r2) * E;
-                        ft = r2 + d2;
-                        if (il.n_sat_heating != nullptr) il.n_sat_heating[i] += 1;
-                    }
-                }
-            } else if (il.cool_chan[i] >= 0 && free_t > c) {
-                const double num = b * (c - tcE);
-                const double need = num / D - a;
-                const double cap = -il.cool_cap[i];
-                q = need < cap ? cap : need;
-                if (!(q < 0.0)) q = 0.0;
-                if (q < 0.0) {
-                    if (q == need) {
-                        ft = c;
-                    } else {
-                        const double a2 = a + q;
-                        const double r2 = a2 / b;
-                        const double d2 = (tc - r2) * E;
-                        ft = r2 + d2;
-                        if (il.n_sat_cooling != nullptr) il.n_sat_cooling[i] += 1;
-                    }
-                }
-            }
-        }
+    double h = 0.0, c = 0.0, heat_cap = 0.0, cool_cap = 0.0;
+    if (i >= 0) {  // (k_series_ideal_begin left NaN where the load has no channel of that kind)
+        h = il.setpoint[i];
+        c = il.setpoint[il.n_loads + i];
+        heat_cap = il.heat_cap[i];
+        cool_cap = il.cool_cap[i];
     }
+    double q, ft;
+    int sat;
+    ideal_zone_rule(i >= 0, partial[z], partial[n_zones + z], a0[z], b0[z], tc, cz, dt, h, c, heat_cap, cool_cap, ft, q, sat);
+    if (sat == 1 && il.n_sat_heating != nullptr) il.n_sat_heating[i] += 1;
+    if (sat == 2 && il.n_sat_cooling != nullptr) il.n_sat_cooling[i] += 1;
     if (ft != ft) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);  // model.rs:417-420
     zone_T[z] = ft;
     if (i >= 0) il.qsum[i] = il.qsum[i] + q;
@@ -3482,17 +3628,19 @@ void launch_surfaces_stream(int variant, const FastTile *tiles, int n_tiles, con
 // Cluster-resident march of one class: one workgroup of `max_waves` (4 or 8) wavefronts per FusedBlock, fa.n_sub
 // sub-timesteps in one launch. Palette classes without cavities only.
 // (what k_surfaces_fast carves up: palettes, V rows where fused_v_in_lds, pairs [2][lanes], six zone arrays, offsets, slots)
-size_t fused_lds_bytes(int max_waves, int M, int pal_stride, bool v_in_lds) {
+// ideal: the IDEAL instantiations' per-zone arrays behind the slot lists (layout.hpp, kFusedIdealLdsBytes)
+size_t fused_lds_bytes(int max_waves, int M, int pal_stride, bool v_in_lds, bool ideal = false) {
     const int v_rows = v_in_lds ? M : 0;
     return (size_t)max_waves * kWave * ((pal_stride + v_rows) * sizeof(double) + 2 * sizeof(double2)) +
-           6 * kFusedMaxZones * sizeof(double) + (kFusedMaxZones + 2) * sizeof(int) + kFusedMaxEntries * sizeof(uint16_t);
+           6 * kFusedMaxZones * sizeof(double) + (kFusedMaxZones + 2) * sizeof(int) + kFusedMaxEntries * sizeof(uint16_t) +
+           (ideal ? kFusedIdealLdsBytes : 0);
 }
 
-template <int MM, int NN, int CC, int FW, int SM>
+template <int MM, int NN, int CC, int FW, int SM, int ID = 0>
 static hipError_t launch_fused_one(int grid_blocks, const FastTile *tiles, int n_tiles, const NodeArrays &na,
                                    const SideArrays &sa, const StepWeather *weather, int *flags,
                                    unsigned long long *nomass_iters, const FusedArgs &fa, hipStream_t st) {
-    const size_t lds = fused_lds_bytes(FW, MM, na.pal_stride, fused_v_in_lds(MM, NN, FW, SM));
+    const size_t lds = fused_lds_bytes(FW, MM, na.pal_stride, fused_v_in_lds(MM, NN, FW, SM), ID != 0);
     // (per instantiation and device) dynamic LDS above the 64 KB default needs the attribute; it grows with the palette width
     constexpr int kMaxDevices = 64;
     static std::atomic<size_t> attr_bytes[kMaxDevices];  // 0: never set
@@ -3500,12 +3648,12 @@ static hipError_t launch_fused_one(int grid_blocks, const FastTile *tiles, int n
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = kMaxDevices - 1;
     if (lds > 64 * 1024 && lds > attr_bytes[dev].load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_surfaces_fast<MM, NN, 1, CC, FW, SM>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_surfaces_fast<MM, NN, 1, CC, FW, SM, ID>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         if (dev != kMaxDevices - 1) attr_bytes[dev].store(lds, std::memory_order_release);  // (an unknown device: set it every time)
     }
-    hipLaunchKernelGGL((k_surfaces_fast<MM, NN, 1, CC, FW, SM>), dim3(grid_blocks), dim3(kWave * FW), lds, st, tiles,
+    hipLaunchKernelGGL((k_surfaces_fast<MM, NN, 1, CC, FW, SM, ID>), dim3(grid_blocks), dim3(kWave * FW), lds, st, tiles,
                        n_tiles, na, sa, weather, nullptr, 0, nullptr, flags, nomass_iters, fa);
     return hipSuccess;
 }
@@ -3515,12 +3663,14 @@ static hipError_t launch_fused_one(int grid_blocks, const FastTile *tiles, int n
 // grid_blocks = n_teams * kTeamMax, fa.supers / team_zinfo / xbuf / tag_base set.
 // How many workgroups of a fused variant one compute unit holds (two waves per SIMD by registers; three for the
 // plain 4-node variants), also bounded by LDS.
-int fused_blocks_per_cu(int M, int cav, int mixed, int max_waves, int pal_stride) {
+// ideal: the IDEAL instantiation of the variant — its extra LDS; by registers it keeps its sibling's waves per SIMD
+// (DESIGN.md 4a tables them side by side).
+int fused_blocks_per_cu(int M, int cav, int mixed, int max_waves, int pal_stride, int ideal) {
     const int waves_per_simd = (M == 4 && !cav && !mixed) ? 3 : 2;
     const int by_regs = std::max(1, waves_per_simd * 4 / max_waves);
     // (mixed is 0 or 1 here — teams: fused_team_blocks_per_cu; workgroups with small surfaces run the NM = 1 variants)
     const bool v_in_lds = fused_v_in_lds(M, mixed ? 1 : 0, max_waves <= 4 ? 4 : 8, mixed);
-    const int by_lds = std::max<int>(1, (int)(160 * 1024 / fused_lds_bytes(max_waves, M, pal_stride, v_in_lds)));
+    const int by_lds = std::max<int>(1, (int)(160 * 1024 / fused_lds_bytes(max_waves, M, pal_stride, v_in_lds, ideal != 0)));
     return std::min(by_regs, by_lds);
 }
 
@@ -3544,10 +3694,31 @@ int fused_team_blocks_per_cu(int M, int nm, int pal_stride) {
 // grid_blocks workgroups for fa.n_blocks FusedBlocks: equal (fa.queue == nullptr) or fewer, with the work queue.
 hipError_t launch_surfaces_fused(int M, int nm, int cav, int mixed, int max_waves, int grid_blocks, const FastTile *tiles,
                                  int n_tiles, const NodeArrays &na, const SideArrays &sa, const StepWeather *weather,
-                                 int *flags, unsigned long long *nomass_iters, const FusedArgs &fa, hipStream_t st) {
+                                 int *flags, unsigned long long *nomass_iters, const FusedArgs &fa, hipStream_t st, int ideal) {
     const int n_blocks = grid_blocks;
     if (n_blocks <= 0) return hipSuccess;
     if (cav && M == 16) return hipErrorInvalidValue;  // (the planner never asks for it)
+    if (ideal) {
+        // A series with ideal loads marched resident: the plain variants (no cavity class, no chunk loop) and the mixed
+        // ones have an IDEAL instantiation, nothing else — the engine asks only where the whole batch is eligible
+        // (plan.hpp, ideal_resident_reason); anything else is an error, never another kernel.
+        if (mixed == 2 || (!mixed && (cav || nm == 2))) return hipErrorInvalidValue;
+#define HEAT_FUSED_I(MM, NN, CC, FW, SM) \
+    launch_fused_one<MM, NN, CC, FW, SM, 1>(n_blocks, tiles, n_tiles, na, sa, weather, flags, nomass_iters, fa, st)
+        if (mixed) {
+            if (M == 4) return max_waves <= 4 ? HEAT_FUSED_I(4, 1, 1, 4, 1) : HEAT_FUSED_I(4, 1, 1, 8, 1);
+            if (M == 8) return max_waves <= 4 ? HEAT_FUSED_I(8, 1, 1, 4, 1) : HEAT_FUSED_I(8, 1, 1, 8, 1);
+            return max_waves <= 4 ? HEAT_FUSED_I(16, 1, 0, 4, 1) : HEAT_FUSED_I(16, 1, 0, 8, 1);
+        }
+#define HEAT_FUSED_INW(MM)                                                          \
+    (max_waves <= 4 ? (nm ? HEAT_FUSED_I(MM, 1, 0, 4, 0) : HEAT_FUSED_I(MM, 0, 0, 4, 0)) \
+                    : (nm ? HEAT_FUSED_I(MM, 1, 0, 8, 0) : HEAT_FUSED_I(MM, 0, 0, 8, 0)))
+        if (M == 4) return HEAT_FUSED_INW(4);
+        if (M == 8) return HEAT_FUSED_INW(8);
+        return HEAT_FUSED_INW(16);
+#undef HEAT_FUSED_INW
+#undef HEAT_FUSED_I
+    }
 #define HEAT_FUSED(MM, NN, CC, FW, SM) \
     launch_fused_one<MM, NN, CC, FW, SM>(n_blocks, tiles, n_tiles, na, sa, weather, flags, nomass_iters, fa, st)
     if (mixed == 2) {  // teams of workgroups (clusters larger than one): four wavefronts each, no cavities, no small surfaces
@@ -3601,8 +3772,8 @@ void launch_zones(const int64_t *zone_off, const ZoneEntry *entries, const ZoneC
                   const double *a0, const double *b0, const double *zone_vol, double *zone_T, double *partial,
                   int n_zones, double dt, int *step_ptr, int *flags, int mode, const int32_t *zlist, int n_list,
                   const int32_t *slot_of, int n_shared, int rows, hipStream_t st) {
-    const int n_z = (mode == 2 || mode == 3) ? n_list : n_zones;
-    if (mode == 2 && n_z <= 0) return;
+    const int n_z = (mode == 2 || mode == 3 || mode == 6) ? n_list : n_zones;
+    if ((mode == 2 || mode == 6) && n_z <= 0) return;
     // rows: a zone per row of 16 lanes (the batch's zones have few walls each), else a zone per wavefront
     if (rows) {
         const int nb = n_z > 0 ? (n_z + 15) / 16 : 1;
@@ -3823,10 +3994,12 @@ void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipSt
 }
 
 void launch_zone_update_ideal(const double *partial, const double *a0, const double *b0, const double *zone_vol, double *zone_T,
-                              int n_zones, double dt, int *step_ptr, int *flags, const IdealLoadsDev &il, hipStream_t st) {
-    const int nb = n_zones > 0 ? (n_zones + 255) / 256 : 1;
+                              int n_zones, double dt, int *step_ptr, int *flags, const IdealLoadsDev &il, hipStream_t st,
+                              const int32_t *zlist, int n_list) {
+    const int n_z = n_list >= 0 ? n_list : n_zones;
+    const int nb = n_z > 0 ? (n_z + 255) / 256 : 1;  // (an empty list still advances the step counter)
     hipLaunchKernelGGL(k_zone_update_ideal, dim3(nb), dim3(256), 0, st, partial, a0, b0, zone_vol, zone_T, n_zones, dt, step_ptr,
-                       flags, il);
+                       flags, il, zlist, n_list);
 }
 
 void launch_series_ideal_end(const IdealLoadsDev &il, double *q_row, int64_t step, hipStream_t st) {

@@ -26,12 +26,13 @@ constexpr int kStreamVariants = 4;
 void launch_surfaces_stream(int variant, const FastTile *tiles, int n_tiles, const NodeArrays &na, int64_t gen_base, const SideArrays &sa,
                             const StepWeather *weather, const int *step_ptr, int step_fixed, const double *zone_T,
                             int *flags, unsigned long long *nomass_iters, int n_cu, hipStream_t st, int reverse = 0);
-int fused_blocks_per_cu(int M, int cav, int mixed, int max_waves, int pal_stride);
+// ideal: the IDEAL instantiation (a series with ideal loads marched resident; plain and mixed workgroups only)
+int fused_blocks_per_cu(int M, int cav, int mixed, int max_waves, int pal_stride, int ideal = 0);
 // ... of a team variant, from the runtime's occupancy query for that very kernel (0: the query failed)
 int fused_team_blocks_per_cu(int M, int nm, int pal_stride);
 hipError_t launch_surfaces_fused(int M, int nm, int cav, int mixed, int max_waves, int grid_blocks, const FastTile *tiles, int n_tiles,
                                  const NodeArrays &na, const SideArrays &sa, const StepWeather *weather, int *flags,
-                                 unsigned long long *nomass_iters, const FusedArgs &fa, hipStream_t st);
+                                 unsigned long long *nomass_iters, const FusedArgs &fa, hipStream_t st, int ideal = 0);
 void launch_surfaces_general(const GeneralTile *tiles, int n_tiles, const NodeArrays &na, int64_t gen_base,
                              const SideArrays &sa, const CavityDev *cavs, double *scratch,
                              const StepWeather *weather, const int *step_ptr, int step_fixed,
@@ -339,6 +340,8 @@ void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 // copies the step's setpoints out of the channel row and zeroes qsum; per sub-timestep, behind the surface kernels and
 // launch_zones in mode 1 (partial = [2][n_zones]): launch_zone_update_ideal, one lane per zone — it takes no per-step
 // argument, so a captured sub-timestep stays valid over the steps; on the step's tail: launch_series_ideal_end.
+// Beside a cluster-resident march that hosts the rule itself (launch_surfaces_fused, ideal; FusedArgs::il_*) the streamed
+// pair is launch_zones in mode 6 and launch_zone_update_ideal with the list of the zones no workgroup owns.
 struct IdealLoadsDev {
     int n_loads;
     const int32_t *load_of_zone;            // [n_zones]: the zone's load, -1: none
@@ -352,7 +355,8 @@ struct IdealLoadsDev {
 };
 void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipStream_t st);
 void launch_zone_update_ideal(const double *partial, const double *a0, const double *b0, const double *zone_vol, double *zone_T,
-                              int n_zones, double dt, int *step_ptr, int *flags, const IdealLoadsDev &il, hipStream_t st);
+                              int n_zones, double dt, int *step_ptr, int *flags, const IdealLoadsDev &il, hipStream_t st,
+                              const int32_t *zlist = nullptr, int n_list = -1);  // n_list >= 0: only the zones of zlist
 // q_row: the step's row of ideal_q, or nullptr; step: K = step_base + k
 void launch_series_ideal_end(const IdealLoadsDev &il, double *q_row, int64_t step, hipStream_t st);
 

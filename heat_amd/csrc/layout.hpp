@@ -230,7 +230,23 @@ struct FusedArgs {
     uint32_t tag_base;                   // launch number << 22 (tag = tag_base | round << 12 | sub-timestep + 1)
     int32_t team_size;                   // workgroups per team in this launch: the most members a cluster of the list has
     int32_t reverse;     // walk the tile list (streamed launches) / the block or cluster list (cluster-resident) from its end: zig-zag sweeps, batch.hip
+    // Ideal loads of a series hosted by the resident march (the IDEAL instantiations of k_surfaces_fast only; nothing else
+    // reads them): the device view of the loads (kernels.hpp, IdealLoadsDev) — the zone's load or -1 [n_zones of the batch],
+    // the step's setpoints [2][il_n_loads], the capacities, the setpoint channels, the step's q-sums and the nullable
+    // saturation counters [il_n_loads] each. A zone has one load and one owning workgroup: plain stores, no atomics.
+    const int32_t *il_load_of_zone;
+    const double *il_setpoint;
+    const double *il_heat_cap, *il_cool_cap;
+    const int32_t *il_heat_chan, *il_cool_chan;
+    double *il_qsum;
+    int64_t *il_n_sat_heating, *il_n_sat_cooling;
+    int32_t il_n_loads;
+    int32_t il_pad;
 };
+// LDS the IDEAL instantiations add behind the slot lists, per zone of the workgroup [kFusedMaxZones] each: heating and
+// cooling setpoint (NaN: no channel of that kind), the two capacities, the step's q accumulator (doubles); the two
+// saturation counters and the zone's load or -1 (ints).
+constexpr int kFusedIdealLdsBytes = kFusedMaxZones * (5 * 8 + 3 * 4);
 
 // Clusters larger than a workgroup (a building whose rooms are all joined by interior walls): a TEAM of up to
 // kTeamMax workgroups of four wavefronts marches the cluster together. Every member holds part of the walls and the

@@ -2128,6 +2128,39 @@ int check_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, const 
     return HEAT_OK;
 }
 
+// ---- ideal loads in the cluster-resident march: eligibility of a batch (plan.hpp) ----
+int ideal_resident_reason(const size_t (&n_blocks)[kNumFast][4], const size_t (&n_supers)[kNumFast], const bool (&has_chunks)[kNumFast]) {
+    bool any = false, teams = false, cavity = false, chunks = false;
+    for (int c = 0; c < kNumFast; c++) {
+        if (n_supers[c] > 0) any = teams = true;
+        for (int g2 = 0; g2 < 4; g2++) {
+            if (n_blocks[c][g2] == 0) continue;
+            any = true;
+            // (a list of workgroups with small surfaces marches the universal variant of its blocking factor whatever
+            // its class — cavities allowed —, and that variant has its ideal instantiation: kernels.hip)
+            if (kFastCAV[c] && !(g2 >> 1)) cavity = true;
+            // (the launch's choice of the chunk-loop variant, NM = 2: batch.hip, enqueue_fused)
+            if (kFastNM[c] && has_chunks[c] && !(g2 >> 1) && !kFastCAV[c] && kFastM[c] <= 8) chunks = true;
+        }
+    }
+    if (!any) return HEAT_IDEAL_RESIDENT_NONE_PLANNED;
+    if (teams) return HEAT_IDEAL_RESIDENT_TEAMS;
+    if (cavity) return HEAT_IDEAL_RESIDENT_CAVITY_CLASS;
+    if (chunks) return HEAT_IDEAL_RESIDENT_CHUNK_LOOP_CLASS;
+    return HEAT_IDEAL_RESIDENT_OK;
+}
+
+const char *ideal_resident_reason_text(int reason) {
+    switch (reason) {
+    case HEAT_IDEAL_RESIDENT_OK: return "eligible";
+    case HEAT_IDEAL_RESIDENT_NONE_PLANNED: return "nothing of the batch is planned resident";
+    case HEAT_IDEAL_RESIDENT_TEAMS: return "clusters marched by teams of workgroups";
+    case HEAT_IDEAL_RESIDENT_CAVITY_CLASS: return "resident workgroups of walls only in a class with gas cavities";
+    case HEAT_IDEAL_RESIDENT_CHUNK_LOOP_CLASS: return "resident workgroups of a class with no-mass chunks other than facings";
+    default: return "unknown";
+    }
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -3348,6 +3381,35 @@ int heat_plan_check(const heat_batch_desc *desc, const heat_batch_options *opt, 
 int heat_plan_check_sites(const heat_batch_desc *desc, const heat_batch_options *opt, int32_t n_sites,
                           const int32_t *site_of_surface, int64_t summary[8]) {
     return plan_check_impl(desc, opt, n_sites, site_of_surface, true, summary);
+}
+
+int heat_plan_ideal_resident(const heat_batch_desc *desc, const heat_batch_options *opt_in, int32_t n_sites,
+                             const int32_t *site_of_surface, int32_t *reason) {
+    if (reason) *reason = HEAT_IDEAL_RESIDENT_NONE_PLANNED;
+    heat_batch_options opt;
+    memset(&opt, 0, sizeof opt);
+    opt.device = -1;
+    opt.n_ranks = 1;
+    if (opt_in) opt = *opt_in;
+    int rc;
+    if (site_of_surface != nullptr || n_sites != 1) {
+        rc = heat::check_sites(desc, opt, n_sites, site_of_surface, heat::last_error());
+        if (rc) return rc;
+    }
+    heat::Plan p;
+    rc = heat::make_plan(desc, opt, p, heat::last_error(), n_sites, site_of_surface);
+    if (rc) return rc;
+    size_t n_blocks[heat::kNumFast][4], n_supers[heat::kNumFast];
+    bool has_chunks[heat::kNumFast];
+    for (int c = 0; c < heat::kNumFast; c++) {
+        for (int g2 = 0; g2 < 4; g2++) n_blocks[c][g2] = p.fblocks[c][g2].size();
+        n_supers[c] = p.team_supers[c].size();
+        has_chunks[c] = false;
+        for (const heat::FastTile &ft : p.fast_tiles[c]) has_chunks[c] = has_chunks[c] || (ft.k & heat::kTileChunkyBit) != 0;
+    }
+    const int why = heat::ideal_resident_reason(n_blocks, n_supers, has_chunks);
+    if (reason) *reason = why;
+    return why == HEAT_IDEAL_RESIDENT_OK ? 1 : 0;
 }
 
 }  // extern "C"

@@ -113,6 +113,17 @@ constexpr int32_t kMaxSites = 65536;
 int check_sites(const heat_batch_desc *d, const heat_batch_options &opt, int32_t n_sites, const int32_t *site_of_surface,
                 std::string &err);
 
+// Ideal loads in the cluster-resident march (heat_batch_set_ideal_resident, include/heat_amd.h): whether EVERY resident
+// launch a batch would make has an ideal instantiation of its kernel — decided for the whole batch from its workgroup
+// lists: n_blocks[c][g2] workgroups per class and list (Plan::fblocks / heat_batch::h_fblocks), n_supers[c] team clusters,
+// has_chunks[c] the class holds tiles with no-mass chunks other than facings (kTileChunkyBit). Returns a
+// heat_ideal_resident_reason: HEAT_IDEAL_RESIDENT_OK, or why not — the first that applies of: nothing planned resident,
+// teams, workgroups of walls only in a cavity class (a workgroup that also holds small surfaces marches the universal
+// variant of its blocking factor, which has an ideal instantiation), workgroups that march with the chunk-loop variant.
+// heat_plan_ideal_resident (from a plan) and the batch (from its lists) both ask this function.
+int ideal_resident_reason(const size_t (&n_blocks)[kNumFast][4], const size_t (&n_supers)[kNumFast], const bool (&has_chunks)[kNumFast]);
+const char *ideal_resident_reason_text(int reason);
+
 // Index into the T buffer of node i of a surface placed at (tile_base, geom) — Plan::node_tile_base / node_geom; the
 // layouts k_nodes_fast / k_nodes_general walk (layout.hpp).
 inline int64_t node_slot_index(int64_t tile_base, int32_t geom, int i) {

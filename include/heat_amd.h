@@ -466,8 +466,24 @@ int heat_batch_march_series_report(heat_batch *b, const heat_series *s, const he
  * step_base + k gives the bits of the series of n (ideal_q, accumulators, trace and state).
  * heat_cap / cool_cap: W, >= 0, +inf = unlimited; a NULL array = all unlimited. A capacity of 0 never acts.
  * The zone of an ideal load may also be a thermostat's target or sensor, a gain or flow zone, a probe or a group entry.
- * Weather sites are supported. A series with ideal loads marches every sub-timestep streamed (surfaces, zone sums, this
- * rule): the cluster-resident march is not used for it, and the batch's fusion setting is left as it is for later calls.
+ * Weather sites are supported. By default a series with ideal loads marches every sub-timestep streamed (surfaces, zone
+ * sums, this rule): the cluster-resident march is not used for it, and the batch's fusion setting is left as it is for
+ * later calls.
+ * RESIDENT FORM, opt-in per batch (heat_batch_set_ideal_resident, below): the clusters the batch marches resident stay
+ * resident in an ideal series, and the lane that finishes a zone in the cluster-resident march applies the rule above. The
+ * rule is unchanged with ONE substitution: for the zones a workgroup owns, s_a, s_b (and the surfaces' march) are the
+ * cluster-resident march's — its lanes, its tree — instead of the streamed zone balance's; the streamed remainder of the
+ * batch keeps the streamed sums. Everything the rule makes exact stays exact (an unsaturated zone is at its setpoint bit for
+ * bit, qsum is the sequential sum over the step's sub-timesteps from 0.0, the accumulators, cut and resume, run-to-run
+ * identity), but the resident form is NOT bit-equal to the streamed form: the two differ by the rounding of the sums. A zone
+ * without a load has, from the same inputs, the bits of the plain resident march. Without the opt-in nothing changes: the
+ * same kernels, the same bits.
+ * LIMIT: residency is decided for the WHOLE batch, once, from its plan — every resident launch the batch would make needs an
+ * ideal instantiation of its kernel, so a batch with clusters marched by teams, with resident workgroups of walls only in a
+ * class with gas cavities, or in a class with no-mass chunks other than facings marches its ideal series streamed as before, batch-wide
+ * (heat_plan_ideal_resident names the reason; with HEAT_AMD_TRACE set the series says so once). Routing only those classes
+ * to the streamed leg for one call is not done: what is streamed and what is resident is fixed when the batch is created.
+ * The call-length rule of the plain march applies: n_sub = 1 on a batch of more than 8 192 surfaces streams.
  * heat_ideal_loads_check (host-only) and heat_batch_march_series_ideal run the same checks before any device work; every
  * message names "ideal load i": a negative count, a NULL array a positive count needs (zone, heat_chan, cool_chan), a step
  * array without its peak array, a capacity that is negative or NaN, a second load on a zone -> HEAT_E_INVALID_ARG; a zone
@@ -1355,6 +1371,31 @@ int heat_batch_comm_destroy(heat_batch *b);
 int heat_batch_set_fusion(heat_batch *b, int32_t enabled);
 int64_t heat_batch_n_fused_surfaces(const heat_batch *b);
 int64_t heat_batch_n_fused_launches(const heat_batch *b); /* cluster-resident launches issued since creation */
+
+/*
+ * Ideal loads in the cluster-resident march (heat_ideal_loads, RESIDENT FORM), opt-in per batch. Default 0: an ideal series
+ * marches streamed, every bit and every launch as without this call. enabled != 0 is durable until set again and
+ * independent of heat_batch_set_fusion (which still decides whether anything marches resident at all).
+ * heat_batch_ideal_resident: 1 when the next ideal series of this batch would march its resident clusters resident — the
+ * opt-in, fusion on, and an eligible batch — otherwise 0 (also for a NULL batch).
+ * heat_plan_ideal_resident (host-only, needs no device; arguments as heat_plan_check_sites, n_sites = 1 and a NULL
+ * site_of_surface for a single site): 1 when a batch made from this descriptor and these options is eligible, 0 when not,
+ * a negative heat_status when the descriptor cannot be planned; *reason (nullable) receives why not. opt->no_fusion = 1
+ * plans nothing resident, so the answer is 0, HEAT_IDEAL_RESIDENT_NONE_PLANNED. The batch asks the same function of its
+ * own plan.
+ */
+typedef enum heat_ideal_resident_reason {
+    HEAT_IDEAL_RESIDENT_OK = 0,
+    HEAT_IDEAL_RESIDENT_NONE_PLANNED = 1,     /* nothing of the batch is planned resident */
+    HEAT_IDEAL_RESIDENT_TEAMS = 2,            /* clusters marched by teams of workgroups */
+    HEAT_IDEAL_RESIDENT_CAVITY_CLASS = 3,     /* resident workgroups of walls only in a class with gas cavities (workgroups
+                                                 that also hold small surfaces — rooms with windows — are eligible) */
+    HEAT_IDEAL_RESIDENT_CHUNK_LOOP_CLASS = 4  /* resident workgroups in a class with no-mass chunks other than facings */
+} heat_ideal_resident_reason;
+int heat_batch_set_ideal_resident(heat_batch *b, int32_t enabled);
+int32_t heat_batch_ideal_resident(const heat_batch *b);
+int heat_plan_ideal_resident(const heat_batch_desc *desc, const heat_batch_options *opt, int32_t n_sites,
+                             const int32_t *site_of_surface, int32_t *reason);
 
 /* Introspection (tests, bench). */
 int64_t heat_batch_n_surfaces(const heat_batch *b);

@@ -157,6 +157,12 @@ extern "C" {
     pub fn heat_batch_download_outputs(b: *mut HeatBatch, state: *mut f64, n_state: usize, what: i32) -> c_int;
     pub fn heat_batch_failed_surface(b: *const HeatBatch, index: *mut i64, kind: *mut i32) -> c_int;
     pub fn heat_batch_set_fusion(b: *mut HeatBatch, enabled: i32) -> c_int;
+    // ideal loads in the cluster-resident march: opt-in per batch, what the batch would do, and the planner's answer
+    // (host-only; reason: heat_ideal_resident_reason, 0 eligible .. 4)
+    pub fn heat_batch_set_ideal_resident(b: *mut HeatBatch, enabled: i32) -> c_int;
+    pub fn heat_batch_ideal_resident(b: *const HeatBatch) -> i32;
+    pub fn heat_plan_ideal_resident(desc: *const HeatBatchDesc, opt: *const HeatBatchOptions, n_sites: i32,
+                                    site_of_surface: *const i32, reason: *mut i32) -> c_int;
     // solar gains of a series: window-transmitted solar onto the room's faces, formed on the device at every step
     pub fn heat_solar_gains_check(desc: *const HeatBatchDesc, n_sites: i32, s: *const HeatSeries, sky: *const HeatSky,
                                   gains: *const HeatSolarGains) -> c_int;

@@ -21,12 +21,14 @@ With --report (heat_batch_march_series_report; the loads of --loads) four legs, 
      the thermostat statistics
   G  F with the inside-face node of every wall as further probes (Q = S + 2 Z) and q_min alone; G4: with F's four statistics
 and writes profiles/series_report.json.
-With --ideal (heat_batch_march_series_ideal; the channels, driven inputs and loads of --loads plus a cooling setpoint channel) three
+With --ideal (heat_batch_march_series_ideal; the channels, driven inputs and loads of --loads plus a cooling setpoint channel) four
 legs, alternated in the same way, one ideal load per zone, heating and cooling, unlimited:
   S  the series with leg D's loads on a batch created with no_fusion: the streamed body the ideal path is built on
   I  the same plus the ideal loads (same batch)
+  R  leg I on the batch of leg D with heat_batch_set_ideal_resident: the ideal loads inside the cluster-resident march
+     (the opt-in is switched off again for leg D, which must stay the plain resident series)
   D  leg D itself, on the batch as planned (cluster-resident)
-and writes profiles/series_ideal.json: ms per step of each, I - S per sub-timestep, I / S and I / D.
+and writes profiles/series_ideal.json: ms per step of each, I - S per sub-timestep, I / S, I / D, R / D and R / I.
 With --sky (heat_batch_march_series_sky; the model, channels, loads and probes of leg D) two legs, alternated in the same way:
   C' every wall's front solar and front long-wave input driven from channels (64 columns shared by all walls: what a channel
      table can hold; with a column per wall — what walls of their own azimuth need — the table is 16 S bytes per step)
@@ -627,19 +629,32 @@ with HeatBatch(md) as b:
                 continue
             leg_d(bs, w, n_sub, min(STEPS, 10))
             leg_d(b, w, n_sub, min(STEPS, 10))
-            ss, ii, dd = [], [], []
+
+            def leg_r(steps):
+                b.set_ideal_resident(True)
+                assert b.ideal_resident == 1, "the batch of leg D is not eligible for resident ideal loads"
+                launches = b.n_fused_launches
+                ms = leg_i(b, w, n_sub, steps)
+                assert b.n_fused_launches > launches, "leg R was streamed"
+                b.set_ideal_resident(False)
+                return ms
+            leg_r(min(STEPS, 10))
+            ss, ii, rr, dd = [], [], [], []
             for r in range(ROUNDS):
                 ss.append(leg_d(bs, w, n_sub, STEPS))
                 ii.append(leg_i(bs, w, n_sub, STEPS))
+                rr.append(leg_r(STEPS))
                 dd.append(leg_d(b, w, n_sub, STEPS))
-            Sm, Im, Dm = float(np.median(ss)), float(np.median(ii)), float(np.median(dd))
+            Sm, Im, Rm, Dm = float(np.median(ss)), float(np.median(ii)), float(np.median(rr)), float(np.median(dd))
             result["legs"]["n_sub=%d" % n_sub] = dict(
-                S_streamed_series_with_loads_ms=Sm, I_ideal_series_ms=Im, D_series_with_loads_ms=Dm, I_minus_S_ms=Im - Sm,
-                I_minus_S_per_sub_timestep_us=(Im - Sm) * 1e3 / n_sub, I_over_S=Im / Sm, I_over_D=Im / Dm, ideal_loads=int(Z),
-                all_rounds=dict(S=ss, I=ii, D=dd))
-            print("n_sub %2d: S streamed series with loads %.3f ms/step, I with ideal loads %.3f, D fused %.3f -> I - S = %.3f ms "
-                  "(%.1f us per sub-timestep), I / S = %.3f, I / D = %.3f (%d steps, median of %d rounds)" % (
-                      n_sub, Sm, Im, Dm, Im - Sm, (Im - Sm) * 1e3 / n_sub, Im / Sm, Im / Dm, STEPS, ROUNDS), flush=True)
+                S_streamed_series_with_loads_ms=Sm, I_ideal_series_ms=Im, R_resident_ideal_series_ms=Rm, D_series_with_loads_ms=Dm,
+                I_minus_S_ms=Im - Sm, I_minus_S_per_sub_timestep_us=(Im - Sm) * 1e3 / n_sub, I_over_S=Im / Sm, I_over_D=Im / Dm,
+                R_minus_D_ms=Rm - Dm, R_minus_D_per_sub_timestep_us=(Rm - Dm) * 1e3 / n_sub, R_over_D=Rm / Dm, R_over_I=Rm / Im,
+                ideal_loads=int(Z), all_rounds=dict(S=ss, I=ii, R=rr, D=dd))
+            print("n_sub %2d: S streamed series with loads %.3f ms/step, I with ideal loads %.3f, R the same resident %.3f, D fused %.3f -> "
+                  "I - S = %.3f ms (%.1f us per sub-timestep), I / S = %.3f, I / D = %.3f, R / D = %.3f, R / I = %.3f (%d steps, median of "
+                  "%d rounds)" % (n_sub, Sm, Im, Rm, Dm, Im - Sm, (Im - Sm) * 1e3 / n_sub, Im / Sm, Im / Dm, Rm / Dm, Rm / Im, STEPS, ROUNDS),
+                  flush=True)
             continue
         if RADIATION:
             leg_d(b, w, n_sub, min(STEPS, 10))  # warm-up
