@@ -20,6 +20,63 @@ def build_host_main(tmp_path, stem):
                           ["-o", str(exe)])
     return exe
 
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The workgroup lists of a plan (tests/plan_lists_shim.cpp): which instantiation of the resident march a batch reaches
+N_FAST = 18                                 # plan.hpp, kNumFast
+FAST_M = [4] * 6 + [8] * 6 + [16] * 6        # plan.cpp, kFastM
+FAST_NM = [0, 0, 0, 1, 1, 1] * 3            # plan.cpp, kFastNM
+_plan_lists_lib = []
+
+
+def plan_lists_library():
+    """tests/plan_lists_shim.cpp and the planner (heat_amd.build.HOST_SOURCES), compiled once per process by g++ into a
+    temporary directory — no sanitizer, nothing preloaded — and loaded with ctypes."""
+    if not _plan_lists_lib:
+        import atexit
+        import ctypes as C
+        import tempfile
+        from heat_amd import binding
+        tmp = tempfile.TemporaryDirectory(prefix="plan_lists_")
+        so = os.path.join(tmp.name, "libplan_lists.so")
+        subprocess.check_call(["g++", "-std=c++17", "-O1", "-fPIC", "-shared", os.path.join(ROOT, "tests", "plan_lists_shim.cpp")] +
+                              [os.path.join(heat_build.CSRC, s) for s in heat_build.HOST_SOURCES] + ["-o", so])
+        L = C.CDLL(so)
+        L.plan_lists.restype = C.c_int
+        L.plan_lists.argtypes = [C.POINTER(binding.Desc), C.POINTER(binding.Options), C.POINTER(C.c_int64), C.c_int]
+        atexit.register(tmp.cleanup)         # (the directory lives as long as the library is loaded)
+        _plan_lists_lib.extend([L, tmp])
+    return _plan_lists_lib[0]
+
+
+def plan_lists(md, **opts):
+    """The plan of a batch made from `md` with the options `opts` (binding.make_options), as heat::make_plan gives it:
+      lists       {(class, list): workgroups} of the non-empty workgroup lists (Plan::fblocks)
+      teams       team clusters over all classes;   stream_tiles   streamed fast tiles over all classes
+      most_zones  the largest FusedBlock::n_zones;  reason         ideal_resident_reason (binding.IDEAL_RESIDENT_*)
+      resident_cavity_tiles   small-surface tiles with a gas cavity that a resident workgroup marches
+    Host-only; needs neither the product library nor a GPU."""
+    import ctypes as C
+    from heat_amd import binding
+    L = plan_lists_library()
+    desc, keep = binding.make_desc(md)
+    opt = binding.make_options(**opts)
+    out = (C.c_int64 * (N_FAST * 6 + 5))()
+    rc = L.plan_lists(C.byref(desc), C.byref(opt), out, len(out))
+    assert rc == 0, "make_plan returned %d" % rc
+    out = list(out)
+    n_small, n_plain, n_cav_streamed = out[N_FAST * 6 + 2:]
+    return dict(lists={(c, g2): out[c * 4 + g2] for c in range(N_FAST) for g2 in range(4) if out[c * 4 + g2]},
+                teams=sum(out[N_FAST * 4:N_FAST * 5]), stream_tiles=sum(out[N_FAST * 5:N_FAST * 6]), most_zones=out[N_FAST * 6],
+                reason=out[N_FAST * 6 + 1], resident_cavity_tiles=n_small - n_plain - n_cav_streamed)
+
+
+def instantiation_of(c, g2):
+    """The IDEAL instantiation a workgroup list marches with (batch.hip, enqueue_fused; kernels.hip, launch_surfaces_fused):
+    (M, "mixed" or "nm0" / "nm1", wavefronts per workgroup)."""
+    return FAST_M[c], "mixed" if g2 >> 1 else "nm%d" % FAST_NM[c], 8 if g2 & 1 else 4
+
+
 BRICKWORK = dict(k=0.816, rho=1700., cp=800., front_thermal_abs=0., back_thermal_abs=0.)   # surface.rs:1061-1075
 POLYURETHANE = dict(k=0.0252, rho=17.5, cp=2400., front_thermal_abs=0., back_thermal_abs=0.)  # surface.rs:1048-1059
 CONCRETE = dict(k=0.816, rho=1700., cp=800.)  # tests/massive_*/in.idf, tests/tilted/back.spl

@@ -78,7 +78,8 @@ def caps_of(ideal, n):
 
 def cpu_series(oracle, md, state, weather, n_sub, channel, drives, probes, loads, ideal, a0=None, b0=None):
     """Marches `state` in place. weather [n_steps, n_sub, 3]. Returns a dict: trace, ideal_q, n_sat_heating, n_sat_cooling,
-    applied, modes, scale [n_steps, n_loads], margin, acting (sub-timesteps with q != 0), n_heat / n_cool (with q > 0 / < 0)."""
+    applied, modes, scale [n_steps, n_loads], margin, acting (sub-timesteps with q != 0), n_heat / n_cool (with q > 0 / < 0),
+    q_sub [n_steps, n_sub, n_loads] (the power of every sub-timestep: ideal_q is its sum over the step)."""
     m = oracle.OracleModel(md)
     zone_slot = md["zone_slot"]
     Z, dt = int(md["n_zones"]), float(md["dt"])
@@ -92,7 +93,7 @@ def cpu_series(oracle, md, state, weather, n_sub, channel, drives, probes, loads
     modes = start_modes(loads)
     out = dict(trace=np.zeros((n_steps, len(probes))), ideal_q=np.zeros((n_steps, N)), n_sat_heating=np.zeros(N, np.int64),
                n_sat_cooling=np.zeros(N, np.int64), applied=np.zeros((n_steps, n_thermostats(loads))), scale=np.zeros((n_steps, N)),
-               margin=math.inf, n_heat=0, n_cool=0, n_free=0)
+               margin=math.inf, n_heat=0, n_cool=0, n_free=0, q_sub=np.zeros((n_steps, n_sub, N)))
     for k in range(n_steps):
         za, zb, out["applied"][k] = host_rule(state[zone_slot], channel[k], term_row(a0, k), term_row(b0, k), loads, modes)
         write_inputs(md, state, k, channel, drives)
@@ -113,6 +114,7 @@ def cpu_series(oracle, md, state, weather, n_sub, channel, drives, probes, loads
                                             cch[i] >= 0, float(hcap[i]), float(ccap[i]))
                 ft[z] = f
                 out["ideal_q"][k, i] = out["ideal_q"][k, i] + q
+                out["q_sub"][k, s, i] = q
                 out["scale"][k, i] = max(out["scale"][k, i], S)
                 out["margin"] = min(out["margin"], margin)
                 out["n_sat_heating"][i] += sat > 0

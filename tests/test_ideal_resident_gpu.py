@@ -100,8 +100,9 @@ def reference_of(oracle, name, n_steps, n_sub):
     return _REF[key]
 
 
-def run_resident(md, st, w, n_sub, channel, drives, probes, a0, b0, loads, ideal, opts, **more):
-    """run() of tests/test_ideal_loads_gpu.py with the opt-in — plus what every resident case asserts of its batch."""
+def run_resident(md, st, w, n_sub, channel, drives, probes, a0, b0, loads, ideal, opts, seen=None, **more):
+    """run() of tests/test_ideal_loads_gpu.py with the opt-in — plus what every resident case asserts of its batch.
+    seen (a dict): receives the batch's n_fused_launches after the series."""
     got = st.copy()
     with HeatBatch(md, **dict(opts, **RES)) as b:
         assert b.ideal_resident == 1, "the batch is not eligible"
@@ -110,6 +111,8 @@ def run_resident(md, st, w, n_sub, channel, drives, probes, a0, b0, loads, ideal
         out = b.march_series(w, n_sub, loads=loads, ideal=ideal, **dict(series_kwargs(channel, drives, probes, a0, b0), **more))
         b.download_state(got)
         assert b.n_fused_launches > 0, "the ideal series was streamed"
+        if seen is not None:
+            seen["n_fused_launches"] = b.n_fused_launches
     assert out["failed_step"] == -1
     return out, got, (fused_surfaces, n_surfaces)
 
