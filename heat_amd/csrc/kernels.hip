@@ -96,8 +96,10 @@ __device__ __forceinline__ double shfl_f64(double v, int src_lane) { return __sh
 template <int CTRL>
 __device__ __forceinline__ double dpp_rotate_f64(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
-    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    // (a rotate has a source in every lane: no `old` value is ever seen, and naming one — a zero — costs a v_mov_b32
+    // into the destination in front of every DPP move)
+    lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+    hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
     return __hiloint2double(hi, lo);
 }
 // Sum over the wavefront with DPP (row shifts inside the rows of 16 lanes, then the two row broadcasts): the
@@ -106,6 +108,13 @@ __device__ __forceinline__ double dpp_rotate_f64(double v) {
 template <int CTRL, int ROW_MASK>
 __device__ __forceinline__ double dpp_add_f64(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
+    if constexpr (ROW_MASK == 0xf) {
+        // (every row written: bound_ctrl delivers the zero of a lane without a source or switched off, `old` is dead —
+        // the row broadcasts below write two rows of four and need their zero in the others)
+        lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+        hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+        return v + __hiloint2double(hi, lo);
+    }
     lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
     hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
     return v + __hiloint2double(hi, lo);
@@ -1470,13 +1479,21 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
     double my_air, my_rad, my_forced;
     bool my_useF;
     prepare(c, dy, my_back, sidx, my_lz, zt_mine, my_air, my_rad, my_forced, my_useF);
+    // Walls of two lanes or more (!kSingleLane): is_first means front and is_last means back, so the RK4's effective
+    // terms are selected straight from h_ / q_ below, not filed under hF / qF / hB / qB and selected again.
+    constexpr bool kFileOnce = !kSingleLane;
+    double h_ = 0.0, q_ = 0.0;
     if (is_first || is_last) {
-        double h_, q_;
         add_face(c, dy, my_back, my_air, my_rad, my_forced, sidx, my_useF, h_, q_);
-        hF = my_back ? 0.0 : h_;
-        qF = my_back ? 0.0 : q_;
-        hB = my_back ? h_ : 0.0;
-        qB = my_back ? q_ : 0.0;
+        if constexpr (kFileOnce) {  // (read under is_first / is_last only, in the RK4's block)
+            hF = h_; qF = q_;
+            hB = h_; qB = q_;
+        } else {
+            hF = my_back ? 0.0 : h_;
+            qF = my_back ? 0.0 : q_;
+            hB = my_back ? h_ : 0.0;
+            qB = my_back ? q_ : 0.0;
+        }
     }
     double b_air = 0.0, b_forced = 0.0, b_cos = 0.0, b_neg = 0.0;
     bool b_useF = false;
