@@ -207,6 +207,17 @@ class AirHandlers(C.Structure):
                 ("steps_heat_saturated", _i64p), ("steps_cool_saturated", _i64p), ("sum_branch_q", _dp)]
 
 
+class AirSpecies(C.Structure):
+    """heat_air_species (include/heat_amd.h): concentrations per species and zone carried by the air a series moves, their
+    sources and statistics, and demand vents whose volume flow follows a concentration"""
+    _fields_ = [("n_species", C.c_int64), ("outdoor_chan", _i32p), ("n_sources", C.c_int64), ("src_zone", _i32p), ("src_species", _i32p),
+                ("src_chan", _i32p), ("src_factor", _dp), ("n_vents", C.c_int64), ("vent_zone", _i32p), ("vent_species", _i32p),
+                ("vent_temp_chan", _i32p), ("vent_enable_chan", _i32p), ("vent_v_min", _dp), ("vent_v_max", _dp), ("vent_c_lo", _dp),
+                ("vent_c_hi", _dp), ("limit_chan", _i32p), ("occ_chan", _i32p), ("resume", C.c_int64), ("step_base", C.c_int64),
+                ("conc", _dp), ("n_occupied", _i64p), ("sum_conc", _dp), ("max_conc", _dp), ("step_max", _i64p), ("n_above", _i64p),
+                ("excess_above", _dp), ("sum_volume", _dp), ("sum_q", _dp), ("steps_saturated", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -288,6 +299,10 @@ SYMBOLS = [
     ("heat_air_handlers_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(AirHandlers)]),
     ("heat_batch_march_series_handlers", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
                                                    _dp, _dp, _dp, _dp]),
+    ("heat_air_species_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(ZoneLoads), C.POINTER(AirPaths),
+                                         C.POINTER(AirHandlers), C.POINTER(AirSpecies)]),
+    ("heat_batch_march_series_species", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
+                                                  _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -444,6 +459,7 @@ HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
                      "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check", "heat_air_handlers_check",
+                     "heat_air_species_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1521,6 +1537,104 @@ def air_handlers_check(md, handlers, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+SPECIES_STATS = ("n_occupied", "sum_conc", "max_conc", "step_max", "n_above", "excess_above", "sum_volume", "sum_q", "steps_saturated")
+_SPECIES_VENT_STATS = ("sum_volume", "sum_q", "steps_saturated")
+_SPECIES_INT = ("n_occupied", "step_max", "n_above", "steps_saturated")
+_SPECIES_SOURCE = (("src_zone", np.int32, True), ("src_species", np.int32, True), ("src_chan", np.int32, True), ("src_factor", np.float64, False))
+_SPECIES_VENT = (("vent_zone", np.int32, True), ("vent_species", np.int32, True), ("vent_temp_chan", np.int32, True),
+                 ("vent_enable_chan", np.int32, False), ("vent_v_min", np.float64, True), ("vent_v_max", np.float64, True),
+                 ("vent_c_lo", np.float64, True), ("vent_c_hi", np.float64, True))
+
+
+def make_air_species(outdoor_chan=None, conc=None, src_zone=(), src_species=(), src_chan=(), src_factor=None, vent_zone=(), vent_species=(),
+                     vent_temp_chan=(), vent_enable_chan=None, vent_v_min=(), vent_v_max=(), vent_c_lo=(), vent_c_hi=(), limit_chan=None,
+                     occ_chan=None, stats=SPECIES_STATS, resume=None, step_base=0):
+    """Builds a heat_air_species. Returns (species, keepalive); the march updates keepalive["conc"] and the accumulators in place.
+    outdoor_chan     [n_species, n_zones] the channel of the concentration of the OUTSIDE air entering a zone, -1: 0.0
+                     (air_species.per_zone broadcasts one channel per species); None: no species
+    conc             [n_species, n_zones] the concentrations the series starts with (copied); None: zeros
+    src_zone, src_species, src_chan, src_factor   [n_sources] amount per second = factor (None: 1) * the channel's value
+    vent_zone, vent_species, vent_temp_chan, vent_enable_chan, vent_v_min, vent_v_max, vent_c_lo, vent_c_hi   [n_vents] the demand
+                     vents: the zone, the species whose concentration in that zone drives it, the channel of the outdoor-air
+                     temperature, the enable channel (None / -1: always), m3/s at and below c_lo, m3/s at and above c_hi
+    limit_chan       [n_species] the channel of the limit n_above / excess_above count against, None / -1: none
+    occ_chan         [n_zones] occupied where row[chan] > 0, None / -1: always
+    stats            names out of SPECIES_STATS: which accumulators are maintained (default: all)
+    resume           a dict of arrays a previous series returned: the accumulators start from them
+    step_base        the number the first step of this series has in step_max
+    (air_species.apply and accumulate are the rule in numpy and take the same dict)"""
+    given = dict(src_zone=src_zone, src_species=src_species, src_chan=src_chan, src_factor=src_factor, vent_zone=vent_zone,
+                 vent_species=vent_species, vent_temp_chan=vent_temp_chan, vent_enable_chan=vent_enable_chan, vent_v_min=vent_v_min,
+                 vent_v_max=vent_v_max, vent_c_lo=vent_c_lo, vent_c_hi=vent_c_hi)
+    unknown = set(stats or ()) - set(SPECIES_STATS)
+    if unknown:
+        raise ValueError("air species: unknown stats %s (known: %s)" % (sorted(unknown), ", ".join(SPECIES_STATS)))
+    sp = AirSpecies()
+    keep = {}
+    oc = np.zeros((0, 0), np.int32) if outdoor_chan is None else np.ascontiguousarray(outdoor_chan, dtype=np.int32)
+    if oc.ndim != 2:
+        raise ValueError("air species outdoor_chan: shape %s is not [n_species, n_zones]" % (oc.shape,))
+    ns, nz = oc.shape
+    nq = len(np.asarray(src_zone if src_zone is not None else ()).reshape(-1))
+    nv = len(np.asarray(vent_zone if vent_zone is not None else ()).reshape(-1))
+    sp.n_species, sp.n_sources, sp.n_vents, sp.resume, sp.step_base = ns, nq, nv, 0 if resume is None else 1, int(step_base)
+    keep["outdoor_chan"] = oc
+    sp.outdoor_chan = oc.ctypes.data_as(_i32p) if oc.size else None
+    c = np.zeros((ns, nz)) if conc is None else np.array(conc, dtype=np.float64)  # (a copy: the march writes it)
+    if c.shape != (ns, nz):
+        raise ValueError("air species conc: %s for %d species in %d zones" % (c.shape, ns, nz))
+    keep["conc"] = c
+    sp.conc = c.ctypes.data_as(_dp) if c.size else None
+    for rows, count, what in ((_SPECIES_SOURCE, nq, "sources"), (_SPECIES_VENT, nv, "vents")):
+        for name, dtype, needed in rows:
+            if given[name] is None and not needed:
+                continue
+            v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+            if v.shape != (count,):
+                raise ValueError("air species %s: %s for %d %s" % (name, v.shape, count, what))
+            keep[name] = v
+            setattr(sp, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if count else None)
+    for name, v, count in (("limit_chan", limit_chan, ns), ("occ_chan", occ_chan, nz)):
+        if v is None:
+            continue
+        v = np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
+        if v.shape != (count,):
+            raise ValueError("air species %s: %s for %d" % (name, v.shape, count))
+        keep[name] = v
+        setattr(sp, name, v.ctypes.data_as(_i32p) if count else None)
+    for name in (stats or ()):
+        dtype = np.int64 if name in _SPECIES_INT else np.float64
+        shape = (nv,) if name in _SPECIES_VENT_STATS else (ns, nz)
+        if resume is not None:
+            if name not in resume:
+                raise ValueError("air species resume: %s is missing" % name)
+            a = np.array(resume[name], dtype=dtype)  # (a copy: the march writes it)
+            if a.shape != shape:
+                raise ValueError("air species resume: %s of shape %s, not %s" % (name, a.shape, shape))
+        else:
+            a = np.zeros(shape, dtype)  # (the library initialises on the device)
+        keep[name] = a
+        setattr(sp, name, a.ctypes.data_as(_i64p if dtype == np.int64 else _dp) if a.size else None)
+    return sp, keep
+
+
+def air_species_check(md, species, loads=None, air=None, handlers=None, lib=None, **series):
+    """heat_air_species_check: everything about the air species of a series that needs no device (series arguments as
+    HeatBatch.march_series; species: the arguments of make_air_species, or None; loads, air, handlers: the terms whose air the
+    species ride on, checked as their own checks do). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    l, lkeep = make_zone_loads(**loads) if loads is not None else (None, None)
+    a, akeep = make_air_paths(**air) if air is not None else (None, None)
+    h, hkeep = make_air_handlers(**handlers) if handlers is not None else (None, None)
+    sp, spkeep = make_air_species(**species) if species is not None else (None, None)
+    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+    rc = L.heat_air_species_check(C.byref(desc), C.byref(s), ref(l), ref(a), ref(h), ref(sp))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1645,7 +1759,8 @@ class HeatBatch:
     def march_series(self, weather, n_sub, loads=None, report=None, trace=True, applied=True, ideal=None, sky=None, gains=None,
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
                      blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True,
-                     handlers=None, supply_t=True, recovered=True, coil_q=True, branch_q=True, **series):
+                     handlers=None, supply_t=True, recovered=True, coil_q=True, branch_q=True, species=None, conc_rows=True,
+                     vent_v=True, vent_q=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1710,7 +1825,14 @@ class HeatBatch:
         air temperatures it holds. Returns what the same call without handlers returns plus one dict: supply_t, recovered,
         coil_q [n_steps, n_units] and branch_q [n_steps, n_branches] (each empty with its flag False), bypass, and of
         HANDLER_STATS those in stats (pass bypass and them on to the next series) — one more element of the tuple, or the key
-        "handlers" of the dict."""
+        "handlers" of the dict.
+        species (a dict of make_air_species' arguments; an empty dict: no species): heat_batch_march_series_species —
+        concentrations per species and zone carried by every flow of air of the series (the loads' flows, the open air paths,
+        the handlers' supply branches) and demand vents whose volume flow follows a concentration, stepped on the device.
+        Returns what the same call without species returns plus one dict, appended last: conc_rows [n_steps, n_species,
+        n_zones], vent_v, vent_q [n_steps, n_vents] (each empty with its flag False), conc (the concentrations after the last
+        step) and of SPECIES_STATS those in stats (pass conc on, and the stats as species["resume"] with step_base, to the
+        next series) — one more element of the tuple, or the key "species" of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -1722,8 +1844,9 @@ class HeatBatch:
                                                                       irradiance=irradiance, ambient_t=ambient_t, position=position,
                                                                       blind_incident=blind_incident, operative=operative, mrt=mrt,
                                                                       supply_t=supply_t, recovered=recovered, coil_q=coil_q,
-                                                                      branch_q=branch_q),
-                                  aniso=aniso, comfort=comfort, handlers=handlers)
+                                                                      branch_q=branch_q, conc_rows=conc_rows, vent_v=vent_v,
+                                                                      vent_q=vent_q),
+                                  aniso=aniso, comfort=comfort, handlers=handlers, species=species)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -1749,10 +1872,11 @@ class HeatBatch:
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
-    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None):
+    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None, species=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
         whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None; comfort: the dict of make_comfort's
-        arguments or None; handlers: the dict of make_air_handlers' arguments or None."""
+        arguments or None; handlers: the dict of make_air_handlers' arguments or None; species: the dict of make_air_species'
+        arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1804,7 +1928,7 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        if aniso is not None or comfort is not None or handlers is not None:
+        if aniso is not None or comfort is not None or handlers is not None or species is not None:
             # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
             # that are recorded, and the anisotropic sky.
             call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
@@ -1826,10 +1950,24 @@ class HeatBatch:
                 cf, ckeep = make_comfort(**comfort)
                 top_rows = np.zeros((s.n_steps if want["operative"] else 0, cf.n_sensors))
                 mrt_rows = np.zeros((s.n_steps if want["mrt"] else 0, cf.n_sensors))
+            ah = None
             if handlers is not None:
                 ah, hkeep = make_air_handlers(**handlers)
                 hrows = {k: np.zeros((s.n_steps if want[k] else 0, ah.n_branches if k == "branch_q" else ah.n_units))
                          for k in ("supply_t", "recovered", "coil_q", "branch_q")}
+            if species is not None:
+                sp, spkeep = make_air_species(**species)
+                if sp.n_species and spkeep["outdoor_chan"].shape[1] != self.n_zones:
+                    raise ValueError("air species outdoor_chan: %d zones, the batch has %d" % (spkeep["outdoor_chan"].shape[1], self.n_zones))
+                sprows = dict(conc_rows=np.zeros((s.n_steps if want["conc_rows"] else 0, sp.n_species, self.n_zones if sp.n_species else 0)),
+                              vent_v=np.zeros((s.n_steps if want["vent_v"] else 0, sp.n_vents)),
+                              vent_q=np.zeros((s.n_steps if want["vent_q"] else 0, sp.n_vents)))
+                hp = [ptr(hrows[k]) for k in ("supply_t", "recovered", "coil_q", "branch_q")] if ah is not None else [None] * 4
+                rc = self._L.heat_batch_march_series_species(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
+                                                             ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
+                                                             C.byref(ah) if ah is not None else None, *hp, C.byref(sp), ptr(sprows["conc_rows"]),
+                                                             ptr(sprows["vent_v"]), ptr(sprows["vent_q"]))
+            elif handlers is not None:
                 rc = self._L.heat_batch_march_series_handlers(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
                                                               ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
                                                               C.byref(ah), ptr(hrows["supply_t"]), ptr(hrows["recovered"]), ptr(hrows["coil_q"]),
@@ -1870,6 +2008,8 @@ class HeatBatch:
             out += [("comfort", dict(operative=top_rows, mrt=mrt_rows, **{k: ckeep[k] for k in COMFORT_STATS if k in ckeep}))]
         if handlers is not None:
             out += [("handlers", dict(hrows, **{k: hkeep[k] for k in ("bypass",) + HANDLER_STATS if k in hkeep}))]
+        if species is not None:
+            out += [("species", dict(sprows, **{k: spkeep[k] for k in ("conc",) + SPECIES_STATS if k in spkeep}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

@@ -80,11 +80,11 @@ inline StepWeather to_step_weather(const heat_weather &w) {
 using namespace heat;  // (heat_batch is the C ABI's type, so it stands outside the namespace its members' types come from)
 
 // The batch. What the series driver (series.hip) may touch of it — a term that needs another field adds it to this list:
-//   reads   sizes and layout: n_surf, n_zones, n_sites, n_ranks, weather_cap, sl, direct_runs; the host tables h_orig_of,
+//   reads   sizes and layout: n_surf, n_zones, n_sites, n_ranks, weather_cap, sl, direct_runs, dt; the host tables h_orig_of,
 //           h_dev_of, h_kind, h_site, h_node_tile_base, h_node_geom, h_node_count, h_first_slot, h_out_slots, h_zone_slot_h;
 //           the thread pool `pool`; the stream `stream`
 //   hands to its kernels (the device buffers, never resized or freed by the driver): d_T, d_state, d_zone_T, d_zone_a0,
-//           d_zone_b0, d_side_const, d_side_alpha, d_side_dyn, d_side_out, d_site, d_weather, d_step, d_flags
+//           d_zone_b0, d_zone_vol, d_side_const, d_side_alpha, d_side_dyn, d_side_out, d_site, d_weather, d_step, d_flags
 //   writes  resolver (made by the first series, kept), n_weather (the sub-timesteps of the step, as heat_batch_set_weather does)
 // Everything else — tiles, workgroup lists, teams, graphs, timing, the collective — is the engine's alone.
 struct heat_batch {

@@ -3505,6 +3505,163 @@ k_series_handler_supply(int n_zones, HandlersDev h, const double *__restrict__ z
     if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
 }
 
+// k_series_vents — the demand vents of one step (heat_air_species, include/heat_amd.h), behind k_series_handler_supply and
+// before k_series_species: one lane per ZONE walks its vents (a CSR range of the vents sorted by zone, the caller's order kept
+// inside a zone), forms each one's volume flow from the concentration of the vent's species in this zone as the step starts
+// with it — `conc` is not written in a step — and adds the enabled ones to the a0 / b0 of its own zone alone, behind what the
+// loads, the paths and the handlers added; a zone without a vent leaves after reading its offsets. The header's rule, every
+// line one rounded operation in the order written, the air properties written out as in k_series_zone_loads (same
+// expressions, same grouping), hence no contraction; a NaN makes every comparison false. V goes to the call's scratch for
+// k_series_species (the caller's order, through `orig`). A vent belongs to the lane of its zone: its elements of the two rows
+// and of the three accumulators have one writer. Which outputs exist is decided by nullable pointers in the kernel argument:
+// wave-uniform branches, an array nobody takes is neither read nor written. A NaN a0 / b0 is reported as the zone's failure,
+// as the air paths report it. No atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_vents(int n_zones, SpeciesDev sp, const double *__restrict__ row, const double *__restrict__ zone_T,
+               const double *__restrict__ conc, double *__restrict__ a0, double *__restrict__ b0, double *__restrict__ v_row,
+               double *__restrict__ q_row, int *__restrict__ flags) {
+#pragma clang fp contract(off)
+    const int z = blockIdx.x * blockDim.x + threadIdx.x;
+    if (z >= n_zones) return;
+    const int p0 = sp.vent_off[z], p1 = sp.vent_off[z + 1];
+    if (p0 == p1) return;
+    double a = a0[z], b = b0[z];
+    const bool clean = a == a && b == b;
+    const double tz = zone_T[z];
+    for (int i = p0; i < p1; i++) {
+        const int orig = sp.v_orig[i], ec = sp.v_enable_chan[i];
+        const double c = conc[(size_t)sp.v_species[i] * (size_t)n_zones + (size_t)z];
+        const double lo = sp.c_lo[i], vmin = sp.v_min[i];
+        const double x = c - lo;
+        const double span = sp.c_hi[i] - lo;
+        double f = x / span;
+        if (f < 0.0) f = 0.0;
+        if (f > 1.0) f = 1.0;
+        bool saturated = f == 1.0;
+        const double dv = sp.v_max[i] - vmin;
+        const double y = f * dv;
+        double V = vmin + y, q = 0.0;
+        if (ec >= 0 && !(row[ec] > 0.0)) {
+            V = 0.0;
+            saturated = false;
+        } else {
+            const double t_in = row[sp.v_temp_chan[i]];
+            const double tk = t_in + 273.15;
+            const double rho = 101325. * 28.97 / (8314.46261815324 * tk);  // gas.rs:175-179
+            const double cp = 1002.7370 + 1.2324e-2 * tk;                  // gas.rs:49,165-167
+            const double m = (rho * V) * cp;
+            const double mt = m * t_in;
+            a = a + mt;
+            b = b + m;
+            const double dt = t_in - tz;
+            q = m * dt;
+        }
+        sp.vent_V[orig] = V;
+        if (v_row != nullptr) v_row[orig] = V;
+        if (q_row != nullptr) q_row[orig] = q;
+        if (sp.sum_volume != nullptr) sp.sum_volume[orig] = sp.sum_volume[orig] + V;
+        if (sp.sum_q != nullptr) sp.sum_q[orig] = sp.sum_q[orig] + q;
+        if (sp.steps_saturated != nullptr && saturated) sp.steps_saturated[orig] += 1;
+    }
+    a0[z] = a;
+    b0[z] = b;
+    if (clean && (a != a || b != b)) report_failure(flags, FLAG_NAN_ZONE, (unsigned int)z);
+}
+
+// What a lane of k_series_species reads of the other terms' tables: the zone loads' flows (ZoneLoadsDev), the air paths
+// (AirPathsDev) and the handlers' supply branches by zone (HandlersDev) — the pointers of those views, nullptr offsets where
+// the term is absent.
+struct SpeciesInflows {
+    const int32_t *fl_off, *fl_chan;               // [n_zones + 1], [n_flows] by zone
+    const double *fl_gain;
+    const int32_t *ap_off, *ap_source, *ap_chan, *ap_open_chan, *ap_orig;   // [n_zones + 1], [n_paths] by target
+    const double *ap_gain;
+    const uint8_t *ap_state;                       // [n_paths], the caller's order
+    const int32_t *br_off, *br_orig;               // [n_zones + 1], [n_supply] by zone
+};
+
+// k_series_species — the concentrations of one step (heat_air_species, include/heat_amd.h), behind k_series_vents: one lane
+// per (SPECIES, ZONE), lane = s * n_zones + z, so a wavefront reads neighbouring zones of one species: conc, the volumes, the
+// offsets and the rows are plain coalesced loads. A lane sums its sources (a CSR range of the sources sorted by lane) and then
+// every inflow into its zone in the header's order — the loads' flows, the air paths that are open behind this step's
+// k_series_air_paths (the state bytes it has just written), the handlers' supply branches, the vents' V of this step's scratch
+// — each a sequential chain in the caller's order, read through the tables those terms uploaded for their own kernels. A path
+// from another zone gathers that zone's concentration out of `conc`, which no lane writes: every neighbour is the start of
+// the step's, whatever the order of the lanes; the new value goes to conc_next, and the driver swaps the two between the
+// steps. The header's rule, every line one rounded operation in the order written, hence no contraction; a NaN makes every
+// comparison false. A lane's elements of the row and of the six accumulators have one writer. No atomics, no LDS.
+__global__ void __launch_bounds__(256)
+k_series_species(int n_zones, SpeciesDev sp, SpeciesInflows in, const double *__restrict__ row, const double *__restrict__ zone_vol,
+                 double h, const double *__restrict__ conc, double *__restrict__ conc_next, double *__restrict__ conc_row, int64_t step) {
+#pragma clang fp contract(off)
+    const int lane = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lane >= sp.n_species * n_zones) return;
+    const int s = lane / n_zones, z = lane - s * n_zones;
+    const double *const cs = conc + (size_t)s * (size_t)n_zones;
+    const double c = cs[z], vol = zone_vol[z];
+    const int oc = sp.outdoor_chan[lane];
+    const double co = oc >= 0 ? row[oc] : 0.0;
+    double S = 0.0, F = 0.0, G = 0.0;
+    for (int i = sp.src_off[lane], i1 = sp.src_off[lane + 1]; i < i1; i++) {
+        const double x = sp.src_factor[i] * row[sp.src_chan[i]];
+        S = S + x;
+    }
+    if (in.fl_off != nullptr)
+        for (int i = in.fl_off[z], i1 = in.fl_off[z + 1]; i < i1; i++) {
+            const double V = in.fl_gain[i] * row[in.fl_chan[i]];
+            const double g = V * co;
+            F = F + V;
+            G = G + g;
+        }
+    if (in.ap_off != nullptr)
+        for (int i = in.ap_off[z], i1 = in.ap_off[z + 1]; i < i1; i++) {
+            if (in.ap_open_chan[i] >= 0 && in.ap_state[in.ap_orig[i]] != 1) continue;
+            const int src = in.ap_source[i];
+            const double ci = src >= 0 ? cs[src] : co;
+            const double V = in.ap_gain[i] * row[in.ap_chan[i]];
+            const double g = V * ci;
+            F = F + V;
+            G = G + g;
+        }
+    if (in.br_off != nullptr)
+        for (int i = in.br_off[z], i1 = in.br_off[z + 1]; i < i1; i++) {
+            const int orig = in.br_orig[i];
+            const double V = sp.br_gain[orig] * row[sp.br_chan[orig]];
+            const double g = V * co;
+            F = F + V;
+            G = G + g;
+        }
+    if (sp.vent_off != nullptr)
+        for (int i = sp.vent_off[z], i1 = sp.vent_off[z + 1]; i < i1; i++) {
+            const double V = sp.vent_V[sp.v_orig[i]];
+            const double g = V * co;
+            F = F + V;
+            G = G + g;
+        }
+    const double p = S + G;
+    const double hp = h * p;
+    const double vc = vol * c;
+    const double num = vc + hp;
+    const double hF = h * F;
+    const double den = vol + hF;
+    conc_next[lane] = num / den;
+    if (conc_row != nullptr) conc_row[lane] = c;
+    const int occ = sp.occ_chan[z];
+    if (occ >= 0 && !(row[occ] > 0.0)) return;
+    if (sp.n_occupied != nullptr) sp.n_occupied[lane] += 1;
+    if (sp.sum_conc != nullptr) sp.sum_conc[lane] = sp.sum_conc[lane] + c;
+    if (sp.max_conc != nullptr && c > sp.max_conc[lane]) {
+        sp.max_conc[lane] = c;
+        if (sp.step_max != nullptr) sp.step_max[lane] = step;
+    }
+    const int lc = sp.limit_chan[s];
+    if (lc < 0) return;
+    const double limit = row[lc];
+    if (!(c > limit)) return;
+    if (sp.n_above != nullptr) sp.n_above[lane] += 1;
+    if (sp.excess_above != nullptr) sp.excess_above[lane] = sp.excess_above[lane] + (c - limit);
+}
+
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = value;
@@ -3998,6 +4155,28 @@ void launch_series_handler_supply(int n_zones, const HandlersDev &h, const doubl
                                   int *flags, hipStream_t st) {
     if (n_zones <= 0 || h.n_units <= 0) return;
     hipLaunchKernelGGL(k_series_handler_supply, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, h, zone_T, a0, b0, branch_row, flags);
+}
+
+void launch_series_vents(int n_zones, const SpeciesDev &sp, const double *row, const double *zone_T, const double *conc, double *a0,
+                         double *b0, double *v_row, double *q_row, int *flags, hipStream_t st) {
+    if (n_zones <= 0 || sp.n_vents <= 0) return;
+    hipLaunchKernelGGL(k_series_vents, dim3((n_zones + 255) / 256), dim3(256), 0, st, n_zones, sp, row, zone_T, conc, a0, b0, v_row, q_row,
+                       flags);
+}
+
+void launch_series_species(int n_zones, const SpeciesDev &sp, const ZoneLoadsDev *zl, const AirPathsDev *ap, const HandlersDev *hd,
+                           const double *row, const double *zone_vol, double h, const double *conc, double *conc_next, double *conc_row,
+                           int64_t step, hipStream_t st) {
+    const int64_t lanes = (int64_t)sp.n_species * n_zones;
+    if (lanes <= 0) return;
+    SpeciesInflows in{};
+    if (zl) in.fl_off = zl->off + (n_zones + 1), in.fl_chan = zl->flow_volume_chan, in.fl_gain = zl->flow_volume_gain;
+    if (ap)
+        in.ap_off = ap->off, in.ap_source = ap->source, in.ap_chan = ap->volume_chan, in.ap_open_chan = ap->open_chan, in.ap_orig = ap->orig,
+        in.ap_gain = ap->volume_gain, in.ap_state = ap->state;
+    if (hd) in.br_off = hd->zone_off, in.br_orig = hd->z_orig;
+    hipLaunchKernelGGL(k_series_species, dim3((unsigned int)((lanes + 255) / 256)), dim3(256), 0, st, n_zones, sp, in, row, zone_vol, h, conc,
+                       conc_next, conc_row, step);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

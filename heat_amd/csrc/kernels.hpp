@@ -334,6 +334,41 @@ void launch_series_handler_units(const HandlersDev &h, const double *row, const 
 // flags: the batch's failure flags (a branch that makes a zone's a0 / b0 NaN is reported as that zone's failure)
 void launch_series_handler_supply(int n_zones, const HandlersDev &h, const double *zone_T, double *a0, double *b0, double *branch_row,
                                   int *flags, hipStream_t st);
+// Air species of a series step (heat_air_species, include/heat_amd.h; tables: plan.hpp, SpeciesTables): launched behind
+// launch_series_handler_supply and before launch_series_ambient, only when there are species. launch_series_vents — one lane
+// per zone, only when there are vents — forms the volume flow of each of the zone's demand vents from the concentrations the
+// step starts with, adds the enabled ones to the zone's a0 / b0, stores V into the call's scratch and updates the vent's rows
+// and accumulators. launch_series_species — one lane per (species, zone), behind it — sums the sources and every inflow of
+// the step (the loads' flows, the open air paths, the handlers' supply branches and the vents, read through those terms' own
+// views), steps the concentration into conc_next and updates the lane's row and accumulators. conc is never written in a
+// step: no lane sees another's new value; the driver swaps the two buffers between the steps.
+struct SpeciesDev {
+    int n_species, n_vents;
+    const int32_t *outdoor_chan;                   // [n_species][n_zones]; -1: 0.0
+    const int32_t *src_off, *src_chan;             // [n_species * n_zones + 1], [n_sources] by lane
+    const double *src_factor;
+    const int32_t *vent_off;                       // [n_zones + 1]; nullptr: no vent
+    const int32_t *v_species, *v_temp_chan, *v_enable_chan, *v_orig;   // [n_vents] by zone
+    const double *v_min, *v_max, *c_lo, *c_hi;
+    const int32_t *limit_chan, *occ_chan;          // [n_species], [n_zones]; -1: none
+    const int32_t *br_chan;                        // [n_branches] of the handlers, the caller's order; nullptr: none
+    const double *br_gain;
+    double *vent_V;                                // [n_vents], the caller's order: the step's scratch
+    int64_t *n_occupied, *step_max, *n_above;      // [n_species][n_zones] each, nullptr: not maintained
+    double *sum_conc, *max_conc, *excess_above;
+    double *sum_volume, *sum_q;                    // [n_vents], the caller's order; nullptr: not maintained
+    int64_t *steps_saturated;
+};
+// row: the step's row of the channel table; conc: the concentrations at the start of the step; v_row / q_row: the step's rows
+// of vent_v / vent_q (caller's order), or nullptr; flags: the batch's failure flags (a vent that makes a zone's a0 / b0 NaN is
+// reported as that zone's failure)
+void launch_series_vents(int n_zones, const SpeciesDev &sp, const double *row, const double *zone_T, const double *conc, double *a0,
+                         double *b0, double *v_row, double *q_row, int *flags, hipStream_t st);
+// zl / ap / hd: the views of the step's zone loads, air paths and handlers, or nullptr each (the term is absent); h: n_sub * dt;
+// conc_row: the step's row of conc_rows, or nullptr; step: K
+void launch_series_species(int n_zones, const SpeciesDev &sp, const ZoneLoadsDev *zl, const AirPathsDev *ap, const HandlersDev *hd,
+                           const double *row, const double *zone_vol, double h, const double *conc, double *conc_next, double *conc_row,
+                           int64_t step, hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Per step: launch_series_ideal_begin (behind the zone loads)

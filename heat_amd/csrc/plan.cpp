@@ -2161,6 +2161,176 @@ const char *ideal_resident_reason_text(int reason) {
     }
 }
 
+// ---- air species of a series (include/heat_amd.h, heat_air_species) ----
+int check_air_species(int64_t n_zones, int32_t n_channels, const heat_air_species *sp, std::string &err) {
+    if (!sp) return HEAT_OK;
+    const int64_t NS = sp->n_species, NQ = sp->n_sources, NV = sp->n_vents, Z = n_zones;
+    const int NC = n_channels;
+    if (NS < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of air species (n_species %lld): no air species s", (long long)NS);
+    if (NQ < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of species sources (n_sources %lld): no species source i", (long long)NQ);
+    if (NV < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of demand vents (n_vents %lld): no demand vent j", (long long)NV);
+    // (the tables number lanes, sources and vents with 32 bits)
+    if (NS > INT32_MAX || NQ > INT32_MAX || NV > INT32_MAX || (Z > 0 && NS > INT32_MAX / Z))
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 lanes of air species s, species sources i or demand vents j (n_species %lld x %lld zones, n_sources %lld, n_vents %lld)",
+                     (long long)NS, (long long)Z, (long long)NQ, (long long)NV);
+    if (NS == 0 && NQ > 0) return failp(err, HEAT_E_INVALID_ARG, "species source 0: %lld sources, but no air species s (n_species 0)", (long long)NQ);
+    if (NS == 0 && NV > 0) return failp(err, HEAT_E_INVALID_ARG, "demand vent 0: %lld vents, but no air species s (n_species 0)", (long long)NV);
+    if (NS == 0) return HEAT_OK;
+    if (Z > 0 && !sp->outdoor_chan) return failp(err, HEAT_E_INVALID_ARG, "air species 0: outdoor_chan is NULL (n_species %lld)", (long long)NS);
+    if (Z > 0 && !sp->conc) return failp(err, HEAT_E_INVALID_ARG, "air species 0: conc is NULL (n_species %lld)", (long long)NS);
+    for (int64_t s = 0; s < NS; s++) {
+        for (int64_t z = 0; z < Z; z++) {
+            const int32_t oc = sp->outdoor_chan[s * Z + z];
+            if (oc < -1 || oc >= NC)
+                return failp(err, HEAT_E_SIZE, "air species %lld: outdoor channel %d of zone %lld outside [-1, %d)", (long long)s, oc, (long long)z, NC);
+        }
+        const int32_t lc = sp->limit_chan ? sp->limit_chan[s] : -1;
+        if (lc < -1 || lc >= NC) return failp(err, HEAT_E_SIZE, "air species %lld: limit channel %d outside [-1, %d)", (long long)s, lc, NC);
+    }
+    for (int64_t z = 0; sp->occ_chan && z < Z; z++)
+        if (sp->occ_chan[z] < -1 || sp->occ_chan[z] >= NC)
+            return failp(err, HEAT_E_SIZE, "air species 0: occupancy channel %d of zone %lld outside [-1, %d)", sp->occ_chan[z], (long long)z, NC);
+    if (NQ > 0 && (!sp->src_zone || !sp->src_species || !sp->src_chan))
+        return failp(err, HEAT_E_INVALID_ARG, "species source 0: %s is NULL (n_sources %lld)",
+                     !sp->src_zone ? "src_zone" : (!sp->src_species ? "src_species" : "src_chan"), (long long)NQ);
+    for (int64_t i = 0; i < NQ; i++) {
+        const int32_t z = sp->src_zone[i], s = sp->src_species[i], ch = sp->src_chan[i];
+        if (z < 0 || z >= Z) return failp(err, HEAT_E_SIZE, "species source %lld: zone %d outside [0, %lld)", (long long)i, z, (long long)Z);
+        if (s < 0 || s >= NS) return failp(err, HEAT_E_SIZE, "species source %lld: species %d outside [0, %lld)", (long long)i, s, (long long)NS);
+        if (ch < 0 || ch >= NC) return failp(err, HEAT_E_SIZE, "species source %lld: channel %d outside [0, %d)", (long long)i, ch, NC);
+        if (sp->src_factor && !std::isfinite(sp->src_factor[i]))
+            return failp(err, HEAT_E_INVALID_ARG, "species source %lld: src_factor %g is not finite", (long long)i, sp->src_factor[i]);
+    }
+    if (NV == 0) return HEAT_OK;
+    const void *const need[7] = {sp->vent_zone, sp->vent_species, sp->vent_temp_chan, sp->vent_v_min, sp->vent_v_max, sp->vent_c_lo, sp->vent_c_hi};
+    static const char *const need_name[7] = {"vent_zone", "vent_species", "vent_temp_chan", "vent_v_min", "vent_v_max", "vent_c_lo", "vent_c_hi"};
+    for (int a = 0; a < 7; a++)
+        if (!need[a]) return failp(err, HEAT_E_INVALID_ARG, "demand vent 0: %s is NULL (n_vents %lld)", need_name[a], (long long)NV);
+    for (int64_t j = 0; j < NV; j++) {
+        const int32_t z = sp->vent_zone[j], s = sp->vent_species[j], tc = sp->vent_temp_chan[j];
+        const int32_t ec = sp->vent_enable_chan ? sp->vent_enable_chan[j] : -1;
+        if (z < 0 || z >= Z) return failp(err, HEAT_E_SIZE, "demand vent %lld: zone %d outside [0, %lld)", (long long)j, z, (long long)Z);
+        if (s < 0 || s >= NS) return failp(err, HEAT_E_SIZE, "demand vent %lld: species %d outside [0, %lld)", (long long)j, s, (long long)NS);
+        if (tc < 0 || tc >= NC) return failp(err, HEAT_E_SIZE, "demand vent %lld: temperature channel %d outside [0, %d)", (long long)j, tc, NC);
+        if (ec < -1 || ec >= NC) return failp(err, HEAT_E_SIZE, "demand vent %lld: enable channel %d outside [-1, %d)", (long long)j, ec, NC);
+        const double v[4] = {sp->vent_v_min[j], sp->vent_v_max[j], sp->vent_c_lo[j], sp->vent_c_hi[j]};
+        for (int a = 0; a < 4; a++)
+            if (!std::isfinite(v[a])) return failp(err, HEAT_E_INVALID_ARG, "demand vent %lld: %s %g is not finite", (long long)j, need_name[3 + a], v[a]);
+        if (v[0] < 0.0) return failp(err, HEAT_E_INVALID_ARG, "demand vent %lld: vent_v_min %g is negative", (long long)j, v[0]);
+        if (v[1] < v[0]) return failp(err, HEAT_E_INVALID_ARG, "demand vent %lld: vent_v_max %g is below vent_v_min %g", (long long)j, v[1], v[0]);
+        if (v[3] <= v[2]) return failp(err, HEAT_E_INVALID_ARG, "demand vent %lld: vent_c_hi %g is not above vent_c_lo %g", (long long)j, v[3], v[2]);
+    }
+    return HEAT_OK;
+}
+
+void build_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const heat_air_species *sp, SpeciesTables &t) {
+    t = SpeciesTables();
+    const size_t NS = sp ? (size_t)sp->n_species : 0, Z = (size_t)n_zones;
+    if (NS == 0) return;
+    const size_t NQ = (size_t)sp->n_sources, NV = (size_t)sp->n_vents, L = NS * Z;
+    t.outdoor_chan.assign(sp->outdoor_chan, sp->outdoor_chan + L);
+    t.limit_chan.assign(NS, -1);
+    t.occ_chan.assign(Z, -1);
+    if (sp->limit_chan) std::copy(sp->limit_chan, sp->limit_chan + NS, t.limit_chan.begin());
+    if (sp->occ_chan) std::copy(sp->occ_chan, sp->occ_chan + Z, t.occ_chan.begin());
+    // two counting sorts, stable: the caller's order survives inside a lane and inside a zone
+    t.src_off.assign(L + 1, 0);
+    t.vent_off.assign(Z + 1, 0);
+    for (size_t i = 0; i < NQ; i++) t.src_off[(size_t)sp->src_species[i] * Z + (size_t)sp->src_zone[i] + 1]++;
+    for (size_t j = 0; j < NV; j++) t.vent_off[(size_t)sp->vent_zone[j] + 1]++;
+    for (size_t l = 0; l < L; l++) t.src_off[l + 1] += t.src_off[l];
+    for (size_t z = 0; z < Z; z++) t.vent_off[z + 1] += t.vent_off[z];
+    t.src_chan.resize(NQ), t.src_factor.resize(NQ);
+    t.v_species.resize(NV), t.v_temp_chan.resize(NV), t.v_enable_chan.resize(NV), t.v_orig.resize(NV);
+    t.v_min.resize(NV), t.v_max.resize(NV), t.c_lo.resize(NV), t.c_hi.resize(NV);
+    std::vector<int32_t> next_s(t.src_off.begin(), t.src_off.end() - 1), next_v(t.vent_off.begin(), t.vent_off.end() - 1);
+    for (size_t i = 0; i < NQ; i++) {
+        const size_t p = (size_t)next_s[(size_t)sp->src_species[i] * Z + (size_t)sp->src_zone[i]]++;
+        t.src_chan[p] = sp->src_chan[i];
+        t.src_factor[p] = sp->src_factor ? sp->src_factor[i] : 1.0;
+    }
+    for (size_t j = 0; j < NV; j++) {
+        const size_t p = (size_t)next_v[(size_t)sp->vent_zone[j]]++;
+        t.v_species[p] = sp->vent_species[j];
+        t.v_temp_chan[p] = sp->vent_temp_chan[j];
+        t.v_enable_chan[p] = sp->vent_enable_chan ? sp->vent_enable_chan[j] : -1;
+        t.v_orig[p] = (int32_t)j;
+        t.v_min[p] = sp->vent_v_min[j], t.v_max[p] = sp->vent_v_max[j], t.c_lo[p] = sp->vent_c_lo[j], t.c_hi[p] = sp->vent_c_hi[j];
+    }
+    const size_t B = h && h->n_units > 0 ? (size_t)h->n_branches : 0;
+    t.br_chan.resize(B), t.br_gain.resize(B);
+    for (size_t j = 0; j < B; j++) {
+        t.br_chan[j] = h->br_volume_chan[j];
+        t.br_gain[j] = h->br_volume_gain ? h->br_volume_gain[j] : 1.0;
+    }
+}
+
+int check_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const heat_air_species *sp, const SpeciesTables &t,
+                             std::string &err) {
+    const size_t NS = sp ? (size_t)sp->n_species : 0, Z = (size_t)n_zones;
+    if (NS == 0) return HEAT_OK;
+    const size_t NQ = (size_t)sp->n_sources, NV = (size_t)sp->n_vents, L = NS * Z;
+    const size_t B = h && h->n_units > 0 ? (size_t)h->n_branches : 0;
+    if (t.outdoor_chan.size() != L || t.src_off.size() != L + 1 || t.src_chan.size() != NQ || t.src_factor.size() != NQ ||
+        t.vent_off.size() != Z + 1 || t.v_species.size() != NV || t.v_temp_chan.size() != NV || t.v_enable_chan.size() != NV ||
+        t.v_orig.size() != NV || t.v_min.size() != NV || t.v_max.size() != NV || t.c_lo.size() != NV || t.c_hi.size() != NV ||
+        t.limit_chan.size() != NS || t.occ_chan.size() != Z || t.br_chan.size() != B || t.br_gain.size() != B)
+        return failp(err, HEAT_E_SIZE, "air species tables: %zu source offsets, %zu vent offsets, %zu and %zu elements for air species s < %zu, species source i < %zu, demand vent j < %zu",
+                     t.src_off.size(), t.vent_off.size(), t.src_chan.size(), t.v_orig.size(), NS, NQ, NV);
+    if (t.src_off[0] != 0 || t.src_off[L] != (int32_t)NQ || t.vent_off[0] != 0 || t.vent_off[Z] != (int32_t)NV)
+        return failp(err, HEAT_E_SIZE, "air species tables: the offsets run from %d to %d for %zu sources and from %d to %d for %zu vents",
+                     t.src_off[0], t.src_off[L], NQ, t.vent_off[0], t.vent_off[Z], NV);
+    for (size_t l = 0; l < L; l++)
+        if (t.src_off[l + 1] < t.src_off[l] || t.src_off[l + 1] > (int32_t)NQ)
+            return failp(err, HEAT_E_SIZE, "air species tables: air species %zu, zone %zu runs from %d to %d", l / Z, l % Z, t.src_off[l], t.src_off[l + 1]);
+    for (size_t z = 0; z < Z; z++)
+        if (t.vent_off[z + 1] < t.vent_off[z] || t.vent_off[z + 1] > (int32_t)NV)
+            return failp(err, HEAT_E_SIZE, "air species tables: zone %zu runs from %d to %d", z, t.vent_off[z], t.vent_off[z + 1]);
+    // every source and vent of the caller's, in the caller's order, is the next element of its range ...
+    std::vector<int32_t> cs(t.src_off.begin(), t.src_off.end() - 1), cv(t.vent_off.begin(), t.vent_off.end() - 1);
+    for (size_t i = 0; i < NQ; i++) {
+        const size_t l = (size_t)sp->src_species[i] * Z + (size_t)sp->src_zone[i];
+        const double factor = sp->src_factor ? sp->src_factor[i] : 1.0;
+        const int32_t p = cs[l]++;
+        if (p >= t.src_off[l + 1]) return failp(err, HEAT_E_SIZE, "air species tables: species source %zu: its lane has no room for it", i);
+        if (t.src_chan[p] != sp->src_chan[i] || std::memcmp(&t.src_factor[p], &factor, sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "air species tables: species source %zu is not element %d of its lane", i, p - t.src_off[l]);
+    }
+    for (size_t j = 0; j < NV; j++) {
+        const size_t z = (size_t)sp->vent_zone[j];
+        const int32_t p = cv[z]++;
+        if (p >= t.vent_off[z + 1]) return failp(err, HEAT_E_SIZE, "air species tables: demand vent %zu: zone %zu has no room for it", j, z);
+        const double want[4] = {sp->vent_v_min[j], sp->vent_v_max[j], sp->vent_c_lo[j], sp->vent_c_hi[j]};
+        const double have[4] = {t.v_min[p], t.v_max[p], t.c_lo[p], t.c_hi[p]};
+        if (t.v_orig[p] != (int32_t)j || t.v_species[p] != sp->vent_species[j] || t.v_temp_chan[p] != sp->vent_temp_chan[j] ||
+            t.v_enable_chan[p] != (sp->vent_enable_chan ? sp->vent_enable_chan[j] : -1) || std::memcmp(want, have, sizeof want) != 0)
+            return failp(err, HEAT_E_SIZE, "air species tables: demand vent %zu is not element %d of zone %zu", j, p - t.vent_off[z], z);
+    }
+    // ... and every range is full: each is present exactly once
+    for (size_t l = 0; l < L; l++)
+        if (cs[l] != t.src_off[l + 1])
+            return failp(err, HEAT_E_SIZE, "air species tables: air species %zu, zone %zu holds %d sources of %d", l / Z, l % Z, cs[l] - t.src_off[l], t.src_off[l + 1] - t.src_off[l]);
+    for (size_t z = 0; z < Z; z++)
+        if (cv[z] != t.vent_off[z + 1])
+            return failp(err, HEAT_E_SIZE, "air species tables: zone %zu holds %d demand vents of %d", z, cv[z] - t.vent_off[z], t.vent_off[z + 1] - t.vent_off[z]);
+    // the rows
+    for (size_t l = 0; l < L; l++)
+        if (t.outdoor_chan[l] != sp->outdoor_chan[l])
+            return failp(err, HEAT_E_SIZE, "air species tables: air species %zu: the outdoor channel of zone %zu is not the caller's", l / Z, l % Z);
+    for (size_t s = 0; s < NS; s++)
+        if (t.limit_chan[s] != (sp->limit_chan ? sp->limit_chan[s] : -1))
+            return failp(err, HEAT_E_SIZE, "air species tables: air species %zu: the limit channel is not the caller's", s);
+    for (size_t z = 0; z < Z; z++)
+        if (t.occ_chan[z] != (sp->occ_chan ? sp->occ_chan[z] : -1))
+            return failp(err, HEAT_E_SIZE, "air species tables: air species 0: the occupancy channel of zone %zu is not the caller's", z);
+    for (size_t j = 0; j < B; j++) {
+        const double gain = h->br_volume_gain ? h->br_volume_gain[j] : 1.0;
+        if (t.br_chan[j] != h->br_volume_chan[j] || std::memcmp(&t.br_gain[j], &gain, sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "air species tables: air species 0: branch %zu of the handlers is not the caller's", j);
+    }
+    return HEAT_OK;
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -3350,6 +3520,25 @@ int heat_air_handlers_check(const heat_batch_desc *desc, const heat_series *s, c
     heat::HandlerTables t;
     heat::build_air_handler_tables(desc->n_zones, h, t);
     return heat::check_air_handler_tables(desc->n_zones, h, t, heat::last_error());
+}
+
+int heat_air_species_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l, const heat_air_paths *air,
+                           const heat_air_handlers *h, const heat_air_species *sp) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    // the three terms whose air the species ride on, as their own checks take them
+    if ((rc = heat::check_zone_loads(desc->n_zones, s->n_channels, l, heat::last_error()))) return rc;
+    if ((rc = heat::check_air_paths(desc->n_zones, s->n_channels, air, heat::last_error()))) return rc;
+    if ((rc = heat::check_air_handlers(desc->n_zones, s->n_channels, h, heat::last_error()))) return rc;
+    rc = heat::check_air_species(desc->n_zones, s->n_channels, sp, heat::last_error());
+    if (rc || !sp) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see)
+    heat::SpeciesTables t;
+    heat::build_air_species_tables(desc->n_zones, h, sp, t);
+    return heat::check_air_species_tables(desc->n_zones, h, sp, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

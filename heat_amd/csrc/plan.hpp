@@ -226,6 +226,37 @@ void build_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, Handl
 // buffers, every row the caller's. HEAT_OK or HEAT_E_SIZE.
 int check_air_handler_tables(int64_t n_zones, const heat_air_handlers *h, const HandlerTables &t, std::string &err);
 
+// Air species of a series (heat_air_species, include/heat_amd.h). Everything heat_air_species_check promises about the term
+// itself; sp == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "air species s", "species source i"
+// or "demand vent j".
+int check_air_species(int64_t n_zones, int32_t n_channels, const heat_air_species *sp, std::string &err);
+// The tables of k_series_vents (one lane per zone) and k_series_species (one lane per (species, zone), lane = s * n_zones + z):
+// the sources stably sorted by lane and the vents stably sorted by zone — two counting sorts, the caller's order survives
+// inside a range — each with CSR offsets; v_orig keeps the caller's number of a vent: V, vent_v, vent_q and the vents'
+// accumulators stay in the caller's order. A NULL src_factor is ones here, a NULL channel list -1. br_chan / br_gain: the
+// volume channel and gain of every branch of the handlers in the CALLER's order (a NULL gain is ones), which the species'
+// lanes reach through the handlers' own supply table (HandlerTables::zone_off, z_orig); empty without handlers.
+struct SpeciesTables {
+    std::vector<int32_t> outdoor_chan;                              // [n_species][n_zones]
+    std::vector<int32_t> src_off;                                   // [n_species * n_zones + 1]
+    std::vector<int32_t> src_chan;                                  // [n_sources] by lane
+    std::vector<double> src_factor;                                 // [n_sources] by lane
+    std::vector<int32_t> vent_off;                                  // [n_zones + 1]
+    std::vector<int32_t> v_species, v_temp_chan, v_enable_chan, v_orig;   // [n_vents] by zone
+    std::vector<double> v_min, v_max, c_lo, c_hi;                   // [n_vents] by zone
+    std::vector<int32_t> limit_chan;                                // [n_species]
+    std::vector<int32_t> occ_chan;                                  // [n_zones]
+    std::vector<int32_t> br_chan;                                   // [n_branches], the caller's order
+    std::vector<double> br_gain;                                    // [n_branches], the caller's order
+};
+// (of terms that passed check_air_handlers and check_air_species)
+void build_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const heat_air_species *sp, SpeciesTables &t);
+// The tables against the caller's lists (used by the host-only check): every source present exactly once in its lane's
+// range, every vent exactly once in its zone's, both in the caller's order, the offsets monotone and inside the buffers,
+// every row the caller's. HEAT_OK or HEAT_E_SIZE.
+int check_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const heat_air_species *sp, const SpeciesTables &t,
+                             std::string &err);
+
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
 // themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".
 // load_of_zone (nullable): [n_zones], the load of every zone or -1 — the table k_zone_update_ideal looks its zone up in.

@@ -779,6 +779,86 @@ struct HandlersTerm {
     }
 };
 
+// The air species (heat_air_species): the sources as CSR over the (species, zone) lanes and the vents as CSR over the zones
+// (plan.hpp, SpeciesTables), the rows of channels, the handlers' branch volumes in the caller's order, the step's scratch (V
+// per vent), the concentrations twice — a step reads one and writes the other, `now` is the one the next step reads —, the
+// accumulators and the three arrays of rows. Nothing of it exists on the device without species.
+struct SpeciesTerm {
+    heat_air_species *sp = nullptr;
+    int64_t NSP = 0, NV = 0, L = 0;  // species, vents, lanes = NSP * Z
+    SpeciesTables spt;
+    DevBuf<int32_t> outdoor_chan, src_off, src_chan, vent_off, v_i32, limit_chan, occ_chan, br_chan;
+    DevBuf<double> src_factor, v_f64, br_gain, vent_V, conc[2], conc_rows, vent_v, vent_q;  // the last three: [n_steps][L], [n_steps][NV] twice
+    int now = 0;
+    Acc<double> lane_f64[3];   // sum_conc, max_conc, excess_above
+    Acc<int64_t> lane_i64[3];  // n_occupied, step_max, n_above
+    Acc<double> vent_f64[2];   // sum_volume, sum_q
+    Acc<int64_t> steps_saturated;
+    SpeciesDev view{};
+    void prepare(const heat_batch *b, const heat_air_handlers *ah, heat_air_species *sp_) {
+        sp = sp_;
+        NSP = sp ? sp->n_species : 0;
+        if (NSP == 0) return;
+        NV = sp->n_vents, L = NSP * b->n_zones;
+        build_air_species_tables(b->n_zones, ah, sp, spt);
+        lane_f64[0].bind(sp->sum_conc, 0.0, &view.sum_conc), lane_f64[1].bind(sp->max_conc, -std::numeric_limits<double>::infinity(), &view.max_conc);
+        lane_f64[2].bind(sp->excess_above, 0.0, &view.excess_above);
+        lane_i64[0].bind(sp->n_occupied, 0, &view.n_occupied), lane_i64[1].bind(sp->step_max, -1, &view.step_max);
+        lane_i64[2].bind(sp->n_above, 0, &view.n_above);
+        vent_f64[0].bind(sp->sum_volume, 0.0, &view.sum_volume), vent_f64[1].bind(sp->sum_q, 0.0, &view.sum_q);
+        steps_saturated.bind(sp->steps_saturated, 0, &view.steps_saturated);
+    }
+    int upload(const double *host_conc, const double *host_v, const double *host_q, int n_steps) {
+        if (NSP == 0) return HEAT_OK;
+        const bool resume = sp->resume != 0;
+        SERIES_TRY(series_upload(outdoor_chan, spt.outdoor_chan, "air species tables"));
+        SERIES_TRY(series_upload(src_off, spt.src_off, "air species tables"));
+        SERIES_TRY(series_upload(src_chan, spt.src_chan, "air species tables"));
+        SERIES_TRY(series_upload(src_factor, spt.src_factor, "air species tables"));
+        SERIES_TRY(series_upload(limit_chan, spt.limit_chan, "air species tables"));
+        SERIES_TRY(series_upload(occ_chan, spt.occ_chan, "air species tables"));
+        SERIES_TRY(series_upload(br_chan, spt.br_chan, "air species tables"));
+        SERIES_TRY(series_upload(br_gain, spt.br_gain, "air species tables"));
+        SERIES_TRY(series_upload(conc[0], sp->conc, (size_t)L, "concentrations"));
+        SERIES_TRY(series_alloc(conc[1], (size_t)L, "concentrations"));
+        if (host_conc) SERIES_TRY(series_alloc(conc_rows, (size_t)n_steps * L, "concentration rows"));
+        for (auto &a : lane_f64) SERIES_TRY(a.stage((size_t)L, resume, "air species accumulators"));
+        for (auto &a : lane_i64) SERIES_TRY(a.stage((size_t)L, resume, "air species accumulators"));
+        view.n_species = (int)NSP, view.n_vents = (int)NV, view.outdoor_chan = outdoor_chan.p, view.src_off = src_off.p, view.src_chan = src_chan.p;
+        view.src_factor = src_factor.p, view.limit_chan = limit_chan.p, view.occ_chan = occ_chan.p, view.br_chan = br_chan.p, view.br_gain = br_gain.p;
+        if (NV == 0) return HEAT_OK;
+        // (the vents' rows packed into two uploads: v_species, v_temp_chan, v_enable_chan, v_orig and v_min, v_max, c_lo, c_hi)
+        std::vector<int32_t> h_i32;
+        std::vector<double> h_f64;
+        for (auto *v : {&spt.v_species, &spt.v_temp_chan, &spt.v_enable_chan, &spt.v_orig}) h_i32.insert(h_i32.end(), v->begin(), v->end());
+        for (auto *v : {&spt.v_min, &spt.v_max, &spt.c_lo, &spt.c_hi}) h_f64.insert(h_f64.end(), v->begin(), v->end());
+        SERIES_TRY(series_upload(vent_off, spt.vent_off, "demand vent tables"));
+        SERIES_TRY(series_upload(v_i32, h_i32, "demand vent tables"));
+        SERIES_TRY(series_upload(v_f64, h_f64, "demand vent tables"));
+        SERIES_TRY(series_alloc(vent_V, (size_t)NV, "vent volume flows"));
+        for (auto &a : vent_f64) SERIES_TRY(a.stage((size_t)NV, resume, "demand vent accumulators"));
+        SERIES_TRY(steps_saturated.stage((size_t)NV, resume, "demand vent accumulators"));
+        if (host_v) SERIES_TRY(series_alloc(vent_v, (size_t)n_steps * NV, "vent volume flows"));
+        if (host_q) SERIES_TRY(series_alloc(vent_q, (size_t)n_steps * NV, "vent powers"));
+        view.vent_off = vent_off.p, view.v_species = v_i32.p, view.v_temp_chan = v_i32.p + NV, view.v_enable_chan = v_i32.p + 2 * NV;
+        view.v_orig = v_i32.p + 3 * NV, view.v_min = v_f64.p, view.v_max = v_f64.p + NV, view.c_lo = v_f64.p + 2 * NV, view.c_hi = v_f64.p + 3 * NV;
+        view.vent_V = vent_V.p;
+        return HEAT_OK;
+    }
+    hipError_t start(hipStream_t st) {
+        if (NSP == 0 || sp->resume != 0) return hipSuccess;
+        hipError_t e = for_each_acc(lane_i64, &Acc<int64_t>::start, st, for_each_acc(lane_f64, &Acc<double>::start, st));
+        return steps_saturated.start(st, for_each_acc(vent_f64, &Acc<double>::start, st, e));
+    }
+    hipError_t fetch(double *host_conc, double *host_v, double *host_q, hipStream_t st) {
+        if (NSP == 0) return hipSuccess;
+        hipError_t e = series_fetch(host_q, vent_q, st, series_fetch(host_v, vent_v, st, series_fetch(host_conc, conc_rows, st)));
+        e = series_fetch(sp->conc, conc[now], st, e);
+        e = for_each_acc(lane_i64, &Acc<int64_t>::fetch, st, for_each_acc(lane_f64, &Acc<double>::fetch, st, e));
+        return steps_saturated.fetch(st, for_each_acc(vent_f64, &Acc<double>::fetch, st, e));
+    }
+};
+
 // The anisotropic sky (heat_sky_aniso): the coefficient table as given, beside the record table, and the bands of the three
 // consumers — the sides' per DEVICE surface, the apertures' and the shades' in the caller's order as their tables are; zeros
 // where the caller gave none. Absent (every pointer NULL) without aniso: the isotropic kernels are launched.
@@ -870,8 +950,8 @@ struct ComfortTerm {
 };
 
 // What heat_batch_march_series_call takes (the eleven positional entry points fill what they have) and, beside it, the comfort
-// term and its two arrays of rows (heat_batch_march_series_comfort) and the air handlers with their four
-// (heat_batch_march_series_handlers); filled by field name. no_trace_ok: a NULL trace records none.
+// term and its two arrays of rows (heat_batch_march_series_comfort), the air handlers with their four
+// (heat_batch_march_series_handlers) and the air species with their three (heat_batch_march_series_species); filled by field name. no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
@@ -893,6 +973,8 @@ struct SeriesCall {
     double *operative = nullptr, *mrt = nullptr;
     heat_air_handlers *handlers = nullptr;
     double *supply_t = nullptr, *recovered = nullptr, *coil_q = nullptr, *branch_q = nullptr;
+    heat_air_species *species = nullptr;
+    double *conc_rows = nullptr, *vent_v = nullptr, *vent_q = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -936,6 +1018,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = check_ambient(b->n_surf, side_kind, b->n_zones, s, c.ambient, heat::last_error()))) return rc;
     if ((rc = check_comfort(b->n_surf, b->n_zones, s, c.comfort, heat::last_error()))) return rc;
     if ((rc = check_air_handlers(b->n_zones, s->n_channels, c.handlers, heat::last_error()))) return rc;
+    if ((rc = check_air_species(b->n_zones, s->n_channels, c.species, heat::last_error()))) return rc;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -964,6 +1047,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     ShadesTerm shades; BlindsTerm blinds; GainsTerm gains; RadiationTerm radiation; AmbientTerm ambient; AirTerm air; AnisoTerm aniso;
     ComfortTerm comfort;
     HandlersTerm handlers;
+    SpeciesTerm species;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
@@ -979,8 +1063,9 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     air.prepare(b, c.air);
     comfort.prepare(b, c.comfort);
     handlers.prepare(b, c.handlers);
+    species.prepare(b, c.handlers, c.species);
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
-    const int64_t NL = blinds.NL, NF = comfort.NF, NU = handlers.NU, NBR = handlers.NBR;
+    const int64_t NL = blinds.NL, NF = comfort.NF, NU = handlers.NU, NBR = handlers.NBR, NSP = species.NSP, NV = species.NV;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -1000,14 +1085,16 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = air.upload(b, c.path_q, n_steps))) return rc;
     if ((rc = comfort.upload(b, c.operative, c.mrt, n_steps))) return rc;
     if ((rc = handlers.upload(c.supply_t, c.recovered, c.coil_q, c.branch_q, n_steps))) return rc;
+    if ((rc = species.upload(c.conc_rows, c.vent_v, c.vent_q, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
     HIP_TRY(report.start(b->stream));
     HIP_TRY(ideal.start(b->stream));
     HIP_TRY(comfort.start(b->stream));
+    HIP_TRY(species.start(b->stream));
     // what the thermostats, the air paths' e and the blinds sense: the zone temperatures, or with a control sensor the step's Tc
     const double *control_T = comfort.control_T.p ? comfort.control_T.p : b->d_zone_T.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    // ---- the steps, enqueued without waiting: head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> ambient drive ->
+    // ---- the steps, enqueued without waiting: head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> air species -> ambient drive ->
     // driven inputs -> shades -> blinds -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
         const double *channel = row(d_channel, k, NC);
@@ -1033,6 +1120,16 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
                                         row(handlers.coil_q, k, NU), branch_row, b->stream);
             if (handlers.supplies())
                 launch_series_handler_supply((int)Z, handlers.view, b->d_zone_T.p, b->d_zone_a0.p, b->d_zone_b0.p, branch_row, b->d_flags.p, b->stream);
+        }
+        if (NSP > 0) {
+            const double *conc = species.conc[species.now].p;
+            if (NV > 0)
+                launch_series_vents((int)Z, species.view, channel, b->d_zone_T.p, conc, b->d_zone_a0.p, b->d_zone_b0.p, row(species.vent_v, k, NV),
+                                    row(species.vent_q, k, NV), b->d_flags.p, b->stream);
+            launch_series_species((int)Z, species.view, loads.on ? &loads.view : nullptr, NP > 0 ? &air.view : nullptr,
+                                  NU > 0 ? &handlers.view : nullptr, channel, b->d_zone_vol.p, (double)n_sub * b->dt, conc,
+                                  species.conc[species.now ^ 1].p, row(species.conc_rows, k, species.L), c.species->step_base + k, b->stream);
+            species.now ^= 1;
         }
         if (NB > 0) launch_series_ambient(ambient.view, channel, b->d_zone_T.p, b->d_side_const.p, row(ambient.t, k, NB), b->stream);
         if (in.driven)
@@ -1083,6 +1180,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(ambient.fetch(c.ambient_t, b->stream));
     HIP_TRY(comfort.fetch(c.operative, c.mrt, b->stream));
     HIP_TRY(handlers.fetch(c.supply_t, c.recovered, c.coil_q, c.branch_q, b->stream));
+    HIP_TRY(species.fetch(c.conc_rows, c.vent_v, c.vent_q, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -1186,8 +1284,9 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
     return march_series_impl(b, c);
 }
 
-// heat_batch_march_series_call, heat_batch_march_series_comfort and heat_batch_march_series_handlers: the struct's fields by
-// name, then the comfort term, then the air handlers (`more`: what the last of them adds, or nullptr).
+// heat_batch_march_series_call, heat_batch_march_series_comfort, heat_batch_march_series_handlers and
+// heat_batch_march_series_species: the struct's fields by name, then the comfort term, then the air handlers and the air species
+// (`more`: what the last two add, or nullptr).
 static int march_series_call(heat_batch *b, const heat_series_call *call, heat_comfort *comfort, double *operative, double *mrt,
                              const SeriesCall *more = nullptr) {
     if (const int rc = check_series_call(call, heat::last_error())) return rc;  // (a struct of another size is not read further)
@@ -1210,6 +1309,14 @@ int heat_batch_march_series_comfort(heat_batch *b, const heat_series_call *call,
 int heat_batch_march_series_handlers(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt,
                                      heat_air_handlers *h, double *supply_t, double *recovered, double *coil_q, double *branch_q) {
     SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
+    return march_series_call(b, call, c, operative, mrt, &more);
+}
+
+int heat_batch_march_series_species(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt,
+                                    heat_air_handlers *h, double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                    heat_air_species *sp, double *conc_rows, double *vent_v, double *vent_q) {
+    SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
+    more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q;
     return march_series_call(b, call, c, operative, mrt, &more);
 }
 

@@ -1281,6 +1281,108 @@ int heat_batch_march_series_handlers(heat_batch *b, const heat_series_call *call
                                      double *coil_q    /* [n_steps][n_units], nullable */,
                                      double *branch_q  /* [n_steps][n_branches], nullable */);
 
+/*
+ * Air species of a series: what rides on the air a series moves — CO2, moisture, any pollutant — as one well-mixed
+ * concentration per species and zone, held on the device over the steps, and DEMAND VENTS whose volume flow follows such a
+ * concentration. Every flow of air of a series enters the balance: the zone loads' flows, the air paths that are open in the
+ * step, the handlers' supply branches and the vents themselves. A concentration depends on which controlled paths are open
+ * — a state the device decides from temperatures only it holds — and a vent's flow enters the zones' a0 / b0: none of it can
+ * be a schedule. The reference has no counterpart (zone.rs, model.rs:500-597); the rule below is this library's own contract,
+ * defined against the per-call loop with the same rule written on the host (heat_amd/air_species.py, apply()). The unit of a
+ * concentration is the caller's (amount per m3 of air); a source is amount per second.
+ * The rule of step k, behind the air handlers and before the ambient drive — a zone's sum is
+ * (((row + loads) + paths) + branches) + vents. T = the zone AIR temperatures, C = the concentrations the device holds when
+ * the step starts, row = channel[k], K = step_base + k. Every line is ONE rounded f64 operation in the order written, no fused
+ * multiply-add; a NaN makes every comparison false:
+ *   per vent j (zone z, species s); a zone's vents in the caller's order:
+ *     c = C[s][z];  x = c - c_lo;  span = c_hi - c_lo;  f = x / span
+ *     if f < 0.0: f = 0.0
+ *     if f > 1.0: f = 1.0
+ *     saturated = (f == 1.0)
+ *     dv = v_max - v_min;  y = f * dv;  V = v_min + y
+ *     disabled (enable_chan >= 0 and not row[enable_chan] > 0):  V = 0.0, q = 0.0, nothing is added to a0 / b0, not saturated
+ *     else: Tin = row[temp_chan];  Tk = Tin + 273.15;  rho = 101325 * 28.97 / (8314.46261815324 * Tk)
+ *           cp = 1002.7370 + 1.2324e-2 * Tk;  m = (rho * V) * cp       (exactly the zone loads' expressions and grouping)
+ *           mt = m * Tin;  a0[z] = a0[z] + mt;  b0[z] = b0[z] + m;  dT = Tin - T[z];  q = m * dT
+ *     vent_v[k][j] = V;  vent_q[k][j] = q;  sum_volume += V;  sum_q += q;  steps_saturated += saturated
+ *   per species s and zone z:
+ *     h = (double)n_sub * dt;  c = C[s][z];  co = outdoor_chan[s][z] >= 0 ? row[outdoor_chan[s][z]] : 0.0
+ *     S = 0.0;  per source of (s, z), in the caller's order:  x = src_factor * row[src_chan];  S = S + x
+ *     F = 0.0;  G = 0.0;  per inflow into z:  g = V * ci;  F = F + V;  G = G + g,  in this order:
+ *       the zone loads' flows of z, caller's order:     V = flow_volume_gain * row[flow_volume_chan];  ci = co
+ *       the air paths with target z that are OPEN in step k (uncontrolled, or state == 1 after this step's decision),
+ *           caller's order:                             V = volume_gain * row[volume_chan];  ci = source >= 0 ? C[s][source] : co
+ *       the handlers' SUPPLY branches of z, caller's order:  V = br_volume_gain * row[br_volume_chan];  ci = co
+ *       the vents of z (of whatever species), caller's order:  V as above (0.0 where disabled);  ci = co
+ *     p = S + G;  hp = h * p;  vc = vol[z] * c;  num = vc + hp;  hF = h * F;  den = vol[z] + hF;  c_new = num / den
+ *     conc_rows[k][s][z] = c                            (the state at the START of step k, as every other row)
+ *     occupied (occ_chan[z] < 0 or row[occ_chan[z]] > 0):
+ *         n_occupied += 1;  sum_conc = sum_conc + c;  if c > max_conc { max_conc = c; step_max = K }
+ *         if limit_chan[s] >= 0 and c > row[limit]:  n_above += 1;  d = c - row[limit];  excess_above = excess_above + d
+ *     C[s][z] = c_new                                   (after every lane of the step has read its sources)
+ * A backward-Euler step of vol dc/dt = S + sum V (ci - c): only inflows appear, as in the heat balance, and neighbours are
+ * taken as they were at the START of the step — a chain A -> B -> C does not propagate within a step. Unconditionally stable
+ * for V >= 0. A gain of 1 is multiplied like any other (x * 1.0 is x). The vents' terms hold for all n_sub sub-timesteps: ideal
+ * loads see them. n_sub == 0 still evaluates every step, with h = 0. conc, the accumulators and the air paths' state carry a
+ * cut: a series of k steps followed by one of n - k with the returned arrays and step_base + k gives the bits of the series of
+ * n. resume == 0 initialises every accumulator on the device, the vents' three included (sums and counts 0, max_conc = -inf,
+ * step_max = -1); conc is always read. A vent that turns a clean a0 / b0 into NaN is
+ * HEAT_N_NAN_ZONE for its zone at that step, as for the air paths; a NaN concentration that reaches no vent is no failure and
+ * stays in its rows. An array that is not asked for costs no traffic and changes no bit of the others. With sp == NULL or
+ * n_species == 0 heat_batch_march_series_species is heat_batch_march_series_handlers exactly: same launches, same bits. A
+ * refused call leaves the device state untouched. Sharded batches are refused as by the series.
+ * heat_air_species_check (host-only; it checks l, air and h as their own checks do, and builds and verifies the tables the
+ * march uploads) and heat_batch_march_series_species run the same checks before any device work; every message names "air
+ * species s", "species source i" or "demand vent j". HEAT_E_INVALID_ARG: a negative count; a NULL array that a positive count
+ * needs (outdoor_chan, conc; src_zone, src_species, src_chan; vent_zone, vent_species, vent_temp_chan, vent_v_min, vent_v_max,
+ * vent_c_lo, vent_c_hi); sources or vents with n_species == 0; a src_factor, v_min, v_max, c_lo or c_hi that is not finite;
+ * v_min < 0, v_max < v_min or c_hi <= c_lo. A conc entry that is not finite is data and is accepted. HEAT_E_SIZE: a zone,
+ * species or channel out of range (outdoor_chan, vent_enable_chan, limit_chan and occ_chan may be -1).
+ * Out of scope: density differences between inflow and zone air (a volume flow carries its concentration as it is);
+ * recirculating units (a handler supplies outside air); sorption in materials; latent heat; deposition and filters, except as
+ * a negative source.
+ */
+typedef struct heat_air_species {
+    int64_t n_species;
+    const int32_t *outdoor_chan;        /* [n_species][n_zones] the concentration of OUTSIDE air entering zone z; -1: 0.0 */
+    int64_t n_sources;
+    const int32_t *src_zone, *src_species, *src_chan;
+    const double  *src_factor;          /* nullable = 1; amount per second = factor * row[chan], negative allowed */
+    int64_t n_vents;
+    const int32_t *vent_zone, *vent_species;
+    const int32_t *vent_temp_chan;      /* outdoor-air temperature, C */
+    const int32_t *vent_enable_chan;    /* nullable / -1: always enabled; else enabled where row[chan] > 0 */
+    const double  *vent_v_min, *vent_v_max;          /* m3/s, finite, 0 <= min <= max */
+    const double  *vent_c_lo, *vent_c_hi;            /* finite, lo < hi */
+    const int32_t *limit_chan;          /* [n_species] nullable / -1: no limit */
+    const int32_t *occ_chan;            /* [n_zones] nullable / -1: always occupied; else occupied where row[chan] > 0 */
+    int64_t resume;                     /* as heat_comfort::resume, for the nine accumulators below */
+    int64_t step_base;                  /* K = step_base + k is what step_max records */
+    double  *conc;                      /* [n_species][n_zones] in/out, required when n_species > 0 */
+    /* accumulators, [n_species][n_zones] each, in/out, nullable */
+    int64_t *n_occupied;
+    double  *sum_conc;
+    double  *max_conc;
+    int64_t *step_max;                  /* kept where max_conc is: it records the step of that maximum */
+    int64_t *n_above;
+    double  *excess_above;
+    /* per vent, [n_vents] each, in/out, nullable */
+    double  *sum_volume;
+    double  *sum_q;
+    int64_t *steps_saturated;
+} heat_air_species;
+
+int heat_air_species_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l /* nullable */,
+                           const heat_air_paths *air /* nullable */, const heat_air_handlers *h /* nullable */,
+                           const heat_air_species *sp /* nullable */); /* host-only */
+int heat_batch_march_series_species(heat_batch *b, const heat_series_call *call, heat_comfort *c /* nullable */,
+                                    double *operative, double *mrt, heat_air_handlers *h /* nullable */,
+                                    double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                    heat_air_species *sp /* nullable */,
+                                    double *conc_rows /* [n_steps][n_species][n_zones], nullable */,
+                                    double *vent_v    /* [n_steps][n_vents], nullable */,
+                                    double *vent_q    /* [n_steps][n_vents], nullable */);
+
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

@@ -125,6 +125,16 @@ pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
     pub steps_bypass: *mut i64, pub switches: *mut i64, pub steps_heat_saturated: *mut i64, pub steps_cool_saturated: *mut i64,
     pub sum_branch_q: *mut f64,
 }
+// heat_air_species: concentrations per species and zone carried by the air a series moves, and demand vents that follow them
+#[repr(C)] pub struct HeatAirSpecies {
+    pub n_species: i64, pub outdoor_chan: *const i32,
+    pub n_sources: i64, pub src_zone: *const i32, pub src_species: *const i32, pub src_chan: *const i32, pub src_factor: *const f64,
+    pub n_vents: i64, pub vent_zone: *const i32, pub vent_species: *const i32, pub vent_temp_chan: *const i32,
+    pub vent_enable_chan: *const i32, pub vent_v_min: *const f64, pub vent_v_max: *const f64, pub vent_c_lo: *const f64,
+    pub vent_c_hi: *const f64, pub limit_chan: *const i32, pub occ_chan: *const i32, pub resume: i64, pub step_base: i64,
+    pub conc: *mut f64, pub n_occupied: *mut i64, pub sum_conc: *mut f64, pub max_conc: *mut f64, pub step_max: *mut i64,
+    pub n_above: *mut i64, pub excess_above: *mut f64, pub sum_volume: *mut f64, pub sum_q: *mut f64, pub steps_saturated: *mut i64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -224,6 +234,13 @@ extern "C" {
     pub fn heat_batch_march_series_handlers(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
                                             operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
                                             recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64) -> c_int;
+    // air species of a series: concentrations carried by every flow of air, demand vents that follow them
+    pub fn heat_air_species_check(desc: *const HeatBatchDesc, s: *const HeatSeries, l: *const HeatZoneLoads, air: *const HeatAirPaths,
+                                  h: *const HeatAirHandlers, sp: *const HeatAirSpecies) -> c_int;
+    pub fn heat_batch_march_series_species(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
+                                           operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
+                                           recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64, sp: *mut HeatAirSpecies,
+                                           conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

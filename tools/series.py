@@ -113,8 +113,15 @@ and writes profiles/series_handlers.json: ms per step of each, H - N, a series o
 per-step times once the set-up is taken off — and, where a kernel trace of one H series has been taken (--one-series --handlers
 under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_handlers_kernel_stats.csv), k_series_handler_units
 and k_series_handler_supply per step. No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers]
+With --species (heat_batch_march_series_species, heat_air_species; the loads and the handlers of --handlers) it alternates
+  N  the series with loads and handlers through heat_batch_march_series_species, species = NULL
+  P  the same call with two species, one demand vent and one source per zone, a limit and every accumulator kept
+and writes profiles/series_species.json: ms per step of each, P - N, a series of ONE step of each (the call's set-up) and the
+per-step times once the set-up is taken off — and, where a kernel trace of one P series has been taken (--one-series --species
+under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_species_kernel_stats.csv), k_series_vents and
+k_series_species per step. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
@@ -125,7 +132,7 @@ and k_series_handler_supply per step. No time is a pass criterion.
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, air_handlers as ahm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -138,7 +145,8 @@ SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
 COMFORT = "--comfort" in sys.argv
-HANDLERS = "--handlers" in sys.argv
+SPECIES = "--species" in sys.argv
+HANDLERS = "--handlers" in sys.argv or SPECIES
 LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT or COMFORT or HANDLERS
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -318,6 +326,29 @@ if HANDLERS:
         dt = time.perf_counter() - t0
         assert out[1] == -1 and np.all(np.isfinite(out[0]))
         assert handlers is None or np.all(np.isfinite(out[4]["sum_branch_q"]))
+        return dt * 1e3 / steps
+if SPECIES:
+    # four more channels (the outdoor levels of the two species, a source strength, a limit) and per zone one demand vent on
+    # the first species — outdoor air at the handlers' outdoor temperature — and one source of each species
+    c_sp = channel.shape[1]
+    channel = np.concatenate([channel, rng.uniform(400.0, 450.0, (STEPS, 1)), rng.uniform(4.0, 9.0, (STEPS, 1)), rng.uniform(0.0, 1.0, (STEPS, 1)),
+                              rng.uniform(900.0, 1100.0, (STEPS, 1))], axis=1)
+    species_args = dict(outdoor_chan=aspm.per_zone([c_sp, c_sp + 1], Z), conc=np.stack([rng.uniform(400.0, 1500.0, Z), rng.uniform(4.0, 12.0, Z)]),
+                        src_zone=np.tile(every, 2), src_species=np.repeat([0, 1], Z), src_chan=np.full(2 * Z, c_sp + 2, np.int32),
+                        src_factor=np.concatenate([rng.uniform(0.5, 3.0, Z), rng.uniform(0.005, 0.03, Z)]), vent_zone=every,
+                        vent_species=np.zeros(Z, np.int32), vent_temp_chan=np.full(Z, c_ah, np.int32), vent_v_min=np.zeros(Z),
+                        vent_v_max=rng.uniform(0.02, 0.1, Z), vent_c_lo=rng.uniform(500.0, 700.0, Z), vent_c_hi=rng.uniform(900.0, 1200.0, Z),
+                        limit_chan=np.array([c_sp + 3, -1], np.int32))
+
+    def leg_sp(b, w, n_sub, steps, species="given"):
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=channel[:steps], probes=probes, loads=loads, handlers=handler_args, supply_t=False,
+                             recovered=False, coil_q=False, branch_q=False, species=species_args if species == "given" else species,
+                             conc_rows=False, vent_v=False, vent_q=False, **drives)
+        dt = time.perf_counter() - t0
+        assert out[1] == -1 and np.all(np.isfinite(out[0]))
+        assert species == {} or (np.all(np.isfinite(out[5]["conc"])) and out[5]["sum_volume"].any())
         return dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
@@ -597,6 +628,29 @@ with HeatBatch(md) as b:
             print("n_sub %2d: N comfort NULL %.3f ms/step, C comfort %.3f -> C - N = %+.3f ms, C / N = %.4f; a series of one step: "
                   "N %.2f ms, C %.2f ms -> per step without the set-up N %.3f, C %.3f, C - N = %+.3f (%d sensors, %d entries, %d steps, "
                   "median of %d rounds)" % (n_sub, N_, C_, C_ - N_, C_ / N_, N1, C1, Ns, Cs, Cs - Ns, Z, NE, STEPS, ROUNDS), flush=True)
+            continue
+        if SPECIES:
+            leg_sp(b, w, n_sub, min(STEPS, 10), {})  # warm-up
+            leg_sp(b, w, n_sub, min(STEPS, 10))
+            if ONE:
+                print("one series with air species: P %.3f ms per step" % leg_sp(b, w, n_sub, STEPS))
+                continue
+            nn, pp, nn1, pp1 = [], [], [], []
+            for r in range(ROUNDS):
+                nn.append(leg_sp(b, w, n_sub, STEPS, {}))
+                pp.append(leg_sp(b, w, n_sub, STEPS))
+                nn1.append(leg_sp(b, w, n_sub, 1, {}))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                pp1.append(leg_sp(b, w, n_sub, 1))
+            N_, P_, N1, P1 = (float(np.median(v)) for v in (nn, pp, nn1, pp1))
+            Ns, Ps = (N_ * STEPS - N1) / (STEPS - 1), (P_ * STEPS - P1) / (STEPS - 1)  # per step once the call is set up
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                N_species_null_ms=N_, P_species_ms=P_, P_minus_N_ms=P_ - N_, P_over_N=P_ / N_, N_series_of_one_step_ms=N1,
+                P_series_of_one_step_ms=P1, P_minus_N_series_of_one_step_ms=P1 - N1, N_without_setup_ms=Ns, P_without_setup_ms=Ps,
+                P_minus_N_without_setup_ms=Ps - Ns, species=2, lanes=int(2 * Z), vents=int(Z), sources=int(2 * Z),
+                all_rounds=dict(N=nn, P=pp, N_one_step=nn1, P_one_step=pp1))
+            print("n_sub %2d: N species NULL %.3f ms/step, P species %.3f -> P - N = %+.3f ms, P / N = %.4f; a series of one step: "
+                  "N %.2f ms, P %.2f ms -> per step without the set-up N %.3f, P %.3f, P - N = %+.3f (%d lanes, %d vents, %d steps, "
+                  "median of %d rounds)" % (n_sub, N_, P_, P_ - N_, P_ / N_, N1, P1, Ns, Ps, Ps - Ns, 2 * Z, Z, STEPS, ROUNDS), flush=True)
             continue
         if HANDLERS:
             leg_ah(b, w, n_sub, min(STEPS, 10), {})  # warm-up
@@ -1080,7 +1134,23 @@ if AMBIENT and not ONE:
         print("kernel trace: k_series_ambient %.2f us per step" % us)
     else:
         print("no kernel trace at %s" % stats)
-if HANDLERS and not ONE:
+if SPECIES and not ONE:
+    # the kernel trace of one P series (--one-series --species under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: the two kernels per step, beside the same trace's k_series_zone_loads
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_species_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_vents", "k_series_species", "k_series_zone_loads")}
+        result["kernel_trace_of_one_P_series"] = dict({"%s_us_per_step" % k: v for k, v in us.items()}, calls=int(rows["k_series_species"]["Calls"]))
+        print("kernel trace: k_series_vents %.2f us per step, k_series_species %.2f, k_series_zone_loads %.2f" % (
+            us["k_series_vents"], us["k_series_species"], us["k_series_zone_loads"]))
+    else:
+        result["kernel_trace_of_one_P_series"] = "not taken yet"
+        print("no kernel trace at %s" % stats)
+if HANDLERS and not SPECIES and not ONE:
     # the kernel trace of one H series (--one-series --handlers under rocprofv3 --kernel-trace --stats, a run of its own), where it
     # has been taken: the two kernels per step, beside the same trace's k_series_zone_loads
     stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
@@ -1098,7 +1168,7 @@ if HANDLERS and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
