@@ -7,9 +7,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libheat_amd.so")
-SOURCES = ["kernels.hip", "batch.hip", "series.hip", "plan.cpp", "setup.cpp"]
+SOURCES = ["kernels.hip", "series_kernels.hip", "batch.hip", "series.hip", "plan.cpp", "setup.cpp"]
 HOST_SOURCES = ["plan.cpp"]  # host-only: g++ compiles them too (build_plan_host, the tests' sanitizer programs)
-HEADERS = ["layout.hpp", "kernels.hpp", "device_math.hpp", "plan.hpp", "batch.hpp", os.path.join("..", "..", "include", "heat_amd.h"),
+HEADERS = ["layout.hpp", "kernels.hpp", "series_kernels.hpp", "device_math.hpp", "plan.hpp", "batch.hpp", os.path.join("..", "..", "include", "heat_amd.h"),
            os.path.join("..", "..", "include", "heat_amd_setup.h")]
 
 

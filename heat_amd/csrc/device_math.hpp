@@ -1,5 +1,6 @@
-// device_math.hpp — leaf physics of the wall heat-conduction path as gfx950 device functions.
-// Each function cites the reference lines (relative to the reference repo root) it implements.
+// device_math.hpp — leaf physics of the wall heat-conduction path as gfx950 device functions, and (at the end) the failure
+// report and the DPP sums that kernels.hip and series_kernels.hip share.
+// Each physics function cites the reference lines (relative to the reference repo root) it implements.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "layout.hpp"
@@ -185,6 +186,55 @@ __device__ inline double cavity_u_value(const CavityDev &c, double t_front, doub
     const double tm = (t_back + t_front) / 2. + 273.15;
     const double rad = 4. * ((tm * tm) * tm) * kSigma * c.ein * c.eout / (1. - (1. - c.ein) * (1. - c.eout));
     return rad + conv;
+}
+
+// ---- not physics: what the march kernels (kernels.hip) and the series kernels (series_kernels.hip) both call ----
+// (here and not in a header of their own: the march depends on them, and the benchmark stamps its counters with this file)
+
+// A numerical failure (the reference panics there: surface.rs:704-707,850; model.rs:417-420): the kind goes into
+// the flag word, and the FIRST place it happened — smallest device surface (or zone) number — into the 64-bit word
+// behind it: number << 8 | kind bits. Rare by nature: no cost on the good path.
+__device__ __forceinline__ void report_failure(int *flags, int bad, unsigned int index) {
+    atomicOr(flags, bad);
+    atomicMin(reinterpret_cast<unsigned long long *>(flags + 2), ((unsigned long long)index << 8) | (unsigned int)(bad & 0xff));
+}
+
+// Sum over the wavefront with DPP (row shifts inside the rows of 16 lanes, then the two row broadcasts): the
+// total arrives in lane 63 and is handed to every lane. A fixed tree: run-to-run deterministic, the same in
+// k_zones and in the cluster-resident march.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_add_f64(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    if constexpr (ROW_MASK == 0xf) {
+        // (every row written: bound_ctrl delivers the zero of a lane without a source or switched off, `old` is dead —
+        // the row broadcasts below write two rows of four and need their zero in the others)
+        lo = __builtin_amdgcn_mov_dpp(lo, CTRL, 0xf, 0xf, true);
+        hi = __builtin_amdgcn_mov_dpp(hi, CTRL, 0xf, 0xf, true);
+        return v + __hiloint2double(hi, lo);
+    }
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
+    return v + __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    v = dpp_add_f64<0x111, 0xf>(v);  // row_shr:1
+    v = dpp_add_f64<0x112, 0xf>(v);  // row_shr:2
+    v = dpp_add_f64<0x114, 0xf>(v);  // row_shr:4
+    v = dpp_add_f64<0x118, 0xf>(v);  // row_shr:8   -> lane 15 of every row holds the row's sum
+    v = dpp_add_f64<0x142, 0xa>(v);  // row_bcast:15 -> rows 1 and 3 add the sum of the row before
+    v = dpp_add_f64<0x143, 0xc>(v);  // row_bcast:31 -> rows 2 and 3 add the sum of rows 0-1
+    const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63);
+    const int hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
+    return __hiloint2double(hi, lo);
+}
+
+// Sums inside the rows of 16 lanes: lane 15 of every row holds its row's sum (the first four steps of wave_sum_f64).
+__device__ __forceinline__ double row_sum_f64(double v) {
+    v = dpp_add_f64<0x111, 0xf>(v);
+    v = dpp_add_f64<0x112, 0xf>(v);
+    v = dpp_add_f64<0x114, 0xf>(v);
+    v = dpp_add_f64<0x118, 0xf>(v);
+    return v;
 }
 
 }  // namespace heat

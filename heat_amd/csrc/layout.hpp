@@ -27,7 +27,7 @@ constexpr double kMassThreshold = 1e-5;    // reference src/discretization.rs:14
 
 enum : int { KIND_SPACE = 0, KIND_AMBIENT = 1, KIND_OUTDOOR = 2 };
 
-// Rows of the shade table of a series (heat_shades; plan.hpp, ShadeTables; kernels.hip, k_series_shading): normal, right and
+// Rows of the shade table of a series (heat_shades; plan.hpp, ShadeTables; series_kernels.hip, k_series_shading): normal, right and
 // up axis, width and height, depth and gap of the overhang, of the fin beside +u and of the fin beside -u, the two factors.
 enum ShadeRow : int { SH_NX, SH_NY, SH_NZ, SH_UX, SH_UY, SH_UZ, SH_VX, SH_VY, SH_VZ, SH_W, SH_H, SH_OD, SH_OG, SH_PD, SH_PG, SH_ND,
                       SH_NG, SH_FD, SH_FG, kShadeRows };

@@ -8,8 +8,8 @@
 #include <vector>
 
 #include "batch.hpp"
-#include "kernels.hpp"
 #include "plan.hpp"
+#include "series_kernels.hpp"
 
 namespace {
 

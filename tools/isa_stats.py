@@ -1,6 +1,7 @@
 """Instruction mix and spill sites of one kernel in a hipcc -S listing:
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only heat_amd/csrc/kernels.hip -o /tmp/k.s
     python tools/isa_stats.py /tmp/k.s k_surfaces_stream
+(the k_series_* kernels and k_fill_f64 are in heat_amd/csrc/series_kernels.hip: take its listing the same way)
 
     python tools/isa_stats.py /tmp/k.s k_surfaces_fastILi16ELi0ELi1ELi0ELi4ELi0ELi0E --blocks [--loop BB112_62] [--json OUT]
 The second form prints the instruction classes of every basic block between the header of the sub-timestep loop and

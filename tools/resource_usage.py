@@ -1,6 +1,7 @@
 """Per-kernel register / scratch / LDS / occupancy table of a -Rpass-analysis=kernel-resource-usage log:
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -c heat_amd/csrc/kernels.hip -o /tmp/k.o -Rpass-analysis=kernel-resource-usage 2> ru.txt
-    python tools/resource_usage.py ru.txt"""
+    python tools/resource_usage.py ru.txt
+(the k_series_* kernels and k_fill_f64 are in heat_amd/csrc/series_kernels.hip: the same command on that file)"""
 import re, subprocess, sys
 rows, cur = [], None
 for line in open(sys.argv[1]):
