@@ -10,10 +10,13 @@ HIP library or without a GPU raises.
 from .binding import HeatBatch, HeatError, ModelBuilder, Weather, lib_path, load_library, build_library  # noqa: F401
 from .binding import AirHandlers, make_air_handlers, air_handlers_check  # noqa: F401
 from .binding import AirSpecies, make_air_species, air_species_check  # noqa: F401
+from .binding import Openings, make_openings, openings_check  # noqa: F401
 from . import modeldict  # noqa: F401
 from . import air_handlers  # noqa: F401
 from . import air_species  # noqa: F401
+from . import openings  # noqa: F401
 
 __all__ = ["HeatBatch", "HeatError", "ModelBuilder", "Weather", "lib_path", "load_library", "build_library", "modeldict",
            "AirHandlers", "make_air_handlers", "air_handlers_check", "air_handlers",
-           "AirSpecies", "make_air_species", "air_species_check", "air_species"]
+           "AirSpecies", "make_air_species", "air_species_check", "air_species",
+           "Openings", "make_openings", "openings_check", "openings"]

@@ -218,6 +218,13 @@ class AirSpecies(C.Structure):
                 ("excess_above", _dp), ("sum_volume", _dp), ("sum_q", _dp), ("steps_saturated", _i64p)]
 
 
+class Openings(C.Structure):
+    """heat_openings (include/heat_amd.h): wind- and stack-driven volume flows through openings, written into derived channels"""
+    _fields_ = [("n_openings", C.c_int64), ("zone_a", _i32p), ("zone_b", _i32p), ("temp_chan", _i32p), ("wind_chan", _i32p),
+                ("frac_chan", _i32p), ("out_chan", _i32p), ("area", _dp), ("cw", _dp), ("cs", _dp), ("ca", _dp), ("c0", _dp),
+                ("resume", C.c_int64), ("step_base", C.c_int64), ("sum_v", _dp), ("max_v", _dp), ("step_max", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -303,6 +310,9 @@ SYMBOLS = [
                                          C.POINTER(AirHandlers), C.POINTER(AirSpecies)]),
     ("heat_batch_march_series_species", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
                                                   _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp]),
+    ("heat_openings_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(Openings)]),
+    ("heat_batch_march_series_openings", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
+                                                   _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp, C.POINTER(Openings), _dp]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -459,7 +469,7 @@ HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
                      "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check", "heat_air_handlers_check",
-                     "heat_air_species_check",
+                     "heat_air_species_check", "heat_openings_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1635,6 +1645,72 @@ def air_species_check(md, species, loads=None, air=None, handlers=None, lib=None
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+OPENING_STATS = ("sum_v", "max_v", "step_max")
+_OPENING_ROWS = (("zone_a", np.int32, True), ("zone_b", np.int32, True), ("temp_chan", np.int32, False), ("wind_chan", np.int32, False),
+                 ("frac_chan", np.int32, False), ("out_chan", np.int32, True), ("area", np.float64, True), ("cw", np.float64, False),
+                 ("cs", np.float64, False), ("ca", np.float64, False), ("c0", np.float64, False))
+
+
+def make_openings(zone_a=(), zone_b=(), out_chan=(), area=(), temp_chan=None, wind_chan=None, frac_chan=None, cw=None, cs=None, ca=None,
+                  c0=None, stats=OPENING_STATS, resume=None, step_base=0):
+    """Builds a heat_openings. Returns (openings, keepalive); the march updates the accumulators in place.
+    zone_a, zone_b   [n] the zones an opening joins; zone_b -1: outside air at the temperature of temp_chan
+    out_chan         [n] the DERIVED channel the opening writes its volume flow into, m3/s: name it as the volume_chan of an air
+                     path, of a flow of the zone loads or of a handler's branch
+    area             [n] m2, the discharge coefficient folded in
+    temp_chan        [n] the outside-air temperature where zone_b is -1, -1 elsewhere; None: no opening to outside
+    wind_chan        [n] the effective wind speed at the opening, m/s; None / -1: no wind term
+    frac_chan        [n] the open fraction, clamped to [0, 1]; None / -1: fully open
+    cw, cs, ca, c0   [n] the coefficients of u^2, |dT| / Tm, |dT| and 1 under the root, each None = 0 (openings.wind_and_stack,
+                     single_sided and doorway give them for three published forms)
+    stats            names out of OPENING_STATS: which accumulators are maintained (default: all)
+    resume           a dict of arrays a previous series returned: the accumulators start from them
+    step_base        the number the first step of this series has in step_max
+    (openings.apply and accumulate are the rule in numpy and take the same dict)"""
+    given = dict(zone_a=zone_a, zone_b=zone_b, out_chan=out_chan, area=area, temp_chan=temp_chan, wind_chan=wind_chan,
+                 frac_chan=frac_chan, cw=cw, cs=cs, ca=ca, c0=c0)
+    unknown = set(stats or ()) - set(OPENING_STATS)
+    if unknown:
+        raise ValueError("openings: unknown stats %s (known: %s)" % (sorted(unknown), ", ".join(OPENING_STATS)))
+    op = Openings()
+    keep = {}
+    n = len(np.asarray(zone_a if zone_a is not None else ()).reshape(-1))
+    op.n_openings, op.resume, op.step_base = n, 0 if resume is None else 1, int(step_base)
+    for name, dtype, needed in _OPENING_ROWS:
+        if given[name] is None and not needed:
+            continue
+        v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+        if v.shape != (n,):
+            raise ValueError("openings %s: %s for %d openings" % (name, v.shape, n))
+        keep[name] = v
+        setattr(op, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    for name in (stats or ()):
+        dtype = np.int64 if name == "step_max" else np.float64
+        if resume is not None:
+            if name not in resume:
+                raise ValueError("openings resume: %s is missing" % name)
+            a = np.array(resume[name], dtype=dtype)  # (a copy: the march writes it)
+            if a.shape != (n,):
+                raise ValueError("openings resume: %s of shape %s, not %s" % (name, a.shape, (n,)))
+        else:
+            a = np.zeros(n, dtype)  # (the library initialises on the device)
+        keep[name] = a
+        setattr(op, name, a.ctypes.data_as(_i64p if dtype == np.int64 else _dp) if a.size else None)
+    return op, keep
+
+
+def openings_check(md, openings, lib=None, **series):
+    """heat_openings_check: everything about the openings of a series that needs no device (series arguments as
+    HeatBatch.march_series; openings: the arguments of make_openings, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    op, okeep = make_openings(**openings) if openings is not None else (None, None)
+    rc = L.heat_openings_check(C.byref(desc), C.byref(s), C.byref(op) if op is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1760,7 +1836,7 @@ class HeatBatch:
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
                      blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True,
                      handlers=None, supply_t=True, recovered=True, coil_q=True, branch_q=True, species=None, conc_rows=True,
-                     vent_v=True, vent_q=True, **series):
+                     vent_v=True, vent_q=True, openings=None, opening_v=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1832,7 +1908,14 @@ class HeatBatch:
         Returns what the same call without species returns plus one dict, appended last: conc_rows [n_steps, n_species,
         n_zones], vent_v, vent_q [n_steps, n_vents] (each empty with its flag False), conc (the concentrations after the last
         step) and of SPECIES_STATS those in stats (pass conc on, and the stats as species["resume"] with step_base, to the
-        next series) — one more element of the tuple, or the key "species" of the dict."""
+        next series) — one more element of the tuple, or the key "species" of the dict.
+        openings (a dict of make_openings' arguments; an empty dict: no opening): heat_batch_march_series_openings — the
+        volume flows that wind and buoyancy drive through openings, formed on the device at the head of every step from the
+        zone air temperatures it holds and written into DERIVED channels, which the air paths, the loads' flows, the handlers'
+        branches and the species read as any channel. Returns what the same call without openings returns plus one dict,
+        appended last: opening_v [n_steps, n_openings] (empty with opening_v=False) and of OPENING_STATS those in stats (pass
+        them as openings["resume"] with step_base to the next series) — one more element of the tuple, or the key "openings"
+        of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -1845,8 +1928,8 @@ class HeatBatch:
                                                                       blind_incident=blind_incident, operative=operative, mrt=mrt,
                                                                       supply_t=supply_t, recovered=recovered, coil_q=coil_q,
                                                                       branch_q=branch_q, conc_rows=conc_rows, vent_v=vent_v,
-                                                                      vent_q=vent_q),
-                                  aniso=aniso, comfort=comfort, handlers=handlers, species=species)
+                                                                      vent_q=vent_q, opening_v=opening_v),
+                                  aniso=aniso, comfort=comfort, handlers=handlers, species=species, openings=openings)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -1872,11 +1955,11 @@ class HeatBatch:
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
-    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None, species=None):
+    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None, species=None, openings=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
         whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None; comfort: the dict of make_comfort's
         arguments or None; handlers: the dict of make_air_handlers' arguments or None; species: the dict of make_air_species'
-        arguments or None."""
+        arguments or None; openings: the dict of make_openings' arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -1928,7 +2011,7 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        if aniso is not None or comfort is not None or handlers is not None or species is not None:
+        if aniso is not None or comfort is not None or handlers is not None or species is not None or openings is not None:
             # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
             # that are recorded, and the anisotropic sky.
             call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
@@ -1955,6 +2038,7 @@ class HeatBatch:
                 ah, hkeep = make_air_handlers(**handlers)
                 hrows = {k: np.zeros((s.n_steps if want[k] else 0, ah.n_branches if k == "branch_q" else ah.n_units))
                          for k in ("supply_t", "recovered", "coil_q", "branch_q")}
+            sp = None
             if species is not None:
                 sp, spkeep = make_air_species(**species)
                 if sp.n_species and spkeep["outdoor_chan"].shape[1] != self.n_zones:
@@ -1962,7 +2046,16 @@ class HeatBatch:
                 sprows = dict(conc_rows=np.zeros((s.n_steps if want["conc_rows"] else 0, sp.n_species, self.n_zones if sp.n_species else 0)),
                               vent_v=np.zeros((s.n_steps if want["vent_v"] else 0, sp.n_vents)),
                               vent_q=np.zeros((s.n_steps if want["vent_q"] else 0, sp.n_vents)))
-                hp = [ptr(hrows[k]) for k in ("supply_t", "recovered", "coil_q", "branch_q")] if ah is not None else [None] * 4
+            hp = [ptr(hrows[k]) for k in ("supply_t", "recovered", "coil_q", "branch_q")] if ah is not None else [None] * 4
+            if openings is not None:
+                op, opkeep = make_openings(**openings)
+                oprows = np.zeros((s.n_steps if want["opening_v"] else 0, op.n_openings))
+                spp = [ptr(sprows[k]) for k in ("conc_rows", "vent_v", "vent_q")] if sp is not None else [None] * 3
+                rc = self._L.heat_batch_march_series_openings(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
+                                                              ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
+                                                              C.byref(ah) if ah is not None else None, *hp,
+                                                              C.byref(sp) if sp is not None else None, *spp, C.byref(op), ptr(oprows))
+            elif species is not None:
                 rc = self._L.heat_batch_march_series_species(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
                                                              ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
                                                              C.byref(ah) if ah is not None else None, *hp, C.byref(sp), ptr(sprows["conc_rows"]),
@@ -2010,6 +2103,8 @@ class HeatBatch:
             out += [("handlers", dict(hrows, **{k: hkeep[k] for k in ("bypass",) + HANDLER_STATS if k in hkeep}))]
         if species is not None:
             out += [("species", dict(sprows, **{k: spkeep[k] for k in ("conc",) + SPECIES_STATS if k in spkeep}))]
+        if openings is not None:
+            out += [("openings", dict(opening_v=oprows, **{k: opkeep[k] for k in OPENING_STATS if k in opkeep}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

@@ -2331,6 +2331,114 @@ int check_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const 
     return HEAT_OK;
 }
 
+// ---- openings of a series (include/heat_amd.h, heat_openings) ----
+int check_openings(int64_t n_zones, int32_t n_channels, const heat_openings *op, std::string &err) {
+    if (!op) return HEAT_OK;
+    const int64_t n = op->n_openings;
+    if (n < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of openings (opening count n_openings %lld)", (long long)n);
+    // (the tables number the openings with 32 bits)
+    if (n > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 openings (opening count n_openings %lld)", (long long)n);
+    if (n == 0) return HEAT_OK;
+    if (!op->zone_a) return failp(err, HEAT_E_INVALID_ARG, "opening 0: zone_a is NULL");
+    if (!op->zone_b) return failp(err, HEAT_E_INVALID_ARG, "opening 0: zone_b is NULL");
+    if (!op->out_chan) return failp(err, HEAT_E_INVALID_ARG, "opening 0: out_chan is NULL");
+    if (!op->area) return failp(err, HEAT_E_INVALID_ARG, "opening 0: area is NULL");
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t za = op->zone_a[i], zb = op->zone_b[i], oc = op->out_chan[i];
+        const int32_t tc = op->temp_chan ? op->temp_chan[i] : -1, wc = op->wind_chan ? op->wind_chan[i] : -1;
+        const int32_t fc = op->frac_chan ? op->frac_chan[i] : -1;
+        if (za < 0 || za >= n_zones)
+            return failp(err, HEAT_E_SIZE, "opening %lld: zone_a %d outside [0, %lld)", (long long)i, za, (long long)n_zones);
+        if (zb < -1 || zb >= n_zones)
+            return failp(err, HEAT_E_SIZE, "opening %lld: zone_b %d outside [-1, %lld)", (long long)i, zb, (long long)n_zones);
+        if (za == zb) return failp(err, HEAT_E_INVALID_ARG, "opening %lld: zone_a and zone_b are the same zone %d", (long long)i, za);
+        if (oc < 0 || oc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "opening %lld: derived channel out_chan %d outside [0, %d)", (long long)i, oc, n_channels);
+        if (zb == -1 && (tc < 0 || tc >= n_channels))
+            return failp(err, HEAT_E_SIZE, "opening %lld: zone_b -1 (outside air) needs a temperature channel in [0, %d), not %d%s", (long long)i,
+                         n_channels, tc, op->temp_chan ? "" : " (temp_chan is NULL)");
+        if (zb >= 0 && tc != -1)
+            return failp(err, HEAT_E_SIZE, "opening %lld: it joins zone %d to zone %d and names temperature channel %d: a side has one temperature",
+                         (long long)i, za, zb, tc);
+        if (wc < -1 || wc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "opening %lld: wind channel %d outside [-1, %d)", (long long)i, wc, n_channels);
+        if (fc < -1 || fc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "opening %lld: open-fraction channel %d outside [-1, %d)", (long long)i, fc, n_channels);
+        const double *const coef[5] = {op->area, op->cw, op->cs, op->ca, op->c0};
+        static const char *const name[5] = {"area", "cw", "cs", "ca", "c0"};
+        for (int a = 0; a < 5; a++)
+            if (coef[a] && (!std::isfinite(coef[a][i]) || coef[a][i] < 0.0))
+                return failp(err, HEAT_E_INVALID_ARG, "opening %lld: %s %g is negative or not finite", (long long)i, name[a], coef[a][i]);
+    }
+    // a derived channel has one writer, and feeds consumers: never another opening (nor its own)
+    std::vector<int32_t> writer((size_t)n_channels, -1);
+    for (int64_t i = 0; i < n; i++) {
+        int32_t &w = writer[(size_t)op->out_chan[i]];
+        if (w >= 0)
+            return failp(err, HEAT_E_SIZE, "opening %lld: its derived channel out_chan %d is also opening %d's: a derived channel has one writer",
+                         (long long)i, op->out_chan[i], w);
+        w = (int32_t)i;
+    }
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t *const read[3] = {op->temp_chan, op->wind_chan, op->frac_chan};
+        static const char *const name[3] = {"temp_chan", "wind_chan", "frac_chan"};
+        for (int a = 0; a < 3; a++) {
+            const int32_t ch = read[a] ? read[a][i] : -1;
+            if (ch >= 0 && writer[(size_t)ch] >= 0)
+                return failp(err, HEAT_E_SIZE, "opening %lld: its %s %d is the derived channel of opening %d: a derived channel feeds consumers, never an opening",
+                             (long long)i, name[a], ch, writer[(size_t)ch]);
+        }
+    }
+    return HEAT_OK;
+}
+
+void build_opening_tables(const heat_openings *op, OpeningTables &t) {
+    const size_t n = op ? (size_t)op->n_openings : 0;
+    t = OpeningTables();
+    t.n_openings = (int64_t)n;
+    t.i32.assign((size_t)kOpeningI32Rows * n, -1);
+    t.f64.assign((size_t)kOpeningF64Rows * n, 0.0);
+    if (n == 0) return;
+    const int32_t *const src_i32[kOpeningI32Rows] = {op->zone_a, op->zone_b, op->temp_chan, op->wind_chan, op->frac_chan, op->out_chan};
+    const double *const src_f64[kOpeningF64Rows] = {op->area, op->cw, op->cs, op->ca, op->c0};
+    for (int a = 0; a < kOpeningI32Rows; a++)
+        if (src_i32[a]) std::copy(src_i32[a], src_i32[a] + n, t.i32.begin() + (size_t)a * n);
+    for (int a = 0; a < kOpeningF64Rows; a++)
+        if (src_f64[a]) std::copy(src_f64[a], src_f64[a] + n, t.f64.begin() + (size_t)a * n);
+}
+
+int check_opening_tables(int64_t n_zones, int32_t n_channels, const heat_openings *op, const OpeningTables &t, std::string &err) {
+    const size_t n = op ? (size_t)op->n_openings : 0;
+    if (t.n_openings != (int64_t)n || t.i32.size() != (size_t)kOpeningI32Rows * n || t.f64.size() != (size_t)kOpeningF64Rows * n)
+        return failp(err, HEAT_E_SIZE, "opening tables: %zu integers and %zu reals for %zu openings", t.i32.size(), t.f64.size(), n);
+    if (n == 0) return HEAT_OK;
+    const int32_t *const src_i32[kOpeningI32Rows] = {op->zone_a, op->zone_b, op->temp_chan, op->wind_chan, op->frac_chan, op->out_chan};
+    const double *const src_f64[kOpeningF64Rows] = {op->area, op->cw, op->cs, op->ca, op->c0};
+    std::vector<uint8_t> written((size_t)n_channels, 0);
+    for (size_t i = 0; i < n; i++) {
+        // every row the caller's ...
+        for (int a = 0; a < kOpeningI32Rows; a++)
+            if (t.list(a)[i] != (src_i32[a] ? src_i32[a][i] : -1))
+                return failp(err, HEAT_E_SIZE, "opening tables: opening %zu: integer row %d is not the caller's", i, a);
+        for (int a = 0; a < kOpeningF64Rows; a++) {
+            const double want = src_f64[a] ? src_f64[a][i] : 0.0;
+            if (std::memcmp(&t.real(a)[i], &want, sizeof(double)) != 0)
+                return failp(err, HEAT_E_SIZE, "opening tables: opening %zu: real row %d is not the caller's", i, a);
+        }
+        // ... and everything the lane indexes with inside its array
+        const int32_t za = t.list(OP_ZONE_A)[i], zb = t.list(OP_ZONE_B)[i], tc = t.list(OP_TEMP_CHAN)[i], oc = t.list(OP_OUT_CHAN)[i];
+        if (za < 0 || za >= n_zones || zb >= n_zones || (zb < 0 && (tc < 0 || tc >= n_channels)) || oc < 0 || oc >= n_channels ||
+            t.list(OP_WIND_CHAN)[i] >= n_channels || t.list(OP_FRAC_CHAN)[i] >= n_channels)
+            return failp(err, HEAT_E_SIZE, "opening tables: opening %zu: a zone or channel lies outside its array", i);
+        if (written[(size_t)oc]++) return failp(err, HEAT_E_SIZE, "opening tables: opening %zu: derived channel %d has two writers", i, oc);
+    }
+    for (size_t i = 0; i < n; i++)
+        for (int a : {OP_TEMP_CHAN, OP_WIND_CHAN, OP_FRAC_CHAN})
+            if (t.list(a)[i] >= 0 && written[(size_t)t.list(a)[i]])
+                return failp(err, HEAT_E_SIZE, "opening tables: opening %zu: it reads derived channel %d", i, t.list(a)[i]);
+    return HEAT_OK;
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -3539,6 +3647,20 @@ int heat_air_species_check(const heat_batch_desc *desc, const heat_series *s, co
     heat::SpeciesTables t;
     heat::build_air_species_tables(desc->n_zones, h, sp, t);
     return heat::check_air_species_tables(desc->n_zones, h, sp, t, heat::last_error());
+}
+
+int heat_openings_check(const heat_batch_desc *desc, const heat_series *s, const heat_openings *op) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    rc = heat::check_openings(desc->n_zones, s->n_channels, op, heat::last_error());
+    if (rc || !op) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the
+    // sanitizers see)
+    heat::OpeningTables t;
+    heat::build_opening_tables(op, t);
+    return heat::check_opening_tables(desc->n_zones, s->n_channels, op, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

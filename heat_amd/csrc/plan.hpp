@@ -257,6 +257,27 @@ void build_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const
 int check_air_species_tables(int64_t n_zones, const heat_air_handlers *h, const heat_air_species *sp, const SpeciesTables &t,
                              std::string &err);
 
+// Openings of a series (heat_openings, include/heat_amd.h). Everything heat_openings_check promises about the term itself;
+// op == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "opening i".
+int check_openings(int64_t n_zones, int32_t n_channels, const heat_openings *op, std::string &err);
+// The tables of k_series_openings (one lane per opening, the caller's order), packed into one int32 and one f64 buffer (one
+// upload each). A NULL channel list is -1 here, a NULL coefficient list zeros.
+enum OpeningI32 : int { OP_ZONE_A, OP_ZONE_B, OP_TEMP_CHAN, OP_WIND_CHAN, OP_FRAC_CHAN, OP_OUT_CHAN, kOpeningI32Rows };
+enum OpeningF64 : int { OP_AREA, OP_CW, OP_CS, OP_CA, OP_C0, kOpeningF64Rows };
+struct OpeningTables {
+    int64_t n_openings = 0;
+    std::vector<int32_t> i32;  // [kOpeningI32Rows][n]
+    std::vector<double> f64;   // [kOpeningF64Rows][n]
+    const int32_t *list(int a) const { return i32.data() + a * n_openings; }
+    const double *real(int a) const { return f64.data() + a * n_openings; }
+};
+// (of a term that passed check_openings)
+void build_opening_tables(const heat_openings *op, OpeningTables &t);
+// The tables against the caller's lists (used by the host-only check): every row the caller's, bit for bit, every zone and
+// channel a lane would index inside [0, n_zones) / [0, n_channels), and every derived channel written by one opening and read
+// by none. HEAT_OK or HEAT_E_SIZE.
+int check_opening_tables(int64_t n_zones, int32_t n_channels, const heat_openings *op, const OpeningTables &t, std::string &err);
+
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
 // themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".
 // load_of_zone (nullable): [n_zones], the load of every zone or -1 — the table k_zone_update_ideal looks its zone up in.

@@ -859,6 +859,49 @@ struct SpeciesTerm {
     }
 };
 
+// The openings (heat_openings): the tables in the caller's order (plan.hpp, OpeningTables), the accumulators (uploaded on
+// resume, else started on the device) and the opening_v rows. Nothing of it exists on the device without openings.
+struct OpeningsTerm {
+    heat_openings *op = nullptr;
+    int64_t NO = 0;
+    OpeningTables opt;
+    DevBuf<int32_t> i32;          // [kOpeningI32Rows][NO]
+    DevBuf<double> f64, v;        // [kOpeningF64Rows][NO]; v: [n_steps][NO]
+    Acc<double> acc_f64[2];       // sum_v, max_v
+    Acc<int64_t> step_max;
+    OpeningsDev view{};
+    void prepare(heat_openings *op_) {
+        op = op_;
+        NO = op ? op->n_openings : 0;
+        if (NO == 0) return;
+        build_opening_tables(op, opt);
+        acc_f64[0].bind(op->sum_v, 0.0, &view.sum_v), acc_f64[1].bind(op->max_v, -std::numeric_limits<double>::infinity(), &view.max_v);
+        step_max.bind(op->step_max, -1, &view.step_max);
+    }
+    int upload(const double *host_v, int n_steps) {
+        if (NO == 0) return HEAT_OK;
+        const bool resume = op->resume != 0;
+        SERIES_TRY(series_upload(i32, opt.i32, "opening tables"));
+        SERIES_TRY(series_upload(f64, opt.f64, "opening tables"));
+        for (auto &a : acc_f64) SERIES_TRY(a.stage((size_t)NO, resume, "opening accumulators"));
+        SERIES_TRY(step_max.stage((size_t)NO, resume, "opening accumulators"));
+        if (host_v) SERIES_TRY(series_alloc(v, (size_t)n_steps * NO, "opening volume flows"));
+        view.n_openings = (int)NO;
+        view.zone_a = i32.p + OP_ZONE_A * NO, view.zone_b = i32.p + OP_ZONE_B * NO, view.temp_chan = i32.p + OP_TEMP_CHAN * NO;
+        view.wind_chan = i32.p + OP_WIND_CHAN * NO, view.frac_chan = i32.p + OP_FRAC_CHAN * NO, view.out_chan = i32.p + OP_OUT_CHAN * NO;
+        view.area = f64.p + OP_AREA * NO, view.cw = f64.p + OP_CW * NO, view.cs = f64.p + OP_CS * NO, view.ca = f64.p + OP_CA * NO;
+        view.c0 = f64.p + OP_C0 * NO;
+        return HEAT_OK;
+    }
+    hipError_t start(hipStream_t st) {
+        return NO > 0 && op->resume == 0 ? step_max.start(st, for_each_acc(acc_f64, &Acc<double>::start, st)) : hipSuccess;
+    }
+    hipError_t fetch(double *host_v, hipStream_t st) {
+        if (NO == 0) return hipSuccess;
+        return step_max.fetch(st, for_each_acc(acc_f64, &Acc<double>::fetch, st, series_fetch(host_v, v, st)));
+    }
+};
+
 // The anisotropic sky (heat_sky_aniso): the coefficient table as given, beside the record table, and the bands of the three
 // consumers — the sides' per DEVICE surface, the apertures' and the shades' in the caller's order as their tables are; zeros
 // where the caller gave none. Absent (every pointer NULL) without aniso: the isotropic kernels are launched.
@@ -951,7 +994,8 @@ struct ComfortTerm {
 
 // What heat_batch_march_series_call takes (the eleven positional entry points fill what they have) and, beside it, the comfort
 // term and its two arrays of rows (heat_batch_march_series_comfort), the air handlers with their four
-// (heat_batch_march_series_handlers) and the air species with their three (heat_batch_march_series_species); filled by field name. no_trace_ok: a NULL trace records none.
+// (heat_batch_march_series_handlers), the air species with their three (heat_batch_march_series_species) and the openings with
+// their one (heat_batch_march_series_openings); filled by field name. no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
@@ -975,6 +1019,8 @@ struct SeriesCall {
     double *supply_t = nullptr, *recovered = nullptr, *coil_q = nullptr, *branch_q = nullptr;
     heat_air_species *species = nullptr;
     double *conc_rows = nullptr, *vent_v = nullptr, *vent_q = nullptr;
+    heat_openings *openings = nullptr;
+    double *opening_v = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -1019,6 +1065,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = check_comfort(b->n_surf, b->n_zones, s, c.comfort, heat::last_error()))) return rc;
     if ((rc = check_air_handlers(b->n_zones, s->n_channels, c.handlers, heat::last_error()))) return rc;
     if ((rc = check_air_species(b->n_zones, s->n_channels, c.species, heat::last_error()))) return rc;
+    if ((rc = check_openings(b->n_zones, s->n_channels, c.openings, heat::last_error()))) return rc;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -1048,6 +1095,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     ComfortTerm comfort;
     HandlersTerm handlers;
     SpeciesTerm species;
+    OpeningsTerm openings;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
@@ -1064,8 +1112,10 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     comfort.prepare(b, c.comfort);
     handlers.prepare(b, c.handlers);
     species.prepare(b, c.handlers, c.species);
+    openings.prepare(c.openings);
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
     const int64_t NL = blinds.NL, NF = comfort.NF, NU = handlers.NU, NBR = handlers.NBR, NSP = species.NSP, NV = species.NV;
+    const int64_t NO = openings.NO;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -1086,17 +1136,21 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = comfort.upload(b, c.operative, c.mrt, n_steps))) return rc;
     if ((rc = handlers.upload(c.supply_t, c.recovered, c.coil_q, c.branch_q, n_steps))) return rc;
     if ((rc = species.upload(c.conc_rows, c.vent_v, c.vent_q, n_steps))) return rc;
+    if ((rc = openings.upload(c.opening_v, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
     HIP_TRY(report.start(b->stream));
     HIP_TRY(ideal.start(b->stream));
     HIP_TRY(comfort.start(b->stream));
     HIP_TRY(species.start(b->stream));
+    HIP_TRY(openings.start(b->stream));
     // what the thermostats, the air paths' e and the blinds sense: the zone temperatures, or with a control sensor the step's Tc
     const double *control_T = comfort.control_T.p ? comfort.control_T.p : b->d_zone_T.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    // ---- the steps, enqueued without waiting: head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> air species -> ambient drive ->
+    // ---- the steps, enqueued without waiting: openings (the one writer of the step's row of d_channel; everything behind reads it, and
+    // a captured graph holds the body of the march only, which reads no channel) -> head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> air species -> ambient drive ->
     // driven inputs -> shades -> blinds -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
+        if (NO > 0) launch_series_openings(openings.view, row(d_channel, k, NC), b->d_zone_T.p, row(openings.v, k, NO), c.openings->step_base + k, b->stream);
         const double *channel = row(d_channel, k, NC);
         const SkyRecord *record = row(sky.record, k, n_sites);
         const SkyCoef *coef = row(aniso.coef, k, n_sites);  // (nullptr without aniso: the isotropic kernels)
@@ -1181,6 +1235,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(comfort.fetch(c.operative, c.mrt, b->stream));
     HIP_TRY(handlers.fetch(c.supply_t, c.recovered, c.coil_q, c.branch_q, b->stream));
     HIP_TRY(species.fetch(c.conc_rows, c.vent_v, c.vent_q, b->stream));
+    HIP_TRY(openings.fetch(c.opening_v, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -1284,9 +1339,9 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
     return march_series_impl(b, c);
 }
 
-// heat_batch_march_series_call, heat_batch_march_series_comfort, heat_batch_march_series_handlers and
-// heat_batch_march_series_species: the struct's fields by name, then the comfort term, then the air handlers and the air species
-// (`more`: what the last two add, or nullptr).
+// heat_batch_march_series_call, heat_batch_march_series_comfort, heat_batch_march_series_handlers,
+// heat_batch_march_series_species and heat_batch_march_series_openings: the struct's fields by name, then the comfort term, then
+// the air handlers, the air species and the openings (`more`: what the last three add, or nullptr).
 static int march_series_call(heat_batch *b, const heat_series_call *call, heat_comfort *comfort, double *operative, double *mrt,
                              const SeriesCall *more = nullptr) {
     if (const int rc = check_series_call(call, heat::last_error())) return rc;  // (a struct of another size is not read further)
@@ -1317,6 +1372,15 @@ int heat_batch_march_series_species(heat_batch *b, const heat_series_call *call,
                                     heat_air_species *sp, double *conc_rows, double *vent_v, double *vent_q) {
     SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
     more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q;
+    return march_series_call(b, call, c, operative, mrt, &more);
+}
+
+int heat_batch_march_series_openings(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt,
+                                     heat_air_handlers *h, double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                     heat_air_species *sp, double *conc_rows, double *vent_v, double *vent_q, heat_openings *op,
+                                     double *opening_v) {
+    SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
+    more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q, more.openings = op, more.opening_v = opening_v;
     return march_series_call(b, call, c, operative, mrt, &more);
 }
 

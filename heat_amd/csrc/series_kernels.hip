@@ -1139,6 +1139,65 @@ k_series_species(int n_zones, SpeciesDev sp, SpeciesInflows in, const double *__
     if (sp.excess_above != nullptr) sp.excess_above[lane] = sp.excess_above[lane] + (c - limit);
 }
 
+// sqrt, correctly rounded: the one rounded operation of the openings' rule that is not an add, a multiply or a divide, and the
+// only sqrt of the series layer. It may be relied on because of how f64 sqrt lowers for gfx950 at the project's flags (-O3, no
+// fast-math): v_rsq_f64 as the seed, a Goldschmidt refinement of s ~ sqrt(x) and h ~ 1 / (2 sqrt(x)), then two residual
+// corrections d = fma(-s, s, x), s = fma(d, h, s) — the residual is exact in the fma, which is what lets the last step round
+// correctly — with small inputs (subnormals among them) scaled up by v_ldexp_f64 first and the result scaled back, and 0 and
+// +inf passed through by a class test. tests/test_openings_gpu.py holds it to numpy.sqrt bit for bit over squares and their
+// neighbours, 4^n and 2 4^n +- 1 ulp, subnormals and both ends of the range. Named, so that a compiler whose lowering differs
+// shows up in one place. (Here and not in device_math.hpp: the march does not call it.)
+__device__ __forceinline__ double sqrt_rn(double x) { return sqrt(x); }
+
+// k_series_openings — the openings of one step (heat_openings, include/heat_amd.h), the FIRST kernel of the step: one lane per
+// opening over structure-of-arrays tables in the caller's order (plan.hpp, OpeningTables). A lane gathers its two
+// temperatures from zone_T — which nothing on the step's head writes: every zone is read as it was at the start of the step
+// — or one of them from the row, up to two more values from the row, forms V by the header's rule, every line one rounded
+// operation in the order written, hence no contraction, and stores V into the row at its DERIVED channel: a plain 8-byte
+// store. The check has made sure that no two openings share an out_chan and that no out_chan is a channel any opening reads,
+// so every element of the row has one writer and no lane reads what another writes, whatever the order of the lanes; the
+// kernels that read the derived columns are launched behind this one on the same stream. The absent outputs are
+// wave-uniform branches. No LDS, no atomics, no scratch.
+__global__ void __launch_bounds__(256)
+k_series_openings(OpeningsDev op, double *row, const double *__restrict__ zone_T, double *__restrict__ v_row, int64_t step) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= op.n_openings) return;
+    const int zb = op.zone_b[i];
+    const double Ta = zone_T[op.zone_a[i]];
+    const double Tb = zb >= 0 ? zone_T[zb] : row[op.temp_chan[i]];
+    const double d = Ta - Tb;
+    const double ad = fabs(d);
+    const double sm = Ta + Tb;
+    const double tm = sm * 0.5;
+    const double tk = tm + 273.15;
+    const double r = ad / tk;
+    const double st = op.cs[i] * r;
+    const double sa = op.ca[i] * ad;
+    const int wc = op.wind_chan[i];
+    const double u = wc >= 0 ? row[wc] : 0.0;
+    const double u2 = u * u;
+    const double w = op.cw[i] * u2;
+    const double x = w + st;
+    const double x2 = x + sa;
+    double y = x2 + op.c0[i];
+    if (y < 0.0) y = 0.0;
+    const double U = sqrt_rn(y);
+    const int fc = op.frac_chan[i];
+    double f = fc >= 0 ? row[fc] : 1.0;
+    if (f < 0.0) f = 0.0;
+    if (f > 1.0) f = 1.0;
+    const double af = op.area[i] * f;
+    const double V = af * U;
+    row[op.out_chan[i]] = V;
+    if (v_row != nullptr) v_row[i] = V;
+    if (op.sum_v != nullptr) op.sum_v[i] = op.sum_v[i] + V;
+    if (op.max_v != nullptr && V > op.max_v[i]) {
+        op.max_v[i] = V;
+        if (op.step_max != nullptr) op.step_max[i] = step;
+    }
+}
+
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = value;
@@ -1328,6 +1387,11 @@ void launch_series_species(int n_zones, const SpeciesDev &sp, const ZoneLoadsDev
     if (hd) in.br_off = hd->zone_off, in.br_orig = hd->z_orig;
     hipLaunchKernelGGL(k_series_species, dim3((unsigned int)((lanes + 255) / 256)), dim3(256), 0, st, n_zones, sp, in, row, zone_vol, h, conc,
                        conc_next, conc_row, step);
+}
+
+void launch_series_openings(const OpeningsDev &op, double *row, const double *zone_T, double *v_row, int64_t step, hipStream_t st) {
+    if (op.n_openings <= 0) return;
+    hipLaunchKernelGGL(k_series_openings, dim3((op.n_openings + 255) / 256), dim3(256), 0, st, op, row, zone_T, v_row, step);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

@@ -306,6 +306,19 @@ void launch_series_vents(int n_zones, const SpeciesDev &sp, const double *row, c
 void launch_series_species(int n_zones, const SpeciesDev &sp, const ZoneLoadsDev *zl, const AirPathsDev *ap, const HandlersDev *hd,
                            const double *row, const double *zone_vol, double h, const double *conc, double *conc_next, double *conc_row,
                            int64_t step, hipStream_t st);
+// Openings of a series step (heat_openings, include/heat_amd.h; tables: plan.hpp, OpeningTables): the FIRST launch of a step,
+// ahead of launch_series_comfort, only when there are openings, one lane per opening in the caller's order. It is the one
+// launch that WRITES the step's row of the device's channel table: every later launch of the step reads the derived columns
+// as it reads any channel.
+struct OpeningsDev {
+    int n_openings;
+    const int32_t *zone_a, *zone_b, *temp_chan, *wind_chan, *frac_chan, *out_chan;   // [n] each; channels -1: none
+    const double *area, *cw, *cs, *ca, *c0;                                           // [n] each
+    double *sum_v, *max_v;                                                            // [n] each, nullptr: not maintained
+    int64_t *step_max;
+};
+// row: the step's row of the channel table, written at out_chan; v_row: the step's row of opening_v, or nullptr; step: K
+void launch_series_openings(const OpeningsDev &op, double *row, const double *zone_T, double *v_row, int64_t step, hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 // Ideal loads of a series: the step's begin and end (the sequence and the view: kernels.hpp, IdealLoadsDev)
 void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipStream_t st);

@@ -1383,6 +1383,79 @@ int heat_batch_march_series_species(heat_batch *b, const heat_series_call *call,
                                     double *vent_v    /* [n_steps][n_vents], nullable */,
                                     double *vent_q    /* [n_steps][n_vents], nullable */);
 
+/*
+ * Openings of a series: the volume flow that wind and buoyancy drive through an open window, a doorway or a vent, as a
+ * DERIVED CHANNEL. Every flow of air of a series takes its volume from a channel, and a channel is a schedule; the flow
+ * through an opening depends on |Ta - Tb| between two zones, or a zone and outside, at the start of the step — temperatures
+ * only the device holds. An opening therefore WRITES its volume flow into one column of the step's row in the device's copy
+ * of the channel table, and every consumer reads that column as it reads any channel, through its volume channel: the air
+ * paths (volume_gain * row[volume_chan]), the zone loads' flows (wind- and stack-driven infiltration), the handlers' branches
+ * and, through the same tables, the species. No struct and no kernel of those terms changes. The reference has no
+ * counterpart (model.rs:546,592-593 take infiltration and mixing volumes as given numbers); the rule below is this library's
+ * own contract, defined against the per-call loop with the same rule written on the host (heat_amd/openings.py, apply()).
+ * Each opening is an explicit formula, the superposition form of EnergyPlus' wind-and-stack open area and of de Gids-Phaff.
+ * The rule of step k. The openings are the FIRST kernel of the step, ahead of the comfort term: nothing of the step has
+ * read the row yet. T = the zone AIR temperatures the device holds when the step starts, row = the device's channel[k],
+ * K = step_base + k. Every line is ONE rounded f64 operation in the order written, no fused multiply-add; a NaN makes every
+ * comparison false:
+ *   per opening i:
+ *     Ta = T[zone_a];  Tb = zone_b >= 0 ? T[zone_b] : row[temp_chan]
+ *     d = Ta - Tb;  ad = |d|            (sign bit cleared)
+ *     sm = Ta + Tb;  tm = sm * 0.5;  tk = tm + 273.15
+ *     r = ad / tk;  st = cs * r;  sa = ca * ad
+ *     u = wind_chan >= 0 ? row[wind_chan] : 0.0;  u2 = u * u;  w = cw * u2
+ *     x = w + st;  x2 = x + sa;  y = x2 + c0
+ *     if y < 0.0: y = 0.0
+ *     U = sqrt(y)                        (correctly rounded)
+ *     f = frac_chan >= 0 ? row[frac_chan] : 1.0;  if f < 0.0: f = 0.0;  if f > 1.0: f = 1.0
+ *     af = area * f;  V = af * U
+ *     row[out_chan] = V;  opening_v[k][i] = V;  sum_v = sum_v + V;  if V > max_v { max_v = V; step_max = K }
+ * V is symmetric in a and b (both |Ta - Tb| and Ta + Tb are): a doorway is ONE opening whose channel both of its air paths
+ * read. V is the flow the opening WOULD carry: whether a controlled path is open remains that path's decision, and path_q
+ * shows what actually moved. The caller's host channel array is never written; a derived column's host values are ignored.
+ * resume == 0 initialises the accumulators on the device (sums 0, max_v = -inf, step_max = -1); a series of k steps followed
+ * by one of n - k with the returned arrays and step_base + k gives the bits of the series of n. n_sub == 0 still evaluates
+ * every step. A NaN V is data here: it becomes HEAT_N_NAN_ZONE where a consumer adds it to a zone, as today. An array that is
+ * not asked for costs no traffic and changes no bit of the others. With op == NULL or n_openings == 0
+ * heat_batch_march_series_openings is heat_batch_march_series_species exactly: same launches, same bits. A refused call
+ * leaves the device state untouched. Sharded batches are refused as by the series.
+ * heat_openings_check (host-only; it also builds and verifies the tables the march uploads) and
+ * heat_batch_march_series_openings run the same checks before any device work; every message names "opening i".
+ * HEAT_E_INVALID_ARG: a negative count; a NULL array that a positive count needs (zone_a, zone_b, out_chan, area);
+ * zone_a == zone_b; an area or coefficient that is not finite or is negative. HEAT_E_SIZE: a zone out of range (zone_b in
+ * [-1, n_zones)); a channel out of range (wind_chan and frac_chan may be -1); zone_b == -1 without a temperature channel; a
+ * temperature channel on a zone-to-zone opening; two openings with the same out_chan; an out_chan that is also some
+ * opening's temp_chan, wind_chan or frac_chan — a derived channel feeds consumers and never another opening.
+ * Out of scope: a pressure network or mass balance across several openings, two-way flow with a neutral plane resolved over
+ * the opening height, wind pressure coefficients from direction, density of moist air, and the opening's own effect on
+ * convection coefficients.
+ */
+typedef struct heat_openings {
+    int64_t n_openings;
+    const int32_t *zone_a;              /* [n] a zone */
+    const int32_t *zone_b;              /* [n] a zone, or -1: outside air at row[temp_chan] */
+    const int32_t *temp_chan;           /* [n] nullable when no zone_b is -1; must be -1 where zone_b >= 0 */
+    const int32_t *wind_chan;           /* [n] nullable / -1: no wind term; else the effective wind speed at the opening, m/s */
+    const int32_t *frac_chan;           /* [n] nullable / -1: fully open; else the open fraction, clamped to [0, 1] */
+    const int32_t *out_chan;            /* [n] the DERIVED channel this opening writes, m3/s */
+    const double  *area;                /* [n] m2 (discharge coefficient folded in), finite, >= 0 */
+    const double  *cw, *cs, *ca, *c0;   /* [n] each nullable = 0; finite, >= 0 */
+    int64_t resume;                     /* as heat_air_species::resume, for the three accumulators below */
+    int64_t step_base;                  /* K = step_base + k is what step_max records */
+    /* accumulators, [n] each, in/out, nullable */
+    double  *sum_v;
+    double  *max_v;
+    int64_t *step_max;                  /* kept where max_v is: it records the step of that maximum */
+} heat_openings;
+
+int heat_openings_check(const heat_batch_desc *desc, const heat_series *s, const heat_openings *op /* nullable */); /* host-only */
+int heat_batch_march_series_openings(heat_batch *b, const heat_series_call *call, heat_comfort *c /* nullable */,
+                                     double *operative, double *mrt, heat_air_handlers *h /* nullable */,
+                                     double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                     heat_air_species *sp /* nullable */, double *conc_rows, double *vent_v, double *vent_q,
+                                     heat_openings *op /* nullable */,
+                                     double *opening_v /* [n_steps][n_openings], nullable */);
+
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the
  * descriptor — or the zone's, when *kind == HEAT_N_NAN_ZONE found by the zone balance itself (the cluster-resident

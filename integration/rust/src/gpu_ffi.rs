@@ -135,6 +135,13 @@ pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
     pub conc: *mut f64, pub n_occupied: *mut i64, pub sum_conc: *mut f64, pub max_conc: *mut f64, pub step_max: *mut i64,
     pub n_above: *mut i64, pub excess_above: *mut f64, pub sum_volume: *mut f64, pub sum_q: *mut f64, pub steps_saturated: *mut i64,
 }
+// heat_openings: wind- and stack-driven volume flows through openings, written into derived channels of the device's table
+#[repr(C)] pub struct HeatOpenings {
+    pub n_openings: i64, pub zone_a: *const i32, pub zone_b: *const i32, pub temp_chan: *const i32, pub wind_chan: *const i32,
+    pub frac_chan: *const i32, pub out_chan: *const i32, pub area: *const f64, pub cw: *const f64, pub cs: *const f64,
+    pub ca: *const f64, pub c0: *const f64, pub resume: i64, pub step_base: i64,
+    pub sum_v: *mut f64, pub max_v: *mut f64, pub step_max: *mut i64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -241,6 +248,13 @@ extern "C" {
                                            operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
                                            recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64, sp: *mut HeatAirSpecies,
                                            conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64) -> c_int;
+    // openings of a series: volume flows from the zone temperatures the device holds, read by every consumer as a channel
+    pub fn heat_openings_check(desc: *const HeatBatchDesc, s: *const HeatSeries, op: *const HeatOpenings) -> c_int;
+    pub fn heat_batch_march_series_openings(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
+                                            operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
+                                            recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64, sp: *mut HeatAirSpecies,
+                                            conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64, op: *mut HeatOpenings,
+                                            opening_v: *mut f64) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

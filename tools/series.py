@@ -120,8 +120,18 @@ and writes profiles/series_species.json: ms per step of each, P - N, a series of
 per-step times once the set-up is taken off — and, where a kernel trace of one P series has been taken (--one-series --species
 under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_species_kernel_stats.csv), k_series_vents and
 k_series_species per step. No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species]
+With --openings (heat_batch_march_series_openings, heat_openings; the loads, handlers and species of --species, plus per zone one
+opening to outside that feeds a CONTROLLED supply path — a night-ventilation window — and per pair of neighbouring zones one
+doorway opening that feeds the two paths of air_paths.doorway) it alternates
+  C  the series with openings = NULL and the SAME flows precomputed into ordinary channels: the opening_v rows of one O series,
+     written into the columns the paths read (the march then computes the same bits: the tool asserts equal traces)
+  O  the same call with the openings, the derived columns of the host table NaN
+and writes profiles/series_openings.json: ms per step of each, O - C, a series of ONE step of each (the call's set-up) and the
+per-step times once the set-up is taken off — and, where a kernel trace of one O series has been taken (--one-series --openings
+under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_openings_kernel_stats.csv), k_series_openings per step.
+No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species | --openings]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species | --openings]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
@@ -132,7 +142,7 @@ k_series_species per step. No time is a pass criterion.
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, openings as opm, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -145,7 +155,8 @@ SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
 COMFORT = "--comfort" in sys.argv
-SPECIES = "--species" in sys.argv
+OPENINGS = "--openings" in sys.argv
+SPECIES = "--species" in sys.argv or OPENINGS
 HANDLERS = "--handlers" in sys.argv or SPECIES
 LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT or COMFORT or HANDLERS
 OUT = next((a[6:] for a in sys.argv[1:] if a.startswith("--out=")), None)
@@ -350,6 +361,44 @@ if SPECIES:
         assert out[1] == -1 and np.all(np.isfinite(out[0]))
         assert species == {} or (np.all(np.isfinite(out[5]["conc"])) and out[5]["sum_volume"].any())
         return dt * 1e3 / steps
+if OPENINGS:
+    # three more channels (the wind speed at the openings, an open fraction that leaves [0, 1] at times, the windows' setpoint)
+    # and the derived columns: per zone one opening to outside air at the handlers' outdoor temperature (wind and stack, or
+    # single-sided, in turn) feeding a controlled supply path of that zone, per pair of zones (2j, 2j + 1) one doorway
+    c_op = channel.shape[1]
+    n_door = Z // 2
+    NO = Z + n_door
+    channel = np.concatenate([channel, rng.uniform(0.2, 6.0, (STEPS, 1)), rng.uniform(-0.2, 1.3, (STEPS, 1)), rng.uniform(18.0, 24.0, (STEPS, 1)),
+                              np.full((STEPS, NO), np.nan)], axis=1)
+    c_der = c_op + 3
+    area = rng.uniform(0.02, 0.08, Z)
+    ws, ss = opm.wind_and_stack(area, 0.6, rng.uniform(0.25, 0.6, Z), rng.uniform(0.3, 1.2, Z)), opm.single_sided(area, rng.uniform(0.8, 1.6, Z))
+    single = np.arange(Z) % 2 == 1
+    dw = opm.doorway(rng.uniform(0.7, 1.0, n_door), rng.uniform(1.9, 2.2, n_door), 0.6)
+    opening_args = opm.concat(
+        dict(zone_a=every, zone_b=np.full(Z, -1), temp_chan=np.full(Z, c_ah), wind_chan=np.full(Z, c_op), frac_chan=np.full(Z, c_op + 1),
+             area=np.where(single, ss["area"], ws["area"]), cw=np.where(single, ss["cw"], ws["cw"]), cs=np.where(single, 0.0, ws["cs"]),
+             ca=np.where(single, ss["ca"], 0.0), c0=np.where(single, ss["c0"], 0.0)),
+        dict(zone_a=2 * np.arange(n_door), zone_b=2 * np.arange(n_door) + 1, area=0.1 * dw["area"], cs=dw["cs"], c0=np.full(n_door, 0.01)))
+    opening_args["out_chan"] = (c_der + np.arange(NO)).astype(np.int32)
+    air_args = apm.concat(dict(target=every, source=np.full(Z, -1), temp_chan=np.full(Z, c_ah), volume_chan=c_der + np.arange(Z),
+                               open_chan=np.full(Z, c_op + 2), sense=np.ones(Z, np.int8), band=np.full(Z, 0.5), min_delta=np.full(Z, 0.5)),
+                          apm.doorway(2 * np.arange(n_door), 2 * np.arange(n_door) + 1, c_der + Z + np.arange(n_door)))
+    # per opening: six integers, five reals, two gathered temperatures, up to three values of the row, V into the row, and the three
+    # accumulators read and written
+    OPENING_BYTES = dict(k_series_openings_per_opening=6 * 4 + 5 * 8 + 2 * 8 + 3 * 8 + 8 + 3 * 16)
+
+    def leg_op(b, w, n_sub, steps, openings="given", table=None, rows=False):
+        table = channel if table is None else table
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=table[:steps], probes=probes, loads=loads, air=air_args, path_q=False, handlers=handler_args,
+                             supply_t=False, recovered=False, coil_q=False, branch_q=False, species=species_args, conc_rows=False, vent_v=False,
+                             vent_q=False, openings=opening_args if openings == "given" else openings, opening_v=rows, **drives)
+        dt = time.perf_counter() - t0
+        assert out[1] == -1 and np.all(np.isfinite(out[0])) and np.all(np.isfinite(out[6]["conc"]))
+        assert openings is None or (np.all(np.isfinite(out[7]["sum_v"])) and out[7]["sum_v"].any())
+        return (dt * 1e3 / steps, out) if rows else dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
     exchange = rrm.exchange_by_area(md)
@@ -628,6 +677,38 @@ with HeatBatch(md) as b:
             print("n_sub %2d: N comfort NULL %.3f ms/step, C comfort %.3f -> C - N = %+.3f ms, C / N = %.4f; a series of one step: "
                   "N %.2f ms, C %.2f ms -> per step without the set-up N %.3f, C %.3f, C - N = %+.3f (%d sensors, %d entries, %d steps, "
                   "median of %d rounds)" % (n_sub, N_, C_, C_ - N_, C_ / N_, N1, C1, Ns, Cs, Cs - Ns, Z, NE, STEPS, ROUNDS), flush=True)
+            continue
+        if OPENINGS:
+            # the flows of one O series into ordinary channels: leg C's table (the state is uploaded anew before every series
+            # of this mode, so that C and O march the same steps from the same start)
+            def fresh(leg, *a, **kw):
+                b.upload_state(state)
+                return leg(b, w, n_sub, *a, **kw)
+            _, first = fresh(leg_op, STEPS, rows=True)  # (warm-up as well)
+            precomputed = channel.copy()
+            precomputed[:, opening_args["out_chan"]] = first[7]["opening_v"]
+            _, same = fresh(leg_op, STEPS, None, precomputed, rows=True)
+            assert np.array_equal(first[0], same[0]), "the series with the flows precomputed marches other bits"
+            if ONE:
+                print("one series with openings: O %.3f ms per step" % fresh(leg_op, STEPS))
+                continue
+            cc, oo, cc1, oo1 = [], [], [], []
+            for r in range(ROUNDS):
+                cc.append(fresh(leg_op, STEPS, None, precomputed))
+                oo.append(fresh(leg_op, STEPS))
+                cc1.append(fresh(leg_op, 1, None, precomputed))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                oo1.append(fresh(leg_op, 1))
+            C_, O_, C1, O1 = (float(np.median(v)) for v in (cc, oo, cc1, oo1))
+            Cs, Os = (C_ * STEPS - C1) / (STEPS - 1), (O_ * STEPS - O1) / (STEPS - 1)  # per step once the call is set up
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                C_flows_precomputed_ms=C_, O_openings_ms=O_, O_minus_C_ms=O_ - C_, O_over_C=O_ / C_, C_series_of_one_step_ms=C1,
+                O_series_of_one_step_ms=O1, O_minus_C_series_of_one_step_ms=O1 - C1, C_without_setup_ms=Cs, O_without_setup_ms=Os,
+                O_minus_C_without_setup_ms=Os - Cs, openings=int(NO), paths=int(Z + 2 * n_door), channels=int(channel.shape[1]),
+                bytes=OPENING_BYTES, bytes_per_step_of_k_series_openings=int(OPENING_BYTES["k_series_openings_per_opening"] * NO),
+                traces_equal=True, all_rounds=dict(C=cc, O=oo, C_one_step=cc1, O_one_step=oo1))
+            print("n_sub %2d: C flows precomputed %.3f ms/step, O openings %.3f -> O - C = %+.3f ms, O / C = %.4f; a series of one step: "
+                  "C %.2f ms, O %.2f ms -> per step without the set-up C %.3f, O %.3f, O - C = %+.3f (%d openings, %d paths, %d steps, "
+                  "median of %d rounds)" % (n_sub, C_, O_, O_ - C_, O_ / C_, C1, O1, Cs, Os, Os - Cs, NO, Z + 2 * n_door, STEPS, ROUNDS), flush=True)
             continue
         if SPECIES:
             leg_sp(b, w, n_sub, min(STEPS, 10), {})  # warm-up
@@ -1134,7 +1215,22 @@ if AMBIENT and not ONE:
         print("kernel trace: k_series_ambient %.2f us per step" % us)
     else:
         print("no kernel trace at %s" % stats)
-if SPECIES and not ONE:
+if OPENINGS and not ONE:
+    # the kernel trace of one O series (--one-series --openings under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: k_series_openings per step, beside the same trace's k_series_air_paths
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_openings_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_openings", "k_series_air_paths")}
+        result["kernel_trace_of_one_O_series"] = dict({"%s_us_per_step" % k: v for k, v in us.items()}, calls=int(rows["k_series_openings"]["Calls"]))
+        print("kernel trace: k_series_openings %.2f us per step, k_series_air_paths %.2f" % (us["k_series_openings"], us["k_series_air_paths"]))
+    else:
+        result["kernel_trace_of_one_O_series"] = "not taken yet"
+        print("no kernel trace at %s" % stats)
+if SPECIES and not OPENINGS and not ONE:
     # the kernel trace of one P series (--one-series --species under rocprofv3 --kernel-trace --stats, a run of its own), where it
     # has been taken: the two kernels per step, beside the same trace's k_series_zone_loads
     stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
@@ -1168,7 +1264,7 @@ if HANDLERS and not SPECIES and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_openings.json" if OPENINGS else "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
