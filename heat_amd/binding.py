@@ -225,6 +225,15 @@ class Openings(C.Structure):
                 ("resume", C.c_int64), ("step_base", C.c_int64), ("sum_v", _dp), ("max_v", _dp), ("step_max", _i64p)]
 
 
+class Controllers(C.Structure):
+    """heat_controllers (include/heat_amd.h): modulating control loops whose outputs are written into derived channels"""
+    _fields_ = [("n_controllers", C.c_int64), ("sense_kind", _i32p), ("sense_index", _i32p), ("sense_node", _i32p), ("set_chan", _i32p),
+                ("action", _i32p), ("en_chan", _i32p), ("lim_kind", _i32p), ("lim_index", _i32p), ("lim_node", _i32p), ("out_chan", _i32p),
+                ("kp", _dp), ("ki", _dp), ("bias", _dp), ("out_lo", _dp), ("out_hi", _dp), ("lim_hi", _dp), ("lim_lo", _dp),
+                ("resume", C.c_int64), ("integral", _dp), ("tripped", C.POINTER(C.c_uint8)), ("sum_u", _dp), ("sum_out", _dp), ("steps_on", _i64p),
+                ("steps_sat", _i64p), ("trips", _i64p)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -313,6 +322,10 @@ SYMBOLS = [
     ("heat_openings_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(Openings)]),
     ("heat_batch_march_series_openings", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
                                                    _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp, C.POINTER(Openings), _dp]),
+    ("heat_controllers_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(Openings), C.POINTER(Controllers)]),
+    ("heat_batch_march_series_controllers", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
+                                                      _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp, C.POINTER(Openings), _dp,
+                                                      C.POINTER(Controllers), _dp, _dp]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -469,7 +482,7 @@ HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
                      "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check", "heat_air_handlers_check",
-                     "heat_air_species_check", "heat_openings_check",
+                     "heat_air_species_check", "heat_openings_check", "heat_controllers_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1711,6 +1724,87 @@ def openings_check(md, openings, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+CONTROLLER_STATE = ("integral", "tripped")
+CONTROLLER_STATS = ("sum_u", "sum_out", "steps_on", "steps_sat", "trips")
+_CONTROLLER_ROWS = (("sense_kind", np.int32, False), ("sense_index", np.int32, True), ("sense_node", np.int32, False),
+                    ("set_chan", np.int32, True), ("action", np.int32, False), ("en_chan", np.int32, False), ("lim_kind", np.int32, False),
+                    ("lim_index", np.int32, False), ("lim_node", np.int32, False), ("out_chan", np.int32, True), ("kp", np.float64, True),
+                    ("ki", np.float64, False), ("bias", np.float64, False), ("out_lo", np.float64, False), ("out_hi", np.float64, True),
+                    ("lim_hi", np.float64, False), ("lim_lo", np.float64, False))
+_CONTROLLER_ACC_DTYPE = dict(integral=np.float64, tripped=np.uint8, sum_u=np.float64, sum_out=np.float64, steps_on=np.int64,
+                             steps_sat=np.int64, trips=np.int64)
+
+
+def make_controllers(sense_index=(), set_chan=(), out_chan=(), kp=(), out_hi=(), sense_kind=None, sense_node=None, action=None, en_chan=None,
+                     lim_kind=None, lim_index=None, lim_node=None, ki=None, bias=None, out_lo=None, lim_hi=None, lim_lo=None,
+                     state=CONTROLLER_STATE, stats=CONTROLLER_STATS, resume=None):
+    """Builds a heat_controllers. Returns (controllers, keepalive); the march updates the state and the accumulators in place.
+    sense_kind       [n] 0: a zone's air, 1: a node of a surface, 2: a channel; None: all 0
+    sense_index      [n] the zone, the surface or the channel
+    sense_node       [n] kind 1: the node, -1 the surface's last; None: all -1
+    set_chan         [n] the setpoint's channel
+    action           [n] > 0 heating (e = setpoint - sensed), else cooling; None: all +1
+    en_chan          [n] enabled where its value is > 0; None / -1: always
+    lim_kind, lim_index, lim_node, lim_hi, lim_lo
+                     [n] a high-limit cut-out on a temperature named as the sensed one is: u = 0 from above lim_hi until below
+                     lim_lo; lim_kind None / -1: none
+    out_chan         [n] the DERIVED channel the controller writes out_lo + u (out_hi - out_lo) into: name it as the channel of a
+                     gain of the zone loads, of the room radiation, of an opening's frac_chan, of an air path's volume, or of
+                     a side's driven solar input (controllers.embed)
+    kp, ki, bias     [n] u = clamp(kp e + I + bias), I = clamp(I + ki e), both to [0, 1]; ki per step; ki, bias None = 0
+                     (controllers.proportional and pi give them)
+    out_lo, out_hi   [n] the output at u = 0 (None: 0) and at u = 1
+    state            names out of CONTROLLER_STATE that are returned (the device keeps both either way)
+    stats            names out of CONTROLLER_STATS: which accumulators are maintained (default: all)
+    resume           a dict of arrays a previous series returned: the state and the accumulators start from them
+    (controllers.apply and accumulate are the rule in numpy and take the same dict)"""
+    given = dict(sense_kind=sense_kind, sense_index=sense_index, sense_node=sense_node, set_chan=set_chan, action=action, en_chan=en_chan,
+                 lim_kind=lim_kind, lim_index=lim_index, lim_node=lim_node, out_chan=out_chan, kp=kp, ki=ki, bias=bias, out_lo=out_lo,
+                 out_hi=out_hi, lim_hi=lim_hi, lim_lo=lim_lo)
+    unknown = set(stats or ()) - set(CONTROLLER_STATS) | set(state or ()) - set(CONTROLLER_STATE)
+    if unknown:
+        raise ValueError("controllers: unknown state or stats %s (known: %s)" % (sorted(unknown), ", ".join(CONTROLLER_STATE + CONTROLLER_STATS)))
+    ct = Controllers()
+    keep = {}
+    n = len(np.asarray(sense_index if sense_index is not None else ()).reshape(-1))
+    ct.n_controllers, ct.resume = n, 0 if resume is None else 1
+    for name, dtype, needed in _CONTROLLER_ROWS:
+        if given[name] is None and not needed:
+            continue
+        v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+        if v.shape != (n,):
+            raise ValueError("controllers %s: %s for %d controllers" % (name, v.shape, n))
+        keep[name] = v
+        setattr(ct, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if n else None)
+    for name in tuple(state or ()) + tuple(stats or ()):
+        dtype = _CONTROLLER_ACC_DTYPE[name]
+        if resume is not None:
+            if name not in resume:
+                raise ValueError("controllers resume: %s is missing" % name)
+            a = np.array(resume[name], dtype=dtype)  # (a copy: the march writes it)
+            if a.shape != (n,):
+                raise ValueError("controllers resume: %s of shape %s, not %s" % (name, a.shape, (n,)))
+        else:
+            a = np.zeros(n, dtype)  # (the library initialises on the device)
+        keep[name] = a
+        setattr(ct, name, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if a.size else None)
+    return ct, keep
+
+
+def controllers_check(md, controllers, openings=None, lib=None, **series):
+    """heat_controllers_check: everything about the controllers of a series, and about them beside its openings, that needs no
+    device (series arguments as HeatBatch.march_series; controllers, openings: the arguments of make_controllers and
+    make_openings, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    op, okeep = make_openings(**openings) if openings is not None else (None, None)
+    ct, ckeep = make_controllers(**controllers) if controllers is not None else (None, None)
+    rc = L.heat_controllers_check(C.byref(desc), C.byref(s), C.byref(op) if op is not None else None, C.byref(ct) if ct is not None else None)
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1836,7 +1930,7 @@ class HeatBatch:
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
                      blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True,
                      handlers=None, supply_t=True, recovered=True, coil_q=True, branch_q=True, species=None, conc_rows=True,
-                     vent_v=True, vent_q=True, openings=None, opening_v=True, **series):
+                     vent_v=True, vent_q=True, openings=None, opening_v=True, controllers=None, control_u=True, control_out=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -1915,7 +2009,14 @@ class HeatBatch:
         branches and the species read as any channel. Returns what the same call without openings returns plus one dict,
         appended last: opening_v [n_steps, n_openings] (empty with opening_v=False) and of OPENING_STATS those in stats (pass
         them as openings["resume"] with step_base to the next series) — one more element of the tuple, or the key "openings"
-        of the dict."""
+        of the dict.
+        controllers (a dict of make_controllers' arguments; an empty dict: no controller): heat_batch_march_series_controllers
+        — modulating control loops, evaluated on the device as the first kernel of every step from the zone and node
+        temperatures it holds and written into DERIVED channels, which the zone loads' gains, the room radiation, the
+        openings' fractions, the air paths and the driven inputs of the sides read as any channel. Returns what the same call
+        without controllers returns plus one dict, appended last: control_u, control_out [n_steps, n_controllers] (each empty
+        with its flag False), of CONTROLLER_STATE those in state and of CONTROLLER_STATS those in stats (pass them as
+        controllers["resume"] to the next series) — one more element of the tuple, or the key "controllers" of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -1928,8 +2029,10 @@ class HeatBatch:
                                                                       blind_incident=blind_incident, operative=operative, mrt=mrt,
                                                                       supply_t=supply_t, recovered=recovered, coil_q=coil_q,
                                                                       branch_q=branch_q, conc_rows=conc_rows, vent_v=vent_v,
-                                                                      vent_q=vent_q, opening_v=opening_v),
-                                  aniso=aniso, comfort=comfort, handlers=handlers, species=species, openings=openings)
+                                                                      vent_q=vent_q, opening_v=opening_v, control_u=control_u,
+                                                                      control_out=control_out),
+                                  aniso=aniso, comfort=comfort, handlers=handlers, species=species, openings=openings,
+                                  controllers=controllers)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -1955,11 +2058,13 @@ class HeatBatch:
                          shades=(make_shades, "sunlit", "n_shades"), radiation=(make_room_radiation, "irradiance", "n_receivers"),
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
-    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None, species=None, openings=None):
+    def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None, species=None, openings=None,
+                      controllers=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
         whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None; comfort: the dict of make_comfort's
         arguments or None; handlers: the dict of make_air_handlers' arguments or None; species: the dict of make_air_species'
-        arguments or None; openings: the dict of make_openings' arguments or None."""
+        arguments or None; openings: the dict of make_openings' arguments or None; controllers: the dict of make_controllers'
+        arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -2011,7 +2116,7 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        if aniso is not None or comfort is not None or handlers is not None or species is not None or openings is not None:
+        if aniso is not None or comfort is not None or handlers is not None or species is not None or openings is not None or controllers is not None:
             # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
             # that are recorded, and the anisotropic sky.
             call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
@@ -2047,10 +2152,21 @@ class HeatBatch:
                               vent_v=np.zeros((s.n_steps if want["vent_v"] else 0, sp.n_vents)),
                               vent_q=np.zeros((s.n_steps if want["vent_q"] else 0, sp.n_vents)))
             hp = [ptr(hrows[k]) for k in ("supply_t", "recovered", "coil_q", "branch_q")] if ah is not None else [None] * 4
+            op = None
             if openings is not None:
                 op, opkeep = make_openings(**openings)
                 oprows = np.zeros((s.n_steps if want["opening_v"] else 0, op.n_openings))
-                spp = [ptr(sprows[k]) for k in ("conc_rows", "vent_v", "vent_q")] if sp is not None else [None] * 3
+            spp = [ptr(sprows[k]) for k in ("conc_rows", "vent_v", "vent_q")] if sp is not None else [None] * 3
+            if controllers is not None:
+                ct, ctkeep = make_controllers(**controllers)
+                ctrows = {k: np.zeros((s.n_steps if want[k] else 0, ct.n_controllers)) for k in ("control_u", "control_out")}
+                rc = self._L.heat_batch_march_series_controllers(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
+                                                                 ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
+                                                                 C.byref(ah) if ah is not None else None, *hp,
+                                                                 C.byref(sp) if sp is not None else None, *spp,
+                                                                 C.byref(op) if op is not None else None, ptr(oprows) if op is not None else None,
+                                                                 C.byref(ct), ptr(ctrows["control_u"]), ptr(ctrows["control_out"]))
+            elif openings is not None:
                 rc = self._L.heat_batch_march_series_openings(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
                                                               ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
                                                               C.byref(ah) if ah is not None else None, *hp,
@@ -2105,6 +2221,8 @@ class HeatBatch:
             out += [("species", dict(sprows, **{k: spkeep[k] for k in ("conc",) + SPECIES_STATS if k in spkeep}))]
         if openings is not None:
             out += [("openings", dict(opening_v=oprows, **{k: opkeep[k] for k in OPENING_STATS if k in opkeep}))]
+        if controllers is not None:
+            out += [("controllers", dict(ctrows, **{k: ctkeep[k] for k in CONTROLLER_STATE + CONTROLLER_STATS if k in ctkeep}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

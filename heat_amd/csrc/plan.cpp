@@ -2439,6 +2439,177 @@ int check_opening_tables(int64_t n_zones, int32_t n_channels, const heat_opening
     return HEAT_OK;
 }
 
+// ---- controllers of a series (include/heat_amd.h, heat_controllers) ----
+namespace {
+// what a NULL list of a controller stands for
+inline int32_t ct_i32(const int32_t *list, int64_t i, int32_t neutral) { return list ? list[i] : neutral; }
+inline double ct_f64(const double *list, int64_t i) { return list ? list[i] : 0.0; }
+}  // namespace
+
+int check_controllers(const SeriesModel &m, int32_t n_channels, const heat_openings *op, const heat_controllers *ct, std::string &err) {
+    if (!ct) return HEAT_OK;
+    const int64_t n = ct->n_controllers;
+    if (n < 0) return failp(err, HEAT_E_INVALID_ARG, "negative count of controllers (controller count n_controllers %lld)", (long long)n);
+    // (the tables number the controllers with 32 bits)
+    if (n > INT32_MAX) return failp(err, HEAT_E_INVALID_ARG, "more than 2^31 - 1 controllers (controller count n_controllers %lld)", (long long)n);
+    if (n == 0) return HEAT_OK;
+    if (!ct->sense_index) return failp(err, HEAT_E_INVALID_ARG, "controller 0: sense_index is NULL");
+    if (!ct->set_chan) return failp(err, HEAT_E_INVALID_ARG, "controller 0: set_chan is NULL");
+    if (!ct->out_chan) return failp(err, HEAT_E_INVALID_ARG, "controller 0: out_chan is NULL");
+    if (!ct->kp) return failp(err, HEAT_E_INVALID_ARG, "controller 0: kp is NULL");
+    if (!ct->out_hi) return failp(err, HEAT_E_INVALID_ARG, "controller 0: out_hi is NULL");
+    // where a controller senses or limits: the kind in its range, then the zone, surface and node, or channel in theirs
+    auto place = [&](int64_t i, const char *what, int32_t kind, int32_t index, int32_t node) {
+        if (kind == 0 && (index < 0 || index >= m.n_zones))
+            return failp(err, HEAT_E_SIZE, "controller %lld: %s zone %d outside [0, %lld)", (long long)i, what, index, (long long)m.n_zones);
+        if (kind == 1) {
+            if (index < 0 || index >= m.n_surfaces)
+                return failp(err, HEAT_E_SIZE, "controller %lld: %s surface %d outside [0, %lld)", (long long)i, what, index, (long long)m.n_surfaces);
+            if (node < -1 || node >= m.node_count[index])
+                return failp(err, HEAT_E_SIZE, "controller %lld: %s node %d outside [-1, %lld), the nodes of surface %d", (long long)i, what, node,
+                             (long long)m.node_count[index], index);
+        }
+        if (kind == 2 && (index < 0 || index >= n_channels))
+            return failp(err, HEAT_E_SIZE, "controller %lld: %s channel %d outside [0, %d)", (long long)i, what, index, n_channels);
+        return (int)HEAT_OK;
+    };
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t sk = ct_i32(ct->sense_kind, i, 0), lk = ct_i32(ct->lim_kind, i, -1);
+        const int32_t sc = ct->set_chan[i], ec = ct_i32(ct->en_chan, i, -1), oc = ct->out_chan[i];
+        if (sk < 0 || sk > 2)
+            return failp(err, HEAT_E_INVALID_ARG, "controller %lld: sense_kind %d is none of 0 (zone), 1 (node), 2 (channel)", (long long)i, sk);
+        if (lk < -1 || lk > 2)
+            return failp(err, HEAT_E_INVALID_ARG, "controller %lld: lim_kind %d is none of -1 (no limit), 0 (zone), 1 (node), 2 (channel)", (long long)i, lk);
+        if (lk >= 0 && (!ct->lim_index || !ct->lim_hi || !ct->lim_lo))
+            return failp(err, HEAT_E_INVALID_ARG, "controller %lld: a limit of kind %d needs lim_index, lim_hi and lim_lo, and one is NULL", (long long)i, lk);
+        if (const int rc = place(i, "sense", sk, ct->sense_index[i], ct_i32(ct->sense_node, i, -1))) return rc;
+        if (lk >= 0)
+            if (const int rc = place(i, "limit", lk, ct->lim_index[i], ct_i32(ct->lim_node, i, -1))) return rc;
+        if (sc == -1) return failp(err, HEAT_E_SIZE, "controller %lld: no setpoint channel (set_chan -1)", (long long)i);
+        if (sc < 0 || sc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "controller %lld: setpoint channel %d outside [0, %d)", (long long)i, sc, n_channels);
+        if (ec < -1 || ec >= n_channels)
+            return failp(err, HEAT_E_SIZE, "controller %lld: enable channel %d outside [-1, %d)", (long long)i, ec, n_channels);
+        if (oc < 0 || oc >= n_channels)
+            return failp(err, HEAT_E_SIZE, "controller %lld: derived channel out_chan %d outside [0, %d)", (long long)i, oc, n_channels);
+        const double *const real[7] = {ct->kp, ct->ki, ct->bias, ct->out_lo, ct->out_hi, lk >= 0 ? ct->lim_hi : nullptr, lk >= 0 ? ct->lim_lo : nullptr};
+        static const char *const name[7] = {"kp", "ki", "bias", "out_lo", "out_hi", "lim_hi", "lim_lo"};
+        for (int a = 0; a < 7; a++) {
+            if (real[a] && !std::isfinite(real[a][i]))
+                return failp(err, HEAT_E_INVALID_ARG, "controller %lld: %s %g is not finite", (long long)i, name[a], real[a][i]);
+            if (a < 2 && real[a] && real[a][i] < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "controller %lld: %s %g is negative", (long long)i, name[a], real[a][i]);
+        }
+        if (lk >= 0 && ct->lim_lo[i] > ct->lim_hi[i])
+            return failp(err, HEAT_E_INVALID_ARG, "controller %lld: lim_lo %g above lim_hi %g", (long long)i, ct->lim_lo[i], ct->lim_hi[i]);
+        if (ct->resume && ct->tripped && ct->tripped[i] > 1)
+            return failp(err, HEAT_E_INVALID_ARG, "controller %lld: tripped byte %d is neither 0 nor 1", (long long)i, (int)ct->tripped[i]);
+        // (a NaN integral is data: a series that met one resumes with it)
+        if (ct->resume && ct->integral && (ct->integral[i] < 0.0 || ct->integral[i] > 1.0))
+            return failp(err, HEAT_E_INVALID_ARG, "controller %lld: integral %g outside [0, 1]", (long long)i, ct->integral[i]);
+    }
+    // a derived channel has one writer among the controllers and the openings ...
+    std::vector<int32_t> writer((size_t)n_channels, -1), opening((size_t)n_channels, -1);
+    const int64_t n_op = op ? op->n_openings : 0;
+    for (int64_t j = 0; j < n_op; j++) opening[(size_t)op->out_chan[j]] = (int32_t)j;
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t oc = ct->out_chan[i];
+        if (writer[(size_t)oc] >= 0)
+            return failp(err, HEAT_E_SIZE, "controller %lld: its derived channel out_chan %d is also controller %d's: a derived channel has one writer",
+                         (long long)i, oc, writer[(size_t)oc]);
+        if (opening[(size_t)oc] >= 0)
+            return failp(err, HEAT_E_SIZE, "controller %lld: its derived channel out_chan %d is also opening %d's: a derived channel has one writer",
+                         (long long)i, oc, opening[(size_t)oc]);
+        writer[(size_t)oc] = (int32_t)i;
+    }
+    // ... and no controller reads one: not a controller's (no cascades), not an opening's (the openings run behind)
+    for (int64_t i = 0; i < n; i++) {
+        const int32_t sk = ct_i32(ct->sense_kind, i, 0), lk = ct_i32(ct->lim_kind, i, -1);
+        const int32_t read[4] = {sk == 2 ? ct->sense_index[i] : -1, ct->set_chan[i], ct_i32(ct->en_chan, i, -1), lk == 2 ? ct->lim_index[i] : -1};
+        static const char *const name[4] = {"sense channel", "set_chan", "en_chan", "limit channel"};
+        for (int a = 0; a < 4; a++) {
+            if (read[a] < 0) continue;
+            if (writer[(size_t)read[a]] >= 0)
+                return failp(err, HEAT_E_SIZE, "controller %lld: its %s %d is the derived channel of controller %d: a controller never reads a controller",
+                             (long long)i, name[a], read[a], writer[(size_t)read[a]]);
+            if (opening[(size_t)read[a]] >= 0)
+                return failp(err, HEAT_E_SIZE, "controller %lld: its %s %d is the derived channel of opening %d: the openings run behind the controllers",
+                             (long long)i, name[a], read[a], opening[(size_t)read[a]]);
+        }
+    }
+    return HEAT_OK;
+}
+
+void build_controller_tables(const SeriesModel &m, const heat_controllers *ct, const std::function<uint32_t(int64_t, int)> &node_at,
+                             ControllerTables &t) {
+    const size_t n = ct ? (size_t)ct->n_controllers : 0;
+    t = ControllerTables();
+    t.n_controllers = (int64_t)n;
+    t.i32.assign((size_t)kControllerI32Rows * n, -1);
+    t.f64.assign((size_t)kControllerF64Rows * n, 0.0);
+    if (n == 0) return;
+    auto at = [&](int32_t kind, int32_t index, int32_t node) {
+        if (kind != 1) return index;
+        return (int32_t)node_at(index, node < 0 ? (int)m.node_count[index] - 1 : node);
+    };
+    int32_t *const I = t.i32.data();
+    for (size_t i = 0; i < n; i++) {
+        const int32_t sk = ct_i32(ct->sense_kind, (int64_t)i, 0), lk = ct_i32(ct->lim_kind, (int64_t)i, -1);
+        I[CT_SENSE_KIND * n + i] = sk;
+        I[CT_SENSE_AT * n + i] = at(sk, ct->sense_index[i], ct_i32(ct->sense_node, (int64_t)i, -1));
+        I[CT_SET_CHAN * n + i] = ct->set_chan[i];
+        I[CT_ACTION * n + i] = ct_i32(ct->action, (int64_t)i, 1);
+        I[CT_EN_CHAN * n + i] = ct_i32(ct->en_chan, (int64_t)i, -1);
+        I[CT_LIM_KIND * n + i] = lk;
+        I[CT_LIM_AT * n + i] = lk >= 0 ? at(lk, ct->lim_index[i], ct_i32(ct->lim_node, (int64_t)i, -1)) : -1;
+        I[CT_OUT_CHAN * n + i] = ct->out_chan[i];
+        const double *const src[kControllerF64Rows] = {ct->kp, ct->ki, ct->bias, ct->out_lo, ct->out_hi, lk >= 0 ? ct->lim_hi : nullptr,
+                                                       lk >= 0 ? ct->lim_lo : nullptr};
+        for (int a = 0; a < kControllerF64Rows; a++) t.f64[(size_t)a * n + i] = ct_f64(src[a], (int64_t)i);
+    }
+}
+
+int check_controller_tables(const SeriesModel &m, int32_t n_channels, int64_t n_nodes, const heat_controllers *ct, const ControllerTables &t,
+                            std::string &err) {
+    const size_t n = ct ? (size_t)ct->n_controllers : 0;
+    if (t.n_controllers != (int64_t)n || t.i32.size() != (size_t)kControllerI32Rows * n || t.f64.size() != (size_t)kControllerF64Rows * n)
+        return failp(err, HEAT_E_SIZE, "controller tables: %zu integers and %zu reals for %zu controllers", t.i32.size(), t.f64.size(), n);
+    if (n == 0) return HEAT_OK;
+    std::vector<uint8_t> written((size_t)n_channels, 0);
+    auto inside = [&](int32_t kind, int32_t at) {
+        const int64_t bound = kind == 0 ? m.n_zones : kind == 1 ? n_nodes : (int64_t)n_channels;
+        return (int64_t)(uint32_t)at < bound;
+    };
+    for (size_t i = 0; i < n; i++) {
+        const int32_t sk = t.list(CT_SENSE_KIND)[i], lk = t.list(CT_LIM_KIND)[i], oc = t.list(CT_OUT_CHAN)[i];
+        // every row the caller's ...
+        const bool same_i32 = sk == ct_i32(ct->sense_kind, (int64_t)i, 0) && lk == ct_i32(ct->lim_kind, (int64_t)i, -1) &&
+                              t.list(CT_SET_CHAN)[i] == ct->set_chan[i] && t.list(CT_ACTION)[i] == ct_i32(ct->action, (int64_t)i, 1) &&
+                              t.list(CT_EN_CHAN)[i] == ct_i32(ct->en_chan, (int64_t)i, -1) && oc == ct->out_chan[i];
+        if (!same_i32) return failp(err, HEAT_E_SIZE, "controller tables: controller %zu: an integer row is not the caller's", i);
+        const double *const src[kControllerF64Rows] = {ct->kp, ct->ki, ct->bias, ct->out_lo, ct->out_hi, lk >= 0 ? ct->lim_hi : nullptr,
+                                                       lk >= 0 ? ct->lim_lo : nullptr};
+        for (int a = 0; a < kControllerF64Rows; a++) {
+            const double want = ct_f64(src[a], (int64_t)i);
+            if (std::memcmp(&t.real(a)[i], &want, sizeof(double)) != 0)
+                return failp(err, HEAT_E_SIZE, "controller tables: controller %zu: real row %d is not the caller's", i, a);
+        }
+        // ... and everything the lane indexes with inside its array
+        if (sk < 0 || sk > 2 || lk < -1 || lk > 2 || !inside(sk, t.list(CT_SENSE_AT)[i]) || (lk >= 0 && !inside(lk, t.list(CT_LIM_AT)[i])) ||
+            !inside(2, t.list(CT_SET_CHAN)[i]) || t.list(CT_EN_CHAN)[i] >= n_channels || !inside(2, oc))
+            return failp(err, HEAT_E_SIZE, "controller tables: controller %zu: a zone, node or channel lies outside its array", i);
+        if (written[(size_t)oc]++) return failp(err, HEAT_E_SIZE, "controller tables: controller %zu: derived channel %d has two writers", i, oc);
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int32_t read[4] = {t.list(CT_SENSE_KIND)[i] == 2 ? t.list(CT_SENSE_AT)[i] : -1, t.list(CT_SET_CHAN)[i], t.list(CT_EN_CHAN)[i],
+                                 t.list(CT_LIM_KIND)[i] == 2 ? t.list(CT_LIM_AT)[i] : -1};
+        for (int a = 0; a < 4; a++)
+            if (read[a] >= 0 && written[(size_t)read[a]])
+                return failp(err, HEAT_E_SIZE, "controller tables: controller %zu: it reads derived channel %d", i, read[a]);
+    }
+    return HEAT_OK;
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -3661,6 +3832,24 @@ int heat_openings_check(const heat_batch_desc *desc, const heat_series *s, const
     heat::OpeningTables t;
     heat::build_opening_tables(op, t);
     return heat::check_opening_tables(desc->n_zones, s->n_channels, op, t, heat::last_error());
+}
+
+int heat_controllers_check(const heat_batch_desc *desc, const heat_series *s, const heat_openings *op, const heat_controllers *ct) {
+    int rc = heat::check_desc(desc, heat::last_error());
+    if (rc) return rc;
+    if (!s) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "series is NULL");
+    if (s->n_channels < 0) return heat::failp(heat::last_error(), HEAT_E_INVALID_ARG, "negative count in series (n_channels %d)", s->n_channels);
+    if ((rc = heat::check_openings(desc->n_zones, s->n_channels, op, heat::last_error()))) return rc;
+    std::vector<int64_t> node_count;
+    const heat::SeriesModel m = heat::series_model_of(desc, node_count);
+    rc = heat::check_controllers(m, s->n_channels, op, ct, heat::last_error());
+    if (rc || !ct) return rc;
+    // ... and the tables the march would upload, with the nodes numbered as the descriptor numbers them (the device's layout
+    // is the batch's), built and checked against the caller's lists (this is the build the sanitizers see)
+    heat::ControllerTables t;
+    const int64_t *const node_offset = desc->node_offset;
+    heat::build_controller_tables(m, ct, [node_offset](int64_t q, int node) { return (uint32_t)(node_offset[q] + node); }, t);
+    return heat::check_controller_tables(m, s->n_channels, node_offset[desc->n_surfaces], ct, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

@@ -8,6 +8,7 @@
 #pragma once
 #include <stdint.h>
 
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -277,6 +278,32 @@ void build_opening_tables(const heat_openings *op, OpeningTables &t);
 // channel a lane would index inside [0, n_zones) / [0, n_channels), and every derived channel written by one opening and read
 // by none. HEAT_OK or HEAT_E_SIZE.
 int check_opening_tables(int64_t n_zones, int32_t n_channels, const heat_openings *op, const OpeningTables &t, std::string &err);
+
+// Controllers of a series (heat_controllers, include/heat_amd.h). Everything heat_controllers_check promises about the term
+// itself and about it beside the openings `op` (nullable; it has passed check_openings); ct == nullptr is none. m: the
+// surfaces' node counts and the zones. HEAT_OK or a negative heat_status with `err` set, naming "controller i".
+int check_controllers(const SeriesModel &m, int32_t n_channels, const heat_openings *op, const heat_controllers *ct, std::string &err);
+// The tables of k_series_controllers (one lane per controller, the caller's order), packed into one int32 and one f64 buffer
+// (one upload each). A NULL list holds its neutral value here (sense_kind 0, action +1, en_chan and lim_kind -1, reals 0).
+// CT_SENSE_AT / CT_LIM_AT: where the lane reads — the zone, the channel, or for kind 1 the node's index in the device's T
+// buffer as `node_at` gives it (32 bits, unsigned, as the probes'), the node already resolved (-1: the last).
+enum ControllerI32 : int { CT_SENSE_KIND, CT_SENSE_AT, CT_SET_CHAN, CT_ACTION, CT_EN_CHAN, CT_LIM_KIND, CT_LIM_AT, CT_OUT_CHAN, kControllerI32Rows };
+enum ControllerF64 : int { CT_KP, CT_KI, CT_BIAS, CT_OUT_LO, CT_OUT_HI, CT_LIM_HI, CT_LIM_LO, kControllerF64Rows };
+struct ControllerTables {
+    int64_t n_controllers = 0;
+    std::vector<int32_t> i32;  // [kControllerI32Rows][n]
+    std::vector<double> f64;   // [kControllerF64Rows][n]
+    const int32_t *list(int a) const { return i32.data() + a * n_controllers; }
+    const double *real(int a) const { return f64.data() + a * n_controllers; }
+};
+// (of a term that passed check_controllers) node_at(surface, node): the index of that node in the T buffer
+void build_controller_tables(const SeriesModel &m, const heat_controllers *ct, const std::function<uint32_t(int64_t, int)> &node_at,
+                             ControllerTables &t);
+// The tables against the caller's lists (used by the host-only check): every row the caller's, every zone, channel and node
+// index a lane would use inside [0, n_zones) / [0, n_channels) / [0, n_nodes), and every derived channel written by one
+// controller and read by none. HEAT_OK or HEAT_E_SIZE.
+int check_controller_tables(const SeriesModel &m, int32_t n_channels, int64_t n_nodes, const heat_controllers *ct, const ControllerTables &t,
+                            std::string &err);
 
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
 // themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".

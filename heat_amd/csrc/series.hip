@@ -902,6 +902,84 @@ struct OpeningsTerm {
     }
 };
 
+// The controllers (heat_controllers): the tables in the caller's order (plan.hpp, ControllerTables) with the sensed nodes
+// resolved to their places in the device's T buffer, the state (always on the device: uploaded on resume where the caller
+// holds it, else zeroed there), the accumulators (uploaded on resume, else started on the device) and the control_u and
+// control_out rows. Nothing of it exists on the device without controllers.
+struct ControllersTerm {
+    heat_controllers *ct = nullptr;
+    int64_t NCT = 0;
+    ControllerTables ctt;
+    DevBuf<int32_t> i32;          // [kControllerI32Rows][NCT]
+    DevBuf<double> f64, u, out;   // [kControllerF64Rows][NCT]; u, out: [n_steps][NCT]
+    DevBuf<double> integral;
+    DevBuf<uint8_t> tripped;
+    Acc<double> acc_f64[2];       // sum_u, sum_out
+    Acc<int64_t> acc_i64[3];      // steps_on, steps_sat, trips
+    ControllersDev view{};
+    // A sensed node's place in T: its slot of the caller's state through the resolver the probes use, then the probes' placement
+    // (the device's node layout is packed: the descriptor's numbering does not index T).
+    int prepare(heat_batch *b, const SeriesModel &m, heat_controllers *ct_) {
+        ct = ct_;
+        NCT = ct ? ct->n_controllers : 0;
+        if (NCT == 0) return HEAT_OK;
+        bool resolved = true;
+        build_controller_tables(m, ct, [&](int64_t q, int node) {
+            int kind = 0, n = 0;
+            int64_t index = 0;
+            uint8_t buf = 0;
+            uint32_t idx = 0;
+            if (!b->resolver->resolve(b->h_first_slot[q] + node, kind, index, n) || kind != PROBE_NODE || index != q || n != node) {
+                resolved = false;
+                return (uint32_t)0;
+            }
+            ProbesTerm::place(b, kind, index, n, buf, idx);
+            if ((size_t)idx >= b->d_T.n) resolved = false;
+            return resolved ? idx : (uint32_t)0;
+        }, ctt);
+        if (!resolved) return fail(HEAT_E_SIZE, "controllers: a sensed node's slot is not resolved to a node of the batch");
+        acc_f64[0].bind(ct->sum_u, 0.0, &view.sum_u), acc_f64[1].bind(ct->sum_out, 0.0, &view.sum_out);
+        acc_i64[0].bind(ct->steps_on, 0, &view.steps_on), acc_i64[1].bind(ct->steps_sat, 0, &view.steps_sat);
+        acc_i64[2].bind(ct->trips, 0, &view.trips);
+        return HEAT_OK;
+    }
+    int upload(const double *host_u, const double *host_out, int n_steps) {
+        if (NCT == 0) return HEAT_OK;
+        const bool resume = ct->resume != 0;
+        SERIES_TRY(series_upload(i32, ctt.i32, "controller tables"));
+        SERIES_TRY(series_upload(f64, ctt.f64, "controller tables"));
+        SERIES_TRY(series_alloc(integral, (size_t)NCT, "controller state", resume ? ct->integral : nullptr));
+        SERIES_TRY(series_alloc(tripped, (size_t)NCT, "controller state", resume ? ct->tripped : nullptr));
+        for (auto &a : acc_f64) SERIES_TRY(a.stage((size_t)NCT, resume, "controller accumulators"));
+        for (auto &a : acc_i64) SERIES_TRY(a.stage((size_t)NCT, resume, "controller accumulators"));
+        if (host_u) SERIES_TRY(series_alloc(u, (size_t)n_steps * NCT, "controller signals"));
+        if (host_out) SERIES_TRY(series_alloc(out, (size_t)n_steps * NCT, "controller outputs"));
+        view.n_controllers = (int)NCT;
+        view.sense_kind = i32.p + CT_SENSE_KIND * NCT, view.set_chan = i32.p + CT_SET_CHAN * NCT, view.action = i32.p + CT_ACTION * NCT;
+        view.en_chan = i32.p + CT_EN_CHAN * NCT, view.lim_kind = i32.p + CT_LIM_KIND * NCT, view.out_chan = i32.p + CT_OUT_CHAN * NCT;
+        view.sense_at = reinterpret_cast<const uint32_t *>(i32.p + CT_SENSE_AT * NCT);
+        view.lim_at = reinterpret_cast<const uint32_t *>(i32.p + CT_LIM_AT * NCT);
+        view.kp = f64.p + CT_KP * NCT, view.ki = f64.p + CT_KI * NCT, view.bias = f64.p + CT_BIAS * NCT, view.out_lo = f64.p + CT_OUT_LO * NCT;
+        view.out_hi = f64.p + CT_OUT_HI * NCT, view.lim_hi = f64.p + CT_LIM_HI * NCT, view.lim_lo = f64.p + CT_LIM_LO * NCT;
+        view.integral = integral.p, view.tripped = tripped.p;
+        return HEAT_OK;
+    }
+    hipError_t start(hipStream_t st) {
+        if (NCT == 0) return hipSuccess;
+        const bool resume = ct->resume != 0;
+        hipError_t e = hipSuccess;
+        if (!(resume && ct->integral)) e = hipMemsetAsync(integral.p, 0, (size_t)NCT * sizeof(double), st);
+        if (e == hipSuccess && !(resume && ct->tripped)) e = hipMemsetAsync(tripped.p, 0, (size_t)NCT, st);
+        return resume ? e : for_each_acc(acc_i64, &Acc<int64_t>::start, st, for_each_acc(acc_f64, &Acc<double>::start, st, e));
+    }
+    hipError_t fetch(double *host_u, double *host_out, hipStream_t st) {
+        if (NCT == 0) return hipSuccess;
+        hipError_t e = series_fetch(host_out, out, st, series_fetch(host_u, u, st));
+        e = series_fetch(ct->tripped, tripped, st, series_fetch(ct->integral, integral, st, e));
+        return for_each_acc(acc_i64, &Acc<int64_t>::fetch, st, for_each_acc(acc_f64, &Acc<double>::fetch, st, e));
+    }
+};
+
 // The anisotropic sky (heat_sky_aniso): the coefficient table as given, beside the record table, and the bands of the three
 // consumers — the sides' per DEVICE surface, the apertures' and the shades' in the caller's order as their tables are; zeros
 // where the caller gave none. Absent (every pointer NULL) without aniso: the isotropic kernels are launched.
@@ -994,8 +1072,9 @@ struct ComfortTerm {
 
 // What heat_batch_march_series_call takes (the eleven positional entry points fill what they have) and, beside it, the comfort
 // term and its two arrays of rows (heat_batch_march_series_comfort), the air handlers with their four
-// (heat_batch_march_series_handlers), the air species with their three (heat_batch_march_series_species) and the openings with
-// their one (heat_batch_march_series_openings); filled by field name. no_trace_ok: a NULL trace records none.
+// (heat_batch_march_series_handlers), the air species with their three (heat_batch_march_series_species), the openings with
+// their one (heat_batch_march_series_openings) and the controllers with their two (heat_batch_march_series_controllers);
+// filled by field name. no_trace_ok: a NULL trace records none.
 struct SeriesCall {
     const heat_series *s = nullptr;
     const heat_sky *sky = nullptr;
@@ -1021,6 +1100,8 @@ struct SeriesCall {
     double *conc_rows = nullptr, *vent_v = nullptr, *vent_q = nullptr;
     heat_openings *openings = nullptr;
     double *opening_v = nullptr;
+    heat_controllers *controllers = nullptr;
+    double *control_u = nullptr, *control_out = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -1066,6 +1147,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = check_air_handlers(b->n_zones, s->n_channels, c.handlers, heat::last_error()))) return rc;
     if ((rc = check_air_species(b->n_zones, s->n_channels, c.species, heat::last_error()))) return rc;
     if ((rc = check_openings(b->n_zones, s->n_channels, c.openings, heat::last_error()))) return rc;
+    if ((rc = check_controllers(m, s->n_channels, c.openings, c.controllers, heat::last_error()))) return rc;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -1096,6 +1178,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HandlersTerm handlers;
     SpeciesTerm species;
     OpeningsTerm openings;
+    ControllersTerm controllers;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
@@ -1113,9 +1196,10 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     handlers.prepare(b, c.handlers);
     species.prepare(b, c.handlers, c.species);
     openings.prepare(c.openings);
+    if ((rc = controllers.prepare(b, m, c.controllers))) return rc;
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
     const int64_t NL = blinds.NL, NF = comfort.NF, NU = handlers.NU, NBR = handlers.NBR, NSP = species.NSP, NV = species.NV;
-    const int64_t NO = openings.NO;
+    const int64_t NO = openings.NO, NCT = controllers.NCT;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -1137,19 +1221,24 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = handlers.upload(c.supply_t, c.recovered, c.coil_q, c.branch_q, n_steps))) return rc;
     if ((rc = species.upload(c.conc_rows, c.vent_v, c.vent_q, n_steps))) return rc;
     if ((rc = openings.upload(c.opening_v, n_steps))) return rc;
+    if ((rc = controllers.upload(c.control_u, c.control_out, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
     HIP_TRY(report.start(b->stream));
     HIP_TRY(ideal.start(b->stream));
     HIP_TRY(comfort.start(b->stream));
     HIP_TRY(species.start(b->stream));
     HIP_TRY(openings.start(b->stream));
+    HIP_TRY(controllers.start(b->stream));
     // what the thermostats, the air paths' e and the blinds sense: the zone temperatures, or with a control sensor the step's Tc
     const double *control_T = comfort.control_T.p ? comfort.control_T.p : b->d_zone_T.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
-    // ---- the steps, enqueued without waiting: openings (the one writer of the step's row of d_channel; everything behind reads it, and
-    // a captured graph holds the body of the march only, which reads no channel) -> head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> air species -> ambient drive ->
+    // ---- the steps, enqueued without waiting: controllers -> openings (the two writers of the step's row of d_channel; everything behind reads it,
+    // and a captured graph holds the body of the march only, which reads no channel) -> head -> comfort -> control temperatures -> zone loads -> thermostat statistics -> air paths -> air handlers -> air species -> ambient drive ->
     // driven inputs -> shades -> blinds -> sky -> solar gains -> room radiation -> the body of a march call of n_sub -> probes -> report ----
     for (int k = 0; k < n_steps; k++) {
+        if (NCT > 0)
+            launch_series_controllers(controllers.view, row(d_channel, k, NC), b->d_T.p, b->d_zone_T.p, row(controllers.u, k, NCT), row(controllers.out, k, NCT),
+                                      b->stream);
         if (NO > 0) launch_series_openings(openings.view, row(d_channel, k, NC), b->d_zone_T.p, row(openings.v, k, NO), c.openings->step_base + k, b->stream);
         const double *channel = row(d_channel, k, NC);
         const SkyRecord *record = row(sky.record, k, n_sites);
@@ -1236,6 +1325,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(handlers.fetch(c.supply_t, c.recovered, c.coil_q, c.branch_q, b->stream));
     HIP_TRY(species.fetch(c.conc_rows, c.vent_v, c.vent_q, b->stream));
     HIP_TRY(openings.fetch(c.opening_v, b->stream));
+    HIP_TRY(controllers.fetch(c.control_u, c.control_out, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -1340,8 +1430,9 @@ int heat_batch_march_series_blinds(heat_batch *b, const heat_series *s, const he
 }
 
 // heat_batch_march_series_call, heat_batch_march_series_comfort, heat_batch_march_series_handlers,
-// heat_batch_march_series_species and heat_batch_march_series_openings: the struct's fields by name, then the comfort term, then
-// the air handlers, the air species and the openings (`more`: what the last three add, or nullptr).
+// heat_batch_march_series_species, heat_batch_march_series_openings and heat_batch_march_series_controllers: the struct's fields
+// by name, then the comfort term, then the air handlers, the air species, the openings and the controllers (`more`: what the
+// last four add, or nullptr).
 static int march_series_call(heat_batch *b, const heat_series_call *call, heat_comfort *comfort, double *operative, double *mrt,
                              const SeriesCall *more = nullptr) {
     if (const int rc = check_series_call(call, heat::last_error())) return rc;  // (a struct of another size is not read further)
@@ -1381,6 +1472,16 @@ int heat_batch_march_series_openings(heat_batch *b, const heat_series_call *call
                                      double *opening_v) {
     SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
     more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q, more.openings = op, more.opening_v = opening_v;
+    return march_series_call(b, call, c, operative, mrt, &more);
+}
+
+int heat_batch_march_series_controllers(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt,
+                                        heat_air_handlers *h, double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                        heat_air_species *sp, double *conc_rows, double *vent_v, double *vent_q, heat_openings *op,
+                                        double *opening_v, heat_controllers *ct, double *control_u, double *control_out) {
+    SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
+    more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q, more.openings = op, more.opening_v = opening_v;
+    more.controllers = ct, more.control_u = control_u, more.control_out = control_out;
     return march_series_call(b, call, c, operative, mrt, &more);
 }
 

@@ -1149,7 +1149,7 @@ k_series_species(int n_zones, SpeciesDev sp, SpeciesInflows in, const double *__
 // shows up in one place. (Here and not in device_math.hpp: the march does not call it.)
 __device__ __forceinline__ double sqrt_rn(double x) { return sqrt(x); }
 
-// k_series_openings — the openings of one step (heat_openings, include/heat_amd.h), the FIRST kernel of the step: one lane per
+// k_series_openings — the openings of one step (heat_openings, include/heat_amd.h), first behind the controllers: one lane per
 // opening over structure-of-arrays tables in the caller's order (plan.hpp, OpeningTables). A lane gathers its two
 // temperatures from zone_T — which nothing on the step's head writes: every zone is read as it was at the start of the step
 // — or one of them from the row, up to two more values from the row, forms V by the header's rule, every line one rounded
@@ -1196,6 +1196,77 @@ k_series_openings(OpeningsDev op, double *row, const double *__restrict__ zone_T
         op.max_v[i] = V;
         if (op.step_max != nullptr) op.step_max[i] = step;
     }
+}
+
+// what a controller senses or limits on: a zone's air, a node of a wall, or a channel of the step's row
+__device__ __forceinline__ double controller_reads(int kind, uint32_t at, const double *row, const double *__restrict__ T,
+                                                   const double *__restrict__ zone_T) {
+    return kind == 0 ? zone_T[at] : kind == 1 ? T[at] : row[at];
+}
+
+// k_series_controllers — the controllers of one step (heat_controllers, include/heat_amd.h), the FIRST kernel of the step,
+// ahead of k_series_openings: one lane per controller over structure-of-arrays tables in the caller's order (plan.hpp,
+// ControllerTables). A lane gathers what it senses and what limits it from zone_T and T — which nothing on the step's head
+// writes: every temperature is read as it was at the start of the step — or from the row, its setpoint and its enable from
+// the row, forms u and out by the header's rule, every line one rounded operation in the order written, hence no
+// contraction, and stores out into the row at its DERIVED channel: a plain 8-byte store. The check has made sure that no two
+// writers of the row (controllers and openings) share an out_chan and that no out_chan is a channel any controller reads, so
+// every element of the row has one writer and no lane reads what another writes, whatever the order of the lanes; the
+// openings and every consumer are launched behind this kernel on the same stream. The state (integral, tripped) is the
+// lane's own element of its arrays. The absent outputs are wave-uniform branches. No LDS, no atomics, no scratch.
+__global__ void __launch_bounds__(256)
+k_series_controllers(ControllersDev ct, double *row, const double *__restrict__ T, const double *__restrict__ zone_T, double *__restrict__ u_row,
+                     double *__restrict__ out_row) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ct.n_controllers) return;
+    const double Ts = controller_reads(ct.sense_kind[i], ct.sense_at[i], row, T, zone_T);
+    const double sp = row[ct.set_chan[i]];
+    const double e0 = sp - Ts;
+    const double e = ct.action[i] > 0 ? e0 : -e0;
+    const int ec = ct.en_chan[i];
+    const bool enabled = ec < 0 || row[ec] > 0.0;
+    int trip = ct.tripped[i];
+    const int lk = ct.lim_kind[i];
+    if (lk >= 0) {
+        const double Tl = controller_reads(lk, ct.lim_at[i], row, T, zone_T);
+        if (Tl > ct.lim_hi[i]) {
+            if (trip == 0 && ct.trips != nullptr) ct.trips[i] = ct.trips[i] + 1;
+            trip = 1;
+        } else if (trip == 1 && Tl < ct.lim_lo[i]) {
+            trip = 0;
+        }
+        ct.tripped[i] = (uint8_t)trip;
+    }
+    double u;
+    if (!enabled) {
+        ct.integral[i] = 0.0;
+        u = 0.0;
+    } else if (trip == 1) {
+        u = 0.0;
+    } else {
+        const double p = ct.kp[i] * e;
+        const double ie = ct.ki[i] * e;
+        double I1 = ct.integral[i] + ie;
+        if (I1 < 0.0) I1 = 0.0;
+        if (I1 > 1.0) I1 = 1.0;
+        ct.integral[i] = I1;
+        const double ub = p + I1;
+        u = ub + ct.bias[i];
+        if (u < 0.0) u = 0.0;
+        if (u > 1.0) u = 1.0;
+    }
+    const double lo = ct.out_lo[i];
+    const double span = ct.out_hi[i] - lo;
+    const double o = u * span;
+    const double out = lo + o;
+    row[ct.out_chan[i]] = out;
+    if (u_row != nullptr) u_row[i] = u;
+    if (out_row != nullptr) out_row[i] = out;
+    if (ct.sum_u != nullptr) ct.sum_u[i] = ct.sum_u[i] + u;
+    if (ct.sum_out != nullptr) ct.sum_out[i] = ct.sum_out[i] + out;
+    if (ct.steps_on != nullptr && u > 0.0) ct.steps_on[i] = ct.steps_on[i] + 1;
+    if (ct.steps_sat != nullptr && u >= 1.0) ct.steps_sat[i] = ct.steps_sat[i] + 1;
 }
 
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
@@ -1392,6 +1463,12 @@ void launch_series_species(int n_zones, const SpeciesDev &sp, const ZoneLoadsDev
 void launch_series_openings(const OpeningsDev &op, double *row, const double *zone_T, double *v_row, int64_t step, hipStream_t st) {
     if (op.n_openings <= 0) return;
     hipLaunchKernelGGL(k_series_openings, dim3((op.n_openings + 255) / 256), dim3(256), 0, st, op, row, zone_T, v_row, step);
+}
+
+void launch_series_controllers(const ControllersDev &ct, double *row, const double *T, const double *zone_T, double *u_row, double *out_row,
+                               hipStream_t st) {
+    if (ct.n_controllers <= 0) return;
+    hipLaunchKernelGGL(k_series_controllers, dim3((ct.n_controllers + 255) / 256), dim3(256), 0, st, ct, row, T, zone_T, u_row, out_row);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

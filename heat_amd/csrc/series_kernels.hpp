@@ -306,10 +306,10 @@ void launch_series_vents(int n_zones, const SpeciesDev &sp, const double *row, c
 void launch_series_species(int n_zones, const SpeciesDev &sp, const ZoneLoadsDev *zl, const AirPathsDev *ap, const HandlersDev *hd,
                            const double *row, const double *zone_vol, double h, const double *conc, double *conc_next, double *conc_row,
                            int64_t step, hipStream_t st);
-// Openings of a series step (heat_openings, include/heat_amd.h; tables: plan.hpp, OpeningTables): the FIRST launch of a step,
-// ahead of launch_series_comfort, only when there are openings, one lane per opening in the caller's order. It is the one
-// launch that WRITES the step's row of the device's channel table: every later launch of the step reads the derived columns
-// as it reads any channel.
+// Openings of a series step (heat_openings, include/heat_amd.h; tables: plan.hpp, OpeningTables): the first launch of a step
+// behind the controllers, ahead of launch_series_comfort, only when there are openings, one lane per opening in the caller's
+// order. With the controllers it is one of the two launches that WRITE the step's row of the device's channel table: every
+// later launch of the step reads the derived columns as it reads any channel.
 struct OpeningsDev {
     int n_openings;
     const int32_t *zone_a, *zone_b, *temp_chan, *wind_chan, *frac_chan, *out_chan;   // [n] each; channels -1: none
@@ -319,6 +319,23 @@ struct OpeningsDev {
 };
 // row: the step's row of the channel table, written at out_chan; v_row: the step's row of opening_v, or nullptr; step: K
 void launch_series_openings(const OpeningsDev &op, double *row, const double *zone_T, double *v_row, int64_t step, hipStream_t st);
+// Controllers of a series step (heat_controllers, include/heat_amd.h; tables: plan.hpp, ControllerTables): the FIRST launch
+// of a step, ahead of launch_series_openings, only when there are controllers, one lane per controller in the caller's
+// order. It writes the step's row of the device's channel table at the controllers' derived columns.
+struct ControllersDev {
+    int n_controllers;
+    const int32_t *sense_kind, *set_chan, *action, *en_chan, *lim_kind, *out_chan;   // [n] each; en_chan, lim_kind -1: none
+    const uint32_t *sense_at, *lim_at;     // [n] each: the zone, the channel, or the node's index in T
+    const double *kp, *ki, *bias, *out_lo, *out_hi, *lim_hi, *lim_lo;                 // [n] each
+    double *integral;                      // [n] the state: always present
+    uint8_t *tripped;
+    double *sum_u, *sum_out;               // [n] each, nullptr: not maintained
+    int64_t *steps_on, *steps_sat, *trips;
+};
+// row: the step's row of the channel table, written at out_chan; T: the node temperatures; u_row, out_row: the step's rows of
+// control_u and control_out, or nullptr
+void launch_series_controllers(const ControllersDev &ct, double *row, const double *T, const double *zone_T, double *u_row, double *out_row,
+                               hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 // Ideal loads of a series: the step's begin and end (the sequence and the view: kernels.hpp, IdealLoadsDev)
 void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipStream_t st);

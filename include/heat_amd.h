@@ -1394,8 +1394,8 @@ int heat_batch_march_series_species(heat_batch *b, const heat_series_call *call,
  * counterpart (model.rs:546,592-593 take infiltration and mixing volumes as given numbers); the rule below is this library's
  * own contract, defined against the per-call loop with the same rule written on the host (heat_amd/openings.py, apply()).
  * Each opening is an explicit formula, the superposition form of EnergyPlus' wind-and-stack open area and of de Gids-Phaff.
- * The rule of step k. The openings are the FIRST kernel of the step, ahead of the comfort term: nothing of the step has
- * read the row yet. T = the zone AIR temperatures the device holds when the step starts, row = the device's channel[k],
+ * The rule of step k. The openings are the first kernel of the step behind the controllers (heat_controllers, below: an
+ * open fraction may be a controller's output), ahead of the comfort term: nothing else of the step has read the row yet. T = the zone AIR temperatures the device holds when the step starts, row = the device's channel[k],
  * K = step_base + k. Every line is ONE rounded f64 operation in the order written, no fused multiply-add; a NaN makes every
  * comparison false:
  *   per opening i:
@@ -1455,6 +1455,106 @@ int heat_batch_march_series_openings(heat_batch *b, const heat_series_call *call
                                      heat_air_species *sp /* nullable */, double *conc_rows, double *vent_v, double *vent_q,
                                      heat_openings *op /* nullable */,
                                      double *opening_v /* [n_steps][n_openings], nullable */);
+
+/*
+ * Controllers of a series: modulating control loops as DERIVED CHANNELS. A thermostat of the zone loads is on or off at a
+ * fixed power into the zone air, and ideal loads need no sizing; nothing else of a series can modulate. A controller senses
+ * a temperature only the device holds — a zone's air, a node of a wall — or a channel, compares it with a setpoint channel
+ * and WRITES its output into one column of the step's row in the device's copy of the channel table, as an opening does.
+ * Every consumer reads that column as it reads any channel: a gain of the zone loads (a modulating radiator), a channel of
+ * the room radiation (a panel), an opening's frac_chan (a window that follows the room temperature), an air path's volume,
+ * a blind's schedule, and the driven solar input of a side, gain[s] * row[chan[s]], which front_alpha / back_alpha spread
+ * over the wall's nodes: with an alpha row that is 1 at one node a controller's watts heat that node (underfloor heating, a
+ * thermally activated ceiling), and since the back side's value is not clamped at zero a negative output cools it
+ * (heat_amd/controllers.py, embed()). No struct and no kernel of those terms changes, and the march kernels do not. The
+ * reference has no counterpart; the rule below is this library's own contract, defined against the per-call loop with the
+ * same rule written on the host (heat_amd/controllers.py, apply()).
+ * The rule of step k. The controllers are the FIRST kernel of the step, ahead of the openings — an opening's frac_chan may be
+ * a controller's output — and nothing of the step has read the row yet. T = the zone AIR temperatures the device holds when
+ * the step starts, N = the node temperatures it holds when the step starts, row = the device's channel[k]. Every line is ONE
+ * rounded f64 operation in the order written, no fused multiply-add; a NaN makes every comparison false:
+ *   per controller i:
+ *     Ts = sense_kind 0: T[sense_index]
+ *          sense_kind 1: N[surface sense_index, node sense_node]     (sense_node -1: the surface's last node)
+ *          sense_kind 2: row[sense_index]
+ *     sp = row[set_chan]
+ *     e0 = sp - Ts;  e = action > 0 ? e0 : -e0          (heating / cooling action; a sign flip)
+ *     enabled = en_chan < 0 or row[en_chan] > 0.0
+ *     if lim_kind >= 0:                                  (a high-limit cut-out, e.g. a floor surface at 29 C)
+ *         Tl = as Ts, from lim_kind / lim_index / lim_node
+ *         if Tl > lim_hi: { if trip == 0: trips += 1;  trip = 1 }
+ *         else if trip == 1 and Tl < lim_lo: trip = 0
+ *     if not enabled: I = 0.0; u = 0.0
+ *     else if trip == 1: u = 0.0                         (I is held)
+ *     else:
+ *         p = kp * e;  ie = ki * e;  I1 = I + ie
+ *         if I1 < 0.0: I1 = 0.0;  if I1 > 1.0: I1 = 1.0;  I = I1     (clamped integrator: the anti-windup)
+ *         ub = p + I1;  u = ub + bias
+ *         if u < 0.0: u = 0.0;  if u > 1.0: u = 1.0
+ *     span = out_hi - out_lo;  o = u * span;  out = out_lo + o
+ *     row[out_chan] = out;  control_u[k][i] = u;  control_out[k][i] = out
+ *     sum_u += u;  sum_out += out;  if u > 0.0: steps_on += 1;  if u >= 1.0: steps_sat += 1
+ * ki is per step: the caller folds the step length in (a reset time of n steps is ki = kp / n). A NaN u stays NaN through
+ * both clamps, and a NaN error makes the integral NaN whatever ki is (0 * NaN), which it stays until the controller is
+ * disabled; a NaN u or out is data here, as a NaN V is for openings: it becomes HEAT_N_NAN_ZONE where a consumer adds it
+ * to a zone. The caller's host channel array is never written; a derived column's host values are ignored.
+ * State and accumulators are in/out and nullable. resume == 0 starts them on the device (I = 0, trip = 0, sums and counts 0);
+ * resume != 0 takes them from the arrays (a NULL one starts at zero). A series of k steps followed by one of n - k with the
+ * returned arrays gives the bits of the series of n. The state is kept on the device whether or not the caller takes it.
+ * n_sub == 0 still evaluates every step. An array that is not asked for costs no traffic and changes no bit of the others.
+ * With ct == NULL or n_controllers == 0 heat_batch_march_series_controllers is heat_batch_march_series_openings exactly:
+ * same launches, same bits. A refused call leaves the device state untouched. Sharded batches are refused as by the series.
+ * heat_controllers_check (host-only; it also builds and verifies the tables the march uploads, with the nodes numbered as
+ * the descriptor numbers them) and heat_batch_march_series_controllers run the same checks before any device work; every
+ * message names "controller i". HEAT_E_INVALID_ARG: a negative count; a NULL array that a positive count needs
+ * (sense_index, set_chan, out_chan, kp, out_hi; lim_index, lim_hi and lim_lo where some lim_kind >= 0); a sense_kind
+ * outside [0, 2] or a lim_kind outside [-1, 2]; a constant that is not finite; kp or ki negative; lim_lo > lim_hi; on
+ * resume a tripped byte above 1 or an integral outside [0, 1]. HEAT_E_SIZE: a zone, surface or channel out of range
+ * (en_chan may be -1); a sense_node or lim_node outside [-1, the surface's nodes); set_chan missing (-1); two controllers
+ * with the same out_chan; an out_chan that is also some opening's out_chan; an out_chan that any controller reads, as sense,
+ * setpoint, enable or limit channel — a controller never reads a controller; a controller that reads an opening's out_chan,
+ * because the openings run behind the controllers. With these every element of the row has one writer, and no lane reads
+ * what another writes.
+ * Out of scope: sensing the comfort term's operative temperature, which is formed later in the step; cascades, where a
+ * controller reads a controller; minimum on and off times; derivative action; any change to the march kernels.
+ */
+typedef struct heat_controllers {
+    int64_t n_controllers;
+    const int32_t *sense_kind;          /* [n] nullable = 0; 0: a zone's air, 1: a node of a surface, 2: a channel */
+    const int32_t *sense_index;         /* [n] the zone, the surface (the descriptor's number) or the channel */
+    const int32_t *sense_node;          /* [n] nullable = -1; kind 1: the node, -1: the surface's last node; else ignored */
+    const int32_t *set_chan;            /* [n] the setpoint */
+    const int32_t *action;              /* [n] nullable = +1; > 0: heating (e = sp - Ts), else cooling (e = Ts - sp) */
+    const int32_t *en_chan;             /* [n] nullable / -1: always enabled; else enabled where row[en_chan] > 0 */
+    const int32_t *lim_kind;            /* [n] nullable / -1: no limit; else as sense_kind */
+    const int32_t *lim_index;           /* [n] as sense_index, where lim_kind >= 0 */
+    const int32_t *lim_node;            /* [n] nullable = -1, as sense_node */
+    const int32_t *out_chan;            /* [n] the DERIVED channel this controller writes */
+    const double  *kp;                  /* [n] 1 / K, finite, >= 0 (a proportional band of B K is kp = 1 / B) */
+    const double  *ki;                  /* [n] nullable = 0; 1 / K per step, finite, >= 0 */
+    const double  *bias;                /* [n] nullable = 0; finite */
+    const double  *out_lo;              /* [n] nullable = 0; the output at u = 0, finite */
+    const double  *out_hi;              /* [n] the output at u = 1, finite (below out_lo: a reverse-acting or cooling output) */
+    const double  *lim_hi, *lim_lo;     /* [n] trip above lim_hi, release below lim_lo; finite, lim_lo <= lim_hi */
+    int64_t resume;                     /* as heat_openings::resume, for the state and the accumulators below */
+    /* state, [n] each, in/out, nullable */
+    double  *integral;                  /* I, in [0, 1] */
+    uint8_t *tripped;                   /* trip, 0 or 1 */
+    /* accumulators, [n] each, in/out, nullable */
+    double  *sum_u, *sum_out;
+    int64_t *steps_on, *steps_sat, *trips;
+} heat_controllers;
+
+int heat_controllers_check(const heat_batch_desc *desc, const heat_series *s, const heat_openings *op /* nullable */,
+                           const heat_controllers *ct /* nullable */); /* host-only */
+int heat_batch_march_series_controllers(heat_batch *b, const heat_series_call *call, heat_comfort *c /* nullable */,
+                                        double *operative, double *mrt, heat_air_handlers *h /* nullable */,
+                                        double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                        heat_air_species *sp /* nullable */, double *conc_rows, double *vent_v, double *vent_q,
+                                        heat_openings *op /* nullable */, double *opening_v,
+                                        heat_controllers *ct /* nullable */,
+                                        double *control_u   /* [n_steps][n_controllers], nullable */,
+                                        double *control_out /* [n_steps][n_controllers], nullable */);
 
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the

@@ -142,6 +142,14 @@ pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
     pub ca: *const f64, pub c0: *const f64, pub resume: i64, pub step_base: i64,
     pub sum_v: *mut f64, pub max_v: *mut f64, pub step_max: *mut i64,
 }
+// heat_controllers: modulating control loops whose outputs are written into derived channels of the device's table
+#[repr(C)] pub struct HeatControllers {
+    pub n_controllers: i64, pub sense_kind: *const i32, pub sense_index: *const i32, pub sense_node: *const i32, pub set_chan: *const i32,
+    pub action: *const i32, pub en_chan: *const i32, pub lim_kind: *const i32, pub lim_index: *const i32, pub lim_node: *const i32,
+    pub out_chan: *const i32, pub kp: *const f64, pub ki: *const f64, pub bias: *const f64, pub out_lo: *const f64, pub out_hi: *const f64,
+    pub lim_hi: *const f64, pub lim_lo: *const f64, pub resume: i64, pub integral: *mut f64, pub tripped: *mut u8,
+    pub sum_u: *mut f64, pub sum_out: *mut f64, pub steps_on: *mut i64, pub steps_sat: *mut i64, pub trips: *mut i64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -255,6 +263,15 @@ extern "C" {
                                             recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64, sp: *mut HeatAirSpecies,
                                             conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64, op: *mut HeatOpenings,
                                             opening_v: *mut f64) -> c_int;
+    // controllers of a series: modulating loops on the temperatures the device holds, read by every consumer as a channel
+    pub fn heat_controllers_check(desc: *const HeatBatchDesc, s: *const HeatSeries, op: *const HeatOpenings,
+                                  ct: *const HeatControllers) -> c_int;
+    pub fn heat_batch_march_series_controllers(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
+                                               operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
+                                               recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64, sp: *mut HeatAirSpecies,
+                                               conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64, op: *mut HeatOpenings,
+                                               opening_v: *mut f64, ct: *mut HeatControllers, control_u: *mut f64,
+                                               control_out: *mut f64) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

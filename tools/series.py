@@ -130,8 +130,18 @@ and writes profiles/series_openings.json: ms per step of each, O - C, a series o
 per-step times once the set-up is taken off — and, where a kernel trace of one O series has been taken (--one-series --openings
 under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_openings_kernel_stats.csv), k_series_openings per step.
 No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species | --openings]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species | --openings]
+With --controllers (heat_batch_march_series_controllers, heat_controllers; the --openings workload, plus per zone one
+proportional valve on the zone's air that feeds a gain of the zone loads and per opening one PI loop on its zone's air, cooling
+action, that feeds the opening's open fraction) it alternates
+  P  the series with controllers = NULL and the SAME outputs precomputed into ordinary channels: the control_out rows of one K
+     series, written into the columns the gains and the openings read (the tool asserts equal traces)
+  K  the same call with the controllers, the derived columns of the host table NaN
+and writes profiles/series_controllers.json: ms per step of each, K - P, a series of ONE step of each (the call's set-up) and the
+per-step times once the set-up is taken off — and, where a kernel trace of one K series has been taken (--one-series
+--controllers under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_controllers_kernel_stats.csv),
+k_series_controllers per step. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species | --openings | --controllers]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species | --openings | --controllers]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
@@ -142,7 +152,7 @@ No time is a pass criterion.
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, openings as opm, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, controllers as ctm, openings as opm, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -155,7 +165,8 @@ SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
 COMFORT = "--comfort" in sys.argv
-OPENINGS = "--openings" in sys.argv
+CONTROLLERS = "--controllers" in sys.argv
+OPENINGS = "--openings" in sys.argv or CONTROLLERS
 SPECIES = "--species" in sys.argv or OPENINGS
 HANDLERS = "--handlers" in sys.argv or SPECIES
 LOADS = "--loads" in sys.argv or REPORT is not None or IDEAL or SKY or GAINS or AIR or SHADES or RADIATION or AMBIENT or COMFORT or HANDLERS
@@ -398,6 +409,37 @@ if OPENINGS:
         dt = time.perf_counter() - t0
         assert out[1] == -1 and np.all(np.isfinite(out[0])) and np.all(np.isfinite(out[6]["conc"]))
         assert openings is None or (np.all(np.isfinite(out[7]["sum_v"])) and out[7]["sum_v"].any())
+        return (dt * 1e3 / steps, out) if rows else dt * 1e3 / steps
+if CONTROLLERS:
+    # two more channels (a heating and a cooling setpoint) and the derived columns: per zone one proportional valve on the zone's
+    # air feeding one more gain of the zone loads, per opening one PI loop on the air of its zone_a, cooling action, feeding the
+    # opening's open fraction (the openings then read a controller's column: the controllers are the first kernel of the step)
+    c_ct = channel.shape[1]
+    NCT = Z + NO
+    channel = np.concatenate([channel, rng.uniform(19.0, 23.0, (STEPS, 1)), rng.uniform(20.0, 24.0, (STEPS, 1)), np.full((STEPS, NCT), np.nan)], axis=1)
+    controller_args = ctm.concat(
+        dict(sense_index=every, set_chan=np.full(Z, c_ct), out_hi=rng.uniform(200.0, 1500.0, Z), **ctm.proportional(rng.uniform(1.0, 4.0, Z))),
+        dict(sense_index=opening_args["zone_a"], set_chan=np.full(NO, c_ct + 1), action=np.full(NO, -1), out_hi=np.ones(NO),
+             **ctm.pi(rng.uniform(2.0, 6.0, NO), 8.0)))
+    controller_args["out_chan"] = (c_ct + 2 + np.arange(NCT)).astype(np.int32)
+    loads_ct = dict(loads, gains=dict(zone=np.concatenate([every, every]), chan=np.concatenate([loads["gains"]["chan"], controller_args["out_chan"][:Z]]),
+                                      factor=np.concatenate([loads["gains"]["factor"], np.ones(Z)])))
+    opening_ct = dict(opening_args, frac_chan=controller_args["out_chan"][Z:])
+    # per controller: eight integers, seven reals, the sensed temperature, the setpoint, the state read and written, out into the
+    # row, and the two sums and two of the counts read and written
+    CONTROLLER_BYTES = dict(k_series_controllers_per_controller=8 * 4 + 7 * 8 + 2 * 8 + (8 + 1) * 2 + 8 + 4 * 16)
+
+    def leg_ct(b, w, n_sub, steps, controllers="given", table=None, rows=False):
+        table = channel if table is None else table
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=table[:steps], probes=probes, loads=loads_ct, air=air_args, path_q=False, handlers=handler_args,
+                             supply_t=False, recovered=False, coil_q=False, branch_q=False, species=species_args, conc_rows=False, vent_v=False,
+                             vent_q=False, openings=opening_ct, opening_v=False, controllers=controller_args if controllers == "given" else controllers,
+                             control_u=False, control_out=rows, **drives)
+        dt = time.perf_counter() - t0
+        assert out[1] == -1 and np.all(np.isfinite(out[0])) and np.all(np.isfinite(out[6]["conc"])) and np.all(np.isfinite(out[7]["sum_v"]))
+        assert controllers is None or (np.all(np.isfinite(out[8]["sum_u"])) and out[8]["sum_u"].any())
         return (dt * 1e3 / steps, out) if rows else dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
@@ -677,6 +719,38 @@ with HeatBatch(md) as b:
             print("n_sub %2d: N comfort NULL %.3f ms/step, C comfort %.3f -> C - N = %+.3f ms, C / N = %.4f; a series of one step: "
                   "N %.2f ms, C %.2f ms -> per step without the set-up N %.3f, C %.3f, C - N = %+.3f (%d sensors, %d entries, %d steps, "
                   "median of %d rounds)" % (n_sub, N_, C_, C_ - N_, C_ / N_, N1, C1, Ns, Cs, Cs - Ns, Z, NE, STEPS, ROUNDS), flush=True)
+            continue
+        if CONTROLLERS:
+            # the outputs of one K series into ordinary channels: leg P's table (the state is uploaded anew before every series of
+            # this mode, so that P and K march the same steps from the same start)
+            def fresh(leg, *a, **kw):
+                b.upload_state(state)
+                return leg(b, w, n_sub, *a, **kw)
+            _, first = fresh(leg_ct, STEPS, rows=True)  # (warm-up as well)
+            precomputed = channel.copy()
+            precomputed[:, controller_args["out_chan"]] = first[8]["control_out"]
+            _, same = fresh(leg_ct, STEPS, None, precomputed, rows=True)
+            assert np.array_equal(first[0], same[0]), "the series with the outputs precomputed marches other bits"
+            if ONE:
+                print("one series with controllers: K %.3f ms per step" % fresh(leg_ct, STEPS))
+                continue
+            pp, kk, pp1, kk1 = [], [], [], []
+            for r in range(ROUNDS):
+                pp.append(fresh(leg_ct, STEPS, None, precomputed))
+                kk.append(fresh(leg_ct, STEPS))
+                pp1.append(fresh(leg_ct, 1, None, precomputed))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                kk1.append(fresh(leg_ct, 1))
+            P_, K_, P1, K1 = (float(np.median(v)) for v in (pp, kk, pp1, kk1))
+            Ps, Ks = (P_ * STEPS - P1) / (STEPS - 1), (K_ * STEPS - K1) / (STEPS - 1)  # per step once the call is set up
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                P_outputs_precomputed_ms=P_, K_controllers_ms=K_, K_minus_P_ms=K_ - P_, K_over_P=K_ / P_, P_series_of_one_step_ms=P1,
+                K_series_of_one_step_ms=K1, K_minus_P_series_of_one_step_ms=K1 - P1, P_without_setup_ms=Ps, K_without_setup_ms=Ks,
+                K_minus_P_without_setup_ms=Ks - Ps, controllers=int(NCT), openings=int(NO), channels=int(channel.shape[1]),
+                bytes=CONTROLLER_BYTES, bytes_per_step_of_k_series_controllers=int(CONTROLLER_BYTES["k_series_controllers_per_controller"] * NCT),
+                traces_equal=True, all_rounds=dict(P=pp, K=kk, P_one_step=pp1, K_one_step=kk1))
+            print("n_sub %2d: P outputs precomputed %.3f ms/step, K controllers %.3f -> K - P = %+.3f ms, K / P = %.4f; a series of one step: "
+                  "P %.2f ms, K %.2f ms -> per step without the set-up P %.3f, K %.3f, K - P = %+.3f (%d controllers, %d openings, %d steps, "
+                  "median of %d rounds)" % (n_sub, P_, K_, K_ - P_, K_ / P_, P1, K1, Ps, Ks, Ks - Ps, NCT, NO, STEPS, ROUNDS), flush=True)
             continue
         if OPENINGS:
             # the flows of one O series into ordinary channels: leg C's table (the state is uploaded anew before every series
@@ -1215,7 +1289,22 @@ if AMBIENT and not ONE:
         print("kernel trace: k_series_ambient %.2f us per step" % us)
     else:
         print("no kernel trace at %s" % stats)
-if OPENINGS and not ONE:
+if CONTROLLERS and not ONE:
+    # the kernel trace of one K series (--one-series --controllers under rocprofv3 --kernel-trace --stats, a run of its own), where
+    # it has been taken: k_series_controllers per step, beside the same trace's k_series_openings
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_controllers_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = {r["Name"].split("(")[0].split("::")[-1]: r for r in csv.DictReader(f)}
+        us = {name: float(rows[name]["AverageNs"]) / 1e3 for name in ("k_series_controllers", "k_series_openings")}
+        result["kernel_trace_of_one_K_series"] = dict({"%s_us_per_step" % k: v for k, v in us.items()}, calls=int(rows["k_series_controllers"]["Calls"]))
+        print("kernel trace: k_series_controllers %.2f us per step, k_series_openings %.2f" % (us["k_series_controllers"], us["k_series_openings"]))
+    else:
+        result["kernel_trace_of_one_K_series"] = "not taken"
+        print("no kernel trace at %s" % stats)
+if OPENINGS and not CONTROLLERS and not ONE:
     # the kernel trace of one O series (--one-series --openings under rocprofv3 --kernel-trace --stats, a run of its own), where it
     # has been taken: k_series_openings per step, beside the same trace's k_series_air_paths
     stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
@@ -1264,7 +1353,7 @@ if HANDLERS and not SPECIES and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_openings.json" if OPENINGS else "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_controllers.json" if CONTROLLERS else "series_openings.json" if OPENINGS else "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
