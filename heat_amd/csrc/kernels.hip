@@ -139,6 +139,10 @@ __device__ __forceinline__ double from_next_lane(double v) { return dpp_rotate_f
 // Four applications of A as before, but no per-stage accumulator: 20 f64 operations per node and sub-timestep instead
 // of 24, the same values up to rounding (1e-15 relative against the oracle's literal stages; tested at 1e-9).
 // Every application consumes its input in place: x_j is dead once f_j is formed.
+// This flux form is what the streamed kernels and the cluster-resident instantiations with gas cavities, no-mass nodes or
+// small surfaces run (U changes inside the sub-timestep there, or the no-mass solves read it). The cluster-resident
+// instantiations of plain walls run the same Horner scheme on premultiplied coefficients, 16 operations per node and
+// sub-timestep: apply_PQ / rk4_horner_pq below (fused_pq_form).
 //
 // The faces cost no select inside the stages: the caller hands in EFFECTIVE conductances —
 //   Ue[last node] = hB (the reference's UValue::Back there is 0) with the node "behind" it held at 0: padding slots
@@ -178,6 +182,51 @@ __device__ __forceinline__ void rk4_horner(double (&T)[M], VF V, const double (&
     apply_A<M, false>(z, V, Ue, ULe, is_first, is_last, qF, qsel,
                       [&](int j, double y) { T[j] = (T[j] + 24.0 * v[j]) + y; });
 }
+
+// The same RK4 with the two products of the flux form taken out of the stages (the cluster-resident march of walls whose
+// U and V never change inside a march call: no gas cavities, no no-mass nodes — fused_pq_form):
+//   g_j = x_{j+1} - x_j,   (A x)_j = P_j g_j - Q_j g_{j-1},   P_j = V_j U_j,   Q_j = V_j U_{j-1}
+// P and Q are formed once per block and live where U and V lived (fast_tile_march). Differences first, as in the flux
+// form, so the rows of A never cancel against each other; one subtraction, one multiply and two FMAs per node and
+// application — 16 f64 operations per node and sub-timestep — with the Horner term as the addend of the first FMA:
+//   y_j = fma(-Q_j, g_{j-1}, fma(P_j, g_j, base(j)))
+// The FMAs are written out and nothing else is contracted (the pragma below): every copy and every instantiation
+// rounds alike, whatever the compiler merges — a plain instantiation and its IDEAL sibling give the same bits.
+// The faces are effective coefficients again, set by the caller once per sub-timestep —
+//   Q_0 = V_0 hF on a surface's first lane (left neighbour held at 0),
+//   P_last = V_last hB at the surface's last node (right neighbour 0: padding slots, or the last lane's xr) —
+// and the sources V_0 qF, V_last qB are the addends base(j) of the first application.
+// No value of a neighbouring surface ever enters: xl and xr are zeroed exactly as in apply_A.
+//   put(j, y): receives base(j) + (A x)_j.
+#pragma clang fp contract(off)
+template <int M, typename BF, typename PUT>
+__device__ __forceinline__ void apply_PQ(const double (&x)[M], const double (&P)[M], const double (&Q)[M], bool is_first,
+                                         bool is_last, BF base, PUT put) {
+    const double xl_raw = from_prev_lane(x[M - 1]);
+    const double xr_raw = from_next_lane(x[0]);
+    const double xl = is_first ? 0.0 : xl_raw;
+    const double xr = is_last ? 0.0 : xr_raw;
+    double gprev = x[0] - xl;
+#pragma unroll
+    for (int j = 0; j < M; j++) {
+        const double g = ((j == M - 1) ? xr : x[j + 1]) - x[j];
+        put(j, __builtin_fma(-Q[j], gprev, __builtin_fma(P[j], g, base(j))));
+        gprev = g;
+    }
+}
+
+// src(j): V_0 qF at node 0 of a surface's first lane, V_last qB at the surface's last node, else 0.
+template <int M, typename SF>
+__device__ __forceinline__ void rk4_horner_pq(double (&T)[M], const double (&P)[M], const double (&Q)[M], bool is_first,
+                                              bool is_last, SF src) {
+    double v[M], z[M];
+    apply_PQ<M>(T, P, Q, is_first, is_last, src, [&](int j, double y) { v[j] = y * (1.0 / 24.0); });
+    apply_PQ<M>(v, P, Q, is_first, is_last, [&](int j) -> double { return 4.0 * v[j]; }, [&](int j, double y) { z[j] = y; });
+    apply_PQ<M>(z, P, Q, is_first, is_last, [&](int j) -> double { return 12.0 * v[j]; }, [&](int j, double y) { z[j] = y; });
+    apply_PQ<M>(z, P, Q, is_first, is_last, [&](int j) -> double { return __builtin_fma(24.0, v[j], T[j]); },
+                [&](int j, double y) { T[j] = y; });
+}
+#pragma clang fp contract(fast)
 
 // ---------------------------------------------------------------------------
 // Small all-no-mass surfaces (n <= 4: single-layer no-mass walls, double glazing with its gas
@@ -513,6 +562,12 @@ struct FusedLds {
 constexpr bool fused_v_in_lds(int M, int NM, int FW, int SMALL) {
     return M == 16 && NM == 1 && (SMALL == 2 || (SMALL == 1 && FW == 4));
 }
+
+// The cluster-resident instantiations whose RK4 runs on premultiplied coefficients (apply_PQ): walls without gas
+// cavities and without no-mass nodes — there U and V change neither inside a march call nor between calls, only the two
+// face conductances do. Plain, IDEAL and team variants alike (a plain instantiation and its IDEAL sibling keep the same
+// arithmetic); everything else — cavities rewrite U every sub-timestep, the no-mass solves read it — keeps apply_A.
+constexpr bool fused_pq_form(int NM, int CAV, int FW, int SMALL) { return FW != 0 && NM == 0 && CAV == 0 && SMALL != 1; }
 
 // Barriers a wavefront of a fused workgroup passes: one at the end of fused_block_init, two per sub-timestep in
 // fused_zone_phase. A wavefront without a tile that stays for the work queue keeps step with exactly these counts
@@ -1051,6 +1106,7 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
                                                 bool write_out = true, const TeamCtx team = TeamCtx{0, 0, 0, 0, nullptr}) {
     constexpr int kLanes = (FUSED ? FUSED : 4) * kWave;
     constexpr bool kVinLds = FUSED && fused_v_in_lds(M, NM, FUSED, SMALL);
+    constexpr bool kPQ = fused_pq_form(NM, CAV, FUSED, SMALL);
     HEAT_STAMP(4, true);
     HEAT_STAMP(0, false);
     HEAT_SSTAMP(0, false);
@@ -1226,7 +1282,9 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
     const int first_lane = lane - seg;
     const int nn = kind_n_mine >> 16;
     // local index of the last node inside the last lane (the last lane's segment number is its surface's k - 1)
-    const int jl = full ? (M - 1) : (nn - 1 - (mixed ? seg : k - 1) * M);
+    // (kPQ: -1 on a lane that is not its surface's last — no node of it is a last node, and every `j == jl` select of
+    // the sub-timestep then needs no is_last beside it)
+    const int jl = full ? (M - 1) : ((kPQ && !is_last) ? -1 : (nn - 1 - (mixed ? seg : k - 1) * M));
 
     auto pick_last = [&](const double (&x)[M]) {
         double r = x[M - 1];
@@ -1263,6 +1321,30 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
         }
         return r;
     };
+
+    // kPQ: the stencil's coefficients, once per block, into the registers of U and V (apply_PQ) —
+    //   P[j] = V[j] U[j] over U,   Q[j] = V[j] U[j-1] over V,   Q[0] = V[0] UL with UL from the previous lane;
+    // padding slots (V = 0) get P = Q = 0. The two face slots (Q[0] of a first lane, P at the last node) are written
+    // anew in every sub-timestep from V at the face, which stays behind in vF / vB: a wall of two lanes or more has one
+    // face per lane at most, so one register pair serves both (as h_ / q_ do, kFileOnce below).
+    double vF = 0.0, vB = 0.0;
+    (void)vF; (void)vB;
+    if constexpr (kPQ) {
+        double ULp = from_prev_lane(U[M - 1]);  // (wave-wide, taken once; a neighbouring surface's value never enters)
+        if (is_first) ULp = 0.0;
+        if constexpr (kSingleLane) {
+            vF = V[0];
+            vB = V_last();
+        } else {
+            vF = is_first ? V[0] : V_last();
+        }
+#pragma unroll
+        for (int j = M - 1; j >= 0; j--) {
+            const double q = V[j] * (j ? U[j - 1] : ULp);
+            U[j] = V[j] * U[j];
+            V[j] = q;
+        }
+    }
 
     int bad_all = 0;
     unsigned int nm_passes = 0;
@@ -1346,8 +1428,13 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
     const double Tn = pick_last(T);
 
     // Conductance towards the previous lane's last node.
-    double UL = from_prev_lane(U[M - 1]);
-    if (is_first) UL = 0.0;
+    // (kPQ: it is part of Q[0] already; U[] holds P by now)
+    double UL = 0.0;
+    if constexpr (!kPQ) {
+        UL = from_prev_lane(U[M - 1]);
+        if (is_first) UL = 0.0;
+    }
+    (void)UL;
     // Last node of the previous lane (wave-wide exchange: must not sit inside a divergent branch).
     double T_prev_last = 0.0;
     if constexpr (NM) T_prev_last = from_prev_lane(T[M - 1]);  // (wave-wide: not under the nm_on gate of a lane)
@@ -1575,7 +1662,32 @@ __device__ __forceinline__ void fast_tile_march(const FastTile tile, int counter
     }
 
     // ---- RK4 (surface.rs:228-308) ----
-    {
+    if constexpr (kPQ) {
+        // The two face coefficients and the two sources (apply_PQ), once per sub-timestep. Both slots are written anew
+        // every time, so nothing is put back afterwards; every other P and Q is the block's. U[] is P and V[] is Q here.
+        double cF, cB, sF, sB;  // V_0 hF, V_last hB, V_0 qF, V_last qB
+        if constexpr (kFileOnce) {
+            cF = cB = vF * h_;
+            sF = sB = vF * q_;
+        } else {
+            cF = vF * hF; sF = vF * qF;
+            cB = vB * hB; sB = vB * qB;
+        }
+        V[0] = is_first ? cF : V[0];
+        const double sFe = is_first ? sF : 0.0;
+        const double sBe = is_last ? sB : 0.0;
+        if (full) {
+            U[M - 1] = is_last ? cB : U[M - 1];
+            rk4_horner_pq<M>(T, U, V, is_first, is_last,
+                             [&](int j) -> double { return (j == 0) ? sFe : ((j == M - 1) ? sBe : 0.0); });
+        } else {
+#pragma unroll
+            for (int j = 0; j < M; j++) U[j] = (j == jl) ? cB : U[j];  // (jl is -1 on every lane but the last)
+            // (node 0 may be first and last node at once: a one-node tail lane, or a single-lane wall)
+            rk4_horner_pq<M>(T, U, V, is_first, is_last,
+                             [&](int j) -> double { return (j == 0) ? sFe + ((jl == 0) ? sBe : 0.0) : ((j == jl) ? sBe : 0.0); });
+        }
+    } else {
         // effective conductances of the two faces (apply_A): once per sub-timestep, not per stage and node
         const double hBe = is_last ? hB : 0.0;
         if (full) {
