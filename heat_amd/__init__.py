@@ -12,14 +12,17 @@ from .binding import AirHandlers, make_air_handlers, air_handlers_check  # noqa:
 from .binding import AirSpecies, make_air_species, air_species_check  # noqa: F401
 from .binding import Openings, make_openings, openings_check  # noqa: F401
 from .binding import Controllers, make_controllers, controllers_check  # noqa: F401
+from .binding import AirNetworks, make_air_networks, air_networks_check  # noqa: F401
 from . import modeldict  # noqa: F401
 from . import air_handlers  # noqa: F401
 from . import air_species  # noqa: F401
 from . import openings  # noqa: F401
 from . import controllers  # noqa: F401
+from . import air_networks  # noqa: F401
 
 __all__ = ["HeatBatch", "HeatError", "ModelBuilder", "Weather", "lib_path", "load_library", "build_library", "modeldict",
            "AirHandlers", "make_air_handlers", "air_handlers_check", "air_handlers",
            "AirSpecies", "make_air_species", "air_species_check", "air_species",
            "Openings", "make_openings", "openings_check", "openings",
-           "Controllers", "make_controllers", "controllers_check", "controllers"]
+           "Controllers", "make_controllers", "controllers_check", "controllers",
+           "AirNetworks", "make_air_networks", "air_networks_check", "air_networks"]

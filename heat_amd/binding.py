@@ -234,6 +234,15 @@ class Controllers(C.Structure):
                 ("steps_sat", _i64p), ("trips", _i64p)]
 
 
+class AirNetworks(C.Structure):
+    """heat_air_networks (include/heat_amd.h): pressure-balanced flows through the links of zone networks, written into derived channels"""
+    _fields_ = [("n_networks", C.c_int64), ("n_nodes", C.c_int64), ("n_links", C.c_int64), ("net_offset", _i32p), ("tol", _dp),
+                ("max_iter", _i32p), ("g_min", _dp), ("node_zone", _i32p), ("src_chan", _i32p), ("src_gain", _dp), ("zone_a", _i32p),
+                ("zone_b", _i32p), ("temp_chan", _i32p), ("wp_chan", _i32p), ("frac_chan", _i32p), ("out_ab", _i32p), ("out_ba", _i32p),
+                ("c", _dp), ("gh", _dp), ("p_lin", _dp), ("wp_gain", _dp), ("resume", C.c_int64), ("pressure", _dp), ("sum_ab", _dp),
+                ("sum_ba", _dp), ("iters_sum", _i64p), ("unconverged", _i64p), ("max_res", _dp)]
+
+
 class Layer(C.Structure):
     """heat_layer (include/heat_amd_setup.h)"""
     _fields_ = [("is_gas", C.c_int32), ("gas", C.c_int32), ("thickness", _d), ("conductivity", _d), ("density", _d),
@@ -326,6 +335,11 @@ SYMBOLS = [
     ("heat_batch_march_series_controllers", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
                                                       _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp, C.POINTER(Openings), _dp,
                                                       C.POINTER(Controllers), _dp, _dp]),
+    ("heat_air_networks_check", C.c_int, [C.POINTER(Desc), C.POINTER(Series), C.POINTER(Openings), C.POINTER(Controllers),
+                                          C.POINTER(AirNetworks)]),
+    ("heat_batch_march_series_networks", C.c_int, [_H, C.POINTER(SeriesCall), C.POINTER(Comfort), _dp, _dp, C.POINTER(AirHandlers),
+                                                   _dp, _dp, _dp, _dp, C.POINTER(AirSpecies), _dp, _dp, _dp, C.POINTER(Openings), _dp,
+                                                   C.POINTER(Controllers), _dp, _dp, C.POINTER(AirNetworks), _dp, _dp, _i32p]),
     ("heat_batch_set_weather", C.c_int, [_H, C.POINTER(Weather), C.c_int32, _dp, _dp]),
     ("heat_batch_step_surfaces", C.c_int, [_H, C.c_int32]),
     ("heat_batch_step_zones", C.c_int, [_H, C.c_void_p, C.c_int32]),
@@ -482,7 +496,7 @@ HOST_ONLY_SYMBOLS = ("heat_partition", "heat_plan_check", "heat_plan_check_sites
                      "heat_series_report_check", "heat_ideal_loads_check", "heat_sky_check", "heat_solar_gains_check",
                      "heat_air_paths_check", "heat_shades_check", "heat_room_radiation_check", "heat_ambient_check",
                      "heat_blinds_check", "heat_sky_aniso_check", "heat_comfort_check", "heat_air_handlers_check",
-                     "heat_air_species_check", "heat_openings_check", "heat_controllers_check",
+                     "heat_air_species_check", "heat_openings_check", "heat_controllers_check", "heat_air_networks_check",
                      "heat_last_error", "heat_amd_abi_version")
 
 
@@ -1805,6 +1819,98 @@ def controllers_check(md, controllers, openings=None, lib=None, **series):
         raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
 
 
+NETWORK_STATE = ("pressure",)
+NETWORK_STATS = ("sum_ab", "sum_ba", "iters_sum", "unconverged", "max_res")
+# (name, dtype, needed, over): over 0 the networks, 1 the nodes, 2 the links
+_NETWORK_ROWS = (("tol", np.float64, True, 0), ("max_iter", np.int32, True, 0), ("g_min", np.float64, True, 0),
+                 ("node_zone", np.int32, True, 1), ("src_chan", np.int32, False, 1), ("src_gain", np.float64, False, 1),
+                 ("zone_a", np.int32, True, 2), ("zone_b", np.int32, True, 2), ("temp_chan", np.int32, True, 2), ("wp_chan", np.int32, False, 2),
+                 ("frac_chan", np.int32, False, 2), ("out_ab", np.int32, False, 2), ("out_ba", np.int32, False, 2), ("c", np.float64, True, 2),
+                 ("gh", np.float64, False, 2), ("p_lin", np.float64, True, 2), ("wp_gain", np.float64, False, 2))
+_NETWORK_ACC = dict(pressure=(np.float64, 1), sum_ab=(np.float64, 2), sum_ba=(np.float64, 2), iters_sum=(np.int64, 0), unconverged=(np.int64, 0),
+                    max_res=(np.float64, 0))
+
+
+def make_air_networks(net_offset=(0,), tol=(), max_iter=(), g_min=(), node_zone=(), zone_a=(), zone_b=(), temp_chan=(), c=(), p_lin=(),
+                      src_chan=None, src_gain=None, wp_chan=None, frac_chan=None, out_ab=None, out_ba=None, gh=None, wp_gain=None,
+                      state=NETWORK_STATE, stats=NETWORK_STATS, resume=None):
+    """Builds a heat_air_networks. Returns (networks, keepalive); the march updates the state and the accumulators in place.
+    net_offset       [n_networks + 1] network w owns the nodes net_offset[w] ... net_offset[w + 1] - 1; 1 to 64 nodes each
+    tol, max_iter, g_min
+                     [n_networks] the residual, kg/s, at which a solve stops; the most iterations, 1 ... 64; the conductance of
+                     every node to the datum, kg/s per Pa, > 0
+    node_zone        [n_nodes] the zone of every node; a zone is in at most one network
+    src_chan, src_gain
+                     [n_nodes] a net mechanical mass inflow src_gain * row[src_chan], kg/s (an extract fan is negative); None /
+                     -1: none; src_gain None = 1
+    zone_a, zone_b   [n_links] the link's zones; zone_b -1: outside
+    temp_chan        [n_links] the outside temperature's channel where zone_b is -1, else -1
+    wp_chan, wp_gain [n_links] outside links: the wind pressure at the link, wp_gain * row[wp_chan] Pa; None / -1: none
+    frac_chan        [n_links] the open fraction, clamped to [0, 1] (it may be a controller's output); None / -1: 1
+    out_ab, out_ba   [n_links] the DERIVED channels the link's volume flow a -> b and b -> a is written into; None / -1: none
+                     (air_networks.paths names the air paths that read them)
+    c, gh, p_lin     [n_links] the flow coefficient, m3/s per sqrt(Pa) (air_networks.orifice, tall_opening); 9.81 times the
+                     link's height above the network's datum (None = 0); the pressure difference below which the law is linear
+    state            names out of NETWORK_STATE that are returned (the device keeps the pressures either way)
+    stats            names out of NETWORK_STATS: which accumulators are maintained (default: all)
+    resume           a dict of arrays a previous series returned: the state and the accumulators start from them
+    (air_networks.apply and accumulate are the rule in numpy and take the same dict)"""
+    given = dict(tol=tol, max_iter=max_iter, g_min=g_min, node_zone=node_zone, src_chan=src_chan, src_gain=src_gain, zone_a=zone_a, zone_b=zone_b,
+                 temp_chan=temp_chan, wp_chan=wp_chan, frac_chan=frac_chan, out_ab=out_ab, out_ba=out_ba, c=c, gh=gh, p_lin=p_lin, wp_gain=wp_gain)
+    unknown = set(stats or ()) - set(NETWORK_STATS) | set(state or ()) - set(NETWORK_STATE)
+    if unknown:
+        raise ValueError("air networks: unknown state or stats %s (known: %s)" % (sorted(unknown), ", ".join(NETWORK_STATE + NETWORK_STATS)))
+    nw = AirNetworks()
+    keep = {}
+    off = np.ascontiguousarray(net_offset if net_offset is not None else (0,), dtype=np.int32).reshape(-1)
+    if off.size == 0:
+        off = np.zeros(1, np.int32)
+    n = (len(off) - 1, len(np.asarray(node_zone if node_zone is not None else ()).reshape(-1)),
+         len(np.asarray(zone_a if zone_a is not None else ()).reshape(-1)))
+    what = ("networks", "nodes", "links")
+    nw.n_networks, nw.n_nodes, nw.n_links = n
+    nw.resume = 0 if resume is None else 1
+    keep["net_offset"] = off
+    nw.net_offset = off.ctypes.data_as(_i32p)
+    for name, dtype, needed, over in _NETWORK_ROWS:
+        if given[name] is None and not needed:
+            continue
+        v = np.ascontiguousarray(given[name] if given[name] is not None else (), dtype=dtype).reshape(-1)
+        if v.shape != (n[over],):
+            raise ValueError("air networks %s: %s for %d %s" % (name, v.shape, n[over], what[over]))
+        keep[name] = v
+        setattr(nw, name, v.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if v.size else None)
+    for name in tuple(state or ()) + tuple(stats or ()):
+        dtype, over = _NETWORK_ACC[name]
+        if resume is not None:
+            if name not in resume:
+                raise ValueError("air networks resume: %s is missing" % name)
+            a = np.array(resume[name], dtype=dtype)  # (a copy: the march writes it)
+            if a.shape != (n[over],):
+                raise ValueError("air networks resume: %s of shape %s, not %s" % (name, a.shape, (n[over],)))
+        else:
+            a = np.zeros(n[over], dtype)  # (the library initialises on the device)
+        keep[name] = a
+        setattr(nw, name, a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(dtype))) if a.size else None)
+    return nw, keep
+
+
+def air_networks_check(md, networks, openings=None, controllers=None, lib=None, **series):
+    """heat_air_networks_check: everything about the air networks of a series, and about them beside its openings and
+    controllers, that needs no device (series arguments as HeatBatch.march_series; networks, openings, controllers: the
+    arguments of make_air_networks, make_openings and make_controllers, or None). Host-only."""
+    L = lib or load_library()
+    desc, keep = make_desc(md)
+    s, skeep = make_series(**series)
+    op, okeep = make_openings(**openings) if openings is not None else (None, None)
+    ct, ckeep = make_controllers(**controllers) if controllers is not None else (None, None)
+    nw, nkeep = make_air_networks(**networks) if networks is not None else (None, None)
+    ref = lambda x: C.byref(x) if x is not None else None  # noqa: E731
+    rc = L.heat_air_networks_check(C.byref(desc), C.byref(s), ref(op), ref(ct), ref(nw))
+    if rc != 0:
+        raise HeatError(rc, L.heat_last_error().decode("utf-8", "replace"))
+
+
 def comm_available():
     """Whether the library can load RCCL (no collective inside: vote on it before comm_init)."""
     return load_library().heat_comm_available() == 0
@@ -1930,7 +2036,8 @@ class HeatBatch:
                      air=None, path_q=True, shades=None, sunlit=True, radiation=None, irradiance=True, ambient=None, ambient_t=True,
                      blinds=None, position=True, blind_incident=True, aniso=None, comfort=None, operative=True, mrt=True,
                      handlers=None, supply_t=True, recovered=True, coil_q=True, branch_q=True, species=None, conc_rows=True,
-                     vent_v=True, vent_q=True, openings=None, opening_v=True, controllers=None, control_u=True, control_out=True, **series):
+                     vent_v=True, vent_q=True, openings=None, opening_v=True, controllers=None, control_u=True, control_out=True, networks=None,
+                     link_q=True, node_p=True, net_iters=True, **series):
         """heat_batch_march_series: n_steps caller timesteps of n_sub sub-timesteps in one call, inputs driven from
         schedules on the device (make_series names the arguments). Returns (trace [n_steps, n_probes], failed_step);
         a numerical failure raises HeatError carrying ``failed_step`` and the ``trace`` so far.
@@ -2016,7 +2123,14 @@ class HeatBatch:
         openings' fractions, the air paths and the driven inputs of the sides read as any channel. Returns what the same call
         without controllers returns plus one dict, appended last: control_u, control_out [n_steps, n_controllers] (each empty
         with its flag False), of CONTROLLER_STATE those in state and of CONTROLLER_STATS those in stats (pass them as
-        controllers["resume"] to the next series) — one more element of the tuple, or the key "controllers" of the dict."""
+        controllers["resume"] to the next series) — one more element of the tuple, or the key "controllers" of the dict.
+        networks (a dict of make_air_networks' arguments; an empty dict: no network): heat_batch_march_series_networks — per step
+        and per network the device solves the node pressures that balance the mass flows through all links, behind the
+        openings, and writes every link's volume flow into DERIVED channels, which the air paths read as any channel
+        (air_networks.paths). Returns what the same call without networks returns plus one dict, appended last: link_q
+        [n_steps, n_links], node_p [n_steps, n_nodes], net_iters [n_steps, n_networks] (each empty with its flag False), of
+        NETWORK_STATE those in state and of NETWORK_STATS those in stats (pass them as networks["resume"] to the next series)
+        — one more element of the tuple, or the key "networks" of the dict."""
         given = dict(loads=loads, report=report, ideal=ideal, sky=sky, gains=gains, air=air, shades=shades, radiation=radiation,
                      ambient=ambient, blinds=blinds)
         # The gains read the sky's records, and so do shades whose sky names no side: such a call gets a sky without mode bits.
@@ -2030,9 +2144,10 @@ class HeatBatch:
                                                                       supply_t=supply_t, recovered=recovered, coil_q=coil_q,
                                                                       branch_q=branch_q, conc_rows=conc_rows, vent_v=vent_v,
                                                                       vent_q=vent_q, opening_v=opening_v, control_u=control_u,
-                                                                      control_out=control_out),
+                                                                      control_out=control_out, link_q=link_q, node_p=node_p,
+                                                                      net_iters=net_iters),
                                   aniso=aniso, comfort=comfort, handlers=handlers, species=species, openings=openings,
-                                  controllers=controllers)
+                                  controllers=controllers, networks=networks)
 
     # The eleven entry points, widest last: the symbol and the optional terms it carries. A call goes to the narrowest that carries
     # what was passed; its arguments are _SERIES_ORDER (the header's order) cut down to those terms and their arrays.
@@ -2059,12 +2174,12 @@ class HeatBatch:
                          ambient=(make_ambient, "ambient_t", "n_sides"), blinds=(make_blinds, "position", "n_blinds"))
 
     def _march_series(self, weather, n_sub, series, given, want, aniso=None, comfort=None, handlers=None, species=None, openings=None,
-                      controllers=None):
+                      controllers=None, networks=None):
         """march_series behind its arguments: given maps every optional term to its dict or None, want the arrays of rows to
         whether they are recorded; aniso: the dict of make_sky_aniso's arguments or None; comfort: the dict of make_comfort's
         arguments or None; handlers: the dict of make_air_handlers' arguments or None; species: the dict of make_air_species'
         arguments or None; openings: the dict of make_openings' arguments or None; controllers: the dict of make_controllers'
-        arguments or None."""
+        arguments or None; networks: the dict of make_air_networks' arguments or None."""
         if given["report"] is None and given["ideal"] is None and not (want["trace"] and want["applied"]):
             raise ValueError("trace=False / applied=False need a report")
         s, keep = make_series(weather, n_sub, n_sites=self.n_sites, **series)
@@ -2116,7 +2231,7 @@ class HeatBatch:
             elif not is_struct and (name == "trace" or term_of[name] in carried):
                 args.append(rows[name].ctypes.data_as(_dp) if name in rows and rows[name].size else None)
         failed = C.c_int32(-1)
-        if aniso is not None or comfort is not None or handlers is not None or species is not None or openings is not None or controllers is not None:
+        if aniso is not None or comfort is not None or handlers is not None or species is not None or openings is not None or controllers is not None or networks is not None:
             # One struct, filled by name: the terms that were passed (the fields' names are the header's), the arrays of rows
             # that are recorded, and the anisotropic sky.
             call = SeriesCall(size=C.sizeof(SeriesCall), s=C.pointer(s), failed_step=C.pointer(failed))
@@ -2157,9 +2272,26 @@ class HeatBatch:
                 op, opkeep = make_openings(**openings)
                 oprows = np.zeros((s.n_steps if want["opening_v"] else 0, op.n_openings))
             spp = [ptr(sprows[k]) for k in ("conc_rows", "vent_v", "vent_q")] if sp is not None else [None] * 3
+            ct = None
             if controllers is not None:
                 ct, ctkeep = make_controllers(**controllers)
                 ctrows = {k: np.zeros((s.n_steps if want[k] else 0, ct.n_controllers)) for k in ("control_u", "control_out")}
+            if networks is not None:
+                nw, nwkeep = make_air_networks(**networks)
+                nwrows = dict(link_q=np.zeros((s.n_steps if want["link_q"] else 0, nw.n_links)),
+                              node_p=np.zeros((s.n_steps if want["node_p"] else 0, nw.n_nodes)),
+                              net_iters=np.zeros((s.n_steps if want["net_iters"] else 0, nw.n_networks), np.int32))
+                rc = self._L.heat_batch_march_series_networks(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
+                                                              ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
+                                                              C.byref(ah) if ah is not None else None, *hp,
+                                                              C.byref(sp) if sp is not None else None, *spp,
+                                                              C.byref(op) if op is not None else None, ptr(oprows) if op is not None else None,
+                                                              C.byref(ct) if ct is not None else None,
+                                                              ptr(ctrows["control_u"]) if ct is not None else None,
+                                                              ptr(ctrows["control_out"]) if ct is not None else None,
+                                                              C.byref(nw), ptr(nwrows["link_q"]), ptr(nwrows["node_p"]),
+                                                              nwrows["net_iters"].ctypes.data_as(_i32p) if nwrows["net_iters"].size else None)
+            elif controllers is not None:
                 rc = self._L.heat_batch_march_series_controllers(self._h, C.byref(call), C.byref(cf) if cf is not None else None,
                                                                  ptr(top_rows) if cf is not None else None, ptr(mrt_rows) if cf is not None else None,
                                                                  C.byref(ah) if ah is not None else None, *hp,
@@ -2223,6 +2355,8 @@ class HeatBatch:
             out += [("openings", dict(opening_v=oprows, **{k: opkeep[k] for k in OPENING_STATS if k in opkeep}))]
         if controllers is not None:
             out += [("controllers", dict(ctrows, **{k: ctkeep[k] for k in CONTROLLER_STATE + CONTROLLER_STATS if k in ctkeep}))]
+        if networks is not None:
+            out += [("networks", dict(nwrows, **{k: nwkeep[k] for k in NETWORK_STATE + NETWORK_STATS if k in nwkeep}))]
         return dict(out) if given["ideal"] is not None else tuple(v for _, v in out)
 
     def set_ambient(self, surfaces, sides, temperatures):

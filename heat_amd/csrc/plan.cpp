@@ -2610,6 +2610,315 @@ int check_controller_tables(const SeriesModel &m, int32_t n_channels, int64_t n_
     return HEAT_OK;
 }
 
+// ---- air networks of a series (include/heat_amd.h, heat_air_networks) ----
+namespace {
+inline double nw_f64(const double *list, int64_t i, double neutral) { return list ? list[i] : neutral; }
+inline int network_class(int n) { return n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : 3; }
+}  // namespace
+
+int check_air_networks(int64_t n_zones, int32_t n_channels, const heat_openings *op, const heat_controllers *ct, const heat_air_networks *nw,
+                       std::string &err) {
+    if (!nw) return HEAT_OK;
+    const int64_t W = nw->n_networks, N = nw->n_nodes, L = nw->n_links;
+    if (W < 0 || N < 0 || L < 0)
+        return failp(err, HEAT_E_INVALID_ARG, "negative count of air networks (n_networks %lld, n_nodes %lld, n_links %lld)", (long long)W,
+                     (long long)N, (long long)L);
+    if (W > INT32_MAX / 2 || N > INT32_MAX / 2 || L > INT32_MAX / 2)
+        return failp(err, HEAT_E_INVALID_ARG, "more than 2^30 air networks, nodes or links (n_networks %lld, n_nodes %lld, n_links %lld)",
+                     (long long)W, (long long)N, (long long)L);
+    if (W == 0) {
+        if (N != 0 || L != 0) return failp(err, HEAT_E_SIZE, "network 0: %lld nodes and %lld links without a network", (long long)N, (long long)L);
+        return HEAT_OK;
+    }
+    if (!nw->net_offset) return failp(err, HEAT_E_INVALID_ARG, "network 0: net_offset is NULL");
+    if (!nw->tol) return failp(err, HEAT_E_INVALID_ARG, "network 0: tol is NULL");
+    if (!nw->max_iter) return failp(err, HEAT_E_INVALID_ARG, "network 0: max_iter is NULL");
+    if (!nw->g_min) return failp(err, HEAT_E_INVALID_ARG, "network 0: g_min is NULL");
+    if (N > 0 && !nw->node_zone) return failp(err, HEAT_E_INVALID_ARG, "node 0: node_zone is NULL");
+    if (L > 0) {
+        if (!nw->zone_a) return failp(err, HEAT_E_INVALID_ARG, "link 0: zone_a is NULL");
+        if (!nw->zone_b) return failp(err, HEAT_E_INVALID_ARG, "link 0: zone_b is NULL");
+        if (!nw->temp_chan) return failp(err, HEAT_E_INVALID_ARG, "link 0: temp_chan is NULL");
+        if (!nw->c) return failp(err, HEAT_E_INVALID_ARG, "link 0: c is NULL");
+        if (!nw->p_lin) return failp(err, HEAT_E_INVALID_ARG, "link 0: p_lin is NULL");
+    }
+    // the networks' extents and numbers
+    if (nw->net_offset[0] != 0) return failp(err, HEAT_E_SIZE, "network 0: net_offset starts at %d, not at 0", nw->net_offset[0]);
+    for (int64_t w = 0; w < W; w++) {
+        const int64_t n = (int64_t)nw->net_offset[w + 1] - nw->net_offset[w];
+        if (n < 1 || n > kNetworkMaxNodes)
+            return failp(err, HEAT_E_SIZE, "network %lld: %lld nodes, outside [1, %d]", (long long)w, (long long)n, kNetworkMaxNodes);
+        if (nw->net_offset[w + 1] > N)
+            return failp(err, HEAT_E_SIZE, "network %lld: its nodes end at %d, beyond the %lld nodes", (long long)w, nw->net_offset[w + 1], (long long)N);
+        if (!std::isfinite(nw->tol[w]) || nw->tol[w] < 0.0)
+            return failp(err, HEAT_E_INVALID_ARG, "network %lld: tol %g is not finite or is negative", (long long)w, nw->tol[w]);
+        if (!std::isfinite(nw->g_min[w]) || !(nw->g_min[w] > 0.0))
+            return failp(err, HEAT_E_INVALID_ARG, "network %lld: g_min %g is not positive and finite", (long long)w, nw->g_min[w]);
+        if (nw->max_iter[w] < 1 || nw->max_iter[w] > kNetworkMaxNodes)
+            return failp(err, HEAT_E_INVALID_ARG, "network %lld: max_iter %d outside [1, %d]", (long long)w, nw->max_iter[w], kNetworkMaxNodes);
+    }
+    if (nw->net_offset[W] != N)
+        return failp(err, HEAT_E_SIZE, "network %lld: net_offset ends at %d, not at the %lld nodes", (long long)(W - 1), nw->net_offset[W], (long long)N);
+    // the nodes: a zone is in at most one network
+    std::vector<int32_t> net_of_zone((size_t)n_zones, -1);
+    for (int64_t w = 0; w < W; w++)
+        for (int64_t i = nw->net_offset[w]; i < nw->net_offset[w + 1]; i++) {
+            const int32_t z = nw->node_zone[i], sc = ct_i32(nw->src_chan, i, -1);
+            if (z < 0 || z >= n_zones) return failp(err, HEAT_E_SIZE, "node %lld: zone %d outside [0, %lld)", (long long)i, z, (long long)n_zones);
+            if (net_of_zone[(size_t)z] >= 0)
+                return failp(err, HEAT_E_SIZE, "node %lld: zone %d is a node of network %d already: a zone is in at most one network", (long long)i, z,
+                             net_of_zone[(size_t)z]);
+            net_of_zone[(size_t)z] = (int32_t)w;
+            if (sc < -1 || sc >= n_channels)
+                return failp(err, HEAT_E_SIZE, "node %lld: source channel %d outside [-1, %d)", (long long)i, sc, n_channels);
+            if (!std::isfinite(nw_f64(nw->src_gain, i, 1.0)))
+                return failp(err, HEAT_E_INVALID_ARG, "node %lld: src_gain %g is not finite", (long long)i, nw->src_gain[i]);
+            if (nw->resume && nw->pressure && !std::isfinite(nw->pressure[i]))
+                return failp(err, HEAT_E_INVALID_ARG, "node %lld: pressure %g is not finite", (long long)i, nw->pressure[i]);
+        }
+    // the links
+    std::vector<uint8_t> has_outside((size_t)W, 0);
+    for (int64_t l = 0; l < L; l++) {
+        const int32_t za = nw->zone_a[l], zb = nw->zone_b[l], tc = nw->temp_chan[l];
+        const int32_t wc = ct_i32(nw->wp_chan, l, -1), fc = ct_i32(nw->frac_chan, l, -1);
+        const int32_t oab = ct_i32(nw->out_ab, l, -1), oba = ct_i32(nw->out_ba, l, -1);
+        if (za < 0 || za >= n_zones) return failp(err, HEAT_E_SIZE, "link %lld: zone_a %d outside [0, %lld)", (long long)l, za, (long long)n_zones);
+        if (zb < -1 || zb >= n_zones) return failp(err, HEAT_E_SIZE, "link %lld: zone_b %d outside [-1, %lld)", (long long)l, zb, (long long)n_zones);
+        if (za == zb) return failp(err, HEAT_E_INVALID_ARG, "link %lld: zone_a == zone_b == %d", (long long)l, za);
+        const int32_t wa = net_of_zone[(size_t)za];
+        if (wa < 0) return failp(err, HEAT_E_SIZE, "link %lld: zone_a %d is in no network", (long long)l, za);
+        if (zb >= 0 && net_of_zone[(size_t)zb] != wa)
+            return failp(err, HEAT_E_SIZE, "link %lld: zone_a %d is in network %d and zone_b %d in %d: a link stays within one network", (long long)l, za, wa,
+                         zb, net_of_zone[(size_t)zb]);
+        if (zb < 0 && tc == -1) return failp(err, HEAT_E_SIZE, "link %lld: a link to outside without a temperature channel (temp_chan -1)", (long long)l);
+        if (zb >= 0 && (tc != -1 || wc != -1))
+            return failp(err, HEAT_E_SIZE, "link %lld: a link between zones with an outside channel (temp_chan %d, wp_chan %d)", (long long)l, tc, wc);
+        const int32_t chans[5] = {tc, wc, fc, oab, oba};
+        static const char *const cname[5] = {"temp_chan", "wp_chan", "frac_chan", "out_ab", "out_ba"};
+        for (int a = 0; a < 5; a++)
+            if (chans[a] < -1 || chans[a] >= n_channels)
+                return failp(err, HEAT_E_SIZE, "link %lld: %s %d outside [-1, %d)", (long long)l, cname[a], chans[a], n_channels);
+        const double real[2] = {nw->c[l], nw_f64(nw->gh, l, 0.0)};
+        static const char *const rname[2] = {"c", "gh"};
+        for (int a = 0; a < 2; a++)
+            if (!std::isfinite(real[a]) || real[a] < 0.0)
+                return failp(err, HEAT_E_INVALID_ARG, "link %lld: %s %g is not finite or is negative", (long long)l, rname[a], real[a]);
+        if (!std::isfinite(nw->p_lin[l]) || !(nw->p_lin[l] > 0.0))
+            return failp(err, HEAT_E_INVALID_ARG, "link %lld: p_lin %g is not positive and finite", (long long)l, nw->p_lin[l]);
+        if (!std::isfinite(nw_f64(nw->wp_gain, l, 1.0)))
+            return failp(err, HEAT_E_INVALID_ARG, "link %lld: wp_gain %g is not finite", (long long)l, nw->wp_gain[l]);
+        if (zb < 0) has_outside[(size_t)wa] = 1;
+    }
+    for (int64_t w = 0; w < W; w++)
+        if (!has_outside[(size_t)w])
+            return failp(err, HEAT_E_SIZE, "network %lld: no link to outside: its pressures have no reference", (long long)w);
+    // every derived channel has one writer among the controllers, the openings and the links ...
+    std::vector<int32_t> link_of((size_t)n_channels, -1), opening((size_t)n_channels, -1), controller((size_t)n_channels, -1);
+    const int64_t n_op = op ? op->n_openings : 0, n_ct = ct ? ct->n_controllers : 0;
+    for (int64_t j = 0; j < n_op; j++) opening[(size_t)op->out_chan[j]] = (int32_t)j;
+    for (int64_t j = 0; j < n_ct; j++) controller[(size_t)ct->out_chan[j]] = (int32_t)j;
+    for (int64_t l = 0; l < L; l++) {
+        const int32_t out[2] = {ct_i32(nw->out_ab, l, -1), ct_i32(nw->out_ba, l, -1)};
+        for (int a = 0; a < 2; a++) {
+            const int32_t oc = out[a];
+            if (oc < 0) continue;
+            if (link_of[(size_t)oc] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %lld: its derived channel %s %d is also link %d's: a derived channel has one writer", (long long)l,
+                             a ? "out_ba" : "out_ab", oc, link_of[(size_t)oc]);
+            if (opening[(size_t)oc] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %lld: its derived channel %s %d is also opening %d's: a derived channel has one writer", (long long)l,
+                             a ? "out_ba" : "out_ab", oc, opening[(size_t)oc]);
+            if (controller[(size_t)oc] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %lld: its derived channel %s %d is also controller %d's: a derived channel has one writer",
+                             (long long)l, a ? "out_ba" : "out_ab", oc, controller[(size_t)oc]);
+            link_of[(size_t)oc] = (int32_t)l;
+        }
+    }
+    // ... a network reads no opening's and no network's (a controller's it may) ...
+    for (int64_t l = 0; l < L; l++) {
+        const int32_t read[3] = {nw->temp_chan[l], ct_i32(nw->wp_chan, l, -1), ct_i32(nw->frac_chan, l, -1)};
+        static const char *const name[3] = {"temp_chan", "wp_chan", "frac_chan"};
+        for (int a = 0; a < 3; a++) {
+            if (read[a] < 0) continue;
+            if (link_of[(size_t)read[a]] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %lld: its %s %d is the derived channel of link %d: a network never reads a network", (long long)l,
+                             name[a], read[a], link_of[(size_t)read[a]]);
+            if (opening[(size_t)read[a]] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %lld: its %s %d is the derived channel of opening %d: a network never reads an opening", (long long)l,
+                             name[a], read[a], opening[(size_t)read[a]]);
+        }
+    }
+    for (int64_t i = 0; i < N; i++) {
+        const int32_t sc = ct_i32(nw->src_chan, i, -1);
+        if (sc < 0) continue;
+        if (link_of[(size_t)sc] >= 0)
+            return failp(err, HEAT_E_SIZE, "node %lld: its src_chan %d is the derived channel of link %d: a network never reads a network", (long long)i, sc,
+                         link_of[(size_t)sc]);
+        if (opening[(size_t)sc] >= 0)
+            return failp(err, HEAT_E_SIZE, "node %lld: its src_chan %d is the derived channel of opening %d: a network never reads an opening", (long long)i,
+                         sc, opening[(size_t)sc]);
+    }
+    // ... and no opening and no controller reads a network's: the networks run behind both
+    for (int64_t j = 0; j < n_op; j++) {
+        const int32_t read[3] = {ct_i32(op->temp_chan, j, -1), ct_i32(op->wind_chan, j, -1), ct_i32(op->frac_chan, j, -1)};
+        for (int a = 0; a < 3; a++)
+            if (read[a] >= 0 && link_of[(size_t)read[a]] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %d: its derived channel %d is read by opening %lld: the networks run behind the openings",
+                             link_of[(size_t)read[a]], read[a], (long long)j);
+    }
+    for (int64_t j = 0; j < n_ct; j++) {
+        const int32_t sk = ct_i32(ct->sense_kind, j, 0), lk = ct_i32(ct->lim_kind, j, -1);
+        const int32_t read[4] = {sk == 2 ? ct->sense_index[j] : -1, ct->set_chan[j], ct_i32(ct->en_chan, j, -1), lk == 2 ? ct->lim_index[j] : -1};
+        for (int a = 0; a < 4; a++)
+            if (read[a] >= 0 && link_of[(size_t)read[a]] >= 0)
+                return failp(err, HEAT_E_SIZE, "link %d: its derived channel %d is read by controller %lld: the networks run behind the controllers",
+                             link_of[(size_t)read[a]], read[a], (long long)j);
+    }
+    return HEAT_OK;
+}
+
+void build_network_tables(const heat_air_networks *nw, NetworkTables &t) {
+    t = NetworkTables();
+    const size_t W = nw ? (size_t)nw->n_networks : 0, N = nw ? (size_t)nw->n_nodes : 0, L = nw ? (size_t)nw->n_links : 0;
+    t.n_networks = (int64_t)W, t.n_nodes = (int64_t)N, t.n_links = (int64_t)L;
+    t.net_i32.assign((size_t)kNetworkNetI32Rows * W, 0);
+    t.net_f64.assign((size_t)kNetworkNetF64Rows * W, 0.0);
+    t.node_i32.assign((size_t)kNetworkNodeI32Rows * N, -1);
+    t.node_f64.assign(N, 1.0);
+    t.link_i32.assign((size_t)kNetworkLinkI32Rows * L, -1);
+    t.link_f64.assign((size_t)kNetworkLinkF64Rows * L, 0.0);
+    if (W == 0) return;
+    // the networks by width class, the caller's order within a class; their nodes behind one another
+    int32_t count[kNetworkClasses] = {0, 0, 0, 0};
+    for (size_t w = 0; w < W; w++) count[network_class(nw->net_offset[w + 1] - nw->net_offset[w])]++;
+    for (int c = 0; c < kNetworkClasses; c++) t.class_start[c + 1] = t.class_start[c] + count[c];
+    int32_t next[kNetworkClasses];
+    for (int c = 0; c < kNetworkClasses; c++) next[c] = t.class_start[c];
+    std::vector<int32_t> sorted_of_net(W);
+    for (size_t w = 0; w < W; w++) sorted_of_net[w] = next[network_class(nw->net_offset[w + 1] - nw->net_offset[w])]++;
+    std::vector<int32_t> net_at(W);
+    for (size_t w = 0; w < W; w++) net_at[(size_t)sorted_of_net[w]] = (int32_t)w;
+    int32_t *const NI = t.net_i32.data();
+    int32_t *const DI = t.node_i32.data();
+    std::vector<int32_t> sorted_of_node(N), local_of_node(N);
+    int32_t at = 0;
+    for (size_t s = 0; s < W; s++) {
+        const size_t w = (size_t)net_at[s];
+        const int32_t n = nw->net_offset[w + 1] - nw->net_offset[w];
+        NI[NW_ID * W + s] = (int32_t)w, NI[NW_N * W + s] = n, NI[NW_NODE0 * W + s] = at, NI[NW_MAX_ITER * W + s] = nw->max_iter[w];
+        t.net_f64[NW_TOL * W + s] = nw->tol[w], t.net_f64[NW_G_MIN * W + s] = nw->g_min[w];
+        for (int32_t i = 0; i < n; i++) {
+            const size_t id = (size_t)nw->net_offset[w] + (size_t)i, p = (size_t)at + (size_t)i;
+            sorted_of_node[id] = (int32_t)p, local_of_node[id] = i;
+            DI[ND_ID * N + p] = (int32_t)id, DI[ND_ZONE * N + p] = nw->node_zone[id], DI[ND_SRC_CHAN * N + p] = ct_i32(nw->src_chan, (int64_t)id, -1);
+            t.node_f64[p] = nw_f64(nw->src_gain, (int64_t)id, 1.0);
+        }
+        at += n;
+    }
+    // the links in the caller's order, their nodes as local numbers; every node's incident links, ascending
+    std::vector<int32_t> node_of_zone;
+    for (size_t id = 0; id < N; id++) {
+        const size_t z = (size_t)nw->node_zone[id];
+        if (z >= node_of_zone.size()) node_of_zone.resize(z + 1, -1);
+        node_of_zone[z] = (int32_t)id;
+    }
+    int32_t *const KI = t.link_i32.data();
+    double *const KF = t.link_f64.data();
+    std::vector<int32_t> degree(N, 0);
+    for (size_t l = 0; l < L; l++) {
+        const int32_t za = nw->zone_a[l], zb = nw->zone_b[l];
+        const int32_t a = node_of_zone[(size_t)za], b = zb >= 0 ? node_of_zone[(size_t)zb] : -1;
+        KI[LK_ZONE_A * L + l] = za, KI[LK_ZONE_B * L + l] = zb;
+        KI[LK_LA * L + l] = local_of_node[(size_t)a], KI[LK_LB * L + l] = b >= 0 ? local_of_node[(size_t)b] : -1;
+        KI[LK_TEMP_CHAN * L + l] = nw->temp_chan[l], KI[LK_WP_CHAN * L + l] = ct_i32(nw->wp_chan, (int64_t)l, -1);
+        KI[LK_FRAC_CHAN * L + l] = ct_i32(nw->frac_chan, (int64_t)l, -1);
+        KI[LK_OUT_AB * L + l] = ct_i32(nw->out_ab, (int64_t)l, -1), KI[LK_OUT_BA * L + l] = ct_i32(nw->out_ba, (int64_t)l, -1);
+        KF[LK_C * L + l] = nw->c[l], KF[LK_GH * L + l] = nw_f64(nw->gh, (int64_t)l, 0.0), KF[LK_P_LIN * L + l] = nw->p_lin[l];
+        KF[LK_S_LIN * L + l] = std::sqrt(nw->p_lin[l]), KF[LK_WP_GAIN * L + l] = nw_f64(nw->wp_gain, (int64_t)l, 1.0);
+        degree[(size_t)sorted_of_node[(size_t)a]]++;
+        if (b >= 0) degree[(size_t)sorted_of_node[(size_t)b]]++;
+    }
+    int32_t first = 0;
+    for (size_t p = 0; p < N; p++) {
+        DI[ND_INC0 * N + p] = first, DI[ND_INC_N * N + p] = 0;
+        first += degree[p];
+    }
+    t.inc.assign((size_t)first, -1);
+    for (size_t l = 0; l < L; l++) {
+        const int32_t zb = nw->zone_b[l];
+        const int32_t ends[2] = {node_of_zone[(size_t)nw->zone_a[l]], zb >= 0 ? node_of_zone[(size_t)zb] : -1};
+        for (int a = 0; a < 2; a++) {
+            if (ends[a] < 0) continue;
+            const size_t p = (size_t)sorted_of_node[(size_t)ends[a]];
+            t.inc[(size_t)DI[ND_INC0 * N + p] + (size_t)DI[ND_INC_N * N + p]++] = (int32_t)l;
+        }
+    }
+}
+
+int check_network_tables(int64_t n_zones, int32_t n_channels, const heat_air_networks *nw, const NetworkTables &t, std::string &err) {
+    const size_t W = nw ? (size_t)nw->n_networks : 0, N = nw ? (size_t)nw->n_nodes : 0, L = nw ? (size_t)nw->n_links : 0;
+    if (t.n_networks != (int64_t)W || t.n_nodes != (int64_t)N || t.n_links != (int64_t)L || t.net_i32.size() != (size_t)kNetworkNetI32Rows * W ||
+        t.net_f64.size() != (size_t)kNetworkNetF64Rows * W || t.node_i32.size() != (size_t)kNetworkNodeI32Rows * N || t.node_f64.size() != N ||
+        t.link_i32.size() != (size_t)kNetworkLinkI32Rows * L || t.link_f64.size() != (size_t)kNetworkLinkF64Rows * L)
+        return failp(err, HEAT_E_SIZE, "network tables: their sizes are not those of %zu networks, %zu nodes and %zu links", W, N, L);
+    if (W == 0) return HEAT_OK;
+    if (t.class_start[0] != 0 || t.class_start[kNetworkClasses] != (int32_t)W)
+        return failp(err, HEAT_E_SIZE, "network tables: the classes hold [%d, %d), not the %zu networks", t.class_start[0], t.class_start[kNetworkClasses], W);
+    std::vector<uint8_t> seen_net(W, 0), seen_node(N, 0);
+    int64_t at = 0;
+    for (int c = 0; c < kNetworkClasses; c++) {
+        if (t.class_start[c + 1] < t.class_start[c]) return failp(err, HEAT_E_SIZE, "network tables: class %d ends before it starts", c);
+        for (int32_t s = t.class_start[c]; s < t.class_start[c + 1]; s++) {
+            const int32_t w = t.net(NW_ID)[s], n = t.net(NW_N)[s];
+            if (w < 0 || (size_t)w >= W || seen_net[(size_t)w]++) return failp(err, HEAT_E_SIZE, "network tables: network %d is listed twice or is none", w);
+            if (n != nw->net_offset[w + 1] - nw->net_offset[w] || n < 1 || n > (8 << c) || (c > 0 && n <= (4 << c)))
+                return failp(err, HEAT_E_SIZE, "network tables: network %d: %d nodes in the class of %d lanes", w, n, 8 << c);
+            if (t.net(NW_NODE0)[s] != at || at + n > (int64_t)N) return failp(err, HEAT_E_SIZE, "network tables: network %d: its nodes are not behind the last", w);
+            if (t.net(NW_MAX_ITER)[s] != nw->max_iter[w] || t.net(NW_MAX_ITER)[s] < 1 || t.net(NW_MAX_ITER)[s] > kNetworkMaxNodes ||
+                std::memcmp(&t.net_f64[NW_TOL * W + (size_t)s], &nw->tol[w], sizeof(double)) != 0 ||
+                std::memcmp(&t.net_f64[NW_G_MIN * W + (size_t)s], &nw->g_min[w], sizeof(double)) != 0)
+                return failp(err, HEAT_E_SIZE, "network tables: network %d: tol, max_iter or g_min is not the caller's", w);
+            for (int32_t i = 0; i < n; i++) {
+                const size_t p = (size_t)(at + i);
+                const int32_t id = t.node(ND_ID)[p], sc = t.node(ND_SRC_CHAN)[p];
+                if (id != nw->net_offset[w] + i || seen_node[(size_t)id]++) return failp(err, HEAT_E_SIZE, "network tables: node %d is not in its network's place", id);
+                if (t.node(ND_ZONE)[p] != nw->node_zone[id] || (int64_t)(uint32_t)t.node(ND_ZONE)[p] >= n_zones || sc != ct_i32(nw->src_chan, id, -1) ||
+                    sc < -1 || sc >= n_channels)
+                    return failp(err, HEAT_E_SIZE, "network tables: node %d: its zone or source channel is not the caller's or lies outside its array", id);
+                const int32_t i0 = t.node(ND_INC0)[p], in = t.node(ND_INC_N)[p];
+                if (i0 < 0 || in < 0 || (size_t)i0 + (size_t)in > t.inc.size()) return failp(err, HEAT_E_SIZE, "network tables: node %d: its links lie outside the list", id);
+                for (int32_t e = 0; e < in; e++) {
+                    const int32_t l = t.inc[(size_t)(i0 + e)];
+                    if (l < 0 || (size_t)l >= L || (e > 0 && l <= t.inc[(size_t)(i0 + e - 1)]))
+                        return failp(err, HEAT_E_SIZE, "network tables: node %d: its links are not ascending links", id);
+                    if (t.link(LK_ZONE_A)[l] != nw->node_zone[id] && t.link(LK_ZONE_B)[l] != nw->node_zone[id])
+                        return failp(err, HEAT_E_SIZE, "network tables: node %d: link %d does not touch it", id, l);
+                    if ((t.link(LK_ZONE_A)[l] == nw->node_zone[id] ? t.link(LK_LA)[l] : t.link(LK_LB)[l]) != i)
+                        return failp(err, HEAT_E_SIZE, "network tables: node %d: link %d names it by another local number", id, l);
+                }
+            }
+            at += n;
+        }
+    }
+    size_t ends = 0;
+    for (size_t l = 0; l < L; l++) {
+        const int32_t za = t.link(LK_ZONE_A)[l], zb = t.link(LK_ZONE_B)[l], la = t.link(LK_LA)[l], lb = t.link(LK_LB)[l];
+        if (za != nw->zone_a[l] || zb != nw->zone_b[l] || (int64_t)(uint32_t)za >= n_zones || zb < -1 || zb >= n_zones || la < 0 ||
+            la >= kNetworkMaxNodes || lb < -1 || lb >= kNetworkMaxNodes || (lb < 0) != (zb < 0))
+            return failp(err, HEAT_E_SIZE, "network tables: link %zu: a zone or a local node number is not the caller's or lies outside its array", l);
+        static const int chan_row[5] = {LK_TEMP_CHAN, LK_WP_CHAN, LK_FRAC_CHAN, LK_OUT_AB, LK_OUT_BA};
+        for (int a = 0; a < 5; a++)
+            if (t.link(chan_row[a])[l] < -1 || t.link(chan_row[a])[l] >= n_channels || (a == 0 && zb < 0 && t.link(chan_row[a])[l] < 0))
+                return failp(err, HEAT_E_SIZE, "network tables: link %zu: a channel lies outside the row", l);
+        const double s_lin = std::sqrt(nw->p_lin[l]);
+        if (std::memcmp(&t.link_real(LK_C)[l], &nw->c[l], sizeof(double)) != 0 || std::memcmp(&t.link_real(LK_S_LIN)[l], &s_lin, sizeof(double)) != 0)
+            return failp(err, HEAT_E_SIZE, "network tables: link %zu: c or sqrt(p_lin) is not the caller's", l);
+        ends += zb >= 0 ? 2 : 1;
+    }
+    if (ends != t.inc.size()) return failp(err, HEAT_E_SIZE, "network tables: %zu incidences for %zu link ends", t.inc.size(), ends);
+    return HEAT_OK;
+}
+
 // ---- ideal loads of a series (include/heat_amd.h, heat_ideal_loads) ----
 int check_ideal_loads(int64_t n_zones, int32_t n_channels, const heat_ideal_loads *il, std::string &err,
                       std::vector<int32_t> *load_of_zone) {
@@ -3850,6 +4159,18 @@ int heat_controllers_check(const heat_batch_desc *desc, const heat_series *s, co
     const int64_t *const node_offset = desc->node_offset;
     heat::build_controller_tables(m, ct, [node_offset](int64_t q, int node) { return (uint32_t)(node_offset[q] + node); }, t);
     return heat::check_controller_tables(m, s->n_channels, node_offset[desc->n_surfaces], ct, t, heat::last_error());
+}
+
+int heat_air_networks_check(const heat_batch_desc *desc, const heat_series *s, const heat_openings *op, const heat_controllers *ct,
+                            const heat_air_networks *nw) {
+    int rc = heat_controllers_check(desc, s, op, ct);
+    if (rc) return rc;
+    rc = heat::check_air_networks(desc->n_zones, s->n_channels, op, ct, nw, heat::last_error());
+    if (rc || !nw) return rc;
+    // ... and the tables the march would upload, built and checked against the caller's lists (this is the build the sanitizers see)
+    heat::NetworkTables t;
+    heat::build_network_tables(nw, t);
+    return heat::check_network_tables(desc->n_zones, s->n_channels, nw, t, heat::last_error());
 }
 
 int heat_series_report_check(const heat_batch_desc *desc, const heat_series *s, const heat_zone_loads *l,

@@ -305,6 +305,47 @@ void build_controller_tables(const SeriesModel &m, const heat_controllers *ct, c
 int check_controller_tables(const SeriesModel &m, int32_t n_channels, int64_t n_nodes, const heat_controllers *ct, const ControllerTables &t,
                             std::string &err);
 
+// Air networks of a series (heat_air_networks, include/heat_amd.h). Everything heat_air_networks_check promises about the term
+// itself and about it beside the openings `op` and the controllers `ct` (nullable; they have passed their checks);
+// nw == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "network w", "node i" or "link l".
+int check_air_networks(int64_t n_zones, int32_t n_channels, const heat_openings *op, const heat_controllers *ct, const heat_air_networks *nw,
+                       std::string &err);
+// The tables of k_series_networks<W> (one lane per node, W = 8, 16, 32 or 64 lanes per network by its node count). The networks
+// are SORTED by width class (stable: the caller's order within a class) and their nodes follow them; class c (W = 8 << c)
+// holds the sorted networks [class_start[c], class_start[c + 1]). NW_ID / ND_ID: the caller's number of a sorted network or
+// node — the index the outputs and the state go through. ND_INC0 / ND_INC_N: the node's incident links in `inc`, ascending
+// link number (the order in which its balance is summed). The links stay in the caller's order; LK_LA / LK_LB: the local
+// numbers of their nodes within the network (LK_LB -1: outside). A NULL list holds its neutral value (a channel -1, a gain 1,
+// gh 0). LK_S_LIN = sqrt(p_lin), formed here once.
+enum NetworkNetI32 : int { NW_ID, NW_N, NW_NODE0, NW_MAX_ITER, kNetworkNetI32Rows };
+enum NetworkNetF64 : int { NW_TOL, NW_G_MIN, kNetworkNetF64Rows };
+enum NetworkNodeI32 : int { ND_ID, ND_ZONE, ND_SRC_CHAN, ND_INC0, ND_INC_N, kNetworkNodeI32Rows };
+enum NetworkLinkI32 : int { LK_ZONE_A, LK_ZONE_B, LK_LA, LK_LB, LK_TEMP_CHAN, LK_WP_CHAN, LK_FRAC_CHAN, LK_OUT_AB, LK_OUT_BA, kNetworkLinkI32Rows };
+enum NetworkLinkF64 : int { LK_C, LK_GH, LK_P_LIN, LK_S_LIN, LK_WP_GAIN, kNetworkLinkF64Rows };
+constexpr int kNetworkClasses = 4;
+constexpr int kNetworkMaxNodes = 64;
+struct NetworkTables {
+    int64_t n_networks = 0, n_nodes = 0, n_links = 0;
+    int32_t class_start[kNetworkClasses + 1] = {0, 0, 0, 0, 0};
+    std::vector<int32_t> net_i32;   // [kNetworkNetI32Rows][n_networks], sorted
+    std::vector<double> net_f64;    // [kNetworkNetF64Rows][n_networks], sorted
+    std::vector<int32_t> node_i32;  // [kNetworkNodeI32Rows][n_nodes], sorted
+    std::vector<double> node_f64;   // [n_nodes] src_gain, sorted
+    std::vector<int32_t> inc;       // the incident links of every sorted node
+    std::vector<int32_t> link_i32;  // [kNetworkLinkI32Rows][n_links], the caller's order
+    std::vector<double> link_f64;   // [kNetworkLinkF64Rows][n_links]
+    const int32_t *net(int a) const { return net_i32.data() + a * n_networks; }
+    const int32_t *node(int a) const { return node_i32.data() + a * n_nodes; }
+    const int32_t *link(int a) const { return link_i32.data() + a * n_links; }
+    const double *link_real(int a) const { return link_f64.data() + a * n_links; }
+};
+// (of a term that passed check_air_networks)
+void build_network_tables(const heat_air_networks *nw, NetworkTables &t);
+// The tables against the caller's lists (used by the host-only check): the classes a partition of the networks with every
+// network inside its width, the nodes and networks permutations, every zone, channel, link and local node number a lane would
+// use inside its array, every incidence list ascending and of links that touch its node. HEAT_OK or HEAT_E_SIZE.
+int check_network_tables(int64_t n_zones, int32_t n_channels, const heat_air_networks *nw, const NetworkTables &t, std::string &err);
+
 // Ideal loads of a series (heat_ideal_loads, include/heat_amd.h). Everything heat_ideal_loads_check promises about the loads
 // themselves; il == nullptr is none. HEAT_OK or a negative heat_status with `err` set, naming "ideal load i".
 // load_of_zone (nullable): [n_zones], the load of every zone or -1 — the table k_zone_update_ideal looks its zone up in.

@@ -980,6 +980,77 @@ struct ControllersTerm {
     }
 };
 
+// The air networks (heat_air_networks): the tables sorted by width class (plan.hpp, NetworkTables), the pressures (always on the
+// device: uploaded on resume where the caller holds them, else zeroed there), the accumulators (uploaded on resume, else
+// started on the device) and the link_q, node_p and net_iters rows, all in the caller's order. Nothing of it exists on the
+// device without networks.
+struct NetworksTerm {
+    heat_air_networks *nw = nullptr;
+    int64_t NW = 0, NN = 0, NK = 0;
+    NetworkTables nt;
+    DevBuf<int32_t> net_i32, node_i32, inc, link_i32, iters;   // iters: [n_steps][NW]
+    DevBuf<double> net_f64, node_f64, link_f64, pressure, q, p; // q: [n_steps][NK]; p: [n_steps][NN]
+    Acc<double> acc_f64[3];       // sum_ab, sum_ba, max_res
+    Acc<int64_t> acc_i64[2];      // iters_sum, unconverged
+    NetworksDev view{};
+    int prepare(int64_t n_zones, int32_t n_channels, heat_air_networks *nw_) {
+        nw = nw_;
+        NW = nw ? nw->n_networks : 0;
+        if (NW == 0) return HEAT_OK;
+        NN = nw->n_nodes, NK = nw->n_links;
+        build_network_tables(nw, nt);
+        // (every index a lane uses lies inside its array: a kernel that wrote out of bounds would not fail alone)
+        SERIES_TRY(check_network_tables(n_zones, n_channels, nw, nt, heat::last_error()));
+        acc_f64[0].bind(nw->sum_ab, 0.0, &view.sum_ab), acc_f64[1].bind(nw->sum_ba, 0.0, &view.sum_ba), acc_f64[2].bind(nw->max_res, 0.0, &view.max_res);
+        acc_i64[0].bind(nw->iters_sum, 0, &view.iters_sum), acc_i64[1].bind(nw->unconverged, 0, &view.unconverged);
+        return HEAT_OK;
+    }
+    int upload(const double *host_q, const double *host_p, const int32_t *host_iters, int n_steps) {
+        if (NW == 0) return HEAT_OK;
+        const bool resume = nw->resume != 0;
+        SERIES_TRY(series_upload(net_i32, nt.net_i32, "network tables"));
+        SERIES_TRY(series_upload(net_f64, nt.net_f64, "network tables"));
+        SERIES_TRY(series_upload(node_i32, nt.node_i32, "network tables"));
+        SERIES_TRY(series_upload(node_f64, nt.node_f64, "network tables"));
+        SERIES_TRY(series_upload(inc, nt.inc, "network tables"));
+        SERIES_TRY(series_upload(link_i32, nt.link_i32, "network tables"));
+        SERIES_TRY(series_upload(link_f64, nt.link_f64, "network tables"));
+        SERIES_TRY(series_alloc(pressure, (size_t)NN, "network pressures", resume ? nw->pressure : nullptr));
+        for (size_t a = 0; a < 2; a++) SERIES_TRY(acc_f64[a].stage((size_t)NK, resume, "network accumulators"));
+        SERIES_TRY(acc_f64[2].stage((size_t)NW, resume, "network accumulators"));
+        for (auto &a : acc_i64) SERIES_TRY(a.stage((size_t)NW, resume, "network accumulators"));
+        if (host_q) SERIES_TRY(series_alloc(q, (size_t)n_steps * NK, "network link flows"));
+        if (host_p) SERIES_TRY(series_alloc(p, (size_t)n_steps * NN, "network node pressures"));
+        if (host_iters) SERIES_TRY(series_alloc(iters, (size_t)n_steps * NW, "network iteration counts"));
+        for (int c = 0; c <= kNetworkClasses; c++) view.class_start[c] = nt.class_start[c];
+        view.n_nodes = (int)NN, view.n_links = (int)NK;
+        view.net_id = net_i32.p + NW_ID * NW, view.net_n = net_i32.p + NW_N * NW, view.net_node0 = net_i32.p + NW_NODE0 * NW;
+        view.net_max_iter = net_i32.p + NW_MAX_ITER * NW, view.net_tol = net_f64.p + NW_TOL * NW, view.net_g_min = net_f64.p + NW_G_MIN * NW;
+        view.node_id = node_i32.p + ND_ID * NN, view.node_zone = node_i32.p + ND_ZONE * NN, view.node_src_chan = node_i32.p + ND_SRC_CHAN * NN;
+        view.node_inc0 = node_i32.p + ND_INC0 * NN, view.node_inc_n = node_i32.p + ND_INC_N * NN, view.node_src_gain = node_f64.p, view.inc = inc.p;
+        view.zone_a = link_i32.p + LK_ZONE_A * NK, view.zone_b = link_i32.p + LK_ZONE_B * NK, view.la = link_i32.p + LK_LA * NK;
+        view.lb = link_i32.p + LK_LB * NK, view.temp_chan = link_i32.p + LK_TEMP_CHAN * NK, view.wp_chan = link_i32.p + LK_WP_CHAN * NK;
+        view.frac_chan = link_i32.p + LK_FRAC_CHAN * NK, view.out_ab = link_i32.p + LK_OUT_AB * NK, view.out_ba = link_i32.p + LK_OUT_BA * NK;
+        view.c = link_f64.p + LK_C * NK, view.gh = link_f64.p + LK_GH * NK, view.p_lin = link_f64.p + LK_P_LIN * NK;
+        view.s_lin = link_f64.p + LK_S_LIN * NK, view.wp_gain = link_f64.p + LK_WP_GAIN * NK;
+        view.pressure = pressure.p;
+        return HEAT_OK;
+    }
+    hipError_t start(hipStream_t st) {
+        if (NW == 0) return hipSuccess;
+        const bool resume = nw->resume != 0;
+        hipError_t e = hipSuccess;
+        if (!(resume && nw->pressure)) e = hipMemsetAsync(pressure.p, 0, (size_t)NN * sizeof(double), st);
+        return resume ? e : for_each_acc(acc_i64, &Acc<int64_t>::start, st, for_each_acc(acc_f64, &Acc<double>::start, st, e));
+    }
+    hipError_t fetch(double *host_q, double *host_p, int32_t *host_iters, hipStream_t st) {
+        if (NW == 0) return hipSuccess;
+        hipError_t e = series_fetch(host_iters, iters, st, series_fetch(host_p, p, st, series_fetch(host_q, q, st)));
+        e = series_fetch(nw->pressure, pressure, st, e);
+        return for_each_acc(acc_i64, &Acc<int64_t>::fetch, st, for_each_acc(acc_f64, &Acc<double>::fetch, st, e));
+    }
+};
+
 // The anisotropic sky (heat_sky_aniso): the coefficient table as given, beside the record table, and the bands of the three
 // consumers — the sides' per DEVICE surface, the apertures' and the shades' in the caller's order as their tables are; zeros
 // where the caller gave none. Absent (every pointer NULL) without aniso: the isotropic kernels are launched.
@@ -1102,6 +1173,9 @@ struct SeriesCall {
     double *opening_v = nullptr;
     heat_controllers *controllers = nullptr;
     double *control_u = nullptr, *control_out = nullptr;
+    heat_air_networks *networks = nullptr;
+    double *link_q = nullptr, *node_p = nullptr;
+    int32_t *net_iters = nullptr;
     int32_t *failed_step = nullptr;
     bool no_trace_ok = false;
 };
@@ -1148,6 +1222,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = check_air_species(b->n_zones, s->n_channels, c.species, heat::last_error()))) return rc;
     if ((rc = check_openings(b->n_zones, s->n_channels, c.openings, heat::last_error()))) return rc;
     if ((rc = check_controllers(m, s->n_channels, c.openings, c.controllers, heat::last_error()))) return rc;
+    if ((rc = check_air_networks(b->n_zones, s->n_channels, c.openings, c.controllers, c.networks, heat::last_error()))) return rc;
     const int64_t S = b->n_surf, Z = b->n_zones, P = s->n_probes, n_sites = b->n_sites;
     const int n_steps = s->n_steps, n_sub = s->n_sub, NC = s->n_channels;
     if (!c.trace && !c.no_trace_ok && (int64_t)n_steps * P > 0) return fail(HEAT_E_INVALID_ARG, "trace is NULL");
@@ -1179,6 +1254,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     SpeciesTerm species;
     OpeningsTerm openings;
     ControllersTerm controllers;
+    NetworksTerm networks;
     in.prepare(b, s);
     sky.prepare(b, c.sky, in);
     gains.prepare(b, c.gains, in);
@@ -1197,9 +1273,10 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     species.prepare(b, c.handlers, c.species);
     openings.prepare(c.openings);
     if ((rc = controllers.prepare(b, m, c.controllers))) return rc;
+    if ((rc = networks.prepare(b->n_zones, s->n_channels, c.networks))) return rc;
     const int64_t NT = loads.NT, NI = ideal.NI, NA = gains.NA, NS = shades.NS, NR = radiation.NR, NB = ambient.NB, NP = air.NP, G = report.G;
     const int64_t NL = blinds.NL, NF = comfort.NF, NU = handlers.NU, NBR = handlers.NBR, NSP = species.NSP, NV = species.NV;
-    const int64_t NO = openings.NO, NCT = controllers.NCT;
+    const int64_t NO = openings.NO, NCT = controllers.NCT, NNW = networks.NW;
     SeriesDrain drain{b};
     if ((rc = series_upload(d_w, h_w, "weather schedule"))) return rc;
     if ((rc = series_upload(d_zab, h_zab, "zone terms"))) return rc;
@@ -1222,6 +1299,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     if ((rc = species.upload(c.conc_rows, c.vent_v, c.vent_q, n_steps))) return rc;
     if ((rc = openings.upload(c.opening_v, n_steps))) return rc;
     if ((rc = controllers.upload(c.control_u, c.control_out, n_steps))) return rc;
+    if ((rc = networks.upload(c.link_q, c.node_p, c.net_iters, n_steps))) return rc;
     HIP_TRY(hipDeviceSynchronize());  // (the uploads went through the null stream; the batch's streams do not wait for it)
     HIP_TRY(report.start(b->stream));
     HIP_TRY(ideal.start(b->stream));
@@ -1229,6 +1307,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(species.start(b->stream));
     HIP_TRY(openings.start(b->stream));
     HIP_TRY(controllers.start(b->stream));
+    HIP_TRY(networks.start(b->stream));
     // what the thermostats, the air paths' e and the blinds sense: the zone temperatures, or with a control sensor the step's Tc
     const double *control_T = comfort.control_T.p ? comfort.control_T.p : b->d_zone_T.p;
     double *mirror = b->direct_runs.empty() ? nullptr : b->d_state.p;
@@ -1240,6 +1319,10 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
             launch_series_controllers(controllers.view, row(d_channel, k, NC), b->d_T.p, b->d_zone_T.p, row(controllers.u, k, NCT), row(controllers.out, k, NCT),
                                       b->stream);
         if (NO > 0) launch_series_openings(openings.view, row(d_channel, k, NC), b->d_zone_T.p, row(openings.v, k, NO), c.openings->step_base + k, b->stream);
+        // (the networks behind the openings: one launch per width class present, the third writer of the step's row)
+        if (NNW > 0)
+            launch_series_networks(networks.view, row(d_channel, k, NC), b->d_zone_T.p, row(networks.q, k, networks.NK), row(networks.p, k, networks.NN),
+                                   row(networks.iters, k, NNW), b->stream);
         const double *channel = row(d_channel, k, NC);
         const SkyRecord *record = row(sky.record, k, n_sites);
         const SkyCoef *coef = row(aniso.coef, k, n_sites);  // (nullptr without aniso: the isotropic kernels)
@@ -1326,6 +1409,7 @@ static int march_series_impl(heat_batch *b, const SeriesCall &c) {
     HIP_TRY(species.fetch(c.conc_rows, c.vent_v, c.vent_q, b->stream));
     HIP_TRY(openings.fetch(c.opening_v, b->stream));
     HIP_TRY(controllers.fetch(c.control_u, c.control_out, b->stream));
+    HIP_TRY(networks.fetch(c.link_q, c.node_p, c.net_iters, b->stream));
     HIP_TRY(hipMemcpyAsync(first_failed, probes.failed.p, sizeof first_failed, hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (first_failed[0] < 0) return HEAT_OK;  // (the flags were clear after the last step: nothing to report)
@@ -1482,6 +1566,18 @@ int heat_batch_march_series_controllers(heat_batch *b, const heat_series_call *c
     SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
     more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q, more.openings = op, more.opening_v = opening_v;
     more.controllers = ct, more.control_u = control_u, more.control_out = control_out;
+    return march_series_call(b, call, c, operative, mrt, &more);
+}
+
+int heat_batch_march_series_networks(heat_batch *b, const heat_series_call *call, heat_comfort *c, double *operative, double *mrt,
+                                     heat_air_handlers *h, double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                     heat_air_species *sp, double *conc_rows, double *vent_v, double *vent_q, heat_openings *op,
+                                     double *opening_v, heat_controllers *ct, double *control_u, double *control_out, heat_air_networks *nw,
+                                     double *link_q, double *node_p, int32_t *net_iters) {
+    SeriesCall more; more.handlers = h, more.supply_t = supply_t, more.recovered = recovered, more.coil_q = coil_q, more.branch_q = branch_q;
+    more.species = sp, more.conc_rows = conc_rows, more.vent_v = vent_v, more.vent_q = vent_q, more.openings = op, more.opening_v = opening_v;
+    more.controllers = ct, more.control_u = control_u, more.control_out = control_out;
+    more.networks = nw, more.link_q = link_q, more.node_p = node_p, more.net_iters = net_iters;
     return march_series_call(b, call, c, operative, mrt, &more);
 }
 

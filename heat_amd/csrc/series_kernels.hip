@@ -1269,6 +1269,220 @@ k_series_controllers(ControllersDev ct, double *row, const double *__restrict__ 
     if (ct.steps_sat != nullptr && u >= 1.0) ct.steps_sat[i] = ct.steps_sat[i] + 1;
 }
 
+// the density of dry air at t C: the expression and grouping of the air paths' rho
+__device__ __forceinline__ double network_rho(double t) {
+#pragma clang fp contract(off)
+    const double tk = t + 273.15;
+    return 101325. * 28.97 / (8314.46261815324 * tk);  // gas.rs:175-179
+}
+
+// One link of an air network by the header's rule, every line one rounded operation: q its volume flow, gm and ms what it adds
+// to the diagonal and to the balance of its nodes. P: the pressures of the link's network (LDS), indexed by local node number.
+struct NetworkLink {
+    double q, gm, ms;
+    bool fwd;
+};
+__device__ __forceinline__ NetworkLink network_link(const NetworksDev &nw, int l, const double *row, const double *__restrict__ zone_T,
+                                                    const double *P) {
+#pragma clang fp contract(off)
+    const int fc = nw.frac_chan[l];
+    double f = fc >= 0 ? row[fc] : 1.0;
+    if (f < 0.0) f = 0.0;
+    if (f > 1.0) f = 1.0;
+    const double C = nw.c[l] * f;
+    const int zb = nw.zone_b[l], lb = nw.lb[l];
+    const double ra = network_rho(zone_T[nw.zone_a[l]]);
+    const double rb = network_rho(zb >= 0 ? zone_T[zb] : row[nw.temp_chan[l]]);
+    double pb = 0.0;
+    if (lb >= 0) {
+        pb = P[lb];
+    } else {
+        const int wc = nw.wp_chan[l];
+        if (wc >= 0) pb = nw.wp_gain[l] * row[wc];
+    }
+    const double dr = ra - rb;
+    const double sh = nw.gh[l] * dr;
+    const double d0 = P[nw.la[l]] - pb;
+    const double dp = d0 - sh;
+    const double ad = fabs(dp);
+    double q, gq;
+    if (ad >= nw.p_lin[l]) {
+        const double s = sqrt_rn(ad);
+        q = C * s;
+        const double hq = 0.5 * q;
+        gq = hq / ad;
+    } else {
+        const double s_lin = nw.s_lin[l];
+        const double ca = C * ad;
+        q = ca / s_lin;
+        gq = C / s_lin;
+    }
+    NetworkLink k;
+    k.fwd = dp >= 0.0;
+    const double ru = k.fwd ? ra : rb;
+    const double m = ru * q;
+    k.q = q;
+    k.gm = ru * gq;
+    k.ms = k.fwd ? m : -m;
+    return k;
+}
+
+// k_series_networks<W> — the air networks of one width class for one step (heat_air_networks, include/heat_amd.h), launched
+// behind the openings: a small nonlinear solve per network, not one lane per item. W lanes per network (its node count is at
+// most W), a workgroup of ONE wavefront holding 64 / W networks (the last workgroup of a class is ragged), lane = node = row
+// of A. The sorted tables are plan.hpp's NetworkTables; the outputs and the state go through net_id / node_id to the
+// caller's order.
+//   assemble: a lane walks its node's incident links in ascending link number and evaluates each itself — a zone-to-zone
+//     link is evaluated by both of its lanes, with the same bits — adding into its own F and into its own row of A in LDS (a
+//     runtime column index into a register array would go to scratch). Rows have the odd stride W + 1 doubles: the lanes of
+//     a half-wave hit distinct banks on a column read, and the pivot row is a broadcast.
+//   res: a cross-lane maximum over the network's W lanes, of |F| where that is > 0 and of 0 elsewhere: order-independent,
+//     and a NaN never raises it, as in the rule.
+//   eliminate: lane r updates row r against row kk; back-substitute by columns: each lane subtracts as d[j] appears.
+// Every loop that encloses a barrier or a cross-lane operation has a wave-uniform bound: the largest n of the wavefront's
+// networks, and "until every network of the wavefront has stopped" by __all, at most 65 assemblies since max_iter <= 64. A
+// network that has stopped keeps walking with its writes masked. A lane of column i >= n of its network, or of a network past
+// the class's end, walks too and touches nothing. The step's row is written at the links' derived columns only, by the lane
+// of the link's first node: the check has made sure that they have one writer each and that no network reads them. No
+// spin-wait, no atomics, no traffic between workgroups, no scratch.
+template <int W>
+__global__ void __launch_bounds__(64)
+k_series_networks(NetworksDev nw, int first, int count, double *row, const double *__restrict__ zone_T, double *q_row, double *p_row,
+                  int32_t *it_row) {
+#pragma clang fp contract(off)
+    constexpr int G = 64 / W, S = W + 1;
+    __shared__ double A[64 * S];
+    __shared__ double Fs[64], Ps[64], Ds[64];
+    const int lane = threadIdx.x, g = lane / W, i = lane % W;
+    const int in_class = blockIdx.x * G + g;
+    const bool net_ok = in_class < count;
+    const int s = first + (net_ok ? in_class : 0);
+    const int n = net_ok ? nw.net_n[s] : 0;
+    const bool mine = i < n;
+    double *const An = A + g * W * S, *const Arow = An + i * S;
+    double *const Fn = Fs + g * W, *const Pn = Ps + g * W, *const Dn = Ds + g * W;
+    int nmax = n;
+    for (int m = 32; m >= 1; m >>= 1) nmax = max(nmax, __shfl_xor(nmax, m));
+    const double tol = net_ok ? nw.net_tol[s] : 0.0, g_min = net_ok ? nw.net_g_min[s] : 0.0;
+    const int max_iter = net_ok ? nw.net_max_iter[s] : 0;
+    int id = 0, inc0 = 0, inc_n = 0;
+    double src = 0.0;
+    Pn[i] = 0.0;
+    if (mine) {
+        const int p = nw.net_node0[s] + i;
+        id = nw.node_id[p], inc0 = nw.node_inc0[p], inc_n = nw.node_inc_n[p];
+        const int sc = nw.node_src_chan[p];
+        if (sc >= 0) src = nw.node_src_gain[p] * row[sc];
+        Pn[i] = nw.pressure[id];
+    }
+    double dold = 0.0, res = 0.0;
+    bool done = !net_ok, conv = false;
+    int iters = 0;
+    __syncthreads();
+    for (int it = 0; it <= 64; it++) {
+        // ---- assemble ----
+        double v = 0.0;
+        if (mine && !done) {
+            for (int j = 0; j < n; j++) Arow[j] = 0.0;
+            double F = src, diag = g_min;
+            for (int e = 0; e < inc_n; e++) {
+                const int l = nw.inc[inc0 + e];
+                const NetworkLink k = network_link(nw, l, row, zone_T, Pn);
+                const int la = nw.la[l];
+                if (la == i) {
+                    F = F - k.ms;
+                    const int lb = nw.lb[l];
+                    if (lb >= 0) Arow[lb] = Arow[lb] - k.gm;
+                } else {
+                    F = F + k.ms;
+                    Arow[la] = Arow[la] - k.gm;
+                }
+                diag = diag + k.gm;
+            }
+            Arow[i] = diag;
+            Fn[i] = F;
+            const double af = fabs(F);
+            if (af > 0.0) v = af;
+        }
+        for (int m = W / 2; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, W));
+        if (!done) {
+            res = v;
+            if (it >= max_iter) {
+                done = true, iters = it;
+            } else if (res <= tol) {
+                done = true, conv = true, iters = it;
+            }
+        }
+        if (__all(done)) break;
+        // ---- eliminate, no pivoting: lane r against row kk ----
+        for (int kk = 0; kk < nmax - 1; kk++) {
+            __syncthreads();
+            if (mine && !done && i > kk) {
+                const double *const Ak = An + kk * S;
+                const double fac = Arow[kk] / Ak[kk];
+                for (int j = kk + 1; j < n; j++) {
+                    const double t = fac * Ak[j];
+                    Arow[j] = Arow[j] - t;
+                }
+                const double t = fac * Fn[kk];
+                Fn[i] = Fn[i] - t;
+            }
+        }
+        // ---- back-substitute by columns ----
+        double d = 0.0;
+        for (int j = nmax - 1; j >= 0; j--) {
+            if (mine && !done && i == j) {
+                d = Fn[j] / Arow[j];
+                Dn[j] = d;
+            }
+            __syncthreads();
+            if (mine && !done && i < j && j < n) {
+                const double t = Arow[j] * Dn[j];
+                Fn[i] = Fn[i] - t;
+            }
+        }
+        // ---- Walton's acceleration, per node ----
+        if (mine && !done) {
+            double w = 1.0;
+            if (dold != 0.0) {
+                const double r = d / dold;
+                if (r < -0.5) {
+                    const double o = 1.0 - r;
+                    w = 1.0 / o;
+                }
+            }
+            const double dn = w * d;
+            Pn[i] = Pn[i] + dn;
+            dold = dn;
+        }
+        __syncthreads();
+    }
+    // ---- write: the links by the lane of their first node, from the final pressures (those of the last assembly) ----
+    if (!mine) return;
+    const double Pi = Pn[i];
+    nw.pressure[id] = Pi;
+    if (p_row != nullptr) p_row[id] = Pi;
+    for (int e = 0; e < inc_n; e++) {
+        const int l = nw.inc[inc0 + e];
+        if (nw.la[l] != i) continue;
+        const NetworkLink k = network_link(nw, l, row, zone_T, Pn);
+        const double ab = k.fwd ? k.q : 0.0, ba = k.fwd ? 0.0 : k.q;
+        const int oab = nw.out_ab[l], oba = nw.out_ba[l];
+        if (oab >= 0) row[oab] = ab;
+        if (oba >= 0) row[oba] = ba;
+        if (q_row != nullptr) q_row[l] = k.fwd ? k.q : -k.q;
+        if (nw.sum_ab != nullptr) nw.sum_ab[l] = nw.sum_ab[l] + ab;
+        if (nw.sum_ba != nullptr) nw.sum_ba[l] = nw.sum_ba[l] + ba;
+    }
+    if (i == 0) {
+        const int w = nw.net_id[s];
+        if (it_row != nullptr) it_row[w] = iters;
+        if (nw.iters_sum != nullptr) nw.iters_sum[w] = nw.iters_sum[w] + iters;
+        if (nw.unconverged != nullptr && !conv) nw.unconverged[w] = nw.unconverged[w] + 1;
+        if (nw.max_res != nullptr && res > nw.max_res[w]) nw.max_res[w] = res;
+    }
+}
+
 __global__ void __launch_bounds__(256) k_fill_f64(double *__restrict__ dst, int64_t n, double value) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = value;
@@ -1469,6 +1683,23 @@ void launch_series_controllers(const ControllersDev &ct, double *row, const doub
                                hipStream_t st) {
     if (ct.n_controllers <= 0) return;
     hipLaunchKernelGGL(k_series_controllers, dim3((ct.n_controllers + 255) / 256), dim3(256), 0, st, ct, row, T, zone_T, u_row, out_row);
+}
+
+template <int W>
+static void launch_networks_class(const NetworksDev &nw, int c, double *row, const double *zone_T, double *q_row, double *p_row, int32_t *it_row,
+                                  hipStream_t st) {
+    constexpr int G = 64 / W;
+    const int first = nw.class_start[c], count = nw.class_start[c + 1] - first;
+    if (count <= 0) return;
+    hipLaunchKernelGGL(k_series_networks<W>, dim3((count + G - 1) / G), dim3(64), 0, st, nw, first, count, row, zone_T, q_row, p_row, it_row);
+}
+
+void launch_series_networks(const NetworksDev &nw, double *row, const double *zone_T, double *q_row, double *p_row, int32_t *it_row,
+                            hipStream_t st) {
+    launch_networks_class<8>(nw, 0, row, zone_T, q_row, p_row, it_row, st);
+    launch_networks_class<16>(nw, 1, row, zone_T, q_row, p_row, it_row, st);
+    launch_networks_class<32>(nw, 2, row, zone_T, q_row, p_row, it_row, st);
+    launch_networks_class<64>(nw, 3, row, zone_T, q_row, p_row, it_row, st);
 }
 
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st) {

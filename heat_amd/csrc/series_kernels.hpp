@@ -336,6 +336,29 @@ struct ControllersDev {
 // control_u and control_out, or nullptr
 void launch_series_controllers(const ControllersDev &ct, double *row, const double *T, const double *zone_T, double *u_row, double *out_row,
                                hipStream_t st);
+// Air networks of a series step (heat_air_networks, include/heat_amd.h; tables: plan.hpp, NetworkTables): launched behind the
+// openings, ahead of launch_series_comfort, only when there are networks: one launch of k_series_networks<W> per width class
+// present, a workgroup of ONE wavefront holding 64 / W networks, lane = node. With the controllers and the openings it is one
+// of the three launches that WRITE the step's row of the device's channel table, at the links' derived columns.
+struct NetworksDev {
+    int class_start[5];                    // the sorted networks of class c (W = 8 << c): [class_start[c], class_start[c + 1])
+    int n_nodes, n_links;
+    const int32_t *net_id, *net_n, *net_node0, *net_max_iter;                       // [n_networks], sorted
+    const double *net_tol, *net_g_min;
+    const int32_t *node_id, *node_zone, *node_src_chan, *node_inc0, *node_inc_n;    // [n_nodes], sorted
+    const double *node_src_gain;
+    const int32_t *inc;                    // the incident links of every sorted node, ascending
+    const int32_t *zone_a, *zone_b, *la, *lb, *temp_chan, *wp_chan, *frac_chan, *out_ab, *out_ba;   // [n_links], the caller's order
+    const double *c, *gh, *p_lin, *s_lin, *wp_gain;
+    double *pressure;                      // [n_nodes], the caller's order: the state, always present
+    double *sum_ab, *sum_ba;               // [n_links], nullptr: not maintained
+    int64_t *iters_sum, *unconverged;      // [n_networks], the caller's order
+    double *max_res;
+};
+// row: the step's row of the channel table, written at out_ab and out_ba; q_row, p_row, it_row: the step's rows of link_q,
+// node_p and net_iters (the caller's order), or nullptr
+void launch_series_networks(const NetworksDev &nw, double *row, const double *zone_T, double *q_row, double *p_row, int32_t *it_row,
+                            hipStream_t st);
 void launch_fill_f64(double *dst, int64_t n, double value, hipStream_t st);
 // Ideal loads of a series: the step's begin and end (the sequence and the view: kernels.hpp, IdealLoadsDev)
 void launch_series_ideal_begin(const IdealLoadsDev &il, const double *row, hipStream_t st);

@@ -1429,6 +1429,7 @@ int heat_batch_march_series_species(heat_batch *b, const heat_series_call *call,
  * Out of scope: a pressure network or mass balance across several openings, two-way flow with a neutral plane resolved over
  * the opening height, wind pressure coefficients from direction, density of moist air, and the opening's own effect on
  * convection coefficients.
+ * (The flows of several openings that balance one another are a term of their own: heat_air_networks, below.)
  */
 typedef struct heat_openings {
     int64_t n_openings;
@@ -1555,6 +1556,128 @@ int heat_batch_march_series_controllers(heat_batch *b, const heat_series_call *c
                                         heat_controllers *ct /* nullable */,
                                         double *control_u   /* [n_steps][n_controllers], nullable */,
                                         double *control_out /* [n_steps][n_controllers], nullable */);
+
+/*
+ * Air networks of a series: pressure-balanced flows as DERIVED CHANNELS. An opening (heat_openings) is an explicit formula of
+ * its own two temperatures, so nothing makes the flows of a building add up: cross ventilation, a stairwell's stack effect
+ * over several storeys and the infiltration an extract fan pulls in cannot be expressed, and the species ride on flows that
+ * do not conserve mass. A network is a building's zones joined by links. Per step and per network the device solves the zone
+ * reference pressures that balance the mass flows through all links — the pressures depend on the zone temperatures of the
+ * moment, which only the device holds — and WRITES each link's volume flow into derived channels of the step's row. The air
+ * paths read those as any channel, and the loads' flows, the handlers' branches and the species read them through the air
+ * paths: a zone-to-zone link feeds two paths, a -> b with volume out_ab and b -> a with volume out_ba; an outside link feeds
+ * one supply path (source -1, the same temp_chan) with volume out_ba; what leaves a zone enters no balance, so out_ab of an
+ * outside link is normally -1. The air path's m = rho(Ts) V is the network's ru q: heat and species ride on flows that
+ * conserve mass. A tall doorway is two links at 1/4 and 3/4 of its height: two-way flow falls out of the balance. No existing
+ * struct, kernel or check changes. The reference has no counterpart; the rule below is this library's own contract, defined
+ * against the per-call loop with the same rule written on the host (heat_amd/air_networks.py, apply()). It is what
+ * EnergyPlus' AirflowNetwork, CONTAM and COMIS solve per time step, with Walton's AIRNET acceleration.
+ * Structure. Network w owns the nodes net_offset[w] ... net_offset[w + 1] - 1 of node_zone: zones, in the caller's order; a
+ * zone is in at most one network; 1 <= n_w <= 64. Link l joins zone_a[l] to zone_b[l], a zone of the same network or -1:
+ * outside. c: the flow coefficient, m3/s per sqrt(Pa), discharge coefficient and area folded in; gh: 9.81 times the link's
+ * height above the network's datum; p_lin > 0: below it the law is linear. frac_chan (optional) scales c, clamped to [0, 1];
+ * it may be a controller's output. Outside links: temp_chan, the outside temperature, and optionally wp_chan with wp_gain,
+ * the wind pressure at the link in Pa (the caller forms 1/2 rho Cp(theta) u2 per facade as a schedule). Per node an optional
+ * src_chan with src_gain: a net mechanical mass inflow in kg/s (an extract fan is negative). Per network tol (kg/s),
+ * max_iter and g_min, a conductance to the datum that keeps the matrix definite.
+ * The rule of step k. Order in the step: controllers -> openings -> networks -> everything else, unchanged. T = the zone AIR
+ * temperatures the device holds when the step starts, row = the device's channel[k], P = the node pressures the step before
+ * left (state). Every line is ONE rounded f64 operation in the order written, no fused multiply-add; sqrt is correctly
+ * rounded; no pow, no transcendental function; a NaN makes every comparison false:
+ *   rho(t):  tk = t + 273.15;  rho = 101325 * 28.97 / (8314.46261815324 * tk)     (expression and grouping of heat_air_paths' rho)
+ *   link l, a = its first node, b = its second node or outside:
+ *     f = frac_chan >= 0 ? row[frac_chan] : 1.0;  if f < 0.0: f = 0.0;  if f > 1.0: f = 1.0;  C = c * f
+ *     ra = rho(T[zone_a]);  rb = b is a zone ? rho(T[zone_b]) : rho(row[temp_chan])
+ *     pb = b is a zone ? P[b] : (wp_chan >= 0 ? wp_gain * row[wp_chan] : 0.0)
+ *     dr = ra - rb;  sh = gh * dr;  d0 = P[a] - pb;  dp = d0 - sh;  ad = |dp|
+ *     if ad >= p_lin:  s = sqrt(ad);  q = C * s;  hq = 0.5 * q;  gq = hq / ad
+ *     else:            ca = C * ad;  q = ca / s_lin;  gq = C / s_lin          (s_lin = sqrt(p_lin), formed once on the host)
+ *     fwd = dp >= 0.0;  ru = fwd ? ra : rb;  m = ru * q;  gm = ru * gq;  ms = fwd ? m : -m
+ *   assemble:  F[i] = src_chan >= 0 ? src_gain * row[src_chan] : 0.0;  A[i][i] = g_min;  A[i][j] = 0.0
+ *     links of the network in ascending l:  F[a] = F[a] - ms;  A[a][a] = A[a][a] + gm
+ *         b a zone:  F[b] = F[b] + ms;  A[b][b] = A[b][b] + gm;  A[a][b] = A[a][b] - gm;  A[b][a] = A[b][a] - gm
+ *     res = 0.0;  for i ascending:  af = |F[i]|;  if af > res: res = af
+ *   iterate:  dold[i] = 0.0;  conv = 0
+ *     for it = 0 ... max_iter - 1:  assemble;  if res <= tol: conv = 1, stop
+ *         eliminate, no pivoting (A is symmetric positive definite):  for kk ascending, r > kk:  fac = A[r][kk] / A[kk][kk]
+ *             for j > kk ascending:  t = fac * A[kk][j];  A[r][j] = A[r][j] - t
+ *             t = fac * F[kk];  F[r] = F[r] - t
+ *         back-substitute by columns:  for j = n - 1 ... 0:  d[j] = F[j] / A[j][j];  for r < j:  t = A[r][j] * d[j];  F[r] = F[r] - t
+ *         per node (Walton's AIRNET acceleration):  w = 1.0;  if dold[i] != 0.0: { r = d[i] / dold[i];  if r < -0.5: { o = 1.0 - r;  w = 1.0 / o } }
+ *             dn = w * d[i];  P[i] = P[i] + dn;  dold[i] = dn
+ *     if conv == 0:  assemble once more (the flows written belong to the final P);  unconverged += 1
+ *   write, per link from the last assembly:  link_q[k][l] = fwd ? q : -q;  row[out_ab] = fwd ? q : 0.0;  row[out_ba] = fwd ? 0.0 : q   (where not -1)
+ *              sum_ab += (fwd ? q : 0.0);  sum_ba += (fwd ? 0.0 : q)
+ *   per network:  net_iters[k][w] = it, the iterations that solved;  iters_sum += it;  if res > max_res: max_res = res
+ *   per node:  node_p[k][i] = P[i]
+ * Plain Newton on a square-root law maps x to -x and cycles; the acceleration halves such a step. The flows hold for all
+ * sub-timesteps of the step, as every a0 / b0 term does. A NaN temperature makes the flows it reaches NaN; |NaN| never raises
+ * res, so a network whose every residual is NaN stops at once. NaN flows are data until a consumer adds them to a zone
+ * (HEAT_N_NAN_ZONE, as today). The caller's host channel array is never written; a derived column's host values are ignored.
+ * State and accumulators are in/out and nullable: pressure [n_nodes] is state, carried over a cut; sum_ab, sum_ba per link;
+ * iters_sum, unconverged, max_res per network. resume == 0 starts them on the device at zero; resume != 0 takes them from the
+ * arrays (a NULL one starts at zero). A series of k steps followed by one of n - k with the returned arrays gives the bits of
+ * the series of n. The pressures are kept on the device whether or not the caller takes them. n_sub == 0 still evaluates
+ * every step. An array that is not asked for costs no traffic and changes no bit of the others. With nw == NULL or
+ * n_networks == 0 heat_batch_march_series_networks is heat_batch_march_series_controllers exactly: same launches, same bits.
+ * A network reads no opening's out_chan and no network's; no opening or controller reads a network's; every derived column
+ * has one writer. A network may read a controller's output channel.
+ * A refused call leaves the device state untouched. Sharded batches are refused as by the series. heat_air_networks_check
+ * (host-only; it also builds and verifies the tables the march uploads) and heat_batch_march_series_networks run the same
+ * checks before any device work; every message names "network w", "node i" or "link l". HEAT_E_INVALID_ARG: a negative
+ * count; a NULL array that a positive count needs (net_offset, node_zone, tol, max_iter, g_min; zone_a, zone_b, temp_chan, c,
+ * p_lin); a c, gh or tol that is not finite or is negative; a p_lin or g_min that is not positive and finite; a src_gain or
+ * wp_gain that is not finite; max_iter outside [1, 64]; zone_a == zone_b; on resume a pressure that is not finite.
+ * HEAT_E_SIZE: a zone or channel out of range; net_offset not starting at 0, not ending at n_nodes or with a network of 0 or
+ * of more than 64 nodes; a zone in two networks; a link whose zones are in different networks or in none; an outside link
+ * without temp_chan, or a zone-to-zone link with a temp_chan or wp_chan; a network with no outside link; two writers of one
+ * channel (out_ab, out_ba, an opening's or a controller's out_chan); a network that reads an opening's or a network's derived
+ * channel; an opening or a controller that reads a network's.
+ * Out of scope: power-law exponents other than 1/2; ducts and fan curves; wind pressure coefficients from direction (the
+ * caller's wp_chan carries them); moist-air density; networks of more than 64 zones; more than one datum per network; any
+ * change to the march kernels or to a consumer.
+ */
+typedef struct heat_air_networks {
+    int64_t n_networks, n_nodes, n_links;
+    const int32_t *net_offset;          /* [n_networks + 1] into node_zone, ascending from 0 to n_nodes */
+    const double  *tol;                 /* [n_networks] kg/s, finite, >= 0 */
+    const int32_t *max_iter;            /* [n_networks] in [1, 64] */
+    const double  *g_min;               /* [n_networks] kg/s per Pa, finite, > 0 */
+    const int32_t *node_zone;           /* [n_nodes] the zone of every node */
+    const int32_t *src_chan;            /* [n_nodes] nullable / -1: no source */
+    const double  *src_gain;            /* [n_nodes] nullable = 1; finite */
+    const int32_t *zone_a;              /* [n_links] a zone of a network */
+    const int32_t *zone_b;              /* [n_links] a zone of the same network, or -1: outside */
+    const int32_t *temp_chan;           /* [n_links] the outside temperature where zone_b == -1, else -1 */
+    const int32_t *wp_chan;             /* [n_links] nullable / -1: no wind pressure; only where zone_b == -1 */
+    const int32_t *frac_chan;           /* [n_links] nullable / -1: fully open */
+    const int32_t *out_ab;              /* [n_links] nullable / -1: the DERIVED channel of the flow a -> b, m3/s */
+    const int32_t *out_ba;              /* [n_links] nullable / -1: the DERIVED channel of the flow b -> a, m3/s */
+    const double  *c;                   /* [n_links] m3/s per sqrt(Pa), finite, >= 0 */
+    const double  *gh;                  /* [n_links] nullable = 0; m2/s2, finite, >= 0 */
+    const double  *p_lin;               /* [n_links] Pa, finite, > 0 */
+    const double  *wp_gain;             /* [n_links] nullable = 1; finite */
+    int64_t resume;                     /* as heat_openings::resume, for the state and the accumulators below */
+    double  *pressure;                  /* [n_nodes] state, in/out, nullable: Pa, finite */
+    double  *sum_ab;                    /* [n_links] accumulators, in/out, nullable */
+    double  *sum_ba;
+    int64_t *iters_sum;                 /* [n_networks] */
+    int64_t *unconverged;
+    double  *max_res;
+} heat_air_networks;
+
+int heat_air_networks_check(const heat_batch_desc *desc, const heat_series *s, const heat_openings *op /* nullable */,
+                            const heat_controllers *ct /* nullable */, const heat_air_networks *nw /* nullable */); /* host-only */
+int heat_batch_march_series_networks(heat_batch *b, const heat_series_call *call, heat_comfort *c /* nullable */,
+                                     double *operative, double *mrt, heat_air_handlers *h /* nullable */,
+                                     double *supply_t, double *recovered, double *coil_q, double *branch_q,
+                                     heat_air_species *sp /* nullable */, double *conc_rows, double *vent_v, double *vent_q,
+                                     heat_openings *op /* nullable */, double *opening_v,
+                                     heat_controllers *ct /* nullable */, double *control_u, double *control_out,
+                                     heat_air_networks *nw /* nullable */,
+                                     double  *link_q    /* [n_steps][n_links], nullable */,
+                                     double  *node_p    /* [n_steps][n_nodes], nullable */,
+                                     int32_t *net_iters /* [n_steps][n_networks], nullable */);
 
 /* Where the numerical failure heat_batch_synchronize / heat_batch_march last reported was seen FIRST (the reference's
  * panics name the offending values, surface.rs:704-707; model.rs:417-420): *index = the surface's number in the

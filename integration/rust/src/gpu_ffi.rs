@@ -150,6 +150,15 @@ pub struct HeatSkyCoef { pub circ: f64, pub horiz: f64 }
     pub lim_hi: *const f64, pub lim_lo: *const f64, pub resume: i64, pub integral: *mut f64, pub tripped: *mut u8,
     pub sum_u: *mut f64, pub sum_out: *mut f64, pub steps_on: *mut i64, pub steps_sat: *mut i64, pub trips: *mut i64,
 }
+// heat_air_networks: pressure-balanced flows through the links of zone networks, written into derived channels
+#[repr(C)] pub struct HeatAirNetworks {
+    pub n_networks: i64, pub n_nodes: i64, pub n_links: i64, pub net_offset: *const i32, pub tol: *const f64, pub max_iter: *const i32,
+    pub g_min: *const f64, pub node_zone: *const i32, pub src_chan: *const i32, pub src_gain: *const f64, pub zone_a: *const i32,
+    pub zone_b: *const i32, pub temp_chan: *const i32, pub wp_chan: *const i32, pub frac_chan: *const i32, pub out_ab: *const i32,
+    pub out_ba: *const i32, pub c: *const f64, pub gh: *const f64, pub p_lin: *const f64, pub wp_gain: *const f64, pub resume: i64,
+    pub pressure: *mut f64, pub sum_ab: *mut f64, pub sum_ba: *mut f64, pub iters_sum: *mut i64, pub unconverged: *mut i64,
+    pub max_res: *mut f64,
+}
 
 pub const HEAT_COMM_ID_BYTES: usize = 128;
 
@@ -272,6 +281,16 @@ extern "C" {
                                                conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64, op: *mut HeatOpenings,
                                                opening_v: *mut f64, ct: *mut HeatControllers, control_u: *mut f64,
                                                control_out: *mut f64) -> c_int;
+    // air networks of a series: node pressures that balance the links' mass flows, the flows read by the air paths as channels
+    pub fn heat_air_networks_check(desc: *const HeatBatchDesc, s: *const HeatSeries, op: *const HeatOpenings,
+                                   ct: *const HeatControllers, nw: *const HeatAirNetworks) -> c_int;
+    pub fn heat_batch_march_series_networks(b: *mut HeatBatch, call: *const HeatSeriesCall, c: *mut HeatComfort,
+                                            operative: *mut f64, mrt: *mut f64, h: *mut HeatAirHandlers, supply_t: *mut f64,
+                                            recovered: *mut f64, coil_q: *mut f64, branch_q: *mut f64, sp: *mut HeatAirSpecies,
+                                            conc_rows: *mut f64, vent_v: *mut f64, vent_q: *mut f64, op: *mut HeatOpenings,
+                                            opening_v: *mut f64, ct: *mut HeatControllers, control_u: *mut f64,
+                                            control_out: *mut f64, nw: *mut HeatAirNetworks, link_q: *mut f64, node_p: *mut f64,
+                                            net_iters: *mut i32) -> c_int;
     pub fn heat_last_error() -> *const c_char;
 }
 

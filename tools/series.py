@@ -140,8 +140,18 @@ and writes profiles/series_controllers.json: ms per step of each, K - P, a serie
 per-step times once the set-up is taken off — and, where a kernel trace of one K series has been taken (--one-series
 --controllers under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_controllers_kernel_stats.csv),
 k_series_controllers per step. No time is a pass criterion.
-  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species | --openings | --controllers]
-  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species | --openings | --controllers]
+With --networks (heat_batch_march_series_networks, heat_air_networks; the --controllers workload, plus one air network per
+building of ten zones: nine doorways, every other one a tall opening of two links, and one link to outside per zone at its
+storey's height behind the wind pressure of one of two facades, every derived column read by an air path) it alternates
+  F  the series with networks = NULL and the SAME flows fed back as ordinary channels: the link_q rows of one W series
+     (equal traces asserted)
+  W  the same call with the networks, the derived columns of the host table NaN
+and writes profiles/series_networks.json: ms per step of each with their spreads, W - F, a series of ONE step of each (the
+call's set-up), how many networks, nodes and links that is and, where a kernel trace of one W series has been taken
+(--one-series --networks under rocprofv3 --kernel-trace --stats, a run of its own; profiles/series_networks_kernel_stats.csv),
+k_series_networks per step and per width class. No time is a pass criterion.
+  python tools/series.py [S] [steps] [rounds] [--out=FILE] [--loads | --report | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --aniso | --comfort | --handlers | --species | --openings | --controllers | --networks]
+  python tools/series.py --one-series [S] [steps] [--loads | --report | --report=one-group | --report=nodes | --ideal | --sky | --gains | --air | --shades | --radiation | --ambient | --blinds | --comfort | --handlers | --species | --openings | --controllers | --networks]
                                                      one warm-up series and one more of n_sub = 2, nothing else (to run under
                                                      rocprofv3 --kernel-trace --stats): leg F; with one-group a single group
                                                      over the flows of all sides instead of one per zone; with nodes leg G;
@@ -152,7 +162,7 @@ k_series_controllers per step. No time is a pass criterion.
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-from heat_amd import HeatBatch, controllers as ctm, openings as opm, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
+from heat_amd import HeatBatch, air_networks as anm, controllers as ctm, openings as opm, air_handlers as ahm, air_species as aspm, ambient as ambm, air_paths as apm, comfort as cfm, modeldict as mdl, room_radiation as rrm, shading as shm, sky as skym, solar_gains as sgm
 ONE = "--one-series" in sys.argv
 REPORT = next((a[9:] or "zones" for a in sys.argv[1:] if a == "--report" or a.startswith("--report=")), None)
 IDEAL = "--ideal" in sys.argv
@@ -165,7 +175,8 @@ SHADES = "--shades" in sys.argv or BLINDS
 RADIATION = "--radiation" in sys.argv
 AMBIENT = "--ambient" in sys.argv
 COMFORT = "--comfort" in sys.argv
-CONTROLLERS = "--controllers" in sys.argv
+NETWORKS = "--networks" in sys.argv
+CONTROLLERS = "--controllers" in sys.argv or NETWORKS
 OPENINGS = "--openings" in sys.argv or CONTROLLERS
 SPECIES = "--species" in sys.argv or OPENINGS
 HANDLERS = "--handlers" in sys.argv or SPECIES
@@ -440,6 +451,50 @@ if CONTROLLERS:
         dt = time.perf_counter() - t0
         assert out[1] == -1 and np.all(np.isfinite(out[0])) and np.all(np.isfinite(out[6]["conc"])) and np.all(np.isfinite(out[7]["sum_v"]))
         assert controllers is None or (np.all(np.isfinite(out[8]["sum_u"])) and out[8]["sum_u"].any())
+        return (dt * 1e3 / steps, out) if rows else dt * 1e3 / steps
+if NETWORKS:
+    # two more channels (the wind pressures of two facades) and the derived columns: per building of ten zones one network — a chain of
+    # doorways, every other one a tall opening of two links, one link to outside per zone at its storey's height; the first of a
+    # building never closes, the others follow the openings' open-fraction schedule — and the air paths that read every column
+    c_nw = channel.shape[1]
+    PER = 10
+    NB = Z // PER
+    zi = np.arange(NB * PER)
+    local = zi % PER
+    door = zi[local > 0]
+    tall = (local[local > 0] % 2 == 1)
+    t = anm.tall_opening(rng.uniform(0.7, 1.0, len(door)), rng.uniform(1.9, 2.2, len(door)), 0.6, sill=3.0 * (local[local > 0] // 5))
+    d_a = np.concatenate([door, door[tall]])
+    d_b = np.concatenate([door - 1, door[tall] - 1])
+    d_c = np.concatenate([np.where(tall, t["c"][0], anm.orifice(rng.uniform(0.005, 0.03, len(door)), 0.6)), t["c"][1][tall]])
+    d_gh = np.concatenate([t["gh"][0], t["gh"][1][tall]])
+    n_in, n_out = len(d_a), len(zi)
+    network_args = dict(net_offset=(PER * np.arange(NB + 1)).astype(np.int32), tol=np.full(NB, 1e-7), max_iter=np.full(NB, 24, np.int32),
+                        g_min=np.full(NB, 1e-9), node_zone=zi.astype(np.int32), zone_a=np.concatenate([d_a, zi]).astype(np.int32),
+                        zone_b=np.concatenate([d_b, np.full(n_out, -1)]).astype(np.int32),
+                        temp_chan=np.concatenate([np.full(n_in, -1), np.full(n_out, c_ah)]).astype(np.int32),
+                        wp_chan=np.concatenate([np.full(n_in, -1), c_nw + zi % 2]).astype(np.int32),
+                        frac_chan=np.concatenate([np.full(n_in, -1), np.where(local == 0, -1, c_op + 1)]).astype(np.int32),
+                        c=np.concatenate([d_c, anm.orifice(rng.uniform(0.004, 0.04, n_out), 0.6)]),
+                        gh=np.concatenate([d_gh, anm.G * (3.0 * (local // 5) + rng.uniform(0.3, 2.6, n_out))]), p_lin=np.full(n_in + n_out, 0.05))
+    NL = n_in + n_out
+    network_args["out_ab"] = np.concatenate([c_nw + 2 + np.arange(n_in), np.full(n_out, -1)]).astype(np.int32)
+    network_args["out_ba"] = (c_nw + 2 + n_in + np.arange(NL)).astype(np.int32)
+    channel = np.concatenate([channel, rng.uniform(-6.0, 6.0, (STEPS, 2)), np.full((STEPS, n_in + NL), np.nan)], axis=1)
+    network_paths = anm.paths(network_args)
+    air_nw = apm.concat(air_args, {k: v for k, v in network_paths.items() if k != "link"})
+
+    def leg_nw(b, w, n_sub, steps, networks="given", table=None, rows=False):
+        table = channel if table is None else table
+        b.synchronize()
+        t0 = time.perf_counter()
+        out = b.march_series(w[:steps], n_sub, channel=table[:steps], probes=probes, loads=loads_ct, air=air_nw, path_q=False, handlers=handler_args,
+                             supply_t=False, recovered=False, coil_q=False, branch_q=False, species=species_args, conc_rows=False, vent_v=False,
+                             vent_q=False, openings=opening_ct, opening_v=False, controllers=controller_args, control_u=False, control_out=False,
+                             networks=network_args if networks == "given" else networks, link_q=rows, node_p=False, net_iters=rows, **drives)
+        dt = time.perf_counter() - t0
+        assert out[1] == -1 and np.all(np.isfinite(out[0])) and np.all(np.isfinite(out[6]["conc"])) and np.all(np.isfinite(out[7]["sum_v"]))
+        assert networks is None or (np.all(np.isfinite(out[9]["sum_ba"])) and out[9]["sum_ba"].any() and not out[9]["unconverged"].any())
         return (dt * 1e3 / steps, out) if rows else dt * 1e3 / steps
 if RADIATION:
     # every back a receiver of the backs of its room, area-weighted; its long-wave channel goes (an input has one source)
@@ -719,6 +774,44 @@ with HeatBatch(md) as b:
             print("n_sub %2d: N comfort NULL %.3f ms/step, C comfort %.3f -> C - N = %+.3f ms, C / N = %.4f; a series of one step: "
                   "N %.2f ms, C %.2f ms -> per step without the set-up N %.3f, C %.3f, C - N = %+.3f (%d sensors, %d entries, %d steps, "
                   "median of %d rounds)" % (n_sub, N_, C_, C_ - N_, C_ / N_, N1, C1, Ns, Cs, Cs - Ns, Z, NE, STEPS, ROUNDS), flush=True)
+            continue
+        if NETWORKS:
+            # the flows of one W series into ordinary channels: leg F's table (the state is uploaded anew before every series of this
+            # mode, so that F and W march the same steps from the same start)
+            def fresh(leg, *a, **kw):
+                b.upload_state(state)
+                return leg(b, w, n_sub, *a, **kw)
+            _, first = fresh(leg_nw, STEPS, rows=True)  # (warm-up as well)
+            q = first[9]["link_q"]
+            fed = channel.copy()
+            ab, ba = network_args["out_ab"], network_args["out_ba"]
+            fed[:, ab[ab >= 0]] = np.where(q > 0, q, 0.0)[:, ab >= 0]
+            fed[:, ba[ba >= 0]] = np.where(q < 0, -q, 0.0)[:, ba >= 0]
+            _, same = fresh(leg_nw, STEPS, None, fed, rows=True)
+            assert np.array_equal(first[0], same[0]), "the series with the flows fed back marches other bits"
+            if ONE:
+                print("one series with networks: W %.3f ms per step" % fresh(leg_nw, STEPS))
+                continue
+            ff, ww, ff1, ww1 = [], [], [], []
+            for r in range(ROUNDS):
+                ff.append(fresh(leg_nw, STEPS, None, fed))
+                ww.append(fresh(leg_nw, STEPS))
+                ff1.append(fresh(leg_nw, 1, None, fed))  # a series of ONE step: the set-up of a call (checks, tables, uploads) + a step
+                ww1.append(fresh(leg_nw, 1))
+            F_, W_, F1, W1 = (float(np.mean(v)) for v in (ff, ww, ff1, ww1))
+            Fs, Ws = (F_ * STEPS - F1) / (STEPS - 1), (W_ * STEPS - W1) / (STEPS - 1)  # per step once the call is set up
+            its = first[9]["net_iters"]
+            result["legs"]["n_sub=%d" % n_sub] = dict(
+                F_flows_fed_back_ms=F_, W_networks_ms=W_, W_minus_F_ms=W_ - F_, W_over_F=W_ / F_, F_spread_ms=[min(ff), max(ff)],
+                W_spread_ms=[min(ww), max(ww)], F_series_of_one_step_ms=F1, W_series_of_one_step_ms=W1, W_minus_F_series_of_one_step_ms=W1 - F1,
+                F_without_setup_ms=Fs, W_without_setup_ms=Ws, W_minus_F_without_setup_ms=Ws - Fs, networks=int(NB), nodes=int(NB * PER),
+                links=int(NL), nodes_per_network=PER, lanes_per_network=next(w for w in (8, 16, 32, 64) if PER <= w), channels=int(channel.shape[1]), iterations_mean=float(its.mean()),
+                iterations_max=int(its.max()), traces_equal=True, all_rounds=dict(F=ff, W=ww, F_one_step=ff1, W_one_step=ww1))
+            print("n_sub %2d: F flows fed back %.3f ms/step (%.3f-%.3f), W networks %.3f (%.3f-%.3f) -> W - F = %+.3f ms, W / F = %.4f; a series of "
+                  "one step: F %.2f ms, W %.2f ms -> per step without the set-up F %.3f, W %.3f, W - F = %+.3f (%d networks, %d nodes, %d links, "
+                  "%.1f iterations a solve, at most %d; %d steps, mean of %d rounds)" % (
+                      n_sub, F_, min(ff), max(ff), W_, min(ww), max(ww), W_ - F_, W_ / F_, F1, W1, Fs, Ws, Ws - Fs, NB, NB * PER, NL, its.mean(),
+                      its.max(), STEPS, ROUNDS), flush=True)
             continue
         if CONTROLLERS:
             # the outputs of one K series into ordinary channels: leg P's table (the state is uploaded anew before every series of
@@ -1289,7 +1382,23 @@ if AMBIENT and not ONE:
         print("kernel trace: k_series_ambient %.2f us per step" % us)
     else:
         print("no kernel trace at %s" % stats)
-if CONTROLLERS and not ONE:
+if NETWORKS and not ONE:
+    # the kernel trace of one W series (--one-series --networks under rocprofv3 --kernel-trace --stats, a run of its own), where it
+    # has been taken: k_series_networks per step and per width class, beside the step's other series kernels together
+    stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
+                 os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "series_networks_kernel_stats.csv"))
+    if os.path.exists(stats):
+        import csv
+        with open(stats) as f:
+            rows = [r for r in csv.DictReader(f)]
+        mine = {r["Name"].split("(")[0].split("::")[-1]: float(r["AverageNs"]) / 1e3 for r in rows if "k_series_networks" in r["Name"]}
+        other = sum(float(r["AverageNs"]) / 1e3 for r in rows if "k_series_" in r["Name"] and "k_series_networks" not in r["Name"])
+        result["kernel_trace_of_one_W_series"] = dict(k_series_networks_us_per_step=mine, other_series_kernels_us_per_step=other)
+        print("kernel trace: k_series_networks %s us per step, the step's other series kernels together %.2f" % (mine, other))
+    else:
+        result["kernel_trace_of_one_W_series"] = "not taken yet"
+        print("no kernel trace at %s" % stats)
+if CONTROLLERS and not NETWORKS and not ONE:
     # the kernel trace of one K series (--one-series --controllers under rocprofv3 --kernel-trace --stats, a run of its own), where
     # it has been taken: k_series_controllers per step, beside the same trace's k_series_openings
     stats = next((a[15:] for a in sys.argv[1:] if a.startswith("--kernel-stats=")),
@@ -1353,7 +1462,7 @@ if HANDLERS and not SPECIES and not ONE:
         print("no kernel trace at %s" % stats)
 if not ONE:
     out = OUT or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "series_controllers.json" if CONTROLLERS else "series_openings.json" if OPENINGS else "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
+                              "series_networks.json" if NETWORKS else "series_controllers.json" if CONTROLLERS else "series_openings.json" if OPENINGS else "series_species.json" if SPECIES else "series_handlers.json" if HANDLERS else "series_comfort.json" if COMFORT else "series_aniso.json" if ANISO else "series_blinds.json" if BLINDS else "series_ambient.json" if AMBIENT else "series_radiation.json" if RADIATION else "series_shades.json" if SHADES else "series_air.json" if AIR else "series_gains.json" if GAINS else "series_sky.json" if SKY else "series_ideal.json" if IDEAL else
                               ("series_report.json" if REPORT else ("series_loads.json" if LOADS else "series_march.json")))
     with open(out, "w") as f:
         json.dump(result, f, indent=1)
